@@ -8,11 +8,17 @@ N>1: one process per GPU (torch.distributed / RCCL), cubes sharded per rank (wea
 per-cube fused surface probabilities per step (north_star's exchange step).
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs bench_outputs
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (schema in the task contract) incl. `roofline` (dominant kernel, HIP-event timed in a second
-loop of the same K steps right after the timed region, which itself runs without per-kernel events) and `cpu_baseline` (oracle timed on the host cores, bounded sample, rank 0 at N=1 only).
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds of one timed step). A plain run
+sets up, warms up, times exactly K steps (no per-kernel events) and prints the line. --full adds everything else: `box` (sn_mfma_probe),
+`roofline` / `kernels_ms_per_step` (dominant kernel, HIP-event timed in a second loop of the same K steps right after the timed region), and
+at N=1 the extra legs (f16x3p / f16 modes, s=64, post pass, similarityNet, scene samples, `cpu_baseline`: oracle timed on the host cores,
+bounded sample); --no-* skips single legs of --full. --dump-outputs DIR writes what the last timed step computed (the fused surface
+probabilities, all ranks' cubes on rank 0) as DIR/fused.npy, float32; the inputs are seeded, so two builds compare output for output.
 """
 import argparse
 import json
@@ -36,6 +42,20 @@ DTYPE = {"f16m8": "f16 main term + 6-bit (fp6 e2m3, MX-scaled MFMA) correction t
          "f16": "f16 (MFMA, f32 accumulate); CVC warp f64"}
 MFMA_F16_DENSE_PEAK_TFLOPS = 2500.0      # /opt/skills/guides/MI355X_MICROARCH.md: BF16/FP16 MFMA dense peak
 CNN_FLOPS_PER_SAMPLE_S32 = 44511690752   # learned-conv FLOPs per cube-view-pair at s=32
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6        # --dump-outputs: a larger output (many ranks) is written as a seeded sample of its cubes
+
+
+def dump_outputs(dirname, fused):
+    """--dump-outputs: the fused surface probabilities (cubes, 1, s, s, s) of the last timed step as DIR/fused.npy (float32); above
+    DUMP_MAX_BYTES a fixed, seeded sample of whole cubes in index order as DIR/fused_sample.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    name = "fused"
+    if fused.nbytes > DUMP_MAX_BYTES:
+        k = DUMP_MAX_BYTES // (fused.nbytes // fused.shape[0])
+        fused, name = fused[np.sort(np.random.RandomState(0).choice(fused.shape[0], k, replace=False))], "fused_sample"
+    np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(fused, dtype=np.float32))
 
 
 KERNEL_SOURCES = ["conv3d_mfma.h", "mx_format.h", "cvc_warp.h", "elementwise.h", "sn_internal.h", "sn_api.hip"]
@@ -273,6 +293,9 @@ def main():
                          "logic (any rank fails => all ranks fall back, MIN all-reduce, MAX-over-ranks timing, rank-seeded shards) runs with a real peer on a "
                          "one-GPU box (tests/test_gpu_bench.py); not a performance mode")
     ap.add_argument("--native-deadline", type=float, default=NATIVE_COMM_DEADLINE_S, help="seconds the library's own RCCL communicator has to come up (and its probe all-gather to verify) before torch.distributed carries the exchange")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the fused surface probabilities of the last timed step as DIR/fused.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="also the non-headline measurements: box probe, per-kernel / roofline loop and, at N=1, the extra "
+                    "legs below (other precisions, s=64, post pass, similarityNet, scenes, CPU baseline); the --no-* options skip single legs")
     ap.add_argument("--no-fast-mode", action="store_true", help="skip the extra f16 fast-mode measurement")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-s64", action="store_true", help="skip the extra s=64 measurement")
@@ -281,6 +304,8 @@ def main():
     ap.add_argument("--no-scenes", action="store_true", help="skip the extra end-to-end scene samples (BASELINE configs[2] and [4] on their dataset calibration)")
     ap.add_argument("--scene-cubes", type=int, default=4000, help="cubes sampled evenly from each scene's grid for the scene samples (0 = the whole grid: 195,360 / 15,456)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -329,14 +354,15 @@ def main():
         return (c,) + tuple(c.upload(scene[k]) for k in ("pairs", "xyz", "resol", "w"))
     ctx, d_pairs, d_xyz, d_resol, d_w = make_ctx()
     # what THIS box sustains on a pure fp16 MFMA stream, measured right before the timed region (boxes of the pool fall into speed classes 5-8 % apart;
-    # every absolute number below moves with it). ~10 ms launches, outside the timed region.
+    # every absolute number below moves with it). ~10 ms launches, outside the timed region. --full only.
     box = None
-    try:
-        tf, ghz = ctx.mfma_probe(10.0)
-        box = {"sustained_f16_tflops": round(tf, 1), "effective_clock_ghz": round(ghz, 3), "frac_of_nominal_peak": round(tf / MFMA_F16_DENSE_PEAK_TFLOPS, 4),
-               "what": "pure v_mfma_f32_16x16x32_f16 stream, all CUs, one wave per SIMD, random operands, last of four ~10 ms launches (sn_mfma_probe)"}
-    except Exception as e:      # noqa: BLE001 - a measurement aid must not cost the bench line
-        box = {"error": "%s: %s" % (type(e).__name__, e)}
+    if args.full:
+        try:
+            tf, ghz = ctx.mfma_probe(10.0)
+            box = {"sustained_f16_tflops": round(tf, 1), "effective_clock_ghz": round(ghz, 3), "frac_of_nominal_peak": round(tf / MFMA_F16_DENSE_PEAK_TFLOPS, 4),
+                   "what": "pure v_mfma_f32_16x16x32_f16 stream, all CUs, one wave per SIMD, random operands, last of four ~10 ms launches (sn_mfma_probe)"}
+        except Exception as e:      # noqa: BLE001 - a measurement aid must not cost the bench line
+            box = {"error": "%s: %s" % (type(e).__name__, e)}
     native = use_dist and not (args.torch_comm or bool(os.environ.get("BENCH_TORCH_COMM")))
     comm_note, native_hung, rccl_info = None, False, None
     if native:
@@ -459,17 +485,31 @@ def main():
         step()
     barrier_sync()
     elapsed = time.perf_counter() - t0
-    # ---- a second loop of the same K steps with HIP events around every kernel launch (on the stream they are launched on):
-    # the roofline / per-kernel numbers come from here, the headline from the loop above
-    ctx.profile_reset()
-    ctx.profile_enable(True)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    barrier_sync()
-    elapsed_prof = time.perf_counter() - t0
-    prof = ctx.profile()
-    ctx.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: the fused probabilities of the last step (N>1: the all-gathered ones of every rank)
+        b = (step_no[0] - 1) & 1
+        fused = np.empty((world * n if use_dist else n, 1, s, s, s), np.float32)
+        if native:
+            ctx.d2h(fused, d_all[b])
+        elif use_dist and args.dist_backend == "gloo":
+            fused[:] = t_all_host.numpy().reshape(fused.shape)
+        elif use_dist:
+            fused[:] = t_all[b].cpu().numpy().reshape(fused.shape)
+        else:
+            ctx.d2h(fused, d_fused[b])
+        dump_outputs(args.dump_outputs, fused)
+    if args.full:
+        # ---- a second loop of the same K steps with HIP events around every kernel launch (on the stream they are launched on):
+        # the roofline / per-kernel numbers come from here, the headline from the loop above
+        ctx.profile_reset()
+        ctx.profile_enable(True)
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        barrier_sync()
+        elapsed_prof = time.perf_counter() - t0
+        prof = ctx.profile()
+        ctx.profile_enable(False)
 
     if use_dist:
         own_elapsed = elapsed
@@ -482,12 +522,6 @@ def main():
 
     if rank == 0:
         cubes_per_s = world * n * args.steps / elapsed
-        dom = max((k for k in prof if prof[k]["flops"] > 0), key=lambda k: prof[k]["ms"])
-        d = prof[dom]
-        ach = d["flops"] / (d["ms"] * 1e-3) / 1e12
-        conv_ms = sum(v["ms"] for v in prof.values() if v["flops"] > 0)
-        conv_fl = sum(v["flops"] for v in prof.values())
-        cvc = prof.get("cvc_warp")
         out = {
             "metric": "voxel-cubes/sec (CVC warp + 3D CNN fwd) at s=%d, N_viewpair=%d" % (s, n_vp),
             "value": round(cubes_per_s, 2), "unit": "cubes/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -499,14 +533,21 @@ def main():
                        **({"comm_note": comm_note} if comm_note else {}),
                        **({"dist_backend": args.dist_backend, "elapsed_s_per_rank": per_rank_s} if use_dist else {}),
                        **({"rccl": {"file": rccl_info[0], "version_code": rccl_info[1]}} if rccl_info else {})},
-            "roofline": {"bound": "mfma", "kernel": "conv3d_f16_mfma<%s>" % dom, "achieved": round(ach, 2), "peak": MFMA_F16_DENSE_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": round(ach / MFMA_F16_DENSE_PEAK_TFLOPS, 4), "traffic": None,
-                         "avg_launch_ms": round(d["ms"] / d["launches"], 4), "launches": d["launches"],
-                         "algorithmic_flops_per_launch": d["flops"] / d["launches"]},
-            "cnn_all_convs": {"achieved_tflops": round(conv_fl / (conv_ms * 1e-3) / 1e12, 2), "ms_per_step": round(conv_ms / args.steps, 3)},
             "end_to_end_tflops": round(cubes_per_s / world * n_vp * CNN_FLOPS_PER_SAMPLE_S32 * (s / 32.0) ** 3 / 1e12, 2),
-            "box": box,
         }
+    if rank == 0 and args.full:
+        dom = max((k for k in prof if prof[k]["flops"] > 0), key=lambda k: prof[k]["ms"])
+        d = prof[dom]
+        ach = d["flops"] / (d["ms"] * 1e-3) / 1e12
+        conv_ms = sum(v["ms"] for v in prof.values() if v["flops"] > 0)
+        conv_fl = sum(v["flops"] for v in prof.values())
+        cvc = prof.get("cvc_warp")
+        out["roofline"] = {"bound": "mfma", "kernel": "conv3d_f16_mfma<%s>" % dom, "achieved": round(ach, 2), "peak": MFMA_F16_DENSE_PEAK_TFLOPS,
+                           "unit": "TFLOP/s", "frac": round(ach / MFMA_F16_DENSE_PEAK_TFLOPS, 4), "traffic": None,
+                           "avg_launch_ms": round(d["ms"] / d["launches"], 4), "launches": d["launches"],
+                           "algorithmic_flops_per_launch": d["flops"] / d["launches"]}
+        out["cnn_all_convs"] = {"achieved_tflops": round(conv_fl / (conv_ms * 1e-3) / 1e12, 2), "ms_per_step": round(conv_ms / args.steps, 3)}
+        out["box"] = box
         if box and "sustained_f16_tflops" in box:
             out["roofline"]["frac_of_box_sustained"] = round(ach / box["sustained_f16_tflops"], 4)
         if cvc:
@@ -561,6 +602,7 @@ def main():
             out["scene_dino"] = bench_scene.run(["--config", "dino"] + lim)
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(scene, values, s, n_vp)
+    if rank == 0:
         try:   # RCCL's banner sits in the C stdio buffer: push it out first so that the JSON line is the last line of stdout
             import ctypes
             ctypes.CDLL(None).fflush(None)

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _run_bench(extra, port):
     env = dict(os.environ, BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--cubes", "8", "--no-fast-mode", "--no-cpu-baseline", "--no-s64",
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--cubes", "8", "--full", "--no-fast-mode", "--no-cpu-baseline", "--no-s64",
            "--no-simil", "--no-post-pass", "--no-scenes"] + extra
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, "bench.py under torch.distributed.run failed:\n%s\n%s" % (p.stdout[-2000:], p.stderr[-3000:])
@@ -25,10 +25,25 @@ def _run_bench(extra, port):
     return json.loads(lines[-1])
 
 
-def test_bench_dist_branch_native_collective(gpu_required):
+def _bench_fused_of_seed0(n):
+    """What the bench's timed path computes for its rank-0 inputs (synthetic scene seed 0, weights seed 0), through the host-array entry point."""
+    import surfacenet_amd
+    from surfacenet_amd import synthetic, weights
+    sc = synthetic.synthetic_scene(n, 2, s=32, seed=0)
+    with surfacenet_amd.Context(cube_D=32, max_samples=2 * n) as ctx:
+        ctx.load_param_values(weights.synthetic_param_values(0))
+        ctx.set_cameras(sc["cams"])
+        ctx.set_images(sc["imgs"])
+        fused, _, _ = ctx.cvc_forward(sc["pairs"], sc["xyz"], sc["resol"], sc["w"], return_unfused=False)
+    return fused
+
+
+def test_bench_dist_branch_native_collective(gpu_required, tmp_path):
     """Default N>1 path: the library's own collective. rc 0, the parallelism string names it, no fall-back note, and the line says which RCCL file
-    the entry points were bound to (a process with two RCCL copies must be visible in SCALE_r*.json, not a hang)."""
-    j = _run_bench([], 29871)
+    the entry points were bound to (a process with two RCCL copies must be visible in SCALE_r*.json, not a hang). --dump-outputs writes the
+    all-gathered fused probabilities of the last step: with one rank, the rank's own cubes."""
+    import numpy as np
+    j = _run_bench(["--dump-outputs", str(tmp_path)], 29871)
     cfg = j["config"]
     assert j["n_gpus"] == 1 and j["steps"] == 2 and j["value"] > 0 and j["scaling"] == "weak"
     assert "comm_note" not in cfg, cfg
@@ -36,6 +51,24 @@ def test_bench_dist_branch_native_collective(gpu_required):
     # torch.distributed's nccl backend loaded RCCL first: the library must have bound THAT copy, not a second one
     assert "already mapped" in cfg["rccl"]["file"], cfg["rccl"]
     assert j["roofline"]["frac"] > 0 and "kernels_ms_per_step" in j
+    np.testing.assert_array_equal(np.load(str(tmp_path / "fused.npy")), _bench_fused_of_seed0(8))
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(gpu_required, tmp_path):
+    """A plain run (no --full) times exactly --steps steps and its line holds the headline only: no probe, no profiled loop, no extra legs.
+    --dump-outputs writes the fused probabilities of the last timed step, bit-identical to Context.cvc_forward on the same seeded inputs."""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--cubes", "8", "--dump-outputs", str(tmp_path)]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, "bench.py failed:\n%s\n%s" % (p.stdout[-2000:], p.stderr[-3000:])
+    j = json.loads(p.stdout.strip().splitlines()[-1])
+    assert j["n_gpus"] == 1 and j["steps"] == 3 and j["warmup"] == 1 and j["unit"] == "cubes/s" and j["higher_is_better"] is True, j
+    assert j["ms_per_step"] > 0 and abs(j["value"] - 8 * 1e3 / j["ms_per_step"]) <= 0.01 * j["value"], j
+    for k in ("roofline", "box", "kernels_ms_per_step", "f16x3p", "s64", "loop_body_with_post_pass", "similarity_net", "scene_dino", "cpu_baseline"):
+        assert k not in j, k
+    got = np.load(str(tmp_path / "fused.npy"))
+    assert got.dtype == np.float32 and got.shape == (8, 1, 32, 32, 32)
+    np.testing.assert_array_equal(got, _bench_fused_of_seed0(8))
 
 
 def test_bench_dist_branch_torch_collective(gpu_required):

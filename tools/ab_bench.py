@@ -53,7 +53,7 @@ def main():
     res = {name: [] for name, _ in variants}
     for r in range(args.rounds):
         for name, lib in variants:
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.steps), "--warmup", "3", "--no-fast-mode", "--no-cpu-baseline", "--no-s64",
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.steps), "--warmup", "3", "--full", "--no-fast-mode", "--no-cpu-baseline", "--no-s64",
                    "--no-post-pass", "--no-scenes"] + ([] if args.with_simil else ["--no-simil"]) + args.extra.split()
             p = subprocess.run(cmd, env=dict(os.environ, SURFACENET_HIP_LIB=lib), capture_output=True, text=True)
             if p.returncode != 0:

@@ -4,7 +4,7 @@
     python tools/pmc_traffic.py --summary profiles/r2/summary_r2x.json --cube-d 32 --samples 128 --precision f16x3
 
 The counters behind the summary must come from rocprofv3 --pmc passes of the HEADLINE workload only
-(`bench.py --no-fast-mode --no-cpu-baseline --no-s64 --no-simil --no-post-pass`): the other legs launch the same kernels with other
+(`bench.py --full --no-fast-mode --no-cpu-baseline --no-s64 --no-simil --no-post-pass`): the other legs launch the same kernels with other
 arguments (e.g. the post-pass leg makes cvc_warp_kernel write the planar fp32 tensor as well, 56 instead of 32 bytes per voxel) and
 would be averaged in. The file is stamped with the hash of the kernel sources it was measured on (bench.kernel_src_sha16); bench.py
 drops the traffic figure when the sources have changed since."""

@@ -8,7 +8,7 @@ TAG="${1:-prof}"
 R="${GRAFT_REPO_ROOT:-$PWD}"
 cd /tmp && export TMPDIR=/tmp
 O="$R/gpurun_out"
-B="python $R/bench.py --steps 10 --warmup 3 --no-fast-mode --no-cpu-baseline --no-s64 --no-simil --no-post-pass --no-scenes"
+B="python $R/bench.py --steps 10 --warmup 3 --full --no-fast-mode --no-cpu-baseline --no-s64 --no-simil --no-post-pass --no-scenes"
 rocprofv3 --kernel-trace --stats -d $O/${TAG}_stats -o s --output-format csv -- $B > $O/${TAG}_bench_under_rocprofv3.json 2>/dev/null
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/${TAG}_pmc_f -o p --output-format csv -- $B > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum -d $O/${TAG}_pmc_w -o p --output-format csv -- $B > /dev/null 2>&1
