@@ -195,6 +195,44 @@ SN_API int sn_dense2sparse_dev(sn_ctx *ctx, int n, int n_vp, const int64_t *view
                         unsigned char *ijk_dev, uint16_t *pred16_dev, unsigned char *rgb_out_dev,
                         unsigned char *votes_out_dev);
 
+/* ---- cross-cube post-pass (main_reconstruct.py:172-176, main.py:37-43) ---------------------------------------------------------------------
+ * Both work on the packed voxel lists sn_dense2sparse produces: offsets (n+1) int64 (cube i owns voxels [offsets[i], offsets[i+1]); offsets[0] = 0,
+ * non-decreasing), ijk (total,3) uint8 voxel indices inside the cube, each < Dc (the bit-row width, 1..64: cube_Dcenter for dense2sparse's lists),
+ * cube_ijk (n,3) uint32 cube indices. Host forms validate the table and the ijk; _dev forms take total = offsets[n] and report a bad table or ijk
+ * through the next sn_synchronize (the cubes concerned are skipped). Both forms return when the work is done.
+ *
+ * denoising.denoise_crossCubes (utils/denoising.py:150-184): mask (total) uint8 0/1 -> out (total) uint8 0/1. A voxel is kept iff it is masked and
+ * its 26-connected component inside its cube holds a voxel v that coincides with a masked voxel u of a neighbouring cube, v == u + (D_cube/2)*shift.
+ * Only cubes with a masked voxel enter the ijk -> cube map; for a repeated ijk the last such cube wins; every other cube keeps nothing.
+ * D_cube (>= 2) is taken as given: main_reconstruct.py:175 passes cube_D, adapthresh cube_Dcenter. */
+SN_API int sn_denoise(sn_ctx *ctx, int n, int Dc, int D_cube, const int64_t *offsets, const unsigned char *ijk, const uint32_t *cube_ijk,
+                      const unsigned char *mask, unsigned char *out);
+SN_API int sn_denoise_dev(sn_ctx *ctx, int n, int Dc, int D_cube, long long total, const int64_t *offsets_dev, const unsigned char *ijk_dev,
+                          const uint32_t *cube_ijk_dev, const unsigned char *mask_dev, unsigned char *out_dev);
+
+/* adapthresh.adapthresh's numeric arguments (utils/adapthresh.py:91-94; min_probThresh is accepted and ignored there, so it is absent here). */
+typedef struct sn_adapthresh_cfg {
+    int N_refine_iter;
+    int D_cube;                /* cube_Dcenter at main.py:39: the half-cube selections are [D_cube/2, D_cube) and [0, D_cube/2) */
+    double init_probThresh;    /* initial mask: float16(pred) >= float16(init_probThresh) AND votes >= rayPool_thresh */
+    double max_probThresh;
+    double rayPool_thresh;
+    double beta;
+} sn_adapthresh_cfg;
+/* The whole refinement device-resident: initial mask, its denoised form, then N_refine_iter Jacobi iterations (every cube reads the thresholds and
+ * masks of the previous one; float16 cost accumulated in the reference's order as numpy 2 rounds it). pred16 (total) float16
+ * bits; votes (total) uint8 or NULL (no vote filter). Outputs, each optional (NULL): init_denoised (total), thresh (N_refine_iter, n) float64 -
+ * every cube's threshold after each iteration, masks (N_refine_iter, total) - the cumulative masks, denoised (N_refine_iter, total) - their
+ * denoised form (the iter{k}.ply content), choice (N_refine_iter, n) int8 - the argmin of each active cube's cost (0: +0.1, 1: 0, 2: -0.1), -1 for
+ * the cubes outside the active set (empty initial mask, or not their ijk's map entry). */
+SN_API int sn_adapthresh(sn_ctx *ctx, int n, int Dc, const sn_adapthresh_cfg *cfg, const int64_t *offsets, const unsigned char *ijk,
+                         const uint16_t *pred16, const unsigned char *votes, const uint32_t *cube_ijk, unsigned char *init_denoised,
+                         double *thresh, unsigned char *masks, unsigned char *denoised, signed char *choice);
+SN_API int sn_adapthresh_dev(sn_ctx *ctx, int n, int Dc, const sn_adapthresh_cfg *cfg, long long total, const int64_t *offsets_dev,
+                             const unsigned char *ijk_dev, const uint16_t *pred16_dev, const unsigned char *votes_dev,
+                             const uint32_t *cube_ijk_dev, unsigned char *init_denoised_dev, double *thresh_dev, unsigned char *masks_dev,
+                             unsigned char *denoised_dev, signed char *choice_dev);
+
 /* ---- similarityNet / early rejection (main_reconstruct.py:76-97) ---------------- */
 /* pickle.load + set_all_param_values([embedding layer, similarity layer]) of similarityNet_inference
  * (nets/similarityNet.py:229-244): 30 arrays in order — 13 x (conv W (Cout,Cin,3,3), b (Cout,)) for conv1_1 .. conv5_3

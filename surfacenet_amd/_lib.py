@@ -19,6 +19,7 @@ ABI_SYMBOLS = [
     "sn_dev_alloc", "sn_dev_free", "sn_memcpy_h2d", "sn_memcpy_d2h", "sn_mark", "sn_memcpy_d2h_after",
     "sn_cvc_forward_dev", "sn_cvc_dev", "sn_forward_dev",
     "sn_ray_pool", "sn_ray_pool_dev", "sn_dense2sparse", "sn_dense2sparse_dev",
+    "sn_denoise", "sn_denoise_dev", "sn_adapthresh", "sn_adapthresh_dev",
     "sn_simil_load_weights", "sn_crop_patches", "sn_patch2embedding", "sn_crop_embed", "sn_embeddingpair2simil", "sn_embeddings2simil",
     "sn_project_points",
     "sn_comm_unique_id", "sn_comm_init", "sn_comm_init_deadline", "sn_comm_info", "sn_allgather_f32_dev", "sn_allgather_f32_dev_overlap", "sn_comm_wait", "sn_allgatherv_counts", "sn_allgatherv_bytes_dev",
@@ -34,6 +35,11 @@ class SurfaceNetHipError(RuntimeError):
 class SparseCfg(ctypes.Structure):
     _fields_ = [("min_prob", ctypes.c_float), ("rayPool_thresh", ctypes.c_int), ("enable_centerCrop", ctypes.c_int),
                 ("cube_Dcenter", ctypes.c_int), ("enable_rayPooling", ctypes.c_int)]
+
+
+class AdapthreshCfg(ctypes.Structure):
+    _fields_ = [("N_refine_iter", ctypes.c_int), ("D_cube", ctypes.c_int), ("init_probThresh", ctypes.c_double), ("max_probThresh", ctypes.c_double),
+                ("rayPool_thresh", ctypes.c_double), ("beta", ctypes.c_double)]
 
 
 class Calibration(ctypes.Structure):
@@ -97,6 +103,10 @@ def load():
         "sn_ray_pool_dev": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 4 + [c_int, ctypes.c_float, c_void_p]),
         "sn_dense2sparse": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 5 + [P(SparseCfg)] + [c_void_p] * 5),
         "sn_dense2sparse_dev": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 5 + [P(SparseCfg)] + [c_void_p] * 6),
+        "sn_denoise": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 5),
+        "sn_denoise_dev": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_longlong] + [c_void_p] * 5),
+        "sn_adapthresh": (c_int, [c_void_p, c_int, c_int, P(AdapthreshCfg)] + [c_void_p] * 10),
+        "sn_adapthresh_dev": (c_int, [c_void_p, c_int, c_int, P(AdapthreshCfg), ctypes.c_longlong] + [c_void_p] * 10),
         "sn_simil_load_weights": (c_int, [c_void_p, c_void_p, c_size_t, P(ParamDesc), c_int]),
         "sn_crop_patches": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
         "sn_patch2embedding": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),

@@ -396,6 +396,47 @@ class Context(object):
         T = int(offsets[-1])
         return offsets, ijk[:T], p16[:T], (None if rgb_out is None else rgb_out[:T]), (None if votes is None else votes[:T])
 
+    @staticmethod
+    def _packed(offsets, ijk, cube_ijk):
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        n = offsets.size - 1
+        ijk = np.ascontiguousarray(ijk, dtype=np.uint8).reshape(-1, 3)
+        cube = np.asarray(cube_ijk).reshape(n, 3)
+        if cube.size and (cube.min() < 0 or cube.max() > 0xFFFFFFFF):
+            raise ValueError("cube ijk must lie in [0, 2^32)")
+        return offsets, n, ijk, np.ascontiguousarray(cube, dtype=np.uint32)
+
+    def denoise(self, offsets, ijk, cube_ijk, mask, D_cube, Dc):
+        """denoising.denoise_crossCubes (utils/denoising.py:150-184) on packed voxel lists: offsets (n+1,) int64, ijk (T,3) uint8 (each < Dc),
+        cube_ijk (n,3), mask (T,) bool -> (T,) bool."""
+        offsets, n, ijk, cube = self._packed(offsets, ijk, cube_ijk)
+        m = np.ascontiguousarray(mask, dtype=bool).reshape(-1).view(np.uint8)
+        out = np.zeros((m.size,), dtype=np.uint8)
+        _lib.check(self._lib.sn_denoise(self._h, n, int(Dc), int(D_cube), _lib.ptr(offsets), _lib.ptr(ijk), _lib.ptr(cube), _lib.ptr(m), _lib.ptr(out)))
+        return out.view(bool)
+
+    def adapthresh(self, offsets, ijk, pred16, votes, cube_ijk, D_cube, N_refine_iter, init_probThresh, max_probThresh, rayPool_thresh, beta, Dc,
+                   keep=("thresh", "masks", "denoised", "choice")):
+        """adapthresh.adapthresh's computation (utils/adapthresh.py:91-178) on packed voxel lists, every iteration on the GPU. pred16 (T,) float16,
+        votes (T,) uint8 or None. Returns a dict: init_denoised (T,) bool and, as listed in `keep`, thresh (N_iter, n) float64, masks /
+        denoised (N_iter, T) bool, choice (N_iter, n) int8 (argmin of each active cube's cost, -1 outside the active set)."""
+        offsets, n, ijk, cube = self._packed(offsets, ijk, cube_ijk)
+        T, it = int(offsets[-1]), int(N_refine_iter)
+        p16 = np.ascontiguousarray(pred16, dtype=np.float16).reshape(-1).view(np.uint16)
+        v = None if votes is None else np.ascontiguousarray(votes, dtype=np.uint8).reshape(-1)
+        cfg = _lib.AdapthreshCfg(it, int(D_cube), float(init_probThresh), float(max_probThresh), float(rayPool_thresh), float(beta))
+        out = dict(init_denoised=np.zeros((T,), np.uint8))
+        shapes = dict(thresh=((it, n), np.float64), masks=((it, T), np.uint8), denoised=((it, T), np.uint8), choice=((it, n), np.int8))
+        for k in keep:
+            out[k] = np.zeros(*shapes[k])
+        _lib.check(self._lib.sn_adapthresh(self._h, n, int(Dc), ctypes.byref(cfg), _lib.ptr(offsets), _lib.ptr(ijk), _lib.ptr(p16), _lib.ptr(v),
+                                           _lib.ptr(cube), _lib.ptr(out["init_denoised"]), _lib.ptr(out.get("thresh")), _lib.ptr(out.get("masks")),
+                                           _lib.ptr(out.get("denoised")), _lib.ptr(out.get("choice"))))
+        for k in ("init_denoised", "masks", "denoised"):
+            if k in out:
+                out[k] = out[k].view(bool)
+        return out
+
     def dev_alloc(self, nbytes):
         p = self._lib.sn_dev_alloc(self._h, int(nbytes))
         if not p:

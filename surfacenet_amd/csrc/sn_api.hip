@@ -673,6 +673,8 @@ static int sync_check(sn_ctx *c)
         HIPCHK(hipMemcpy(&e, c->d_err, sizeof e, hipMemcpyDeviceToHost));
         if (e) {
             HIPCHK(hipMemset(c->d_err, 0, sizeof e));
+            if (e == CC_ERR_INPUT_FLAG)
+                return fail(SN_ERR_ARG, "cross-cube post-pass: offsets table or voxel ijk out of range (the cubes concerned were skipped)");
             return fail(SN_ERR_ARG, "ray pooling: a projected pixel or depth bin fell outside the int32 range (cube on a camera plane?)");
         }
     }

@@ -88,6 +88,8 @@ static inline const char *sn_ab_switch(const char *name)
 #endif
 }
 
+constexpr int CC_ERR_INPUT_FLAG = 2;      // sn_ctx::d_err value of the cross-cube post-pass (crosscube.h CC_ERR_INPUT): bad offsets table / voxel ijk
+
 struct sn_ctx {
     int device = 0, s = 32, max_samples = 0;
     hipStream_t stream = nullptr;
@@ -140,7 +142,7 @@ struct sn_ctx {
     // post-pass (ray pooling / dense2sparse) workspace
     unsigned *d_num = nullptr;    // numeric status word: bit i = conv layer i of the launch order stored a non-finite / fp16-overflowing value
     std::vector<std::string> num_names;   // layer name of each status bit
-    void *rp_ws = nullptr; size_t rp_ws_bytes = 0; int *d_err = nullptr; int *d_counts = nullptr; int d_counts_cap = 0;
+    void *rp_ws = nullptr; size_t rp_ws_bytes = 0; int *d_err = nullptr;   /* device error flag: 1 ray pooling range, CC_ERR_INPUT_FLAG post-pass input */ int *d_counts = nullptr; int d_counts_cap = 0;
     std::vector<void *> owned;
     // profiling
     bool prof_on = false;

@@ -9,6 +9,8 @@
                            sparse voxel lists come down
 * `reconstruct_scene`       main_reconstruct.reconstruction() from the early rejection to the sparse voxel lists
                            (main_reconstruct.py:67-173) for in-memory images / cameras / cubes: every stage on the GPU
+* `scene_postpass`          what follows the thinning masks in the reference (main_reconstruct.py:172-176, main.py:37-43): the
+                           fixed-threshold cross-cube denoising and the adaptive thresholding, in memory, on the GPU
 * `gather_sparse_sharded`   the multi-GPU exchange when the post-pass runs on the GPU: every rank holds only the packed
                            sparse voxel lists of its cube shard (9 B per kept voxel instead of 4 B x s^3 per cube); two
                            all-gathers (lengths, then one padded byte buffer) rebuild the global lists on every rank
@@ -438,7 +440,8 @@ def reconstruct_scene(images_list, cameraPOs_np, cubes_param_np, cube_D_mm, cube
     patch2embedding_fn, embeddingPair2simil_fn, viewPair_relativeImpt_fn: the callables of similarityNet.similarityNet_inference /
     SurfaceNet.SurfaceNet_inference (their weights are bound in `runtime`); `timings`: a dict that receives the wall seconds of every stage.
     A missing argument fails here, before any stage has run. Returns a dict with the reference's variable names. Not included (SURVEY §2.1,
-    out of scope): image / camera readers, cube tiling, cross-cube denoising, PLY / npz writers."""
+    out of scope): image / camera readers, cube tiling, PLY / npz writers; cross-cube denoising and adaptive thresholding follow in
+    `scene_postpass`."""
     sel_kw, loop_kw = _split_scene_kw(locals())
     out = scene_select(images_list, cameraPOs_np, cubes_param_np, cube_D_mm, cube_D, N_viewPairs4inference, **sel_kw)
     valid = out["validCubes"]
@@ -448,6 +451,49 @@ def reconstruct_scene(images_list, cameraPOs_np, cubes_param_np, cube_D_mm, cube
     out.update(scene_cube_loop(images_list, cameraPOs_np, cubes_param_np[valid], out["viewPairs4Reconstr"], out["w_viewPairs4Reconstr"], cube_D,
                                N_viewPairs4inference, **loop_kw))
     return out
+
+
+def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, gamma=0.8, beta=6, N_refine_iter=8, init_probThresh=0.5,
+                   max_probThresh=0.9, keep_iterations=False):
+    """The reconstruction's last two stages on `reconstruct_scene`'s dict, in memory and on the GPU, as the reference runs them on its files:
+      * main_reconstruct.py:172-175  thinning masks (prob >= tau, votes >= gamma * N_vp * 2), then denoise_crossCubes with D_cube = cube_D
+      * main.py:37-43 -> utils/adapthresh.py  adaptive thresholding with D_cube = cube_Dcenter, init / max threshold init_probThresh /
+        max_probThresh, rayPool_thresh = int(round(gamma * N_vp * 2)), beta, N_refine_iter iterations
+    (the npz round trip between the two stages changes nothing). Returns a dict of per-cube lists / arrays:
+      fixThresh_mask_list, fixThresh_denoised_list                 the fixThresh_tau*_gamma*.ply content is the denoised one
+      adapt_init_denoised_list                                     initialization.ply
+      adapt_thresh (n,) float64, adapt_mask_list, adapt_denoised_list   after the last iteration (iter{N-1}.ply = adapt_denoised_list)
+      adapt_iterations (keep_iterations): thresh (N,n), choice (N,n) int8, mask_lists, denoised_lists - every iteration."""
+    from . import adapthresh, denoising, sparseCubes
+    N_vp = int(N_viewPairs4inference)
+    pred_l, ijk_l, votes_l = out["prediction_list"], out["vxl_ijk_list"], out["rayPooling_votes_list"]
+    n = len(ijk_l)
+    res = dict(fixThresh_mask_list=[], fixThresh_denoised_list=[], adapt_init_denoised_list=[], adapt_thresh=np.full((n,), float(init_probThresh)),
+               adapt_mask_list=[], adapt_denoised_list=[])
+    if keep_iterations:
+        res["adapt_iterations"] = dict(thresh=np.zeros((int(N_refine_iter), n)), choice=np.zeros((int(N_refine_iter), n), np.int8),
+                                       mask_lists=[], denoised_lists=[])
+    if n == 0:
+        return res
+    cube_ijk = out["cube_ijk_np"]
+    res["fixThresh_mask_list"] = sparseCubes.filter_voxels(vxl_mask_list=[], prediction_list=pred_l, prob_thresh=tau, rayPooling_votes_list=votes_l,
+                                                           rayPool_thresh=gamma * N_vp * 2)
+    res["fixThresh_denoised_list"] = denoising.denoise_crossCubes(cube_ijk, ijk_l, res["fixThresh_mask_list"], cube_D)
+    a = adapthresh.adapthresh_lists(pred_l, ijk_l, votes_l, cube_ijk, N_refine_iter, cube_Dcenter, init_probThresh, max_probThresh,
+                                    int(round(gamma * N_vp * 2)), beta)
+    off = a["offsets"]
+    split = lambda flat: [x.copy() for x in denoising.split_lists(flat, off)]
+    res["adapt_init_denoised_list"] = split(a["init_denoised"])
+    if N_refine_iter > 0:
+        res.update(adapt_thresh=a["thresh"][-1].copy(), adapt_mask_list=split(a["masks"][-1]), adapt_denoised_list=split(a["denoised"][-1]))
+    else:
+        init_mask = sparseCubes.filter_voxels(vxl_mask_list=[], prediction_list=pred_l, prob_thresh=init_probThresh, rayPooling_votes_list=votes_l,
+                                              rayPool_thresh=int(round(gamma * N_vp * 2)))
+        res.update(adapt_mask_list=init_mask, adapt_denoised_list=res["adapt_init_denoised_list"])
+    if keep_iterations:
+        res["adapt_iterations"] = dict(thresh=a["thresh"], choice=a["choice"], mask_lists=[split(m) for m in a["masks"]],
+                                       denoised_lists=[split(m) for m in a["denoised"]])
+    return res
 
 
 def _allgather_bytes(blob, group=None, device=None, ctx=None):

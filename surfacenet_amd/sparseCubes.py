@@ -3,11 +3,15 @@
     dense2sparse              utils/sparseCubes.py:9-77
     append_dense_2sparseList  utils/sparseCubes.py:82-160   (call site main_reconstruct.py:153-160)
     filter_voxels             utils/sparseCubes.py:205-243  (host-side list thresholding, unchanged semantics)
+    save2ply, save_sparseCubes_2ply, save_sparseCubes, load_sparseCubes   utils/sparseCubes.py:246-410 (host file I/O:
+                              binary little-endian PLY with plyfile's header, npz with the reference's keys - files cross both ways)
 
 Same names, keyword arguments, output lists and dtypes. The ray pooling, thresholding, centre crop and compaction of a
 whole batch run in one GPU call (surfacenet_amd/csrc/postpass.h); only the packed voxel lists cross PCIe. `param` is
 the reference's structured array ('xyz' f32x3, 'ijk' u32x3, 'resol' f32; utils/scene.py:55).
 """
+import os
+
 import numpy as np
 
 from . import runtime
@@ -89,3 +93,85 @@ def filter_voxels(vxl_mask_list=[], prediction_list=None, prob_thresh=None, rayP
             raise Warning('rayPool_thresh should not be None.')
         merge([v >= rayPool_thresh for v in rayPooling_votes_list])
     return vxl_mask_list
+
+
+_PLY_TYPES = {"<f4": "float", "|u1": "uchar"}
+
+
+def save2ply(ply_filePath, xyz_np, rgb_np=None, normal_np=None):
+    """xyz (N,3) [+ normals (N,3)] [+ rgb (N,3)] -> binary little-endian PLY, the bytes plyfile's PlyData([vertex]).write produces for the
+    reference's dtypes (utils/sparseCubes.py:246-280): 'float' x y z [nx ny nz], 'uchar' red green blue."""
+    N_voxels = xyz_np.shape[0]
+    atributes = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')]
+    if normal_np is not None:
+        atributes += [('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4')]
+    if rgb_np is not None:
+        atributes += [('red', 'u1'), ('green', 'u1'), ('blue', 'u1')]
+    saved_pts = np.zeros(shape=(N_voxels,), dtype=np.dtype(atributes))
+    saved_pts['x'], saved_pts['y'], saved_pts['z'] = xyz_np[:, 0], xyz_np[:, 1], xyz_np[:, 2]
+    if rgb_np is not None:
+        saved_pts['red'], saved_pts['green'], saved_pts['blue'] = rgb_np[:, 0], rgb_np[:, 1], rgb_np[:, 2]
+    if normal_np is not None:
+        saved_pts['nx'], saved_pts['ny'], saved_pts['nz'] = normal_np[:, 0], normal_np[:, 1], normal_np[:, 2]
+    lines = ["ply", "format binary_little_endian 1.0", "element vertex %d" % N_voxels]
+    lines += ["property %s %s" % (_PLY_TYPES[saved_pts.dtype.fields[name][0].str], name) for name in saved_pts.dtype.names]
+    lines.append("end_header")
+    outputFolder = os.path.dirname(ply_filePath)
+    if outputFolder and not os.path.exists(outputFolder):
+        os.makedirs(outputFolder)
+    with open(ply_filePath, "wb") as f:
+        f.write(("\n".join(lines) + "\n").encode("ascii"))
+        f.write(saved_pts.tobytes())
+    return 1
+
+
+def save_sparseCubes_2ply(vxl_mask_list, vxl_ijk_list, rgb_list, param, ply_filePath, normal_list=None):
+    """The masked voxels of every cube as one PLY (utils/sparseCubes.py:284-327): xyz = ijk * resol + xyz_min of the cube, in float32 as the
+    reference computes it (uint8 * float32 scalar, then + float32)."""
+    vxl_mask_np = np.concatenate(vxl_mask_list, axis=0)
+    vxl_ijk_np = np.vstack(vxl_ijk_list)
+    rgb_np = np.vstack(rgb_list)
+    if not vxl_mask_np.shape[0] == vxl_ijk_np.shape[0] == rgb_np.shape[0]:
+        raise Warning('make sure # of voxels in each cube are consistent.')
+    normal_np = None if normal_list is None else np.vstack(normal_list)[vxl_mask_np]
+    cube_of = np.repeat(np.arange(len(vxl_mask_list)), [len(m) for m in vxl_mask_list])[vxl_mask_np]
+    resol = np.asarray(param['resol'])[cube_of]
+    xyz_np = vxl_ijk_np[vxl_mask_np] * resol[:, None] + np.asarray(param['xyz'])[cube_of]
+    save2ply(ply_filePath, xyz_np, rgb_np[vxl_mask_np], normal_np)
+    return 1
+
+
+def save_sparseCubes(filePath, prediction_list, rgb_list, vxl_ijk_list, rayPooling_votes_list, cube_ijk_np, param_np, viewPair_np):
+    """The sparse lists + per-cube tables as one compressed npz with the reference's keys (utils/sparseCubes.py:331-368)."""
+    prediction_np = np.concatenate(prediction_list, axis=0)
+    rgb_np = np.vstack(rgb_list)
+    vxl_ijk_np = np.vstack(vxl_ijk_list)
+    rayPooling_votes_np = np.empty((0,), np.uint8) if len(rayPooling_votes_list) == 0 else np.concatenate(rayPooling_votes_list, axis=0)
+    N_cube = cube_ijk_np.shape[0]
+    cube_1st_vxlIndx_np = np.zeros((N_cube + 1,)).astype(np.uint32)
+    cube_1st_vxlIndx_np[1:] = np.cumsum([p.size for p in prediction_list])
+    if not cube_1st_vxlIndx_np[-1] == prediction_np.shape[0] == rgb_np.shape[0] == vxl_ijk_np.shape[0]:
+        raise Warning("# of voxels is not consistent while saving sparseCubes.")
+    with open(filePath, 'wb') as f:
+        np.savez_compressed(f, cube_1st_vxlIndx_np=cube_1st_vxlIndx_np, prediction_np=prediction_np, rgb_np=rgb_np, vxl_ijk_np=vxl_ijk_np,
+                            rayPooling_votes_np=rayPooling_votes_np, cube_ijk_np=cube_ijk_np, param_np=param_np, viewPair_np=viewPair_np)
+
+
+def load_sparseCubes(filePath):
+    """utils/sparseCubes.py:371-407: -> (prediction_list, rgb_list, vxl_ijk_list, rayPooling_votes_list, cube_ijk_np, param_np, viewPair_np)."""
+    with np.load(filePath) as npz:
+        cube_1st_vxlIndx_np, prediction_np, rgb_np, vxl_ijk_np, rayPooling_votes_np, cube_ijk_np, param_np, viewPair_np = \
+            npz['cube_1st_vxlIndx_np'], npz['prediction_np'], npz['rgb_np'], npz['vxl_ijk_np'], npz['rayPooling_votes_np'], \
+            npz['cube_ijk_np'], npz['param_np'], npz['viewPair_np']
+    if not cube_1st_vxlIndx_np[-1] == prediction_np.shape[0] == rgb_np.shape[0] == vxl_ijk_np.shape[0]:
+        raise Warning("# of voxels is not consistent while saving sparseCubes.")
+    if not rayPooling_votes_np.shape[0] in [0, cube_1st_vxlIndx_np[-1]]:
+        raise Warning("rayPooling_votes_np.shape[0] != 0 / # of voxels.")
+    prediction_list, rgb_list, vxl_ijk_list, rayPooling_votes_list = [], [], [], []
+    for _n_cube in range(cube_ijk_np.shape[0]):
+        slc = np.s_[cube_1st_vxlIndx_np[_n_cube]: cube_1st_vxlIndx_np[_n_cube + 1]]
+        prediction_list.append(prediction_np[slc])
+        rgb_list.append(rgb_np[slc])
+        vxl_ijk_list.append(vxl_ijk_np[slc])
+        rayPooling_votes_list.append(rayPooling_votes_np[slc])
+    return prediction_list, rgb_list, vxl_ijk_list, rayPooling_votes_list, cube_ijk_np, param_np, viewPair_np

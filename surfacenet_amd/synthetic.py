@@ -7,6 +7,8 @@ from disk, so it travels to the GPU box as code.
     cube_grid         the cube table of utils/scene.py:7-61 (`initializeCubes`) — an INPUT CONTRACT of the hot path
                       (structured dtype xyz f32x3 | ijk u32x3 | resol f32, k fastest); checked row for row against
                       tables produced by the reference itself (tests/golden/scene_cases.npz, tests/test_host_logic.py)
+    sparse_surface    packed sparse voxel lists of a surface seen by a lattice of overlapping cubes (the input of the cross-cube
+                      post-pass: denoising / adapthresh), with floating specks and per-cube prediction noise
 """
 import numpy as np
 
@@ -82,3 +84,54 @@ def dataset_scene(config, cube_D=32, max_cubes=0, n_vp=0):
         cubes = cubes[np.linspace(0, len(cubes) - 1, min(int(max_cubes), len(cubes))).astype(np.int64)]
     imgs = [synth_image(2000 + v, hw[0], hw[1]) for v in range(P.shape[0])]
     return np.asarray(P, dtype=np.float64), imgs, cubes, cube_D_mm, Dc, n_vp
+
+
+def sparse_surface(lattice=(4, 4, 2), Dc=26, thickness=2, amplitude=6.0, speck_rate=0.002, seed=0, resol=0.4):
+    """The sparse lists dense2sparse would keep for a wavy surface seen by a lattice of overlapping cubes (stride Dc // 2, ijk from 0).
+    Every cube sees the surface voxels inside its extent in ascending flat index, with its own prediction noise (overlapping cubes predict
+    independently), uint8 votes, plus random floating specks. Returns a dict with the reference's list names: prediction_list (f16),
+    rgb_list (u8), vxl_ijk_list (u8), rayPooling_votes_list (u8), cube_ijk_np (u32), param_np (CUBE_DTYPE), viewPair_np (u16)."""
+    rs = np.random.RandomState(seed)
+    st = Dc // 2
+    L = [(n + 1) * st for n in lattice]
+    X, Y = np.meshgrid(np.arange(L[0]), np.arange(L[1]), indexing="ij")
+    z0 = L[2] / 2.0 + amplitude * np.sin(X / 9.0 + rs.uniform(0, 6)) * np.cos(Y / 13.0 + rs.uniform(0, 6))
+    Z = np.floor(z0).astype(np.int64)[..., None] + np.arange(thickness) - thickness // 2
+    pts = np.stack(np.broadcast_arrays(X[..., None], Y[..., None], Z), -1).reshape(-1, 3)
+    dist = np.abs(pts[:, 2] + 0.5 - z0.reshape(-1).repeat(thickness)) / max(thickness, 1)
+    n_speck = int(speck_rate * L[0] * L[1] * L[2])
+    specks = np.stack([rs.randint(0, L[d], n_speck) for d in range(3)], -1)
+    pts = np.concatenate([pts, specks])
+    dist = np.concatenate([dist, rs.uniform(0, 0.5, n_speck)])
+    keep = (pts[:, 2] >= 0) & (pts[:, 2] < L[2])
+    pts, dist = pts[keep], dist[keep]
+    lists = {k: [] for k in ("prediction_list", "rgb_list", "vxl_ijk_list", "rayPooling_votes_list")}
+    cubes = np.stack(np.meshgrid(*[np.arange(n) for n in lattice], indexing="ij"), -1).reshape(-1, 3)
+    # every point goes to the cubes whose extent holds it (index pts // st - o for o < ceil(Dc / st) per axis), in point order per cube
+    lat = np.asarray(lattice)
+    cand_cube, cand_pt = [], []
+    for o in np.stack(np.meshgrid(*[np.arange(-(-Dc // st))] * 3, indexing="ij"), -1).reshape(-1, 3):
+        idx = pts // st - o
+        ok = np.all((idx >= 0) & (idx < lat) & (pts - idx * st < Dc), axis=1)
+        cand_cube.append(((idx[ok, 0] * lat[1] + idx[ok, 1]) * lat[2] + idx[ok, 2]))
+        cand_pt.append(np.nonzero(ok)[0])
+    cand_cube, cand_pt = np.concatenate(cand_cube), np.concatenate(cand_pt)
+    order = np.lexsort((cand_pt, cand_cube))
+    cand_cube, cand_pt = cand_cube[order], cand_pt[order]
+    bounds = np.searchsorted(cand_cube, np.arange(len(cubes) + 1))
+    for ci, cube in enumerate(cubes):
+        sel = cand_pt[bounds[ci]:bounds[ci + 1]]
+        loc, d = pts[sel] - cube * st, dist[sel]
+        order = np.argsort((loc[:, 0] * Dc + loc[:, 1]) * Dc + loc[:, 2], kind="stable")
+        loc, d = loc[order], d[order]
+        pred = np.clip(0.95 - 0.6 * d + rs.normal(0, 0.12, d.size), 0.461, 1.0).astype(np.float16)
+        lists["prediction_list"].append(pred)
+        lists["vxl_ijk_list"].append(loc.astype(np.uint8))
+        lists["rgb_list"].append(rs.randint(0, 255, (d.size, 3)).astype(np.uint8))
+        lists["rayPooling_votes_list"].append(np.clip(np.round(8 - 10 * d + rs.normal(0, 2, d.size)), 0, 10).astype(np.uint8))
+    param = np.zeros((len(cubes),), CUBE_DTYPE)
+    param["ijk"] = cubes
+    param["resol"] = resol
+    param["xyz"] = (cubes * st * resol).astype(np.float32) + np.float32(-20.0)
+    lists.update(cube_ijk_np=cubes.astype(np.uint32), param_np=param, viewPair_np=np.zeros((len(cubes), 1, 2), np.uint16))
+    return lists
