@@ -233,6 +233,23 @@ SN_API int sn_adapthresh_dev(sn_ctx *ctx, int n, int Dc, const sn_adapthresh_cfg
                              const uint32_t *cube_ijk_dev, unsigned char *init_denoised_dev, double *thresh_dev, unsigned char *masks_dev,
                              unsigned char *denoised_dev, signed char *choice_dev);
 
+/* ---- DTU point-cloud evaluation (experiments/DTU/eval_ply.m -> PointCompareMain of the DTU kit) ----------------------
+ * Points are (n,3) float64, row-major, finite. d^2 = (dx*dx + dy*dy) + dz*dz in float64 without contraction: the results are those of the numpy
+ * restatement bit for bit. Host arrays in and out; the device workspace belongs to the context (grown on demand). Synchronous. n <= 2^29.
+ *
+ * sn_point_reduce (reducePts_haa): visit the points in ascending rank (rank: a permutation of 0..n-1); a point still alive removes every other
+ * point within d^2 <= dst^2. keep (n) receives 1 for the survivors - the greedy maximal independent set of that order - and rounds (optional) the
+ * number of parallel rounds it took; SN_ERR_STATE past 65536 rounds (orders that chain the points, not random ones). */
+SN_API int sn_point_reduce(sn_ctx *ctx, long long n, const double *xyz, const long long *rank, double dst, unsigned char *keep, int *rounds);
+/* sn_nn_dist2 (MaxDistCP): d2[i] = min_j d^2(from_i, to_j) when that minimum is below max_dist^2 * (1 + 2^-40), else +inf (also for an empty
+ * "to" cloud): min(sqrt(d2), max_dist) is the capped distance. */
+SN_API int sn_nn_dist2(sn_ctx *ctx, long long n_to, const double *to, long long n_from, const double *from, double max_dist, double *d2);
+/* sn_point_flags: in_mask[i] (DataInMask) = 1 iff v = round((xyz_i - bb_min) / res) per axis (half away from zero) lies in [0, dims) and
+ * mask[v0][v1][v2] != 0 (mask: dims[0] x dims[1] x dims[2] bytes, C order); above[i] (StlAbovePlane) = 1 iff
+ * ((plane[0]*x + plane[1]*y) + plane[2]*z) + plane[3] > 0. Either output may be NULL (its inputs are then not read). */
+SN_API int sn_point_flags(sn_ctx *ctx, long long n, const double *xyz, const unsigned char *mask, const int *dims, const double *bb_min, double res,
+                          const double *plane, unsigned char *in_mask, unsigned char *above);
+
 /* ---- similarityNet / early rejection (main_reconstruct.py:76-97) ---------------- */
 /* pickle.load + set_all_param_values([embedding layer, similarity layer]) of similarityNet_inference
  * (nets/similarityNet.py:229-244): 30 arrays in order — 13 x (conv W (Cout,Cin,3,3), b (Cout,)) for conv1_1 .. conv5_3

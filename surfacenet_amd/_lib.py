@@ -20,6 +20,7 @@ ABI_SYMBOLS = [
     "sn_cvc_forward_dev", "sn_cvc_dev", "sn_forward_dev",
     "sn_ray_pool", "sn_ray_pool_dev", "sn_dense2sparse", "sn_dense2sparse_dev",
     "sn_denoise", "sn_denoise_dev", "sn_adapthresh", "sn_adapthresh_dev",
+    "sn_point_reduce", "sn_nn_dist2", "sn_point_flags",
     "sn_simil_load_weights", "sn_crop_patches", "sn_patch2embedding", "sn_crop_embed", "sn_embeddingpair2simil", "sn_embeddings2simil",
     "sn_project_points",
     "sn_comm_unique_id", "sn_comm_init", "sn_comm_init_deadline", "sn_comm_info", "sn_allgather_f32_dev", "sn_allgather_f32_dev_overlap", "sn_comm_wait", "sn_allgatherv_counts", "sn_allgatherv_bytes_dev",
@@ -107,6 +108,9 @@ def load():
         "sn_denoise_dev": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_longlong] + [c_void_p] * 5),
         "sn_adapthresh": (c_int, [c_void_p, c_int, c_int, P(AdapthreshCfg)] + [c_void_p] * 10),
         "sn_adapthresh_dev": (c_int, [c_void_p, c_int, c_int, P(AdapthreshCfg), ctypes.c_longlong] + [c_void_p] * 10),
+        "sn_point_reduce": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_double, c_void_p, P(c_int)]),
+        "sn_nn_dist2": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_double, c_void_p]),
+        "sn_point_flags": (c_int, [c_void_p, ctypes.c_longlong] + [c_void_p] * 4 + [ctypes.c_double] + [c_void_p] * 3),
         "sn_simil_load_weights": (c_int, [c_void_p, c_void_p, c_size_t, P(ParamDesc), c_int]),
         "sn_crop_patches": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
         "sn_patch2embedding": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),

@@ -437,6 +437,49 @@ class Context(object):
                 out[k] = out[k].view(bool)
         return out
 
+    @staticmethod
+    def _points(xyz):
+        return np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))
+
+    def point_reduce(self, xyz, rank, dst):
+        """reducePts_haa of the DTU kit: xyz (n,3), rank (n,) a permutation of 0..n-1 (the visiting order's inverse) -> (keep (n,) bool, rounds):
+        the greedy maximal independent set under d^2 <= dst^2, visiting the points in ascending rank."""
+        p = self._points(xyz)
+        r = np.ascontiguousarray(rank, dtype=np.int64).reshape(-1)
+        if r.size != p.shape[0]:
+            raise ValueError("rank has %d entries for %d points" % (r.size, p.shape[0]))
+        keep = np.zeros((p.shape[0],), np.uint8)
+        rounds = ctypes.c_int(0)
+        _lib.check(self._lib.sn_point_reduce(self._h, p.shape[0], _lib.ptr(p), _lib.ptr(r), float(dst), _lib.ptr(keep), ctypes.byref(rounds)))
+        return keep.view(bool), rounds.value
+
+    def nn_dist2(self, to, frm, max_dist):
+        """MaxDistCP's search: (n_from,) float64 min_j d^2(frm_i, to_j), exact when below max_dist^2 (1 + 2^-40), else +inf."""
+        t, f = self._points(to), self._points(frm)
+        d2 = np.zeros((f.shape[0],), np.float64)
+        _lib.check(self._lib.sn_nn_dist2(self._h, t.shape[0], _lib.ptr(t), f.shape[0], _lib.ptr(f), float(max_dist), _lib.ptr(d2)))
+        return d2
+
+    def point_flags(self, xyz, mask=None, bb_min=None, res=None, plane=None):
+        """DataInMask (mask (X,Y,Z) uint8, bb_min (3,), res; None: not computed) and StlAbovePlane (plane (4,); None: not computed) of xyz (n,3)
+        -> (in_mask, above), (n,) bool arrays or None."""
+        p = self._points(xyz)
+        n = p.shape[0]
+        in_mask = above = m = dims = bb = pl = None
+        if mask is not None:
+            m = np.ascontiguousarray(mask, dtype=np.uint8)
+            if m.ndim != 3:
+                raise ValueError("mask must be 3-D")
+            dims = np.asarray(m.shape, dtype=np.int32)
+            bb = np.ascontiguousarray(bb_min, dtype=np.float64).reshape(3)
+            in_mask = np.zeros((n,), np.uint8)
+        if plane is not None:
+            pl = np.ascontiguousarray(plane, dtype=np.float64).reshape(4)
+            above = np.zeros((n,), np.uint8)
+        _lib.check(self._lib.sn_point_flags(self._h, n, _lib.ptr(p), _lib.ptr(m), _lib.ptr(dims), _lib.ptr(bb), float(res) if mask is not None else 0.0,
+                                            _lib.ptr(pl), _lib.ptr(in_mask), _lib.ptr(above)))
+        return (None if in_mask is None else in_mask.view(bool)), (None if above is None else above.view(bool))
+
     def dev_alloc(self, nbytes):
         p = self._lib.sn_dev_alloc(self._h, int(nbytes))
         if not p:

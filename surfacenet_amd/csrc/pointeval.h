@@ -1,0 +1,399 @@
+// pointeval.h — the DTU point-cloud evaluation (experiments/DTU/eval_ply.m -> PointCompareMain of the DTU kit) on the GPU:
+//   density reduction   reducePts_haa: greedy maximal independent set of the points under d^2 <= dst^2, in a given visiting order
+//   capped NN distance  MaxDistCP: min_j d^2(q, p_j) for every query, exact, for every minimum below the cap
+//   flags               DataInMask (ObsMask voxel lookup) and StlAbovePlane (plane side)
+// Integer and fp64 VALU work: no MFMA. d^2 = (dx*dx + dy*dy) + dz*dz in fp64 with no contraction (the Makefile passes -ffp-contract=off), so
+// the results equal the numpy restatement (tests/pointeval_ref.py) bit for bit (DESIGN.md section 4.7 states the contract).
+//
+// Every cloud is bucketed on a uniform grid: cell = floor((x - origin) / h) per axis (dims <= 2^21 per axis, so a cell key packs into 63 bits).
+// Occupied cells live in an open-addressing hash table (key -> slot, linear probing, as crosscube.h's ijk -> cube map); per-slot counts come from
+// wave-aggregated atomics (one atomic per run of equal slots in a wave), an exclusive scan gives each slot its range, and a scatter writes the
+// points cell-sorted (CSR). Neighbour and ring searches walk cells and read each occupied cell's contiguous run of points.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace sn {
+
+constexpr int PE_NT = 256;
+constexpr int PE_SCAN = 1024;                         // elements per workgroup of the scan (256 threads x 4)
+constexpr unsigned long long PE_EMPTY = ~0ull;        // free hash slot (cell keys are < 2^63)
+constexpr unsigned char PE_UND = 0, PE_IN = 1, PE_OUT = 2;   // reduction states
+
+// A cloud bucketed on a grid. xyz / idx are the cell-sorted points and their original indices; keys / start / count are indexed by hash slot.
+struct PEGrid {
+    double o[3], h;
+    double lo[3], hi[3];                // bounding box of the points (a lower bound for every distance to them)
+    long long dim[3];
+    const unsigned long long *keys;
+    const int *start, *count;
+    unsigned mask;                      // table capacity - 1
+    const double *xyz;
+    const int *idx;
+};
+
+__device__ inline unsigned pe_hash(unsigned long long k, unsigned mask)
+{
+    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
+    return (unsigned)k & mask;
+}
+
+__device__ inline unsigned long long pe_key(const long long *dim, long long x, long long y, long long z)
+{
+    return (unsigned long long)((x * dim[1] + y) * dim[2] + z);
+}
+
+// cell index of one coordinate, clamped to [-1, dim]: a query outside the grid sits in the layer of cells just outside it, which keeps the
+// shell bounds of pe_shell_bound valid (every point lies at index >= 0 resp. <= dim - 1).
+__device__ inline long long pe_cell(double x, double o, double h, long long dim)
+{
+    const double c = floor((x - o) / h);
+    return c < -1.0 ? -1 : (c > (double)dim ? dim : (long long)c);
+}
+
+// slot of a cell, -1 if the cell holds no point. The probe ends at a free slot: the table is at most half full.
+__device__ inline int pe_find(const PEGrid &g, long long x, long long y, long long z)
+{
+    if (x < 0 || y < 0 || z < 0 || x >= g.dim[0] || y >= g.dim[1] || z >= g.dim[2]) return -1;
+    const unsigned long long key = pe_key(g.dim, x, y, z);
+    unsigned h = pe_hash(key, g.mask);
+    for (;;) {
+        const unsigned long long cur = g.keys[h];
+        if (cur == key) return (int)h;
+        if (cur == PE_EMPTY) return -1;
+        h = (h + 1) & g.mask;
+    }
+}
+
+__device__ inline double pe_d2(const double *a, const double *b)
+{
+    const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+// A distance lower bound lb (mm) -> a value no computed d^2 of a point at least lb away falls below. `slack` covers the rounding of the cell
+// indices and of the bound's own arithmetic; it only makes the searches visit a little more.
+__device__ inline double pe_bound2(double lb, double slack)
+{
+    lb -= slack;
+    return lb > 0.0 ? lb * lb * (1.0 - 1e-12) : 0.0;
+}
+
+// lower bound on the distance from q to every point of the grid outside the (2r+1)^3 block of cells around c (+inf: no cell outside it)
+__device__ inline double pe_shell_lb(const PEGrid &g, const double *q, const long long *c, long long r, double h)
+{
+    double lb = __builtin_inf();
+    for (int a = 0; a < 3; ++a) {
+        if (c[a] + r + 1 <= g.dim[a] - 1) lb = fmin(lb, (g.o[a] + (double)(c[a] + r + 1) * h) - q[a]);
+        if (c[a] - r - 1 >= 0) lb = fmin(lb, q[a] - (g.o[a] + (double)(c[a] - r) * h));
+    }
+    return lb;
+}
+
+// squared-distance lower bound from q to the box [lo, hi]
+__device__ inline double pe_box_bound2(const double *q, const double *lo, const double *hi, double slack)
+{
+    double s = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        const double gap = fmax(fmax(lo[a] - q[a], q[a] - hi[a]), 0.0) - slack;
+        if (gap > 0.0) s += gap * gap;
+    }
+    return s * (1.0 - 1e-12);
+}
+
+// Calls f(slot) for every occupied cell at Chebyshev distance exactly r from c, inside the grid.
+template <typename F>
+__device__ inline void pe_for_shell(const PEGrid &g, const long long *c, long long r, F &&f)
+{
+    const long long x0 = c[0] - r > 0 ? c[0] - r : 0, x1 = c[0] + r < g.dim[0] - 1 ? c[0] + r : g.dim[0] - 1;
+    const long long y0 = c[1] - r > 0 ? c[1] - r : 0, y1 = c[1] + r < g.dim[1] - 1 ? c[1] + r : g.dim[1] - 1;
+    const long long z0 = c[2] - r > 0 ? c[2] - r : 0, z1 = c[2] + r < g.dim[2] - 1 ? c[2] + r : g.dim[2] - 1;
+    for (long long x = x0; x <= x1; ++x)
+        for (long long y = y0; y <= y1; ++y) {
+            const bool side = x == c[0] - r || x == c[0] + r || y == c[1] - r || y == c[1] + r;
+            const long long step = side || r == 0 ? 1 : 2 * r;          // off the x / y faces only the two z faces belong to the shell
+            for (long long z = side ? z0 : c[2] - r; z <= (side ? z1 : c[2] + r); z += step) {
+                if (z < 0 || z >= g.dim[2]) continue;
+                const int s = pe_find(g, x, y, z);
+                if (s >= 0) f(s);
+            }
+        }
+}
+
+// ---- grid build ---------------------------------------------------------------------------------------------------------------------------
+struct PEBuildArgs {
+    const double *xyz;                  // [n][3], original order
+    const long long *rank;              // optional: per-point rank, scattered into rank_s
+    unsigned long long *keys;
+    int *start, *count, *slot, *pos, *idx, *rank_s;
+    double *xyz_s;
+    int *occupied;                      // number of distinct cells (counted at insertion)
+    double o[3], h;
+    long long dim[3];
+    unsigned mask;
+    int n;
+};
+
+// Inserts every point's cell and counts the points per cell; pos = the point's place in its cell's run. One atomic per run of equal
+// slots in a wave (input in spatial order - the data cloud of a reconstruction is - makes runs long).
+__global__ void __launch_bounds__(PE_NT) pe_insert_kernel(PEBuildArgs a)
+{
+    const int i = blockIdx.x * PE_NT + threadIdx.x, lane = threadIdx.x & 63;
+    int s = -1;
+    if (i < a.n) {
+        const double *p = a.xyz + 3 * (size_t)i;
+        long long c[3];
+        for (int d = 0; d < 3; ++d) {
+            const long long v = pe_cell(p[d], a.o[d], a.h, a.dim[d]);
+            c[d] = v < 0 ? 0 : (v >= a.dim[d] ? a.dim[d] - 1 : v);      // (host-sized dims hold every point; the clamp guards rounding only)
+        }
+        const unsigned long long key = pe_key(a.dim, c[0], c[1], c[2]);
+        unsigned h = pe_hash(key, a.mask);
+        for (;;) {
+            unsigned long long cur = __hip_atomic_load(a.keys + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (cur == PE_EMPTY) {
+                unsigned long long expected = PE_EMPTY;
+                if (__hip_atomic_compare_exchange_strong(a.keys + h, &expected, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+                    atomicAdd(a.occupied, 1);
+                    break;
+                }
+                cur = expected;
+            }
+            if (cur == key) break;
+            h = (h + 1) & a.mask;
+        }
+        s = (int)h;
+    }
+    // runs of equal slots: a lane heads a run when its slot differs from the lane before; the head adds the run's length
+    const int prev = __shfl_up(s, 1);
+    const unsigned long long heads = __ballot(lane == 0 || prev != s);
+    const unsigned long long upto = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
+    const int head = 63 - __clzll(heads & upto);
+    const unsigned long long above = heads & ~upto;
+    const int next = above ? __ffsll(above) - 1 : 64;
+    int base = 0;
+    if (lane == head && s >= 0) base = atomicAdd(a.count + s, next - lane);
+    base = __shfl(base, head);
+    if (i < a.n) { a.slot[i] = s; a.pos[i] = base + (lane - head); }
+}
+
+// exclusive scan of in[0, n) within each block of PE_SCAN elements; block totals to sums (if given). in may alias out.
+__global__ void __launch_bounds__(PE_NT) pe_scan_kernel(const int *in, int *out, int n, int *sums)
+{
+    __shared__ int sh[PE_NT];
+    const int tid = threadIdx.x;
+    const long long base = (long long)blockIdx.x * PE_SCAN + 4 * tid;
+    int v[4], t = 0;
+    for (int k = 0; k < 4; ++k) { v[k] = base + k < n ? in[base + k] : 0; t += v[k]; }
+    sh[tid] = t;
+    __syncthreads();
+    for (int off = 1; off < PE_NT; off <<= 1) {
+        const int add = tid >= off ? sh[tid - off] : 0;
+        __syncthreads();
+        sh[tid] += add;
+        __syncthreads();
+    }
+    int run = sh[tid] - t;
+    if (sums && tid == PE_NT - 1) sums[blockIdx.x] = sh[tid];
+    for (int k = 0; k < 4; ++k) {
+        if (base + k < n) out[base + k] = run;
+        run += v[k];
+    }
+}
+
+__global__ void __launch_bounds__(PE_NT) pe_scan_add_kernel(int *out, int n, const int *offs)
+{
+    const long long i = (long long)blockIdx.x * PE_NT + threadIdx.x;
+    if (i < n) out[i] += offs[i / PE_SCAN];
+}
+
+__global__ void __launch_bounds__(PE_NT) pe_scatter_kernel(PEBuildArgs a)
+{
+    const int i = blockIdx.x * PE_NT + threadIdx.x;
+    if (i >= a.n) return;
+    const int t = a.start[a.slot[i]] + a.pos[i];
+    a.idx[t] = i;
+    for (int d = 0; d < 3; ++d) a.xyz_s[3 * (size_t)t + d] = a.xyz[3 * (size_t)i + d];
+    if (a.rank) a.rank_s[t] = (int)a.rank[i];
+}
+
+// ---- density reduction (reducePts_haa): the parallel form of the greedy MIS --------------------------------------------------------------
+// A round: (select) an undecided point whose every neighbour of smaller rank is OUT becomes IN; (exclude) an undecided point with an IN
+// neighbour becomes OUT. Neighbours: d^2 <= dst2, j != i; the cell size exceeds dst, so they lie in the 27 cells around a point's own.
+// Both steps only move undecided points, and a concurrent UND -> IN change is read the same either way (both are "not OUT"), so updating
+// the states in place is race-free in effect. The result is the sequential greedy result for the rank order.
+struct PEReduceArgs {
+    PEGrid g;
+    const int *rank;                    // cell-sorted ranks
+    unsigned char *state;               // cell-sorted
+    unsigned long long *undecided;
+    double dst2;
+    int n;
+};
+
+__global__ void __launch_bounds__(PE_NT) pe_reduce_select_kernel(PEReduceArgs a)
+{
+    const int t = blockIdx.x * PE_NT + threadIdx.x;
+    if (t >= a.n || a.state[t] != PE_UND) return;
+    const PEGrid &g = a.g;
+    const double *q = g.xyz + 3 * (size_t)t;
+    const int rk = a.rank[t];
+    long long c[3];
+    for (int d = 0; d < 3; ++d) c[d] = pe_cell(q[d], g.o[d], g.h, g.dim[d]);
+    for (int nb = 0; nb < 27; ++nb) {
+        const int s = pe_find(g, c[0] + nb / 9 - 1, c[1] + (nb / 3) % 3 - 1, c[2] + nb % 3 - 1);
+        if (s < 0) continue;
+        const int e = g.start[s] + g.count[s];
+        for (int j = g.start[s]; j < e; ++j)
+            if (a.rank[j] < rk && a.state[j] != PE_OUT && pe_d2(q, g.xyz + 3 * (size_t)j) <= a.dst2) return;   // blocked this round
+    }
+    a.state[t] = PE_IN;
+}
+
+__global__ void __launch_bounds__(PE_NT) pe_reduce_exclude_kernel(PEReduceArgs a)
+{
+    const int t = blockIdx.x * PE_NT + threadIdx.x;
+    bool und = t < a.n && a.state[t] == PE_UND;
+    if (und) {
+        const PEGrid &g = a.g;
+        const double *q = g.xyz + 3 * (size_t)t;
+        long long c[3];
+        for (int d = 0; d < 3; ++d) c[d] = pe_cell(q[d], g.o[d], g.h, g.dim[d]);
+        for (int nb = 0; nb < 27 && und; ++nb) {
+            const int s = pe_find(g, c[0] + nb / 9 - 1, c[1] + (nb / 3) % 3 - 1, c[2] + nb % 3 - 1);
+            if (s < 0) continue;
+            const int e = g.start[s] + g.count[s];
+            for (int j = g.start[s]; j < e; ++j)
+                if (a.state[j] == PE_IN && pe_d2(q, g.xyz + 3 * (size_t)j) <= a.dst2) { und = false; break; }
+        }
+        if (!und) a.state[t] = PE_OUT;
+    }
+    if (und) atomicAdd(a.undecided, 1ull);
+}
+
+__global__ void __launch_bounds__(PE_NT) pe_reduce_keep_kernel(const int *idx, const unsigned char *state, int n, unsigned char *keep)
+{
+    const int t = blockIdx.x * PE_NT + threadIdx.x;
+    if (t < n) keep[idx[t]] = state[t] == PE_IN ? 1 : 0;
+}
+
+// ---- capped nearest-neighbour distance (MaxDistCP) -----------------------------------------------------------------------------------------
+// Queries run in the cell-sorted order of their own cloud (lanes of a wave are neighbours). The near pass walks the fine grid of the "to"
+// cloud ring by ring from the query's cell; after ring r every point not yet seen lies outside the (2r+1)^3 block, so the distance to the
+// block's faces (and to the cloud's box) bounds it from below. A query stops when its best d^2 is at most that bound, or the bound reaches
+// lim (every minimum below lim is found; above it the result is +inf). Queries left after PE_NEAR_RINGS rings go to a list, which the far pass
+// serves on a coarse grid (PE_COARSE fine cells per axis): rings of coarse cells, each occupied one scanned point by point unless its box
+// lies beyond the best d^2 so far - a query far from every point walks O((max_dist / H)^3) coarse cells, not O((max_dist / h)^3) fine ones.
+constexpr int PE_NEAR_RINGS = 2;
+constexpr int PE_COARSE = 8;
+
+struct PENNArgs {
+    PEGrid fine, coarse;
+    const double *q;                    // queries, cell-sorted
+    const int *q_idx;                   // their original indices
+    double *best;                       // [n_q] the near pass's best d^2 per sorted query (far queries)
+    int *far_list, *far_count;
+    double *d2;                         // [n_q] result, original order
+    double lim, slack;
+    int n_q;
+};
+
+__device__ inline double pe_query_slack(const double *q, double slack)
+{
+    return slack + 1e-12 * (fabs(q[0]) + fabs(q[1]) + fabs(q[2]));
+}
+
+__global__ void __launch_bounds__(PE_NT) pe_nn_near_kernel(PENNArgs a)
+{
+    const int t = blockIdx.x * PE_NT + threadIdx.x;
+    if (t >= a.n_q) return;
+    const PEGrid &g = a.fine;
+    const double *q = a.q + 3 * (size_t)t;
+    const double slack = pe_query_slack(q, a.slack);
+    const double box = pe_box_bound2(q, g.lo, g.hi, slack);
+    double best = __builtin_inf();
+    bool done = box >= a.lim;
+    if (!done) {
+        long long c[3];
+        for (int d = 0; d < 3; ++d) c[d] = pe_cell(q[d], g.o[d], g.h, g.dim[d]);
+        for (long long r = 0; r <= PE_NEAR_RINGS && !done; ++r) {
+            pe_for_shell(g, c, r, [&](int s) {
+                const int e = g.start[s] + g.count[s];
+                for (int j = g.start[s]; j < e; ++j) best = fmin(best, pe_d2(q, g.xyz + 3 * (size_t)j));
+            });
+            const double bnd = fmax(pe_bound2(pe_shell_lb(g, q, c, r, g.h), slack), box);
+            done = best <= bnd || bnd >= a.lim;
+        }
+    }
+    if (done) {
+        a.d2[a.q_idx[t]] = best < a.lim ? best : __builtin_inf();
+        return;
+    }
+    a.best[t] = best;
+    a.far_list[atomicAdd(a.far_count, 1)] = t;
+}
+
+__global__ void __launch_bounds__(PE_NT) pe_nn_far_kernel(PENNArgs a)
+{
+    const int k = blockIdx.x * PE_NT + threadIdx.x;
+    if (k >= *a.far_count) return;
+    const int t = a.far_list[k];
+    const PEGrid &g = a.coarse;
+    const double *q = a.q + 3 * (size_t)t;
+    const double slack = pe_query_slack(q, a.slack);
+    const double box = pe_box_bound2(q, g.lo, g.hi, slack);
+    double best = a.best[t];
+    long long c[3];
+    for (int d = 0; d < 3; ++d) c[d] = pe_cell(q[d], g.o[d], g.h, g.dim[d]);
+    const long long rmax = g.dim[0] + g.dim[1] + g.dim[2] + 2;     // past this ring no cell is left (the loop ends on the bound first)
+    for (long long r = 0; r <= rmax; ++r) {
+        pe_for_shell(g, c, r, [&](int s) {
+            const int j0 = g.start[s];
+            const unsigned long long key = g.keys[s];       // the cell's box, from its key
+            const long long ci[3] = {(long long)(key / (unsigned long long)(g.dim[1] * g.dim[2])), (long long)((key / (unsigned long long)g.dim[2]) % (unsigned long long)g.dim[1]),
+                                     (long long)(key % (unsigned long long)g.dim[2])};
+            double lo[3], hi[3];
+            for (int d = 0; d < 3; ++d) {
+                lo[d] = g.o[d] + (double)ci[d] * g.h;
+                hi[d] = g.o[d] + (double)(ci[d] + 1) * g.h;
+            }
+            const double cb = pe_box_bound2(q, lo, hi, slack);
+            if (cb >= best || cb >= a.lim) return;
+            const int e = j0 + g.count[s];
+            for (int j = j0; j < e; ++j) best = fmin(best, pe_d2(q, g.xyz + 3 * (size_t)j));
+        });
+        const double bnd = fmax(pe_bound2(pe_shell_lb(g, q, c, r, g.h), slack), box);
+        if (best <= bnd || bnd >= a.lim) break;
+    }
+    a.d2[a.q_idx[t]] = best < a.lim ? best : __builtin_inf();
+}
+
+// ---- DataInMask / StlAbovePlane -------------------------------------------------------------------------------------------------------------
+struct PEFlagsArgs {
+    const double *xyz;
+    const unsigned char *mask;          // ObsMask, [dim0][dim1][dim2]
+    long long dim[3];
+    double bb[3], res, plane[4];
+    unsigned char *in_mask, *above;
+    int n;
+};
+
+__global__ void __launch_bounds__(PE_NT) pe_flags_kernel(PEFlagsArgs a)
+{
+    const int i = blockIdx.x * PE_NT + threadIdx.x;
+    if (i >= a.n) return;
+    const double *q = a.xyz + 3 * (size_t)i;
+    if (a.in_mask) {
+        bool in = true;
+        long long v[3] = {0, 0, 0};
+        for (int d = 0; d < 3; ++d) {
+            const double r = round((q[d] - a.bb[d]) / a.res);        // half away from zero, as MATLAB's round
+            if (!(r >= 0.0 && r < (double)a.dim[d])) { in = false; break; }
+            v[d] = (long long)r;
+        }
+        a.in_mask[i] = in && a.mask[(v[0] * a.dim[1] + v[1]) * a.dim[2] + v[2]] != 0 ? 1 : 0;
+    }
+    if (a.above) a.above[i] = ((a.plane[0] * q[0] + a.plane[1] * q[1]) + a.plane[2] * q[2]) + a.plane[3] > 0.0 ? 1 : 0;
+}
+
+}  // namespace sn

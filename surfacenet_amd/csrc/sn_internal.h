@@ -143,6 +143,7 @@ struct sn_ctx {
     unsigned *d_num = nullptr;    // numeric status word: bit i = conv layer i of the launch order stored a non-finite / fp16-overflowing value
     std::vector<std::string> num_names;   // layer name of each status bit
     void *rp_ws = nullptr; size_t rp_ws_bytes = 0; int *d_err = nullptr;   /* device error flag: 1 ray pooling range, CC_ERR_INPUT_FLAG post-pass input */ int *d_counts = nullptr; int d_counts_cap = 0;
+    void *pe_ws = nullptr; size_t pe_ws_bytes = 0;   // point-cloud evaluation workspace (sn_pointeval.hip)
     std::vector<void *> owned;
     // profiling
     bool prof_on = false;

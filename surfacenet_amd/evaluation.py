@@ -1,0 +1,149 @@
+"""The DTU accuracy / completeness protocol of the reference (experiments/DTU/eval_ply.m, which calls PointCompareMain of the DTU kit), on the
+MI355X. DESIGN.md section 4.7 states the contract and what of the kit (not part of the reference) is a documented choice here.
+
+    read_ply_xyz     a PLY's vertex x, y, z (ascii, binary little / big endian; also the reference's scene.readPointCloud_xyz)
+    reduce_points    reducePts_haa: greedy density reduction of the data cloud (minimum distance dst)
+    max_dist_cp      MaxDistCP: nearest-neighbour distance from every point of one cloud to another, capped at max_dist
+    point_compare    PointCompareMain: the BaseEval fields
+    eval_acc_compl   eval_ply.m's four numbers from a BaseEval
+    eval_ply         the drop-in for eval_ply.m: the DTU folder's files in, BaseEval .mat out, the four numbers back
+
+The reduction, the distances and the mask / plane flags run on the GPU (surfacenet_amd/csrc/pointeval.h); the statistics are numpy on the
+host. A scene is evaluated in memory with sparseCubes.sparse_xyz (the points save_sparseCubes_2ply would write). Only the .mat I/O of
+eval_ply needs scipy (imported there).
+"""
+import os
+
+import numpy as np
+
+from . import runtime
+
+_PLY_SCALARS = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+                "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def _ply_header(f):
+    if f.readline().strip() != b"ply":
+        raise ValueError("not a PLY file")
+    fmt, elements = None, []
+    while True:
+        line = f.readline()
+        if not line:
+            raise ValueError("PLY header without end_header")
+        tok = line.decode("ascii", "replace").split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "end_header":
+            return fmt, elements
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append((tok[1], int(tok[2]), []))
+        elif tok[0] == "property":
+            if tok[1] == "list":
+                elements[-1][2].append((tok[4], None))
+            else:
+                elements[-1][2].append((tok[2], _PLY_SCALARS[tok[1]]))
+
+
+def read_ply_xyz(path):
+    """(N,3) array of the vertex element's x, y, z (dtype as stored, promoted across the three). The vertex element may be preceded only by
+    elements of fixed size (no list properties)."""
+    with open(path, "rb") as f:
+        fmt, elements = _ply_header(f)
+        body = f.read()
+    if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
+        raise ValueError("unknown PLY format %r" % fmt)
+    skip = 0
+    for name, count, props in elements:
+        if name == "vertex":
+            break
+        if any(t is None for _, t in props):
+            raise ValueError("element %r before the vertices has list properties: unsupported" % name)
+        skip += count * (1 if fmt == "ascii" else sum(np.dtype(t).itemsize for _, t in props))
+    else:
+        raise ValueError("PLY file without a vertex element")
+    if any(t is None for _, t in props):
+        raise ValueError("vertex element with list properties: unsupported")
+    names = [p for p, _ in props]
+    if fmt == "ascii":
+        lines = body.decode("ascii").splitlines()
+        lines = [ln for ln in lines if ln.strip()][skip:skip + count]
+        vals = np.asarray([ln.split() for ln in lines], dtype=object).reshape(count, len(props))
+        cols = [vals[:, names.index(k)].astype(np.float64).astype(dict(props)[k]) for k in ("x", "y", "z")]
+    else:
+        end = "<" if fmt == "binary_little_endian" else ">"
+        dt = np.dtype([(p, end + t) for p, t in props])
+        v = np.frombuffer(body, dtype=dt, count=count, offset=skip)
+        cols = [v[k].astype(v[k].dtype.newbyteorder("=")) for k in ("x", "y", "z")]
+    return np.stack(cols, axis=1) if count else np.zeros((0, 3), np.result_type(*cols))
+
+
+def _points(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1, 3))
+
+
+def reduce_points(pts, dst=0.2, seed=0, order=None, return_index=False):
+    """reducePts_haa(Qdata, dst): visit the points in `order` (default np.random.RandomState(seed).permutation(n); the kit's MATLAB randperm
+    cannot be reproduced); a point still alive removes every other point within d^2 <= dst^2. Returns the survivors in ascending index order
+    (and their indices)."""
+    p = _points(pts)
+    n = p.shape[0]
+    order = np.random.RandomState(seed).permutation(n) if order is None else np.asarray(order, dtype=np.int64).reshape(-1)
+    if order.size != n or not np.array_equal(np.sort(order), np.arange(n)):
+        raise ValueError("order must be a permutation of range(%d)" % n)
+    rank = np.empty((n,), np.int64)
+    rank[order] = np.arange(n)
+    keep, _ = runtime.any_context().point_reduce(p, rank, dst)
+    idx = np.nonzero(keep)[0]
+    return (p[idx], idx) if return_index else p[idx]
+
+
+def max_dist_cp(Qto, Qfrom, max_dist=60.0):
+    """MaxDistCP(Qto, Qfrom, BB, MaxDist): for every point of Qfrom, min(sqrt(min_j d^2), max_dist), and max_dist when Qto is empty. Exact at
+    every distance. The kit's answer beyond max_dist depends on its block tiling (BB), which is not known; here it is max_dist, and BB plays
+    no part in the distances."""
+    d2 = runtime.any_context().nn_dist2(_points(Qto), _points(Qfrom), max_dist)
+    return np.minimum(np.sqrt(d2), float(max_dist))
+
+
+def point_compare(Qdata, Qstl, obs_mask, BB, Res, plane, dst=0.2, max_dist=60.0, seed=0, order=None, cSet=None, Margin=None):
+    """PointCompareMain(cSet, Qdata, dst, dataPath) on arrays: Qdata, Qstl (N,3); obs_mask (X,Y,Z) uint8, BB (2,3) and Res of the ObsMask file;
+    plane (4,) of the Plane file. Returns the BaseEval fields: cSet, Margin, dst, Qdata (the reduced data cloud), Ddata, Qstl, Dstl,
+    DataInMask, GroundPlane, StlAbovePlane (points (N,3), per-point arrays (N,))."""
+    ctx = runtime.any_context()
+    Qd = reduce_points(Qdata, dst, seed, order)
+    Qs = _points(Qstl)
+    BB = np.asarray(BB, dtype=np.float64).reshape(2, 3)
+    plane = np.asarray(plane, dtype=np.float64).reshape(4)
+    in_mask, _ = ctx.point_flags(Qd, mask=obs_mask, bb_min=BB[0], res=float(np.asarray(Res, dtype=np.float64).reshape(-1)[0]))
+    _, above = ctx.point_flags(Qs, plane=plane)
+    return dict(cSet=cSet, Margin=Margin, dst=float(dst), Qdata=Qd, Ddata=max_dist_cp(Qs, Qd, max_dist), Qstl=Qs, Dstl=max_dist_cp(Qd, Qs, max_dist),
+                DataInMask=in_mask, GroundPlane=plane, StlAbovePlane=above)
+
+
+def eval_acc_compl(base):
+    """eval_ply.m's result: [mean, median] of Ddata .* DataInMask, then of Dstl .* StlAbovePlane - products over ALL points (points outside the
+    mask / below the plane count as 0), as eval_ply.m computes them. float64."""
+    acc = np.asarray(base["Ddata"], dtype=np.float64) * np.asarray(base["DataInMask"], dtype=np.float64)
+    compl = np.asarray(base["Dstl"], dtype=np.float64) * np.asarray(base["StlAbovePlane"], dtype=np.float64)
+    return np.asarray([np.mean(acc), np.median(acc), np.mean(compl), np.median(compl)], dtype=np.float64)
+
+
+def eval_ply(cSet, DataInName, EvalName, dataPath, dst=0.2, max_dist=60.0, seed=0):
+    """eval_ply.m (getPaths' dataPath passed in): reads DataInName (PLY), dataPath/Points/stl/stl{cSet:03d}_total.ply,
+    dataPath/ObsMask/ObsMask{cSet}_10.mat (BB, Res, Margin, ObsMask) and dataPath/ObsMask/Plane{cSet}.mat (P); writes EvalName (.mat, variable
+    BaseEval, point arrays 3 x N as MATLAB holds them); returns the four numbers of eval_acc_compl."""
+    import scipy.io as sio
+    Qdata = read_ply_xyz(DataInName)
+    Qstl = read_ply_xyz(os.path.join(dataPath, "Points", "stl", "stl%03d_total.ply" % cSet))
+    m = sio.loadmat(os.path.join(dataPath, "ObsMask", "ObsMask%d_10.mat" % cSet))
+    P = sio.loadmat(os.path.join(dataPath, "ObsMask", "Plane%d.mat" % cSet))["P"]
+    base = point_compare(Qdata, Qstl, m["ObsMask"], m["BB"], m["Res"], P, dst=dst, max_dist=max_dist, seed=seed, cSet=cSet,
+                         Margin=m["Margin"] if "Margin" in m else None)
+    mat = dict(base)
+    mat.update(cSet=float(cSet), Qdata=base["Qdata"].T, Qstl=base["Qstl"].T, GroundPlane=base["GroundPlane"].reshape(4, 1))
+    if mat["Margin"] is None:
+        del mat["Margin"]
+    sio.savemat(EvalName, {"BaseEval": mat})
+    return eval_acc_compl(base)

@@ -5,6 +5,7 @@
     filter_voxels             utils/sparseCubes.py:205-243  (host-side list thresholding, unchanged semantics)
     save2ply, save_sparseCubes_2ply, save_sparseCubes, load_sparseCubes   utils/sparseCubes.py:246-410 (host file I/O:
                               binary little-endian PLY with plyfile's header, npz with the reference's keys - files cross both ways)
+    sparse_xyz                the points save_sparseCubes_2ply writes, in memory (input of evaluation.point_compare)
 
 Same names, keyword arguments, output lists and dtypes. The ray pooling, thresholding, centre crop and compaction of a
 whole batch run in one GPU call (surfacenet_amd/csrc/postpass.h); only the packed voxel lists cross PCIe. `param` is
@@ -134,11 +135,18 @@ def save_sparseCubes_2ply(vxl_mask_list, vxl_ijk_list, rgb_list, param, ply_file
     if not vxl_mask_np.shape[0] == vxl_ijk_np.shape[0] == rgb_np.shape[0]:
         raise Warning('make sure # of voxels in each cube are consistent.')
     normal_np = None if normal_list is None else np.vstack(normal_list)[vxl_mask_np]
+    save2ply(ply_filePath, sparse_xyz(vxl_mask_list, vxl_ijk_list, param), rgb_np[vxl_mask_np], normal_np)
+    return 1
+
+
+def sparse_xyz(vxl_mask_list, vxl_ijk_list, param):
+    """The (N,3) float32 points save_sparseCubes_2ply writes: xyz = ijk * resol + xyz_min of the cube for every masked voxel, cube by cube
+    (a scene's masks - reconstruct.scene_postpass - evaluated in memory, without the PLY round trip)."""
+    vxl_mask_np = np.concatenate(vxl_mask_list, axis=0)
+    vxl_ijk_np = np.vstack(vxl_ijk_list)
     cube_of = np.repeat(np.arange(len(vxl_mask_list)), [len(m) for m in vxl_mask_list])[vxl_mask_np]
     resol = np.asarray(param['resol'])[cube_of]
-    xyz_np = vxl_ijk_np[vxl_mask_np] * resol[:, None] + np.asarray(param['xyz'])[cube_of]
-    save2ply(ply_filePath, xyz_np, rgb_np[vxl_mask_np], normal_np)
-    return 1
+    return vxl_ijk_np[vxl_mask_np] * resol[:, None] + np.asarray(param['xyz'])[cube_of]
 
 
 def save_sparseCubes(filePath, prediction_list, rgb_list, vxl_ijk_list, rayPooling_votes_list, cube_ijk_np, param_np, viewPair_np):
