@@ -151,7 +151,7 @@ def forward_emulated(X, values, w=None, n_vp=1, mode="f16x3", table=None, s8_act
             E = block_exp(amax, vmax).view(O, Up // 2, 1, 1)
             back = lambda z: z.reshape(O, Up, 8)[:, :U].reshape(O, G, Tn, 8).permute(0, 1, 3, 2).reshape(O, Cp, Tn)
             return back(q(a / 2.0 ** E) * 2.0 ** E), back(q(b / 2.0 ** E) * 2.0 ** E)
-        # 1x1x1: slabs of up to 5 channel groups (tile_for), blocks = consecutive group pairs inside a slab
+        # 1x1x1: slabs of up to 5 channel groups (the plan's 1x1x1 store kernel: sn_api.hip build_plan_t, Side, CS8 = 5), blocks = consecutive group pairs inside a slab
         aq, bq = torch.zeros_like(a), torch.zeros_like(b)
         g0 = 0
         while g0 < G:

@@ -1,23 +1,24 @@
 // sn_api.hip — C ABI (include/surfacenet_hip.h) over the gfx950 kernels: context, weight folding and
-// MFMA-fragment packing, activation workspace, the layer schedule of the SurfaceNet graph
-// (nets/SurfaceNet.py:18-76), and HIP-event profiling. Build: surfacenet_amd/csrc/Makefile.
+// MFMA-fragment packing, activation workspace, the plan of the SurfaceNet graph (nets/SurfaceNet.py:18-76; build_plan: which kernel runs which
+// layer on which tensors - sn_load_weights packs from it, run_net walks it), and HIP-event profiling. Build: surfacenet_amd/csrc/Makefile.
 #include "sn_internal.h"
 
 // ------------------------------------------------------------------------------------------------
 // network description (restated from nets/SurfaceNet.py:18-76; order = weight-file order, App. B)
 // ------------------------------------------------------------------------------------------------
 enum Kind { K_CONV3, K_CONV1, K_DIL3, K_DIL1, K_UP };
-struct LayerSpec { const char *name; Kind kind; int cin, cout, act; };  // K_UP: cin = kernel size, cout = factor
+// input: the layer whose (exponent-scaled, see pack_conv) output it reads; none: conv1_1 <- CVC, merge_conv_a <- sigmoid side outputs: exponent 0
+struct LayerSpec { const char *name; Kind kind; int cin, cout, act; const char *input; };  // K_UP: cin = kernel size, cout = factor
 static const LayerSpec kSpecs[] = {
-    {"conv1_1", K_CONV3, 6, 32, 0},    {"conv1_2", K_CONV3, 32, 32, 0},   {"conv1_3", K_CONV3, 32, 32, 0},
-    {"side_op1", K_CONV1, 32, 16, 1},
-    {"conv2_1", K_CONV3, 32, 80, 0},   {"conv2_2", K_CONV3, 80, 80, 0},   {"conv2_3", K_CONV3, 80, 80, 0},
-    {"side_op2", K_CONV1, 80, 16, 1},  {"side_op2_deconv", K_UP, 3, 2, 0},
-    {"conv3_1", K_CONV3, 80, 160, 0},  {"conv3_2", K_CONV3, 160, 160, 0}, {"conv3_3", K_CONV3, 160, 160, 0},
-    {"side_op3", K_CONV1, 160, 16, 1}, {"side_op3_deconv", K_UP, 5, 4, 0},
-    {"conv4_1", K_DIL3, 160, 300, 0},  {"conv4_2", K_DIL3, 300, 300, 0},  {"conv4_3", K_DIL3, 300, 300, 0},
-    {"side_op4", K_DIL1, 300, 16, 1},  {"side_op4_deconv", K_UP, 5, 4, 0},
-    {"merge_conv_a", K_CONV3, 64, 100, 0}, {"merge_conv_b", K_CONV3, 100, 100, 0}, {"merge_conv3", K_CONV1, 100, 1, 1},
+    {"conv1_1", K_CONV3, 6, 32, 0, nullptr},       {"conv1_2", K_CONV3, 32, 32, 0, "conv1_1"},    {"conv1_3", K_CONV3, 32, 32, 0, "conv1_2"},
+    {"side_op1", K_CONV1, 32, 16, 1, "conv1_3"},
+    {"conv2_1", K_CONV3, 32, 80, 0, "conv1_3"},    {"conv2_2", K_CONV3, 80, 80, 0, "conv2_1"},    {"conv2_3", K_CONV3, 80, 80, 0, "conv2_2"},
+    {"side_op2", K_CONV1, 80, 16, 1, "conv2_3"},   {"side_op2_deconv", K_UP, 3, 2, 0, nullptr},
+    {"conv3_1", K_CONV3, 80, 160, 0, "conv2_3"},   {"conv3_2", K_CONV3, 160, 160, 0, "conv3_1"},  {"conv3_3", K_CONV3, 160, 160, 0, "conv3_2"},
+    {"side_op3", K_CONV1, 160, 16, 1, "conv3_3"},  {"side_op3_deconv", K_UP, 5, 4, 0, nullptr},
+    {"conv4_1", K_DIL3, 160, 300, 0, "conv3_3"},   {"conv4_2", K_DIL3, 300, 300, 0, "conv4_1"},   {"conv4_3", K_DIL3, 300, 300, 0, "conv4_2"},
+    {"side_op4", K_DIL1, 300, 16, 1, "conv4_3"},   {"side_op4_deconv", K_UP, 5, 4, 0, nullptr},
+    {"merge_conv_a", K_CONV3, 64, 100, 0, nullptr}, {"merge_conv_b", K_CONV3, 100, 100, 0, "merge_conv_a"}, {"merge_conv3", K_CONV1, 100, 1, 1, "merge_conv_b"},
 };
 static constexpr int kNumSpecs = sizeof(kSpecs) / sizeof(kSpecs[0]);
 static constexpr int kNetParams = 98, kAllParams = 105, kDFeature = 258, kHidden = 100;
@@ -280,13 +281,15 @@ static int pack_conv_host(PackedConv &L, const float *W_in, const float *beta, c
     return SN_OK;
 }
 
-int pack_conv(sn_ctx *c, PackedConv &L, const float *W_in, const float *beta, const float *gamma, const float *mean,
-              const float *inv_std, int nf, int nsplit, int cs8max, int split, const int *in_exp, const int *out_exp)
+int pack_conv(sn_ctx *c, PackedConv &L, const ConvEntry &e, const float *W_in, const float *beta, const float *gamma, const float *mean,
+              const float *inv_std, const int *in_exp, const int *out_exp)
 {
+    L = PackedConv();
+    L.name = e.name; L.cin = e.cin; L.cout = e.cout; L.act = e.act; L.ks = e.k.ks; L.dil = e.k.dil; L.k2d = e.k.k2d; L.bridge = e.bridge;
     std::vector<_Float16> h;
     std::vector<float> sc, sh;
     int rc;
-    if ((rc = pack_conv_host(L, W_in, beta, gamma, mean, inv_std, nf, nsplit, cs8max, split, in_exp, out_exp, h, sc, sh)) != SN_OK) return rc;
+    if ((rc = pack_conv_host(L, W_in, beta, gamma, mean, inv_std, e.k.nf, e.k.nsplit(e.cout), e.k.cs8max, e.k.split, in_exp, out_exp, h, sc, sh)) != SN_OK) return rc;
     if ((rc = dev_alloc(c, &L.wpack, h.size() + 8192)) != SN_OK) return rc;
     if ((rc = dev_alloc(c, &L.scale, sc.size())) != SN_OK) return rc;
     if ((rc = dev_alloc(c, &L.shift, sh.size())) != SN_OK) return rc;
@@ -319,19 +322,6 @@ static int pack_side_frag(sn_ctx *c, PackedConv &S, int producer_nf)
     return SN_OK;
 }
 
-struct TileChoice { int nf, nsplit, cs8max; };
-// Must agree with the kernel instantiations in run_net_t<SPLIT> (launch_conv verifies it).
-static TileChoice tile_for(const LayerSpec &sp, int split)
-{
-    if (sp.kind == K_CONV1 || sp.kind == K_DIL1) return {1, 1, 5};
-    if (sp.kind == K_DIL3) return {5, 4, 1};        // conv4: dilation-2 halo is big -> 8-channel slabs; 4 x 80 output channels
-    if (sp.cout == 32) return {2, 1, 1};
-    if (sp.cout == 80) return {5, 1, 1};
-    if (sp.cout == 160) return {5, 2, 1};
-    // cout 100 (merge_conv_a/b). f16 mode has LDS room for two 8-channel groups per slab in merge_conv_a (-18 % there)
-    return {7, 1, (split == 0 && sp.cin == 64) ? 2 : 1};
-}
-
 template <int SPLIT>
 static int launch_pool(sn_ctx *c, const char *tag, Act in, Act out, int B, int D, int C)
 {
@@ -359,121 +349,140 @@ static int launch_up3(sn_ctx *c, Act s2, Act s3, Act s4, Act cat, int B, int Do,
     return SN_OK;
 }
 
-// x0 [S][s^3][8] fp16 -> unf [S][s^3] fp32 surface probabilities (nets/SurfaceNet.py:18-76).
-// Kernel configurations <KS, DIL, MF, NF, EPI, SPLIT, CS8, PCH> per layer family; LDS budgets in DESIGN.md.
+// ------------------------------------------------------------------------------------------------
+// the plan: which kernel runs which layer, on which tensors - the one place that says so
+// ------------------------------------------------------------------------------------------------
+// The activation workspace (ensure_workspace). T_A3_HLC / T_A3_HC: conv3_3's output with its third plane of code slots, as its writer / as conv4_1 sees it.
+enum Tensor : unsigned char { T_NONE, T_X0, T_A1, T_B1, T_CAT, T_P1, T_A2, T_B2, T_S2, T_P2, T_A3, T_B3, T_A4, T_B4, T_S3, T_S4, T_MA, T_A3_HLC, T_A3_HC, T_COUNT };
+// static premultipliers of the 6-bit code planes (mx_format.h): the concat buffer holds sigmoid outputs, everything else ReLU(BN(.))
+static const TensorSpec kTensors[T_COUNT] = {
+    {nullptr, 0, 0, MX_ACT, 0},      {&sn_ctx::x0, 0, 8, MX_X0, 0},    {&sn_ctx::a1, 0, 32, MX_ACT, 0},  {&sn_ctx::b1, 0, 32, MX_ACT, 0},  {&sn_ctx::cat, 0, 64, MX_CAT, 0},
+    {&sn_ctx::p1, 1, 32, MX_ACT, 0}, {&sn_ctx::a2, 1, 80, MX_ACT, 0},  {&sn_ctx::b2, 1, 80, MX_ACT, 0},  {&sn_ctx::s2, 1, 16, MX_ACT, 0},  {&sn_ctx::p2, 2, 80, MX_ACT, 0},
+    {&sn_ctx::a3, 2, 160, MX_ACT, 0}, {&sn_ctx::b3, 2, 160, MX_ACT, 0}, {&sn_ctx::a4, 2, 304, MX_ACT, 0}, {&sn_ctx::b4, 2, 304, MX_ACT, 0}, {&sn_ctx::s3, 2, 16, MX_ACT, 0},
+    {&sn_ctx::s4, 2, 16, MX_ACT, 0}, {&sn_ctx::ma, 0, 104, MX_ACT, 0}, {&sn_ctx::a3, 2, 160, MX_ACT, 1}, {&sn_ctx::a3, 2, 160, MX_ACT, 2},
+};
+
+// x0 [S][s^3][8] fp16 -> unf [S][s^3] fp32 surface probabilities (nets/SurfaceNet.py:18-76), as a function of the state that selects kernels: the operand
+// mode SP = sn_ctx::split, tail_m8, c4_m8 and the process-wide A/B switches SN_NO_EPI_FUSION / SN_NO_BRIDGE.
+// Kernel configurations <KS, DIL, MF, NF, EPI, SPLIT, CS8, PCH, NW, PADV[, K2D, OSPLIT]> per layer family; LDS budgets in DESIGN.md.
 template <int SP>
-static int run_net_t(sn_ctx *c, int S, float *unf)
+static NetPlan build_plan_t(int tail_m8, int c4_m8)
 {
-    const int s = c->s, D2 = s / 2, D3 = s / 4;
-    const long long M = c->max_samples, v1 = (long long)s * s * s, v2 = v1 / 8, v3 = v1 / 64;
-    auto A = [&](_Float16 *p, long long vox, int ch) { return Act{p, SP ? M * vox * ch : 0}; };
-    const Act x0 = A(c->x0, v1, 8), a1 = A(c->a1, v1, 32), b1 = A(c->b1, v1, 32), cat = A(c->cat, v1, 64), p1 = A(c->p1, v2, 32),
-              a2 = A(c->a2, v2, 80), b2 = A(c->b2, v2, 80), s2 = A(c->s2, v2, 16), p2 = A(c->p2, v3, 80), a3 = A(c->a3, v3, 160),
-              b3 = A(c->b3, v3, 160), a4 = A(c->a4, v3, 304), b4 = A(c->b4, v3, 304), s3 = A(c->s3, v3, 16), s4 = A(c->s4, v3, 16),
-              ma = A(c->ma, v1, 104), none = Act{nullptr, 0};
-    int rc;
-#define RUN(x) do { if ((rc = (x)) != SN_OK) return rc; } while (0)
-// conv1_x: 8 voxel fragments per wave = 16x8x8 tiles (half the weight staging and weight-fragment reads per MFMA of an 8x8x8 tile: -6..7 %, A/B r3l),
-// 4-chunk weight pieces - the LDS holds no more
-#define CONV1 3, 1, 8, 2, EPI_STORE, SP, 1, (SP == 2 ? 2 : 4), 8, 0
-#define SIDE  1, 1, 4, 1, EPI_STORE, SP, 5, 2, 4, 0
-// conv2_x / conv3_x: the ping-pong loop needs >= 2 chunks per weight piece, which fits the LDS only with 8-channel slabs (4-chunk pieces: a 7-chunk slab = pieces of 4 + 3)
-#define C23_CS8 1
-#define C23_PCH (SP == 2 ? 2 : 4)
-#define CONV2 3, 1, 4, 5, EPI_STORE, SP, C23_CS8, C23_PCH, 8, 0
-#define CONV3 3, 1, 4, 5, EPI_STORE, SP, C23_CS8, C23_PCH, 8, 0
-#define CONV4 3, 2, 4, 5, EPI_STORE, SP, 1, 2, 8, 0
-// f16 mode (one activation plane): 4-chunk weight pieces halve the barriers; merge_conv_a also takes 16-channel slabs
-#define MERGA 3, 1, 4, 7, EPI_STORE, SP, (SP == 0 ? 2 : 1), (SP == 0 ? 4 : 2), 8, 0
-#define MERGB 3, 1, 4, 7, EPI_FINAL, SP, 1, (SP == 0 ? 4 : 2), 8, 0
-    auto &L = c->conv;
-    RUN((launch_conv<CONV1>(c, L["conv1_1"], x0, 8, a1, 32, 0, 32, nullptr, S, s)));
-    RUN((launch_conv<CONV1>(c, L["conv1_2"], a1, 32, b1, 32, 0, 32, nullptr, S, s)));
+    // conv1_x: 8 voxel fragments per wave = 16x8x8 tiles (half the weight staging and weight-fragment reads per MFMA of an 8x8x8 tile: -6..7 %, A/B r3l),
+    // 4-chunk weight pieces - the LDS holds no more
+    constexpr int PCH = SP == 2 ? 2 : 4;
+    using Conv1 = ConvKernel<3, 1, 8, 2, EPI_STORE, SP, 1, PCH, 8, 0>;
+    using Side = ConvKernel<1, 1, 4, 1, EPI_STORE, SP, 5, 2, 4, 0>;
+    // conv2_x / conv3_x: the ping-pong loop needs >= 2 chunks per weight piece, which fits the LDS only with 8-channel slabs (4-chunk pieces: a 7-chunk slab = pieces of 4 + 3)
+    using Conv23 = ConvKernel<3, 1, 4, 5, EPI_STORE, SP, 1, PCH, 8, 0>;
+    // conv4: dilation-2 halo is big -> 8-channel slabs; 4 x 80 output channels
+    using Conv4 = ConvKernel<3, 2, 4, 5, EPI_STORE, SP, 1, 2, 8, 0>;
+    static const bool unfused = sn_ab_switch("SN_NO_EPI_FUSION") != nullptr;      // A/B measurements: the three separate launches
+    static const bool no_bridge = sn_ab_switch("SN_NO_BRIDGE") != nullptr;        // (A/B switch)
+    NetPlan p{SP, tail_m8, c4_m8, {}, {kTensors, kTensors + T_COUNT}, launch_pool<SP>, launch_up3<SP>};
+    // the layers whose kernel depends on more than the operand mode. merge_conv_a / merge_conv_b, f16 mode (one activation plane): 4-chunk weight pieces halve the
+    // barriers; merge_conv_a also has LDS room for two 8-channel groups per slab (-18 % there)
+    ConvGeom conv1_3 = ConvKernel<3, 1, 4, 2, EPI_SIDEPOOL, SP, 1, (SP == 2 ? 2 : 7), 8, 0>::geom, side_op1 = Side::geom, conv3_3 = Conv23::geom,
+             conv4_1 = Conv4::geom, conv4_2 = conv4_1, conv4_3 = conv4_1,
+             merge_a = ConvKernel<3, 1, 4, 7, EPI_STORE, SP, (SP == 0 ? 2 : 1), (SP == 0 ? 4 : 2), 8, 0>::geom,
+             merge_b = ConvKernel<3, 1, 4, 7, EPI_FINAL, SP, 1, (SP == 0 ? 4 : 2), 8, 0>::geom;
+    Tensor conv3_3_out = T_A3, conv4_1_in = T_A3;
+    if constexpr (SP == 1) {
+        // f16x3 default (tail_m8 == 2): merge_conv_a AND merge_conv_b compute in f16m8 (main term f16, both correction terms on one MX-fp8
+        // MFMA), so everything that writes the concat buffer stores it in the f16m8 format (OSPLIT = 2); upstream stays three-fp16-MFMA.
+        if (tail_m8 >= 2) {
+            conv1_3 = ConvKernel<3, 1, 8, 2, EPI_SIDEPOOL, 1, 1, 4, 8, 0, 0, 2>::geom;      // (f16x3: 16x8x8 tiles as conv1_1 / conv1_2)
+            side_op1 = ConvKernel<1, 1, 4, 1, EPI_STORE, 1, 5, 2, 4, 0, 0, 2>::geom;
+            p.up3 = launch_up3<1, 2>;
+            // 4-wave workgroups, one wave per SIMD with 8 x 7 fragment tiles and the accumulators in AGPRs (conv3d_mfma.h, the one-wave-per-SIMD loop)
+            merge_a = ConvKernel<3, 1, 8, 7, EPI_STORE, 2, 1, 2, 4, 0>::geom;
+            merge_b = ConvKernel<3, 1, 8, 7, EPI_FINAL, 2, 1, 2, 4, 0>::geom;
+        }
+        // Round 5, default mode: the dilated chain conv4_1 .. conv4_3 in the f16m8e arithmetic - the main term on the f16 MFMA, both correction terms on ONE fp8 e4m3
+        // MX MFMA per 64 k (2 MFMA units per product instead of 3) - on the one-wave-per-SIMD loop. fp8, not the merge layers' 6-bit codes: those ran 20 % faster
+        // still but their static range cannot hold the conv4 chain's data-dependent outliers (3.6e-4 .. 4.3e-4 on scene cubes; profiles/r5/README.md). conv3_3's
+        // output has readers of both kinds - side_op3 reads hi + lo planes, conv4_1 hi + code slots - and is stored with three planes; conv4_1 / conv4_2 store
+        // hi + codes; conv4_3 stores hi + lo again (side_op4).
+        if (c4_m8) {
+            conv4_1 = conv4_2 = ConvKernel<3, 2, 8, 5, EPI_STORE, 3, 1, 2, 4, 0>::geom;
+            conv4_3 = ConvKernel<3, 2, 8, 5, EPI_STORE, 3, 1, 2, 4, 0, 0, 1>::geom;
+            if (c4_m8 == 2) conv4_1 = ConvKernel<3, 2, 4, 5, EPI_STORE, 1, 1, 2, 8, 0, 0, 3>::geom;      // (A/B: conv4_1 stays on three fp16 MFMAs and stores hi + codes for conv4_2)
+            else { conv3_3 = ConvKernel<3, 1, 4, 5, EPI_STORE, 1, 1, 4, 8, 0, 0, 4>::geom; conv3_3_out = T_A3_HLC; conv4_1_in = T_A3_HC; }
+            for (Tensor t : {T_A3, T_A3_HLC, T_A3_HC, T_A4, T_B4}) p.tens[t].e8 = MX_C4;      // the chain's buffers carry the fp8 planes' exponent
+        }
+    }
+    auto add = [&](const char *name, ConvGeom k, Tensor in, Tensor out, Tensor pool_out = T_NONE, const char *pool_tag = nullptr) -> ConvEntry & {
+        // bridge chunks: 27 K-chunks per four slabs instead of 28 (f16x3), 27 weight pieces per eight slabs instead of 32 (f16m8): pack_conv_host decides
+        ConvEntry e{name, 0, 0, 0, k, (k.has_bridge && !no_bridge) ? 1 : 0, in, out, pool_out, pool_tag};
+        for (const LayerSpec &sp : kSpecs) if (!strcmp(sp.name, name)) { e.cin = sp.cin; e.cout = sp.cout; e.act = sp.act; }
+        p.conv.push_back(e);
+        return p.conv.back();
+    };
+    add("conv1_1", Conv1::geom, T_X0, T_A1);
+    add("conv1_2", Conv1::geom, T_A1, T_B1);
     // conv1_3 with its two consumers in the epilogue: side_op1 (1x1x1 + BN + sigmoid -> concat channels 0..15) and pool1; the 32-channel
     // full-resolution tensor itself is never written (nets/SurfaceNet.py:35-38).
-    // f16x3 default (tail_m8 == 2): merge_conv_a AND merge_conv_b compute in f16m8 (main term f16, both correction terms on one MX-fp8
-    // MFMA), so everything that writes the concat buffer stores it in the f16m8 format (OSPLIT = 2); upstream stays three-fp16-MFMA.
-    const bool cat_m8 = SP == 1 && c->tail_m8 >= 2;
-    static const bool unfused = sn_ab_switch("SN_NO_EPI_FUSION") != nullptr;      // A/B measurements: the three separate launches
-    if (!unfused) {
-        const SideFuse sf1{&L["side_op1"], cat, 64, 0, p1, 32};
-        // (f16x3: 16x8x8 tiles as conv1_1 / conv1_2)
-        if (cat_m8) { if constexpr (SP == 1) RUN((launch_conv<3, 1, 8, 2, EPI_SIDEPOOL, 1, 1, 4, 8, 0, 0, 2>(c, L["conv1_3"], b1, 32, none, 0, 0, 32, nullptr, S, s, 0, &sf1))); }
-        else RUN((launch_conv<3, 1, 4, 2, EPI_SIDEPOOL, SP, 1, (SP == 2 ? 2 : 7), 8, 0>(c, L["conv1_3"], b1, 32, none, 0, 0, 32, nullptr, S, s, 0, &sf1)));
-    } else {
-        RUN((launch_conv<CONV1>(c, L["conv1_3"], b1, 32, a1, 32, 0, 32, nullptr, S, s)));
-        if (cat_m8) { if constexpr (SP == 1) RUN((launch_conv<1, 1, 4, 1, EPI_STORE, 1, 5, 2, 4, 0, 0, 2>(c, L["side_op1"], a1, 32, cat, 64, 0, 16, nullptr, S, s))); }
-        else RUN((launch_conv<SIDE>(c, L["side_op1"], a1, 32, cat, 64, 0, 16, nullptr, S, s)));
-        RUN((launch_pool<SP>(c, "pool1", a1, p1, S, s, 32)));
-    }
-    RUN((launch_conv<CONV2>(c, L["conv2_1"], p1, 32, a2, 80, 0, 80, nullptr, S, D2)));
-    RUN((launch_conv<CONV2>(c, L["conv2_2"], a2, 80, b2, 80, 0, 80, nullptr, S, D2)));
-    if (!unfused) {
-        // conv2_3 likewise: side_op2 (-> the 16-channel half-resolution side map) and pool2 in its epilogue (nets/SurfaceNet.py:44-47)
-        const SideFuse sf2{&L["side_op2"], s2, 16, 0, p2, 80};
-        RUN((launch_conv<3, 1, 4, 5, EPI_SIDEPOOL, SP, C23_CS8, C23_PCH, 8, 0>(c, L["conv2_3"], b2, 80, none, 0, 0, 80, nullptr, S, D2, 0, &sf2)));
-    } else {
-        RUN((launch_conv<CONV2>(c, L["conv2_3"], b2, 80, a2, 80, 0, 80, nullptr, S, D2)));
-        RUN((launch_conv<SIDE>(c, L["side_op2"], a2, 80, s2, 16, 0, 16, nullptr, S, D2)));
-        RUN((launch_pool<SP>(c, "pool2", a2, p2, S, D2, 80)));
-    }
-    RUN((launch_conv<CONV3>(c, L["conv3_1"], p2, 80, a3, 160, 0, 160, nullptr, S, D3)));
-    RUN((launch_conv<CONV3>(c, L["conv3_2"], a3, 160, b3, 160, 0, 160, nullptr, S, D3)));
-    // Round 5, default mode: the dilated chain conv4_1 .. conv4_3 in the f16m8e arithmetic - the main term on the f16 MFMA, both correction terms on ONE fp8 e4m3
-    // MX MFMA per 64 k (2 MFMA units per product instead of 3) - on the one-wave-per-SIMD loop. fp8, not the merge layers' 6-bit codes: those ran 20 % faster
-    // still but their static range cannot hold the conv4 chain's data-dependent outliers (3.6e-4 .. 4.3e-4 on scene cubes; profiles/r5/README.md). conv3_3's
-    // output has readers of both kinds - side_op3 reads hi + lo planes, conv4_1 hi + code slots - and is stored with three planes; conv4_1 / conv4_2 store
-    // hi + codes; conv4_3 stores hi + lo again (side_op4).
-    bool c4_done = false;
-    if constexpr (SP == 1) {
-        if (c->c4_m8 == 2) {      // (A/B: conv4_1 stays on three fp16 MFMAs and stores hi + codes for conv4_2)
-            RUN((launch_conv<CONV3>(c, L["conv3_3"], b3, 160, a3, 160, 0, 160, nullptr, S, D3)));
-            RUN((launch_conv<SIDE>(c, L["side_op3"], a3, 160, s3, 16, 0, 16, nullptr, S, D3)));
-            RUN((launch_conv<3, 2, 4, 5, EPI_STORE, 1, 1, 2, 8, 0, 0, 3>(c, L["conv4_1"], a3, 160, a4, 304, 0, 304, nullptr, S, D3)));
-            RUN((launch_conv<3, 2, 8, 5, EPI_STORE, 3, 1, 2, 4, 0>(c, L["conv4_2"], a4, 304, b4, 304, 0, 304, nullptr, S, D3)));
-            RUN((launch_conv<3, 2, 8, 5, EPI_STORE, 3, 1, 2, 4, 0, 0, 1>(c, L["conv4_3"], b4, 304, a4, 304, 0, 304, nullptr, S, D3)));
-            c4_done = true;
-        } else
-        if (c->c4_m8) {
-            const Act a3o{a3.p, a3.lo, (long long)(c->a3c - a3.p)}, a3i{a3.p, (long long)(c->a3c - a3.p)};
-            RUN((launch_conv<3, 1, 4, 5, EPI_STORE, 1, C23_CS8, C23_PCH, 8, 0, 0, 4>(c, L["conv3_3"], b3, 160, a3o, 160, 0, 160, nullptr, S, D3)));
-            RUN((launch_conv<SIDE>(c, L["side_op3"], a3, 160, s3, 16, 0, 16, nullptr, S, D3)));
-            RUN((launch_conv<3, 2, 8, 5, EPI_STORE, 3, 1, 2, 4, 0>(c, L["conv4_1"], a3i, 160, a4, 304, 0, 304, nullptr, S, D3)));
-            RUN((launch_conv<3, 2, 8, 5, EPI_STORE, 3, 1, 2, 4, 0>(c, L["conv4_2"], a4, 304, b4, 304, 0, 304, nullptr, S, D3)));
-            RUN((launch_conv<3, 2, 8, 5, EPI_STORE, 3, 1, 2, 4, 0, 0, 1>(c, L["conv4_3"], b4, 304, a4, 304, 0, 304, nullptr, S, D3)));
-            c4_done = true;
-        }
-    }
-    if (!c4_done) {
-    RUN((launch_conv<CONV3>(c, L["conv3_3"], b3, 160, a3, 160, 0, 160, nullptr, S, D3)));
-    RUN((launch_conv<SIDE>(c, L["side_op3"], a3, 160, s3, 16, 0, 16, nullptr, S, D3)));
-    RUN((launch_conv<CONV4>(c, L["conv4_1"], a3, 160, a4, 304, 0, 304, nullptr, S, D3)));
-    RUN((launch_conv<CONV4>(c, L["conv4_2"], a4, 304, b4, 304, 0, 304, nullptr, S, D3)));
-    RUN((launch_conv<CONV4>(c, L["conv4_3"], b4, 304, a4, 304, 0, 304, nullptr, S, D3)));
-    }
-    RUN((launch_conv<SIDE>(c, L["side_op4"], a4, 304, s4, 16, 0, 16, nullptr, S, D3)));
-    if (cat_m8) { if constexpr (SP == 1) RUN((launch_up3<1, 2>(c, s2, s3, s4, cat, S, s, 64))); }
-    else RUN((launch_up3<SP>(c, s2, s3, s4, cat, S, s, 64)));
-    if constexpr (SP == 1) {
-        if (c->tail_m8 >= 2) {
-            // 4-wave workgroups, one wave per SIMD with 8 x 7 fragment tiles and the accumulators in AGPRs (conv3d_mfma.h, the one-wave-per-SIMD loop)
-            RUN((launch_conv<3, 1, 8, 7, EPI_STORE, 2, 1, 2, 4, 0>(c, L["merge_conv_a"], cat, 64, ma, 104, 0, 104, nullptr, S, s)));
-            RUN((launch_conv<3, 1, 8, 7, EPI_FINAL, 2, 1, 2, 4, 0>(c, L["merge_conv_b"], ma, 104, none, 0, 0, 0, unf, S, s)));
-            return SN_OK;
-        }
-    }
-    RUN((launch_conv<MERGA>(c, L["merge_conv_a"], cat, 64, ma, 104, 0, 104, nullptr, S, s)));
-    RUN((launch_conv<MERGB>(c, L["merge_conv_b"], ma, 104, none, 0, 0, 0, unf, S, s)));
-#undef RUN
-    return SN_OK;
+    add("conv1_3", unfused ? Conv1::geom : conv1_3, T_B1, unfused ? T_A1 : T_NONE);
+    add("side_op1", side_op1, T_A1, T_CAT, T_P1, "pool1");
+    add("conv2_1", Conv23::geom, T_P1, T_A2);
+    add("conv2_2", Conv23::geom, T_A2, T_B2);
+    // conv2_3 likewise: side_op2 (-> the 16-channel half-resolution side map) and pool2 in its epilogue (nets/SurfaceNet.py:44-47)
+    add("conv2_3", unfused ? Conv23::geom : ConvKernel<3, 1, 4, 5, EPI_SIDEPOOL, SP, 1, PCH, 8, 0>::geom, T_B2, unfused ? T_A2 : T_NONE);
+    add("side_op2", Side::geom, T_A2, T_S2, T_P2, "pool2");
+    add("conv3_1", Conv23::geom, T_P2, T_A3);
+    add("conv3_2", Conv23::geom, T_A3, T_B3);
+    add("conv3_3", conv3_3, T_B3, conv3_3_out);
+    add("side_op3", Side::geom, T_A3, T_S3);
+    add("conv4_1", conv4_1, conv4_1_in, T_A4);
+    add("conv4_2", conv4_2, T_A4, T_B4);
+    add("conv4_3", conv4_3, T_B4, T_A4);
+    add("side_op4", Side::geom, T_A4, T_S4).up3 = true;
+    add("merge_conv_a", merge_a, T_CAT, T_MA);
+    add("merge_conv_b", merge_b, T_MA, T_NONE);
+    return p;
+}
+
+static NetPlan build_plan(int split, int tail_m8, int c4_m8)
+{
+    return split == 2 ? build_plan_t<2>(tail_m8, c4_m8) : (split == 1 ? build_plan_t<1>(tail_m8, c4_m8) : build_plan_t<0>(tail_m8, c4_m8));
 }
 
 static int run_net(sn_ctx *c, int S, float *unf)
 {
     c->last_run_samples = 0;
-    const int rc = c->split == 2 ? run_net_t<2>(c, S, unf) : (c->split == 1 ? run_net_t<1>(c, S, unf) : run_net_t<0>(c, S, unf));
-    if (rc == SN_OK) c->last_run_samples = S;      // (what sn_calibrate_dev may scan)
-    return rc;
+    const NetPlan &p = c->plan;
+    if (p.split != c->split || p.tail_m8 != c->tail_m8 || p.c4_m8 != c->c4_m8 || c->conv.size() != p.conv.size())
+        return fail(SN_ERR_STATE, "the weights are packed for a different kernel configuration");
+    const long long M = c->max_samples, v1 = (long long)c->s * c->s * c->s;
+    auto A = [&](int id) {
+        const TensorSpec &t = p.tens[id];
+        Act a{t.buf ? c->*t.buf : nullptr, c->split ? M * (v1 >> (3 * t.level)) * t.ch : 0, 0, t.e8};      // (T_NONE: no buffer, no channels)
+        if (t.code == 1) a.code = c->a3c - a.p;
+        if (t.code == 2) a.lo = c->a3c - a.p;
+        return a;
+    };
+    auto cs = [&](int id) { return p.tens[id].ch; };
+    int rc;
+    for (size_t i = 0; i < p.conv.size(); ++i) {
+        const ConvEntry &e = p.conv[i];
+        const int D = c->s >> p.tens[e.in].level;
+        if (e.k.epi == EPI_SIDEPOOL) {      // the entry after it, a 1x1x1 layer, and that entry's pooling run in this one's epilogue
+            if (i + 1 >= p.conv.size()) return fail(SN_ERR_STATE, "%s: a fused epilogue without the layer it runs", e.name);
+            const ConvEntry &sd = p.conv[i + 1];
+            const SideFuse sf{&c->conv[i + 1], A(sd.out), cs(sd.out), 0, A(sd.pool_out), cs(sd.pool_out)};
+            if ((rc = e.k.launch(c, c->conv[i], A(e.in), cs(e.in), A(T_NONE), 0, 0, e.cout, nullptr, S, D, 0, &sf)) != SN_OK) return rc;
+            ++i;
+            continue;
+        }
+        const bool fin = e.k.epi == EPI_FINAL;      // merge_conv_b: no fp16 output, the fp32 probabilities instead
+        rc = e.k.launch(c, c->conv[i], A(e.in), cs(e.in), A(e.out), cs(e.out), 0, fin ? 0 : round_up(e.cout, 8), fin ? unf : nullptr,
+                        S, D, 0, nullptr);
+        if (rc != SN_OK) return rc;
+        if (e.pool_tag && (rc = p.pool(c, e.pool_tag, A(e.in), A(e.pool_out), S, D, cs(e.in))) != SN_OK) return rc;
+        if (e.up3 && (rc = p.up3(c, A(T_S2), A(T_S3), A(T_S4), A(T_CAT), S, c->s, cs(T_CAT))) != SN_OK) return rc;
+    }
+    c->last_run_samples = S;      // (what sn_calibrate_dev may scan)
+    return SN_OK;
 }
 
 static int launch_fuse(sn_ctx *c, const float *unf, const float *w_dev, float *fused, int n, int n_vp)
@@ -552,20 +561,17 @@ static int ensure_workspace(sn_ctx *c)
     for (void *p : c->ws_owned) dev_free_owned(c, p);
     c->ws_owned.clear();
     const size_t S = (size_t)c->max_samples, s = (size_t)c->s, npl = c->split ? 2 : 1;
-    const size_t v1 = s * s * s, v2 = v1 / 8, v3 = v1 / 64;
+    const size_t v1 = s * s * s, v3 = v1 / 64;
     int rc;
-#define AL(p, n) do { if ((rc = dev_alloc(c, &c->p, (n) * npl)) != SN_OK) return rc; c->ws_owned.push_back(c->p); } while (0)
-    AL(x0, S * v1 * 8); AL(a1, S * v1 * 32); AL(b1, S * v1 * 32); AL(cat, S * v1 * 64);
-    AL(p1, S * v2 * 32); AL(a2, S * v2 * 80); AL(b2, S * v2 * 80); AL(s2, S * v2 * 16);
-    AL(p2, S * v3 * 80); AL(a3, S * v3 * 160); AL(b3, S * v3 * 160); AL(a4, S * v3 * 304); AL(b4, S * v3 * 304);
-    AL(s3, S * v3 * 16); AL(s4, S * v3 * 16);
-    AL(ma, S * v1 * 104);
-#undef AL
+    for (int t = T_X0; t <= T_MA; ++t) {      // one buffer per tensor of the plan's table: [samples][extent^3][channel stride] per plane
+        _Float16 *&p = c->*kTensors[t].buf;
+        if ((rc = dev_alloc(c, &p, S * (v1 >> (3 * kTensors[t].level)) * kTensors[t].ch * npl)) != SN_OK) return rc;
+        c->ws_owned.push_back(p);
+    }
     if (c->split == 1) {      // default mode: the fp8 code plane of conv3_3's output (read by conv4_1; side_op3 reads the hi / lo planes)
         if ((rc = dev_alloc(c, &c->a3c, (size_t)(S * v3 * 160))) != SN_OK) return rc;
         c->ws_owned.push_back(c->a3c);
     }
-
     c->ws_ready = true; c->ws_split = c->split;
     return SN_OK;
 }
@@ -575,7 +581,7 @@ sn_ctx *sn_create(int device_id, int cube_D, int max_samples)
     if (cube_D < 8 || cube_D % 4 != 0 || cube_D > 96) { fail(SN_ERR_ARG, "cube_D must be a multiple of 4 in [8,96], got %d (the reference uses 32 and 64, params.py:65)", cube_D); return nullptr; }
     {
         // the conv kernel's halo addressing needs, per layer extent n (cube_D, /2, /4) and halo radius R: n <= 8, n % 8 == 0 or n % 8 >= R
-        // (launch_conv checks it per launch; refuse here what would fail there: the dilated layers, R = 2, at extent cube_D/4)
+        // (ConvKernel::launch checks it per launch; refuse here what would fail there: the dilated layers, R = 2, at extent cube_D/4)
         const int n4 = cube_D / 4;
         if (n4 > 8 && n4 % 8 == 1) { fail(SN_ERR_ARG, "cube_D = %d is not supported (cube_D/4 = %d leaves a 1-voxel partial tile under the dilation-2 layers)", cube_D, n4); return nullptr; }
     }
@@ -618,6 +624,7 @@ static void reset_mx_exponents(sn_ctx *c)
     }
 }
 
+// (This and sn_set_conv4_fp8 touch host fields only - no device, no stream: sn_debug_plan runs them on a context that was never created.)
 int sn_set_precision(sn_ctx *c, int mode)
 {
     if (!c) return fail(SN_ERR_ARG, "null context");
@@ -628,7 +635,7 @@ int sn_set_precision(sn_ctx *c, int mode)
     c->split = mode == SN_PRECISION_F16X3_PURE ? 1 : mode;
     c->tail_m8 = mode == SN_PRECISION_F16X3 ? 2 : 0;
     c->last_run_samples = 0;
-    c->c4_m8 = mode == SN_PRECISION_F16X3 ? 1 : 0;                                                  // conv4_1 .. conv4_3 on the fp8 MX step (run_net_t)
+    c->c4_m8 = mode == SN_PRECISION_F16X3 ? 1 : 0;                                                  // conv4_1 .. conv4_3 on the fp8 MX step (build_plan_t)
     if (c->c4_m8 && sn_ab_switch("SN_C4_M8")) c->c4_m8 = std::max(0, std::min(2, atoi(sn_ab_switch("SN_C4_M8"))));       // A/B measurements only (test-only twin)
     if (mode == SN_PRECISION_F16X3 && sn_ab_switch("SN_M8_TAIL")) c->tail_m8 = atoi(sn_ab_switch("SN_M8_TAIL")) >= 2 ? 2 : 0;   // A/B measurements only (0 = f16x3p's arithmetic)
     if (c->tail_m8 < 2) c->c4_m8 = 0;
@@ -782,19 +789,15 @@ int sn_load_weights(sn_ctx *c, const float *blob, size_t n_floats, const sn_para
     { int rcw = ensure_workspace(c); if (rcw != SN_OK) return rcw; }
     reset_mx_exponents(c);      // (a calibration belongs to the weights it was measured with)
     // free previously loaded weights
-    for (auto &kv : c->conv) { dev_free_owned(c, kv.second.wpack); dev_free_owned(c, kv.second.scale); dev_free_owned(c, kv.second.shift); dev_free_owned(c, kv.second.side_frag); }
-    c->conv.clear();
+    for (PackedConv &L : c->conv) { dev_free_owned(c, L.wpack); dev_free_owned(c, L.scale); dev_free_owned(c, L.shift); dev_free_owned(c, L.side_frag); }
+    c->plan = build_plan(c->split, c->tail_m8, c->c4_m8);
+    c->conv.assign(c->plan.conv.size(), PackedConv());
     c->have_weights = false;
     c->last_run_samples = 0;
 
     // per-channel output exponents of the ReLU layers (see pack_conv): the stored activation is y * 2^e with e chosen from the
     // layer's own BatchNorm so that its typical magnitude (|gamma| + |beta|: z ~ N(beta, gamma^2) under true statistics) is O(1)
     std::map<std::string, std::vector<int>> out_exps;
-    static const std::map<std::string, std::string> kInputOf = {
-        {"conv1_2", "conv1_1"}, {"conv1_3", "conv1_2"}, {"side_op1", "conv1_3"}, {"conv2_1", "conv1_3"}, {"conv2_2", "conv2_1"},
-        {"conv2_3", "conv2_2"}, {"side_op2", "conv2_3"}, {"conv3_1", "conv2_3"}, {"conv3_2", "conv3_1"}, {"conv3_3", "conv3_2"},
-        {"side_op3", "conv3_3"}, {"conv4_1", "conv3_3"}, {"conv4_2", "conv4_1"}, {"conv4_3", "conv4_2"}, {"side_op4", "conv4_3"},
-        {"merge_conv_b", "merge_conv_a"}, {"merge_conv3", "merge_conv_b"}};     // conv1_1 <- CVC, merge_conv_a <- sigmoid side outputs: exponent 0
     int pi = 0, rc;
     for (int li = 0; li < kNumSpecs; ++li) {
         const LayerSpec &sp = kSpecs[li];
@@ -833,11 +836,7 @@ int sn_load_weights(sn_ctx *c, const float *blob, size_t n_floats, const sn_para
                     for (int t = 0; t < ntap; ++t) Wt[((size_t)o * sp.cin + ci) * ntap + t] = W[((size_t)ci * sp.cout + o) * ntap + t];
             W = Wt.data();
         }
-        const int *in_exp = nullptr;
-        {
-            auto src = kInputOf.find(sp.name);
-            if (src != kInputOf.end()) in_exp = out_exps.at(src->second).data();
-        }
+        const int *in_exp = sp.input ? out_exps.at(sp.input).data() : nullptr;
         if (strcmp(sp.name, "merge_conv3") == 0) {
             // fused into merge_conv_b's epilogue in fp32
             std::vector<float> w3(7 * 16 + 16, 0.f);
@@ -852,11 +851,12 @@ int sn_load_weights(sn_ctx *c, const float *blob, size_t n_floats, const sn_para
             if (!fin) return fail(SN_ERR_ARG, "merge_conv3: non-finite weight or folded BatchNorm scale / shift");
             continue;
         }
-        PackedConv L;
-        L.name = sp.name; L.cin = sp.cin; L.cout = sp.cout; L.ks = k; L.dil = (sp.kind == K_DIL3) ? 2 : 1; L.act = sp.act;
-        const int lsplit = (c->split == 1 && c->tail_m8 >= 2 && (L.name == "merge_conv_b" || L.name == "merge_conv_a")) ? 2 :
-                           ((c->split == 1 && c->c4_m8 && sp.kind == K_DIL3 && !(c->c4_m8 == 2 && L.name == "conv4_1")) ? 3 : c->split);   // see run_net_t
-        const TileChoice tc = tile_for(sp, lsplit);
+        // the layer's plan entry: it is packed for the kernel that entry launches
+        size_t ei = 0;
+        while (ei < c->plan.conv.size() && strcmp(c->plan.conv[ei].name, sp.name) != 0) ++ei;
+        if (ei == c->plan.conv.size()) return fail(SN_ERR_STATE, "%s: the plan has no entry for the layer", sp.name);
+        const ConvEntry &e = c->plan.conv[ei];
+        if (e.k.ks != k || e.k.dil != (sp.kind == K_DIL3 ? 2 : 1)) return fail(SN_ERR_STATE, "%s: the taps of the plan's kernel do not match the layer", sp.name);
         std::vector<int> &oe = out_exps[sp.name];
         oe.assign(sp.cout, 0);
         if (sp.act == 0)                                     // ReLU layers only: a sigmoid output lies in (0,1) as it is
@@ -864,14 +864,11 @@ int sn_load_weights(sn_ctx *c, const float *blob, size_t n_floats, const sn_para
                 const float m = std::max(std::fabs(gamma[o]), std::fabs(beta[o]));
                 if (m > 0.f && std::isfinite(m)) oe[o] = std::max(-60, std::min(60, -std::ilogb(m)));
             }
-        static const bool no_bridge = sn_ab_switch("SN_NO_BRIDGE") != nullptr;               // (A/B switch)
-        L.bridge = (lsplit >= 1 && k == 3 && !no_bridge) ? 1 : 0;   // 27 K-chunks per four slabs instead of 28 (f16x3), 27 weight pieces per eight slabs instead of 32 (f16m8): pack_conv_host decides
-        if ((rc = pack_conv(c, L, W, beta, gamma, mean, inv_std, tc.nf, tc.nsplit, tc.cs8max, lsplit, in_exp, oe.data())) != SN_OK) return rc;
-        c->conv[L.name] = L;
+        if ((rc = pack_conv(c, c->conv[ei], e, W, beta, gamma, mean, inv_std, in_exp, oe.data())) != SN_OK) return rc;
     }
     // side_op1 / side_op2 run inside the epilogues of conv1_3 / conv2_3 (EPI_SIDEPOOL): their A fragments in the producers' register order
-    if ((rc = pack_side_frag(c, c->conv["side_op1"], c->conv["conv1_3"].nf)) != SN_OK) return rc;
-    if ((rc = pack_side_frag(c, c->conv["side_op2"], c->conv["conv2_3"].nf)) != SN_OK) return rc;
+    for (size_t i = 1; i < c->conv.size(); ++i)
+        if (c->plan.conv[i].pool_tag && (rc = pack_side_frag(c, c->conv[i], c->conv[i - 1].nf)) != SN_OK) return rc;
     c->have_relw = false;
     if (n_params == kAllParams) {
         const sn_param_desc *d = descs + pi;
@@ -1559,6 +1556,25 @@ SN_API int sn_debug_pack_host(int cin, int cout, int ks, int dil, int k2d, int n
     const unsigned char *b = reinterpret_cast<const unsigned char *>(h.data());
     for (size_t i = 0; i < h.size() * sizeof(_Float16); ++i) sum = sum * 1099511628211ull + b[i];
     out[0] = h.size(); out[1] = sc.size(); out[2] = sh.size(); out[3] = sum;
+    return SN_OK;
+}
+
+// Test hook: the plan's conv entries for a network (0 SurfaceNet, 1 similarityNet), a precision mode and a conv4_fp8 value (< 0: the mode's
+// default), one text row "name cin cout ks dil k2d nf nsplit cs8max split osplit epi bridge_requested" per layer - what the packer and the
+// launcher are both driven by. Host data: needs no context and no GPU. Like the library itself it follows the A/B switches of the process
+// (SN_C4_M8, SN_M8_TAIL, SN_NO_BRIDGE, SN_NO_EPI_FUSION, SN_SIMIL_NO_BRIDGE): with one of them set the rows are not the shipped plan's.
+SN_API int sn_debug_plan(int net, int mode, int conv4_fp8, char *rows, int cap)
+{
+    if (!rows || cap < 1 || net < 0 || net > 1) return fail(SN_ERR_ARG, "sn_debug_plan: bad argument");
+    sn_ctx st;      // never created: sn_set_precision / sn_set_conv4_fp8 only write host fields of the context, and must stay so (noted there)
+    int rc = sn_set_precision(&st, mode), n = 0;
+    if (rc == SN_OK && conv4_fp8 >= 0) rc = sn_set_conv4_fp8(&st, conv4_fp8);
+    if (rc != SN_OK) return rc;
+    for (const ConvEntry &e : net == 0 ? build_plan(st.split, st.tail_m8, st.c4_m8).conv : simil_plan(st.split)) {
+        n += snprintf(rows + n, (size_t)(cap - n), "%s %d %d %d %d %d %d %d %d %d %d %d %d\n", e.name, e.cin, e.cout, e.k.ks, e.k.dil, e.k.k2d,
+                      e.k.nf, e.k.nsplit(e.cout), e.k.cs8max, e.k.split, e.k.osplit, e.k.epi, e.bridge);
+        if (n >= cap) return fail(SN_ERR_ARG, "sn_debug_plan: the rows do not fit %d bytes", cap);
+    }
     return SN_OK;
 }
 

@@ -1,6 +1,8 @@
 // sn_internal.h — shared by the translation units of libsurfacenet_hip.so (sn_api.hip: context, weights, hot path,
 // RCCL, profiling; sn_post.hip: ray pooling + dense2sparse; sn_simil.hip: similarityNet + patch cropping): error state,
-// the context, owned device memory, HIP-event profiling, packed conv layers and the launcher of conv3d_f16_mfma.
+// the context, owned device memory, HIP-event profiling, packed conv layers, ConvKernel (one conv3d_f16_mfma
+// instantiation as a type: its packing geometry and its launcher) and the plan rows - which kernel runs which layer -
+// that the weight packers and the forward passes walk.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -71,6 +73,47 @@ struct PackedConv {
     _Float16 *side_frag = nullptr;
 };
 
+// ------------------------------------------------------------------------------------------------
+// kernel choice and layer plan
+// ------------------------------------------------------------------------------------------------
+struct sn_ctx;
+// Which premultiplier a tensor's code plane is stored and read with (mx_format.h). The values live on the context - sn_calibrate_dev and
+// reset_mx_exponents change them (MX_X0: the constant kMxX0E8) - a tensor only says which one.
+enum MxExp : unsigned char { MX_ACT, MX_CAT, MX_X0, MX_C4 };
+
+// A channels-last fp16 activation tensor: hi plane at p, lo plane (f16x3 mode) at p + lo elements.
+struct Act { _Float16 *p; long long lo; long long code = 0; MxExp e8 = MX_ACT; };      // code: a third plane of fp8 code slots (OSPLIT 4), in halfs from p
+
+// What EPI_SIDEPOOL needs beside the conv's own arguments: the fused 1x1x1 layer and the two destinations.
+struct SideFuse { const PackedConv *side; Act side_out; int side_cs, side_coff; Act pool_out; int pool_cs; };
+
+// A kernel instantiation as data (ConvKernel::geom): what the weight packer has to know of it, and its launcher.
+struct ConvGeom {
+    int ks, dil, k2d, nf, cs8max, split, osplit, epi;      // k2d: 0 / 1 as PackedConv::k2d (taps over (y,z) only); osplit: storage format of the output
+    bool has_bridge;                                       // the kernel reads bridge chunks: the packer may be asked for them (it grants them per layer)
+    int (*launch)(sn_ctx *c, const PackedConv &L, Act in, int in_cs, Act out, int out_cs, int out_coff, int out_cp, float *out_f32, int B, int D, int DX, const SideFuse *sf);
+    int nsplit(int cout) const { return ((cout + 15) / 16 + nf - 1) / nf; }      // workgroup columns of nf 16-channel fragments
+};
+
+// One conv layer of a network's plan, in launch order: the layer, the kernel that runs it, the tensors it reads and writes (ids of the network's
+// tensor table). An EPI_SIDEPOOL entry runs the entry after it - a 1x1x1 layer, packed for the kernel that would run it unfused - and that
+// entry's 2x max-pool in its epilogue.
+struct ConvEntry {
+    const char *name; int cin, cout, act;
+    ConvGeom k;
+    int bridge;                                     // bridge chunks requested from the packer
+    unsigned char in = 0, out = 0, pool_out = 0;    // pool_out: destination of the 2x max-pool of `in` that follows the layer (0: none)
+    const char *pool_tag = nullptr;                 // ... and its profile tag
+    bool up3 = false;                               // followed by the upsampling of the three side maps into the concat buffer
+};
+struct TensorSpec { _Float16 *sn_ctx::*buf; int level, ch; MxExp e8; int code; };      // extent cube_D >> level; code: 1 = + the code plane a3c, 2 = a3c in place of the lo plane
+struct NetPlan {
+    int split = -1, tail_m8 = 0, c4_m8 = 0;         // the precision state it was built for
+    std::vector<ConvEntry> conv;
+    std::vector<TensorSpec> tens;
+    int (*pool)(sn_ctx *, const char *, Act, Act, int, int, int) = nullptr;      // the operand mode's max-pool and side-map upsampling launchers
+    int (*up3)(sn_ctx *, Act, Act, Act, Act, int, int, int) = nullptr;
+};
 
 struct ProfRec { int tag; hipEvent_t e0, e1; double flops, bytes; };
 struct ProfStat { std::string name; double ms = 0; int64_t launches = 0; double flops = 0, bytes = 0; };
@@ -110,7 +153,8 @@ struct sn_ctx {
     int tail_m8 = 2;            // f16x3: 2 = merge_conv_a + merge_conv_b run their two correction terms on the MX MFMA (the default), 0 = none (f16x3p)
     bool ws_ready = false; int ws_split = -1;
     int last_run_samples = 0;   // samples of the last network run whose activations are still in the workspace (0: none since the weights / mode changed) - sn_calibrate_dev
-    std::map<std::string, PackedConv> conv;
+    NetPlan plan;               // of the precision state the weights were packed in (sn_load_weights)
+    std::vector<PackedConv> conv;      // conv[i] = plan.conv[i] packed
     float *w3 = nullptr; float scale3 = 0, shift3 = 0;
     void *zero_page = nullptr; int num_cus = 256;
     void *rccl_comm = nullptr; int comm_world = 0, comm_rank = 0;   // RCCL communicator (lazy dlopen of librccl)
@@ -133,7 +177,7 @@ struct sn_ctx {
     float *d_fused = nullptr;     // [max_samples][s^3]
     std::vector<long long> h_img_off; std::vector<int> h_img_h, h_img_w;   // host copies (patch cropping addresses one view)
     // similarityNet (N3)
-    PackedConv sconv[13]; bool simil_loaded = false; int simil_split = -1;
+    std::vector<ConvEntry> splan; PackedConv sconv[13]; bool simil_loaded = false; int simil_split = -1;
     float *semb_W = nullptr, *semb_b = nullptr; float ssim_w = 0, ssim_b = 0;
     std::vector<float> simil_host;   // the 13 conv layers' fp32 parameters, kept to re-pack on a precision switch
     std::vector<sn_param_desc> simil_descs;
@@ -224,9 +268,10 @@ static int prof_drain(sn_ctx *c)
     return SN_OK;
 }
 
-// Folds BN, packs the weights of one conv layer into MFMA fragment order (defined in sn_api.hip).
-int pack_conv(sn_ctx *c, PackedConv &L, const float *W, const float *beta, const float *gamma, const float *mean,
-              const float *inv_std, int nf, int nsplit, int cs8max, int split, const int *in_exp = nullptr, const int *out_exp = nullptr);
+// Folds BN, packs the weights of one plan entry into MFMA fragment order, for the kernel the entry names (defined in sn_api.hip).
+int pack_conv(sn_ctx *c, PackedConv &L, const ConvEntry &e, const float *W, const float *beta, const float *gamma, const float *mean,
+              const float *inv_std, const int *in_exp = nullptr, const int *out_exp = nullptr);
+std::vector<ConvEntry> simil_plan(int split);      // the similarityNet's plan for a context's operand mode (sn_ctx::split; defined in sn_simil.hip)
 
 static bool shape_is(const sn_param_desc &d, std::initializer_list<int> s)
 {
@@ -239,99 +284,96 @@ static bool shape_is(const sn_param_desc &d, std::initializer_list<int> s)
 // ------------------------------------------------------------------------------------------------
 // launches
 // ------------------------------------------------------------------------------------------------
-// A channels-last fp16 activation tensor: hi plane at p, lo plane (f16x3 mode) at p + lo elements.
-struct Act { _Float16 *p; long long lo; long long code = 0; };      // code: a third plane of fp8 code slots (OSPLIT 4), in halfs from p
+static int mx_e8(const sn_ctx *c, MxExp w) { return w == MX_C4 ? c->mx_c4_e8 : (w == MX_CAT ? c->mx_cat_e8 : (w == MX_X0 ? kMxX0E8 : c->mx_act_e8)); }
 
-// What EPI_SIDEPOOL needs beside the conv's own arguments: the fused 1x1x1 layer and the two destinations.
-struct SideFuse { const PackedConv *side; Act side_out; int side_cs, side_coff; Act pool_out; int pool_cs; };
-
+// A kernel choice: one instantiation of conv3d_f16_mfma as a type. What a layer has to be packed with to run on it (geom) and its launcher are
+// members of the same type, so the two cannot disagree; launch() ("launch_conv" in the comments of conv3d_mfma.h) still checks the layer it is
+// handed (a stale pack after a mode switch).
 template <int KS, int DIL, int MF, int NF, int EPI, int SPLIT, int CS8, int PCH, int NW, int PADV, int K2D = 0, int OSPLIT = -1>
-static int launch_conv(sn_ctx *c, const PackedConv &L, Act in, int in_cs, Act out, int out_cs, int out_coff, int out_cp,
-                       float *out_f32, int B, int D, int DX = 0, const SideFuse *sf = nullptr)
-{
+struct ConvKernel {
     using C = ConvCfg<KS, DIL, MF, NF, EPI, SPLIT, CS8, PCH, NW, PADV, K2D>;
-    if (DX <= 0) DX = D;
-    if ((L.k2d != 0) != (K2D != 0)) return fail(SN_ERR_STATE, "%s: packed for a different tap geometry", L.name.c_str());
-    if (L.nf != NF || L.ks != KS || L.dil != DIL || L.cs8max != C::CS8MAX || L.split != SPLIT)
-        return fail(SN_ERR_STATE, "%s: packed for a different kernel configuration", L.name.c_str());
-    ConvArgs a;
-    memset(&a, 0, sizeof a);
-    a.in = in.p; a.in_lo_off = in.lo; a.out = out.p; a.out_lo_off = out.lo; a.out_code_off = out.code; a.out_f32 = out_f32;
-    a.wpack = L.wpack; a.scale = L.scale; a.shift = L.shift;
-    a.w3 = c->w3; a.scale3 = c->scale3; a.shift3 = c->shift3; a.zero_page = c->zero_page;
-    a.wsplit_stride = L.wsplit_stride;
-    a.in_cs = in_cs; a.out_cs = out_cs; a.out_coff = out_coff; a.out_cp = out_cp;
-    a.D = D; a.DX = DX;
-    a.tiles_x = (DX + C::TX - 1) / C::TX; a.tiles_y = (D + C::TY - 1) / C::TY; a.tiles_z = (D + C::TZ - 1) / C::TZ;
-    a.total_tiles = B * a.tiles_x * a.tiles_y * a.tiles_z;
+    static int launch(sn_ctx *c, const PackedConv &L, Act in, int in_cs, Act out, int out_cs, int out_coff, int out_cp,
+                      float *out_f32, int B, int D, int DX, const SideFuse *sf)
     {
-        // preconditions of the buffer-addressed halo staging (conv3d_mfma.h, stage_halo_buf)
-        auto edge_only = [](int n, int T, int R) { return n <= T || n % T == 0 || n % T >= R; };   // only the first / last tile sees padding
-        if ((K2D == 0 && !edge_only(DX, C::TX, C::RX)) || !edge_only(D, C::TY, C::R) || !edge_only(D, C::TZ, C::R))
-            return fail(SN_ERR_ARG, "%s: volume extent %d is not supported by this kernel's halo addressing (extent mod 8 must be 0 or >= %d)", L.name.c_str(), D, C::R);
-        const long long plane = (long long)DX * D * D * 16, slack = 4LL * C::HVOX * 16;
-        if (K2D == 0 && C::CS8MAX * plane + slack >= (1LL << 25))
-            return fail(SN_ERR_ARG, "%s: a %d-group channel slab of a %dx%dx%d volume exceeds the 32 MiB this kernel's halo addressing covers", L.name.c_str(), C::CS8MAX, DX, D, D);
-        if (K2D != 0 && SPLIT != 0 && C::CS8MAX * plane + slack >= 0x0FFFFFF0LL - (1 << 16))
-            return fail(SN_ERR_ARG, "%s: %d images of %dx%d exceed the 256 MiB this kernel's halo addressing covers per channel slab", L.name.c_str(), DX, D, D);
-    }
-    a.act = L.act;
-    if (EPI == EPI_STORE && KS != 1 && L.act != 0)       // conv3d_mfma.h: only the 1x1x1 store kernels carry the sigmoid epilogue
-        return fail(SN_ERR_STATE, "%s: a sigmoid activation is only built for the 1x1x1 store kernels", L.name.c_str());
-    {
-        // static premultipliers of the 6-bit code planes (mx_format.h): the concat buffer holds sigmoid outputs, everything else ReLU(BN(.))
-        auto e8_of = [&](const _Float16 *t) {
-            if (t && c->c4_m8 && c->split == 1 && (t == c->a3 || t == c->a4 || t == c->b4)) return c->mx_c4_e8;
-            return t && t == c->cat ? c->mx_cat_e8 : (t && t == c->x0 ? kMxX0E8 : c->mx_act_e8);
-        };
-        a.mx_in_e8 = e8_of(in.p); a.mx_out_e8 = e8_of(out.p); a.mx_side_e8 = sf ? e8_of(sf->side_out.p) : c->mx_act_e8;
-    }
-    if (EPI == EPI_SIDEPOOL) {
-        if (!sf || !sf->side || !sf->side->side_frag || sf->side->cin != L.cout || sf->side->cout != 16 || L.nsplit != 1 || L.act != 0 || (D & 1))
-            return fail(SN_ERR_STATE, "%s: fused side-conv / pool epilogue misconfigured", L.name.c_str());
-        a.side_w = sf->side->side_frag; a.side_scale = sf->side->scale; a.side_shift = sf->side->shift; a.side_act = sf->side->act;
-        a.side_out = sf->side_out.p; a.side_lo_off = sf->side_out.lo; a.side_cs = sf->side_cs; a.side_coff = sf->side_coff;
-        a.pool_out = sf->pool_out.p; a.pool_lo_off = sf->pool_out.lo; a.pool_cs = sf->pool_cs;
-    }
-    if (c->d_num) {
-        // one status bit per layer name (2-D similarityNet layers share bit 31)
-        auto it = std::find(c->num_names.begin(), c->num_names.end(), L.name);
-        size_t bit = it - c->num_names.begin();
-        if (it == c->num_names.end() && c->num_names.size() < 31) c->num_names.push_back(L.name);
-        a.status = c->d_num;
-        // saturation warning: only for tensors stored with a 6-bit code plane whose values are not bounded by construction (ReLU outputs)
-        constexpr int OS = OSPLIT < 0 ? SPLIT : OSPLIT;
-        if (EPI == EPI_STORE && OS >= 2 && L.act == 0) {
-            // (fp8 planes: the hi code holds values up to 448 * 2^-s, but the lo code - lo * 2^12 * 2^s with |lo| <= half an ulp of the fp16 hi - can already
-            // saturate from |x| = 256 * 2^-s on (ulp 0.25: lo up to 0.125 -> 512 > 448); the warning starts where the first code can saturate. ADVICE r5)
-            const _Float16 lim = (_Float16)std::min(60000.f, std::ldexp(OS >= 3 ? 255.875f : (SN_MX_FMT == 2 ? 7.5f : 28.f), a.mx_out_e8 - 127));
-            unsigned short bits; memcpy(&bits, &lim, 2);
-            a.mx_sat_bits = bits;
+        if (DX <= 0) DX = D;
+        if ((L.k2d != 0) != (K2D != 0)) return fail(SN_ERR_STATE, "%s: packed for a different tap geometry", L.name.c_str());
+        if (L.nf != NF || L.ks != KS || L.dil != DIL || L.cs8max != C::CS8MAX || L.split != SPLIT)
+            return fail(SN_ERR_STATE, "%s: packed for a different kernel configuration", L.name.c_str());
+        ConvArgs a;
+        memset(&a, 0, sizeof a);
+        a.in = in.p; a.in_lo_off = in.lo; a.out = out.p; a.out_lo_off = out.lo; a.out_code_off = out.code; a.out_f32 = out_f32;
+        a.wpack = L.wpack; a.scale = L.scale; a.shift = L.shift;
+        a.w3 = c->w3; a.scale3 = c->scale3; a.shift3 = c->shift3; a.zero_page = c->zero_page;
+        a.wsplit_stride = L.wsplit_stride;
+        a.in_cs = in_cs; a.out_cs = out_cs; a.out_coff = out_coff; a.out_cp = out_cp;
+        a.D = D; a.DX = DX;
+        a.tiles_x = (DX + C::TX - 1) / C::TX; a.tiles_y = (D + C::TY - 1) / C::TY; a.tiles_z = (D + C::TZ - 1) / C::TZ;
+        a.total_tiles = B * a.tiles_x * a.tiles_y * a.tiles_z;
+        {
+            // preconditions of the buffer-addressed halo staging (conv3d_mfma.h, stage_halo_buf)
+            auto edge_only = [](int n, int T, int R) { return n <= T || n % T == 0 || n % T >= R; };   // only the first / last tile sees padding
+            if ((K2D == 0 && !edge_only(DX, C::TX, C::RX)) || !edge_only(D, C::TY, C::R) || !edge_only(D, C::TZ, C::R))
+                return fail(SN_ERR_ARG, "%s: volume extent %d is not supported by this kernel's halo addressing (extent mod 8 must be 0 or >= %d)", L.name.c_str(), D, C::R);
+            const long long plane = (long long)DX * D * D * 16, slack = 4LL * C::HVOX * 16;
+            if (K2D == 0 && C::CS8MAX * plane + slack >= (1LL << 25))
+                return fail(SN_ERR_ARG, "%s: a %d-group channel slab of a %dx%dx%d volume exceeds the 32 MiB this kernel's halo addressing covers", L.name.c_str(), C::CS8MAX, DX, D, D);
+            if (K2D != 0 && SPLIT != 0 && C::CS8MAX * plane + slack >= 0x0FFFFFF0LL - (1 << 16))
+                return fail(SN_ERR_ARG, "%s: %d images of %dx%d exceed the 256 MiB this kernel's halo addressing covers per channel slab", L.name.c_str(), DX, D, D);
         }
-        a.status_bit = bit < 31 ? (1u << bit) : (1u << 31);
+        a.act = L.act;
+        if (EPI == EPI_STORE && KS != 1 && L.act != 0)       // conv3d_mfma.h: only the 1x1x1 store kernels carry the sigmoid epilogue
+            return fail(SN_ERR_STATE, "%s: a sigmoid activation is only built for the 1x1x1 store kernels", L.name.c_str());
+        // premultipliers of the code planes (mx_format.h): each tensor says which of the context's exponents it is stored with
+        a.mx_in_e8 = mx_e8(c, in.e8); a.mx_out_e8 = mx_e8(c, out.e8); a.mx_side_e8 = mx_e8(c, sf ? sf->side_out.e8 : MX_ACT);
+        if (EPI == EPI_SIDEPOOL) {
+            if (!sf || !sf->side || !sf->side->side_frag || sf->side->cin != L.cout || sf->side->cout != 16 || L.nsplit != 1 || L.act != 0 || (D & 1))
+                return fail(SN_ERR_STATE, "%s: fused side-conv / pool epilogue misconfigured", L.name.c_str());
+            a.side_w = sf->side->side_frag; a.side_scale = sf->side->scale; a.side_shift = sf->side->shift; a.side_act = sf->side->act;
+            a.side_out = sf->side_out.p; a.side_lo_off = sf->side_out.lo; a.side_cs = sf->side_cs; a.side_coff = sf->side_coff;
+            a.pool_out = sf->pool_out.p; a.pool_lo_off = sf->pool_out.lo; a.pool_cs = sf->pool_cs;
+        }
+        if (c->d_num) {
+            // one status bit per layer name (2-D similarityNet layers share bit 31)
+            auto it = std::find(c->num_names.begin(), c->num_names.end(), L.name);
+            size_t bit = it - c->num_names.begin();
+            if (it == c->num_names.end() && c->num_names.size() < 31) c->num_names.push_back(L.name);
+            a.status = c->d_num;
+            // saturation warning: only for tensors stored with a 6-bit code plane whose values are not bounded by construction (ReLU outputs)
+            constexpr int OS = OSPLIT < 0 ? SPLIT : OSPLIT;
+            if (EPI == EPI_STORE && OS >= 2 && L.act == 0) {
+                // (fp8 planes: the hi code holds values up to 448 * 2^-s, but the lo code - lo * 2^12 * 2^s with |lo| <= half an ulp of the fp16 hi - can already
+                // saturate from |x| = 256 * 2^-s on (ulp 0.25: lo up to 0.125 -> 512 > 448); the warning starts where the first code can saturate. ADVICE r5)
+                const _Float16 lim = (_Float16)std::min(60000.f, std::ldexp(OS >= 3 ? 255.875f : (SN_MX_FMT == 2 ? 7.5f : 28.f), a.mx_out_e8 - 127));
+                unsigned short bits; memcpy(&bits, &lim, 2);
+                a.mx_sat_bits = bits;
+            }
+            a.status_bit = bit < 31 ? (1u << bit) : (1u << 31);
+        }
+        a.nslab = (int)L.slab_c8.size();
+        if (a.nslab < 1) return fail(SN_ERR_STATE, "%s: no channel slabs", L.name.c_str());      // (the kernel assumes at least one)
+        a.bridge = L.bridge;
+        if (L.bridge && !geom.has_bridge)
+            return fail(SN_ERR_STATE, "%s: packed with bridge chunks, launched on a kernel without them", L.name.c_str());
+        if (C::PWM) {      // one-wave-per-SIMD loop: a slab's first piece issues DMAs that its second piece waits for
+            for (unsigned char c8n : L.slab_c8)
+                if (C::NTAP * c8n < 9) return fail(SN_ERR_STATE, "%s: a channel slab of fewer than two weight pieces", L.name.c_str());
+        }
+        for (int i = 0; i + 1 < a.nslab; ++i)
+            if (L.slab_c8[i] != C::CS8MAX) return fail(SN_ERR_STATE, "%s: channel slab %d holds %d groups, the kernel expects %d in all but the last", L.name.c_str(), i, (int)L.slab_c8[i], C::CS8MAX);
+        a.c8_last = L.slab_c8.back();
+        const double vox = (double)B * DX * D * D;
+        const double bytes = vox * 2.0 * (SPLIT ? 2 : 1) * (L.cin + (EPI == EPI_FINAL ? 2 : (EPI == EPI_SIDEPOOL ? 16 + L.cout / 8.0 : L.cout)));
+        ProfScope ps(c, L.name, 2.0 * L.macs_per_voxel * vox, bytes);
+        // persistent workgroups: one resident set, each walking tiles blockIdx.x, +gridDim.x, ...
+        const int resident = std::max(1, c->num_cus * C::WG_PER_CU / L.nsplit);
+        dim3 grid((unsigned)std::min(a.total_tiles, resident), (unsigned)L.nsplit);
+        hipLaunchKernelGGL((conv3d_f16_mfma<KS, DIL, MF, NF, EPI, SPLIT, CS8, PCH, NW, PADV, K2D, OSPLIT>), grid, dim3(NW * 64), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+        return SN_OK;
     }
-    a.nslab = (int)L.slab_c8.size();
-    if (a.nslab < 1) return fail(SN_ERR_STATE, "%s: no channel slabs", L.name.c_str());      // (the kernel assumes at least one)
-    a.bridge = L.bridge;
-    if (L.bridge && !sn::sn_conv_has_bridge<KS, SPLIT, NW, PCH, NF, K2D, MF>())
-        return fail(SN_ERR_STATE, "%s: packed with bridge chunks, launched on a kernel without them", L.name.c_str());
-    if (C::PWM) {      // one-wave-per-SIMD loop: a slab's first piece issues DMAs that its second piece waits for
-        for (unsigned char c8n : L.slab_c8)
-            if (C::NTAP * c8n < 9) return fail(SN_ERR_STATE, "%s: a channel slab of fewer than two weight pieces", L.name.c_str());
-    }
-    for (int i = 0; i + 1 < a.nslab; ++i)
-        if (L.slab_c8[i] != C::CS8MAX) return fail(SN_ERR_STATE, "%s: channel slab %d holds %d groups, the kernel expects %d in all but the last", L.name.c_str(), i, (int)L.slab_c8[i], C::CS8MAX);
-    a.c8_last = L.slab_c8.back();
-    const double vox = (double)B * DX * D * D;
-    const double bytes = vox * 2.0 * (SPLIT ? 2 : 1) * (L.cin + (EPI == EPI_FINAL ? 2 : (EPI == EPI_SIDEPOOL ? 16 + L.cout / 8.0 : L.cout)));
-    ProfScope ps(c, L.name, 2.0 * L.macs_per_voxel * vox, bytes);
-    // persistent workgroups: one resident set, each walking tiles blockIdx.x, +gridDim.x, ...
-    const int resident = std::max(1, c->num_cus * C::WG_PER_CU / L.nsplit);
-    dim3 grid((unsigned)std::min(a.total_tiles, resident), (unsigned)L.nsplit);
-    hipLaunchKernelGGL((conv3d_f16_mfma<KS, DIL, MF, NF, EPI, SPLIT, CS8, PCH, NW, PADV, K2D, OSPLIT>), grid, dim3(NW * 64), 0, c->stream, a);
-    HIPCHK(hipGetLastError());
-    return SN_OK;
-}
+    static constexpr ConvGeom geom = {KS, DIL, K2D != 0, NF, C::CS8MAX, SPLIT, OSPLIT < 0 ? SPLIT : OSPLIT, EPI,
+                                      sn::sn_conv_has_bridge<KS, SPLIT, NW, PCH, NF, K2D, MF>(), &launch};
+};
 
 // Temporary device buffers of the host-array entry points (freed on scope exit).
 struct TmpDev {

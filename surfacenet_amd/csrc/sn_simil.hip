@@ -1,5 +1,5 @@
 // sn_simil.hip — C ABI of the similarityNet / early-rejection stage over simil.h and the 2-D form
-// of conv3d_f16_mfma.
+// of conv3d_f16_mfma. simil_plan says which kernel runs which of the 13 conv layers; simil_pack packs from it, run_simil walks it.
 #include "sn_internal.h"
 #include "simil.h"
 
@@ -13,62 +13,58 @@ static constexpr int kSimParams = 30, kSimNF = 4;
 // patches per pass: two 64x64 group planes of a chunk (2040 * 4096 * 16 B * 2 = 267.4 MB) must stay below the 2^28 - 16 offset field of the
 // conv kernel's buffer-addressed halo staging (conv3d_mfma.h)
 static constexpr int kSimChunk = 2040;
-// channel groups per slab / K-chunks per weight piece: f16x3 (two activation planes) 2 / 2 (3 measured equal); f16 (one plane)
-// 4 / 3, i.e. 36 groups = exactly 9 chunks per slab: +18 % in that mode
-#define SIMCS8 (SP == 0 ? 4 : 2)
-#ifndef SN_SIMPCH
-#define SN_SIMPCH 2
-#endif
-#define SIMPCH (SP == 0 ? 3 : SN_SIMPCH)
-static int simil_cs8(int mode) { return mode == 0 ? 4 : 2; }
-#define SCONV 3, 1, 4, kSimNF, EPI_STORE, SP, SIMCS8, SIMPCH, 8, 0, 1
-// the 4x4 maps of conv5_x: one MFMA voxel fragment = one image (K2D = 2), 16 images x 128 output channels per workgroup
-#define SCONV5 3, 1, 2, 8, EPI_STORE, SP, 2, 2, 8, 0, 2
-// the last conv of every block writes the 2x2 max-pooled map directly (EPI_POOL2D): the unpooled map is never stored
-#define SCONVP 3, 1, 4, kSimNF, EPI_POOL2D, SP, SIMCS8, SIMPCH, 8, 0, 1
-#define SCONV5P 3, 1, 2, 8, EPI_POOL2D, SP, 2, 2, 8, 0, 2
-// SN_SIM_NF8 (round 4): 128 output channels per workgroup with ONE-group channel slabs for the f16x3 layers with >= 128 outputs (two-group slabs + 128-channel weight pieces
-// would need 169 KB of LDS): half the halo DMAs per MFMA, a slab boundary every 2.25 chunks. Same-box (profiles/r4/ab_r4ak_nf8.log): s_conv2_1 -6 %, s_conv3_x -2..5 %, s_conv4_x
-// -3..6 %, s_conv2_2 (pooled, 128 outputs) +5 % -> not that one; similarityNet +2.5 % patches/s. 0: every layer on the 64-channel kernels; 1: unpooled layers only.
-#ifndef SN_SIM_NF8
-#define SN_SIM_NF8 2
-#endif
-// SN_SIM_MF8 (round 6, experiment): the 64-output layers of the 64x64 / 32x32 maps (s_conv1_1, s_conv1_2, s_conv2_2 in two cout splits) with EIGHT voxel fragments per wave over
-// one-group slabs - 16 patches x 8x8 pixels x 64 channels per workgroup: bursts of 96 instead of 48 MFMAs per segment, 24 instead of 32 operand reads and half the weight DMAs per
-// 96 MFMAs, the same halo bytes per MFMA
-#ifndef SN_SIM_MF8
-#define SN_SIM_MF8 0
-#endif
-#define SCONV16 3, 1, 8, kSimNF, EPI_STORE, SP, 1, 2, 8, 0, 1
-#define SCONV16P 3, 1, 8, kSimNF, EPI_POOL2D, SP, 1, 2, 8, 0, 1
-#define SCONV8 3, 1, 4, 8, EPI_STORE, SP, 1, 2, 8, 0, 1
-#define SCONV8P 3, 1, 4, 8, EPI_POOL2D, SP, 1, 2, 8, 0, 1
-static bool simil_wide(int i, int mode)
-{
-    const bool last = (i == 12 || kSimStage[i + 1] != kSimStage[i]);
-    return SN_SIM_NF8 && mode == 1 && kSimStage[i] < 4 && kSimC[i + 1] >= 128 && (!last || (SN_SIM_NF8 >= 2 && kSimC[i + 1] >= 256));
-}
-static int simil_nf(int i, int mode = 0) { return kSimStage[i] == 4 || simil_wide(i, mode) ? 8 : kSimNF; }
-static bool simil_mf8(int i, int mode) { return SN_SIM_MF8 && mode == 1 && kSimStage[i] < 2 && !simil_wide(i, mode); }
 
 static int simil_mode(sn_ctx *c) { return c->split == 0 ? 0 : 1; }   // f16m8 contexts run this net in f16x3 (own workspace)
+
+// Kernel configurations <KS, DIL, MF, NF, EPI, SPLIT, CS8, PCH, NW, PADV, K2D>; the last conv of every block writes the 2x2 max-pooled map directly
+// (EPI_POOL2D): the unpooled map is never stored.
+template <int SP, int EPI>
+struct SimilKernels {
+    // channel groups per slab / K-chunks per weight piece: f16x3 (two activation planes) 2 / 2 (3 measured equal); f16 (one plane)
+    // 4 / 3, i.e. 36 groups = exactly 9 chunks per slab: +18 % in that mode
+    using Conv = ConvKernel<3, 1, 4, kSimNF, EPI, SP, (SP == 0 ? 4 : 2), (SP == 0 ? 3 : 2), 8, 0, 1>;
+    // the 4x4 maps of conv5_x: one MFMA voxel fragment = one image (K2D = 2), 16 images x 128 output channels per workgroup
+    using Conv5 = ConvKernel<3, 1, 2, 8, EPI, SP, 2, 2, 8, 0, 2>;
+    // round 4: 128 output channels per workgroup with ONE-group channel slabs for the f16x3 layers with >= 128 outputs (two-group slabs + 128-channel weight pieces
+    // would need 169 KB of LDS): half the halo DMAs per MFMA, a slab boundary every 2.25 chunks. Same-box (profiles/r4/ab_r4ak_nf8.log): s_conv2_1 -6 %, s_conv3_x -2..5 %, s_conv4_x
+    // -3..6 %, s_conv2_2 (pooled, 128 outputs) +5 % -> not that one; similarityNet +2.5 % patches/s.
+    using Wide = ConvKernel<3, 1, 4, 8, EPI, SP, 1, 2, 8, 0, 1>;
+};
+
+template <int SP>
+static std::vector<ConvEntry> simil_plan_t()
+{
+    static const bool no_bridge = sn_ab_switch("SN_SIMIL_NO_BRIDGE") != nullptr;      // (A/B switch)
+    std::vector<ConvEntry> plan;
+    for (int i = 0; i < 13; ++i) {
+        const int st = kSimStage[i], cout = kSimC[i + 1];
+        const bool last = (i == 12 || kSimStage[i + 1] != st);
+        using S = SimilKernels<SP, EPI_STORE>;
+        using P = SimilKernels<SP, EPI_POOL2D>;
+        ConvGeom k = st == 4 ? (last ? P::Conv5::geom : S::Conv5::geom) : (last ? P::Conv::geom : S::Conv::geom);
+        if constexpr (SP == 1) {
+            if (st < 4 && cout >= 128 && (!last || cout >= 256)) k = last ? P::Wide::geom : S::Wide::geom;
+        }
+        // bridge chunks, f16x3: two-group slabs = 4.5 K-chunks -> 9 chunks per slab pair (pack_conv_host decides per layer)
+        plan.push_back(ConvEntry{kSimName[i], kSimC[i], cout, 0, k, (k.has_bridge && !no_bridge) ? 1 : 0});
+    }
+    return plan;
+}
+std::vector<ConvEntry> simil_plan(int split) { return split == 0 ? simil_plan_t<0>() : simil_plan_t<1>(); }
 
 static int simil_pack(sn_ctx *c)
 {
     const int want = simil_mode(c);
     if (c->simil_split == want) return SN_OK;
     HIPCHK(hipStreamSynchronize(c->stream));
+    c->splan = simil_plan(c->split);
     int rc;
     for (int i = 0; i < 13; ++i) {
         PackedConv &L = c->sconv[i];
         dev_free_owned(c, L.wpack); dev_free_owned(c, L.scale); dev_free_owned(c, L.shift);
-        L = PackedConv();
-        L.name = kSimName[i]; L.cin = kSimC[i]; L.cout = kSimC[i + 1]; L.ks = 3; L.dil = 1; L.act = 0; L.k2d = 1;
-        static const bool no_bridge = sn_ab_switch("SN_SIMIL_NO_BRIDGE") != nullptr;      // (A/B switch)
-        L.bridge = (want == 1 && !no_bridge) ? 1 : 0;       // f16x3: two-group slabs = 4.5 K-chunks -> 9 chunks per slab pair (pack_conv_host decides per layer)
         const float *W = c->simil_host.data() + c->simil_descs[2 * i].offset, *b = c->simil_host.data() + c->simil_descs[2 * i + 1].offset;
-        std::vector<float> one((size_t)L.cout, 1.f), zero((size_t)L.cout, 0.f);
-        if ((rc = pack_conv(c, L, W, b, one.data(), zero.data(), one.data(), simil_nf(i, want), L.cout / (16 * simil_nf(i, want)), kSimStage[i] == 4 ? 2 : ((simil_wide(i, want) || simil_mf8(i, want)) ? 1 : simil_cs8(want)), want)) != SN_OK) return rc;
+        std::vector<float> one((size_t)c->splan[i].cout, 1.f), zero(one.size(), 0.f);
+        if ((rc = pack_conv(c, L, c->splan[i], W, b, one.data(), zero.data(), one.data())) != SN_OK) return rc;
     }
     c->simil_split = want;
     return SN_OK;
@@ -151,62 +147,29 @@ static int simil_workspace(sn_ctx *c, int n, SimilWs *w)
     return SN_OK;
 }
 
-extern "C++" {
-template <int SP>
-static int run_simil_t(sn_ctx *c, const SimilWs &w, int n)
+static int run_simil(sn_ctx *c, const SimilWs &w, int n)
 {
+    const int sp = simil_mode(c);
     int rc;
     Act cur = w.p0;
     int cur_cs = 8;
     int flip[5] = {0, 0, 0, 0, 0};
     for (int i = 0; i < 13; ++i) {
+        const ConvEntry &e = c->splan[i];
         const int st = kSimStage[i], H = kPatch >> st;
-        const bool last = (i == 12 || kSimStage[i + 1] != st);
-        if (last) {      // conv + bias + ReLU + Pool2DLayer(2) in one kernel
-            Act out = w.pool[st];
-            bool done = false;
-            if constexpr (SN_SIM_NF8 >= 2 && SP == 1) {
-                if (simil_wide(i, 1)) { rc = launch_conv<SCONV8P>(c, c->sconv[i], cur, cur_cs, out, kSimC[i + 1], 0, kSimC[i + 1], nullptr, 1, H, n); done = true; }
-            }
-            if constexpr (SN_SIM_MF8 && SP == 1) {
-                if (!done && simil_mf8(i, 1)) { rc = launch_conv<SCONV16P>(c, c->sconv[i], cur, cur_cs, out, kSimC[i + 1], 0, kSimC[i + 1], nullptr, 1, H, n); done = true; }
-            }
-            if (!done)
-            rc = st == 4 ? launch_conv<SCONV5P>(c, c->sconv[i], cur, cur_cs, out, kSimC[i + 1], 0, kSimC[i + 1], nullptr, 1, H, n)
-                         : launch_conv<SCONVP>(c, c->sconv[i], cur, cur_cs, out, kSimC[i + 1], 0, kSimC[i + 1], nullptr, 1, H, n);
-            if (rc != SN_OK) return rc;
-            cur = out; cur_cs = kSimC[i + 1];
-            continue;
-        }
-        Act out = w.a[st][flip[st]];
-        flip[st] ^= 1;
-        if constexpr (SN_SIM_NF8 && SP == 1) {
-            if (simil_wide(i, 1)) {
-                rc = launch_conv<SCONV8>(c, c->sconv[i], cur, cur_cs, out, kSimC[i + 1], 0, kSimC[i + 1], nullptr, 1, H, n);
-                if (rc != SN_OK) return rc;
-                cur = out; cur_cs = kSimC[i + 1];
-                continue;
-            }
-        }
-        if constexpr (SN_SIM_MF8 && SP == 1) {
-            if (simil_mf8(i, 1)) {
-                rc = launch_conv<SCONV16>(c, c->sconv[i], cur, cur_cs, out, kSimC[i + 1], 0, kSimC[i + 1], nullptr, 1, H, n);
-                if (rc != SN_OK) return rc;
-                cur = out; cur_cs = kSimC[i + 1];
-                continue;
-            }
-        }
-        rc = st == 4 ? launch_conv<SCONV5>(c, c->sconv[i], cur, cur_cs, out, kSimC[i + 1], 0, kSimC[i + 1], nullptr, 1, H, n)
-                     : launch_conv<SCONV>(c, c->sconv[i], cur, cur_cs, out, kSimC[i + 1], 0, kSimC[i + 1], nullptr, 1, H, n);
-        if (rc != SN_OK) return rc;
-        cur = out; cur_cs = kSimC[i + 1];
+        const bool pooled = e.k.epi == EPI_POOL2D;      // the block's last layer: conv + bias + ReLU + Pool2DLayer(2) in one kernel
+        const Act out = pooled ? w.pool[st] : w.a[st][flip[st]];
+        if (!pooled) flip[st] ^= 1;
+        if ((rc = e.k.launch(c, c->sconv[i], cur, cur_cs, out, e.cout, 0, e.cout, nullptr, 1, H, n, nullptr)) != SN_OK) return rc;
+        cur = out; cur_cs = e.cout;
     }
     {
         SimilFeatArgs fa;
         for (int k = 0; k < 5; ++k) { fa.pool[k] = w.pool[k].p; fa.lo_off[k] = w.pool[k].lo; }
         fa.feat = w.feat; fa.n = n;
-        ProfScope ps(c, "s_features", 0, (double)n * kSimilFeat * (2.0 * (SP ? 2 : 1) + 4.0));
-        hipLaunchKernelGGL(simil_features_kernel<SP>, dim3((unsigned)n), dim3(256), 0, c->stream, fa);
+        ProfScope ps(c, "s_features", 0, (double)n * kSimilFeat * (2.0 * (sp ? 2 : 1) + 4.0));
+        if (sp) hipLaunchKernelGGL(simil_features_kernel<1>, dim3((unsigned)n), dim3(256), 0, c->stream, fa);
+        else hipLaunchKernelGGL(simil_features_kernel<0>, dim3((unsigned)n), dim3(256), 0, c->stream, fa);
         HIPCHK(hipGetLastError());
     }
     {
@@ -217,8 +180,6 @@ static int run_simil_t(sn_ctx *c, const SimilWs &w, int n)
     }
     return SN_OK;
 }
-}   // extern "C++"
-static int run_simil(sn_ctx *c, const SimilWs &w, int n) { return simil_mode(c) ? run_simil_t<1>(c, w, n) : run_simil_t<0>(c, w, n); }
 
 static int simil_ready(sn_ctx *c)
 {

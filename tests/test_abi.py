@@ -36,7 +36,7 @@ def test_header_binding_and_library_agree(built):
     dbg = os.path.join(os.path.dirname(built.LIB_PATH), "libsurfacenet_hip_dbg.so")       # the test-only twin: the same ABI + the hooks
     out = subprocess.check_output(["nm", "-D", "--defined-only", dbg]).decode()
     exported = sorted(line.split()[-1] for line in out.splitlines() if line.strip())
-    assert set(hdr) <= set(exported) and set(exported) - set(hdr) == {"sn_debug_tensor", "sn_debug_mx6_encode", "sn_debug_timing", "sn_debug_trace", "sn_debug_pack_host"}
+    assert set(hdr) <= set(exported) and set(exported) - set(hdr) == {"sn_debug_tensor", "sn_debug_mx6_encode", "sn_debug_timing", "sn_debug_trace", "sn_debug_pack_host", "sn_debug_plan"}
 
 
 def test_version_and_no_gpu_fails_loudly(built):
@@ -152,6 +152,60 @@ def test_packed_weight_stream_length_with_bridge_chunks(built, cin, cout, ks, k2
     halfs, bridged, total = _packed_halfs(cin, ks, taps, cs8, split, nf, nsplit)
     assert total == chunks and bridged == (ks == 3 and split != 0 and cin > 8), (total, chunks, bridged)
     assert out[0] == halfs, (out[0], halfs, bridged)
+
+
+def test_conv_plan_matches_the_recorded_schedule(built):
+    """The plan - which kernel geometry every conv layer of both networks is packed for and launched on, per precision mode and conv4_fp8 value
+    (sn_debug_plan) - equals, row for row, what the code before the plan handed to pack_conv (tests/golden/conv_plan.json, recorded from that
+    code's own tile_for / lsplit / simil_* expressions, not from the plan); every row packs, to the length _packed_halfs restates. The hook follows
+    the process's A/B switches (SN_C4_M8, SN_M8_TAIL, SN_NO_BRIDGE ...): this test is meant for an environment without them."""
+    import ctypes
+    import json
+    import numpy as np
+    dbg = ctypes.CDLL(os.path.join(os.path.dirname(built.LIB_PATH), "libsurfacenet_hip_dbg.so"))
+    plan = dbg.sn_debug_plan
+    plan.restype = ctypes.c_int
+    plan.argtypes = [ctypes.c_int] * 3 + [ctypes.c_char_p, ctypes.c_int]
+    pack = dbg.sn_debug_pack_host
+    pack.restype = ctypes.c_int
+    pack.argtypes = [ctypes.c_int] * 9 + [ctypes.c_void_p] * 6
+    P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "conv_plan.json")))
+    assert golden["columns"] == ["name", "cin", "cout", "ks", "dil", "k2d", "nf", "nsplit", "cs8max", "split", "bridge_requested"]
+    modes = {"f16": 0, "f16x3": 1, "f16m8": 2, "f16x3p": 3}
+    seen = set()
+    rs = np.random.RandomState(3)
+    for g in golden["plans"]:
+        net = {"surfacenet": 0, "similaritynet": 1}[g["net"]]
+        seen.add((g["net"], g["mode"], g["conv4_fp8"]))
+        # conv4_fp8 is a setting of the default mode of SurfaceNet alone (sn_set_conv4_fp8 refuses it elsewhere): -1 = leave the mode's own
+        c4 = g["conv4_fp8"] if (net == 0 and g["mode"] == "f16x3") else -1
+        buf = ctypes.create_string_buffer(1 << 14)
+        assert plan(net, modes[g["mode"]], c4, buf, len(buf)) == 0
+        rows = [r.split() for r in buf.value.decode().splitlines()]
+        # sn_debug_plan: name cin cout ks dil k2d nf nsplit cs8max split osplit epi bridge_requested
+        got = [[r[0]] + [int(v) for v in r[1:10]] + [int(r[12])] for r in rows]
+        assert all(len(r) == 13 for r in rows) and got == g["rows"], (g["net"], g["mode"], g["conv4_fp8"], got)
+        # osplit (storage format of the output) and epi (conv3d_mfma.h: 0 store, 1 final, 2 2-D pool, 3 side conv + pool) were never tabulated before
+        # the plan; typed here from the launch sequence it replaced: outputs are stored in the layer's own format except for the writers of the concat
+        # buffer in the default mode (6-bit codes, 2, for the f16m8 merge layers) and around the fp8 conv4 chain (conv3_3: three planes, 4; a three-fp16
+        # conv4_1 that feeds an fp8 conv4_2: 3; conv4_3: hi + lo again, 1)
+        osplit = {}
+        if net == 0 and g["mode"] == "f16x3":
+            osplit = {"conv1_3": 2, "side_op1": 2}
+            osplit.update({0: {}, 1: {"conv3_3": 4, "conv4_3": 1}, 2: {"conv4_1": 3, "conv4_3": 1}}[g["conv4_fp8"]])
+        epi = {"conv1_3": 3, "conv2_3": 3, "merge_conv_b": 1, "s_conv1_2": 2, "s_conv2_2": 2, "s_conv3_3": 2, "s_conv4_3": 2, "s_conv5_3": 2}
+        assert [(r[0], int(r[10]), int(r[11])) for r in rows] == [(r[0], osplit.get(r[0], int(r[9])), epi.get(r[0], 0)) for r in rows], (g["mode"], g["conv4_fp8"])
+        for name, cin, cout, ks, dil, k2d, nf, nsplit, cs8, split, _ in got:
+            taps = ks * ks * (1 if k2d else ks)
+            W = rs.randn(cout, cin, taps).astype(np.float32)
+            one = np.ones(cout, np.float32)
+            out = (ctypes.c_ulonglong * 4)()
+            assert pack(cin, cout, ks, dil, k2d, nf, nsplit, cs8, split, P(W), P(one), P(one), P(one), P(one), out) == 0, (g["mode"], name)
+            assert out[0] == _packed_halfs(cin, ks, taps, cs8, split, nf, nsplit)[0], (g["mode"], name, out[0])
+    assert seen == {("surfacenet", "f16", 0), ("surfacenet", "f16x3", 0), ("surfacenet", "f16x3", 1), ("surfacenet", "f16x3", 2), ("surfacenet", "f16m8", 0),
+                    ("surfacenet", "f16x3p", 0), ("similaritynet", "f16", 0), ("similaritynet", "f16x3", 0)}
+    assert plan(0, 0, 1, buf, len(buf)) != 0 and plan(0, 7, -1, buf, len(buf)) != 0 and plan(0, 1, -1, buf, 8) != 0      # what the setters refuse; a short buffer
 
 
 def test_ab_switches_exist_in_the_test_twin_only():

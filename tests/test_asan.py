@@ -34,27 +34,50 @@ pack.restype = ctypes.c_int
 pack.argtypes = [ctypes.c_int] * 9 + [ctypes.c_void_p] * 6
 P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
 rs = np.random.RandomState(0)
-# (cin, cout, ks, dil, k2d, nf, nsplit): every conv layer family of SurfaceNet (sn_api.hip tile_for) and of the similarityNet (sn_simil.hip)
+n_calls = 0
+def run_packer(cin, cout, ks, dil, k2d, nf, nsplit, cs8max, split, W, bn):
+    global n_calls
+    out = (ctypes.c_ulonglong * 4)()
+    rc = pack(cin, cout, ks, dil, k2d, nf, nsplit, cs8max, split, P(W), P(bn[0]), P(bn[1]), P(bn[2]), P(bn[3]), out)
+    assert rc == 0, (cin, cout, ks, split, cs8max, lib.sn_last_error())
+    again = (ctypes.c_ulonglong * 4)()
+    assert pack(cin, cout, ks, dil, k2d, nf, nsplit, cs8max, split, P(W), P(bn[0]), P(bn[1]), P(bn[2]), P(bn[3]), again) == 0
+    assert list(out) == list(again) and out[0] > 0 and out[1] == nsplit * nf * 16 + 16           # deterministic, sized as the kernels expect
+    n_calls += 1
+def layer_data(cin, cout, ks, k2d):
+    taps = ks * ks * (1 if k2d else ks)
+    W = (rs.randn(cout, cin, taps) * 10.0 ** rs.uniform(-6, 4)).astype(np.float32)          # any magnitude: the packer renormalises by powers of two
+    return W, [rs.uniform(0.5, 1.5, cout).astype(np.float32) for _ in range(4)]
+# every layer as the library itself packs it: the rows of the two networks' plans (sn_debug_plan: name cin cout ks dil k2d nf nsplit cs8max split osplit epi
+# bridge) in every precision mode and conv4_fp8 setting, each distinct geometry once
+plan = lib.sn_debug_plan
+plan.restype = ctypes.c_int
+plan.argtypes = [ctypes.c_int] * 3 + [ctypes.c_char_p, ctypes.c_int]
+rows = set()
+for net, mode, c4 in [(0, 0, -1), (0, 1, 0), (0, 1, 1), (0, 1, 2), (0, 2, -1), (0, 3, -1), (1, 0, -1), (1, 1, -1)]:
+    buf = ctypes.create_string_buffer(1 << 14)
+    assert plan(net, mode, c4, buf, len(buf)) == 0, lib.sn_last_error()
+    got = [tuple(int(v) for v in r.split()[1:10]) for r in buf.value.decode().splitlines()]
+    assert len(got) == (13 if net else 18), got
+    rows.update(got)
+for cin, cout, ks, dil, k2d, nf, nsplit, cs8max, split in sorted(rows):
+    W, bn = layer_data(cin, cout, ks, k2d)
+    run_packer(cin, cout, ks, dil, k2d, nf, nsplit, cs8max, split, W, bn)
+n_plan_calls = n_calls
+# ... and a fixed list beside it, (cin, cout, ks, dil, k2d, nf, nsplit): every conv layer family of SurfaceNet (sn_api.hip build_plan_t) and of the similarityNet
+# (sn_simil.hip simil_plan_t) in every operand format and slab width a kernel is instantiated with, whether a plan uses the combination or not
 net = [(6, 32, 3, 1, 0, 2, 1), (32, 32, 3, 1, 0, 2, 1), (32, 16, 1, 1, 0, 1, 1), (32, 80, 3, 1, 0, 5, 1), (80, 80, 3, 1, 0, 5, 1), (80, 16, 1, 1, 0, 1, 1),
        (80, 160, 3, 1, 0, 5, 2), (160, 160, 3, 1, 0, 5, 2), (160, 16, 1, 1, 0, 1, 1), (160, 300, 3, 2, 0, 5, 4), (300, 300, 3, 2, 0, 5, 4), (300, 16, 1, 1, 0, 1, 1),
        (64, 100, 3, 1, 0, 7, 1), (100, 100, 3, 1, 0, 7, 1)]
 sim = [(3, 64, 3, 1, 1, 4, 1), (64, 64, 3, 1, 1, 4, 1), (64, 128, 3, 1, 1, 4, 2), (256, 512, 3, 1, 1, 4, 8), (512, 512, 3, 1, 1, 8, 4)]
-n_calls = 0
 for cin, cout, ks, dil, k2d, nf, nsplit in net + sim:
-    taps = ks * ks * (1 if k2d else ks)
-    W = (rs.randn(cout, cin, taps) * 10.0 ** rs.uniform(-6, 4)).astype(np.float32)          # any magnitude: the packer renormalises by powers of two
-    bn = [rs.uniform(0.5, 1.5, cout).astype(np.float32) for _ in range(4)]
+    W, bn = layer_data(cin, cout, ks, k2d)
     for split in (0, 1, 2, 3):
         if split >= 2 and (ks == 1 or k2d):
             continue                                                                          # f16m8 / f16m8e (fp8 codes: the dilated layers) exist for the 3x3x3 kernels only
         for cs8max in ((5,) if ks == 1 else ((2, 4) if k2d else (1, 2))):              # the slab widths the kernels are instantiated with
-            out = (ctypes.c_ulonglong * 4)()
-            rc = pack(cin, cout, ks, dil, k2d, nf, nsplit, cs8max, split, P(W), P(bn[0]), P(bn[1]), P(bn[2]), P(bn[3]), out)
-            assert rc == 0, (cin, cout, ks, split, cs8max, lib.sn_last_error())
-            again = (ctypes.c_ulonglong * 4)()
-            assert pack(cin, cout, ks, dil, k2d, nf, nsplit, cs8max, split, P(W), P(bn[0]), P(bn[1]), P(bn[2]), P(bn[3]), again) == 0
-            assert list(out) == list(again) and out[0] > 0 and out[1] == nsplit * nf * 16 + 16           # deterministic, sized as the kernels expect
-            n_calls += 1
+            run_packer(cin, cout, ks, dil, k2d, nf, nsplit, cs8max, split, W, bn)
+assert n_plan_calls >= 42 and n_calls - n_plan_calls >= 80, (n_plan_calls, n_calls)      # 14 distinct SurfaceNet layer shapes x 3 operand modes at the least
 bad = np.full((16, 8, 27), np.nan, np.float32)                                               # a non-finite weight is refused with a message, not packed
 one = np.ones(16, np.float32)
 assert pack(8, 16, 3, 1, 0, 1, 1, 1, 1, P(bad), P(one), P(one), P(one), P(one), (ctypes.c_ulonglong * 4)()) != 0 and b"non-finite" in lib.sn_last_error()

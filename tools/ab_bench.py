@@ -61,16 +61,18 @@ def main():
                 continue
             j = json.loads(p.stdout.strip().splitlines()[-1])
             k = j["kernels_ms_per_step"]
-            res[name].append((j["value"], [k.get(x, float("nan")) for x in keys]))
+            res[name].append((j["value"], [k.get(x, float("nan")) for x in keys], j.get("similarity_net", {}).get("value")))
             sim = ("  simil %.0f patches/s (s_conv1_2 %.3f ms)" % (j["similarity_net"]["value"], j["similarity_net"]["kernels_ms_per_step"].get("s_conv1_2", float("nan")))) if "similarity_net" in j else ""
             print("round %d %-12s %8.1f cubes/s  %s%s" % (r, name, j["value"], "  ".join("%s %.3f" % (x, k.get(x, float("nan"))) for x in keys), sim), flush=True)
     print("== medians")
     for name, _ in variants:
         if not res[name]:
             continue
-        med = statistics.median(v for v, _ in res[name])
-        km = [statistics.median(ks[i] for _, ks in res[name]) for i in range(len(keys))]
-        print("%-12s %8.1f cubes/s  %s" % (name, med, "  ".join("%s %.3f" % (x, v) for x, v in zip(keys, km))), flush=True)
+        med = statistics.median(v for v, _, _ in res[name])
+        km = [statistics.median(ks[i] for _, ks, _ in res[name]) for i in range(len(keys))]
+        sim = [s for _, _, s in res[name] if s is not None]
+        print("%-12s %8.1f cubes/s  %s%s" % (name, med, "  ".join("%s %.3f" % (x, v) for x, v in zip(keys, km)),
+                                             ("  simil %.0f patches/s" % statistics.median(sim)) if sim else ""), flush=True)
 
 
 if __name__ == "__main__":

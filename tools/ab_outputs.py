@@ -24,12 +24,13 @@ def main():
     out = {}
     for s, n, n_vp in ((32, 3, 2), (16, 2, 3), (12, 2, 1)):
         sc = synthetic.synthetic_scene(n, n_vp, s=s, seed=s, hw=(600, 800))
-        for prec in ("f16x3", "f16x3p", "f16m8", "f16"):
-            with surfacenet_amd.Context(cube_D=s, max_samples=n * n_vp, precision=prec) as ctx:
+        # (precision, conv4_fp8): the four modes, and the default mode with the dilated chain back on three fp16 MFMAs
+        for prec, c4 in (("f16x3", True), ("f16x3", False), ("f16x3p", True), ("f16m8", True), ("f16", True)):
+            with surfacenet_amd.Context(cube_D=s, max_samples=n * n_vp, precision=prec, conv4_fp8=c4) as ctx:
                 ctx.load_param_values(weights.synthetic_param_values(1))
                 ctx.set_cameras(sc["cams"]); ctx.set_images(sc["imgs"])
                 fused, unfused, _ = ctx.cvc_forward(sc["pairs"], sc["xyz"], sc["resol"], sc["w"])
-            out["s%d_%s_unfused" % (s, prec)] = unfused
+            out["s%d_%s%s_unfused" % (s, prec, "" if c4 else "_conv4x3")] = unfused
     # the 2-D form of the kernel: similarityNet embeddings of 40 patches in the three arithmetic modes
     sc = synthetic.synthetic_scene(1, 1, s=16, seed=1, hw=(300, 400))
     rs = np.random.RandomState(2)

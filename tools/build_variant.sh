@@ -9,12 +9,13 @@ OUT="$ROOT/gpurun_abl/$NAME"
 mkdir -p "$OUT"
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fvisibility=hidden -DSN_DEBUG_HOOKS -Wall -Wno-unused-function $*"
 cd "$ROOT/surfacenet_amd/csrc"
-pids=()
-for f in sn_api sn_post sn_simil; do
-  /opt/rocm/bin/hipcc $FLAGS -c -o "$OUT/$f.o" $f.hip &
-  pids+=($!)
+SRCS=$(sed -n 's/^SRCS *= *//p' Makefile)      # the library's translation units, as the Makefile lists them
+pids=(); objs=()
+for f in $SRCS; do
+  /opt/rocm/bin/hipcc $FLAGS -c -o "$OUT/${f%.hip}.o" $f &
+  pids+=($!); objs+=("$OUT/${f%.hip}.o")
 done
 for p in "${pids[@]}"; do wait $p; done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -Wl,--version-script=exports.map -o "$OUT/libsurfacenet_hip.so" "$OUT"/sn_api.o "$OUT"/sn_post.o "$OUT"/sn_simil.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -Wl,--version-script=exports.map -o "$OUT/libsurfacenet_hip.so" "${objs[@]}"
 rm -f "$OUT"/*.o
 echo "$OUT/libsurfacenet_hip.so  [$*]"
