@@ -25,6 +25,8 @@ extern "C" {
 #endif
 
 #define SN_ABI_VERSION 2   /* 2 (round 6): + sn_mfma_probe, sn_set_conv4_fp8; sn_calibrate_dev refuses the all-MX mode with SN_ERR_STATE (since round 5) */
+/* Added since, without a version change (additions only): sn_ptcubes, sn_ptcubes_dev, sn_ptcubes_sparse_dev and sn_ptcubes_cfg - the
+ * point-seeded cube list. */
 
 /* The library is built with -fvisibility=hidden: the functions below are its WHOLE dynamic symbol table
  * (tests/test_abi.py compares `nm -D` with this header). */
@@ -249,6 +251,37 @@ SN_API int sn_nn_dist2(sn_ctx *ctx, long long n_to, const double *to, long long 
  * ((plane[0]*x + plane[1]*y) + plane[2]*z) + plane[3] > 0. Either output may be NULL (its inputs are then not read). */
 SN_API int sn_point_flags(sn_ctx *ctx, long long n, const double *xyz, const unsigned char *mask, const int *dims, const double *bb_min, double res,
                           const double *plane, unsigned char *in_mask, unsigned char *above);
+
+/* ---- point-seeded cube list (scene.quantizePts2Cubes, utils/scene.py:63-108; the initialPtsNamePattern branch of main_reconstruct.py:52-60;
+ * DESIGN.md section 4.8) -------------------------------------------------------------------------------------------------------------------
+ * The cubes around a point cloud: a point is kept when lo <= p <= hi on every axis (has_box; compared in float64), shift = the per-axis minimum of
+ * the kept points, q = (p - shift) // stride_q per axis with numpy's floor_divide - the subtraction in the points' type, the division in float32
+ * (compute_f64 = 0: float32 points only; stride_q is then rounded to float32) or float64 - and every kept point contributes the two cells q and
+ * q + 1 (the floor corner and the diagonal corner: what the reference's vstack + row-wise unique yields). The result is the set of distinct cells in
+ * ascending (i, j, k): ijk (n_cells,3) uint32 and xyz (n_cells,3) float32 = float32((double(ijk) * stride_xyz + double(shift)) - half).
+ * Variable-length result, as sn_dense2sparse's lists: the caller's arrays hold `cap` cells (2 n always suffices), *n_cells receives the number
+ * produced. When more than cap are needed nothing is written, *n_cells holds the number needed and SN_ERR_ARG is returned. SN_ERR_ARG too for a
+ * non-finite coordinate and for a cloud spanning 2^21 or more strides on an axis (cell indices are below 2^21). No kept point: *n_cells = 0.
+ * n <= 2^27. All three forms return when the work is done. */
+typedef struct sn_ptcubes_cfg {
+    int pts_f64;             /* points are float64 (else float32) */
+    int compute_f64;         /* the type numpy promotes (pts - shift) // stride to; float64 points require 1 */
+    double stride_q;         /* the stride the cell index divides by */
+    double stride_xyz;       /* the stride as float64, for xyz */
+    double half;             /* cube_D_mm / 2 */
+    int has_box;
+    double lo[3], hi[3];     /* BB_min - cube_D_mm / 2, BB_max + cube_D_mm / 2 */
+} sn_ptcubes_cfg;
+SN_API int sn_ptcubes(sn_ctx *ctx, long long n, const void *pts, const sn_ptcubes_cfg *cfg, long long cap, uint32_t *ijk, float *xyz,
+                      long long *n_cells);
+SN_API int sn_ptcubes_dev(sn_ctx *ctx, long long n, const void *pts_dev, const sn_ptcubes_cfg *cfg, long long cap, uint32_t *ijk_dev,
+                          float *xyz_dev, long long *n_cells);
+/* The same for the masked voxels of a scene's packed sparse lists (offsets (n_cubes+1) int64, vxl_ijk (total,3) uint8, mask (total) uint8, per-cube
+ * xyz (n_cubes,3) and resol (n_cubes) float32), the points never leaving HBM: p = float32(vxl_ijk) * resol + xyz of the voxel's cube, in float32,
+ * as sparseCubes.sparse_xyz forms them (cfg->pts_f64 = 0). */
+SN_API int sn_ptcubes_sparse_dev(sn_ctx *ctx, int n_cubes, long long total, const int64_t *offsets_dev, const unsigned char *vxl_ijk_dev,
+                                 const unsigned char *mask_dev, const float *cube_xyz_dev, const float *cube_resol_dev, const sn_ptcubes_cfg *cfg,
+                                 long long cap, uint32_t *ijk_dev, float *xyz_dev, long long *n_cells);
 
 /* ---- similarityNet / early rejection (main_reconstruct.py:76-97) ---------------- */
 /* pickle.load + set_all_param_values([embedding layer, similarity layer]) of similarityNet_inference

@@ -21,6 +21,7 @@ ABI_SYMBOLS = [
     "sn_ray_pool", "sn_ray_pool_dev", "sn_dense2sparse", "sn_dense2sparse_dev",
     "sn_denoise", "sn_denoise_dev", "sn_adapthresh", "sn_adapthresh_dev",
     "sn_point_reduce", "sn_nn_dist2", "sn_point_flags",
+    "sn_ptcubes", "sn_ptcubes_dev", "sn_ptcubes_sparse_dev",
     "sn_simil_load_weights", "sn_crop_patches", "sn_patch2embedding", "sn_crop_embed", "sn_embeddingpair2simil", "sn_embeddings2simil",
     "sn_project_points",
     "sn_comm_unique_id", "sn_comm_init", "sn_comm_init_deadline", "sn_comm_info", "sn_allgather_f32_dev", "sn_allgather_f32_dev_overlap", "sn_comm_wait", "sn_allgatherv_counts", "sn_allgatherv_bytes_dev",
@@ -41,6 +42,11 @@ class SparseCfg(ctypes.Structure):
 class AdapthreshCfg(ctypes.Structure):
     _fields_ = [("N_refine_iter", ctypes.c_int), ("D_cube", ctypes.c_int), ("init_probThresh", ctypes.c_double), ("max_probThresh", ctypes.c_double),
                 ("rayPool_thresh", ctypes.c_double), ("beta", ctypes.c_double)]
+
+
+class PtCubesCfg(ctypes.Structure):
+    _fields_ = [("pts_f64", ctypes.c_int), ("compute_f64", ctypes.c_int), ("stride_q", ctypes.c_double), ("stride_xyz", ctypes.c_double),
+                ("half", ctypes.c_double), ("has_box", ctypes.c_int), ("lo", ctypes.c_double * 3), ("hi", ctypes.c_double * 3)]
 
 
 class Calibration(ctypes.Structure):
@@ -111,6 +117,10 @@ def load():
         "sn_point_reduce": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_double, c_void_p, P(c_int)]),
         "sn_nn_dist2": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_double, c_void_p]),
         "sn_point_flags": (c_int, [c_void_p, ctypes.c_longlong] + [c_void_p] * 4 + [ctypes.c_double] + [c_void_p] * 3),
+        "sn_ptcubes": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, P(PtCubesCfg), ctypes.c_longlong, c_void_p, c_void_p, P(ctypes.c_longlong)]),
+        "sn_ptcubes_dev": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, P(PtCubesCfg), ctypes.c_longlong, c_void_p, c_void_p, P(ctypes.c_longlong)]),
+        "sn_ptcubes_sparse_dev": (c_int, [c_void_p, c_int, ctypes.c_longlong] + [c_void_p] * 5 + [P(PtCubesCfg), ctypes.c_longlong, c_void_p, c_void_p,
+                                          P(ctypes.c_longlong)]),
         "sn_simil_load_weights": (c_int, [c_void_p, c_void_p, c_size_t, P(ParamDesc), c_int]),
         "sn_crop_patches": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
         "sn_patch2embedding": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),

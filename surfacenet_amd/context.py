@@ -480,6 +480,95 @@ class Context(object):
                                             _lib.ptr(pl), _lib.ptr(in_mask), _lib.ptr(above)))
         return (None if in_mask is None else in_mask.view(bool)), (None if above is None else above.view(bool))
 
+    @staticmethod
+    def _ptcubes_cfg(pts_f64, compute_f64, stride_q, stride_xyz, half, box):
+        cfg = _lib.PtCubesCfg(int(bool(pts_f64)), int(bool(compute_f64)), float(stride_q), float(stride_xyz), float(half), int(box is not None))
+        if box is not None:
+            b = np.asarray(box, dtype=np.float64).reshape(2, 3)
+            cfg.lo[:], cfg.hi[:] = b[0].tolist(), b[1].tolist()
+        return cfg
+
+    def _ptcubes_sized(self, call, cap):
+        """Runs call(cap, n_cells) -> status; a list longer than cap comes back as SN_ERR_ARG with the length needed: one retry at that length.
+        Returns (n_cells, cap used)."""
+        n_cells = ctypes.c_longlong(0)
+        rc = call(cap, n_cells)
+        if rc == -1 and n_cells.value > cap:
+            cap = n_cells.value
+            rc = call(cap, n_cells)
+        _lib.check(rc)
+        return n_cells.value, cap
+
+    def ptcubes(self, pts, stride_q, stride_xyz, half, compute_f64, box=None, cap=None):
+        """The cell list of scene.quantizePts2Cubes (sn_ptcubes): pts (n,3) float32 or float64; stride_q the stride of the cell index (in the
+        type compute_f64 names), stride_xyz the stride as float64, half = cube_D_mm / 2, box (2,3) = [lo, hi] or None. Returns (ijk (m,3) uint32,
+        xyz (m,3) float32), cells in ascending (i, j, k); m = 0 when no point is kept."""
+        p = np.asarray(pts)
+        if p.dtype not in (np.float32, np.float64):
+            p = p.astype(np.float64)
+        p = np.ascontiguousarray(p.reshape(-1, 3))
+        n = p.shape[0]
+        cfg = self._ptcubes_cfg(p.dtype == np.float64, compute_f64, stride_q, stride_xyz, half, box)
+        out = {}
+
+        def call(cap, n_cells):
+            out["ijk"], out["xyz"] = np.empty((cap, 3), np.uint32), np.empty((cap, 3), np.float32)
+            return self._lib.sn_ptcubes(self._h, n, _lib.ptr(p), ctypes.byref(cfg), cap, _lib.ptr(out["ijk"]), _lib.ptr(out["xyz"]), ctypes.byref(n_cells))
+
+        m, _ = self._ptcubes_sized(call, min(2 * n, 1 << 22) if cap is None else int(cap))
+        return out["ijk"][:m].copy(), out["xyz"][:m].copy()
+
+    def _ptcubes_dev_sized(self, run, cap):
+        """The device-output forms: run(cap, ijk_dev, xyz_dev, n_cells) -> status. Returns the arrays on the host."""
+        bufs = []
+
+        def call(cap, n_cells):
+            for b in bufs:
+                self.dev_free(b)
+            bufs[:] = [self.dev_alloc(max(12 * cap, 16)), self.dev_alloc(max(12 * cap, 16))]
+            return run(cap, bufs[0], bufs[1], n_cells)
+
+        try:
+            m, _ = self._ptcubes_sized(call, cap)
+            ijk, xyz = np.empty((m, 3), np.uint32), np.empty((m, 3), np.float32)
+            if m:
+                self.d2h(ijk, bufs[0])
+                self.d2h(xyz, bufs[1])
+        finally:
+            for b in bufs:
+                self.dev_free(b)
+        return ijk, xyz
+
+    def ptcubes_dev(self, n, pts_dev, pts_f64, stride_q, stride_xyz, half, compute_f64, box=None, cap=None):
+        """ptcubes for n points already in HBM (sn_ptcubes_dev); the cell list is built in device memory and returned on the host."""
+        cfg = self._ptcubes_cfg(pts_f64, compute_f64, stride_q, stride_xyz, half, box)
+        run = lambda cap, ijk_dev, xyz_dev, n_cells: self._lib.sn_ptcubes_dev(self._h, int(n), pts_dev, ctypes.byref(cfg), cap, ijk_dev, xyz_dev,
+                                                                              ctypes.byref(n_cells))
+        return self._ptcubes_dev_sized(run, min(2 * int(n), 1 << 22) if cap is None else int(cap))
+
+    def ptcubes_sparse(self, offsets, vxl_ijk, mask, cube_xyz, cube_resol, stride_q, stride_xyz, half, compute_f64, box=None, cap=None):
+        """The cell list around the masked voxels of packed sparse lists (sn_ptcubes_sparse_dev): offsets (n+1,) int64, vxl_ijk (T,3) uint8, mask
+        (T,) bool, cube_xyz (n,3) / cube_resol (n,) float32. The voxels' points - float32(ijk) * resol + xyz of their cube - are formed on the
+        GPU and never reach the host."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        n = offsets.size - 1
+        ijk = np.ascontiguousarray(vxl_ijk, dtype=np.uint8).reshape(-1, 3)
+        m = np.ascontiguousarray(mask, dtype=bool).reshape(-1).view(np.uint8)
+        T = int(offsets[-1])
+        if ijk.shape[0] != T or m.size != T:
+            raise ValueError("offsets end at %d voxels: %d ijk rows, %d mask entries" % (T, ijk.shape[0], m.size))
+        cx = np.ascontiguousarray(cube_xyz, dtype=np.float32).reshape(n, 3)
+        cr = np.ascontiguousarray(cube_resol, dtype=np.float32).reshape(n)
+        cfg = self._ptcubes_cfg(False, compute_f64, stride_q, stride_xyz, half, box)
+        dev = [self.upload(a) for a in (offsets, ijk, m, cx, cr)]
+        try:
+            run = lambda cap, ijk_dev, xyz_dev, n_cells: self._lib.sn_ptcubes_sparse_dev(self._h, n, T, dev[0], dev[1], dev[2], dev[3], dev[4],
+                                                                                         ctypes.byref(cfg), cap, ijk_dev, xyz_dev, ctypes.byref(n_cells))
+            return self._ptcubes_dev_sized(run, min(2 * T, 1 << 22) if cap is None else int(cap))
+        finally:
+            for d in dev:
+                self.dev_free(d)
+
     def dev_alloc(self, nbytes):
         p = self._lib.sn_dev_alloc(self._h, int(nbytes))
         if not p:

@@ -16,7 +16,6 @@
 namespace sn {
 
 constexpr int PE_NT = 256;
-constexpr int PE_SCAN = 1024;                         // elements per workgroup of the scan (256 threads x 4)
 constexpr unsigned long long PE_EMPTY = ~0ull;        // free hash slot (cell keys are < 2^63)
 constexpr unsigned char PE_UND = 0, PE_IN = 1, PE_OUT = 2;   // reduction states
 
@@ -175,36 +174,6 @@ __global__ void __launch_bounds__(PE_NT) pe_insert_kernel(PEBuildArgs a)
     if (lane == head && s >= 0) base = atomicAdd(a.count + s, next - lane);
     base = __shfl(base, head);
     if (i < a.n) { a.slot[i] = s; a.pos[i] = base + (lane - head); }
-}
-
-// exclusive scan of in[0, n) within each block of PE_SCAN elements; block totals to sums (if given). in may alias out.
-__global__ void __launch_bounds__(PE_NT) pe_scan_kernel(const int *in, int *out, int n, int *sums)
-{
-    __shared__ int sh[PE_NT];
-    const int tid = threadIdx.x;
-    const long long base = (long long)blockIdx.x * PE_SCAN + 4 * tid;
-    int v[4], t = 0;
-    for (int k = 0; k < 4; ++k) { v[k] = base + k < n ? in[base + k] : 0; t += v[k]; }
-    sh[tid] = t;
-    __syncthreads();
-    for (int off = 1; off < PE_NT; off <<= 1) {
-        const int add = tid >= off ? sh[tid - off] : 0;
-        __syncthreads();
-        sh[tid] += add;
-        __syncthreads();
-    }
-    int run = sh[tid] - t;
-    if (sums && tid == PE_NT - 1) sums[blockIdx.x] = sh[tid];
-    for (int k = 0; k < 4; ++k) {
-        if (base + k < n) out[base + k] = run;
-        run += v[k];
-    }
-}
-
-__global__ void __launch_bounds__(PE_NT) pe_scan_add_kernel(int *out, int n, const int *offs)
-{
-    const long long i = (long long)blockIdx.x * PE_NT + threadIdx.x;
-    if (i < n) out[i] += offs[i / PE_SCAN];
 }
 
 __global__ void __launch_bounds__(PE_NT) pe_scatter_kernel(PEBuildArgs a)

@@ -2,6 +2,7 @@
 // mask / plane flags of PointCompareMain (experiments/DTU/eval_ply.m). Host arrays in and out; the device workspace is the context's.
 #include "sn_internal.h"
 #include "pointeval.h"
+#include "scan.h"
 
 namespace {
 
@@ -67,13 +68,6 @@ unsigned table_cap(long long n)
     return cap;
 }
 
-size_t scan_sums(size_t n)
-{
-    size_t total = 1;
-    while (n > (size_t)PE_SCAN) { n = (n + PE_SCAN - 1) / PE_SCAN; total += n; }
-    return total;
-}
-
 struct GridBufs {
     unsigned long long *keys; int *start, *count, *slot, *pos, *idx, *rank_s, *sums; double *xyz_s;
     unsigned cap; int n;
@@ -85,23 +79,6 @@ void grid_carve(Carve &cv, GridBufs &b, long long n, bool with_rank)
     b.keys = cv.get<unsigned long long>(b.cap); b.start = cv.get<int>(b.cap); b.count = cv.get<int>(b.cap); b.sums = cv.get<int>(scan_sums(b.cap));
     b.slot = cv.get<int>(n); b.pos = cv.get<int>(n); b.idx = cv.get<int>(n); b.xyz_s = cv.get<double>(3 * (size_t)n);
     b.rank_s = with_rank ? cv.get<int>(n) : nullptr;
-}
-
-int pe_scan(sn_ctx *c, const int *in, int *out, int n, int *sums)
-{
-    const int nb = (n + PE_SCAN - 1) / PE_SCAN;
-    if (nb <= 1) {
-        hipLaunchKernelGGL(pe_scan_kernel, dim3(1), dim3(PE_NT), 0, c->stream, in, out, n, (int *)nullptr);
-        HIPCHK(hipGetLastError());
-        return SN_OK;
-    }
-    hipLaunchKernelGGL(pe_scan_kernel, dim3((unsigned)nb), dim3(PE_NT), 0, c->stream, in, out, n, sums);
-    HIPCHK(hipGetLastError());
-    int rc = pe_scan(c, sums, sums, nb, sums + nb);
-    if (rc != SN_OK) return rc;
-    hipLaunchKernelGGL(pe_scan_add_kernel, dim3((unsigned)((n + PE_NT - 1) / PE_NT)), dim3(PE_NT), 0, c->stream, out, n, (const int *)sums);
-    HIPCHK(hipGetLastError());
-    return SN_OK;
 }
 
 // Buckets xyz_dev (n points inside box) on cells of size h: the hash table and the per-cell counts; with `sort`, also the scan and the
@@ -130,7 +107,7 @@ int pe_build(sn_ctx *c, const GridBufs &b, const double *xyz_dev, const long lon
     hipLaunchKernelGGL(pe_insert_kernel, dim3(nb), dim3(PE_NT), 0, c->stream, a);
     HIPCHK(hipGetLastError());
     if (!sort) return SN_OK;
-    int rc = pe_scan(c, b.count, b.start, (int)b.cap, b.sums);
+    int rc = scan_exclusive(c, b.count, b.start, (int)b.cap, b.sums);
     if (rc != SN_OK) return rc;
     hipLaunchKernelGGL(pe_scatter_kernel, dim3(nb), dim3(PE_NT), 0, c->stream, a);
     HIPCHK(hipGetLastError());

@@ -1,0 +1,230 @@
+// sn_ptcubes.hip — C ABI of the point-seeded cube list (ptcubes.h): scene.quantizePts2Cubes (utils/scene.py:63-108) for a point cloud in host or
+// device memory, and for the masked voxels of a scene's sparse lists without the points ever being on the host (the coarse-to-fine step).
+#include "sn_internal.h"
+#include "ptcubes.h"
+#include "scan.h"
+
+namespace {
+
+constexpr long long PC_MAX_POINTS = 1ll << 27;       // hash tables of 4n slots stay within 2^29
+constexpr long long PC_DENSE_CELLS = 1ll << 27;      // largest grid of cells the occupancy bitmap is used for (16 MiB of bits)
+
+struct SyncOnExit {                                  // temporary device buffers are freed on return: the stream must be done with them
+    sn_ctx *c;
+    ~SyncOnExit() { (void)hipStreamSynchronize(c->stream); }
+};
+
+unsigned blocks(long long n) { return (unsigned)((n + PC_NT - 1) / PC_NT); }
+
+// ascending sort of list[0, n), n a power of two >= PC_TILE
+int pc_sort(sn_ctx *c, unsigned long long *list, long long n)
+{
+    ProfScope ps(c, "pc_sort", 0, 0.0);
+    hipLaunchKernelGGL(pc_bitonic_tile_kernel, dim3((unsigned)(n / PC_TILE)), dim3(PC_NT), 0, c->stream, list, 2ll, (long long)PC_TILE);
+    for (long long k = 2 * PC_TILE; k <= n; k <<= 1) {
+        for (long long j = k / 2; j >= PC_TILE; j >>= 1)
+            hipLaunchKernelGGL(pc_bitonic_global_kernel, dim3(blocks(n / 2)), dim3(PC_NT), 0, c->stream, list, n, j, k);
+        hipLaunchKernelGGL(pc_bitonic_tile_kernel, dim3((unsigned)(n / PC_TILE)), dim3(PC_NT), 0, c->stream, list, k, k);
+    }
+    HIPCHK(hipGetLastError());
+    return SN_OK;
+}
+
+int pc_check_cfg(const sn_ptcubes_cfg *cfg, long long n, long long cap, const long long *n_cells)
+{
+    if (!cfg || !n_cells) return fail(SN_ERR_ARG, "null argument");
+    if (n < 0 || n > PC_MAX_POINTS) return fail(SN_ERR_ARG, "n = %lld: 0 <= n <= %lld points", n, PC_MAX_POINTS);
+    if (cap < 0) return fail(SN_ERR_ARG, "cap must be >= 0");
+    if (cfg->pts_f64 && !cfg->compute_f64) return fail(SN_ERR_ARG, "float64 points divide in float64");
+    if (!(cfg->stride_q > 0.0) || !std::isfinite(cfg->stride_q) || !std::isfinite(cfg->stride_xyz) || !std::isfinite(cfg->half))
+        return fail(SN_ERR_ARG, "stride = %g must be finite and > 0 (stride_xyz = %g, half = %g finite)", cfg->stride_q, cfg->stride_xyz, cfg->half);
+    if (!cfg->compute_f64 && !((double)(float)cfg->stride_q > 0.0)) return fail(SN_ERR_ARG, "stride = %g vanishes in float32", cfg->stride_q);
+    return SN_OK;
+}
+
+// The whole computation on device-resident points. out_host: ijk / xyz are host arrays (staged through temporary device buffers).
+template <typename P, typename T>
+int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap, bool out_host, uint32_t *ijk, float *xyz, long long *n_cells)
+{
+    *n_cells = 0;
+    const long long n = src.n;
+    if (n == 0) return SN_OK;
+    src.has_box = cfg->has_box;
+    for (int d = 0; d < 3; ++d) { src.lo[d] = cfg->lo[d]; src.hi[d] = cfg->hi[d]; }
+    TmpDev t;
+    SyncOnExit sync{c};
+    PCStats *d_st = t.get<PCStats>(1);
+    if (!d_st) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
+    PCStats st;
+    {
+        ProfScope ps(c, "pc_bounds", 0, (double)n * 3.0 * sizeof(P));
+        hipLaunchKernelGGL(pc_stats_init_kernel, dim3(1), dim3(64), 0, c->stream, d_st);
+        hipLaunchKernelGGL((pc_bounds_kernel<P>), dim3(std::min(blocks(n), 2048u)), dim3(PC_NT), 0, c->stream, src, d_st);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (st.flags & PC_FLAG_NONFINITE) return fail(SN_ERR_ARG, "a coordinate is not finite");
+    if (st.kept == 0) return SN_OK;                  // no point (left by the box): no cell
+
+    PCCellArgs<P, T> a;
+    memset(&a, 0, sizeof a);
+    a.s = src; a.st = d_st; a.stride = (T)cfg->stride_q;
+    PCEmitArgs e;
+    memset(&e, 0, sizeof e);
+    e.stride = cfg->stride_xyz; e.half = cfg->half;
+    for (int d = 0; d < 3; ++d) {
+        a.shift[d] = (P)pc_decode(st.kmin[d]);
+        e.shift[d] = (double)a.shift[d];
+        const P rel = (P)pc_decode(st.kmax[d]) - a.shift[d];
+        const T top = pc_floor_div<T>((T)rel, a.stride);       // floor_divide is monotone in its numerator: the largest index of the axis
+        if (!(top >= (T)0 && top + (T)1 < (T)PC_AXIS_MAX))
+            return fail(SN_ERR_ARG, "axis %d spans %g strides: cell indices must stay below 2^%d", d, (double)top + 2.0, PC_AXIS_BITS);
+        a.dim[d] = e.dim[d] = (long long)top + 2;
+    }
+    const bool dense = a.dim[0] * a.dim[1] <= PC_DENSE_CELLS && a.dim[0] * a.dim[1] * a.dim[2] <= PC_DENSE_CELLS;
+    long long total = 0;
+    int n_words = 0;
+    int *start = nullptr;
+    unsigned long long *list = nullptr;
+    if (dense) {
+        n_words = (int)((a.dim[0] * a.dim[1] * a.dim[2] + 63) / 64);
+        a.bitmap = t.get<unsigned long long>(n_words);
+        int *count = t.get<int>((size_t)n_words + 1), *sums = t.get<int>(scan_sums((size_t)n_words + 1));
+        start = t.get<int>((size_t)n_words + 1);
+        if (!a.bitmap || !count || !sums || !start) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
+        HIPCHK(hipMemsetAsync(a.bitmap, 0, sizeof(unsigned long long) * (size_t)n_words, c->stream));
+        HIPCHK(hipMemsetAsync(count + n_words, 0, sizeof(int), c->stream));
+        {
+            ProfScope ps(c, "pc_cells", 0, (double)n * 3.0 * sizeof(P) + (double)n_words * 8.0);
+            hipLaunchKernelGGL((pc_mark_kernel<P, T>), dim3(blocks(n)), dim3(PC_NT), 0, c->stream, a);
+            HIPCHK(hipGetLastError());
+        }
+        ProfScope ps(c, "pc_scan", 0, (double)n_words * 20.0);
+        hipLaunchKernelGGL(pc_popc_kernel, dim3(blocks(n_words)), dim3(PC_NT), 0, c->stream, (const unsigned long long *)a.bitmap, n_words, count);
+        int rc = scan_exclusive(c, count, start, n_words + 1, sums);       // start[n_words] = number of cells
+        if (rc != SN_OK) return rc;
+        int tot = 0;
+        HIPCHK(hipMemcpyAsync(&tot, start + n_words, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        total = tot;
+    } else {
+        unsigned tcap = 2048;
+        while (tcap < 4ull * (unsigned long long)n) tcap <<= 1;
+        a.mask = tcap - 1;
+        a.table = t.get<unsigned long long>(tcap);
+        a.list = list = t.get<unsigned long long>(tcap / 2);       // >= 2n keys, a power of two >= PC_TILE: room for the sort's padding
+        a.n_list = t.get<unsigned long long>(1);
+        if (!a.table || !a.list || !a.n_list) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
+        HIPCHK(hipMemsetAsync(a.table, 0xff, sizeof(unsigned long long) * (size_t)tcap, c->stream));
+        HIPCHK(hipMemsetAsync(a.n_list, 0, sizeof(unsigned long long), c->stream));
+        {
+            ProfScope ps(c, "pc_cells", 0, (double)n * 3.0 * sizeof(P) + (double)tcap * 8.0);
+            hipLaunchKernelGGL((pc_insert_kernel<P, T>), dim3(blocks(n)), dim3(PC_NT), 0, c->stream, a);
+            HIPCHK(hipGetLastError());
+        }
+        unsigned long long m = 0;
+        HIPCHK(hipMemcpyAsync(&m, a.n_list, sizeof m, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        total = (long long)m;
+    }
+    if (st.flags & PC_FLAG_EXTENT) return fail(SN_ERR_STATE, "sn_ptcubes: a cell index left the extent computed from the cloud's bounds");
+    *n_cells = total;
+    if (total > cap) return fail(SN_ERR_ARG, "the outputs hold %lld cells, %lld are needed", cap, total);
+    if (total == 0) return SN_OK;
+    if (!out_host && (!ijk || !xyz)) return fail(SN_ERR_ARG, "null output");
+    e.ijk = ijk; e.xyz = xyz; e.cap = cap;
+    if (out_host) {
+        e.ijk = t.get<uint32_t>(3 * (size_t)total); e.xyz = t.get<float>(3 * (size_t)total); e.cap = total;
+        if (!e.ijk || !e.xyz) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
+    }
+    if (dense) {
+        ProfScope ps(c, "pc_emit", 0, (double)total * 24.0 + (double)n_words * 12.0);
+        hipLaunchKernelGGL(pc_emit_dense_kernel, dim3(blocks(n_words)), dim3(PC_NT), 0, c->stream, (const unsigned long long *)a.bitmap, (const int *)start, n_words, e);
+        HIPCHK(hipGetLastError());
+    } else {
+        long long p2 = PC_TILE;
+        while (p2 < total) p2 <<= 1;
+        if (p2 > total) hipLaunchKernelGGL(pc_pad_kernel, dim3(blocks(p2 - total)), dim3(PC_NT), 0, c->stream, list, total, p2);
+        int rc = pc_sort(c, list, p2);
+        if (rc != SN_OK) return rc;
+        ProfScope ps(c, "pc_emit", 0, (double)total * 32.0);
+        hipLaunchKernelGGL(pc_emit_keys_kernel, dim3(blocks(total)), dim3(PC_NT), 0, c->stream, (const unsigned long long *)list, total, e);
+        HIPCHK(hipGetLastError());
+    }
+    if (out_host) {
+        HIPCHK(hipMemcpyAsync(ijk, e.ijk, sizeof(uint32_t) * 3 * (size_t)total, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(xyz, e.xyz, sizeof(float) * 3 * (size_t)total, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return SN_OK;
+}
+
+int pc_points(sn_ctx *c, long long n, const void *pts_dev, const sn_ptcubes_cfg *cfg, long long cap, bool out_host, uint32_t *ijk, float *xyz,
+              long long *n_cells)
+{
+    if (cfg->pts_f64) {
+        PCPoints<double> s;
+        memset(&s, 0, sizeof s);
+        s.xyz = static_cast<const double *>(pts_dev); s.n = n;
+        return pc_run<double, double>(c, s, cfg, cap, out_host, ijk, xyz, n_cells);
+    }
+    PCPoints<float> s;
+    memset(&s, 0, sizeof s);
+    s.xyz = static_cast<const float *>(pts_dev); s.n = n;
+    return cfg->compute_f64 ? pc_run<float, double>(c, s, cfg, cap, out_host, ijk, xyz, n_cells)
+                            : pc_run<float, float>(c, s, cfg, cap, out_host, ijk, xyz, n_cells);
+}
+
+}  // namespace
+
+extern "C" int sn_ptcubes_dev(sn_ctx *c, long long n, const void *pts_dev, const sn_ptcubes_cfg *cfg, long long cap, uint32_t *ijk_dev, float *xyz_dev,
+                              long long *n_cells)
+{
+    if (!c) return fail(SN_ERR_ARG, "null context");
+    int rc;
+    if ((rc = pc_check_cfg(cfg, n, cap, n_cells)) != SN_OK) return rc;
+    if (n > 0 && !pts_dev) return fail(SN_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(c->device));
+    return pc_points(c, n, pts_dev, cfg, cap, false, ijk_dev, xyz_dev, n_cells);
+}
+
+extern "C" int sn_ptcubes(sn_ctx *c, long long n, const void *pts, const sn_ptcubes_cfg *cfg, long long cap, uint32_t *ijk, float *xyz, long long *n_cells)
+{
+    if (!c) return fail(SN_ERR_ARG, "null context");
+    int rc;
+    if ((rc = pc_check_cfg(cfg, n, cap, n_cells)) != SN_OK) return rc;
+    if (n > 0 && !pts) return fail(SN_ERR_ARG, "null argument");
+    if (cap > 0 && (!ijk || !xyz)) return fail(SN_ERR_ARG, "null output");
+    HIPCHK(hipSetDevice(c->device));
+    TmpDev t;
+    const size_t bytes = 3 * (size_t)n * (cfg->pts_f64 ? sizeof(double) : sizeof(float));
+    unsigned char *d_pts = t.get<unsigned char>(bytes);
+    if (!d_pts) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
+    if (n) HIPCHK(hipMemcpyAsync(d_pts, pts, bytes, hipMemcpyHostToDevice, c->stream));
+    rc = pc_points(c, n, d_pts, cfg, cap, true, ijk, xyz, n_cells);
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+extern "C" int sn_ptcubes_sparse_dev(sn_ctx *c, int n_cubes, long long total, const int64_t *offsets_dev, const unsigned char *vxl_ijk_dev,
+                                     const unsigned char *mask_dev, const float *cube_xyz_dev, const float *cube_resol_dev, const sn_ptcubes_cfg *cfg,
+                                     long long cap, uint32_t *ijk_dev, float *xyz_dev, long long *n_cells)
+{
+    if (!c) return fail(SN_ERR_ARG, "null context");
+    int rc;
+    if ((rc = pc_check_cfg(cfg, total, cap, n_cells)) != SN_OK) return rc;
+    if (cfg->pts_f64) return fail(SN_ERR_ARG, "the voxels of sparse lists are float32 points");
+    if (n_cubes < 0) return fail(SN_ERR_ARG, "n_cubes must be >= 0");
+    if (n_cubes == 0) { *n_cells = 0; return total == 0 ? SN_OK : fail(SN_ERR_ARG, "offsets table of 0 cubes holds %lld voxels", total); }
+    if (!offsets_dev || !cube_xyz_dev || !cube_resol_dev || (total > 0 && (!vxl_ijk_dev || !mask_dev))) return fail(SN_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(c->device));
+    PCPoints<float> s;
+    memset(&s, 0, sizeof s);
+    s.off = reinterpret_cast<const long long *>(offsets_dev); s.vijk = vxl_ijk_dev; s.vmask = mask_dev; s.cxyz = cube_xyz_dev; s.cresol = cube_resol_dev;
+    s.n_cubes = n_cubes; s.n = total;
+    return cfg->compute_f64 ? pc_run<float, double>(c, s, cfg, cap, false, ijk_dev, xyz_dev, n_cells)
+                            : pc_run<float, float>(c, s, cfg, cap, false, ijk_dev, xyz_dev, n_cells);
+}

@@ -12,7 +12,11 @@ readers in oracle/gen_golden_scene.py), the cube grid (synthetic.cube_grid == th
 image sizes, every stage of main_reconstruct.py:67-173 as executed by the GPU drop-ins. What is synthetic: the views (seeded noise
 textures; no dataset images on the GPU box) and the weights of both networks (random init; the logistic unit of the similarityNet is
 set so that a plausible share of the cubes survives early rejection). Prints one JSON line with the wall seconds of every stage.
---max-cubes N takes the first N cubes of the grid (smoke runs)."""
+--max-cubes N takes the first N cubes of the grid (smoke runs).
+--seed-surface (opt-in) adds a second run whose cubes are seeded from a point cloud instead of the full grid: the voxels of
+synthetic.sparse_surface (a wavy sheet, moved to the middle of the grid) go through scene.quantizePts2Cubes, and the cube count and stage
+seconds of that cube set are reported next to the full-grid run under "seed_surface". Pixels and weights are synthetic there too: the figure
+is what the seeded cube set costs, not a statement about reconstruction quality."""
 import argparse
 import json
 import os
@@ -58,6 +62,7 @@ def run(argv):
     ap.add_argument("--n-vp", type=int, default=0)
     ap.add_argument("--max-cubes", type=int, default=0)
     ap.add_argument("--max-samples", type=int, default=0, help="cube-view-pair samples the scene's context is sized for (0: 128, or 8 x n_vp above 8 view pairs)")
+    ap.add_argument("--seed-surface", action="store_true", help="also run the scene on cubes seeded from synthetic.sparse_surface's points")
     ap.add_argument("--batch", type=int, default=0, help="cubes per SurfaceNet batch (default: max_samples / n_vp; the reference's is 14 at s=32, params.py:117-118)")
     a = ap.parse_args(argv)
     from surfacenet_amd import SurfaceNet, reconstruct, runtime, similarityNet, weights
@@ -86,8 +91,34 @@ def run(argv):
            "valid_cubes_per_s_in_loop": round(n_valid / max(stages.get("cube_loop", 0.0), 1e-9), 1),
            "patches_per_s": round(int(res["inScope_cubes_vs_views"].sum()) / max(stages.get("patch2embedding", 0.0), 1e-9), 1),
            "data": "calibration + cube grid of the dataset; synthetic noise views and random-init networks"}
+    if a.seed_surface:
+        out["seed_surface"] = seeded_run(a, cubes, Dc, lambda c, **k: reconstruct.reconstruct_scene(imgs, P, c, cube_D_mm, a.cube_d, n_vp, p2e, pair_fn, relw_fn, **k, **kw))
     runtime.reset()
     return out
+
+
+def seeded_run(a, grid, Dc, reconstruct_fn):
+    """The scene on cubes placed around a wavy sheet of points through the middle of the full grid's extent."""
+    from surfacenet_amd import scene, sparseCubes, synthetic
+    resol = grid["resol"][0]
+    span = (grid["xyz"].max(axis=0) - grid["xyz"].min(axis=0)) / (resol * (Dc // 2))
+    lattice = tuple(int(min(24, max(2, span[d]))) for d in range(2)) + (3,)
+    s = synthetic.sparse_surface(lattice=lattice, Dc=Dc, resol=float(resol))
+    pts = sparseCubes.sparse_xyz([np.ones(len(v), bool) for v in s["vxl_ijk_list"]], s["vxl_ijk_list"], s["param_np"])
+    centre = (grid["xyz"].max(axis=0) + grid["xyz"].min(axis=0)) / 2 + resol * a.cube_d / 2
+    pts = (pts + (centre - (pts.max(axis=0) + pts.min(axis=0)) / 2)).astype(np.float32)
+    t0 = time.perf_counter()
+    cubes, _ = scene.quantizePts2Cubes(pts, resol, a.cube_d, Dc, 1 / 2.)
+    t_seed = time.perf_counter() - t0
+    stages = {}
+    t0 = time.perf_counter()
+    res = reconstruct_fn(cubes, timings=stages)
+    total = time.perf_counter() - t0
+    return {"seed_points": int(pts.shape[0]), "sheet_lattice": list(lattice), "cubes": int(len(cubes)), "full_grid_cubes": int(len(grid)),
+            "quantizePts2Cubes_seconds": round(t_seed, 4), "valid_cubes": int(res["validCubes"].sum()), "nonempty_cubes": len(res["prediction_list"]),
+            "stage_seconds": {k: round(v, 4) for k, v in stages.items()}, "total_seconds": round(total, 3),
+            "data": "synthetic throughout: seed points from synthetic.sparse_surface, noise views, random-init networks - the cost of the seeded cube set, "
+                    "not a reconstruction quality figure"}
 
 
 if __name__ == "__main__":
