@@ -26,7 +26,8 @@ extern "C" {
 
 #define SN_ABI_VERSION 2   /* 2 (round 6): + sn_mfma_probe, sn_set_conv4_fp8; sn_calibrate_dev refuses the all-MX mode with SN_ERR_STATE (since round 5) */
 /* Added since, without a version change (additions only): sn_ptcubes, sn_ptcubes_dev, sn_ptcubes_sparse_dev and sn_ptcubes_cfg - the
- * point-seeded cube list. */
+ * point-seeded cube list; sn_normals, sn_normals_dev, sn_unique_voxels, sn_unique_voxels_dev and sn_normals_cfg - oriented normals and
+ * de-duplication of the output cloud. */
 
 /* The library is built with -fvisibility=hidden: the functions below are its WHOLE dynamic symbol table
  * (tests/test_abi.py compares `nm -D` with this header). */
@@ -234,6 +235,42 @@ SN_API int sn_adapthresh_dev(sn_ctx *ctx, int n, int Dc, const sn_adapthresh_cfg
                              const unsigned char *ijk_dev, const uint16_t *pred16_dev, const unsigned char *votes_dev,
                              const uint32_t *cube_ijk_dev, unsigned char *init_denoised_dev, double *thresh_dev, unsigned char *masks_dev,
                              unsigned char *denoised_dev, signed char *choice_dev);
+
+/* ---- oriented normals and de-duplication of the output cloud ---------------------------------------------------------
+ * On the packed sparse lists of the cross-cube post-pass (offsets, ijk, cube_ijk, mask as sn_denoise takes them). World cell of a voxel:
+ * g = cube_ijk * stride_vox + ijk per axis (stride_vox = cube_Dcenter * cube_overlapping_ratio, the cube stride in voxels, >= 1); the occupied set O
+ * holds the distinct cells of the masked voxels of all cubes. Masked cells must satisfy g + radius < 2^21 per axis (SN_ERR_ARG otherwise); cells with
+ * a negative coordinate do not exist: windows at the lattice's edge simply miss there.
+ *
+ * sn_normals: for every masked voxel, N = { d in [-radius, radius]^3 : g + d in O } (d = 0 included), radius 1, 2 or 3.
+ *   moments (total,10) int32, optional: |N|, sum d (x y z), sum d d^T (xx xy xz yy yz zz) - exact; ten zeros for an unmasked voxel.
+ *   normals (total,3) float32, optional: (0,0,0) when |N| < min_neighbours or the voxel is unmasked; else the unit eigenvector of the smallest
+ *   eigenvalue of |N| * sum d d^T - (sum d)(sum d)^T, solved in float64, oriented toward c = (sum_k cameraTs[view_idx[cube][k]]) / views_per_cube
+ *   (float64, summed in index order): with x = float64(float32(ijk) * resol + xyz) of the voxel's cube, the normal is negated when
+ *   (nx*dx + ny*dy) + nz*dz < 0, d = c - x; rounded to float32 once, after that. Where the two smallest eigenvalues coincide the direction is
+ *   unspecified (finite, unit length). cube_xyz (n,3) / cube_resol (n) float32, view_idx (n, views_per_cube) int32 each in [0, n_views)
+ *   (SN_ERR_ARG otherwise), cameraTs (n_views,3) float64: read only when normals is given. All cube_resol must be equal: the host form checks it
+ *   (SN_ERR_ARG), the device form takes it on trust.
+ * sn_unique_voxels: keep (total) uint8 = 1 iff the voxel is masked and has the smallest packed index among the masked voxels of its world cell.
+ * Both are deterministic. The workspace belongs to the context (grown on demand); a bad offsets table is SN_ERR_ARG in both forms; all four
+ * return when the work is done. total <= 2^28. */
+typedef struct sn_normals_cfg {
+    int radius;                /* 1, 2 or 3 */
+    int min_neighbours;        /* >= 1; below it the normal is zero */
+    int stride_vox;            /* cube stride in voxels */
+    int n_views;               /* rows of cameraTs */
+    int views_per_cube;        /* columns of view_idx: 2 * N_viewPairs4inference for viewPair_np */
+} sn_normals_cfg;
+SN_API int sn_normals(sn_ctx *ctx, int n, const sn_normals_cfg *cfg, const int64_t *offsets, const unsigned char *ijk, const uint32_t *cube_ijk,
+                      const unsigned char *mask, const float *cube_xyz, const float *cube_resol, const int32_t *view_idx, const double *cameraTs,
+                      float *normals, int32_t *moments);
+SN_API int sn_normals_dev(sn_ctx *ctx, int n, const sn_normals_cfg *cfg, long long total, const int64_t *offsets_dev, const unsigned char *ijk_dev,
+                          const uint32_t *cube_ijk_dev, const unsigned char *mask_dev, const float *cube_xyz_dev, const float *cube_resol_dev,
+                          const int32_t *view_idx_dev, const double *cameraTs_dev, float *normals_dev, int32_t *moments_dev);
+SN_API int sn_unique_voxels(sn_ctx *ctx, int n, int stride_vox, const int64_t *offsets, const unsigned char *ijk, const uint32_t *cube_ijk,
+                            const unsigned char *mask, unsigned char *keep);
+SN_API int sn_unique_voxels_dev(sn_ctx *ctx, int n, int stride_vox, long long total, const int64_t *offsets_dev, const unsigned char *ijk_dev,
+                                const uint32_t *cube_ijk_dev, const unsigned char *mask_dev, unsigned char *keep_dev);
 
 /* ---- DTU point-cloud evaluation (experiments/DTU/eval_ply.m -> PointCompareMain of the DTU kit) ----------------------
  * Points are (n,3) float64, row-major, finite. d^2 = (dx*dx + dy*dy) + dz*dz in float64 without contraction: the results are those of the numpy

@@ -20,6 +20,7 @@ ABI_SYMBOLS = [
     "sn_cvc_forward_dev", "sn_cvc_dev", "sn_forward_dev",
     "sn_ray_pool", "sn_ray_pool_dev", "sn_dense2sparse", "sn_dense2sparse_dev",
     "sn_denoise", "sn_denoise_dev", "sn_adapthresh", "sn_adapthresh_dev",
+    "sn_normals", "sn_normals_dev", "sn_unique_voxels", "sn_unique_voxels_dev",
     "sn_point_reduce", "sn_nn_dist2", "sn_point_flags",
     "sn_ptcubes", "sn_ptcubes_dev", "sn_ptcubes_sparse_dev",
     "sn_simil_load_weights", "sn_crop_patches", "sn_patch2embedding", "sn_crop_embed", "sn_embeddingpair2simil", "sn_embeddings2simil",
@@ -42,6 +43,11 @@ class SparseCfg(ctypes.Structure):
 class AdapthreshCfg(ctypes.Structure):
     _fields_ = [("N_refine_iter", ctypes.c_int), ("D_cube", ctypes.c_int), ("init_probThresh", ctypes.c_double), ("max_probThresh", ctypes.c_double),
                 ("rayPool_thresh", ctypes.c_double), ("beta", ctypes.c_double)]
+
+
+class NormalsCfg(ctypes.Structure):
+    _fields_ = [("radius", ctypes.c_int), ("min_neighbours", ctypes.c_int), ("stride_vox", ctypes.c_int), ("n_views", ctypes.c_int),
+                ("views_per_cube", ctypes.c_int)]
 
 
 class PtCubesCfg(ctypes.Structure):
@@ -114,6 +120,10 @@ def load():
         "sn_denoise_dev": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_longlong] + [c_void_p] * 5),
         "sn_adapthresh": (c_int, [c_void_p, c_int, c_int, P(AdapthreshCfg)] + [c_void_p] * 10),
         "sn_adapthresh_dev": (c_int, [c_void_p, c_int, c_int, P(AdapthreshCfg), ctypes.c_longlong] + [c_void_p] * 10),
+        "sn_normals": (c_int, [c_void_p, c_int, P(NormalsCfg)] + [c_void_p] * 10),
+        "sn_normals_dev": (c_int, [c_void_p, c_int, P(NormalsCfg), ctypes.c_longlong] + [c_void_p] * 10),
+        "sn_unique_voxels": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 5),
+        "sn_unique_voxels_dev": (c_int, [c_void_p, c_int, c_int, ctypes.c_longlong] + [c_void_p] * 5),
         "sn_point_reduce": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_double, c_void_p, P(c_int)]),
         "sn_nn_dist2": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_double, c_void_p]),
         "sn_point_flags": (c_int, [c_void_p, ctypes.c_longlong] + [c_void_p] * 4 + [ctypes.c_double] + [c_void_p] * 3),

@@ -437,6 +437,46 @@ class Context(object):
                 out[k] = out[k].view(bool)
         return out
 
+    def normals(self, offsets, ijk, cube_ijk, mask, stride_vox, cube_xyz=None, cube_resol=None, view_idx=None, cameraTs=None, radius=2,
+                min_neighbours=6, return_normals=True, return_moments=False):
+        """Oriented normals of the masked voxels of packed voxel lists (sn_normals): offsets (n+1,) int64, ijk (T,3) uint8,
+        cube_ijk (n,3), mask (T,) bool, stride_vox the cube stride in voxels; cube_xyz (n,3) / cube_resol (n,) float32, view_idx (n,K) int32 and
+        cameraTs (V,3) float64 orient them (needed with return_normals). Returns normals (T,3) float32, moments (T,10) int32, or both as a tuple."""
+        offsets, n, ijk, cube = self._packed(offsets, ijk, cube_ijk)
+        m = np.ascontiguousarray(mask, dtype=bool).reshape(-1).view(np.uint8)
+        T = int(offsets[-1])
+        if ijk.shape[0] != T or m.size != T:
+            raise ValueError("offsets end at %d voxels: %d ijk rows, %d mask entries" % (T, ijk.shape[0], m.size))
+        cx = cr = vi = cam = nrm = mom = None
+        K = V = 0
+        if return_normals:
+            cx = np.ascontiguousarray(cube_xyz, dtype=np.float32).reshape(n, 3)
+            cr = np.ascontiguousarray(cube_resol, dtype=np.float32).reshape(n)
+            vi = np.ascontiguousarray(np.asarray(view_idx).reshape(n, -1) if n else np.zeros((0, 1)), dtype=np.int32)
+            cam = np.ascontiguousarray(cameraTs, dtype=np.float64).reshape(-1, 3)
+            K, V = vi.shape[1], cam.shape[0]
+            nrm = np.zeros((T, 3), np.float32)
+        if return_moments:
+            mom = np.zeros((T, 10), np.int32)
+        cfg = _lib.NormalsCfg(int(radius), int(min_neighbours), int(stride_vox), V, K)
+        _lib.check(self._lib.sn_normals(self._h, n, ctypes.byref(cfg), _lib.ptr(offsets), _lib.ptr(ijk), _lib.ptr(cube), _lib.ptr(m), _lib.ptr(cx),
+                                        _lib.ptr(cr), _lib.ptr(vi), _lib.ptr(cam), _lib.ptr(nrm), _lib.ptr(mom)))
+        if return_normals and return_moments:
+            return nrm, mom
+        return nrm if return_normals else mom
+
+    def unique_voxels(self, offsets, ijk, cube_ijk, mask, stride_vox):
+        """One voxel per world cell (sn_unique_voxels): (T,) bool, True for a masked voxel with the smallest packed index among the masked voxels
+        that share its cell cube_ijk * stride_vox + ijk."""
+        offsets, n, ijk, cube = self._packed(offsets, ijk, cube_ijk)
+        m = np.ascontiguousarray(mask, dtype=bool).reshape(-1).view(np.uint8)
+        T = int(offsets[-1])
+        if ijk.shape[0] != T or m.size != T:
+            raise ValueError("offsets end at %d voxels: %d ijk rows, %d mask entries" % (T, ijk.shape[0], m.size))
+        keep = np.zeros((T,), np.uint8)
+        _lib.check(self._lib.sn_unique_voxels(self._h, n, int(stride_vox), _lib.ptr(offsets), _lib.ptr(ijk), _lib.ptr(cube), _lib.ptr(m), _lib.ptr(keep)))
+        return keep.view(bool)
+
     @staticmethod
     def _points(xyz):
         return np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))

@@ -1,0 +1,270 @@
+// normals.h — what the output cloud needs beyond the masks, over the packed sparse voxel lists of dense2sparse (DESIGN.md section 4.9 states the
+// contract; tests/normals_ref.py restates it in numpy):
+//   normals          per masked voxel: integer moments of the occupied world cells in its (2r+1)^3 window - across cubes - then the unit
+//                    eigenvector of the smallest eigenvalue of n*q - s*s^T (fp64 cyclic Jacobi), oriented toward the mean centre of the cameras its
+//                    cube selected
+//   unique voxels    keep[t] = t is the smallest packed index among the masked voxels of its world cell
+// World cell of a voxel: g = cube_ijk * stride_vox + vxl_ijk per axis, 0 <= g and g + r < 2^21.
+//
+// Representation: the scene's occupancy as a hash table of 4^3 bricks. Key = the brick's coordinates (g >> 2, 19 bits per axis), value = one
+// 64-bit word, bit (x&3)*16 + (y&3)*4 + (z&3) = cell occupied, filled with atomicOr. A window of radius <= 2 touches at most 2^3 bricks, of radius 3
+// at most 3^3: 8 or 27 probes instead of 125 or 343. A slot is two words {key + 1, occupancy}; key + 1 != 0, so an all-zero table is empty.
+// The unique-owner table is per cell: {cell key + 1, NM_OWNER_TOP - smallest packed index}: the value words start as 0 as well, so the minimum
+// of the indices is kept as the atomicMax of their complements.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace sn {
+
+constexpr int NM_NT = 256;
+constexpr int NM_AXIS_BITS = 21;                     // cells per axis: 63-bit keys, as pointeval.h / ptcubes.h
+constexpr long long NM_AXIS_MAX = 1ll << NM_AXIS_BITS;
+constexpr int NM_SWEEPS = 12;                        // cyclic Jacobi sweeps (3 rotations each)
+constexpr unsigned long long NM_OWNER_TOP = 1ull << 62;
+// bits of the call's status word (read back by the host before the main kernel runs)
+constexpr int NM_FLAG_TABLE = 1, NM_FLAG_CELL = 2, NM_FLAG_VIEW = 4;
+
+struct NMArgs {
+    const int64_t *off; const uint8_t *ijk; const uint32_t *cube_ijk; const uint8_t *mask;
+    const float *cube_xyz, *cube_resol;              // per cube (normals only)
+    const double *cbar;                              // per cube: mean camera centre (normals only)
+    int *cube_of;                                    // [total] the cube of every voxel
+    unsigned long long *tab;                         // [2 * cap] brick table / cell table
+    int *flags;
+    float *normals; int32_t *moments;
+    long long total;
+    unsigned hmask;
+    int n, stride, radius, min_nb;
+};
+
+__device__ inline unsigned nm_hash(unsigned long long k, unsigned mask)
+{
+    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
+    return (unsigned)k & mask;
+}
+
+__device__ inline unsigned long long nm_key(long long x, long long y, long long z) { return ((unsigned long long)x << 42) | ((unsigned long long)y << 21) | (unsigned long long)z; }
+
+// the cube that owns packed index t: the first c with off[c + 1] > t. Any table contents give an index in [0, n).
+__device__ inline int nm_cube_of(const int64_t *off, int n, long long t)
+{
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (off[mid + 1] <= t) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ inline void nm_cell(const NMArgs &a, int c, long long t, long long g[3])
+{
+    for (int d = 0; d < 3; ++d) g[d] = (long long)a.cube_ijk[3 * c + d] * a.stride + (long long)a.ijk[3 * t + d];
+}
+
+// slot of `key` (stored as key + 1), claimed if absent
+__device__ inline unsigned nm_claim(unsigned long long *tab, unsigned hmask, unsigned long long key)
+{
+    const unsigned long long stored = key + 1ull;
+    unsigned h = nm_hash(key, hmask);
+    for (;;) {                                       // ends: the table holds at least twice the keys that can be inserted
+        unsigned long long cur = __hip_atomic_load(tab + 2 * (size_t)h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == 0ull) {
+            unsigned long long expected = 0ull;
+            if (__hip_atomic_compare_exchange_strong(tab + 2 * (size_t)h, &expected, stored, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return h;
+            cur = expected;
+        }
+        if (cur == stored) return h;
+        h = (h + 1) & hmask;
+    }
+}
+
+// value word of `key`, 0 if absent (read-only: after the insert kernel has finished)
+__device__ inline unsigned long long nm_find(const unsigned long long *tab, unsigned hmask, unsigned long long key)
+{
+    const unsigned long long stored = key + 1ull;
+    unsigned h = nm_hash(key, hmask);
+    for (;;) {
+        const unsigned long long cur = tab[2 * (size_t)h];
+        if (cur == stored) return tab[2 * (size_t)h + 1];
+        if (cur == 0ull) return 0ull;
+        h = (h + 1) & hmask;
+    }
+}
+
+// offsets table: starts at 0, non-decreasing, ends at total. Per cube (view_idx given): every view index in [0, V), cbar = mean camera centre,
+// summed in index order.
+__global__ void __launch_bounds__(NM_NT) nm_check_kernel(const int64_t *off, int n, long long total, const int32_t *view_idx, int K, const double *cams, int V,
+                                                         double *cbar, int *flags)
+{
+    const int c = blockIdx.x * NM_NT + threadIdx.x;
+    if (c > n) return;
+    const long long o = off[c];
+    if ((c == 0 && o != 0) || (c == n && o != total) || (c > 0 && o < off[c - 1])) atomicOr(flags, NM_FLAG_TABLE);
+    if (c == n || !view_idx) return;
+    double s[3] = {0.0, 0.0, 0.0};
+    bool bad = false;
+    for (int k = 0; k < K; ++k) {
+        const int v = view_idx[(size_t)c * K + k];
+        if (v < 0 || v >= V) { bad = true; continue; }
+        for (int d = 0; d < 3; ++d) s[d] += cams[3 * (size_t)v + d];
+    }
+    if (bad) atomicOr(flags, NM_FLAG_VIEW);
+    for (int d = 0; d < 3; ++d) cbar[3 * (size_t)c + d] = s[d] / (double)K;
+}
+
+// every voxel: its cube; every masked voxel: its cell's bit into the brick table or its packed index into the cell table (CELLS)
+template <bool CELLS>
+__global__ void __launch_bounds__(NM_NT) nm_insert_kernel(NMArgs a)
+{
+    const long long t = (long long)blockIdx.x * NM_NT + threadIdx.x;
+    if (t >= a.total) return;
+    const int c = nm_cube_of(a.off, a.n, t);
+    a.cube_of[t] = c;
+    if (!a.mask[t]) return;
+    long long g[3];
+    nm_cell(a, c, t, g);
+    if (g[0] + a.radius >= NM_AXIS_MAX || g[1] + a.radius >= NM_AXIS_MAX || g[2] + a.radius >= NM_AXIS_MAX) { atomicOr(a.flags, NM_FLAG_CELL); return; }
+    if (CELLS) {
+        const unsigned h = nm_claim(a.tab, a.hmask, nm_key(g[0], g[1], g[2]));
+        atomicMax(a.tab + 2 * (size_t)h + 1, NM_OWNER_TOP - (unsigned long long)t);      // the smallest index is the largest stored value
+    } else {
+        const unsigned h = nm_claim(a.tab, a.hmask, nm_key(g[0] >> 2, g[1] >> 2, g[2] >> 2));
+        const unsigned long long bit = 1ull << (((g[0] & 3) << 4) | ((g[1] & 3) << 2) | (g[2] & 3));
+        unsigned long long *w = a.tab + 2 * (size_t)h + 1;
+        if (!(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) atomicOr(w, bit);
+    }
+}
+
+// bits of a brick word whose local coordinate along an axis lies in [lo, hi] (0 <= lo <= hi <= 3); axis 0 = x (16-bit slabs), 1 = y, 2 = z
+__device__ inline unsigned long long nm_axis_mask(int lo, int hi, int axis)
+{
+    const unsigned sel = ((1u << (hi - lo + 1)) - 1u) << lo;      // 4 bits: which local coordinates
+    if (axis == 0) {
+        unsigned long long m = 0ull;
+        for (int x = 0; x < 4; ++x)
+            if ((sel >> x) & 1u) m |= 0xFFFFull << (16 * x);
+        return m;
+    }
+    if (axis == 1) {
+        unsigned m16 = 0u;
+        for (int y = 0; y < 4; ++y)
+            if ((sel >> y) & 1u) m16 |= 0xFu << (4 * y);
+        return (unsigned long long)m16 * 0x0001000100010001ull;
+    }
+    return (unsigned long long)sel * 0x1111111111111111ull;
+}
+
+// unit eigenvector of the smallest eigenvalue of the symmetric matrix {xx, xy, xz, yy, yz, zz}: cyclic Jacobi in fp64, a fixed number of sweeps.
+// Always finite and of unit length (a product of rotations), whatever the spectrum.
+__device__ inline void nm_smallest_eigvec(const double C[6], double v[3])
+{
+    double A[3][3] = {{C[0], C[1], C[2]}, {C[1], C[3], C[4]}, {C[2], C[4], C[5]}};
+    double V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    for (int sweep = 0; sweep < NM_SWEEPS; ++sweep) {
+#pragma unroll
+        for (int pq = 0; pq < 3; ++pq) {
+            const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2, o = 3 - p - q;
+            const double apq = A[p][q];
+            if (apq == 0.0) continue;
+            const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+            const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));      // (theta = +-inf: t = 0)
+            const double cs = 1.0 / sqrt(t * t + 1.0), sn_ = t * cs;
+            A[p][p] -= t * apq; A[q][q] += t * apq;
+            A[p][q] = A[q][p] = 0.0;
+            const double aop = A[o][p], aoq = A[o][q];
+            A[o][p] = A[p][o] = cs * aop - sn_ * aoq;
+            A[o][q] = A[q][o] = sn_ * aop + cs * aoq;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double vp = V[k][p], vq = V[k][q];
+                V[k][p] = cs * vp - sn_ * vq;
+                V[k][q] = sn_ * vp + cs * vq;
+            }
+        }
+    }
+    int m = 0;
+    if (A[1][1] < A[m][m]) m = 1;
+    if (A[2][2] < A[m][m]) m = 2;
+    const double x = m == 0 ? V[0][0] : (m == 1 ? V[0][1] : V[0][2]);
+    const double y = m == 0 ? V[1][0] : (m == 1 ? V[1][1] : V[1][2]);
+    const double z = m == 0 ? V[2][0] : (m == 1 ? V[2][1] : V[2][2]);
+    const double inv = 1.0 / sqrt((x * x + y * y) + z * z);
+    v[0] = x * inv; v[1] = y * inv; v[2] = z * inv;
+}
+
+// one voxel per lane: window moments from the brick words, then the eigen-solve and the orientation
+__global__ void __launch_bounds__(NM_NT) nm_normals_kernel(NMArgs a)
+{
+    const long long t = (long long)blockIdx.x * NM_NT + threadIdx.x;
+    if (t >= a.total) return;
+    int mom[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    float nrm[3] = {0.f, 0.f, 0.f};
+    if (a.mask[t]) {
+        const int c = a.cube_of[t], r = a.radius;
+        long long g[3];
+        nm_cell(a, c, t, g);
+        // (the insert kernel has flagged cells past the key range: the host does not launch this kernel then)
+        const long long b0[3] = {(g[0] - r) >> 2, (g[1] - r) >> 2, (g[2] - r) >> 2};       // arithmetic shifts: floor, also below zero
+        const long long b1[3] = {(g[0] + r) >> 2, (g[1] + r) >> 2, (g[2] + r) >> 2};
+        for (long long bx = b0[0]; bx <= b1[0]; ++bx) {
+            if (bx < 0) continue;                                                      // no cell has a negative coordinate: a miss, never a wrap
+            const int ox = (int)(4 * bx - g[0]);                                       // d of the brick's local coordinate 0
+            const unsigned long long mx = nm_axis_mask(max(0, -r - ox), min(3, r - ox), 0);
+            for (long long by = b0[1]; by <= b1[1]; ++by) {
+                if (by < 0) continue;
+                const int oy = (int)(4 * by - g[1]);
+                const unsigned long long mxy = mx & nm_axis_mask(max(0, -r - oy), min(3, r - oy), 1);
+                for (long long bz = b0[2]; bz <= b1[2]; ++bz) {
+                    if (bz < 0) continue;
+                    const int oz = (int)(4 * bz - g[2]);
+                    unsigned long long w = nm_find(a.tab, a.hmask, nm_key(bx, by, bz)) & mxy & nm_axis_mask(max(0, -r - oz), min(3, r - oz), 2);
+                    mom[0] += __popcll(w);
+                    for (; w; w &= w - 1) {
+                        const int b = __builtin_ctzll(w);
+                        const int dx = ox + (b >> 4), dy = oy + ((b >> 2) & 3), dz = oz + (b & 3);
+                        mom[1] += dx; mom[2] += dy; mom[3] += dz;
+                        mom[4] += dx * dx; mom[5] += dx * dy; mom[6] += dx * dz; mom[7] += dy * dy; mom[8] += dy * dz; mom[9] += dz * dz;
+                    }
+                }
+            }
+        }
+        if (a.normals && mom[0] >= a.min_nb) {
+            const int n = mom[0];
+            const int Ci[6] = {n * mom[4] - mom[1] * mom[1], n * mom[5] - mom[1] * mom[2], n * mom[6] - mom[1] * mom[3],
+                               n * mom[7] - mom[2] * mom[2], n * mom[8] - mom[2] * mom[3], n * mom[9] - mom[3] * mom[3]};
+            const double C[6] = {(double)Ci[0], (double)Ci[1], (double)Ci[2], (double)Ci[3], (double)Ci[4], (double)Ci[5]};
+            double v[3];
+            nm_smallest_eigvec(C, v);
+            const float resol = a.cube_resol[c];
+            double d[3];
+            for (int k = 0; k < 3; ++k) {
+                const float x = (float)a.ijk[3 * t + k] * resol + a.cube_xyz[3 * (size_t)c + k];      // the point sparse_xyz writes (no contraction)
+                d[k] = a.cbar[3 * (size_t)c + k] - (double)x;
+            }
+            const double dot = (v[0] * d[0] + v[1] * d[1]) + v[2] * d[2];
+            const double sg = dot < 0.0 ? -1.0 : 1.0;
+            for (int k = 0; k < 3; ++k) nrm[k] = (float)(sg * v[k]);
+        }
+    }
+    if (a.normals)
+        for (int k = 0; k < 3; ++k) a.normals[3 * t + k] = nrm[k];
+    if (a.moments)
+        for (int k = 0; k < 10; ++k) a.moments[10 * t + k] = mom[k];
+}
+
+// keep[t] = masked and the smallest packed index of its cell
+__global__ void __launch_bounds__(NM_NT) nm_owner_kernel(NMArgs a, uint8_t *keep)
+{
+    const long long t = (long long)blockIdx.x * NM_NT + threadIdx.x;
+    if (t >= a.total) return;
+    uint8_t k = 0;
+    if (a.mask[t]) {
+        long long g[3];
+        nm_cell(a, a.cube_of[t], t, g);
+        k = nm_find(a.tab, a.hmask, nm_key(g[0], g[1], g[2])) == NM_OWNER_TOP - (unsigned long long)t ? 1 : 0;
+    }
+    keep[t] = k;
+}
+
+}  // namespace sn

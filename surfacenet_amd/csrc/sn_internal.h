@@ -14,6 +14,7 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -188,6 +189,7 @@ struct sn_ctx {
     std::vector<std::string> num_names;   // layer name of each status bit
     void *rp_ws = nullptr; size_t rp_ws_bytes = 0; int *d_err = nullptr;   /* device error flag: 1 ray pooling range, CC_ERR_INPUT_FLAG post-pass input */ int *d_counts = nullptr; int d_counts_cap = 0;
     void *pe_ws = nullptr; size_t pe_ws_bytes = 0;   // point-cloud evaluation workspace (sn_pointeval.hip)
+    void *nm_ws = nullptr; size_t nm_ws_bytes = 0;   // normals / unique-voxel workspace: staged arrays, brick or cell table (sn_normals.hip)
     std::vector<void *> owned;
     // profiling
     bool prof_on = false;

@@ -1,0 +1,276 @@
+// sn_normals.hip — C ABI of the output cloud's oriented normals and de-duplication over the packed sparse voxel lists (normals.h; DESIGN.md
+// section 4.9). The host forms stage their arrays in the context's workspace and wrap the device forms' computation.
+#include "sn_internal.h"
+#include "normals.h"
+
+namespace {
+
+constexpr long long NM_MAX_VOXELS = 1ll << 28;       // hash tables of >= 2 * total slots stay within 2^29
+
+// Carves the context's workspace (base == nullptr: only measures).
+struct NMCarve {
+    unsigned char *base = nullptr;
+    size_t off = 0;
+    template <typename T> T *get(size_t n)
+    {
+        off = (off + 255) & ~(size_t)255;
+        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += std::max<size_t>(n, 1) * sizeof(T);
+        return p;
+    }
+};
+
+int nm_workspace(sn_ctx *c, size_t need, unsigned char **base)
+{
+    if (c->nm_ws_bytes < need) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->nm_ws) dev_free_owned(c, c->nm_ws);
+        c->nm_ws = nullptr; c->nm_ws_bytes = 0;
+        unsigned char *w = nullptr;
+        int rc = dev_alloc(c, &w, need);
+        if (rc != SN_OK) return rc;
+        c->nm_ws = w; c->nm_ws_bytes = need;
+    }
+    *base = static_cast<unsigned char *>(c->nm_ws);
+    return SN_OK;
+}
+
+// One call's arrays: the inputs and outputs (the caller's device arrays, or staged copies of host arrays) and the work buffers.
+struct NMCall {
+    int n = 0, K = 0, V = 0;
+    long long total = 0;
+    bool host = false, unique = false;
+    const int64_t *off = nullptr; const uint8_t *ijk = nullptr, *mask = nullptr; const uint32_t *cube_ijk = nullptr;
+    const float *xyz = nullptr, *resol = nullptr; const int32_t *view = nullptr; const double *cams = nullptr;
+    float *normals = nullptr; int32_t *moments = nullptr; uint8_t *keep = nullptr;
+    // work
+    unsigned cap = 0;
+    int *flags = nullptr, *cube_of = nullptr; double *cbar = nullptr; unsigned long long *tab = nullptr;
+    // which staged arrays the host form needs
+    bool want_normals = false, want_moments = false;
+};
+
+template <typename T> void nm_stage(NMCarve &w, bool host, T *&p, size_t count, bool wanted = true)
+{
+    if (host && wanted) p = w.get<typename std::remove_const<T>::type>(count);
+}
+
+void nm_layout(NMCarve &w, NMCall &k)
+{
+    const size_t n = (size_t)k.n, T = (size_t)k.total;
+    nm_stage(w, k.host, k.off, n + 1);
+    nm_stage(w, k.host, k.cube_ijk, 3 * n);
+    nm_stage(w, k.host, k.ijk, 3 * T);
+    nm_stage(w, k.host, k.mask, T);
+    nm_stage(w, k.host, k.xyz, 3 * n, k.want_normals);
+    nm_stage(w, k.host, k.resol, n, k.want_normals);
+    nm_stage(w, k.host, k.view, n * (size_t)k.K, k.want_normals);
+    nm_stage(w, k.host, k.cams, 3 * (size_t)k.V, k.want_normals);
+    nm_stage(w, k.host, k.normals, 3 * T, k.want_normals);
+    nm_stage(w, k.host, k.moments, 10 * T, k.want_moments);
+    nm_stage(w, k.host, k.keep, T, k.unique);
+    k.flags = w.get<int>(1);
+    k.cube_of = w.get<int>(T);
+    k.cbar = w.get<double>(3 * n);
+    k.tab = w.get<unsigned long long>(2 * (size_t)k.cap);
+}
+
+int nm_prepare(sn_ctx *c, NMCall &k)
+{
+    unsigned cap = 64;
+    while (cap < 2ull * (unsigned long long)k.total) cap <<= 1;
+    k.cap = cap;
+    NMCarve measure;
+    NMCall probe = k;
+    nm_layout(measure, probe);
+    NMCarve w;
+    int rc = nm_workspace(c, measure.off + 256, &w.base);
+    if (rc != SN_OK) return rc;
+    nm_layout(w, k);
+    return SN_OK;
+}
+
+int nm_check_common(sn_ctx *c, int n, int stride_vox)
+{
+    if (!c) return fail(SN_ERR_ARG, "null context");
+    if (n < 0) return fail(SN_ERR_ARG, "n must be >= 0");
+    if (stride_vox < 1) return fail(SN_ERR_ARG, "stride_vox = %d must be a positive number of voxels", stride_vox);
+    return SN_OK;
+}
+
+int nm_check_cfg(const sn_normals_cfg *cfg, bool want_normals)
+{
+    if (!cfg) return fail(SN_ERR_ARG, "null cfg");
+    if (cfg->radius < 1 || cfg->radius > 3) return fail(SN_ERR_ARG, "radius = %d: the window radius is 1, 2 or 3 cells", cfg->radius);
+    if (cfg->min_neighbours < 1) return fail(SN_ERR_ARG, "min_neighbours must be >= 1");
+    if (want_normals && (cfg->n_views < 1 || cfg->views_per_cube < 1))
+        return fail(SN_ERR_ARG, "n_views = %d and views_per_cube = %d must be >= 1", cfg->n_views, cfg->views_per_cube);
+    return SN_OK;
+}
+
+int nm_check_total(int n, long long total)
+{
+    if (total < 0) return fail(SN_ERR_ARG, "total must be >= 0");
+    if (total > NM_MAX_VOXELS) return fail(SN_ERR_ARG, "total = %lld: at most %lld voxels", total, NM_MAX_VOXELS);
+    if (n == 0 && total != 0) return fail(SN_ERR_ARG, "offsets table of 0 cubes holds %lld voxels", total);
+    return SN_OK;
+}
+
+int nm_check_host_table(int n, const int64_t *offsets)
+{
+    if (offsets[0] != 0) return fail(SN_ERR_ARG, "offsets[0] = %lld, must be 0", (long long)offsets[0]);
+    for (int i = 0; i < n; ++i)
+        if (offsets[i + 1] < offsets[i]) return fail(SN_ERR_ARG, "offsets table decreases at cube %d", i);
+    return SN_OK;
+}
+
+// The computation on device arrays. Returns when the stream is done (the flags are read in between, the work buffers are the context's).
+int nm_run(sn_ctx *c, NMCall &k, const sn_normals_cfg *cfg, int stride_vox)
+{
+    const int n = k.n;
+    const long long total = k.total;
+    const bool normals = k.normals != nullptr;
+    HIPCHK(hipMemsetAsync(k.flags, 0, sizeof(int), c->stream));
+    hipLaunchKernelGGL(nm_check_kernel, dim3((unsigned)(n / NM_NT + 1)), dim3(NM_NT), 0, c->stream, k.off, n, total, normals ? k.view : nullptr, k.K, k.cams, k.V,
+                       k.cbar, k.flags);
+    HIPCHK(hipGetLastError());
+    NMArgs a;
+    memset(&a, 0, sizeof a);
+    a.off = k.off; a.ijk = k.ijk; a.cube_ijk = k.cube_ijk; a.mask = k.mask; a.cube_xyz = k.xyz; a.cube_resol = k.resol; a.cbar = k.cbar;
+    a.cube_of = k.cube_of; a.tab = k.tab; a.flags = k.flags; a.normals = k.normals; a.moments = k.moments;
+    a.total = total; a.hmask = k.cap - 1; a.n = n; a.stride = stride_vox; a.radius = cfg ? cfg->radius : 0; a.min_nb = cfg ? cfg->min_neighbours : 0;
+    const unsigned nb = (unsigned)((total + NM_NT - 1) / NM_NT);
+    if (total > 0) {
+        ProfScope ps(c, k.unique ? "nm_cells" : "nm_bricks", 0, (double)total * 12.0 + (double)k.cap * 16.0);
+        HIPCHK(hipMemsetAsync(k.tab, 0, sizeof(unsigned long long) * 2 * (size_t)k.cap, c->stream));
+        if (k.unique) hipLaunchKernelGGL(nm_insert_kernel<true>, dim3(nb), dim3(NM_NT), 0, c->stream, a);
+        else hipLaunchKernelGGL(nm_insert_kernel<false>, dim3(nb), dim3(NM_NT), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    int flags = 0;
+    HIPCHK(hipMemcpyAsync(&flags, k.flags, sizeof flags, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (flags & NM_FLAG_TABLE) return fail(SN_ERR_ARG, "offsets table does not start at 0, decreases, or does not end at total = %lld", total);
+    if (flags & NM_FLAG_VIEW) return fail(SN_ERR_ARG, "a view index lies outside [0, %d)", k.V);
+    if (flags & NM_FLAG_CELL)
+        return fail(SN_ERR_ARG, "a masked voxel's world cell (cube_ijk * %d + vxl_ijk) plus the radius %d reaches 2^%d on an axis", stride_vox, a.radius, NM_AXIS_BITS);
+    if (total == 0) return SN_OK;
+    if (k.unique) {
+        ProfScope ps(c, "nm_owner", 0, (double)total * 10.0);
+        hipLaunchKernelGGL(nm_owner_kernel, dim3(nb), dim3(NM_NT), 0, c->stream, a, k.keep);
+        HIPCHK(hipGetLastError());
+    } else {
+        ProfScope ps(c, "nm_normals", 0, (double)total * (9.0 + (normals ? 12.0 : 0.0) + (k.moments ? 40.0 : 0.0)));
+        hipLaunchKernelGGL(nm_normals_kernel, dim3(nb), dim3(NM_NT), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    if (!k.host) HIPCHK(hipStreamSynchronize(c->stream));
+    return SN_OK;
+}
+
+template <typename T> int nm_upload(sn_ctx *c, const T *dst_dev, const T *src, size_t count)
+{
+    if (count) HIPCHK(hipMemcpyAsync(const_cast<T *>(dst_dev), src, sizeof(T) * count, hipMemcpyHostToDevice, c->stream));
+    return SN_OK;
+}
+
+}  // namespace
+
+extern "C" int sn_normals_dev(sn_ctx *c, int n, const sn_normals_cfg *cfg, long long total, const int64_t *offsets_dev, const unsigned char *ijk_dev,
+                              const uint32_t *cube_ijk_dev, const unsigned char *mask_dev, const float *cube_xyz_dev, const float *cube_resol_dev,
+                              const int32_t *view_idx_dev, const double *cameraTs_dev, float *normals_dev, int32_t *moments_dev)
+{
+    int rc;
+    if ((rc = nm_check_cfg(cfg, normals_dev != nullptr)) != SN_OK) return rc;
+    if ((rc = nm_check_common(c, n, cfg->stride_vox)) != SN_OK) return rc;
+    if ((rc = nm_check_total(n, total)) != SN_OK) return rc;
+    if (n == 0) return SN_OK;
+    if (!offsets_dev || !cube_ijk_dev || (total > 0 && (!ijk_dev || !mask_dev))) return fail(SN_ERR_ARG, "null argument");
+    if (normals_dev && (!cube_xyz_dev || !cube_resol_dev || !view_idx_dev || !cameraTs_dev)) return fail(SN_ERR_ARG, "normals need the cubes' xyz, resol, view indices and the camera centres");
+    HIPCHK(hipSetDevice(c->device));
+    NMCall k;
+    k.n = n; k.total = total; k.K = cfg->views_per_cube; k.V = cfg->n_views;
+    k.off = offsets_dev; k.ijk = ijk_dev; k.cube_ijk = cube_ijk_dev; k.mask = mask_dev; k.xyz = cube_xyz_dev; k.resol = cube_resol_dev;
+    k.view = view_idx_dev; k.cams = cameraTs_dev; k.normals = normals_dev; k.moments = moments_dev;
+    if ((rc = nm_prepare(c, k)) != SN_OK) return rc;
+    return nm_run(c, k, cfg, cfg->stride_vox);
+}
+
+extern "C" int sn_normals(sn_ctx *c, int n, const sn_normals_cfg *cfg, const int64_t *offsets, const unsigned char *ijk, const uint32_t *cube_ijk,
+                          const unsigned char *mask, const float *cube_xyz, const float *cube_resol, const int32_t *view_idx, const double *cameraTs,
+                          float *normals, int32_t *moments)
+{
+    int rc;
+    if ((rc = nm_check_cfg(cfg, normals != nullptr)) != SN_OK) return rc;
+    if ((rc = nm_check_common(c, n, cfg->stride_vox)) != SN_OK) return rc;
+    if (!offsets) return fail(SN_ERR_ARG, "null argument");
+    if (n == 0) return offsets[0] == 0 ? SN_OK : fail(SN_ERR_ARG, "offsets[0] = %lld, must be 0", (long long)offsets[0]);
+    if ((rc = nm_check_host_table(n, offsets)) != SN_OK) return rc;
+    const long long total = offsets[n];
+    if ((rc = nm_check_total(n, total)) != SN_OK) return rc;
+    if (!cube_ijk || (total > 0 && (!ijk || !mask))) return fail(SN_ERR_ARG, "null argument");
+    if (normals) {
+        if (!cube_xyz || !cube_resol || !view_idx || !cameraTs) return fail(SN_ERR_ARG, "normals need the cubes' xyz, resol, view indices and the camera centres");
+        for (int i = 1; i < n; ++i)
+            if (cube_resol[i] != cube_resol[0])
+                return fail(SN_ERR_ARG, "cube %d has resol %g, cube 0 %g: a cell-space normal is a direction in mm only on an isotropic lattice", i, cube_resol[i], cube_resol[0]);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    NMCall k;
+    k.host = true; k.want_normals = normals != nullptr; k.want_moments = moments != nullptr;
+    k.n = n; k.total = total; k.K = cfg->views_per_cube; k.V = cfg->n_views;
+    if ((rc = nm_prepare(c, k)) != SN_OK) return rc;
+    const size_t N = (size_t)n, T = (size_t)total;
+    if ((rc = nm_upload(c, k.off, offsets, N + 1)) != SN_OK || (rc = nm_upload(c, k.cube_ijk, cube_ijk, 3 * N)) != SN_OK ||
+        (rc = nm_upload(c, k.ijk, ijk, 3 * T)) != SN_OK || (rc = nm_upload(c, k.mask, mask, T)) != SN_OK)
+        return rc;
+    if (normals && ((rc = nm_upload(c, k.xyz, cube_xyz, 3 * N)) != SN_OK || (rc = nm_upload(c, k.resol, cube_resol, N)) != SN_OK ||
+                    (rc = nm_upload(c, k.view, view_idx, N * (size_t)k.K)) != SN_OK || (rc = nm_upload(c, k.cams, cameraTs, 3 * (size_t)k.V)) != SN_OK))
+        return rc;
+    if ((rc = nm_run(c, k, cfg, cfg->stride_vox)) != SN_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (normals && T) HIPCHK(hipMemcpyAsync(normals, k.normals, sizeof(float) * 3 * T, hipMemcpyDeviceToHost, c->stream));
+    if (moments && T) HIPCHK(hipMemcpyAsync(moments, k.moments, sizeof(int32_t) * 10 * T, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return SN_OK;
+}
+
+extern "C" int sn_unique_voxels_dev(sn_ctx *c, int n, int stride_vox, long long total, const int64_t *offsets_dev, const unsigned char *ijk_dev,
+                                    const uint32_t *cube_ijk_dev, const unsigned char *mask_dev, unsigned char *keep_dev)
+{
+    int rc;
+    if ((rc = nm_check_common(c, n, stride_vox)) != SN_OK) return rc;
+    if ((rc = nm_check_total(n, total)) != SN_OK) return rc;
+    if (n == 0) return SN_OK;
+    if (!offsets_dev || !cube_ijk_dev || (total > 0 && (!ijk_dev || !mask_dev || !keep_dev))) return fail(SN_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(c->device));
+    NMCall k;
+    k.unique = true; k.n = n; k.total = total;
+    k.off = offsets_dev; k.ijk = ijk_dev; k.cube_ijk = cube_ijk_dev; k.mask = mask_dev; k.keep = keep_dev;
+    if ((rc = nm_prepare(c, k)) != SN_OK) return rc;
+    return nm_run(c, k, nullptr, stride_vox);
+}
+
+extern "C" int sn_unique_voxels(sn_ctx *c, int n, int stride_vox, const int64_t *offsets, const unsigned char *ijk, const uint32_t *cube_ijk,
+                                const unsigned char *mask, unsigned char *keep)
+{
+    int rc;
+    if ((rc = nm_check_common(c, n, stride_vox)) != SN_OK) return rc;
+    if (!offsets) return fail(SN_ERR_ARG, "null argument");
+    if (n == 0) return offsets[0] == 0 ? SN_OK : fail(SN_ERR_ARG, "offsets[0] = %lld, must be 0", (long long)offsets[0]);
+    if ((rc = nm_check_host_table(n, offsets)) != SN_OK) return rc;
+    const long long total = offsets[n];
+    if ((rc = nm_check_total(n, total)) != SN_OK) return rc;
+    if (!cube_ijk || (total > 0 && (!ijk || !mask || !keep))) return fail(SN_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(c->device));
+    NMCall k;
+    k.host = true; k.unique = true; k.n = n; k.total = total;
+    if ((rc = nm_prepare(c, k)) != SN_OK) return rc;
+    const size_t N = (size_t)n, T = (size_t)total;
+    if ((rc = nm_upload(c, k.off, offsets, N + 1)) != SN_OK || (rc = nm_upload(c, k.cube_ijk, cube_ijk, 3 * N)) != SN_OK ||
+        (rc = nm_upload(c, k.ijk, ijk, 3 * T)) != SN_OK || (rc = nm_upload(c, k.mask, mask, T)) != SN_OK)
+        return rc;
+    if ((rc = nm_run(c, k, nullptr, stride_vox)) != SN_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (T) HIPCHK(hipMemcpyAsync(keep, k.keep, T, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return SN_OK;
+}

@@ -454,7 +454,7 @@ def reconstruct_scene(images_list, cameraPOs_np, cubes_param_np, cube_D_mm, cube
 
 
 def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, gamma=0.8, beta=6, N_refine_iter=8, init_probThresh=0.5,
-                   max_probThresh=0.9, keep_iterations=False):
+                   max_probThresh=0.9, keep_iterations=False, cameraTs_np=None, cube_overlapping_ratio=0.5, unique=False):
     """The reconstruction's last two stages on `reconstruct_scene`'s dict, in memory and on the GPU, as the reference runs them on its files:
       * main_reconstruct.py:172-175  thinning masks (prob >= tau, votes >= gamma * N_vp * 2), then denoise_crossCubes with D_cube = cube_D
       * main.py:37-43 -> utils/adapthresh.py  adaptive thresholding with D_cube = cube_Dcenter, init / max threshold init_probThresh /
@@ -463,9 +463,16 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
       fixThresh_mask_list, fixThresh_denoised_list                 the fixThresh_tau*_gamma*.ply content is the denoised one
       adapt_init_denoised_list                                     initialization.ply
       adapt_thresh (n,) float64, adapt_mask_list, adapt_denoised_list   after the last iteration (iter{N-1}.ply = adapt_denoised_list)
-      adapt_iterations (keep_iterations): thresh (N,n), choice (N,n) int8, mask_lists, denoised_lists - every iteration."""
+      adapt_iterations (keep_iterations): thresh (N,n), choice (N,n) int8, mask_lists, denoised_lists - every iteration.
+    Beyond the reference (nothing is added to the dict without these arguments):
+      cameraTs_np (V,3): fixThresh_normal_list, adapt_normal_list - oriented normals of the two denoised masks (normals.estimate_normals with
+        the cubes' view pairs out["viewPair_np"], cube stride cube_Dcenter * cube_overlapping_ratio), ready for save_sparseCubes_2ply(normal_list=)
+      unique=True: fixThresh_unique_list, adapt_unique_list - the two denoised masks with every world voxel kept once (normals.unique_voxels)."""
     from . import adapthresh, denoising, sparseCubes
+    from . import normals as _normals
     N_vp = int(N_viewPairs4inference)
+    extras = cameraTs_np is not None or unique
+    stride_vox = _normals.stride_voxels(cube_Dcenter, cube_overlapping_ratio) if extras else None      # (fails here, before any stage has run)
     pred_l, ijk_l, votes_l = out["prediction_list"], out["vxl_ijk_list"], out["rayPooling_votes_list"]
     n = len(ijk_l)
     res = dict(fixThresh_mask_list=[], fixThresh_denoised_list=[], adapt_init_denoised_list=[], adapt_thresh=np.full((n,), float(init_probThresh)),
@@ -473,6 +480,10 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
     if keep_iterations:
         res["adapt_iterations"] = dict(thresh=np.zeros((int(N_refine_iter), n)), choice=np.zeros((int(N_refine_iter), n), np.int8),
                                        mask_lists=[], denoised_lists=[])
+    if cameraTs_np is not None:
+        res.update(fixThresh_normal_list=[], adapt_normal_list=[])
+    if unique:
+        res.update(fixThresh_unique_list=[], adapt_unique_list=[])
     if n == 0:
         return res
     cube_ijk = out["cube_ijk_np"]
@@ -493,6 +504,12 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
     if keep_iterations:
         res["adapt_iterations"] = dict(thresh=a["thresh"], choice=a["choice"], mask_lists=[split(m) for m in a["masks"]],
                                        denoised_lists=[split(m) for m in a["denoised"]])
+    for name in ("fixThresh", "adapt"):
+        masks = res[name + "_denoised_list"]
+        if cameraTs_np is not None:
+            res[name + "_normal_list"] = _normals.estimate_normals(cube_ijk, ijk_l, masks, out["param_np"], out["viewPair_np"], cameraTs_np, stride_vox)
+        if unique:
+            res[name + "_unique_list"] = _normals.unique_voxels(cube_ijk, ijk_l, masks, stride_vox)
     return res
 
 
