@@ -738,8 +738,8 @@ int sn_calibrate_dev(sn_ctx *c, int n_samples, double max_sat_fraction, sn_calib
     // two 6-bit code planes: 0 "act" = merge_conv_a's output, 1 "cat" = the concat buffer (the conv4 chain's fp8 codes have the exponent range: nothing to calibrate)
     constexpr int NT = 2, HB = kMxScanBins + 2;
     TmpDev tmp;
-    unsigned long long *d_hist = tmp.get<unsigned long long>(NT * HB);
-    if (!d_hist) return fail(SN_ERR_HIP, "out of device memory");
+    unsigned long long *d_hist = tmp.out<unsigned long long>(NT * HB);
+    if (!tmp.ok) return fail(SN_ERR_HIP, "out of device memory");
     HIPCHK(hipMemsetAsync(d_hist, 0, sizeof(unsigned long long) * NT * HB, c->stream));
     const _Float16 *tens[NT] = {c->ma, c->cat};
     const long long halfs[NT] = {(long long)n_samples * vox * 104, (long long)n_samples * vox * 64};
@@ -1106,9 +1106,8 @@ int sn_relative_weights(sn_ctx *c, int n, int n_vp, const float *features, float
     HIPCHK(hipSetDevice(c->device));
     const size_t rows = (size_t)n * n_vp;
     TmpDev t;      // freed on every return path
-    float *d_f = t.get<float>(rows * kDFeature), *d_z = t.get<float>(rows), *d_o = t.get<float>(rows);
-    if (!d_f || !d_z || !d_o) return fail(SN_ERR_NOMEM, "sn_relative_weights: device allocation failed");
-    HIPCHK(hipMemcpyAsync(d_f, features, rows * kDFeature * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    float *d_f = t.up(c, features, rows * kDFeature), *d_z = t.out<float>(rows), *d_o = t.out<float>(rows);
+    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_relative_weights: device allocation failed");
     hipLaunchKernelGGL(relw_mlp_kernel, dim3((unsigned)rows), dim3(128), 0, c->stream, d_f, c->relw_W1, c->relw_scale, c->relw_shift,
                        c->relw_w2, c->relw_b2, d_z, kDFeature, kHidden);
     hipLaunchKernelGGL(relw_softmax_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, c->stream, d_z, d_o, n, n_vp);
@@ -1135,13 +1134,9 @@ int sn_viewpair_weights(sn_ctx *c, int n_cubes, int n_views, const float *embedd
         for (int j = i + 1; j < n_views; ++j) { pairs.push_back(i); pairs.push_back(j); }
     const size_t rows = (size_t)n_cubes * P, ne = (size_t)n_cubes * n_views * 128;
     TmpDev t;
-    float *d_e = t.get<float>(ne), *d_d = t.get<float>(rows), *d_t = t.get<float>(rows), *d_z = t.get<float>(rows), *d_o = t.get<float>(rows);
-    int *d_p = t.get<int>(pairs.size());
-    if (!d_e || !d_d || !d_t || !d_z || !d_o || !d_p) return fail(SN_ERR_NOMEM, "sn_viewpair_weights: device allocation failed");
-    HIPCHK(hipMemcpyAsync(d_e, embeddings, sizeof(float) * ne, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_d, dissimilarity, sizeof(float) * rows, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_t, theta, sizeof(float) * rows, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_p, pairs.data(), sizeof(int) * pairs.size(), hipMemcpyHostToDevice, c->stream));
+    float *d_e = t.up(c, embeddings, ne), *d_d = t.up(c, dissimilarity, rows), *d_t = t.up(c, theta, rows), *d_z = t.out<float>(rows), *d_o = t.out<float>(rows);
+    int *d_p = t.up(c, pairs.data(), pairs.size());
+    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_viewpair_weights: device allocation failed");
     {
         ProfScope ps(c, "relw_mlp_pairs", 2.0 * rows * kDFeature * kHidden, (double)rows * 12.0 + (double)ne * 4.0);
         hipLaunchKernelGGL(relw_mlp_pairs_kernel, dim3((unsigned)rows), dim3(128), 0, c->stream, d_e, d_p, d_d, d_t, n_views, P, c->relw_W1, c->relw_scale,
@@ -1397,16 +1392,6 @@ int sn_comm_wait(sn_ctx *c, int slot)
 // cannot hold the total is reported AFTER the payload all-gather has run (SN_ERR_ARG with counts[] filled in), so a rank that fails never leaves its peers inside a
 // collective it does not take part in (the first version returned between the two all-gathers, and a caller that retried on its own then
 // issued a counts all-gather against its peers' payload all-gather). sn_allgatherv_counts is the sizing query: the counts all-gather alone.
-static int comm_stage_need(sn_ctx *c, size_t bytes)
-{
-    if (bytes <= c->comm_stage_cap) return SN_OK;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->comm_stage) { dev_free_owned(c, c->comm_stage); c->comm_stage = nullptr; c->comm_stage_cap = 0; }
-    int rc = dev_alloc(c, &c->comm_stage, bytes);
-    if (rc != SN_OK) return rc;
-    c->comm_stage_cap = bytes;
-    return SN_OK;
-}
 // one 8-byte word per rank, gathered to the host of every rank (counts; per-rank status)
 static int comm_gather_u64(sn_ctx *c, unsigned long long mine, unsigned long long *all, const char *what)
 {
@@ -1444,7 +1429,7 @@ int sn_allgatherv_bytes_dev(sn_ctx *c, const void *local_dev, size_t n_local, vo
     // The staging buffer is sized by the LARGEST rank's payload, known only now - and its allocation is the one step between the two collectives that a
     // single rank can fail. Its outcome is exchanged (8 bytes per rank) before anyone enters the payload all-gather: all ranks go on, or all
     // ranks return the same error.
-    const int stage_rc = comm_stage_need(c, (size_t)(W + 1) * cap);              // [W padded payloads | this rank's padded payload]
+    const int stage_rc = dev_reserve(c, c->comm_stage, (size_t)(W + 1) * cap);              // [W padded payloads | this rank's padded payload]
     const std::string stage_err = stage_rc != SN_OK ? g_err : std::string();
     std::vector<unsigned long long> flags((size_t)W, 0);
     rc = comm_gather_u64(c, stage_rc != SN_OK ? 1ull : 0ull, flags.data(), "status");
@@ -1453,12 +1438,12 @@ int sn_allgatherv_bytes_dev(sn_ctx *c, const void *local_dev, size_t n_local, vo
         if (flags[(size_t)r])
             return fail(stage_rc != SN_OK ? stage_rc : SN_ERR_NOMEM, "sn_allgatherv_bytes_dev: rank %d could not stage %llu bytes%s%s - no rank entered the payload all-gather",
                         r, (unsigned long long)(W + 1) * cap, stage_err.empty() ? "" : ": ", stage_err.c_str());
-    unsigned char *mine_pad = c->comm_stage + (size_t)W * cap;
+    unsigned char *stage = c->comm_stage.as<unsigned char>(), *mine_pad = stage + (size_t)W * cap;
     if (n_local) HIPCHK(hipMemcpyAsync(mine_pad, local_dev, n_local, hipMemcpyDeviceToDevice, c->stream));
     int e;
     {
         ProfScope ps(c, "rccl_allgatherv", 0, (double)cap * W);
-        e = g_rccl.AllGather(mine_pad, c->comm_stage, cap, /*ncclUint8*/ 1, c->rccl_comm, c->stream);
+        e = g_rccl.AllGather(mine_pad, stage, cap, /*ncclUint8*/ 1, c->rccl_comm, c->stream);
     }
     if (e != 0) return fail(SN_ERR_COMM, "ncclAllGather (payload): %s", rccl_err(e));
     // rank-local checks only from here on: every collective of the call has been issued
@@ -1469,7 +1454,7 @@ int sn_allgatherv_bytes_dev(sn_ctx *c, const void *local_dev, size_t n_local, vo
     }
     size_t off = 0;
     for (int r = 0; r < W; ++r) {
-        if (counts[r]) HIPCHK(hipMemcpyAsync(static_cast<unsigned char *>(global_dev) + off, c->comm_stage + (size_t)r * cap, counts[r], hipMemcpyDeviceToDevice, c->stream));
+        if (counts[r]) HIPCHK(hipMemcpyAsync(static_cast<unsigned char *>(global_dev) + off, stage + (size_t)r * cap, counts[r], hipMemcpyDeviceToDevice, c->stream));
         off += counts[r];
     }
     HIPCHK(hipStreamSynchronize(c->stream));

@@ -20,33 +20,19 @@ struct CCWork {
 int cc_work(sn_ctx *c, CCWork &w, int n, int Dc, bool adapt)
 {
     w.n = n; w.Dc = Dc;
-    unsigned cap = 64;
-    while (cap < 2u * (unsigned)n) cap <<= 1;
-    w.cap = (int)cap; w.hmask = cap - 1;
+    w.cap = (int)table_cap((unsigned long long)n, 2, 64); w.hmask = (unsigned)w.cap - 1;
     const size_t D2 = (size_t)Dc * Dc, D3 = D2 * Dc;
-    w.tab = w.t.get<int>(cap); w.nonempty = w.t.get<int>(n); w.mapped = w.t.get<int>(n); w.nbr26 = w.t.get<int>(26 * (size_t)n);
-    w.grid1 = w.t.get<unsigned long long>((size_t)n * D2);
+    w.tab = w.t.out<int>(w.cap); w.nonempty = w.t.out<int>(n); w.mapped = w.t.out<int>(n); w.nbr26 = w.t.out<int>(26 * (size_t)n);
+    w.grid1 = w.t.out<unsigned long long>((size_t)n * D2);
     if (D3 > (size_t)DN_LDS_CELLS) {
         w.dn_blocks = std::min(n, 512);
-        w.ws = w.t.get<unsigned>((size_t)w.dn_blocks * D3);
-        if (!w.ws) return fail(SN_ERR_NOMEM, "cross-cube post-pass: device allocation failed");
+        w.ws = w.t.out<unsigned>((size_t)w.dn_blocks * D3);
     }
     if (adapt) {
-        w.cnt = w.t.get<int>(18 * (size_t)n);
-        w.grid3 = w.t.get<unsigned long long>(3 * (size_t)n * D2);
-        if (!w.cnt || !w.grid3) return fail(SN_ERR_NOMEM, "cross-cube post-pass: device allocation failed");
+        w.cnt = w.t.out<int>(18 * (size_t)n);
+        w.grid3 = w.t.out<unsigned long long>(3 * (size_t)n * D2);
     }
-    if (!w.tab || !w.nonempty || !w.mapped || !w.nbr26 || !w.grid1) return fail(SN_ERR_NOMEM, "cross-cube post-pass: device allocation failed");
-    return SN_OK;
-}
-
-int cc_err_flag(sn_ctx *c)
-{
-    if (!c->d_err) {
-        int rc = dev_alloc(c, &c->d_err, 1);
-        if (rc != SN_OK) return rc;
-        HIPCHK(hipMemsetAsync(c->d_err, 0, sizeof(int), c->stream));
-    }
+    if (!w.t.ok) return fail(SN_ERR_NOMEM, "cross-cube post-pass: device allocation failed");
     return SN_OK;
 }
 
@@ -94,18 +80,6 @@ int cc_check_args(int n, int Dc, int D_cube)
     return SN_OK;
 }
 
-// host-array forms: the offsets table and the voxel ijk are validated here
-int cc_check_host(int n, int Dc, const int64_t *offsets, const unsigned char *ijk)
-{
-    if (offsets[0] != 0) return fail(SN_ERR_ARG, "offsets[0] = %lld, must be 0", (long long)offsets[0]);
-    for (int i = 0; i < n; ++i)
-        if (offsets[i + 1] < offsets[i]) return fail(SN_ERR_ARG, "offsets table decreases at cube %d", i);
-    const long long total = offsets[n];
-    for (long long v = 0; v < 3 * total; ++v)
-        if (ijk[v] >= Dc) return fail(SN_ERR_ARG, "voxel %lld: ijk component %d >= Dc = %d", v / 3, (int)ijk[v], Dc);
-    return SN_OK;
-}
-
 int cc_check_dev(sn_ctx *c, int n, int Dc, long long total, const int64_t *off, const unsigned char *ijk)
 {
     const long long m = std::max<long long>(n + 1, total);
@@ -121,11 +95,11 @@ int cc_adapthresh(sn_ctx *c, int n, int Dc, const sn_adapthresh_cfg *cfg, long l
     CCWork w;
     int rc;
     if ((rc = cc_work(c, w, n, Dc, true)) != SN_OK) return rc;
-    uint8_t *mask = w.t.get<uint8_t>((size_t)total), *scratch = w.t.get<uint8_t>((size_t)total);
-    int *active = w.t.get<int>(n), *face6 = w.t.get<int>(6 * (size_t)n);
-    double *t = w.t.get<double>(n), *t_new = w.t.get<double>(n);
-    signed char *ch = w.t.get<signed char>(n);
-    if (!mask || !scratch || !active || !face6 || !t || !t_new || !ch) return fail(SN_ERR_NOMEM, "sn_adapthresh: device allocation failed");
+    uint8_t *mask = w.t.out<uint8_t>((size_t)total), *scratch = w.t.out<uint8_t>((size_t)total);
+    int *active = w.t.out<int>(n), *face6 = w.t.out<int>(6 * (size_t)n);
+    double *t = w.t.out<double>(n), *t_new = w.t.out<double>(n);
+    signed char *ch = w.t.out<signed char>(n);
+    if (!w.t.ok) return fail(SN_ERR_NOMEM, "sn_adapthresh: device allocation failed");
     if (total > 0) {
         hipLaunchKernelGGL(cc_init_mask_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, total, pred16, votes, cfg->init_probThresh,
                            cfg->rayPool_thresh, mask);
@@ -188,11 +162,10 @@ extern "C" int sn_denoise_dev(sn_ctx *c, int n, int Dc, int D_cube, long long to
     if (!c) return fail(SN_ERR_ARG, "null context");
     int rc;
     if ((rc = cc_check_args(n, Dc, D_cube)) != SN_OK) return rc;
-    if (total < 0) return fail(SN_ERR_ARG, "total must be >= 0");
-    if (n == 0) return total == 0 ? SN_OK : fail(SN_ERR_ARG, "offsets table of 0 cubes holds %lld voxels", total);
+    if ((rc = pl_check_counts(n, total)) != SN_OK || n == 0) return rc;
     if (!offsets_dev || !cube_ijk_dev || (total > 0 && (!ijk_dev || !mask_dev || !out_dev))) return fail(SN_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(c->device));
-    if ((rc = cc_err_flag(c)) != SN_OK) return rc;
+    if ((rc = err_flag(c)) != SN_OK) return rc;
     if ((rc = cc_check_dev(c, n, Dc, total, offsets_dev, ijk_dev)) != SN_OK) return rc;
     CCWork w;
     if ((rc = cc_work(c, w, n, Dc, false)) != SN_OK) return rc;
@@ -207,23 +180,17 @@ extern "C" int sn_denoise(sn_ctx *c, int n, int Dc, int D_cube, const int64_t *o
     if (!c || !offsets) return fail(SN_ERR_ARG, "null argument");
     int rc;
     if ((rc = cc_check_args(n, Dc, D_cube)) != SN_OK) return rc;
-    if (n == 0) return offsets[0] == 0 ? SN_OK : fail(SN_ERR_ARG, "offsets[0] = %lld, must be 0", (long long)offsets[0]);
+    if (n == 0) return pl_check_host_offsets(0, offsets);
     if (!cube_ijk || (offsets[n] > 0 && (!ijk || !mask || !out))) return fail(SN_ERR_ARG, "null argument");
-    if ((rc = cc_check_host(n, Dc, offsets, ijk)) != SN_OK) return rc;
+    if ((rc = pl_check_host_offsets(n, offsets)) != SN_OK || (rc = pl_check_host_ijk(offsets[n], ijk, Dc)) != SN_OK) return rc;
     HIPCHK(hipSetDevice(c->device));
     const long long total = offsets[n];
     TmpDev t;
-    int64_t *d_off = t.get<int64_t>((size_t)n + 1);
-    uint32_t *d_cube = t.get<uint32_t>(3 * (size_t)n);
-    unsigned char *d_ijk = t.get<unsigned char>(3 * (size_t)total), *d_mask = t.get<unsigned char>((size_t)total), *d_out = t.get<unsigned char>((size_t)total);
-    if (!d_off || !d_cube || !d_ijk || !d_mask || !d_out) return fail(SN_ERR_NOMEM, "sn_denoise: device allocation failed");
-    HIPCHK(hipMemcpyAsync(d_off, offsets, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_cube, cube_ijk, sizeof(uint32_t) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    if (total) {
-        HIPCHK(hipMemcpyAsync(d_ijk, ijk, 3 * (size_t)total, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(d_mask, mask, (size_t)total, hipMemcpyHostToDevice, c->stream));
-    }
-    if ((rc = cc_err_flag(c)) != SN_OK) return rc;
+    int64_t *d_off = t.up(c, offsets, (size_t)n + 1);
+    uint32_t *d_cube = t.up(c, cube_ijk, 3 * (size_t)n);
+    unsigned char *d_ijk = t.up(c, ijk, 3 * (size_t)total), *d_mask = t.up(c, mask, (size_t)total), *d_out = t.out<unsigned char>((size_t)total);
+    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_denoise: device allocation failed");
+    if ((rc = err_flag(c)) != SN_OK) return rc;
     CCWork w;
     if ((rc = cc_work(c, w, n, Dc, false)) != SN_OK) return rc;
     if ((rc = cc_denoise(c, w, D_cube, total, d_off, d_ijk, d_cube, d_mask, d_out, nullptr)) != SN_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
@@ -248,11 +215,10 @@ extern "C" int sn_adapthresh_dev(sn_ctx *c, int n, int Dc, const sn_adapthresh_c
     int rc;
     if ((rc = cc_check_cfg(cfg)) != SN_OK) return rc;
     if ((rc = cc_check_args(n, Dc, cfg->D_cube)) != SN_OK) return rc;
-    if (total < 0) return fail(SN_ERR_ARG, "total must be >= 0");
-    if (n == 0) return total == 0 ? SN_OK : fail(SN_ERR_ARG, "offsets table of 0 cubes holds %lld voxels", total);
+    if ((rc = pl_check_counts(n, total)) != SN_OK || n == 0) return rc;
     if (!offsets_dev || !cube_ijk_dev || (total > 0 && (!ijk_dev || !pred16_dev))) return fail(SN_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(c->device));
-    if ((rc = cc_err_flag(c)) != SN_OK) return rc;
+    if ((rc = err_flag(c)) != SN_OK) return rc;
     if ((rc = cc_check_dev(c, n, Dc, total, offsets_dev, ijk_dev)) != SN_OK) return rc;
     return cc_adapthresh(c, n, Dc, cfg, total, offsets_dev, ijk_dev, pred16_dev, votes_dev, cube_ijk_dev, init_denoised_dev, thresh_dev, masks_dev,
                          denoised_dev, choice_dev);
@@ -266,32 +232,23 @@ extern "C" int sn_adapthresh(sn_ctx *c, int n, int Dc, const sn_adapthresh_cfg *
     int rc;
     if ((rc = cc_check_cfg(cfg)) != SN_OK) return rc;
     if ((rc = cc_check_args(n, Dc, cfg->D_cube)) != SN_OK) return rc;
-    if (n == 0) return offsets[0] == 0 ? SN_OK : fail(SN_ERR_ARG, "offsets[0] = %lld, must be 0", (long long)offsets[0]);
+    if (n == 0) return pl_check_host_offsets(0, offsets);
     if (!cube_ijk || (offsets[n] > 0 && (!ijk || !pred16))) return fail(SN_ERR_ARG, "null argument");
-    if ((rc = cc_check_host(n, Dc, offsets, ijk)) != SN_OK) return rc;
+    if ((rc = pl_check_host_offsets(n, offsets)) != SN_OK || (rc = pl_check_host_ijk(offsets[n], ijk, Dc)) != SN_OK) return rc;
     HIPCHK(hipSetDevice(c->device));
     const long long total = offsets[n];
     const size_t T = (size_t)total, it = (size_t)cfg->N_refine_iter;
     TmpDev t;
-    int64_t *d_off = t.get<int64_t>((size_t)n + 1);
-    uint32_t *d_cube = t.get<uint32_t>(3 * (size_t)n);
-    unsigned char *d_ijk = t.get<unsigned char>(3 * T), *d_votes = votes ? t.get<unsigned char>(T) : nullptr;
-    uint16_t *d_pred = t.get<uint16_t>(T);
-    unsigned char *d_init = init_denoised ? t.get<unsigned char>(T) : nullptr, *d_masks = masks ? t.get<unsigned char>(it * T) : nullptr;
-    unsigned char *d_den = denoised ? t.get<unsigned char>(it * T) : nullptr;
-    double *d_thr = thresh ? t.get<double>(it * n) : nullptr;
-    signed char *d_ch = choice ? t.get<signed char>(it * n) : nullptr;
-    if (!d_off || !d_cube || !d_ijk || !d_pred || (votes && !d_votes) || (init_denoised && !d_init) || (masks && !d_masks) || (denoised && !d_den) ||
-        (thresh && !d_thr) || (choice && !d_ch))
-        return fail(SN_ERR_NOMEM, "sn_adapthresh: device allocation failed");
-    HIPCHK(hipMemcpyAsync(d_off, offsets, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_cube, cube_ijk, sizeof(uint32_t) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    if (T) {
-        HIPCHK(hipMemcpyAsync(d_ijk, ijk, 3 * T, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(d_pred, pred16, 2 * T, hipMemcpyHostToDevice, c->stream));
-        if (votes) HIPCHK(hipMemcpyAsync(d_votes, votes, T, hipMemcpyHostToDevice, c->stream));
-    }
-    if ((rc = cc_err_flag(c)) != SN_OK) return rc;
+    int64_t *d_off = t.up(c, offsets, (size_t)n + 1);
+    uint32_t *d_cube = t.up(c, cube_ijk, 3 * (size_t)n);
+    unsigned char *d_ijk = t.up(c, ijk, 3 * T), *d_votes = votes ? t.up(c, votes, T) : nullptr;
+    uint16_t *d_pred = t.up(c, pred16, T);
+    unsigned char *d_init = init_denoised ? t.out<unsigned char>(T) : nullptr, *d_masks = masks ? t.out<unsigned char>(it * T) : nullptr;
+    unsigned char *d_den = denoised ? t.out<unsigned char>(it * T) : nullptr;
+    double *d_thr = thresh ? t.out<double>(it * n) : nullptr;
+    signed char *d_ch = choice ? t.out<signed char>(it * n) : nullptr;
+    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_adapthresh: device allocation failed");
+    if ((rc = err_flag(c)) != SN_OK) return rc;
     rc = cc_adapthresh(c, n, (int)Dc, cfg, total, d_off, d_ijk, d_pred, d_votes, d_cube, d_init, d_thr, d_masks, d_den, d_ch);
     if (rc != SN_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
     if (init_denoised && T) HIPCHK(hipMemcpyAsync(init_denoised, d_init, T, hipMemcpyDeviceToHost, c->stream));

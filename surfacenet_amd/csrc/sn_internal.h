@@ -1,8 +1,10 @@
-// sn_internal.h — shared by the translation units of libsurfacenet_hip.so (sn_api.hip: context, weights, hot path,
-// RCCL, profiling; sn_post.hip: ray pooling + dense2sparse; sn_simil.hip: similarityNet + patch cropping): error state,
-// the context, owned device memory, HIP-event profiling, packed conv layers, ConvKernel (one conv3d_f16_mfma
-// instantiation as a type: its packing geometry and its launcher) and the plan rows - which kernel runs which layer -
-// that the weight packers and the forward passes walk.
+// sn_internal.h — shared by the translation units of libsurfacenet_hip.so (sn_api.hip: context, weights, hot path, RCCL, profiling;
+// sn_post.hip: ray pooling + dense2sparse; sn_simil.hip: similarityNet + patch cropping; sn_crosscube.hip: cross-cube denoising + adaptive
+// thresholding; sn_pointeval.hip: point-cloud evaluation; sn_ptcubes.hip: point-seeded cube list; sn_normals.hip: normals + de-duplication):
+// the context, owned device memory and the buffers that grow on demand (DevBuf), temporary device arrays with their host staging (TmpDev),
+// HIP-event profiling, packed conv layers, ConvKernel (one conv3d_f16_mfma instantiation as a type: its packing geometry and its launcher) and
+// the plan rows - which kernel runs which layer - that the weight packers and the forward passes walk. What needs no device (error text,
+// table sizes, Carve, the packed-list checks) is in sn_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -15,45 +17,23 @@
 #include <mutex>
 #include <thread>
 #include <type_traits>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <map>
 #include <string>
 #include <vector>
 
-#include "../../include/surfacenet_hip.h"
+#include "sn_host.h"
 #include "conv3d_mfma.h"
 #include "cvc_warp.h"
 #include "elementwise.h"
 
 using namespace sn;
 
-// ------------------------------------------------------------------------------------------------
-// errors
-// ------------------------------------------------------------------------------------------------
-inline thread_local std::string g_err;   // one per thread for the whole library (C++17 inline variable)
-
-static int fail(int code, const char *fmt, ...)
-{
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
 #define HIPCHK(expr)                                                                                       \
     do {                                                                                                   \
         hipError_t e_ = (expr);                                                                            \
         if (e_ != hipSuccess) return fail(SN_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
-
-
-static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
-
 
 // A conv layer prepared for conv3d_f16_mfma: packed fp16 weight fragments + folded BN.
 struct PackedConv {
@@ -132,6 +112,12 @@ static inline const char *sn_ab_switch(const char *name)
 #endif
 }
 
+// A device buffer of the context that grows on demand (dev_reserve) and lives until sn_destroy.
+struct DevBuf {
+    void *p = nullptr; size_t bytes = 0;
+    template <typename T> T *as() const { return static_cast<T *>(p); }
+};
+
 constexpr int CC_ERR_INPUT_FLAG = 2;      // sn_ctx::d_err value of the cross-cube post-pass (crosscube.h CC_ERR_INPUT): bad offsets table / voxel ijk
 
 struct sn_ctx {
@@ -162,7 +148,7 @@ struct sn_ctx {
     hipStream_t comm_stream = nullptr;                               // collectives that overlap the kernels (sn_allgather_f32_dev_overlap)
     hipEvent_t comm_ev[8] = {};                                      // ... their completion, per caller slot; comm_fork: "the kernels so far are done"
     hipEvent_t comm_fork = nullptr;
-    unsigned char *comm_stage = nullptr; size_t comm_stage_cap = 0;  // sn_allgatherv_bytes_dev: padded payloads of all ranks
+    DevBuf comm_stage;                                               // sn_allgatherv_bytes_dev: padded payloads of all ranks
     unsigned char *comm_small = nullptr;                             // ... its 8-byte-per-rank exchanges (counts, status): allocated with the communicator
     float *relw_W1 = nullptr, *relw_scale = nullptr, *relw_shift = nullptr, *relw_w2 = nullptr; float relw_b2 = 0;
     // activation workspace (channels-last fp16)
@@ -182,14 +168,15 @@ struct sn_ctx {
     float *semb_W = nullptr, *semb_b = nullptr; float ssim_w = 0, ssim_b = 0;
     std::vector<float> simil_host;   // the 13 conv layers' fp32 parameters, kept to re-pack on a precision switch
     std::vector<sn_param_desc> simil_descs;
-    void *sws = nullptr; size_t sws_bytes = 0; int sws_n = 0, sws_split = -1;
-    void *sview = nullptr; size_t sview_bytes = 0;      // sn_crop_embed: centres and embeddings of one whole call (no per-chunk host round trip)
+    DevBuf sws; int sws_n = 0, sws_split = -1;          // one chunk's tensors, re-made when the chunk capacity or the plane count changes
+    DevBuf sview;                                       // sn_crop_embed: centres and embeddings of one whole call (no per-chunk host round trip)
     // post-pass (ray pooling / dense2sparse) workspace
     unsigned *d_num = nullptr;    // numeric status word: bit i = conv layer i of the launch order stored a non-finite / fp16-overflowing value
     std::vector<std::string> num_names;   // layer name of each status bit
-    void *rp_ws = nullptr; size_t rp_ws_bytes = 0; int *d_err = nullptr;   /* device error flag: 1 ray pooling range, CC_ERR_INPUT_FLAG post-pass input */ int *d_counts = nullptr; int d_counts_cap = 0;
-    void *pe_ws = nullptr; size_t pe_ws_bytes = 0;   // point-cloud evaluation workspace (sn_pointeval.hip)
-    void *nm_ws = nullptr; size_t nm_ws_bytes = 0;   // normals / unique-voxel workspace: staged arrays, brick or cell table (sn_normals.hip)
+    DevBuf rp_ws, d_counts;       // ray pooling's hash tables; dense2sparse's per-cube counts
+    int *d_err = nullptr;         // device error flag (err_flag): 1 ray pooling range, CC_ERR_INPUT_FLAG post-pass input
+    DevBuf pe_ws;                 // point-cloud evaluation workspace (sn_pointeval.hip)
+    DevBuf nm_ws;                 // normals / unique-voxel workspace: staged arrays, brick or cell table (sn_normals.hip)
     std::vector<void *> owned;
     // profiling
     bool prof_on = false;
@@ -216,6 +203,32 @@ static int dev_free_owned(sn_ctx *c, void *p)
     auto it = std::find(c->owned.begin(), c->owned.end(), p);
     if (it != c->owned.end()) c->owned.erase(it);
     HIPCHK(hipFree(p));
+    return SN_OK;
+}
+
+// Makes b hold at least `need` bytes. A buffer that is too small is replaced, not copied: by one of need + extra bytes (headroom against
+// the next growth), once the stream is done with the old one. On failure b is empty.
+static int dev_reserve(sn_ctx *c, DevBuf &b, size_t need, size_t extra = 0)
+{
+    if (b.bytes >= need) return SN_OK;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    dev_free_owned(c, b.p);
+    b = DevBuf();
+    unsigned char *q = nullptr;
+    int rc = dev_alloc(c, &q, need + extra);
+    if (rc != SN_OK) return rc;
+    b.p = q; b.bytes = need + extra;
+    return SN_OK;
+}
+
+// The device error flag sn_synchronize reports (sn_ctx::d_err), allocated and cleared on first use.
+static int err_flag(sn_ctx *c)
+{
+    if (!c->d_err) {
+        int rc = dev_alloc(c, &c->d_err, 1);
+        if (rc != SN_OK) return rc;
+        HIPCHK(hipMemsetAsync(c->d_err, 0, sizeof(int), c->stream));
+    }
     return SN_OK;
 }
 
@@ -377,10 +390,24 @@ struct ConvKernel {
                                       sn::sn_conv_has_bridge<KS, SPLIT, NW, PCH, NF, K2D, MF>(), &launch};
 };
 
-// Temporary device buffers of the host-array entry points (freed on scope exit).
+// Temporary device arrays of one call (freed on scope exit: the stream must be done with them by then). out() allocates, up() allocates and
+// copies a host array in on the context's stream. A failed allocation (or copy) clears `ok` for good: an entry stages all its arrays, then
+// tests `ok` once.
 struct TmpDev {
     std::vector<void *> p;
+    bool ok = true;
     ~TmpDev() { for (void *q : p) (void)hipFree(q); }
-    template <typename T> T *get(size_t count) { void *q = nullptr; if (hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) return nullptr; p.push_back(q); return static_cast<T *>(q); }
+    template <typename T> T *out(size_t count)
+    {
+        void *q = nullptr;
+        if (hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) { ok = false; return nullptr; }
+        p.push_back(q);
+        return static_cast<T *>(q);
+    }
+    template <typename T> T *up(sn_ctx *c, const T *host, size_t count)
+    {
+        T *d = out<T>(count);
+        if (d && count && hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, c->stream) != hipSuccess) ok = false;
+        return d;
+    }
 };
-

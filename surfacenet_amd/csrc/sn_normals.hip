@@ -7,34 +7,6 @@ namespace {
 
 constexpr long long NM_MAX_VOXELS = 1ll << 28;       // hash tables of >= 2 * total slots stay within 2^29
 
-// Carves the context's workspace (base == nullptr: only measures).
-struct NMCarve {
-    unsigned char *base = nullptr;
-    size_t off = 0;
-    template <typename T> T *get(size_t n)
-    {
-        off = (off + 255) & ~(size_t)255;
-        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
-        off += std::max<size_t>(n, 1) * sizeof(T);
-        return p;
-    }
-};
-
-int nm_workspace(sn_ctx *c, size_t need, unsigned char **base)
-{
-    if (c->nm_ws_bytes < need) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->nm_ws) dev_free_owned(c, c->nm_ws);
-        c->nm_ws = nullptr; c->nm_ws_bytes = 0;
-        unsigned char *w = nullptr;
-        int rc = dev_alloc(c, &w, need);
-        if (rc != SN_OK) return rc;
-        c->nm_ws = w; c->nm_ws_bytes = need;
-    }
-    *base = static_cast<unsigned char *>(c->nm_ws);
-    return SN_OK;
-}
-
 // One call's arrays: the inputs and outputs (the caller's device arrays, or staged copies of host arrays) and the work buffers.
 struct NMCall {
     int n = 0, K = 0, V = 0;
@@ -50,12 +22,12 @@ struct NMCall {
     bool want_normals = false, want_moments = false;
 };
 
-template <typename T> void nm_stage(NMCarve &w, bool host, T *&p, size_t count, bool wanted = true)
+template <typename T> void nm_stage(Carve &w, bool host, T *&p, size_t count, bool wanted = true)
 {
     if (host && wanted) p = w.get<typename std::remove_const<T>::type>(count);
 }
 
-void nm_layout(NMCarve &w, NMCall &k)
+void nm_layout(Carve &w, NMCall &k)
 {
     const size_t n = (size_t)k.n, T = (size_t)k.total;
     nm_stage(w, k.host, k.off, n + 1);
@@ -77,15 +49,13 @@ void nm_layout(NMCarve &w, NMCall &k)
 
 int nm_prepare(sn_ctx *c, NMCall &k)
 {
-    unsigned cap = 64;
-    while (cap < 2ull * (unsigned long long)k.total) cap <<= 1;
-    k.cap = cap;
-    NMCarve measure;
+    k.cap = (unsigned)table_cap((unsigned long long)k.total, 2, 64);
+    Carve measure;
     NMCall probe = k;
     nm_layout(measure, probe);
-    NMCarve w;
-    int rc = nm_workspace(c, measure.off + 256, &w.base);
+    int rc = dev_reserve(c, c->nm_ws, measure.off + 256);
     if (rc != SN_OK) return rc;
+    Carve w{c->nm_ws.as<unsigned char>()};
     nm_layout(w, k);
     return SN_OK;
 }
@@ -110,18 +80,8 @@ int nm_check_cfg(const sn_normals_cfg *cfg, bool want_normals)
 
 int nm_check_total(int n, long long total)
 {
-    if (total < 0) return fail(SN_ERR_ARG, "total must be >= 0");
     if (total > NM_MAX_VOXELS) return fail(SN_ERR_ARG, "total = %lld: at most %lld voxels", total, NM_MAX_VOXELS);
-    if (n == 0 && total != 0) return fail(SN_ERR_ARG, "offsets table of 0 cubes holds %lld voxels", total);
-    return SN_OK;
-}
-
-int nm_check_host_table(int n, const int64_t *offsets)
-{
-    if (offsets[0] != 0) return fail(SN_ERR_ARG, "offsets[0] = %lld, must be 0", (long long)offsets[0]);
-    for (int i = 0; i < n; ++i)
-        if (offsets[i + 1] < offsets[i]) return fail(SN_ERR_ARG, "offsets table decreases at cube %d", i);
-    return SN_OK;
+    return pl_check_counts(n, total);
 }
 
 // The computation on device arrays. Returns when the stream is done (the flags are read in between, the work buffers are the context's).
@@ -204,8 +164,7 @@ extern "C" int sn_normals(sn_ctx *c, int n, const sn_normals_cfg *cfg, const int
     if ((rc = nm_check_cfg(cfg, normals != nullptr)) != SN_OK) return rc;
     if ((rc = nm_check_common(c, n, cfg->stride_vox)) != SN_OK) return rc;
     if (!offsets) return fail(SN_ERR_ARG, "null argument");
-    if (n == 0) return offsets[0] == 0 ? SN_OK : fail(SN_ERR_ARG, "offsets[0] = %lld, must be 0", (long long)offsets[0]);
-    if ((rc = nm_check_host_table(n, offsets)) != SN_OK) return rc;
+    if ((rc = pl_check_host_offsets(n, offsets)) != SN_OK || n == 0) return rc;      // (no cubes: the table is its single entry)
     const long long total = offsets[n];
     if ((rc = nm_check_total(n, total)) != SN_OK) return rc;
     if (!cube_ijk || (total > 0 && (!ijk || !mask))) return fail(SN_ERR_ARG, "null argument");
@@ -256,8 +215,7 @@ extern "C" int sn_unique_voxels(sn_ctx *c, int n, int stride_vox, const int64_t 
     int rc;
     if ((rc = nm_check_common(c, n, stride_vox)) != SN_OK) return rc;
     if (!offsets) return fail(SN_ERR_ARG, "null argument");
-    if (n == 0) return offsets[0] == 0 ? SN_OK : fail(SN_ERR_ARG, "offsets[0] = %lld, must be 0", (long long)offsets[0]);
-    if ((rc = nm_check_host_table(n, offsets)) != SN_OK) return rc;
+    if ((rc = pl_check_host_offsets(n, offsets)) != SN_OK || n == 0) return rc;      // (no cubes: the table is its single entry)
     const long long total = offsets[n];
     if ((rc = nm_check_total(n, total)) != SN_OK) return rc;
     if (!cube_ijk || (total > 0 && (!ijk || !mask || !keep))) return fail(SN_ERR_ARG, "null argument");

@@ -10,34 +10,6 @@ constexpr long long PE_MAX_POINTS = 1ll << 29;       // hash tables of 2n slots 
 constexpr int PE_MAX_ROUNDS = 1 << 16;               // reduction rounds before sn_point_reduce gives up (random orders take tens)
 constexpr double PE_CELL_TARGET = 6.0;               // mean points per occupied fine cell of the NN grid
 
-// Bump allocation from the context's evaluation workspace: a first pass with no base sizes it.
-struct Carve {
-    unsigned char *base = nullptr;
-    size_t off = 0;
-    template <typename T> T *get(size_t n)
-    {
-        off = (off + 255) & ~(size_t)255;
-        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
-        off += std::max<size_t>(n, 1) * sizeof(T);
-        return p;
-    }
-};
-
-int pe_workspace(sn_ctx *c, size_t need, unsigned char **base)
-{
-    if (c->pe_ws_bytes < need) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->pe_ws) dev_free_owned(c, c->pe_ws);
-        c->pe_ws = nullptr; c->pe_ws_bytes = 0;
-        unsigned char *w = nullptr;
-        int rc = dev_alloc(c, &w, need);
-        if (rc != SN_OK) return rc;
-        c->pe_ws = w; c->pe_ws_bytes = need;
-    }
-    *base = static_cast<unsigned char *>(c->pe_ws);
-    return SN_OK;
-}
-
 struct Box { double lo[3], hi[3]; };
 
 bool host_box(const double *xyz, long long n, Box &b)
@@ -61,13 +33,6 @@ double fit_h(double h, const Box &b)
     return (h > 0 && std::isfinite(h)) ? h : 1.0;
 }
 
-unsigned table_cap(long long n)
-{
-    unsigned cap = 1024;
-    while (cap < 2 * (unsigned long long)n) cap <<= 1;
-    return cap;
-}
-
 struct GridBufs {
     unsigned long long *keys; int *start, *count, *slot, *pos, *idx, *rank_s, *sums; double *xyz_s;
     unsigned cap; int n;
@@ -75,7 +40,7 @@ struct GridBufs {
 
 void grid_carve(Carve &cv, GridBufs &b, long long n, bool with_rank)
 {
-    b.n = (int)n; b.cap = table_cap(n);
+    b.n = (int)n; b.cap = (unsigned)table_cap((unsigned long long)n, 2, 1024);
     b.keys = cv.get<unsigned long long>(b.cap); b.start = cv.get<int>(b.cap); b.count = cv.get<int>(b.cap); b.sums = cv.get<int>(scan_sums(b.cap));
     b.slot = cv.get<int>(n); b.pos = cv.get<int>(n); b.idx = cv.get<int>(n); b.xyz_s = cv.get<double>(3 * (size_t)n);
     b.rank_s = with_rank ? cv.get<int>(n) : nullptr;
@@ -158,8 +123,8 @@ extern "C" int sn_point_reduce(sn_ctx *c, long long n, const double *xyz, const 
     };
     Carve sizing;
     layout(sizing);
-    Carve cv;
-    if ((rc = pe_workspace(c, sizing.off, &cv.base)) != SN_OK) return rc;
+    if ((rc = dev_reserve(c, c->pe_ws, sizing.off)) != SN_OK) return rc;
+    Carve cv{c->pe_ws.as<unsigned char>()};
     layout(cv);
     HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(d_rank, rank, sizeof(long long) * (size_t)n, hipMemcpyHostToDevice, c->stream));
@@ -219,8 +184,8 @@ extern "C" int sn_nn_dist2(sn_ctx *c, long long n_to, const double *to, long lon
     };
     Carve sizing;
     layout(sizing);
-    Carve cv;
-    if ((rc = pe_workspace(c, sizing.off, &cv.base)) != SN_OK) return rc;
+    if ((rc = dev_reserve(c, c->pe_ws, sizing.off)) != SN_OK) return rc;
+    Carve cv{c->pe_ws.as<unsigned char>()};
     layout(cv);
     HIPCHK(hipMemcpyAsync(d_to, to, sizeof(double) * 3 * (size_t)n_to, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(d_from, from, sizeof(double) * 3 * (size_t)n_from, hipMemcpyHostToDevice, c->stream));
@@ -291,8 +256,8 @@ extern "C" int sn_point_flags(sn_ctx *c, long long n, const double *xyz, const u
     };
     Carve sizing;
     layout(sizing);
-    Carve cv;
-    if ((rc = pe_workspace(c, sizing.off, &cv.base)) != SN_OK) return rc;
+    if ((rc = dev_reserve(c, c->pe_ws, sizing.off)) != SN_OK) return rc;
+    Carve cv{c->pe_ws.as<unsigned char>()};
     layout(cv);
     HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
     if (mbytes) HIPCHK(hipMemcpyAsync(d_mask, mask, mbytes, hipMemcpyHostToDevice, c->stream));

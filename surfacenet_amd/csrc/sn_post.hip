@@ -21,23 +21,14 @@ static int launch_ray_pool(sn_ctx *c, int n, int n_vp, const int64_t *pairs_dev,
     if (!c->cams) return fail(SN_ERR_STATE, "sn_set_cameras must be called before ray pooling");
     if (2 * n_vp > 255) return fail(SN_ERR_ARG, "2*n_vp = %d votes do not fit the uint8 result", 2 * n_vp);
     const size_t s3 = (size_t)c->s * c->s * c->s;
-    size_t cap = 64;
-    while (cap < 2 * s3) cap <<= 1;
+    const size_t cap = table_cap(s3, 2, 64);
     const size_t per_wg = cap * (8 + 8 + 8 + 4) + s3 * 4;
     const int E = 2 * n_vp;
     const size_t budget = (size_t)1 << 30;                      // hash-table workspace per launch
     int cubes = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, budget / (per_wg * E)));
     const size_t need = per_wg * E * cubes;
-    if (!c->d_err) { int rc = dev_alloc(c, &c->d_err, 1); if (rc != SN_OK) return rc; HIPCHK(hipMemsetAsync(c->d_err, 0, sizeof(int), c->stream)); }
-    if (c->rp_ws_bytes < need) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->rp_ws) dev_free_owned(c, c->rp_ws);
-        c->rp_ws = nullptr; c->rp_ws_bytes = 0;
-        unsigned char *w = nullptr;
-        int rc = dev_alloc(c, &w, need);
-        if (rc != SN_OK) return rc;
-        c->rp_ws = w; c->rp_ws_bytes = need;
-    }
+    int rc;
+    if ((rc = err_flag(c)) != SN_OK || (rc = dev_reserve(c, c->rp_ws, need)) != SN_OK) return rc;
     HIPCHK(hipMemsetAsync(votes_dev, 0, (size_t)n * s3, c->stream));
     for (int i0 = 0; i0 < n; i0 += cubes) {
         const int m = std::min(cubes, n - i0);
@@ -46,12 +37,12 @@ static int launch_ray_pool(sn_ctx *c, int n, int n_vp, const int64_t *pairs_dev,
         memset(&a, 0, sizeof a);
         a.pairs = pairs_dev + (size_t)i0 * E; a.xyz = xyz_dev + 3 * (size_t)i0; a.resol = resol_dev + i0; a.cams = c->cams;
         a.pred = pred_dev + (size_t)i0 * s3; a.votes = votes_dev + (size_t)i0 * s3;
-        unsigned char *w = static_cast<unsigned char *>(c->rp_ws);
-        a.pix_key = reinterpret_cast<unsigned long long *>(w); w += wgs * cap * 8;
-        a.pix_best = reinterpret_cast<unsigned long long *>(w); w += wgs * cap * 8;
-        a.cell_key = reinterpret_cast<unsigned long long *>(w); w += wgs * cap * 8;
-        a.cell_idx = reinterpret_cast<unsigned *>(w); w += wgs * cap * 4;
-        a.cslot = reinterpret_cast<unsigned *>(w);
+        // Five tables of this launch's wgs workgroups, packed: three of cap 8-byte slots per workgroup, one of cap 4-byte slots, one of s3
+        // 4-byte slots, at the byte offsets 0, 8 wgs cap, 16 wgs cap, 24 wgs cap and 28 wgs cap. cap is a power of two >= 64, so each of them is
+        // a multiple of 256 and Carve's alignment moves none.
+        Carve w{c->rp_ws.as<unsigned char>()};
+        a.pix_key = w.get<unsigned long long>(wgs * cap); a.pix_best = w.get<unsigned long long>(wgs * cap);
+        a.cell_key = w.get<unsigned long long>(wgs * cap); a.cell_idx = w.get<unsigned>(wgs * cap); a.cslot = w.get<unsigned>(wgs * s3);
         a.err = c->d_err;
         a.n_vp = n_vp; a.s = c->s; a.V = c->V_cam; a.cap_max = (int)cap; a.use_thresh = use_thresh; a.thresh = min_prob;
         // algorithmic bytes: the prediction cube is read once per distinct view (<= E), the votes are written once
@@ -99,17 +90,11 @@ extern "C" int sn_dense2sparse_dev(sn_ctx *c, int n, int n_vp, const int64_t *pa
         if (!pairs_dev || !xyz_dev || !resol_dev || !votes_ws_dev) return fail(SN_ERR_ARG, "ray pooling needs view pairs, xyz, resol and the votes scratch");
         if ((rc = launch_ray_pool(c, n, n_vp, pairs_dev, xyz_dev, resol_dev, pred_dev, 1, cfg->min_prob, votes_ws_dev)) != SN_OK) return rc;
     }
-    if (c->d_counts_cap < n) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->d_counts) dev_free_owned(c, c->d_counts);
-        c->d_counts = nullptr; c->d_counts_cap = 0;
-        if ((rc = dev_alloc(c, &c->d_counts, (size_t)n)) != SN_OK) return rc;
-        c->d_counts_cap = n;
-    }
+    if ((rc = dev_reserve(c, c->d_counts, sizeof(int) * (size_t)n)) != SN_OK) return rc;
     SparseArgs a;
     memset(&a, 0, sizeof a);
     a.pred = pred_dev; a.rgb = rgb_out_dev ? rgb_dev : nullptr; a.votes = need_votes ? votes_ws_dev : nullptr;
-    a.offsets = reinterpret_cast<long long *>(offsets_dev); a.counts = c->d_counts;
+    a.offsets = reinterpret_cast<long long *>(offsets_dev); a.counts = c->d_counts.as<int>();
     a.ijk = ijk_dev; a.pred16 = pred16_dev; a.rgb_out = rgb_out_dev; a.votes_out = votes_out_dev;
     a.s = c->s; a.lo = lo; a.dc = dc;
     a.by_votes = by_votes ? 1 : 0; a.vote_thresh = cfg->rayPool_thresh; a.min_prob = cfg->min_prob;
@@ -117,7 +102,7 @@ extern "C" int sn_dense2sparse_dev(sn_ctx *c, int n, int n_vp, const int64_t *pa
     // algorithmic bytes: the keep rule reads 4 B (pred) or 1 B (votes) per voxel twice (count + write); kept voxels add <= 9 B
     ProfScope ps(c, "dense2sparse", 0, vox * (by_votes ? 1.0 : 4.0) * 2.0);
     hipLaunchKernelGGL(d2s_count_kernel, dim3((unsigned)n), dim3(D2S_NT), 0, c->stream, a);
-    hipLaunchKernelGGL(d2s_scan_kernel, dim3(1), dim3(64), 0, c->stream, c->d_counts, a.offsets, n);
+    hipLaunchKernelGGL(d2s_scan_kernel, dim3(1), dim3(64), 0, c->stream, a.counts, a.offsets, n);
     hipLaunchKernelGGL(d2s_write_kernel, dim3((unsigned)n), dim3(D2S_NT), 0, c->stream, a);
     HIPCHK(hipGetLastError());
     return SN_OK;
@@ -137,13 +122,9 @@ extern "C" int sn_ray_pool(sn_ctx *c, int n, int n_vp, const int64_t *pairs, con
     if ((rc = check_pairs_cam(c, (long long)n * n_vp * 2, pairs, wp)) != SN_OK) return rc;
     const size_t s3 = (size_t)c->s * c->s * c->s;
     TmpDev t;
-    int64_t *d_p = t.get<int64_t>((size_t)n * n_vp * 2); float *d_x = t.get<float>(3 * (size_t)n), *d_r = t.get<float>(n), *d_pr = t.get<float>(n * s3);
-    unsigned char *d_v = t.get<unsigned char>(n * s3);
-    if (!d_p || !d_x || !d_r || !d_pr || !d_v) return fail(SN_ERR_NOMEM, "sn_ray_pool: device allocation failed");
-    HIPCHK(hipMemcpyAsync(d_p, wp.data(), sizeof(int64_t) * 2 * n * n_vp, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_x, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_r, resol, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_pr, pred, sizeof(float) * n * s3, hipMemcpyHostToDevice, c->stream));
+    int64_t *d_p = t.up(c, wp.data(), (size_t)n * n_vp * 2); float *d_x = t.up(c, xyz, 3 * (size_t)n), *d_r = t.up(c, resol, (size_t)n), *d_pr = t.up(c, pred, n * s3);
+    unsigned char *d_v = t.out<unsigned char>(n * s3);
+    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_ray_pool: device allocation failed");
     if ((rc = launch_ray_pool(c, n, n_vp, d_p, d_x, d_r, d_pr, use_thresh, min_prob, d_v)) != SN_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
     HIPCHK(hipMemcpyAsync(votes, d_v, n * s3, hipMemcpyDeviceToHost, c->stream));
     return sn_synchronize(c);
@@ -168,22 +149,15 @@ extern "C" int sn_dense2sparse(sn_ctx *c, int n, int n_vp, const int64_t *pairs,
         if (!pairs || !xyz || !resol) return fail(SN_ERR_ARG, "ray pooling needs view pairs, xyz and resol");
         if (!c->cams) return fail(SN_ERR_STATE, "sn_set_cameras must be called before ray pooling");
         if ((rc = check_pairs_cam(c, (long long)n * n_vp * 2, pairs, wp)) != SN_OK) return rc;
-        d_p = t.get<int64_t>((size_t)n * n_vp * 2); d_x = t.get<float>(3 * (size_t)n); d_r = t.get<float>(n); d_vws = t.get<unsigned char>(n * s3);
-        if (!d_p || !d_x || !d_r || !d_vws) return fail(SN_ERR_NOMEM, "sn_dense2sparse: device allocation failed");
-        HIPCHK(hipMemcpyAsync(d_p, wp.data(), sizeof(int64_t) * 2 * n * n_vp, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(d_x, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(d_r, resol, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+        d_p = t.up(c, wp.data(), (size_t)n * n_vp * 2); d_x = t.up(c, xyz, 3 * (size_t)n); d_r = t.up(c, resol, (size_t)n); d_vws = t.out<unsigned char>(n * s3);
     }
-    float *d_pr = t.get<float>(n * s3);
-    unsigned char *d_rgb = rgb_out ? t.get<unsigned char>(3 * n * s3) : nullptr;
-    int64_t *d_off = t.get<int64_t>((size_t)n + 1);
-    unsigned char *d_ijk = t.get<unsigned char>(3 * cap), *d_ro = rgb_out ? t.get<unsigned char>(3 * cap) : nullptr;
-    unsigned char *d_vo = (votes_out && cfg->enable_rayPooling) ? t.get<unsigned char>(cap) : nullptr;
-    uint16_t *d_p16 = t.get<uint16_t>(cap);
-    if (!d_pr || !d_off || !d_ijk || !d_p16 || (rgb_out && (!d_rgb || !d_ro)) || (votes_out && cfg->enable_rayPooling && !d_vo))
-        return fail(SN_ERR_NOMEM, "sn_dense2sparse: device allocation failed");
-    HIPCHK(hipMemcpyAsync(d_pr, pred, sizeof(float) * n * s3, hipMemcpyHostToDevice, c->stream));
-    if (rgb_out) HIPCHK(hipMemcpyAsync(d_rgb, rgb, 3 * n * s3, hipMemcpyHostToDevice, c->stream));
+    float *d_pr = t.up(c, pred, n * s3);
+    unsigned char *d_rgb = rgb_out ? t.up(c, rgb, 3 * n * s3) : nullptr;
+    int64_t *d_off = t.out<int64_t>((size_t)n + 1);
+    unsigned char *d_ijk = t.out<unsigned char>(3 * cap), *d_ro = rgb_out ? t.out<unsigned char>(3 * cap) : nullptr;
+    unsigned char *d_vo = (votes_out && cfg->enable_rayPooling) ? t.out<unsigned char>(cap) : nullptr;
+    uint16_t *d_p16 = t.out<uint16_t>(cap);
+    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_dense2sparse: device allocation failed");
     rc = sn_dense2sparse_dev(c, n, n_vp, d_p, d_x, d_r, d_pr, d_rgb, cfg, d_vws, d_off, d_ijk, d_p16, d_ro, d_vo);
     if (rc != SN_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
     HIPCHK(hipMemcpyAsync(offsets, d_off, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, c->stream));
@@ -213,11 +187,9 @@ extern "C" int sn_project_points(sn_ctx *c, int V, const double *P, int n, const
     HIPCHK(hipSetDevice(c->device));
     const size_t tot = (size_t)V * n;
     TmpDev t;
-    double *d_x = t.get<double>((size_t)n * 3), *d_h = t.get<double>(tot), *d_w = t.get<double>(tot), *d_d = depth ? t.get<double>(tot) : nullptr;
-    double *d_P = P ? t.get<double>((size_t)V * 12) : c->cams;
-    if (!d_x || !d_h || !d_w || !d_P || (depth && !d_d)) return fail(SN_ERR_NOMEM, "sn_project_points: device allocation failed");
-    if (P) HIPCHK(hipMemcpyAsync(d_P, P, sizeof(double) * 12 * V, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_x, xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream));
+    double *d_x = t.up(c, xyz, (size_t)n * 3), *d_h = t.out<double>(tot), *d_w = t.out<double>(tot), *d_d = depth ? t.out<double>(tot) : nullptr;
+    double *d_P = P ? t.up(c, P, (size_t)V * 12) : c->cams;
+    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_project_points: device allocation failed");
     {
         ProfScope ps(c, "project_points", 0, (double)n * 24.0 + (double)tot * (depth ? 24.0 : 16.0));
         hipLaunchKernelGGL(project_points_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)V), dim3(256), 0, c->stream, d_P, d_x, n, round_int,

@@ -53,8 +53,8 @@ int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap,
     for (int d = 0; d < 3; ++d) { src.lo[d] = cfg->lo[d]; src.hi[d] = cfg->hi[d]; }
     TmpDev t;
     SyncOnExit sync{c};
-    PCStats *d_st = t.get<PCStats>(1);
-    if (!d_st) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
+    PCStats *d_st = t.out<PCStats>(1);
+    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
     PCStats st;
     {
         ProfScope ps(c, "pc_bounds", 0, (double)n * 3.0 * sizeof(P));
@@ -89,10 +89,10 @@ int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap,
     unsigned long long *list = nullptr;
     if (dense) {
         n_words = (int)((a.dim[0] * a.dim[1] * a.dim[2] + 63) / 64);
-        a.bitmap = t.get<unsigned long long>(n_words);
-        int *count = t.get<int>((size_t)n_words + 1), *sums = t.get<int>(scan_sums((size_t)n_words + 1));
-        start = t.get<int>((size_t)n_words + 1);
-        if (!a.bitmap || !count || !sums || !start) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
+        a.bitmap = t.out<unsigned long long>(n_words);
+        int *count = t.out<int>((size_t)n_words + 1), *sums = t.out<int>(scan_sums((size_t)n_words + 1));
+        start = t.out<int>((size_t)n_words + 1);
+        if (!t.ok) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
         HIPCHK(hipMemsetAsync(a.bitmap, 0, sizeof(unsigned long long) * (size_t)n_words, c->stream));
         HIPCHK(hipMemsetAsync(count + n_words, 0, sizeof(int), c->stream));
         {
@@ -110,13 +110,12 @@ int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap,
         HIPCHK(hipStreamSynchronize(c->stream));
         total = tot;
     } else {
-        unsigned tcap = 2048;
-        while (tcap < 4ull * (unsigned long long)n) tcap <<= 1;
+        const unsigned tcap = (unsigned)table_cap((unsigned long long)n, 4, 2048);
         a.mask = tcap - 1;
-        a.table = t.get<unsigned long long>(tcap);
-        a.list = list = t.get<unsigned long long>(tcap / 2);       // >= 2n keys, a power of two >= PC_TILE: room for the sort's padding
-        a.n_list = t.get<unsigned long long>(1);
-        if (!a.table || !a.list || !a.n_list) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
+        a.table = t.out<unsigned long long>(tcap);
+        a.list = list = t.out<unsigned long long>(tcap / 2);       // >= 2n keys, a power of two >= PC_TILE: room for the sort's padding
+        a.n_list = t.out<unsigned long long>(1);
+        if (!t.ok) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
         HIPCHK(hipMemsetAsync(a.table, 0xff, sizeof(unsigned long long) * (size_t)tcap, c->stream));
         HIPCHK(hipMemsetAsync(a.n_list, 0, sizeof(unsigned long long), c->stream));
         {
@@ -137,16 +136,15 @@ int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap,
     if (!out_host && (!ijk || !xyz)) return fail(SN_ERR_ARG, "null output");
     e.ijk = ijk; e.xyz = xyz; e.cap = cap;
     if (out_host) {
-        e.ijk = t.get<uint32_t>(3 * (size_t)total); e.xyz = t.get<float>(3 * (size_t)total); e.cap = total;
-        if (!e.ijk || !e.xyz) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
+        e.ijk = t.out<uint32_t>(3 * (size_t)total); e.xyz = t.out<float>(3 * (size_t)total); e.cap = total;
+        if (!t.ok) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
     }
     if (dense) {
         ProfScope ps(c, "pc_emit", 0, (double)total * 24.0 + (double)n_words * 12.0);
         hipLaunchKernelGGL(pc_emit_dense_kernel, dim3(blocks(n_words)), dim3(PC_NT), 0, c->stream, (const unsigned long long *)a.bitmap, (const int *)start, n_words, e);
         HIPCHK(hipGetLastError());
     } else {
-        long long p2 = PC_TILE;
-        while (p2 < total) p2 <<= 1;
+        const long long p2 = (long long)table_cap((unsigned long long)total, 1, PC_TILE);
         if (p2 > total) hipLaunchKernelGGL(pc_pad_kernel, dim3(blocks(p2 - total)), dim3(PC_NT), 0, c->stream, list, total, p2);
         int rc = pc_sort(c, list, p2);
         if (rc != SN_OK) return rc;
@@ -201,9 +199,8 @@ extern "C" int sn_ptcubes(sn_ctx *c, long long n, const void *pts, const sn_ptcu
     HIPCHK(hipSetDevice(c->device));
     TmpDev t;
     const size_t bytes = 3 * (size_t)n * (cfg->pts_f64 ? sizeof(double) : sizeof(float));
-    unsigned char *d_pts = t.get<unsigned char>(bytes);
-    if (!d_pts) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
-    if (n) HIPCHK(hipMemcpyAsync(d_pts, pts, bytes, hipMemcpyHostToDevice, c->stream));
+    unsigned char *d_pts = t.up(c, static_cast<const unsigned char *>(pts), bytes);
+    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
     rc = pc_points(c, n, d_pts, cfg, cap, true, ijk, xyz, n_cells);
     (void)hipStreamSynchronize(c->stream);
     return rc;
@@ -218,7 +215,7 @@ extern "C" int sn_ptcubes_sparse_dev(sn_ctx *c, int n_cubes, long long total, co
     if ((rc = pc_check_cfg(cfg, total, cap, n_cells)) != SN_OK) return rc;
     if (cfg->pts_f64) return fail(SN_ERR_ARG, "the voxels of sparse lists are float32 points");
     if (n_cubes < 0) return fail(SN_ERR_ARG, "n_cubes must be >= 0");
-    if (n_cubes == 0) { *n_cells = 0; return total == 0 ? SN_OK : fail(SN_ERR_ARG, "offsets table of 0 cubes holds %lld voxels", total); }
+    if ((rc = pl_check_counts(n_cubes, total)) != SN_OK || n_cubes == 0) { *n_cells = 0; return rc; }      // (total >= 0: pc_check_cfg)
     if (!offsets_dev || !cube_xyz_dev || !cube_resol_dev || (total > 0 && (!vxl_ijk_dev || !mask_dev))) return fail(SN_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(c->device));
     PCPoints<float> s;

@@ -103,16 +103,12 @@ struct SimilWs {
     Act p0, a[5][2], pool[5];
     float *feat, *emb, *part; double *centers; unsigned char *patches;
 };
-static size_t simil_carve(sn_ctx *c, int cap, int npl, SimilWs *w)
+static size_t simil_carve(unsigned char *base, int cap, int npl, SimilWs *w)
 {
-    size_t off = 0;
-    char *base = static_cast<char *>(c->sws);
+    Carve cv{base};
     auto act = [&](int ch, int H) {
         const size_t halfs = (size_t)ch * H * H * cap;
-        Act t{base ? reinterpret_cast<_Float16 *>(base + off) : nullptr, (long long)halfs};
-        off += halfs * 2 * npl;
-        off = (off + 255) / 256 * 256;
-        return t;
+        return Act{cv.get<_Float16>(halfs * npl), (long long)halfs};
     };
     static const int C[5] = {64, 128, 256, 512, 512};
     SimilWs t;
@@ -121,29 +117,24 @@ static size_t simil_carve(sn_ctx *c, int cap, int npl, SimilWs *w)
         const int H = kPatch >> st;
         t.a[st][0] = act(C[st], H); t.a[st][1] = act(C[st], H); t.pool[st] = act(C[st], H / 2);
     }
-    auto raw = [&](size_t bytes) { char *p = base ? base + off : nullptr; off += (bytes + 255) / 256 * 256; return p; };
-    t.feat = reinterpret_cast<float *>(raw((size_t)cap * kSimilFeat * 4));
-    t.emb = reinterpret_cast<float *>(raw((size_t)cap * kEmb * 4));
-    t.part = reinterpret_cast<float *>(raw((size_t)cap * kEmb * 4 * kDenseKS));
-    t.centers = reinterpret_cast<double *>(raw((size_t)cap * 2 * 8));
-    t.patches = reinterpret_cast<unsigned char *>(raw((size_t)cap * kPatch * kPatch * 3));
+    t.feat = cv.get<float>((size_t)cap * kSimilFeat);
+    t.emb = cv.get<float>((size_t)cap * kEmb);
+    t.part = cv.get<float>((size_t)cap * kEmb * kDenseKS);
+    t.centers = cv.get<double>((size_t)cap * 2);
+    t.patches = cv.get<unsigned char>((size_t)cap * kPatch * kPatch * 3);      // (a multiple of 256 bytes: `off` ends aligned)
     if (w) *w = t;
-    return off;
+    return cv.off;
 }
 static int simil_workspace(sn_ctx *c, int n, SimilWs *w)
 {
     const int cap = std::min(std::max(n, 8), kSimChunk), npl = simil_mode(c) ? 2 : 1;
-    if (!c->sws || c->sws_n < cap || c->sws_split != npl) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->sws) dev_free_owned(c, c->sws);
-        c->sws = nullptr; c->sws_n = 0;
-        const size_t bytes = simil_carve(c, cap, npl, nullptr);
-        unsigned char *p = nullptr;
-        int rc = dev_alloc(c, &p, bytes);
+    if (!c->sws.p || c->sws_n < cap || c->sws_split != npl) {
+        c->sws.bytes = 0; c->sws_n = 0;      // re-made whenever a key changes, whatever its size: dev_reserve frees it and allocates
+        int rc = dev_reserve(c, c->sws, simil_carve(nullptr, cap, npl, nullptr));
         if (rc != SN_OK) return rc;
-        c->sws = p; c->sws_bytes = bytes; c->sws_n = cap; c->sws_split = npl;
+        c->sws_n = cap; c->sws_split = npl;
     }
-    simil_carve(c, c->sws_n, npl, w);
+    simil_carve(c->sws.as<unsigned char>(), c->sws_n, npl, w);
     return SN_OK;
 }
 
@@ -241,8 +232,8 @@ extern "C" int sn_patch2embedding(sn_ctx *c, int n, const float *patches, float 
     if ((rc = simil_ready(c)) != SN_OK) return rc;
     TmpDev t;
     const size_t per = (size_t)3 * kPatch * kPatch;
-    float *d_x = t.get<float>(per * std::min(n, kSimChunk));
-    if (!d_x) return fail(SN_ERR_NOMEM, "sn_patch2embedding: device allocation failed");
+    float *d_x = t.out<float>(per * std::min(n, kSimChunk));
+    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_patch2embedding: device allocation failed");
     SimilWs w;
     for (int i0 = 0; i0 < n; i0 += kSimChunk) {
         const int m = std::min(kSimChunk, n - i0);
@@ -274,16 +265,8 @@ extern "C" int sn_crop_embed(sn_ctx *c, int view, int n, const double *center_h,
     // centres up and embeddings down ONCE per call: the chunks of a view (62 for a DTU image) run back to back on the stream instead of
     // each waiting for two uploads, a download and a host synchronisation (7 % of the early-rejection stage)
     const size_t need = (size_t)n * (2 * sizeof(double) + kEmb * sizeof(float)) + 256;
-    if (c->sview_bytes < need) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->sview) dev_free_owned(c, c->sview);
-        c->sview = nullptr; c->sview_bytes = 0;
-        unsigned char *p = nullptr;
-        const size_t cap = need + need / 4;
-        if ((rc = dev_alloc(c, &p, cap)) != SN_OK) return rc;
-        c->sview = p; c->sview_bytes = cap;
-    }
-    double *d_ch = static_cast<double *>(c->sview), *d_cw = d_ch + n;
+    if ((rc = dev_reserve(c, c->sview, need, need / 4)) != SN_OK) return rc;
+    double *d_ch = c->sview.as<double>(), *d_cw = d_ch + n;
     float *d_emb = reinterpret_cast<float *>(d_cw + n);
     HIPCHK(hipMemcpyAsync(d_ch, center_h, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(d_cw, center_w, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
@@ -308,9 +291,8 @@ extern "C" int sn_embeddingpair2simil(sn_ctx *c, int n_pairs, const float *emb_p
     if (!c->simil_loaded) return fail(SN_ERR_STATE, "sn_simil_load_weights has not been called");
     HIPCHK(hipSetDevice(c->device));
     TmpDev t;
-    float *d_e = t.get<float>((size_t)2 * n_pairs * kEmb), *d_s = t.get<float>(n_pairs);
-    if (!d_e || !d_s) return fail(SN_ERR_NOMEM, "sn_embeddingpair2simil: device allocation failed");
-    HIPCHK(hipMemcpyAsync(d_e, emb_pairs, sizeof(float) * 2 * n_pairs * kEmb, hipMemcpyHostToDevice, c->stream));
+    float *d_e = t.up(c, emb_pairs, (size_t)2 * n_pairs * kEmb), *d_s = t.out<float>(n_pairs);
+    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_embeddingpair2simil: device allocation failed");
     {
         ProfScope ps(c, "pair_simil", 0, (double)n_pairs * (2.0 * kEmb + 1.0) * 4.0);
         hipLaunchKernelGGL(pair_simil_kernel, dim3((unsigned)((n_pairs + 3) / 4)), dim3(256), 0, c->stream, d_e, d_s, n_pairs, c->ssim_w, c->ssim_b);
@@ -335,11 +317,9 @@ extern "C" int sn_embeddings2simil(sn_ctx *c, int n_cubes, int n_views, const fl
         for (int j = i + 1; j < n_views; ++j) { pairs.push_back(i); pairs.push_back(j); }      // itertools.combinations order
     TmpDev t;
     const size_t ne = (size_t)n_cubes * n_views * kEmb, ns = (size_t)n_cubes * P;
-    float *d_e = t.get<float>(ne), *d_s = t.get<float>(ns);
-    int *d_p = t.get<int>(pairs.size());
-    if (!d_e || !d_s || !d_p) return fail(SN_ERR_NOMEM, "sn_embeddings2simil: device allocation failed");
-    HIPCHK(hipMemcpyAsync(d_e, embeddings, sizeof(float) * ne, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_p, pairs.data(), sizeof(int) * pairs.size(), hipMemcpyHostToDevice, c->stream));
+    float *d_e = t.up(c, embeddings, ne), *d_s = t.out<float>(ns);
+    int *d_p = t.up(c, pairs.data(), pairs.size());
+    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_embeddings2simil: device allocation failed");
     {
         ProfScope ps(c, "pair_simil_all", 0, (double)ns * (2.0 * kEmb + 1.0) * 4.0);
         hipLaunchKernelGGL(pair_simil_all_kernel, dim3((unsigned)((ns + 3) / 4)), dim3(256), 0, c->stream, d_e, d_p, d_s, (long long)ns, n_views, P,

@@ -1,0 +1,176 @@
+"""GPU (-m gpu): the context's device workspaces (sn_internal.h DevBuf / dev_reserve) through the entries that carve them. One context, and
+per entry three calls, small -> large -> small: the first allocates the workspace, the second has to grow it, the third runs in a buffer
+larger than it needs. Every result equals the entry's restatement (bit for bit, or within the tolerance the entry's own test module uses),
+and the third equals the first bit for bit. The packed-list entries also take a call without cubes and one without voxels in between."""
+import os
+
+import numpy as np
+import pytest
+
+import golden_util
+import normals_ref
+import pointeval_ref
+from oracle import post_oracle, simil_oracle
+
+pytestmark = pytest.mark.gpu
+GOLD = os.path.join(os.path.dirname(__file__), "golden")
+P_DTU = np.load(os.path.join(GOLD, "cameras.npz"))["P_dtu"]
+SIMIL = np.load(os.path.join(GOLD, "simil_cases.npz"))
+MEAN_BGR = np.asarray([103.939, 116.779, 123.68]).astype(np.float32)
+S = 8                      # the smallest cube edge a context takes
+TOL_NORMAL = 2e-7          # tests/test_gpu_normals.py TOL
+TOL_EMB = 2e-5             # tests/test_gpu_simil.py TOL_EMB_X3
+
+
+@pytest.fixture(scope="module")
+def ctx(gpu_required):
+    import surfacenet_amd
+    from surfacenet_amd import weights
+    H, W = (int(v) for v in SIMIL["sc_hw"])
+    with surfacenet_amd.Context(cube_D=S, max_samples=2) as c:
+        c.set_cameras(P_DTU)
+        c.set_images([golden_util.synth_image(int(sd), H, W) for sd in SIMIL["sc_seeds"]])
+        c.load_simil_param_values(weights.synthetic_simil_param_values(1))      # the weights tests/test_gpu_simil.py sets against the oracle
+        yield c
+
+
+def _same(a, b):
+    return all(np.array_equal(np.asarray(x).view(np.uint8), np.asarray(y).view(np.uint8)) for x, y in zip(a, b)) and len(a) == len(b)
+
+
+# ---- normals and unique voxels: one workspace ------------------------------------------------------------------------------------------------
+def _stepped_sheet(nx, ny):
+    """nx x ny cubes of 8^3 voxels at a stride of 4 (neighbours overlap by half): each lists its part of the one-voxel sheet z = (x + y) // 10."""
+    cubes, lists = [], []
+    for cx in range(nx):
+        for cy in range(ny):
+            cubes.append([cx, cy, 0])
+            lists.append(np.asarray([(i, j, (4 * cx + i + 4 * cy + j) // 10) for i in range(8) for j in range(8)], np.uint8))
+    return normals_ref.hand_scene(cubes, lists, stride_vox=4)
+
+
+def _normals_and_unique(ctx, s):
+    nrm, mom = ctx.normals(*normals_ref.scene_args(s), return_moments=True)
+    keep = ctx.unique_voxels(s["offsets"], s["ijk"], s["cube_ijk"], s["mask"], s["stride_vox"])      # between two normals calls: the same workspace
+    r = normals_ref.normals_ref(*normals_ref.scene_args(s))
+    assert np.array_equal(mom, r["moments"])
+    assert np.array_equal(keep, normals_ref.unique_ref(s["offsets"], s["ijk"], s["cube_ijk"], s["mask"], s["stride_vox"]))
+    assert r["comparable"].any() and np.abs(nrm[r["comparable"]].astype(np.float64) - r["normals"][r["comparable"]]).max() <= TOL_NORMAL
+    assert not nrm[~r["solved"]].any()
+    return nrm, mom, keep
+
+
+def _empty_packed_calls(ctx):
+    none = normals_ref.hand_scene(np.zeros((0, 3)), [], stride_vox=4)                                  # n = 0
+    bare = normals_ref.hand_scene([[0, 0, 0], [1, 0, 0]], [np.zeros((0, 3), np.uint8)] * 2, stride_vox=4)   # total = 0
+    for e in (none, bare):
+        nrm, mom = ctx.normals(*normals_ref.scene_args(e), return_moments=True)
+        assert nrm.shape == (0, 3) and mom.shape == (0, 10)
+        assert ctx.unique_voxels(e["offsets"], e["ijk"], e["cube_ijk"], e["mask"], 4).shape == (0,)
+
+
+def test_normals_and_unique_share_a_growing_workspace(ctx):
+    small, large = _stepped_sheet(2, 1), _stepped_sheet(8, 5)
+    assert len(small["cube_ijk"]) == 2 and len(large["cube_ijk"]) == 40
+    first = _normals_and_unique(ctx, small)
+    _empty_packed_calls(ctx)
+    _normals_and_unique(ctx, large)
+    _empty_packed_calls(ctx)
+    third = _normals_and_unique(ctx, small)
+    assert _same(first, third)
+    assert not first[2].all() and first[2].any()               # the overlap: some cells are listed by both cubes
+
+
+# ---- point-cloud evaluation --------------------------------------------------------------------------------------------------------------------
+def _cloud(n, seed):
+    rs = np.random.RandomState(seed)
+    p = np.concatenate([rs.uniform(0, 4, (n - n // 5, 3)), np.repeat(rs.uniform(0, 4, (n // 10, 3)), 2, axis=0)])      # a tenth of them twice
+    return p[rs.permutation(n)], rs.permutation(n)
+
+
+def _reduce_and_nn(ctx, n):
+    p, order = _cloud(n, n)
+    rank = np.empty(n, np.int64)
+    rank[order] = np.arange(n)
+    keep, rounds = ctx.point_reduce(p, rank, 0.2)
+    assert np.array_equal(keep, pointeval_ref.reduce_sequential(p, order, 0.2)) and rounds >= 1 and not keep.all()
+    to, frm = p[: n // 2], p[n // 2:] + 0.01
+    d2 = ctx.nn_dist2(to, frm, 0.5)
+    want = pointeval_ref.nn_d2(to, frm)
+    below = want < 0.25 * (1.0 + 2.0 ** -40)
+    assert below.any() and np.array_equal(d2[below], want[below]) and np.all(d2[~below] == np.inf)
+    return keep, d2
+
+
+def test_point_reduce_and_nn_dist2_small_large_small(ctx):
+    first = _reduce_and_nn(ctx, 50)
+    _reduce_and_nn(ctx, 5000)
+    assert _same(first, _reduce_and_nn(ctx, 50))
+
+
+# ---- ray pooling and dense2sparse ---------------------------------------------------------------------------------------------------------------
+def _cubes(n):
+    rs = np.random.RandomState(40 + n)
+    g = np.indices((S, S, S)).astype(np.float32) / S
+    pred = np.stack([np.clip(np.exp(-((g[i % 3] - 0.5) * 4) ** 2) * 0.9 + 0.08 * rs.rand(S, S, S), 0, 0.9999) for i in range(n)]).astype(np.float32)
+    pairs = rs.randint(0, 4, (n, 2, 2))
+    xyz = (rs.rand(n, 3) * [60, 60, 40] + [-30, -30, 590]).astype(np.float32)
+    resol = np.full(n, 0.4, np.float32)
+    rgb = rs.randint(0, 256, (n, 3, S, S, S)).astype(np.uint8)
+    return pred, pairs, xyz, resol, rgb
+
+
+def _ray_pool(ctx, n):
+    pred, pairs, xyz, resol, _ = _cubes(n)
+    votes = ctx.ray_pool(pairs, xyz, resol, pred, 0.5)
+    p16 = pred.astype(np.float16)
+    for i in range(n):
+        assert np.array_equal(votes[i], post_oracle.ray_pool_1cube(P_DTU, p16[i], pairs[i], xyz[i], resol[i], 0.5).astype(np.uint8)), i
+    assert votes.any()
+    return (votes,)
+
+
+def test_ray_pool_small_large_small(ctx):
+    first = _ray_pool(ctx, 1)
+    _ray_pool(ctx, 4)
+    assert _same(first, _ray_pool(ctx, 1))
+
+
+def _dense2sparse(ctx, n):
+    pred, pairs, xyz, resol, rgb = _cubes(n)
+    off, ijk, p16, rgb_out, votes = ctx.dense2sparse(pred, rgb, pairs, xyz, resol, min_prob=0.5, rayPool_thresh=0, enable_rayPooling=True)
+    want = post_oracle.dense2sparse(pred.astype(np.float16), np.ascontiguousarray(np.transpose(rgb, (0, 2, 3, 4, 1))), xyz, resol, pairs, min_prob=0.5,
+                                    rayPool_thresh=0, enable_rayPooling=True, cameraPOs=P_DTU)
+    counts = np.diff(off)
+    assert off[0] == 0 and np.nonzero(counts)[0].tolist() == list(want[0]) and counts.sum() > 0
+    assert np.array_equal(ijk, np.concatenate(want[1])) and np.array_equal(p16.view(np.uint16), np.concatenate(want[2]).view(np.uint16))
+    assert np.array_equal(rgb_out, np.concatenate(want[3])) and np.array_equal(votes, np.concatenate(want[4]))
+    return off, ijk, p16, rgb_out, votes
+
+
+def test_dense2sparse_small_large_small(ctx):
+    first = _dense2sparse(ctx, 1)
+    _dense2sparse(ctx, 4)
+    assert _same(first, _dense2sparse(ctx, 1))
+
+
+# ---- similarityNet: the chunk workspace and the per-call buffer ---------------------------------------------------------------------------------------
+def _centres(n):
+    rs = np.random.RandomState(n)
+    H, W = (int(v) for v in SIMIL["sc_hw"])
+    return rs.uniform(40, H - 40, n), rs.uniform(40, W - 40, n)
+
+
+def test_crop_embed_small_large_small(ctx):
+    from surfacenet_amd import weights
+    H, W = (int(v) for v in SIMIL["sc_hw"])
+    (h3, w3), (h40, w40) = _centres(3), _centres(40)
+    # the oracle once, for the 43 patches of both sizes
+    raw = simil_oracle.crop_patches(golden_util.synth_image(int(SIMIL["sc_seeds"][0]), H, W), np.concatenate([h3, h40]), np.concatenate([w3, w40]))
+    want = simil_oracle.embedding_torch(simil_oracle.preprocess(raw, MEAN_BGR), weights.synthetic_simil_param_values(1))
+    first = ctx.crop_embed(0, h3, w3, MEAN_BGR)
+    large = ctx.crop_embed(0, h40, w40, MEAN_BGR)
+    third = ctx.crop_embed(0, h3, w3, MEAN_BGR)
+    assert first.shape == (3, 128) and large.shape == (40, 128)
+    assert np.abs(first - want[:3]).max() < TOL_EMB and np.abs(large - want[3:]).max() < TOL_EMB
+    assert _same((first,), (third,))
