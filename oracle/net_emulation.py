@@ -59,7 +59,18 @@ def _ilogb(a):
     return out
 
 
-def forward_emulated(X, values, w=None, n_vp=1, mode="f16x3", table=None, s8_act=S8_ACT, s6_of=None, m8_block_scale=False):
+def renorm_exponents(p):
+    """Per-channel exponents e of a ReLU layer's stored output y * 2^e (sn_load_weights): e = -ilogb(max(|gamma|, |beta|)); p: the layer's parameters."""
+    m = np.maximum(np.abs(p["gamma"].astype(np.float64)), np.abs(p["beta"].astype(np.float64)))
+    oe = np.clip(-_ilogb(m), -60, 60).astype(np.float64)
+    oe[~(m > 0)] = 0
+    return oe
+
+
+def _model(values, mode="f16x3", table=None, s8_act=S8_ACT, s6_of=None, m8_block_scale=False):
+    """The model's building blocks for one parameter set and mode: the stored-tensor class T, conv (one layer), up (the fixed upsampler), the
+    per-layer format lookup f and the format A of the 1x1x1 layers - shared by forward_emulated and layer_step."""
+    import types
     import torch
     import torch.nn.functional as F
     assert mode in ("f16x3", "f16m8")
@@ -207,11 +218,7 @@ def forward_emulated(X, values, w=None, n_vp=1, mode="f16x3", table=None, s8_act
         y = (torch.relu(y) if act == "relu" else torch.sigmoid(y)).to(td)
         if raw_out:
             return y
-        oe = np.zeros(O)
-        if act == "relu":
-            m = np.maximum(np.abs(p["gamma"].astype(np.float64)), np.abs(p["beta"].astype(np.float64)))
-            oe = np.clip(-_ilogb(m), -60, 60).astype(np.float64)
-            oe[~(m > 0)] = 0
+        oe = renorm_exponents(p) if act == "relu" else np.zeros(O)
         return T(y, oe, s6_tab.get(name, s6_out))       # s6_tab: premultiplier of a layer's OUTPUT tensor as its fp6 readers see it
 
     def up(x, name, f):
@@ -224,6 +231,26 @@ def forward_emulated(X, values, w=None, n_vp=1, mode="f16x3", table=None, s8_act
 
     A = "m6" if full else "x3"          # arithmetic / storage of the 1x1x1 layers and side maps upstream of the concat buffer
     f = (lambda name: "m6") if full else (lambda name: fmt_of[name])
+    return types.SimpleNamespace(T=T, conv=conv, up=up, A=A, f=f, P=P, s6_tab=s6_tab, full=full)
+
+
+# format in which each stored tensor's 3x3x3 (or, for the side maps and conv4_3, 1x1x1 / upsampling) reader sees it: (default mode, f16m8 mode)
+def _reader_fmt(m, name):
+    if m.full:
+        return "m6"
+    return {"conv3_3": m.f("conv4_1"), "conv4_1": m.f("conv4_2"), "conv4_2": m.f("conv4_3"), "cat": m.f("merge_conv_a"),
+            "merge_a": m.f("merge_conv_b")}.get(name, "x3")
+
+
+def forward_emulated(X, values, w=None, n_vp=1, mode="f16x3", table=None, s8_act=S8_ACT, s6_of=None, m8_block_scale=False,
+                     return_intermediates=False):
+    """return_intermediates: also a dict name -> fp64 array (names of net_oracle.forward_torch) of every stored tensor AS ITS READERS SEE IT,
+    i.e. the model's decoded storage in original units (conv3_3 additionally as "conv3_3_x3": the hi + lo planes side_op3 reads)."""
+    import torch
+    import torch.nn.functional as F
+    td = torch.float64
+    m = _model(values, mode, table, s8_act, s6_of, m8_block_scale)
+    T, conv, up, A, f, P, s6_tab = m.T, m.conv, m.up, m.A, m.f, m.P, m.s6_tab
     x = T(torch.from_numpy(np.ascontiguousarray(X)).to(td), np.zeros(X.shape[1]), S_X0, 0)
     c11 = conv(x, "conv1_1", "conv3", "relu", f("conv1_1"))
     c12 = conv(c11, "conv1_2", "conv3", "relu", f("conv1_2"))
@@ -259,4 +286,79 @@ def forward_emulated(X, values, w=None, n_vp=1, mode="f16x3", table=None, s8_act
     unf = out.numpy().astype(np.float64)
     s = X.shape[-1]
     unfused = unf.reshape(-1, n_vp, s, s, s)
+    if return_intermediates:
+        stored = dict(conv1_1=c11, conv1_2=c12, conv1_3=c13, pool1=p1, conv2_1=c21, conv2_2=c22, conv2_3=c23, pool2=p2, side2_pre=s2,
+                      conv3_1=c31, conv3_2=c32, conv3_3=c33, side3_pre=s3, conv4_1=c41, conv4_2=c42, conv4_3=c43, side4_pre=s4, cat=cat, merge_a=ma)
+        inter = {k: t.v(_reader_fmt(m, k)).numpy() for k, t in stored.items()}
+        inter["conv3_3_x3"] = c33.v(A).numpy()
+        inter["side1"] = inter["cat"][:, :16]
+        inter["merge_b"] = mb.numpy()
+        inter["x"] = x.v(_reader_fmt(m, "x")).numpy()
+        # the producers' unrounded fp32 results (original units) the stored planes were made from - what an encoder of the storage formats starts from
+        inter["unrounded"] = {k: (t.r / torch.exp2(t.oe)).numpy() for k, t in dict(stored, x=x).items()}
+        return net_oracle.fuse(unfused, w, n_vp), unfused, inter
     return net_oracle.fuse(unfused, w, n_vp), unfused
+
+
+STEPS = net_oracle.STEPS
+_KIND = {name: (kind, act) for name, kind, _, _, act in net_oracle.LAYERS}
+
+
+def layer_step(values, step, inputs, mode="f16x3", **kw):
+    """The model's output for one step of STEPS, given the DECODED stored inputs (fp64 arrays in original units, e.g. what tests/act_decode.py
+    makes of the device's planes): a list of fp64 arrays, the step's stored outputs as their readers see them. Same arithmetic as
+    forward_emulated - the same conv / T / up objects."""
+    import torch
+    import torch.nn.functional as F
+    td = torch.float64
+    m = _model(values, mode, **kw)
+    T, conv, up, A, f, P = m.T, m.conv, m.up, m.A, m.f, m.P
+
+    def oe_of(name):                      # the renormalisation exponents a stored ReLU tensor carries
+        return renorm_exponents(P[name])
+
+    def stored(a, name):                  # a decoded array -> the T its producer would have left
+        a = torch.from_numpy(np.ascontiguousarray(a)).to(td)
+        if name == "x":
+            return T(a, np.zeros(a.shape[1]), S_X0, 0)
+        if name == "cat":
+            return T(a, np.zeros(64), S_CAT)
+        if name.startswith("side"):
+            return T(a, np.zeros(16))
+        src = {"pool1": "conv1_3", "pool2": "conv2_3", "conv3_3_x3": "conv3_3", "merge_a": "merge_conv_a"}.get(name, name)
+        return T(a, oe_of(src), m.s6_tab.get(src if not name.startswith("pool") else name, S_ACT))
+
+    def c(x, name, **k2):
+        kind, act = _KIND[name]
+        return conv(x, name, kind, act, f(name) if kind in ("conv3", "dil3") else A, **k2)
+
+    ins, outs = STEPS[step]
+    assert len(inputs) == len(ins), (step, len(inputs))
+    x = [stored(a, n) for a, n in zip(inputs, ins)]
+    if step in ("conv1_3+side_op1+pool1", "conv2_3+side_op2+pool2"):
+        main, side = step.split("+")[:2]
+        t = c(x[0], main)
+        y = t.r / torch.exp2(t.oe)
+        sv = conv(y, side, "conv1", "sigmoid", "x3", raw_out=True)
+        pool = T(F.max_pool3d(y, 2, 2), t.oe.view(-1).numpy(), m.s6_tab.get(outs[1], S_ACT))
+        if side == "side_op1":            # written into the concat buffer, in its format
+            pad = torch.zeros(sv.shape[0], 48, *sv.shape[2:], dtype=td)
+            sv = T(torch.cat([sv, pad], dim=1), np.zeros(64), S_CAT).v(_reader_fmt(m, "cat"))[:, :16]
+        else:
+            sv = T(sv, np.zeros(16)).v(A)
+        return [sv.numpy(), pool.v(_reader_fmt(m, outs[1])).numpy()]
+    if step == "upsample":
+        v = torch.cat([up(x[0].v(A), "side_op2_deconv", 2), up(x[1].v(A), "side_op3_deconv", 4), up(x[2].v(A), "side_op4_deconv", 4)], dim=1)
+        pad = torch.zeros(v.shape[0], 16, *v.shape[2:], dtype=td)
+        return [T(torch.cat([pad, v], dim=1), np.zeros(64), S_CAT).v(_reader_fmt(m, "cat"))[:, 16:].numpy()]
+    if step == "merge_conv_b+merge_conv3":
+        mb = c(x[0], "merge_conv_b", raw_out=True)
+        p3 = P["merge_conv3"]
+        y = F.conv3d(mb, torch.from_numpy(np.ascontiguousarray(p3["W"].astype(np.float64))).to(td))
+        scale = (p3["gamma"].astype(np.float64) * p3["inv_std"].astype(np.float64)).astype(np.float32)
+        shift = (p3["beta"].astype(np.float64) - p3["mean"].astype(np.float64) * scale.astype(np.float64)).astype(np.float32)
+        return [torch.sigmoid(y.to(torch.float32) * float(scale[0]) + float(shift[0])).to(td).numpy()]
+    t = x[0]
+    for name in step.split("+"):
+        t = c(t, name)
+    return [t.v(A if o.endswith("_x3") else _reader_fmt(m, o)).numpy() for o in outs]

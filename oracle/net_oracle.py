@@ -156,18 +156,23 @@ def forward_torch(X, values, w=None, n_vp=1, quant=None, dtype="float64", return
     s1 = conv(c13, "side_op1", "conv1", "sigmoid")
     c21 = conv(p1, "conv2_1", "conv3", "relu"); c22 = conv(c21, "conv2_2", "conv3", "relu"); c23 = conv(c22, "conv2_3", "conv3", "relu")
     p2 = F.max_pool3d(c23, 2, 2)
-    s2 = up(conv(c23, "side_op2", "conv1", "sigmoid"), "side_op2_deconv", 2)
+    s2p = conv(c23, "side_op2", "conv1", "sigmoid")
+    s2 = up(s2p, "side_op2_deconv", 2)
     c31 = conv(p2, "conv3_1", "conv3", "relu"); c32 = conv(c31, "conv3_2", "conv3", "relu"); c33 = conv(c32, "conv3_3", "conv3", "relu")
-    s3 = up(conv(c33, "side_op3", "conv1", "sigmoid"), "side_op3_deconv", 4)
+    s3p = conv(c33, "side_op3", "conv1", "sigmoid")
+    s3 = up(s3p, "side_op3_deconv", 4)
     c41 = conv(c33, "conv4_1", "dil3", "relu"); c42 = conv(c41, "conv4_2", "dil3", "relu"); c43 = conv(c42, "conv4_3", "dil3", "relu")
-    s4 = up(conv(c43, "side_op4", "dil1", "sigmoid"), "side_op4_deconv", 4)
+    s4p = conv(c43, "side_op4", "dil1", "sigmoid")
+    s4 = up(s4p, "side_op4_deconv", 4)
     cat = torch.cat([s1, s2, s3, s4], dim=1)
     ma = conv(cat, "merge_conv_a", "conv3", "relu")
     mb = conv(ma, "merge_conv_b", "conv3", "relu", store=(quant is None))  # device keeps merge_b in fp32 registers
     out = conv(mb, "merge_conv3", "conv1", "sigmoid", store=False)
     if return_intermediates:
-        inter = dict(conv1_1=c11, conv1_3=c13, pool1=p1, side1=s1, conv2_3=c23, side2=s2, conv3_3=c33, side3=s3,
-                     conv4_1=c41, conv4_3=c43, side4=s4, cat=cat, merge_a=ma, merge_b=mb)
+        # every tensor the device stores in one plan or another (side2_pre .. side4_pre: the side maps before their upsampling)
+        inter = dict(conv1_1=c11, conv1_2=c12, conv1_3=c13, pool1=p1, side1=s1, conv2_1=c21, conv2_2=c22, conv2_3=c23, pool2=p2,
+                     side2_pre=s2p, side2=s2, conv3_1=c31, conv3_2=c32, conv3_3=c33, side3_pre=s3p, side3=s3,
+                     conv4_1=c41, conv4_2=c42, conv4_3=c43, side4_pre=s4p, side4=s4, cat=cat, merge_a=ma, merge_b=mb)
         inter = {k: v.numpy() for k, v in inter.items()}
     unf = out.numpy().astype(np.float64)
     s = X.shape[-1]
@@ -176,6 +181,88 @@ def forward_torch(X, values, w=None, n_vp=1, quant=None, dtype="float64", return
     if return_intermediates:
         return fused, unfused, inter
     return fused, unfused
+
+
+# The local steps of the device's plan: stored input(s) -> stored output(s), in forward_torch's names. A fused entry (conv1_3 / conv2_3 with side
+# conv and pool in the epilogue, the three side maps' upsampling into concat channels 16..63 = "cat48", merge_conv_b with merge_conv3) is
+# one step, and so is a pair of layers whose intermediate buffer is overwritten later in the pass (conv3_1 + conv3_2: conv3_3 reuses the
+# buffer; conv4_1 + conv4_2: conv4_3 does). "conv3_3" / "conv3_3_x3": conv3_3's output as conv4_1 / as side_op3 reads it (the default mode stores it
+# with hi, lo and code planes; the same tensor to the oracle).
+STEPS = {
+    "conv1_1": (("x",), ("conv1_1",)), "conv1_2": (("conv1_1",), ("conv1_2",)), "conv1_3+side_op1+pool1": (("conv1_2",), ("side1", "pool1")),
+    "conv2_1": (("pool1",), ("conv2_1",)), "conv2_2": (("conv2_1",), ("conv2_2",)), "conv2_3+side_op2+pool2": (("conv2_2",), ("side2_pre", "pool2")),
+    "conv3_1+conv3_2": (("pool2",), ("conv3_2",)), "conv3_3": (("conv3_2",), ("conv3_3", "conv3_3_x3")), "side_op3": (("conv3_3_x3",), ("side3_pre",)),
+    "conv4_1+conv4_2": (("conv3_3",), ("conv4_2",)), "conv4_3": (("conv4_2",), ("conv4_3",)), "side_op4": (("conv4_3",), ("side4_pre",)),
+    "upsample": (("side2_pre", "side3_pre", "side4_pre"), ("cat48",)),
+    "merge_conv_a": (("cat",), ("merge_a",)), "merge_conv_b+merge_conv3": (("merge_a",), ("out",)),
+}
+
+
+def step_torch(values, step, inputs, dtype="float64", quant=None):
+    """One step of STEPS applied to given inputs (arrays in original units, e.g. the device's decoded stored tensors): the same layer
+    arithmetic as forward_torch (dtype / quant as there; quant rounds the weights, every layer output of the step and the inputs; quant "x3"
+    rounds them to an unevaluated sum hi + lo of two halfs, the operand and storage format of the device's f16x3 arithmetic).
+    Returns (outputs, scales): per output the result and the forward-error scale A of the element, the magnitude an error of relative size
+    eps in every product and every stored value can reach: one layer, A = (|W| (*) |x|) |scale|; a second layer of the step sees its
+    input off by up to eps (A1 + |y1|) (ReLU and max are 1-Lipschitz), so A2 = (|W2| (*) (A1 + |y1|)) |scale2|; the pool takes the max of A;
+    a sigmoid (slope <= 1/4 < 1) keeps its pre-activation's A; the upsampler's weights and inputs are non-negative, A = its output."""
+    import torch
+    import torch.nn.functional as F
+    td = getattr(torch, dtype)
+    P = params_to_dict(values)
+    kinds = {name: (kind, act) for name, kind, _, _, act in LAYERS}
+
+    def q(t):
+        if quant == "x3":
+            h = t.to(torch.float16).to(td)
+            return h + (t - h).to(torch.float16).to(td)
+        return t.to(torch.float16).to(td) if quant == "fp16" else t
+
+    def layer(x, ax, name):
+        kind, act = kinds[name]
+        p = P[name]
+        W = np.transpose(p["W"], (1, 0, 2, 3, 4)) if kind in ("dil3", "dil1") else p["W"]
+        Wt = q(torch.from_numpy(np.ascontiguousarray(W)).to(td))
+        k = W.shape[2]
+        cv = (lambda xx, ww: F.conv3d(F.pad(xx, (2,) * 6), ww, dilation=2)) if kind == "dil3" else (lambda xx, ww: F.conv3d(xx, ww, padding=k // 2))
+        scale = p["gamma"].astype(np.float64) * p["inv_std"].astype(np.float64)
+        shift = p["beta"].astype(np.float64) - p["mean"].astype(np.float64) * scale
+        bt = torch.float32 if (quant == "fp16" or dtype == "float32") else td      # the device's epilogue (and forward_torch's quant path): fp32 constants
+        sc = torch.from_numpy(scale.astype(np.float32 if bt == torch.float32 else np.float64)).view(1, -1, 1, 1, 1)
+        sh = torch.from_numpy(shift.astype(np.float32 if bt == torch.float32 else np.float64)).view(1, -1, 1, 1, 1)
+        y = cv(x, Wt).to(bt) * sc + sh
+        y = (torch.relu(y) if act == "relu" else torch.sigmoid(y)).to(td)
+        a = cv(ax, Wt.abs()) * torch.from_numpy(np.abs(scale)).to(td).view(1, -1, 1, 1, 1)
+        return y, a
+
+    def up(x, name, f):
+        k = P[name]["W"].shape[2]
+        Wk = torch.from_numpy(np.ascontiguousarray(P[name]["W"])).to(td)
+        B, C = x.shape[:2]
+        z = torch.zeros((B, C, x.shape[2] * f, x.shape[3] * f, x.shape[4] * f), dtype=td)
+        z[:, :, ::f, ::f, ::f] = x
+        return F.conv3d(z.reshape(B * C, 1, *z.shape[2:]), Wk, padding=k // 2).reshape(B, C, *z.shape[2:])
+
+    ins, _ = STEPS[step]
+    assert len(inputs) == len(ins), (step, len(inputs))
+    x = [q(torch.from_numpy(np.ascontiguousarray(a)).to(td)) for a in inputs]
+    if step == "upsample":
+        y = q(torch.cat([up(x[0], "side_op2_deconv", 2), up(x[1], "side_op3_deconv", 4), up(x[2], "side_op4_deconv", 4)], dim=1))
+        outs, scales = [y], [y.abs()]
+    elif "pool" in step:
+        main, side = step.split("+")[:2]
+        t, at = layer(x[0], x[0].abs(), main)
+        sv, asv = layer(t, at + t.abs(), side)          # (side conv and pool read the unrounded registers)
+        outs, scales = [q(sv), q(F.max_pool3d(t, 2, 2))], [asv, F.max_pool3d(at, 2, 2)]
+    else:
+        t, at = x[0], None
+        names = step.split("+")
+        for i, name in enumerate(names):
+            t, at = layer(t, t.abs() if at is None else at + t.abs(), name)
+            if i + 1 < len(names) and name != "merge_conv_b":      # (merge_conv_b's output stays in fp32 registers)
+                t = q(t)
+        outs, scales = [t if names[-1] == "merge_conv3" else q(t)] * len(STEPS[step][1]), [at] * len(STEPS[step][1])
+    return [o.to(torch.float64).numpy() for o in outs], [a.to(torch.float64).numpy() for a in scales]
 
 
 def fuse(unfused, w, n_vp):

@@ -1510,16 +1510,78 @@ int sn_memcpy_d2h_after(sn_ctx *c, int slot, void *dst, const void *src, size_t 
 }
 
 #ifdef SN_DEBUG_HOOKS     // test-only twin library (Makefile target dbg): not in the product .so, not in the ABI header
-// Test hook (not part of the ABI header): raw copy of an internal activation buffer ("cat": concat buffer, "ma": merge_conv_a output;
-// both planes, layout of DESIGN.md section 3) for comparing the device's stored codes with oracle/net_emulation.py.
+// What a workspace buffer holds after a forward pass of the context's current plan: the tensor-table row it was LAST written as, and the
+// storage format of that write (conv3d_mfma.h OSPLIT: 0 fp16 | 1 hi + lo | 2 hi + 6-bit code slots | 3 hi + fp8 code slots | 4 hi + lo + fp8
+// code slots). Host fields only. Buffers are named as the context's members: kTensors rows T_X0 .. T_MA in order, plus "a3c".
+static const char *const kDebugTensorNames[] = {"", "x0", "a1", "b1", "cat", "p1", "a2", "b2", "s2", "p2", "a3", "b3", "a4", "b4", "s3", "s4", "ma"};
+struct DebugTensor { int buf = 0, tid = 0, fmt = 0; bool a3c = false; };
+static int debug_tensor_find(const sn_ctx *c, const char *name, DebugTensor &d)
+{
+    const NetPlan &p = c->plan;
+    if (p.conv.empty() || p.tens.size() != (size_t)T_COUNT) return fail(SN_ERR_STATE, "sn_debug_tensor: no plan yet (sn_load_weights first)");
+    d = DebugTensor();
+    d.a3c = !strcmp(name, "a3c");
+    for (int t = T_X0; t <= T_MA; ++t) if (!strcmp(d.a3c ? "a3" : name, kDebugTensorNames[t])) d.buf = t;
+    if (!d.buf) return fail(SN_ERR_ARG, "unknown tensor %s", name);
+    d.tid = d.buf; d.fmt = d.buf == T_X0 ? p.split : -1;      // (the network input: written by the CVC warp / the upload in the operand mode's format)
+    auto wrote = [&](int tid, int fmt) { if (tid != T_NONE && kTensors[tid].buf == kTensors[d.buf].buf) { d.tid = tid; d.fmt = fmt; } };
+    for (size_t i = 0; i < p.conv.size(); ++i) {      // the launch order of run_net
+        const ConvEntry &e = p.conv[i];
+        if (e.k.epi == EPI_SIDEPOOL && i + 1 < p.conv.size()) {      // the side map in the kernel's output format, the pooled tensor in its operand format
+            wrote(p.conv[i + 1].out, e.k.osplit); wrote(p.conv[i + 1].pool_out, e.k.split);
+            ++i;
+            continue;
+        }
+        if (e.k.epi != EPI_FINAL) wrote(e.out, e.k.osplit);
+        if (e.pool_tag) wrote(e.pool_out, p.split);
+    }
+    if (d.fmt < 0) return fail(SN_ERR_STATE, "sn_debug_tensor: the current plan never writes %s", name);
+    if (d.a3c && p.tens[d.tid].code == 0) return fail(SN_ERR_STATE, "sn_debug_tensor: the current plan keeps no code plane a3c");
+    return SN_OK;
+}
+
+// Test hook (not part of the ABI header): for the context's current plan, how the named workspace buffer is laid out -
+// out = {extent (cube_D >> level), channel stride, planes, lo-plane offset, code-plane offset (both in halfs from the start, -1: none), E8M0
+// premultiplier exponent of its code plane (127 - s), total bytes, storage format as above}. A tensor whose code plane lives in the separate
+// buffer a3c (conv3_3's output in the default mode) is described - and copied by sn_debug_tensor - as if a3c followed its own two planes.
+// "a3c" alone names that plane: one plane of 16-byte slots. Reads host fields only.
+SN_API int sn_debug_tensor_info(sn_ctx *c, const char *name, long long *out)
+{
+    if (!c || !name || !out) return fail(SN_ERR_ARG, "null argument");
+    DebugTensor d;
+    const int rc = debug_tensor_find(c, name, d);
+    if (rc != SN_OK) return rc;
+    const TensorSpec &t = c->plan.tens[d.tid];
+    const long long plane = (long long)c->max_samples * ((long long)c->s * c->s * c->s >> (3 * t.level)) * t.ch, npl = c->split ? 2 : 1;
+    const bool lo = d.fmt == 1 || d.fmt == 4, code = d.fmt >= 2;
+    out[0] = c->s >> t.level; out[1] = t.ch;
+    out[2] = d.a3c ? 1 : 1 + (lo ? 1 : 0) + (code ? 1 : 0);
+    out[3] = (lo && !d.a3c) ? plane : -1;
+    out[4] = d.a3c ? 0 : (code ? (d.fmt == 4 ? npl * plane : plane) : -1);
+    out[5] = mx_e8(c, t.e8);
+    out[6] = 2 * (d.a3c ? plane : npl * plane + (d.fmt == 4 ? plane : 0));
+    out[7] = d.fmt;
+    return SN_OK;
+}
+
+// Test hook (not part of the ABI header): raw copy of the first `bytes` bytes of an internal activation buffer (every plane, layout of
+// DESIGN.md section 3 and sn_debug_tensor_info) for comparing what the device stores with oracle/net_oracle.py and oracle/net_emulation.py.
 SN_API int sn_debug_tensor(sn_ctx *c, const char *name, void *host, size_t bytes)
 {
     if (!c || !name || !host) return fail(SN_ERR_ARG, "null argument");
-    const _Float16 *p = !strcmp(name, "cat") ? c->cat : (!strcmp(name, "ma") ? c->ma : nullptr);
-    if (!p) return fail(SN_ERR_ARG, "unknown tensor %s", name);
+    DebugTensor d;
+    long long info[8];
+    int rc = debug_tensor_find(c, name, d);
+    if (rc == SN_OK) rc = sn_debug_tensor_info(c, name, info);
+    if (rc != SN_OK) return rc;
+    if (!c->ws_ready || c->ws_split != c->split) return fail(SN_ERR_STATE, "sn_debug_tensor: the activation workspace is not that of the current precision mode (sn_load_weights first)");
+    if (bytes > (size_t)info[6]) return fail(SN_ERR_ARG, "sn_debug_tensor: %s holds %lld bytes, %zu asked for", name, info[6], bytes);
+    const _Float16 *p = d.a3c ? c->a3c : c->*kTensors[d.buf].buf;
+    const size_t own = d.a3c || d.fmt != 4 ? bytes : std::min(bytes, (size_t)info[4] * 2);      // (format 4: the code plane is a buffer of its own)
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(host, p, own, hipMemcpyDeviceToHost));
+    if (bytes > own) HIPCHK(hipMemcpy(static_cast<char *>(host) + own, c->a3c, bytes - own, hipMemcpyDeviceToHost));
     return SN_OK;
 }
 

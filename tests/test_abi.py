@@ -36,7 +36,16 @@ def test_header_binding_and_library_agree(built):
     dbg = os.path.join(os.path.dirname(built.LIB_PATH), "libsurfacenet_hip_dbg.so")       # the test-only twin: the same ABI + the hooks
     out = subprocess.check_output(["nm", "-D", "--defined-only", dbg]).decode()
     exported = sorted(line.split()[-1] for line in out.splitlines() if line.strip())
-    assert set(hdr) <= set(exported) and set(exported) - set(hdr) == {"sn_debug_tensor", "sn_debug_mx6_encode", "sn_debug_timing", "sn_debug_trace", "sn_debug_pack_host", "sn_debug_plan"}
+    assert set(hdr) <= set(exported) and set(exported) - set(hdr) == {"sn_debug_tensor", "sn_debug_tensor_info", "sn_debug_mx6_encode", "sn_debug_timing", "sn_debug_trace", "sn_debug_pack_host", "sn_debug_plan"}
+
+
+@pytest.mark.parametrize("s", [36, 68])
+def test_create_refuses_a_one_voxel_partial_tile_under_the_dilated_layers(built, s):
+    """cube_D / 4 = 9, 17: extent mod 8 = 1 < R = 2, which the halo addressing of conv4_x does not cover (ConvKernel::launch, edge_only);
+    sn_create says so before it looks for a device."""
+    import surfacenet_amd
+    with pytest.raises(surfacenet_amd.SurfaceNetHipError, match="1-voxel partial tile"):
+        surfacenet_amd.Context(cube_D=s, max_samples=1)
 
 
 def test_version_and_no_gpu_fails_loudly(built):

@@ -236,9 +236,10 @@ def test_relative_weight_mlp_vs_oracle(sn):
             ctx.relative_weights(f, 5)
 
 
-@pytest.mark.parametrize("s", [12, 20])
+@pytest.mark.parametrize("s", [12, 20, 24, 28, 40, 44])
 def test_forward_ragged_cube_sizes(sn, s):
-    """Cube sizes that are not multiples of the 8x8x8 tile (partial tiles, odd pooled extents 6/3 and 10/5)."""
+    """Cube sizes that are not multiples of the 8x8x8 tile (partial tiles, odd pooled extents 6/3 and 10/5); 24, 28, 40, 44: quarter-resolution
+    extents 6, 7, 10 (= 8 + the dilated layers' halo radius 2) and 11, i.e. partial tiles above 8 under conv4_x."""
     from oracle import net_oracle
     values, X, w = _net_case(s, 2, 2, seed=3 + s)
     with sn.Context(cube_D=s, max_samples=4) as ctx:
