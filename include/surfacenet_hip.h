@@ -27,7 +27,8 @@ extern "C" {
 #define SN_ABI_VERSION 2   /* 2 (round 6): + sn_mfma_probe, sn_set_conv4_fp8; sn_calibrate_dev refuses the all-MX mode with SN_ERR_STATE (since round 5) */
 /* Added since, without a version change (additions only): sn_ptcubes, sn_ptcubes_dev, sn_ptcubes_sparse_dev and sn_ptcubes_cfg - the
  * point-seeded cube list; sn_normals, sn_normals_dev, sn_unique_voxels, sn_unique_voxels_dev and sn_normals_cfg - oriented normals and
- * de-duplication of the output cloud. */
+ * de-duplication of the output cloud; sn_gt_bind, sn_gt_bind_dev, sn_gt_cubes, sn_gt_cubes_dev, sn_weighted_accuracy and
+ * sn_weighted_accuracy_dev - the ground-truth mode. */
 
 /* The library is built with -fvisibility=hidden: the functions below are its WHOLE dynamic symbol table
  * (tests/test_abi.py compares `nm -D` with this header). */
@@ -319,6 +320,30 @@ SN_API int sn_ptcubes_dev(sn_ctx *ctx, long long n, const void *pts_dev, const s
 SN_API int sn_ptcubes_sparse_dev(sn_ctx *ctx, int n_cubes, long long total, const int64_t *offsets_dev, const unsigned char *vxl_ijk_dev,
                                  const unsigned char *mask_dev, const float *cube_xyz_dev, const float *cube_resol_dev, const sn_ptcubes_cfg *cfg,
                                  long long cap, uint32_t *ijk_dev, float *xyz_dev, long long *n_cells);
+
+/* ---- ground-truth mode (__SurfaceNet_fn_inference__(with_groundTruth=True), nets/SurfaceNet.py:359-378; the val_fn of SurfaceNet_fn_trainVal,
+ * nets/SurfaceNet.py:253-264; __weighted_accuracy__, nets/SurfaceNet.py:203-224) -----------------------------------------
+ * The target tensor Y of those functions from a ground-truth point cloud, and the counts their accuracy is formed from.
+ * sn_gt_bind: binds n float32 points (n,3) to the context, sorted into a uniform grid of edge `cell` > 0 (a quarter of a cube's side is a good
+ *   choice; it decides speed only). Rebinding replaces the cloud; n = 0 is legal (every Y is then zero). SN_ERR_ARG for a non-finite coordinate and
+ *   for a cloud spanning 2^21 or more cells on an axis; a failed bind leaves no cloud bound. n <= 2^27. Needs no weights, images or cameras.
+ *   Both forms return when the cloud is sorted (the caller's array is not read afterwards).
+ * sn_gt_cubes: Y (n,1,s,s,s) float32 for n cubes (xyz (n,3), resol (n) float32; s = cube_D): with q = floor((p - xyz_c) / resol_c) per axis in
+ *   float32 - one subtraction, one correctly rounded division - Y[c,0,q0,q1,q2] = 1 iff some bound point has 0 <= q < s on all three axes (q = -0
+ *   counts as 0), every other voxel 0. Independent of the order of the points and of `cell`. SN_ERR_STATE when no cloud is bound; SN_ERR_ARG for a
+ *   non-finite xyz and for a resol that is not finite and > 0: the host form checks before it starts, the device form - asynchronous on the
+ *   context's stream - leaves such a cube's Y zero and reports at the next sn_synchronize.
+ * sn_weighted_accuracy: counts (n,4) int64 = per cube n_pos, n_neg, hit_pos, hit_neg of pred and Y (both (n,1,s,s,s) float32): positive is Y > 0,
+ *   negative Y == 0 (a negative or NaN target is neither), a hit is float(pred >= threshold) == Y (lasagne's binary_accuracy: ge; a NaN prediction
+ *   compares false). Integer arithmetic: exact. n <= 65535. The reference's accuracy of the whole batch tensor follows from the column sums
+ *   S in float64: acc_neg = S[3] / S[1], acc_pos = S[2] / S[0] (acc_neg when S[0] = 0, the reference's ifelse), (acc_pos + acc_neg) / 2. The device
+ *   form is asynchronous on the context's stream. */
+SN_API int sn_gt_bind(sn_ctx *ctx, long long n, const float *pts, double cell);
+SN_API int sn_gt_bind_dev(sn_ctx *ctx, long long n, const float *pts_dev, double cell);
+SN_API int sn_gt_cubes(sn_ctx *ctx, int n, const float *xyz, const float *resol, float *Y);
+SN_API int sn_gt_cubes_dev(sn_ctx *ctx, int n, const float *xyz_dev, const float *resol_dev, float *Y_dev);
+SN_API int sn_weighted_accuracy(sn_ctx *ctx, int n, const float *pred, const float *Y, float threshold, int64_t *counts);
+SN_API int sn_weighted_accuracy_dev(sn_ctx *ctx, int n, const float *pred_dev, const float *Y_dev, float threshold, int64_t *counts_dev);
 
 /* ---- similarityNet / early rejection (main_reconstruct.py:76-97) ---------------- */
 /* pickle.load + set_all_param_values([embedding layer, similarity layer]) of similarityNet_inference

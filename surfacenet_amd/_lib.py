@@ -23,6 +23,7 @@ ABI_SYMBOLS = [
     "sn_normals", "sn_normals_dev", "sn_unique_voxels", "sn_unique_voxels_dev",
     "sn_point_reduce", "sn_nn_dist2", "sn_point_flags",
     "sn_ptcubes", "sn_ptcubes_dev", "sn_ptcubes_sparse_dev",
+    "sn_gt_bind", "sn_gt_bind_dev", "sn_gt_cubes", "sn_gt_cubes_dev", "sn_weighted_accuracy", "sn_weighted_accuracy_dev",
     "sn_simil_load_weights", "sn_crop_patches", "sn_patch2embedding", "sn_crop_embed", "sn_embeddingpair2simil", "sn_embeddings2simil",
     "sn_project_points",
     "sn_comm_unique_id", "sn_comm_init", "sn_comm_init_deadline", "sn_comm_info", "sn_allgather_f32_dev", "sn_allgather_f32_dev_overlap", "sn_comm_wait", "sn_allgatherv_counts", "sn_allgatherv_bytes_dev",
@@ -131,6 +132,12 @@ def load():
         "sn_ptcubes_dev": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, P(PtCubesCfg), ctypes.c_longlong, c_void_p, c_void_p, P(ctypes.c_longlong)]),
         "sn_ptcubes_sparse_dev": (c_int, [c_void_p, c_int, ctypes.c_longlong] + [c_void_p] * 5 + [P(PtCubesCfg), ctypes.c_longlong, c_void_p, c_void_p,
                                           P(ctypes.c_longlong)]),
+        "sn_gt_bind": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_double]),
+        "sn_gt_bind_dev": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_double]),
+        "sn_gt_cubes": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+        "sn_gt_cubes_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+        "sn_weighted_accuracy": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_float, c_void_p]),
+        "sn_weighted_accuracy_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_float, c_void_p]),
         "sn_simil_load_weights": (c_int, [c_void_p, c_void_p, c_size_t, P(ParamDesc), c_int]),
         "sn_crop_patches": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
         "sn_patch2embedding": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),

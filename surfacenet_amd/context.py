@@ -609,6 +609,126 @@ class Context(object):
             for d in dev:
                 self.dev_free(d)
 
+    # ---- ground-truth mode (surfacenet_amd/groundTruth.py) -------------------------
+    def gt_bind(self, pts_xyz, cell):
+        """Binds a ground-truth cloud (sn_gt_bind): pts_xyz (n,3), converted with np.asarray(pts, np.float32); cell > 0 the edge of the grid the
+        points are sorted into (speed only). Rebinding replaces the cloud. Returns the number of points."""
+        p = np.ascontiguousarray(np.asarray(pts_xyz, np.float32).reshape(-1, 3))
+        self._gt_serial = getattr(self, "_gt_serial", 0) + 1
+        _lib.check(self._lib.sn_gt_bind(self._h, p.shape[0], _lib.ptr(p), float(cell)))
+        return p.shape[0]
+
+    def gt_bind_dev(self, n, pts_dev, cell):
+        """gt_bind for n float32 points already in HBM (sn_gt_bind_dev)."""
+        self._gt_serial = getattr(self, "_gt_serial", 0) + 1
+        _lib.check(self._lib.sn_gt_bind_dev(self._h, int(n), pts_dev, float(cell)))
+
+    def bind_points(self, pts_xyz, cube_D_mm):
+        """groundTruth.bind_points in this context: the grid cell is a quarter of the cube side. Returns the bound cloud (groundTruth.BoundCloud)."""
+        from . import groundTruth
+        return groundTruth.BoundCloud(self, pts_xyz, cube_D_mm)
+
+    @staticmethod
+    def _cube_params(cubes):
+        """cubes_param_np (a structured array with 'xyz' and 'resol') or a pair (xyz (n,3), resol (n,) or scalar) -> float32 (n,3), (n,)."""
+        if isinstance(cubes, np.ndarray) and cubes.dtype.names:
+            xyz, resol = cubes["xyz"], cubes["resol"]
+        else:
+            xyz, resol = cubes
+        xyz = np.ascontiguousarray(np.asarray(xyz, np.float32).reshape(-1, 3))
+        resol = np.ascontiguousarray(np.broadcast_to(np.asarray(resol, np.float32).reshape(-1), (xyz.shape[0],)))
+        return xyz, resol
+
+    def gt_cubes(self, cubes):
+        """The occupancy tensors of cubes (cubes_param_np or (xyz, resol)) from the bound cloud (sn_gt_cubes): Y (n,1,s,s,s) float32,
+        Y[c,0,q] = 1 iff some point has floor((p - xyz_c) / resol_c) == q in float32."""
+        xyz, resol = self._cube_params(cubes)
+        s, n = self.cube_D, xyz.shape[0]
+        Y = np.zeros((n, 1, s, s, s), np.float32)
+        _lib.check(self._lib.sn_gt_cubes(self._h, n, _lib.ptr(xyz), _lib.ptr(resol), _lib.ptr(Y)))
+        return Y
+
+    def gt_cubes_dev(self, n, xyz_dev, resol_dev, Y_dev):
+        _lib.check(self._lib.sn_gt_cubes_dev(self._h, int(n), xyz_dev, resol_dev, Y_dev))
+
+    def _check_target(self, Y, n, what="Y"):
+        s = self.cube_D
+        if not isinstance(Y, np.ndarray) or Y.dtype != np.float32 or Y.ndim != 5:
+            raise TypeError("%s must be a float32 5-D ndarray" % what)
+        if Y.shape != (n, 1, s, s, s):
+            raise TypeError("%s must have shape (%d, 1, %d, %d, %d), got %s" % (what, n, s, s, s, Y.shape))
+        return np.ascontiguousarray(Y)
+
+    def weighted_accuracy_counts(self, pred, Y, threshold=0.5):
+        """(n,4) int64: per cube n_pos, n_neg, hit_pos, hit_neg of pred against Y, both (n,1,s,s,s) float32 (sn_weighted_accuracy)."""
+        if not isinstance(pred, np.ndarray) or pred.ndim != 5:
+            raise TypeError("pred must be a float32 5-D ndarray")
+        pred = self._check_target(pred, pred.shape[0], "pred")
+        Y = self._check_target(Y, pred.shape[0])
+        counts = np.zeros((pred.shape[0], 4), np.int64)
+        _lib.check(self._lib.sn_weighted_accuracy(self._h, pred.shape[0], _lib.ptr(pred), _lib.ptr(Y), float(threshold), _lib.ptr(counts)))
+        return counts
+
+    def weighted_accuracy_dev(self, n, pred_dev, Y_dev, counts_dev, threshold=0.5):
+        _lib.check(self._lib.sn_weighted_accuracy_dev(self._h, int(n), pred_dev, Y_dev, float(threshold), counts_dev))
+
+    def weighted_accuracy(self, pred, Y, threshold=0.5, per_cube=False):
+        """groundTruth.weighted_accuracy in this context: np.float64 accuracy of the whole batch [, (n,4) per-cube counts]."""
+        from . import groundTruth
+        counts = self.weighted_accuracy_counts(pred, Y, threshold)
+        acc = groundTruth.accuracy_from_counts(counts)
+        return (acc, counts) if per_cube else acc
+
+    def forward_gt(self, X, w, Y, n_vp=1, threshold=0.5):
+        """`forward` in ground-truth mode: -> (fused, unfused, counts (n,4) int64). The counts are taken on the device from the fused tensor
+        before it is copied back (sn_forward_dev, sn_weighted_accuracy_dev); Y goes up, it never comes down. Same argument checks as `forward`."""
+        s = self.cube_D
+        if not isinstance(X, np.ndarray) or X.dtype != np.float32:
+            raise TypeError("X must be a float32 ndarray (the reference's Theano function rejects other dtypes)")
+        if X.ndim != 5 or X.shape[1:] != (6, s, s, s):
+            raise TypeError("X must have shape (N*n_vp, 6, %d, %d, %d), got %s" % (s, s, s, X.shape))
+        if X.shape[0] % n_vp:
+            raise ValueError("X.shape[0]=%d is not a multiple of n_vp=%d" % (X.shape[0], n_vp))
+        n = X.shape[0] // n_vp
+        X = np.ascontiguousarray(X)
+        if n_vp > 1:
+            if not isinstance(w, np.ndarray) or w.dtype != np.float32 or w.shape != (n, n_vp):
+                raise TypeError("w must be a float32 ndarray of shape (%d, %d)" % (n, n_vp))
+            w = np.ascontiguousarray(w)
+        else:
+            w = None
+        Y = self._check_target(Y, n)
+        if n_vp > self.max_samples:
+            raise ValueError("n_vp exceeds the context's max_samples")
+        fused = np.empty((n, 1, s, s, s), dtype=np.float32)
+        unfused = np.empty((n, n_vp, s, s, s), dtype=np.float32)
+        counts = np.zeros((n, 4), np.int64)
+        step = self.max_samples // n_vp                  # the chunks of sn_forward
+        m0, v = min(step, n), s ** 3
+        if n == 0:
+            return fused, unfused, counts
+        d = [self.dev_alloc(m0 * n_vp * 6 * v * 4), self.dev_alloc(m0 * n_vp * 4), self.dev_alloc(m0 * v * 4), self.dev_alloc(m0 * v * 4),
+             self.dev_alloc(m0 * n_vp * v * 4), self.dev_alloc(m0 * 32)]
+        dX, dw, dY, dF, dU, dC = d
+        try:
+            for i0 in range(0, n, step):
+                i1 = min(n, i0 + step)
+                m = i1 - i0
+                self.h2d(dX, X[i0 * n_vp:i1 * n_vp])
+                if w is not None:
+                    self.h2d(dw, w[i0:i1])
+                self.h2d(dY, Y[i0:i1])
+                _lib.check(self._lib.sn_forward_dev(self._h, m, n_vp, dX, dw if w is not None else None, dF, dU))
+                self.weighted_accuracy_dev(m, dF, dY, dC, threshold)
+                self.d2h(fused[i0:i1], dF)
+                self.d2h(unfused[i0:i1], dU)
+                self.d2h(counts[i0:i1], dC)
+                self.synchronize()
+        finally:
+            for p in d:
+                self.dev_free(p)
+        return fused, unfused, counts
+
     def dev_alloc(self, nbytes):
         p = self._lib.sn_dev_alloc(self._h, int(nbytes))
         if not p:

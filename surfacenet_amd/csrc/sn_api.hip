@@ -682,6 +682,8 @@ static int sync_check(sn_ctx *c)
             HIPCHK(hipMemset(c->d_err, 0, sizeof e));
             if (e == CC_ERR_INPUT_FLAG)
                 return fail(SN_ERR_ARG, "cross-cube post-pass: offsets table or voxel ijk out of range (the cubes concerned were skipped)");
+            if (e == GT_ERR_INPUT_FLAG)
+                return fail(SN_ERR_ARG, "sn_gt_cubes_dev: a cube's xyz or resol is not finite, or resol <= 0 (its Y was left all zero)");
             return fail(SN_ERR_ARG, "ray pooling: a projected pixel or depth bin fell outside the int32 range (cube on a camera plane?)");
         }
     }

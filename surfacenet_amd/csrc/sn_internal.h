@@ -1,6 +1,7 @@
 // sn_internal.h — shared by the translation units of libsurfacenet_hip.so (sn_api.hip: context, weights, hot path, RCCL, profiling;
 // sn_post.hip: ray pooling + dense2sparse; sn_simil.hip: similarityNet + patch cropping; sn_crosscube.hip: cross-cube denoising + adaptive
-// thresholding; sn_pointeval.hip: point-cloud evaluation; sn_ptcubes.hip: point-seeded cube list; sn_normals.hip: normals + de-duplication):
+// thresholding; sn_pointeval.hip: point-cloud evaluation; sn_ptcubes.hip: point-seeded cube list; sn_normals.hip: normals + de-duplication;
+// sn_gtcubes.hip: ground-truth occupancy cubes + weighted accuracy):
 // the context, owned device memory and the buffers that grow on demand (DevBuf), temporary device arrays with their host staging (TmpDev),
 // HIP-event profiling, packed conv layers, ConvKernel (one conv3d_f16_mfma instantiation as a type: its packing geometry and its launcher) and
 // the plan rows - which kernel runs which layer - that the weight packers and the forward passes walk. What needs no device (error text,
@@ -119,6 +120,7 @@ struct DevBuf {
 };
 
 constexpr int CC_ERR_INPUT_FLAG = 2;      // sn_ctx::d_err value of the cross-cube post-pass (crosscube.h CC_ERR_INPUT): bad offsets table / voxel ijk
+constexpr int GT_ERR_INPUT_FLAG = 3;      // ... of sn_gt_cubes_dev (gtcubes.h GT_ERR_INPUT): a cube's xyz / resol not finite or resol <= 0
 
 struct sn_ctx {
     int device = 0, s = 32, max_samples = 0;
@@ -174,9 +176,11 @@ struct sn_ctx {
     unsigned *d_num = nullptr;    // numeric status word: bit i = conv layer i of the launch order stored a non-finite / fp16-overflowing value
     std::vector<std::string> num_names;   // layer name of each status bit
     DevBuf rp_ws, d_counts;       // ray pooling's hash tables; dense2sparse's per-cube counts
-    int *d_err = nullptr;         // device error flag (err_flag): 1 ray pooling range, CC_ERR_INPUT_FLAG post-pass input
+    int *d_err = nullptr;         // device error flag (err_flag): 1 ray pooling range, CC_ERR_INPUT_FLAG post-pass input, GT_ERR_INPUT_FLAG GT cube parameters
     DevBuf pe_ws;                 // point-cloud evaluation workspace (sn_pointeval.hip)
     DevBuf nm_ws;                 // normals / unique-voxel workspace: staged arrays, brick or cell table (sn_normals.hip)
+    // the ground-truth cloud sn_gt_bind sorted into its grid (sn_gtcubes.hip gt_layout places the arrays in gt_ws from gt_n alone)
+    DevBuf gt_ws; bool gt_bound = false; long long gt_n = 0, gt_dim[3] = {0, 0, 0}; double gt_o[3] = {0, 0, 0}, gt_cell = 0;
     std::vector<void *> owned;
     // profiling
     bool prof_on = false;

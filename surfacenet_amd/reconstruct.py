@@ -2,7 +2,8 @@
 
 * `gen_non0Batch_npBool`   the reference's batch partition (utils/utils.py:77-110), same selectors
 * `hot_loop`               generator with the loop body's contract: per batch selector it yields
-                           (surfacePrediction, unfused_predictions, CVC + mean) exactly as lines 134-150 produce them
+                           (surfacePrediction, unfused_predictions, CVC + mean) exactly as lines 134-150 produce them; with `gt=` (a bound
+                           ground-truth cloud) also the per-cube counts of the reference's weighted accuracy, taken on the device
 * `infer_cubes`            the same work for a plain list of cubes, fused CVC->CNN->fusion per batch
 * `SparseLoop`             the WHOLE loop body (main_reconstruct.py:134-160: CVC -> CNN -> fusion -> voxel colours ->
                            ray pooling -> dense2sparse) device-resident: only cube parameters go up and only the packed
@@ -38,27 +39,111 @@ def gen_non0Batch_npBool(boolIndicators, batch_size):
     return np.array(out)
 
 
-def hot_loop(ctx, validCubes, viewPairs4Reconstr, w_viewPairs4Reconstr, cubes_param_np, batch_size, return_cvc=True, auto_calibrate=True):
+def hot_loop(ctx, validCubes, viewPairs4Reconstr, w_viewPairs4Reconstr, cubes_param_np, batch_size, return_cvc=True, auto_calibrate=True, gt=None):
     """main_reconstruct.py:132-150 for every batch: yields (_batch, surfacePrediction (n,1,s,s,s), unfused (n,N_vp,s,s,s),
     _CVCs2_sub + mean (n*N_vp,6,s,s,s) raw colours or None). `cubes_param_np` is the reference's structured array
     ('xyz' f32x3, 'resol' f32, ...; utils/scene.py:7-61).
     auto_calibrate (default on): the saturation warning of the default mode's 6-bit code planes is read after every batch; the first report
-    recalibrates the premultipliers on that batch, which is recomputed, with one RuntimeWarning (context.NumericsGuard)."""
+    recalibrates the premultipliers on that batch, which is recomputed, with one RuntimeWarning (context.NumericsGuard).
+    gt (default None: nothing changes): a ground-truth cloud bound to `ctx` (ctx.bind_points / groundTruth.bind_points). Every batch then also
+    yields, as a fifth item, its rows of the count table - (n,4) int64 n_pos, n_neg, hit_pos, hit_neg per cube (groundTruth.accuracy_from_counts
+    turns rows into the reference's accuracy; stacked over the batches they are the (N_cubes,4) table of the valid cubes). The target tensor is
+    voxelised on the device from the batch's xyz / resol (sn_gt_cubes_dev) and counted against the fused tensor there (sn_weighted_accuracy_dev):
+    neither crosses PCIe for it. A batch redone after a recalibration is recounted."""
     validCubes = np.asarray(validCubes).astype(bool)
     n_vp = viewPairs4Reconstr.shape[1]
     mean = MEAN_CVC_RGBRGB[None, :, None, None, None]
     guard = NumericsGuard(ctx, enabled=auto_calibrate)
-    for _batch in gen_non0Batch_npBool(validCubes, batch_size):
-        sel = _batch[validCubes]
-        w = None if n_vp == 1 else np.ascontiguousarray(w_viewPairs4Reconstr[sel], dtype=np.float32)
-        args = (viewPairs4Reconstr[sel], cubes_param_np["xyz"][_batch], cubes_param_np["resol"][_batch], w)
-        fused, unfused, cvc = ctx.cvc_forward(*args, return_unfused=True, return_cvc=return_cvc)
-        if guard.check("hot_loop") is not None:
-            fused, unfused, cvc = ctx.cvc_forward(*args, return_unfused=True, return_cvc=return_cvc)      # recalibrated on this batch: redo it
-            ctx.numeric_status()
-        if cvc is not None:
-            cvc += mean          # main_reconstruct.py:150
-        yield _batch, fused, (fused if n_vp == 1 else unfused), cvc
+    if gt is not None:
+        gt.check(ctx)
+        run = _GtBatches(ctx, n_vp)
+    try:
+        for _batch in gen_non0Batch_npBool(validCubes, batch_size):
+            sel = _batch[validCubes]
+            w = None if n_vp == 1 else np.ascontiguousarray(w_viewPairs4Reconstr[sel], dtype=np.float32)
+            args = (viewPairs4Reconstr[sel], cubes_param_np["xyz"][_batch], cubes_param_np["resol"][_batch], w)
+            if gt is None:
+                out = ctx.cvc_forward(*args, return_unfused=True, return_cvc=return_cvc)
+            else:
+                out = run(*args, return_cvc=return_cvc)
+            if guard.check("hot_loop") is not None:
+                # recalibrated on this batch: redo it
+                out = ctx.cvc_forward(*args, return_unfused=True, return_cvc=return_cvc) if gt is None else run(*args, return_cvc=return_cvc)
+                ctx.numeric_status()
+            fused, unfused, cvc = out[:3]
+            if cvc is not None:
+                cvc += mean          # main_reconstruct.py:150
+            if gt is None:
+                yield _batch, fused, (fused if n_vp == 1 else unfused), cvc
+            else:
+                yield _batch, fused, (fused if n_vp == 1 else unfused), cvc, out[3]
+    finally:
+        if gt is not None:
+            run.close()
+
+
+class _GtBatches(object):
+    """`Context.cvc_forward` in ground-truth mode for hot_loop: the same kernels on the same inputs (chunked by max_samples as sn_cvc_forward
+    chunks), with the batch's cube parameters and fused tensor kept in device buffers of its own, so that sn_gt_cubes_dev and
+    sn_weighted_accuracy_dev run on them where they are. Returns (fused, unfused, cvc | None, counts (n,4) int64)."""
+
+    def __init__(self, ctx, n_vp):
+        self.ctx, self.n_vp, self.d, self.cap = ctx, int(n_vp), {}, 0
+        if self.n_vp > ctx.max_samples:
+            raise ValueError("n_vp exceeds the context's max_samples")
+        self.step = ctx.max_samples // self.n_vp
+
+    def close(self):
+        for p in self.d.values():
+            self.ctx.dev_free(p)
+        self.d, self.cap = {}, 0
+
+    def _reserve(self, m, with_cvc):
+        if m > self.cap or (with_cvc and "cvc" not in self.d):
+            self.close()
+            A, S, v = self.ctx.dev_alloc, m * self.n_vp, self.ctx.cube_D ** 3
+            self.d = dict(pairs=A(S * 16), xyz=A(m * 12), resol=A(m * 4), w=A(S * 4), fused=A(m * v * 4), unfused=A(S * v * 4), Y=A(m * v * 4),
+                          counts=A(m * 32))
+            if with_cvc:
+                self.d["cvc"] = A(S * 6 * v * 4)
+            self.cap = m
+
+    def __call__(self, viewPairs, xyz, resol, w, return_cvc=True):
+        ctx, n_vp = self.ctx, self.n_vp
+        pairs, xyz, resol, n, _ = ctx._batch_args(viewPairs, xyz, resol)
+        if pairs.shape[1] != n_vp:
+            raise ValueError("viewPairs must have shape (n, %d, 2)" % n_vp)
+        s = ctx.cube_D
+        fused = np.empty((n, 1, s, s, s), np.float32)
+        unfused = np.empty((n, n_vp, s, s, s), np.float32)
+        cvc = np.empty((n * n_vp, 6, s, s, s), np.float32) if return_cvc else None
+        counts = np.zeros((n, 4), np.int64)
+        if n == 0:
+            return fused, unfused, cvc, counts
+        V = ctx.n_views
+        if pairs.max() >= V or pairs.min() < -V:
+            raise IndexError("view index out of range for %d views" % V)
+        pairs = np.where(pairs < 0, pairs + V, pairs)
+        if n_vp > 1:
+            if w is None:
+                raise TypeError("w (n, n_vp) float32 is required when a cube has more than one view pair")
+            w = np.ascontiguousarray(w, dtype=np.float32).reshape(n, n_vp)
+        self._reserve(min(self.step, n), return_cvc)
+        d = self.d
+        for i0 in range(0, n, self.step):
+            i1 = min(n, i0 + self.step)
+            m = i1 - i0
+            ctx.h2d(d["pairs"], pairs[i0:i1]); ctx.h2d(d["xyz"], xyz[i0:i1]); ctx.h2d(d["resol"], resol[i0:i1])
+            if n_vp > 1:
+                ctx.h2d(d["w"], w[i0:i1])
+            ctx.cvc_forward_dev(m, n_vp, d["pairs"], d["xyz"], d["resol"], d["w"] if n_vp > 1 else None, d["fused"], d["unfused"], d.get("cvc"))
+            ctx.gt_cubes_dev(m, d["xyz"], d["resol"], d["Y"])
+            ctx.weighted_accuracy_dev(m, d["fused"], d["Y"], d["counts"])
+            ctx.d2h(fused[i0:i1], d["fused"]); ctx.d2h(unfused[i0:i1], d["unfused"]); ctx.d2h(counts[i0:i1], d["counts"])
+            if cvc is not None:
+                ctx.d2h(cvc[i0 * n_vp:i1 * n_vp], d["cvc"])
+            ctx.synchronize()
+        return fused, unfused, cvc, counts
 
 
 def infer_cubes(ctx, viewPairs, xyz, resol, w=None, batch_size=None):
@@ -81,12 +166,16 @@ class SparseLoop(object):
     run(viewPairs (n,N_vp,2), xyz (n,3), resol (n,), w (n,N_vp)) returns what `sparseCubes.dense2sparse` returns for
     the batch: (nonempty_cube_indx, vxl_ijk_list, prediction_list, rgb_list, rayPooling_votes_list, xyz_new) with the
     keyword settings given at construction (defaults = the reference's call: min_prob params.__min_prob, rayPool_thresh 0,
-    centre crop on, ray pooling on). auto_calibrate (default on): the first batch whose stored activations exceed the range of the default mode's 6-bit
+    centre crop on, ray pooling on). gt (default None: nothing changes): a ground-truth cloud bound to `ctx` (ctx.bind_points); `run` and
+    `run_many` then return one more item, the (n,4) int64 count table n_pos, n_neg, hit_pos, hit_neg of the n cubes of the call - per batch the
+    target tensor is voxelised on the device from the cube parameters already there (sn_gt_cubes_dev) and counted against the fused tensor
+    (sn_weighted_accuracy_dev); only the 32 bytes per cube come down. auto_calibrate (default on): the first batch whose stored activations exceed the range of the default mode's 6-bit
     code planes recalibrates their premultipliers and is recomputed, with one RuntimeWarning (context.NumericsGuard)."""
 
     def __init__(self, ctx, n_vp, max_cubes=None, min_prob=0.5, rayPool_thresh=0, enable_centerCrop=True, cube_Dcenter=None,
-                 enable_rayPooling=True, mean=MEAN_CVC_RGBRGB, auto_calibrate=True):
+                 enable_rayPooling=True, mean=MEAN_CVC_RGBRGB, auto_calibrate=True, gt=None):
         self.ctx, self.n_vp = ctx, int(n_vp)
+        self.gt = None if gt is None else gt.check(ctx)
         self.guard = NumericsGuard(ctx, enabled=auto_calibrate)     # saturation of the 6-bit code planes: checked on the first batch, then once per call
         s = ctx.cube_D
         self.max_cubes = int(max_cubes or max(1, ctx.max_samples // self.n_vp))
@@ -103,7 +192,15 @@ class SparseLoop(object):
         self.d = dict(pairs=A(S * 16), xyz=A(N * 12), resol=A(N * 4), w=A(S * 4), fused=A(N * v * 4), unfused=A(S * v * 4),
                       cvc=A(S * 6 * v * 4), rgb=A(N * 3 * v), votes=A(N * v), offsets=A((N + 1) * 8), ijk=A(cap * 3), p16=A(cap * 2),
                       rgb_out=A(cap * 3), votes_out=A(cap))
+        if self.gt is not None:
+            self.d.update(Y=A(N * v * 4), counts=A(N * 32))
         self._off = np.zeros((N + 1,), dtype=np.int64)
+
+    def _count(self, m, xyz_dev, resol_dev, counts_dev):
+        """ground-truth mode: the batch's target tensor from its cube parameters, counted against the fused tensor, all in HBM"""
+        self.gt.check()
+        self.ctx.gt_cubes_dev(m, xyz_dev, resol_dev, self.d["Y"])
+        self.ctx.weighted_accuracy_dev(m, self.d["fused"], self.d["Y"], counts_dev)
 
     def close(self):
         for p in self.d.values():
@@ -120,7 +217,7 @@ class SparseLoop(object):
         resol = np.ascontiguousarray(resol, dtype=np.float32).reshape(n)
         xyz_new = xyz + (resol[:, None] * self.lo).astype(np.float32) if self.cfg["enable_centerCrop"] else xyz.copy()
         if n == 0:
-            return [], [], [], [], [], xyz_new
+            return ([], [], [], [], [], xyz_new) + (() if self.gt is None else (np.zeros((0, 4), np.int64),))
         V = ctx.n_views
         if pairs.max() >= V or pairs.min() < -V:
             raise IndexError("view index out of range for %d views" % V)
@@ -128,6 +225,8 @@ class SparseLoop(object):
         w = np.full((n, n_vp), 1.0 / n_vp, np.float32) if w is None else np.ascontiguousarray(w, dtype=np.float32).reshape(n, n_vp)
         ctx.h2d(d["pairs"], pairs); ctx.h2d(d["xyz"], xyz); ctx.h2d(d["resol"], resol); ctx.h2d(d["w"], w)
         ctx.cvc_forward_dev(n, n_vp, d["pairs"], d["xyz"], d["resol"], d["w"], d["fused"], d["unfused"], d["cvc"], mean=self.mean)
+        if self.gt is not None:
+            self._count(n, d["xyz"], d["resol"], d["counts"])
         ctx.color_fuse_dev(n, n_vp, d["cvc"], d["unfused"], d["w"], d["rgb"], mean=self.mean)      # main_reconstruct.py:150-152
         ctx.dense2sparse_dev(n, n_vp, d["pairs"], d["xyz"], d["resol"], d["fused"], d["rgb"], d["votes"], d["offsets"], d["ijk"], d["p16"],
                              d["rgb_out"], d["votes_out"], **self.cfg)                                 # :153-160
@@ -146,7 +245,12 @@ class SparseLoop(object):
                 ctx.d2h(votes, d["votes_out"])
         nonempty = [int(i) for i in np.nonzero(np.diff(off))[0]]
         cut = lambda a: [a[off[i]:off[i + 1]] for i in nonempty]
-        return nonempty, cut(ijk), cut(p16), cut(rgb), (cut(votes) if votes is not None else []), xyz_new
+        res = (nonempty, cut(ijk), cut(p16), cut(rgb), (cut(votes) if votes is not None else []), xyz_new)
+        if self.gt is not None:
+            counts = np.zeros((n, 4), np.int64)
+            ctx.d2h(counts, d["counts"])
+            res += (counts,)
+        return res
 
 
     def run_many(self, viewPairs, xyz, resol, w=None):
@@ -162,8 +266,9 @@ class SparseLoop(object):
         resol = np.ascontiguousarray(resol, dtype=np.float32).reshape(n)
         xyz_new = xyz + (resol[:, None] * self.lo).astype(np.float32) if self.cfg["enable_centerCrop"] else xyz.copy()
         out = ([], [], [], [], [], xyz_new)
+        counts = np.zeros((n, 4), np.int64) if self.gt is not None else None
         if n == 0:
-            return out
+            return out if counts is None else out + (counts,)
         V = ctx.n_views
         if pairs.max() >= V or pairs.min() < -V:
             raise IndexError("view index out of range for %d views" % V)
@@ -178,11 +283,14 @@ class SparseLoop(object):
         outs = [dict(offsets=d["offsets" + t], ijk=d["ijk" + t], p16=d["p16" + t], rgb_out=d["rgb_out" + t], votes_out=d["votes_out" + t])
                 for t in ("", "2", "3")]
         gp, gx, gr, gw = ctx.upload(pairs), ctx.upload(xyz), ctx.upload(resol), ctx.upload(w)
+        gc = ctx.dev_alloc(n * 32) if counts is not None else None       # the count table of the whole call: one copy at the end
         try:
             def enqueue(i0, o):
                 m = min(B, n - i0)
                 pp, px, pr, pw = gp + i0 * n_vp * 16, gx + i0 * 12, gr + i0 * 4, gw + i0 * n_vp * 4
                 ctx.cvc_forward_dev(m, n_vp, pp, px, pr, pw, d["fused"], d["unfused"], d["cvc"], mean=self.mean)
+                if gc is not None:
+                    self._count(m, px, pr, gc + i0 * 32)
                 ctx.color_fuse_dev(m, n_vp, d["cvc"], d["unfused"], pw, d["rgb"], mean=self.mean)
                 ctx.dense2sparse_dev(m, n_vp, pp, px, pr, d["fused"], d["rgb"], d["votes"], o["offsets"], o["ijk"], o["p16"], o["rgb_out"],
                                      o["votes_out"], **self.cfg)
@@ -223,14 +331,16 @@ class SparseLoop(object):
             for item in pending:
                 fetch(*item)
             ctx.synchronize()                    # surfaces the ray-pooling range error, if any
+            if gc is not None:
+                ctx.d2h(counts, gc)
             if self.guard.checks and self.guard.check("SparseLoop.run_many, later batches") is not None:
                 # a batch after the first saturated codes for the first time: the premultipliers are recalibrated (on the call's last batch) for what
                 # follows; this call's results stand - a saturated value loses its own correction term only
                 ctx.numeric_status()
         finally:
-            for p in (gp, gx, gr, gw):
+            for p in (gp, gx, gr, gw) + ((gc,) if gc is not None else ()):
                 ctx.dev_free(p)
-        return out
+        return out if counts is None else out + (counts,)
 
 
 def shard_bounds(n, world, rank):
