@@ -345,6 +345,42 @@ SN_API int sn_gt_cubes_dev(sn_ctx *ctx, int n, const float *xyz_dev, const float
 SN_API int sn_weighted_accuracy(sn_ctx *ctx, int n, const float *pred, const float *Y, float threshold, int64_t *counts);
 SN_API int sn_weighted_accuracy_dev(sn_ctx *ctx, int n, const float *pred_dev, const float *Y_dev, float threshold, int64_t *counts_dev);
 
+/* ---- training the view-pair weighting net with SurfaceNet frozen ("train the softmaxWeight with(out) finetuning the SurfaceNet",
+ * nets/SurfaceNet.py:266-294; the 258 -> 100 -> 1 MLP of __relativeWeight_net__, nets/SurfaceNet.py:84-100) ------------
+ * Trainable: feature_fc1.W / beta / gamma and feature_linear1.W / b; feature_fc1.mean / inv_std follow as running statistics. The 3-D network
+ * is not touched: a step takes its unfused predictions U (n, n_vp, s,s,s), the features F (n * n_vp, 258) and the target Y (n,1,s,s,s), all float32.
+ * Forward in training mode (batch statistics, biased variance, bn_eps), w = softmax over each cube's n_vp rows, f = sum_p w_p U_p,
+ * loss = mean of -(w_for_1 Y log f' + (1 - w_for_1)(1 - Y) log(1 - f')) with f' = clamp(f, clip, 1 - clip), + l2 (sum W1^2 + sum w2^2); backward in
+ * closed form; then the update. fp32 throughout, every sum in a fixed order: the same inputs give the same bits on every run.
+ * sn_relw_train_begin: starts a session from the loaded weights (master copies, zero velocities). update: 0 = gradients only (nothing changes),
+ *   1 = sgd (p -= lr g), 2 = Nesterov momentum as lasagne.updates.nesterov_momentum (t = lr g; v = momentum v - t; p = (p - t) + momentum v); with
+ *   1 and 2 the running statistics move by bn_alpha (mean = (1 - bn_alpha) mean + bn_alpha mu, inv_std alike). SN_ERR_STATE when only the 98
+ *   network arrays were loaded. Beginning again restarts from the weights as trained so far; sn_load_weights ends the session.
+ * sn_relw_train_step(_dev): one step on n cubes (1 <= n <= 65535) of 2 <= n_vp <= 16 pairs each. Optional results (null: not wanted): fused f
+ *   (n,1,s,s,s), weights w (n, n_vp), counts (n,4) int64 of f against Y as sn_weighted_accuracy (threshold 0.5), *loss (host). The device form is
+ *   asynchronous on the context's stream unless loss is given. After a step with update != 0, sn_relative_weights and sn_viewpair_weights use
+ *   the trained weights (running statistics). SN_ERR_STATE before sn_relw_train_begin, SN_ERR_ARG for a null argument or n / n_vp out of range.
+ * sn_relw_train_grads: the last step's gradients W1 (258,100) | beta | gamma | w2 (100 each) | b2 (1), then its batch statistics mu | istd
+ *   (100 each): 26301 floats. sn_relw_train_velocities: the velocities, laid out as the gradients (26101 floats). sn_relw_train_dw: the last
+ *   step's d loss / d w (n * n_vp floats). SN_ERR_STATE when no step has run.
+ * sn_relw_get_params: the seven arrays in weight-file order W1 | beta | gamma | mean | inv_std | w2 | b2 (26301 floats), from the session
+ *   when one is open, else as loaded or as the last session left them.
+ * sn_relw_train_end: closes the session; the trained weights stay in force for the inference entries. */
+typedef struct sn_relw_train_cfg {
+    float lr, momentum, w_for_1, l2, bn_alpha, bn_eps, clip;     /* the reference: 0.9, 0.96, 0, 0.1 (Lasagne alpha), 1e-4, 1e-7 */
+    int update;
+} sn_relw_train_cfg;
+SN_API int sn_relw_train_begin(sn_ctx *ctx, const sn_relw_train_cfg *cfg);
+SN_API int sn_relw_train_end(sn_ctx *ctx);
+SN_API int sn_relw_train_step(sn_ctx *ctx, int n, int n_vp, const float *unfused, const float *features, const float *Y, float *fused,
+                              float *weights, int64_t *counts, double *loss);
+SN_API int sn_relw_train_step_dev(sn_ctx *ctx, int n, int n_vp, const float *unfused_dev, const float *features_dev, const float *Y_dev,
+                                  float *fused_dev, float *weights_dev, int64_t *counts_dev, double *loss);
+SN_API int sn_relw_train_grads(sn_ctx *ctx, float *out);
+SN_API int sn_relw_train_velocities(sn_ctx *ctx, float *out);
+SN_API int sn_relw_train_dw(sn_ctx *ctx, float *out);
+SN_API int sn_relw_get_params(sn_ctx *ctx, float *out);
+
 /* ---- similarityNet / early rejection (main_reconstruct.py:76-97) ---------------- */
 /* pickle.load + set_all_param_values([embedding layer, similarity layer]) of similarityNet_inference
  * (nets/similarityNet.py:229-244): 30 arrays in order — 13 x (conv W (Cout,Cin,3,3), b (Cout,)) for conv1_1 .. conv5_3

@@ -104,7 +104,8 @@ def SurfaceNet_fn_trainVal(N_viewPairs4inference, default_lr=None, input_cube_si
                            CHANNEL_MEAN=None, return_train_fn=False, return_val_fn=True, with_weight=True, param_values=None, model_file=None,
                            auto_calibrate=True):
     """The validation half of the reference's SurfaceNet_fn_trainVal (nets/SurfaceNet.py:227-294): returns (None, None, val_fn) - the
-    reference returns (net, train_fn, val_fn); there is no Lasagne net here and no training (return_train_fn=True raises NotImplementedError).
+    reference returns (net, train_fn, val_fn); there is no Lasagne net here, and the train_fn is training.SurfaceNet_fn_train's (return_train_fn=True
+    raises NotImplementedError and says so).
         val_fn(X, similFeature, Y) -> [accuracy, fused]          (with_weight; nets/SurfaceNet.py:260-264)
         val_fn(X, Y)               -> [accuracy, fused]          (with_weight=False and one view pair)
     similFeature is the float32 (n*N_vp, 258) matrix of viewPair_relativeImpt_fn: the weights are relative_weights(similFeature), then the
@@ -113,7 +114,8 @@ def SurfaceNet_fn_trainVal(N_viewPairs4inference, default_lr=None, input_cube_si
     D_viewPairFeature, num_hidden_units and CHANNEL_MEAN are accepted for the reference's signature and not used (the weight file fixes the
     layer sizes; X comes mean-subtracted). Weights: param_values (list in weight-file order) or model_file."""
     if return_train_fn:
-        raise NotImplementedError("training is not part of this package: only the val_fn of SurfaceNet_fn_trainVal is built")
+        raise NotImplementedError("SurfaceNet_fn_trainVal builds the val_fn only; the view-pair weighting net is trained, with SurfaceNet frozen, by "
+                                  "training.SurfaceNet_fn_train")
     if not return_val_fn:
         return None, None, None
     N_vp = int(N_viewPairs4inference)

@@ -5,6 +5,7 @@ Only what the hot path needs:
   context.Context  one GPU's state over the C ABI (ctypes)
   CVC, SurfaceNet  drop-in mirrors of the reference's utils/CVC.py and nets/SurfaceNet.py entry points
   reconstruct      the cube-batch loop of main_reconstruct.py:126-166 + multi-GPU sharding
+  training         trains the view-pair weighting net on the GPU with SurfaceNet frozen (nets/SurfaceNet.py:266-294)
   weights          weight-file layout, loader for the reference pickle, synthetic weights
 """
 from .context import Context, MEAN_CVC_RGBRGB  # noqa: F401

@@ -24,6 +24,8 @@ ABI_SYMBOLS = [
     "sn_point_reduce", "sn_nn_dist2", "sn_point_flags",
     "sn_ptcubes", "sn_ptcubes_dev", "sn_ptcubes_sparse_dev",
     "sn_gt_bind", "sn_gt_bind_dev", "sn_gt_cubes", "sn_gt_cubes_dev", "sn_weighted_accuracy", "sn_weighted_accuracy_dev",
+    "sn_relw_train_begin", "sn_relw_train_end", "sn_relw_train_step", "sn_relw_train_step_dev", "sn_relw_train_grads", "sn_relw_train_velocities",
+    "sn_relw_train_dw", "sn_relw_get_params",
     "sn_simil_load_weights", "sn_crop_patches", "sn_patch2embedding", "sn_crop_embed", "sn_embeddingpair2simil", "sn_embeddings2simil",
     "sn_project_points",
     "sn_comm_unique_id", "sn_comm_init", "sn_comm_init_deadline", "sn_comm_info", "sn_allgather_f32_dev", "sn_allgather_f32_dev_overlap", "sn_comm_wait", "sn_allgatherv_counts", "sn_allgatherv_bytes_dev",
@@ -54,6 +56,11 @@ class NormalsCfg(ctypes.Structure):
 class PtCubesCfg(ctypes.Structure):
     _fields_ = [("pts_f64", ctypes.c_int), ("compute_f64", ctypes.c_int), ("stride_q", ctypes.c_double), ("stride_xyz", ctypes.c_double),
                 ("half", ctypes.c_double), ("has_box", ctypes.c_int), ("lo", ctypes.c_double * 3), ("hi", ctypes.c_double * 3)]
+
+
+class RelwTrainCfg(ctypes.Structure):
+    _fields_ = [("lr", ctypes.c_float), ("momentum", ctypes.c_float), ("w_for_1", ctypes.c_float), ("l2", ctypes.c_float),
+                ("bn_alpha", ctypes.c_float), ("bn_eps", ctypes.c_float), ("clip", ctypes.c_float), ("update", ctypes.c_int)]
 
 
 class Calibration(ctypes.Structure):
@@ -138,6 +145,14 @@ def load():
         "sn_gt_cubes_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
         "sn_weighted_accuracy": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_float, c_void_p]),
         "sn_weighted_accuracy_dev": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.c_float, c_void_p]),
+        "sn_relw_train_begin": (c_int, [c_void_p, P(RelwTrainCfg)]),
+        "sn_relw_train_end": (c_int, [c_void_p]),
+        "sn_relw_train_step": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 6 + [P(ctypes.c_double)]),
+        "sn_relw_train_step_dev": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 6 + [P(ctypes.c_double)]),
+        "sn_relw_train_grads": (c_int, [c_void_p, c_void_p]),
+        "sn_relw_train_velocities": (c_int, [c_void_p, c_void_p]),
+        "sn_relw_train_dw": (c_int, [c_void_p, c_void_p]),
+        "sn_relw_get_params": (c_int, [c_void_p, c_void_p]),
         "sn_simil_load_weights": (c_int, [c_void_p, c_void_p, c_size_t, P(ParamDesc), c_int]),
         "sn_crop_patches": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
         "sn_patch2embedding": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),

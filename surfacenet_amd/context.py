@@ -111,6 +111,37 @@ class NumericsGuard(object):
         return cal
 
 
+RELW_MAX_VP = 16            # relwtrain.h RT_MAX_VP
+
+
+def check_train_args(s, first, features, Y, n_vp, first_is_X):
+    """The dtype / ndim / shape rules of Context.forward_gt for the arguments of a training step on cubes of s^3 - (unfused | X, similFeature, Y) -
+    as TypeErrors, with no device call. -> n, the number of cubes."""
+    s, n_vp = int(s), int(n_vp)
+    if not 2 <= n_vp <= RELW_MAX_VP:
+        raise TypeError("training needs 2 <= n_vp <= %d view pairs per cube, got %d" % (RELW_MAX_VP, n_vp))
+    what = "X" if first_is_X else "unfused"
+    if not isinstance(first, np.ndarray) or first.dtype != np.float32 or first.ndim != 5:
+        raise TypeError("%s must be a float32 5-D ndarray" % what)
+    if first_is_X:
+        if first.shape[1:] != (6, s, s, s) or first.shape[0] % n_vp or first.shape[0] == 0:
+            raise TypeError("X must have shape (n*%d, 6, %d, %d, %d), got %s" % (n_vp, s, s, s, first.shape))
+        n = first.shape[0] // n_vp
+    else:
+        if first.shape[1:] != (n_vp, s, s, s) or first.shape[0] == 0:
+            raise TypeError("unfused must have shape (n, %d, %d, %d, %d), got %s" % (n_vp, s, s, s, first.shape))
+        n = first.shape[0]
+    if not isinstance(features, np.ndarray) or features.dtype != np.float32 or features.ndim != 2:
+        raise TypeError("similFeature must be a float32 matrix")
+    if features.shape != (n * n_vp, _weights.D_VIEWPAIR_FEATURE):
+        raise TypeError("similFeature must have shape (%d, %d), got %s" % (n * n_vp, _weights.D_VIEWPAIR_FEATURE, features.shape))
+    if not isinstance(Y, np.ndarray) or Y.dtype != np.float32 or Y.ndim != 5:
+        raise TypeError("Y must be a float32 5-D ndarray")
+    if Y.shape != (n, 1, s, s, s):
+        raise TypeError("Y must have shape (%d, 1, %d, %d, %d), got %s" % (n, s, s, s, Y.shape))
+    return n
+
+
 class Context(object):
     PRECISIONS = {"f16": 0, "f16x3": 1, "f16m8": 2, "f16x3p": 3}      # f16x3p: f16x3 without the MX tail (see surfacenet_hip.h)
 
@@ -728,6 +759,110 @@ class Context(object):
             for p in d:
                 self.dev_free(p)
         return fused, unfused, counts
+
+    # ---- training the view-pair weighting net, SurfaceNet frozen (training.py) ----------------------------------
+    RELW_UPDATES = {"none": 0, "sgd": 1, "nesterov_momentum": 2}
+    # offsets of sn_relw_train_grads / sn_relw_train_velocities (W1 | beta | gamma | w2 | b2 [| mu | istd]) and of sn_relw_get_params
+    _RELW_G = (("W1", 25800, (258, 100)), ("beta", 100, (100,)), ("gamma", 100, (100,)), ("w2", 100, (100,)), ("b2", 1, (1,)),
+               ("mu", 100, (100,)), ("istd", 100, (100,)))
+    _RELW_P = ((25800, (258, 100)), (100, (100,)), (100, (100,)), (100, (100,)), (100, (100,)), (100, (100, 1)), (1, (1,)))
+
+    def relw_train_begin(self, lr, momentum=0.9, update="nesterov_momentum", w_for_1=0.96, l2=0.0, bn_alpha=0.1, bn_eps=1e-4, clip=1e-7):
+        """Starts a training session from the loaded weights (sn_relw_train_begin). update: 'none' (gradients only), 'sgd', 'nesterov_momentum'."""
+        if update not in self.RELW_UPDATES:
+            raise ValueError("update must be one of %s" % sorted(self.RELW_UPDATES))
+        cfg = _lib.RelwTrainCfg(float(lr), float(momentum), float(w_for_1), float(l2), float(bn_alpha), float(bn_eps), float(clip),
+                                self.RELW_UPDATES[update])
+        _lib.check(self._lib.sn_relw_train_begin(self._h, ctypes.byref(cfg)))
+
+    def relw_train_end(self):
+        _lib.check(self._lib.sn_relw_train_end(self._h))
+
+    def _check_train_args(self, first, features, Y, n_vp, first_is_X):
+        return check_train_args(self.cube_D, first, features, Y, n_vp, first_is_X)
+
+    def relw_train_step(self, unfused, features, Y, n_vp):
+        """One step on cached predictions (sn_relw_train_step): unfused (n,n_vp,s,s,s), features (n*n_vp,258), Y (n,1,s,s,s), all float32.
+        -> (loss float, counts (n,4) int64, fused (n,1,s,s,s), w (n,n_vp))."""
+        n = self._check_train_args(unfused, features, Y, n_vp, False)
+        s = self.cube_D
+        U, F, Yc = np.ascontiguousarray(unfused), np.ascontiguousarray(features), np.ascontiguousarray(Y)
+        fused, w, counts = np.empty((n, 1, s, s, s), np.float32), np.empty((n, n_vp), np.float32), np.zeros((n, 4), np.int64)
+        loss = ctypes.c_double(0.0)
+        _lib.check(self._lib.sn_relw_train_step(self._h, n, int(n_vp), _lib.ptr(U), _lib.ptr(F), _lib.ptr(Yc), _lib.ptr(fused), _lib.ptr(w),
+                                                _lib.ptr(counts), ctypes.byref(loss)))
+        return loss.value, counts, fused, w
+
+    def relw_train_step_dev(self, n, n_vp, unfused_dev, features_dev, Y_dev, fused_dev=None, weights_dev=None, counts_dev=None, want_loss=False):
+        """sn_relw_train_step_dev on device arrays; asynchronous on the context's stream unless want_loss (then the loss is returned)."""
+        loss = ctypes.c_double(0.0)
+        _lib.check(self._lib.sn_relw_train_step_dev(self._h, int(n), int(n_vp), unfused_dev, features_dev, Y_dev, fused_dev, weights_dev, counts_dev,
+                                                    ctypes.byref(loss) if want_loss else None))
+        return loss.value if want_loss else None
+
+    def relw_train_fn(self, X, features, Y, n_vp):
+        """The same step from the colored cubes X (n*n_vp,6,s,s,s): the frozen SurfaceNet runs first (sn_forward_dev, BN folded, as in inference)
+        and its unfused predictions go to the step without leaving the device. The batch statistics span the whole batch, so it is one step:
+        n * n_vp <= max_samples. -> (loss, counts, fused, w) as relw_train_step."""
+        n = self._check_train_args(X, features, Y, n_vp, True)
+        s, S = self.cube_D, n * int(n_vp)
+        if S > self.max_samples:
+            raise ValueError("a training step is one batch: n * n_vp = %d exceeds the context's max_samples = %d" % (S, self.max_samples))
+        v = s ** 3
+        fused, w, counts = np.empty((n, 1, s, s, s), np.float32), np.empty((n, n_vp), np.float32), np.zeros((n, 4), np.int64)
+        d = [self.dev_alloc(S * 6 * v * 4), self.dev_alloc(S * v * 4), self.dev_alloc(S * v * 4), self.dev_alloc(S * _weights.D_VIEWPAIR_FEATURE * 4),
+             self.dev_alloc(n * v * 4), self.dev_alloc(S * 4), self.dev_alloc(n * 32)]
+        dX, dU, dF1, dF, dY, dW, dC = d
+        try:
+            self.h2d(dX, X)
+            self.h2d(dF, features)
+            self.h2d(dY, Y)
+            # the S samples as S one-pair cubes: the fused tensor of that call (dF1) is the unfused one again, and no weights are needed
+            _lib.check(self._lib.sn_forward_dev(self._h, S, 1, dX, None, dF1, dU))
+            loss = self.relw_train_step_dev(n, n_vp, dU, dF, dY, dF1, dW, dC, want_loss=True)
+            self.d2h(fused, dF1)
+            self.d2h(w, dW)
+            self.d2h(counts, dC)
+            self.synchronize()
+        finally:
+            for p in d:
+                self.dev_free(p)
+        return loss, counts, fused, w
+
+    def _relw_split(self, flat, names):
+        out, off = {}, 0
+        for name, size, shape in self._RELW_G:
+            if name in names:
+                out[name] = flat[off:off + size].reshape(shape).copy()
+                off += size
+        return out
+
+    def relw_train_grads(self):
+        """The last step's gradients {'W1','beta','gamma','w2','b2'} and its batch statistics {'mu','istd'} (sn_relw_train_grads)."""
+        flat = np.empty(26301, np.float32)
+        _lib.check(self._lib.sn_relw_train_grads(self._h, _lib.ptr(flat)))
+        return self._relw_split(flat, ("W1", "beta", "gamma", "w2", "b2", "mu", "istd"))
+
+    def relw_train_velocities(self):
+        flat = np.empty(26101, np.float32)
+        _lib.check(self._lib.sn_relw_train_velocities(self._h, _lib.ptr(flat)))
+        return self._relw_split(flat, ("W1", "beta", "gamma", "w2", "b2"))
+
+    def relw_train_dw(self, n, n_vp):
+        """d loss / d w of the last step, which ran on n cubes of n_vp pairs (sn_relw_train_dw)."""
+        out = np.empty((int(n), int(n_vp)), np.float32)
+        _lib.check(self._lib.sn_relw_train_dw(self._h, _lib.ptr(out)))
+        return out
+
+    def relw_get_params(self):
+        """The seven arrays of feature_fc1 / feature_linear1 in weight-file order (W, beta, gamma, mean, inv_std, W, b) as the device holds them."""
+        flat = np.empty(26301, np.float32)
+        _lib.check(self._lib.sn_relw_get_params(self._h, _lib.ptr(flat)))
+        out, off = [], 0
+        for size, shape in self._RELW_P:
+            out.append(flat[off:off + size].reshape(shape).copy())
+            off += size
+        return out
 
     def dev_alloc(self, nbytes):
         p = self._lib.sn_dev_alloc(self._h, int(nbytes))

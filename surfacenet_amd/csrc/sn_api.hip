@@ -872,6 +872,7 @@ int sn_load_weights(sn_ctx *c, const float *blob, size_t n_floats, const sn_para
     for (size_t i = 1; i < c->conv.size(); ++i)
         if (c->plan.conv[i].pool_tag && (rc = pack_side_frag(c, c->conv[i], c->conv[i - 1].nf)) != SN_OK) return rc;
     c->have_relw = false;
+    c->rt_on = false; c->relw_b2_stale = false;          // (a training session belongs to the weights it started from)
     if (n_params == kAllParams) {
         const sn_param_desc *d = descs + pi;
         if (!shape_is(d[0], {kDFeature, kHidden}) || !shape_is(d[5], {kHidden, 1}) || !shape_is(d[6], {1}))
@@ -880,15 +881,18 @@ int sn_load_weights(sn_ctx *c, const float *blob, size_t n_floats, const sn_para
         std::vector<float> sc(kHidden), sh(kHidden);
         const float *beta = blob + d[1].offset, *gamma = blob + d[2].offset, *mean = blob + d[3].offset, *inv_std = blob + d[4].offset;
         for (int j = 0; j < kHidden; ++j) { sc[j] = gamma[j] * inv_std[j]; sh[j] = beta[j] - mean[j] * sc[j]; }
-        if (c->relw_W1) { dev_free_owned(c, c->relw_W1); dev_free_owned(c, c->relw_scale); dev_free_owned(c, c->relw_shift); dev_free_owned(c, c->relw_w2); }
+        if (c->relw_W1) { dev_free_owned(c, c->relw_W1); dev_free_owned(c, c->relw_scale); dev_free_owned(c, c->relw_shift); dev_free_owned(c, c->relw_w2); dev_free_owned(c, c->relw_bn); }
         if ((rc = dev_alloc(c, &c->relw_W1, (size_t)kDFeature * kHidden)) != SN_OK) return rc;
         if ((rc = dev_alloc(c, &c->relw_scale, kHidden)) != SN_OK) return rc;
         if ((rc = dev_alloc(c, &c->relw_shift, kHidden)) != SN_OK) return rc;
         if ((rc = dev_alloc(c, &c->relw_w2, kHidden)) != SN_OK) return rc;
+        if ((rc = dev_alloc(c, &c->relw_bn, 4 * (size_t)kHidden)) != SN_OK) return rc;
         HIPCHK(hipMemcpy(c->relw_W1, blob + d[0].offset, sizeof(float) * kDFeature * kHidden, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(c->relw_scale, sc.data(), sizeof(float) * kHidden, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(c->relw_shift, sh.data(), sizeof(float) * kHidden, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(c->relw_w2, blob + d[5].offset, sizeof(float) * kHidden, hipMemcpyHostToDevice));
+        for (int j = 0; j < 4; ++j)                          // raw beta | gamma | mean | inv_std: what sn_relw_train_begin starts from
+            HIPCHK(hipMemcpy(c->relw_bn + j * kHidden, blob + d[1 + j].offset, sizeof(float) * kHidden, hipMemcpyHostToDevice));
         c->relw_b2 = blob[d[6].offset];
         c->have_relw = true;
     }
@@ -1106,6 +1110,7 @@ int sn_relative_weights(sn_ctx *c, int n, int n_vp, const float *features, float
     if (n == 0) return SN_OK;
     if (!c->have_relw) return fail(SN_ERR_STATE, "the relative-weight MLP arrays (params 98..104) were not loaded");
     HIPCHK(hipSetDevice(c->device));
+    { int rcb = relw_fresh_b2(c); if (rcb != SN_OK) return rcb; }
     const size_t rows = (size_t)n * n_vp;
     TmpDev t;      // freed on every return path
     float *d_f = t.up(c, features, rows * kDFeature), *d_z = t.out<float>(rows), *d_o = t.out<float>(rows);
@@ -1130,6 +1135,7 @@ int sn_viewpair_weights(sn_ctx *c, int n_cubes, int n_views, const float *embedd
     if (!c->have_relw) return fail(SN_ERR_STATE, "the relative-weight MLP arrays (params 98..104) were not loaded");
     if (kDFeature != 258 || kHidden > 128) return fail(SN_ERR_STATE, "unexpected MLP geometry");
     HIPCHK(hipSetDevice(c->device));
+    { int rcb = relw_fresh_b2(c); if (rcb != SN_OK) return rcb; }
     const int P = n_views * (n_views - 1) / 2;
     std::vector<int> pairs;
     for (int i = 0; i < n_views; ++i)

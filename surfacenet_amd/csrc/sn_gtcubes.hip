@@ -118,6 +118,9 @@ int gt_check_cubes(sn_ctx *c, int n, const float *xyz, const float *resol, const
     return SN_OK;
 }
 
+}  // namespace
+
+// (declared in sn_internal.h: sn_relwtrain.hip counts a training step's fused tensor with it)
 int gt_accuracy_device(sn_ctx *c, int n, const float *pred_dev, const float *Y_dev, float threshold, int64_t *counts_dev)
 {
     const size_t s3 = (size_t)c->s * c->s * c->s;
@@ -131,6 +134,8 @@ int gt_accuracy_device(sn_ctx *c, int n, const float *pred_dev, const float *Y_d
     HIPCHK(hipGetLastError());
     return SN_OK;
 }
+
+namespace {
 
 int gt_check_accuracy(sn_ctx *c, int n, const float *pred, const float *Y, const int64_t *counts)
 {

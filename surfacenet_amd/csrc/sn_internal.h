@@ -1,7 +1,7 @@
 // sn_internal.h — shared by the translation units of libsurfacenet_hip.so (sn_api.hip: context, weights, hot path, RCCL, profiling;
 // sn_post.hip: ray pooling + dense2sparse; sn_simil.hip: similarityNet + patch cropping; sn_crosscube.hip: cross-cube denoising + adaptive
 // thresholding; sn_pointeval.hip: point-cloud evaluation; sn_ptcubes.hip: point-seeded cube list; sn_normals.hip: normals + de-duplication;
-// sn_gtcubes.hip: ground-truth occupancy cubes + weighted accuracy):
+// sn_gtcubes.hip: ground-truth occupancy cubes + weighted accuracy; sn_relwtrain.hip: training of the view-pair weighting net):
 // the context, owned device memory and the buffers that grow on demand (DevBuf), temporary device arrays with their host staging (TmpDev),
 // HIP-event profiling, packed conv layers, ConvKernel (one conv3d_f16_mfma instantiation as a type: its packing geometry and its launcher) and
 // the plan rows - which kernel runs which layer - that the weight packers and the forward passes walk. What needs no device (error text,
@@ -153,6 +153,12 @@ struct sn_ctx {
     DevBuf comm_stage;                                               // sn_allgatherv_bytes_dev: padded payloads of all ranks
     unsigned char *comm_small = nullptr;                             // ... its 8-byte-per-rank exchanges (counts, status): allocated with the communicator
     float *relw_W1 = nullptr, *relw_scale = nullptr, *relw_shift = nullptr, *relw_w2 = nullptr; float relw_b2 = 0;
+    float *relw_bn = nullptr;     // feature_fc1's raw beta | gamma | mean | inv_std, [4][100]: what a training session starts from
+    // training of the view-pair weighting net (sn_relwtrain.hip): the session's master parameters | velocities | gradients, a step's workspace,
+    // the cubes and pairs of the last step (0: none). A step updates relw_W1 .. relw_bn on the stream; relw_b2 lives on the host, so it is
+    // fetched from relw_b2_dev the next time a synchronous entry needs it (relw_fresh_b2).
+    bool rt_on = false, relw_b2_stale = false; const float *relw_b2_dev = nullptr;
+    sn_relw_train_cfg rt_cfg = {}; DevBuf rt_par, rt_ws; int rt_n = 0, rt_nvp = 0;
     // activation workspace (channels-last fp16)
     _Float16 *x0 = nullptr, *a1 = nullptr, *b1 = nullptr, *cat = nullptr, *p1 = nullptr, *a2 = nullptr, *b2 = nullptr,
              *p2 = nullptr, *a3 = nullptr, *b3 = nullptr, *a4 = nullptr, *b4 = nullptr, *s2 = nullptr, *s3 = nullptr,
@@ -236,6 +242,16 @@ static int err_flag(sn_ctx *c)
     return SN_OK;
 }
 
+// relw_b2 as the last training step left it (a step does not wait for the device; the entries that pass b2 by value do).
+static int relw_fresh_b2(sn_ctx *c)
+{
+    if (!c->relw_b2_stale || !c->relw_b2_dev) return SN_OK;
+    HIPCHK(hipMemcpyAsync(&c->relw_b2, c->relw_b2_dev, sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->relw_b2_stale = false;
+    return SN_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // profiling: every launch goes through prof_begin / prof_end
 // ------------------------------------------------------------------------------------------------
@@ -290,6 +306,8 @@ static int prof_drain(sn_ctx *c)
 // Folds BN, packs the weights of one plan entry into MFMA fragment order, for the kernel the entry names (defined in sn_api.hip).
 int pack_conv(sn_ctx *c, PackedConv &L, const ConvEntry &e, const float *W, const float *beta, const float *gamma, const float *mean,
               const float *inv_std, const int *in_exp = nullptr, const int *out_exp = nullptr);
+// per-cube counts of __weighted_accuracy__ on the context's stream (defined in sn_gtcubes.hip; a training step counts its fused tensor with it)
+int gt_accuracy_device(sn_ctx *c, int n, const float *pred_dev, const float *Y_dev, float threshold, int64_t *counts_dev);
 std::vector<ConvEntry> simil_plan(int split);      // the similarityNet's plan for a context's operand mode (sn_ctx::split; defined in sn_simil.hip)
 
 static bool shape_is(const sn_param_desc &d, std::initializer_list<int> s)
