@@ -53,24 +53,111 @@ def _features(pools):
     return np.concatenate([pools[4].reshape(n, -1), crop(pools[0]), crop(pools[1]), crop(pools[2]), crop(pools[3])], axis=1)
 
 
-def embedding_torch(X, values, dtype="float64", return_pools=False):
+def _quantizer(torch, quant, td):
+    """Storage rounding of an arithmetic class: None exact; "fp16" one half; "x3" an unevaluated sum hi + lo of two halfs (the operand and
+    storage format of the device's f16x3 arithmetic)."""
+    def q(t):
+        if quant == "x3":
+            h = t.to(torch.float16).to(td)
+            return h + (t - h).to(torch.float16).to(td)
+        return t.to(torch.float16).to(td) if quant == "fp16" else t
+    return q
+
+
+def _layer(torch, F, values, i, x, ax, td, q, quant):
+    """Layer i on x: -> (y, A) AFTER ReLU and, for i in POOL_AFTER, the 2x2 max-pool; y not yet rounded for storage. The bias is added in
+    float32 where the class's epilogue is float32 (quant "fp16", dtype float32), as the device's is. ax: |x| (None: no error scale wanted)."""
+    W = q(torch.from_numpy(np.asarray(values[2 * i])).to(td))
+    b = np.asarray(values[2 * i + 1])
+    bt = torch.float32 if (quant == "fp16" or td == torch.float32) else td
+    y = F.conv2d(x, W, None, padding=1).to(bt) + torch.from_numpy(b).to(bt).view(1, -1, 1, 1)
+    y = torch.relu(y).to(td)
+    a = None
+    if ax is not None:
+        a = F.conv2d(ax, W.abs(), None, padding=1) + torch.from_numpy(np.abs(b)).to(td).view(1, -1, 1, 1)
+    if i in POOL_AFTER:
+        y = F.max_pool2d(y, 2)
+        a = F.max_pool2d(a, 2) if a is not None else None      # |max a - max b| <= max |a - b|
+    return y, a
+
+
+def embedding_torch(X, values, dtype="float64", return_pools=False, quant=None, return_intermediates=False):
+    """quant / dtype: the arithmetic class, as net_oracle.forward_torch / step_torch - None exact; "x3" weights, input and every stored
+    map as hi + lo pairs of halfs (use dtype float32: the class reference of the f16x3 arithmetic); "fp16" weights, input and stored maps as
+    halfs, wide accumulation, float32 bias (the class reference of the f16 mode). With a quant, feat and emb are evaluated in float32
+    from the class's stored pools (feat_step / emb_step); without one in float64, whatever the convolutions' dtype.
+    return_intermediates: -> (emb, inter), inter = {"p0": the input as stored, layer name: its post-ReLU (post-pool) map, "feat", "emb"}."""
     import torch
     import torch.nn.functional as F
     dt = getattr(torch, dtype)
-    x = torch.from_numpy(np.ascontiguousarray(X)).to(dt)
-    pools = []
+    q = _quantizer(torch, quant, dt)
+    x = q(torch.from_numpy(np.ascontiguousarray(X)).to(dt))
+    pools, inter = [], {"p0": x.to(torch.float64).numpy()}
     with torch.no_grad():
         for i in range(13):
-            W = torch.from_numpy(np.asarray(values[2 * i])).to(dt)
-            b = torch.from_numpy(np.asarray(values[2 * i + 1])).to(dt)
-            x = F.relu(F.conv2d(x, W, b, padding=1))
+            x = q(_layer(torch, F, values, i, x, None, dt, q, quant)[0])
+            inter[LAYER_NAMES[i]] = x.to(torch.float64).numpy()
             if i in POOL_AFTER:
-                x = F.max_pool2d(x, 2)
                 pools.append(x.numpy().copy())
-    f = _features(pools).astype(np.float64)
-    f = f / np.sqrt((f ** 2).sum(axis=1))[:, None]
-    emb = f @ np.asarray(values[26], dtype=np.float64) + np.asarray(values[27], dtype=np.float64)
-    return (emb, pools) if return_pools else emb
+    fd = "float64" if quant is None else "float32"
+    f = feat_step(pools, dtype=fd)
+    emb = emb_step(values, f, dtype=fd)
+    if not return_intermediates and not return_pools:
+        return emb
+    inter["feat"], inter["emb"] = np.asarray(f, dtype=np.float64), np.asarray(emb, dtype=np.float64)
+    return (emb, inter) if return_intermediates else (emb, pools)
+
+
+LAYER_NAMES = ["s_conv1_1", "s_conv1_2", "s_conv2_1", "s_conv2_2", "s_conv3_1", "s_conv3_2", "s_conv3_3", "s_conv4_1", "s_conv4_2", "s_conv4_3",
+               "s_conv5_1", "s_conv5_2", "s_conv5_3"]
+
+
+def step(values, i, x, dtype="float64", quant=None):
+    """One launch of the device's plan applied to a given input x (n, Cin, H, H), e.g. the device's own decoded stored tensor: layer i's
+    conv + bias + ReLU, + the 2x2 max-pool if i in POOL_AFTER, stored in the class's format (dtype / quant as embedding_torch; quant also
+    rounds the weights and the input). Returns (y, A): A, the forward-error scale of the element - the magnitude an error of relative
+    size eps in every product and in the bias can reach: |W| (*) |x| + |b| before ReLU (1-Lipschitz) and pooling; a pooled element takes the
+    maximum of A over its window."""
+    import torch
+    import torch.nn.functional as F
+    td = getattr(torch, dtype)
+    q = _quantizer(torch, quant, td)
+    with torch.no_grad():
+        xt = q(torch.from_numpy(np.ascontiguousarray(x)).to(td))
+        y, a = _layer(torch, F, values, i, xt, xt.abs(), td, q, quant)
+        return q(y).to(torch.float64).numpy(), a.to(torch.float64).numpy()
+
+
+def _seq_sum(a, dtype):
+    """Sum over the last axis; in float32 the textbook left-to-right sum (numpy's pairwise / BLAS's blocked orders are properties of a
+    library, not of the number format)."""
+    if dtype == "float64":
+        return a.sum(axis=-1)
+    return np.cumsum(a, axis=-1, dtype=np.float32)[..., -1]
+
+
+def feat_step(pools, dtype="float64"):
+    """pool1 .. pool5 (n, C, H, H) -> the (n, 5888) L2-normalised feature rows (gather of _features, x * (1 / sqrt(sum x^2)))."""
+    dt = np.dtype(dtype)
+    f = _features([np.asarray(p) for p in pools]).astype(dt)
+    inv = dt.type(1) / np.sqrt(_seq_sum(f * f, dtype))
+    return f * inv[:, None]
+
+
+def emb_step(values, feat, dtype="float64", with_scale=False):
+    """feat (n, 5888) -> emb (n, 128) = feat . W + b; with_scale: also A = |feat| . |W| + |b|."""
+    dt = np.dtype(dtype)
+    f, W, b = np.asarray(feat).astype(dt), np.asarray(values[26]).astype(dt), np.asarray(values[27]).astype(dt)
+    if dtype == "float64":
+        emb = f @ W + b
+    else:
+        acc = np.zeros((f.shape[0], W.shape[1]), dtype=dt)
+        for k in range(W.shape[0]):
+            acc += f[:, k, None] * W[k][None, :]
+        emb = acc + b
+    if with_scale:
+        return emb, np.abs(np.asarray(feat, dtype=np.float64)) @ np.abs(W.astype(np.float64)) + np.abs(b.astype(np.float64))
+    return emb
 
 
 def embedding_numpy(X, values):

@@ -177,6 +177,9 @@ struct sn_ctx {
     std::vector<float> simil_host;   // the 13 conv layers' fp32 parameters, kept to re-pack on a precision switch
     std::vector<sn_param_desc> simil_descs;
     DevBuf sws; int sws_n = 0, sws_split = -1;          // one chunk's tensors, re-made when the chunk capacity or the plane count changes
+    // the last run_simil on this workspace: patches (0: none yet, -1: the workspace was re-made since), the capacity and plane count it was
+    // carved for, where the embeddings went (sn_crop_embed: the call's own buffer). Host fields; read by the test-only sn_debug_simil_* hooks.
+    int sws_run_n = 0, sws_run_cap = 0, sws_run_npl = 0; const float *sws_run_emb = nullptr;
     DevBuf sview;                                       // sn_crop_embed: centres and embeddings of one whole call (no per-chunk host round trip)
     // post-pass (ray pooling / dense2sparse) workspace
     unsigned *d_num = nullptr;    // numeric status word: bit i = conv layer i of the launch order stored a non-finite / fp16-overflowing value

@@ -130,12 +130,24 @@ static int simil_workspace(sn_ctx *c, int n, SimilWs *w)
     const int cap = std::min(std::max(n, 8), kSimChunk), npl = simil_mode(c) ? 2 : 1;
     if (!c->sws.p || c->sws_n < cap || c->sws_split != npl) {
         c->sws.bytes = 0; c->sws_n = 0;      // re-made whenever a key changes, whatever its size: dev_reserve frees it and allocates
+        if (c->sws_run_n) c->sws_run_n = -1;      // (what the last run left is gone)
         int rc = dev_reserve(c, c->sws, simil_carve(nullptr, cap, npl, nullptr));
         if (rc != SN_OK) return rc;
         c->sws_n = cap; c->sws_split = npl;
     }
     simil_carve(c->sws.as<unsigned char>(), c->sws_n, npl, w);
     return SN_OK;
+}
+
+// The workspace tensor layer i of the plan writes; flip[st]: which of a block's two ping-pong buffers is next (run_simil walks the layers
+// in order with one flip state; the test-only read-back hook replays the same walk).
+static Act simil_out(const SimilWs &w, const std::vector<ConvEntry> &plan, int i, int (&flip)[5])
+{
+    const int st = kSimStage[i];
+    if (plan[i].k.epi == EPI_POOL2D) return w.pool[st];      // the block's last layer: conv + bias + ReLU + Pool2DLayer(2) in one kernel
+    const Act out = w.a[st][flip[st]];
+    flip[st] ^= 1;
+    return out;
 }
 
 static int run_simil(sn_ctx *c, const SimilWs &w, int n)
@@ -145,12 +157,11 @@ static int run_simil(sn_ctx *c, const SimilWs &w, int n)
     Act cur = w.p0;
     int cur_cs = 8;
     int flip[5] = {0, 0, 0, 0, 0};
+    c->sws_run_n = n; c->sws_run_cap = c->sws_n; c->sws_run_npl = c->sws_split; c->sws_run_emb = w.emb;
     for (int i = 0; i < 13; ++i) {
         const ConvEntry &e = c->splan[i];
-        const int st = kSimStage[i], H = kPatch >> st;
-        const bool pooled = e.k.epi == EPI_POOL2D;      // the block's last layer: conv + bias + ReLU + Pool2DLayer(2) in one kernel
-        const Act out = pooled ? w.pool[st] : w.a[st][flip[st]];
-        if (!pooled) flip[st] ^= 1;
+        const int H = kPatch >> kSimStage[i];
+        const Act out = simil_out(w, c->splan, i, flip);
         if ((rc = e.k.launch(c, c->sconv[i], cur, cur_cs, out, e.cout, 0, e.cout, nullptr, 1, H, n, nullptr)) != SN_OK) return rc;
         cur = out; cur_cs = e.cout;
     }
@@ -330,3 +341,83 @@ extern "C" int sn_embeddings2simil(sn_ctx *c, int n_cubes, int n_views, const fl
     HIPCHK(hipStreamSynchronize(c->stream));
     return SN_OK;
 }
+
+#ifdef SN_DEBUG_HOOKS     // test-only twin library (Makefile target dbg): not in the product .so, not in the ABI header
+// What the last run_simil left in the similarityNet workspace, by name: "p0" (the network input, 3 -> 8 channels), the 13 layer names of
+// kSimName (a block's last layer names its POOLED output: the unpooled map is never stored), "feat" (n x 5888 fp32), "emb" (n x 128 fp32).
+// A plane of a stored map is [C/8][n][H][H][8] halfs - the group stride is the RUN's n - and the lo plane (two-plane modes) sits at the
+// offset simil_carve computed from the workspace's CAPACITY. Which buffer a layer wrote comes from replaying run_simil's walk (simil_out).
+struct DebugSimil { const _Float16 *p = nullptr; const float *f = nullptr; long long lo = -1; int H = 0, C = 0, npl = 1, n = 0, cap = 0; };
+static int debug_simil_find(sn_ctx *c, const char *name, DebugSimil &d)
+{
+    if (c->sws_run_n == 0) return fail(SN_ERR_STATE, "sn_debug_simil: no similarityNet run on this context yet");
+    if (c->sws_run_n < 0 || !c->sws.p || c->sws_n != c->sws_run_cap || c->sws_split != c->sws_run_npl)
+        return fail(SN_ERR_STATE, "sn_debug_simil: the workspace was re-made (another mode or capacity) since the last similarityNet run");
+    if (c->splan.size() != 13) return fail(SN_ERR_STATE, "sn_debug_simil: no plan");
+    SimilWs w;
+    simil_carve(c->sws.as<unsigned char>(), c->sws_n, c->sws_split, &w);
+    d = DebugSimil();
+    d.n = c->sws_run_n; d.cap = c->sws_run_cap; d.npl = c->sws_run_npl;
+    if (!strcmp(name, "feat")) { d.f = w.feat; d.C = kSimilFeat; d.npl = 1; return SN_OK; }
+    if (!strcmp(name, "emb")) { d.f = c->sws_run_emb; d.C = kEmb; d.npl = 1; return SN_OK; }      // (sn_crop_embed: in the call's own buffer)
+    Act a{nullptr, 0};
+    if (!strcmp(name, "p0")) { a = w.p0; d.H = kPatch; d.C = 8; }
+    int flip[5] = {0, 0, 0, 0, 0};
+    for (int i = 0; i < 13; ++i) {
+        const Act out = simil_out(w, c->splan, i, flip);
+        if (strcmp(name, kSimName[i])) continue;
+        a = out; d.C = c->splan[i].cout;
+        d.H = (kPatch >> kSimStage[i]) >> (c->splan[i].k.epi == EPI_POOL2D ? 1 : 0);
+    }
+    if (!a.p) return fail(SN_ERR_ARG, "sn_debug_simil: unknown tensor %s", name);
+    // (a later layer of the block may have reused the buffer: the plan's flip walk never does - each block has at most 3 layers, the last one pooled -
+    // but say so instead of serving another layer's tensor)
+    int flip2[5] = {0, 0, 0, 0, 0};
+    bool seen = false;
+    for (int i = 0; i < 13; ++i) {
+        const Act out = simil_out(w, c->splan, i, flip2);
+        if (seen && out.p == a.p) return fail(SN_ERR_STATE, "sn_debug_simil: %s was overwritten by %s later in the pass", name, kSimName[i]);
+        if (!strcmp(name, kSimName[i])) seen = true;
+    }
+    d.p = a.p; d.lo = d.npl == 2 ? a.lo : -1;
+    return SN_OK;
+}
+
+// out = {map extent H (0 for feat / emb), channel stride (feat / emb: row length), planes (1 in f16, 2 = hi + lo otherwise), lo-plane offset
+// in halfs from the start (-1: none), n = patches of the last run, cap = patches the workspace was carved for, total bytes of the n patches as
+// sn_debug_simil_tensor packs them}. Host fields only.
+extern "C" SN_API int sn_debug_simil_info(sn_ctx *c, const char *name, long long *out)
+{
+    if (!c || !name || !out) return fail(SN_ERR_ARG, "null argument");
+    DebugSimil d;
+    const int rc = debug_simil_find(c, name, d);
+    if (rc != SN_OK) return rc;
+    out[0] = d.H; out[1] = d.C; out[2] = d.npl; out[3] = d.lo; out[4] = d.n; out[5] = d.cap;
+    out[6] = d.f ? (long long)d.n * d.C * 4 : (long long)d.npl * d.n * d.C * d.H * d.H * 2;
+    return SN_OK;
+}
+
+// Patches [first, first + count) of every channel group and plane, packed as [planes][C/8][count][H][H][8] halfs (feat / emb: count plain
+// fp32 rows); bytes must be exactly that.
+extern "C" SN_API int sn_debug_simil_tensor(sn_ctx *c, const char *name, int first, int count, void *host, size_t bytes)
+{
+    if (!c || !name || !host) return fail(SN_ERR_ARG, "null argument");
+    DebugSimil d;
+    const int rc = debug_simil_find(c, name, d);
+    if (rc != SN_OK) return rc;
+    if (first < 0 || count < 1 || (long long)first + count > d.n)
+        return fail(SN_ERR_ARG, "sn_debug_simil_tensor: patches [%d, %lld) are beyond the %d of the last run", first, (long long)first + count, d.n);
+    const size_t row = d.f ? (size_t)d.C * 4 : (size_t)d.H * d.H * 16;      // bytes of one patch: a row, or one channel group of one plane
+    const size_t want = d.f ? row * count : row * count * (d.C / 8) * d.npl;
+    if (bytes != want) return fail(SN_ERR_ARG, "sn_debug_simil_tensor: patches [%d, %d) of %s are %zu bytes, %zu asked for", first, first + count, name, want, bytes);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (d.f) { HIPCHK(hipMemcpy(host, d.f + (size_t)first * d.C, want, hipMemcpyDeviceToHost)); return SN_OK; }
+    for (int pl = 0; pl < d.npl; ++pl) {
+        const char *src = reinterpret_cast<const char *>(d.p + (pl ? d.lo : 0)) + row * first;
+        char *dst = static_cast<char *>(host) + (size_t)pl * row * count * (d.C / 8);
+        HIPCHK(hipMemcpy2D(dst, row * count, src, row * d.n, row * count, (size_t)(d.C / 8), hipMemcpyDeviceToHost));      // one row per channel group
+    }
+    return SN_OK;
+}
+#endif  // SN_DEBUG_HOOKS
