@@ -46,6 +46,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "mx_format.h"
+#include "sn_consts.h"     // kMaxSlab
 #include <stdint.h>
 #include <type_traits>
 
@@ -68,8 +69,6 @@ namespace sn {
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kMaxSlab = 128;
 
 struct ConvArgs {
     const _Float16 *in;   // [B][in_cs/8][D][D][D][8]  (hi plane; lo plane at +in_lo_off elements when SPLIT)

@@ -15,30 +15,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#ifndef SN_MX_FMT
-#define SN_MX_FMT 2
-#endif
-static_assert(SN_MX_FMT == 2 || SN_MX_FMT == 3, "SN_MX_FMT: 2 fp6 e2m3, 3 bf6 e3m2 (fp8 e4m3 is a per-kernel format since round 5: conv3d_mfma.h SPLIT 3)");
-constexpr int kMxLoExp = 11;
-constexpr float kMxLoMul = (float)(1 << kMxLoExp);
-// Static premultipliers 2^s of the code planes (fp6 forms), as E8M0 exponents 127 - s. Sized for what the tensors hold after the exact
-// power-of-two renormalisation of sn_load_weights: ReLU(BN(.)) outputs of O(1) ("act"), and the concat buffer of sigmoid side outputs in
-// (0, 1) ("cat"). A value above the format's range saturates and one far below it rounds to zero: either way only that element's
-// correction term degrades to plain fp16 accuracy.
-#ifndef SN_MX_S_ACT
-#define SN_MX_S_ACT 0
-#endif
-#ifndef SN_MX_S_CAT
-#define SN_MX_S_CAT 2
-#endif
-#ifndef SN_MX_S_C4
-#define SN_MX_S_C4 0        // the FP8 e4m3 code planes of the conv4 chain (conv3d_mfma.h SPLIT 3; conv3_3's, conv4_1's, conv4_2's outputs): codes of the values themselves -
-#endif                      // normal range 2^-6 .. 448. Measured on the device, s = -2 .. +1 are equivalent (worst L_inf 1.56e-4 .. 1.74e-4), s = 3: 2.3e-4, s = 4: 8.6e-4 -
-                            // scene cubes hold activations beyond 28, which is what the 6-bit codes of the merge layers could not represent here (profiles/r5/README.md)
-constexpr int kMxActE8 = 127 - SN_MX_S_ACT;
-constexpr int kMxC4E8 = 127 - (SN_MX_S_C4);
-constexpr int kMxCatE8 = 127 - SN_MX_S_CAT;
-constexpr int kMxX0E8 = 127 + 5;      // the network input (f16m8 mode only): mean-subtracted 8-bit colours, |x| < 256 -> 2^-5
+#include "sn_consts.h"      // SN_MX_FMT, kMxLoExp / kMxLoMul and the static premultipliers kMx*E8 (hip-free: the host packer reads them too)
 
 typedef int mx_v6i __attribute__((ext_vector_type(6)));
 typedef _Float16 mx_v32h __attribute__((ext_vector_type(32)));

@@ -3,9 +3,9 @@
 // thresholding; sn_pointeval.hip: point-cloud evaluation; sn_ptcubes.hip: point-seeded cube list; sn_normals.hip: normals + de-duplication;
 // sn_gtcubes.hip: ground-truth occupancy cubes + weighted accuracy; sn_relwtrain.hip: training of the view-pair weighting net):
 // the context, owned device memory and the buffers that grow on demand (DevBuf), temporary device arrays with their host staging (TmpDev),
-// HIP-event profiling, packed conv layers, ConvKernel (one conv3d_f16_mfma instantiation as a type: its packing geometry and its launcher) and
-// the plan rows - which kernel runs which layer - that the weight packers and the forward passes walk. What needs no device (error text,
-// table sizes, Carve, the packed-list checks) is in sn_host.h.
+// HIP-event profiling, ConvKernel (one conv3d_f16_mfma instantiation as a type: its packing geometry and its launcher) and
+// the plan rows - which kernel runs which layer - that the weight packers and the forward passes walk. What needs no device is in two hip-free
+// headers: sn_host.h (error text, table sizes, Carve, the packed-list checks) and sn_pack.h (PackedConv and the host half of weight packing).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "sn_host.h"
+#include "sn_pack.h"
 #include "conv3d_mfma.h"
 #include "cvc_warp.h"
 #include "elementwise.h"
@@ -35,25 +36,6 @@ using namespace sn;
         hipError_t e_ = (expr);                                                                            \
         if (e_ != hipSuccess) return fail(SN_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
-
-// A conv layer prepared for conv3d_f16_mfma: packed fp16 weight fragments + folded BN.
-struct PackedConv {
-    std::string name;
-    int cin = 0, cout = 0, ks = 1, dil = 1, act = 0;
-    int cin_p = 0;             // input channels padded to 8
-    int nf = 0, nsplit = 1;    // 16-channel fragments per workgroup, workgroup columns
-    int cs8max = 4, split = 0, k2d = 0;   // k2d: ks x ks taps over (y,z) only (2-D nets)
-    int bridge = 0;            // in: bridge chunks wanted; out of pack_conv: granted (sn_api.hip pack_conv_host, conv3d_mfma.h write_koff_part)
-    std::vector<unsigned char> slab_c8;
-    long long wsplit_stride = 0;   // halfs
-    _Float16 *wpack = nullptr;     // device
-    float *scale = nullptr, *shift = nullptr;  // device, nsplit*nf*16
-    double macs_per_voxel = 0;
-    // 1x1x1 layers only: the normalised weights (cout x cin, after pack_conv's power-of-two scalings) and, when the layer is fused into
-    // its producer's epilogue (EPI_SIDEPOOL), its A fragments in the producer's register order (device)
-    std::vector<float> w_norm;
-    _Float16 *side_frag = nullptr;
-};
 
 // ------------------------------------------------------------------------------------------------
 // kernel choice and layer plan

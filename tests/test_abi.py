@@ -88,7 +88,7 @@ def _dec6(code, fmt):
 
 @pytest.mark.parametrize("fmt", [2, 3])
 def test_host_mx6_encoder_matches_the_format(built, fmt):
-    """The weight packer's 6-bit encoder (sn_api.hip mx6_encode): exact on every representable value, round-to-nearest-even on the
+    """The weight packer's 6-bit encoder (sn_pack.h mx6_encode): exact on every representable value, round-to-nearest-even on the
     midpoints, saturating, monotone - the properties the device-side conversions have (fp6_probe) and the CPU model assumes."""
     import ctypes
     lib = ctypes.CDLL(os.path.join(os.path.dirname(built.LIB_PATH), "libsurfacenet_hip_dbg.so"))      # hooks live in the test-only twin
