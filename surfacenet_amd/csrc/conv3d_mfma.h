@@ -39,8 +39,12 @@
 //     stream in pieces of PCH K-chunks (double-buffered, continuous across slabs and tiles) and the halo tile
 //     of the NEXT (tile, slab) into the second halo buffer while the current one is being multiplied. Voxels
 //     outside the volume ('same' padding / PadLayer) are fetched from a zero page.
-//   * One barrier per weight piece; the K loop inside a piece is software-pipelined by hand (inline-asm
-//     ds_read_b128 with counted s_waitcnt: hipcc would sink every read to its first use and drain lgkmcnt(0)).
+//   * K loops: four, chosen per configuration in ONE expression, ConvCfg::LOOP (the layers on each: there; measurements: DESIGN.md 4.2):
+//       one wave per SIMD  LOOP_ONE_WAVE     4-wave workgroups, accumulators in AGPRs, every other instruction behind an MFMA of a burst, one barrier per piece
+//       ping-pong          LOOP_PINGPONG     f16 / f16x3, 8-wave workgroups: a segment (one K-chunk) is loaded, then computed as one burst; two wave groups alternate
+//       MX ping-pong       LOOP_PINGPONG_MX  the same for f16m8 on 8 waves: segments = f16 chunk 2p, f16 chunk 2p+1, the MX step
+//       hand-pipelined     LOOP_PIPELINED    one barrier per weight piece; inside a piece software-pipelined by hand (inline-asm ds_read_b128 with counted
+//                                            s_waitcnt: hipcc would sink every read to its first use and drain lgkmcnt(0))
 //   * Workgroup = NW waves = (NW*XS) x 8 x 8 output voxels x (NF*16) output channels; wave w owns x-slices
 //     [w*XS, (w+1)*XS) and all NF channel fragments, so the 1x1x1 reduction of merge_conv3 stays inside a wave.
 #pragma once
@@ -146,6 +150,17 @@ __device__ __forceinline__ void sn_split(float y, _Float16 &hi, _Float16 &lo)
 {
     hi = (_Float16)y;
     lo = (_Float16)(y - (float)hi);
+}
+// The parts of a value that a store epilogue writes: hi = rn(y), and the rest either as a second fp16 (LO16: lo = rn(y - hi), sn_split) or in fp32,
+// pre-scaled for a code plane (lo32 = (y - hi) * mul)
+template <bool LO16>
+__device__ __forceinline__ void sn_parts(float y, float mul, _Float16 &hi, _Float16 &lo, float &lo32)
+{
+    if constexpr (LO16) sn_split(y, hi, lo);
+    else {
+        hi = (_Float16)y;
+        lo32 = (y - (float)hi) * mul;
+    }
 }
 
 // ---- inline-asm LDS reads with counted waits --------------------------------------------------------------------
@@ -256,6 +271,17 @@ __device__ __forceinline__ void pw_mfma_mx6(f32x4 &c, const mx_v6i &a, const mx_
     else asm volatile(SN_MX6_ASM("op_sel:[1,0,0] op_sel_hi:[1,0,0]") : "+a"(c) : "v"(a), "v"(b), "v"(sa), "v"(sb));
 #undef SN_MX6_ASM
 }
+// A lane's 192-bit weight operand of that step from its two LDS reads: dwords 0..3 (128-bit read) and 4..5 (64-bit read). OP: mx_v6i for the inline-asm MFMA
+// above, v8i (two registers more, contents irrelevant) for the builtin
+template <typename OP>
+__device__ __forceinline__ OP sn_mx6_weight(const v4i &a4, long long b2)
+{
+    typedef int v2i_ __attribute__((ext_vector_type(2)));
+    const v2i_ b = __builtin_bit_cast(v2i_, b2);
+    const v4i b4 = __builtin_shufflevector(b, b, 0, 1, -1, -1);
+    if constexpr (std::is_same_v<OP, mx_v6i>) return __builtin_shufflevector(a4, b4, 0, 1, 2, 3, 4, 5);
+    else return __builtin_shufflevector(a4, b4, 0, 1, 2, 3, 4, 5, -1, -1);
+}
 // The same on fp8 e4m3 operands (256 bits per lane); sa, sb: E8M0 scales of the weight / activation side in byte 0
 __device__ __forceinline__ void pw_mfma_mx8(f32x4 &c, const v8i &a, const v8i &b, int sa, int sb)
 {
@@ -265,6 +291,9 @@ __device__ __forceinline__ void pw_mfma_mx8(f32x4 &c, const v8i &a, const v8i &b
 // the tile at hand stays in the offset and pushes it out of the descriptor's range.
 constexpr unsigned HB_ALWAYS = 1u << 31, HB_XLO = 1u << 30, HB_XHI = 1u << 29, HB_YLO = 1u << 28, HB_YHI = 1u << 27, HB_ZLO = 1u << 26,
                    HB_ZHI = 1u << 25, HB_OFFMASK = (1u << 25) - 1;
+
+// The four K loops of conv3d_f16_mfma (file header: "K loops"); ConvCfg::LOOP says which one a configuration runs
+enum ConvLoop { LOOP_PIPELINED, LOOP_PINGPONG, LOOP_PINGPONG_MX, LOOP_ONE_WAVE };
 
 template <int KS, int DIL, int MF, int NF, int EPI, int SPLIT, int CS8, int PCH_, int NW_, int PADV_, int K2D = 0>
 struct ConvCfg {
@@ -290,53 +319,43 @@ struct ConvCfg {
     static constexpr int WBUF = PCH * NF * FRAG;
     static constexpr int NTAP = (K2D ? 1 : KS) * KS * KS;
     static constexpr int KOFF_N = NTAP * CS8MAX + 24;      // + look-ahead padding (2 chunks; f16m8: one 8-group piece; bridged slabs: up to 7 units of the next slab)
-    // one wave per SIMD (conv3d_f16_mfma, PWM loop): 4 waves x (8 voxel x NF cout) fragments, accumulators in AGPRs; the tap tables of ALL slabs
-    // (x both halo buffers) are written once per launch instead of once per slab
-    static constexpr bool PWM = (SPLIT == 3 || (SPLIT == 2 && SN_MX_FMT != 0)) && K2D == 0 && NW_ == 4 && KS == 3 && MF == 8 && PCH_ == 2;
-    // tap tables of the one-wave-per-SIMD loop, written once per launch: a slab's table depends only on the halo buffer it sits in, on its first unit (bridge
-    // pieces: 27 units per slab against 8 per piece - a function of slab mod 8) and on whether it is the tile's last: 16 tables per buffer, any number of slabs
-    static constexpr int PW_TABS = 16;
-    static constexpr int pw_tab(int kb, int slab, bool last) { return kb * PW_TABS + (last ? 8 : 0) + (slab & 7); }
+    // buffer-addressed halo staging (conv3d_f16_mfma, stage_halo_buf); the one-plane f16 mode of the 2-D nets (4-group slabs: up to 400 MB) keeps the generic path
+    static constexpr bool BUFH = (K2D == 0) || (SPLIT != 0);
+    // WHICH K LOOP RUNS THIS CONFIGURATION - decided here and nowhere else; first match wins. Beside each case: the layers that reach it
+    // (sn_api.hip build_plan_t, sn_simil.hip SimilKernels).
+    static constexpr ConvLoop LOOP =
+        (KS == 3 && K2D == 0 && SPLIT >= 2 && NW_ == 4 && MF == 8 && PCH_ == 2) ? LOOP_ONE_WAVE      // default mode: merge_conv_a / merge_conv_b (f16m8), conv4_1 .. conv4_3 (f16m8e)
+        : (KS == 3 && K2D == 0 && SPLIT == 2 && NW_ == 8)                       ? LOOP_PINGPONG_MX   // all-MX mode (f16m8 contexts): every 3x3x3 layer
+        : (KS == 3 && SPLIT < 2 && NW_ == 8 && PCH_ >= 2 && BUFH)               ? LOOP_PINGPONG      // f16 / f16x3: every 3x3x3 layer (3-D nets, both modes), the similarityNet's layers (f16x3)
+                                                                                : LOOP_PIPELINED;    // the 1x1x1 side convolutions (every mode), the similarityNet's layers in its one-plane f16 mode
+    // bridge chunks / pieces (conv3d_f16_mfma, "BRIDGE chunks"): the loops that can run a slab's last chunk / piece into the next slab's units; the launcher refuses a
+    // layer packed with them on any other kernel
+    static constexpr bool HAS_BRIDGE = LOOP == LOOP_ONE_WAVE || LOOP == LOOP_PINGPONG_MX || (LOOP == LOOP_PINGPONG && SPLIT == 1);
+    // Tap tables per halo buffer. One-wave-per-SIMD and ping-pong loops: the tables of ALL slabs (x both halo buffers) are written once per launch instead of once
+    // per slab in a load slot - a slab's table depends only on the halo buffer it sits in, on its first unit (bridge chunks / pieces: 27 or 18 units per slab against 4
+    // per chunk, 8 per piece - a function of slab mod TABS/2) and on whether it is the tile's last (b = 0, possibly fewer groups). The other loops rewrite ONE table per slab.
+    static constexpr int TABS = LOOP == LOOP_ONE_WAVE ? 16 : (LOOP == LOOP_PINGPONG ? 8 : 1);
+    static constexpr int tab(int kb, int slab, int last) { return TABS == 1 ? kb : kb * TABS + (last ? TABS / 2 : 0) + (slab & (TABS / 2 - 1)); }      // table of slab `slab` in halo buffer kb; last: it is the tile's last slab (an int: as a bool parameter it swapped two scalar operands in the bridged ping-pong kernels)
     // LDS distance of voxel fragment m from fragment 0 of the same lane under the row-gap-4 map (frag_xyz: hx = wave * XS + (m >> 2), hy = (m & 3) + 4 (v >> 3)):
-    // a compile-time constant, so the PWM loop addresses all fragments as one per-lane register + the read's immediate offset
+    // a compile-time constant, so the one-wave-per-SIMD loop addresses all fragments as one per-lane register + the read's immediate offset
     static constexpr int pw_xoff(int m) { return (((m >> 2) * HY + (m & 3)) * HZ) * VS; }
     // the same under the row-gap-2 map (hy = (m & 1) + 4 ((m >> 1) & 1) + 2 (v >> 3)); XGAP = the map this kernel's 3-D form uses (frag_xyz)
     static constexpr int XGAP = DIL == 2 ? kRowGapDil2 : kRowGap3x3;
     static constexpr int xoff_of(int m) { return XGAP == 4 ? pw_xoff(m) : (((m >> 2) * HY + (m & 1) + 4 * ((m >> 1) & 1)) * HZ) * VS; }
-    // f16x3 3x3(x3) kernels on the ping-pong loop (PTAB): a slab's tap table depends only on the halo buffer it sits in, on its first unit (a function of
-    // slab mod 4 with bridge chunks: 27 or 18 units per slab, 4 per chunk) and on whether it is the tile's last (b = 0, possibly fewer groups) - 8 tables per buffer, written once per launch instead of once per slab in a load slot
-    static constexpr bool PTAB = SPLIT < 2 && NW_ == 8 && KS == 3 && PCH_ >= 2 && (K2D == 0 || SPLIT != 0) && !PWM;      // (= the kernels of the f16 / f16x3 ping-pong loop, 3-D and 2-D)
-    static constexpr int KTAB_N = PWM ? PW_TABS * KOFF_N : (PTAB ? 8 * KOFF_N : KOFF_N);   // ints per halo buffer
+    static constexpr int KTAB_N = TABS * KOFF_N;           // ints per halo buffer
     static constexpr int NSEG0 = (HVOX * VS + 1023) / 1024;
-    static constexpr int NSEG = PWM ? (NSEG0 + NW_ - 1) / NW_ * NW_ : NSEG0;   // 1 KiB DMA segments per plane (one-wave-per-SIMD loop: the same number for every wave)
+    static constexpr int NSEG = LOOP == LOOP_ONE_WAVE ? (NSEG0 + NW_ - 1) / NW_ * NW_ : NSEG0;   // 1 KiB DMA segments per plane (one-wave-per-SIMD loop: the same number for every wave)
     static constexpr int XPLANE = NSEG * 1024;
     static constexpr int XBUF = XPLANE * NPL;
-#ifndef SN_PW_WB3
-#define SN_PW_WB3 0       // 1: one-wave-per-SIMD loop with a RING OF THREE weight-piece buffers where the LDS has room (the merge layers: 159 KB) - a piece's DMAs are issued two
-                          // pieces ahead and the per-piece wait lets the newest ones fly. Built and measured in round 6 (profiles/r6/ab_r6_wb3.log): bit-identical, merge_conv_b
-                          // 2.751 -> 2.793 ms, merge_conv_a 1.863 -> 1.861 - the per-piece vmcnt + barrier wait is the waves' skew at the barrier, not DMA latency. Off.
-#endif
     static constexpr bool CST_LDS = (EPI == EPI_STORE) && NF >= 7;   // wide store epilogues: keep scale/shift in LDS so the compiler's vmcnt(0) before their use cannot serialise the stores (measured: merge_conv_a -4 %, narrower layers +3..6 % -> off there)
     static constexpr int EPI_CONST = CST_LDS ? NF * 16 * 4 * 2 : 0;   // scale, shift of this cout split, fp32
-    static constexpr int NWB = (SN_PW_WB3 && PWM && 2 * XBUF + 3 * WBUF + 2 * KTAB_N * 4 + EPI_CONST <= 160 * 1024) ? 3 : 2;      // weight-piece buffers
-    static constexpr int wb_next(int b) { return NWB == 3 ? (b == 2 ? 0 : b + 1) : (b ^ 1); }
-    static constexpr int LDS_BYTES = 2 * XBUF + NWB * WBUF + 2 * KTAB_N * 4 + EPI_CONST;
+    static constexpr int LDS_BYTES = 2 * XBUF + 2 * WBUF + 2 * KTAB_N * 4 + EPI_CONST;
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget exceeded");
     // two 4-wave workgroups per CU only when 256 registers per lane are plausibly enough (accumulators = MF*NF*4)
     static constexpr int WG_PER_CU = (LDS_BYTES <= 80 * 1024 && NW == 4 && MF * NF <= 32) ? 2 : 1;
     // two waves per SIMD (8-wave workgroup or two 4-wave workgroups per CU): keep <= 256 registers per lane
     static constexpr int MIN_WAVES_PER_SIMD = (NW == 8 || WG_PER_CU == 2) ? 2 : 1;
 };
-
-// Does this configuration run the f16 / f16x3 ping-pong loop with bridge chunks (kernel: PPX, BRIDGE_OK)? - the launcher refuses a layer packed
-// with bridge chunks on any other kernel
-template <int KS, int SPLIT, int NW, int PCH, int NF, int K2D, int MF = 4>
-constexpr bool sn_conv_has_bridge()
-{
-    return (SPLIT == 1 && NW == 8 && KS == 3 && PCH >= 2) ||
-           (SPLIT == 2 && K2D == 0 && NW == 8 && KS == 3 && SN_MX_FMT != 0) ||
-           ((SPLIT == 3 || (SPLIT == 2 && SN_MX_FMT != 0)) && K2D == 0 && NW == 4 && MF == 8 && KS == 3 && PCH == 2);
-}
 
 // OSPLIT: storage format of the OUTPUT tensor (defaults to SPLIT): lets an f16x3 layer feed an f16m8 layer.
 template <int KS, int DIL, int MF, int NF, int EPI, int SPLIT, int CS8, int PCH_, int NW_, int PADV_, int K2D = 0, int OSPLIT_ = -1>
@@ -348,11 +367,11 @@ conv3d_f16_mfma(ConvArgs a)
     constexpr int NPL = C::NPL;
     __shared__ __attribute__((aligned(16))) char lds[C::LDS_BYTES];
     char *const xbuf = lds;                                   // [2][NPL][XPLANE]
-    char *const wbuf = lds + 2 * C::XBUF;                     // [NWB][WBUF]
-    int *const kbuf = reinterpret_cast<int *>(lds + 2 * C::XBUF + C::NWB * C::WBUF);   // [2][KOFF_N]  (PWM: [2][PW_TABS][KOFF_N])
+    char *const wbuf = lds + 2 * C::XBUF;                     // [2][WBUF]
+    int *const kbuf = reinterpret_cast<int *>(lds + 2 * C::XBUF + 2 * C::WBUF);   // [2][TABS][KOFF_N]
     // epilogue constants live in LDS: a global load in the epilogue would make hipcc wait vmcnt(0), i.e. for every store
     // issued before it (measured: 21 us per tile of serialised store->load round trips in merge_conv_a)
-    float *const cst = reinterpret_cast<float *>(lds + 2 * C::XBUF + C::NWB * C::WBUF + 2 * C::KTAB_N * 4);   // [2][NF*16]
+    float *const cst = reinterpret_cast<float *>(lds + 2 * C::XBUF + 2 * C::WBUF + 2 * C::KTAB_N * 4);   // [2][NF*16]
 
     // the wave id IS wave-uniform, but anything derived from threadIdx is divergent to hipcc: without the readfirstlane every
     // loop and LDS-DMA destination indexed by it becomes an EXEC-masked (waterfall) loop (guide T20)
@@ -419,13 +438,9 @@ conv3d_f16_mfma(ConvArgs a)
     //   descriptor starts at the TILE's first image, so offsets (up to one group plane of the whole chunk) stay < 2^28. Images past
     //   the end of a partial last tile read whatever follows inside the descriptor (or zeros): their outputs are never stored.
     // Preconditions (checked by launch_conv): only the first / last tile along an axis has out-of-volume halo voxels, and the
-    // slab fits the offset field. The one-plane f16 mode of the 2-D nets (4-group slabs: up to 400 MB) keeps the generic path.
-    constexpr bool BUFH = (K2D == 0) || (SPLIT != 0);
-    constexpr bool PPM = SPLIT == 2 && K2D == 0 && NW_ == 8 && KS == 3 && SN_MX_FMT != 0;   // ping-pong K loop, f16m8 kernels (slab loop)
-    constexpr bool PPX = SPLIT < 2 && NW_ == 8 && KS == 3 && PCH_ >= 2 && BUFH;          // ... f16 / f16x3 kernels
-    constexpr bool PP = PPM || PPX;
-    constexpr bool PWM = C::PWM;                   // one wave per SIMD (slab loop)
-    constexpr bool UNI = PP || PWM;                // loops in which hipcc's divergence analysis loses wave-uniform values (stage_halo_buf)
+    // slab fits the offset field (ConvCfg::BUFH).
+    constexpr bool BUFH = C::BUFH;
+    constexpr ConvLoop LOOP = C::LOOP;
     constexpr unsigned FB_YLO = K2D ? (1u << 31) : HB_YLO, FB_YHI = K2D ? (1u << 30) : HB_YHI, FB_ZLO = K2D ? (1u << 29) : HB_ZLO,
                        FB_ZHI = K2D ? (1u << 28) : HB_ZHI, FB_NEVER = K2D ? 0x0FFFFFF0u : HB_ALWAYS, FB_OFFMASK = K2D ? 0x0FFFFFFFu : HB_OFFMASK;
     unsigned hword[HT];
@@ -471,7 +486,7 @@ conv3d_f16_mfma(ConvArgs a)
     auto stage_halo_buf = [&](int b, unsigned keep, int toff, int c0, int c8n, int xb, int kb = 0, int ke = 1 << 20) -> int {      // [kb, ke): this call's instalment of the wave's HT slots
         // opaque to the optimiser: otherwise it hoists (hword[k] & keep) + toff and the descriptors of BOTH candidate tiles out of the
         // K loop as loop invariants (8 VGPRs + 16 SGPRs live across it) and the accumulators spill
-        if constexpr (UNI) {      // (wave-uniform values that hipcc's divergence analysis loses inside the ping-pong piece loop)
+        if constexpr (LOOP != LOOP_PIPELINED) {      // (wave-uniform values that hipcc's divergence analysis loses inside the ping-pong piece loop)
             b = __builtin_amdgcn_readfirstlane(b); keep = __builtin_amdgcn_readfirstlane(keep);
             toff = __builtin_amdgcn_readfirstlane(toff); c0 = __builtin_amdgcn_readfirstlane(c0);
         }
@@ -485,7 +500,7 @@ conv3d_f16_mfma(ConvArgs a)
             base0 = reinterpret_cast<const char *>(a.in) + 2 * ((size_t)c0 * VOL * 8 + (size_t)b * D * D * 8);
             nrec = (c8n * (int)VOL - b * D * D) * 16;
         }
-        if constexpr (UNI) {      // ... and of the descriptor itself: a buffer_load with a "divergent" resource becomes a waterfall loop
+        if constexpr (LOOP != LOOP_PIPELINED) {      // ... and of the descriptor itself: a buffer_load with a "divergent" resource becomes a waterfall loop
             const unsigned long long bq = (unsigned long long)(size_t)base0;
             base0 = (const char *)(size_t)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(bq >> 32)) << 32) |
                                            (unsigned)__builtin_amdgcn_readfirstlane((int)bq));
@@ -518,11 +533,12 @@ conv3d_f16_mfma(ConvArgs a)
     // The f16m8 kernels work in PIECES of 8 units (two f16 chunks + one MX step over the same 8): 27 units = 3.375 pieces were run as 4, the
     // 4th with one chunk, three units and a full-size weight DMA. Bridged, merge_conv_a's 8 slabs are 27 pieces instead of 32 and merge_conv_b's
     // 13 are 44 instead of 52; the bridge piece is a slab's third or fourth, behind the vmcnt(0) of the second piece's MX load slot.
-    constexpr bool BRIDGE_OK = (PPX && SPLIT == 1) || PPM || PWM;
-    constexpr int UM = SPLIT >= 2 ? 8 : 4;                   // units per chunk / per piece: what a slab's unit count is rounded up to
-    constexpr int BSTEP = (UM - (C::NTAP * C::CS8MAX) % UM) % UM;      // bridged layers (all slabs hold CS8MAX groups): a slab starts this many units later (mod UM) than its predecessor
-    const bool bridge = BRIDGE_OK && a.bridge != 0;
-    // units of slab `slab` in its chunks: GU - o of its own (o: taken by the slab before) + b of the next slab's
+    // THE rule - units per step, a slab's units and borrow b, the next slab's o - is sn_consts.h's (slab_step, slab_units, slab_next_o, slab_first_o: the packer cuts
+    // its stream by those functions). Its run-time uses below are written out: called as functions, each of them changed the device code of the bridged kernels.
+    constexpr int UM = slab_step(SPLIT);                     // units per chunk / per piece: what a slab's unit count is rounded up to
+    constexpr int BSTEP = slab_shift(C::NTAP * C::CS8MAX, UM);      // bridged layers (all slabs hold CS8MAX groups): a slab starts this many units later (mod UM) than its predecessor
+    const bool bridge = C::HAS_BRIDGE && a.bridge != 0;
+    // units of slab `slab` in its chunks: GU - o of its own (o: taken by the slab before) + b of the next slab's (sn_consts.h: slab_first_o, slab_units)
     auto slab_units = [&](int c8n, int slab, int &o, int &b) {
         const int GU = C::NTAP * c8n;
         o = 0; b = 0;
@@ -541,7 +557,7 @@ conv3d_f16_mfma(ConvArgs a)
     auto write_koff_part = [&](int c8n, int kb, int slab, int t0, int nt) {
         int uo, ub;
         const int own = slab_units(c8n, slab, uo, ub) - ub, nchunk = (own + ub + 3) >> 2;
-        int *k = kbuf + (PWM ? C::pw_tab(kb, slab, slab + 1 == a.nslab) : (C::PTAB ? kb * 8 + ((slab + 1 == a.nslab) ? 4 : 0) + (slab & 3) : kb)) * C::KOFF_N;
+        int *k = kbuf + C::tab(kb, slab, slab + 1 == a.nslab) * C::KOFF_N;
         for (int g = t0; g < (nchunk + 4) * 4; g += nt) {
             int o = 0;
             if (g < own + ub) {
@@ -611,20 +627,13 @@ conv3d_f16_mfma(ConvArgs a)
             tile_halo_consts(x0, y0, z0, keep, toff);
             stage_halo_buf(K2D ? x0 : b, keep, toff, 0, c8n, 0);
         } else stage_halo(tile, 0, c8n, 0, 0, HT);
-        if constexpr (C::PTAB) {      // the 8 tables per halo buffer (see ConvCfg::PTAB): slabs 0..3 as representatives of their residue, the last slab once per residue
+        if constexpr (C::TABS > 1) {      // all tables of both halo buffers (ConvCfg::tab; the bridge entries depend on the buffer): slabs 0 .. TABS/2-1 as representatives of their residue, and the last slab
             for (int kb = 0; kb < 2; ++kb)
                 for (int sl = 0; sl < a.nslab; ++sl)
-                    if (sl < 4 || sl + 1 == a.nslab) write_koff(slab_c8_of(sl), kb, sl);
-        } else
-        if constexpr (PWM) {      // the 16 tables per halo buffer (ConvCfg::pw_tab; the bridge entries depend on the buffer): slabs 0..7 as representatives, the last slab
-            for (int kb = 0; kb < 2; ++kb)
-                for (int sl = 0; sl < a.nslab; ++sl)
-                    if (sl < 8 || sl + 1 == a.nslab) write_koff(slab_c8_of(sl), kb, sl);
-        } else
-        write_koff(c8n, 0, 0);
+                    if (sl < C::TABS / 2 || sl + 1 == a.nslab) write_koff(slab_c8_of(sl), kb, sl);
+        } else write_koff(c8n, 0, 0);
         const int nch = wchunks_of(c8n, 0);
         stage_w(0, nch < C::PCH ? nch : C::PCH, 0);
-        if constexpr (C::NWB == 3) stage_w((size_t)C::PCH * NF * C::FRAG, C::PCH, 1);      // ring of three: the layer's second piece as well (every slab of such a layer holds >= 2 pieces)
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         wg_barrier();
     }
@@ -664,27 +673,27 @@ conv3d_f16_mfma(ConvArgs a)
         // behind its last segment), so that both groups run the epilogue at the same time. With a free-running offset the tile boundary costs
         // two slots of (epilogue + load) each - a group's epilogue sits in its load slot while the partner's short MFMA burst ends and waits -
         // which merge_conv_a's store epilogue cannot afford (+4 % against the non-ping-pong kernel before this, A/B r3e).
-        if constexpr (PP) { if (wave >= C::NW / 2) wg_barrier(); }
+        if constexpr (LOOP == LOOP_PINGPONG || LOOP == LOOP_PINGPONG_MX) { if (wave >= C::NW / 2) wg_barrier(); }
         const long long t_tile0 = SN_TIMING == 10 ? __builtin_readcyclecounter() : 0;     // 10: per tile {epilogue, K loop}
-        // PWM: what a piece hands to its successor - the operand fragments of the successor's first f16 chunk (read during the MX burst), the tap
+        // One-wave-per-SIMD loop: what a piece hands to its successor - the operand fragments of the successor's first f16 chunk (read during the MX burst), the tap
         // offsets of its second chunk and of its MX step. A tile's first piece loads them cold, right here.
-        half8 pw_xf[PWM ? MF : 1], pw_wf[PWM ? NF : 1];
+        half8 pw_xf[LOOP == LOOP_ONE_WAVE ? MF : 1], pw_wf[LOOP == LOOP_ONE_WAVE ? NF : 1];
         const unsigned pw_wv = (unsigned)(wave * 1024 + lane * 16);      // this lane's bytes within this wave's first KiB of a weight piece (weight DMAs)
         // Per-slab scalars carried from slab to slab instead of re-derived (slab_units with its branches, three to four times per slab): the slab's first unit
-        // (all loops), and - PWM, where the slab boundary is the one place with no MFMA in flight: ~120 scalar instructions there were 480 clocks per slab,
+        // (all loops), and - one-wave-per-SIMD loop, where the slab boundary is the one place with no MFMA in flight: ~120 scalar instructions there were 480 clocks per slab,
         // 3 % of the kernel - the base of the halo tile staged during the slab (one 8-channel group plane further per slab; behind the tile's last slab the
         // next tile's first group)
         int sl_o = 0;             // first (tap, group) unit of the current slab's chunk / piece sequence (bridge chunks: the units before it went to the slab before)
         const char *pw_hnext = nullptr, *pw_hptr = nullptr;
-        if constexpr (PWM) {
+        if constexpr (LOOP == LOOP_ONE_WAVE) {
             const bool hn = tile + tstride < a.total_tiles;
             pw_hptr = reinterpret_cast<const char *>(a.in) + 2 * ((size_t)b * VOL * a.in_cs) + VOL * 16;                 // slab 0 stages slab 1
             pw_hnext = reinterpret_cast<const char *>(a.in) + 2 * ((size_t)(hn ? nxt_b : b) * VOL * a.in_cs);             // (no next tile: this tile's first slab once more, the buffer is idle)
         }
         int pw_koB = 0;
         long long pw_k2 = 0;
-        if constexpr (PWM) {
-            const unsigned tab0 = kbuf_a + (unsigned)(C::pw_tab(xb, 0, a.nslab == 1) * (C::KOFF_N * 4));
+        if constexpr (LOOP == LOOP_ONE_WAVE) {
+            const unsigned tab0 = kbuf_a + (unsigned)(C::tab(xb, 0, a.nslab == 1) * (C::KOFF_N * 4));
             int koA;
             lds_read32<0>(koA, tab0);
             lds_read32<16>(pw_koB, tab0);
@@ -697,11 +706,11 @@ conv3d_f16_mfma(ConvArgs a)
         }
         // (launch_conv: nslab >= 1. Said out loud because the zero-trip path around the slab loop, never taken, otherwise meets the loop's exit in front of the
         // epilogue with the accumulators in a different register assignment: ~220 AGPR-to-AGPR copies per tile on the path that is taken)
-        if constexpr (PWM) __builtin_assume(a.nslab >= 1);       // (the eight-wave kernels: conv4_x / conv1_3 +1 % with it - left as they were)
+        if constexpr (LOOP == LOOP_ONE_WAVE) __builtin_assume(a.nslab >= 1);       // (the eight-wave kernels: conv4_x / conv1_3 +1 % with it - left as they were)
         for (int slab = 0; slab < a.nslab; ++slab) {
             const bool last_slab = slab + 1 == a.nslab;
             const int c8n = last_slab ? a.c8_last : C::CS8MAX;
-            // units of this slab's chunks / pieces: GU - o of its own (o: taken by the slab before) + b of the next slab's (slab_units, branch-free on the carried o)
+            // units of this slab's chunks / pieces: GU - o of its own (o: taken by the slab before) + b of the next slab's (sn_consts.h: slab_units, on the carried o)
             const int su_o = sl_o, su_b = (UM - ((C::NTAP * c8n - su_o) & (UM - 1))) & ((bridge && !last_slab) ? UM - 1 : 0);
             const int units = C::NTAP * c8n - su_o + su_b;
             const int nchunk = (units + 3) >> 2, wchunk = SPLIT >= 2 ? ((units + 7) >> 3) << 1 : nchunk;
@@ -712,20 +721,20 @@ conv3d_f16_mfma(ConvArgs a)
             const int nslab_i = last_slab ? 0 : slab + 1;
             const bool nlast = nslab_i + 1 == a.nslab;
             const int nc8n = nlast ? a.c8_last : C::CS8MAX;
-            // ... and the K-chunks its weight stream holds (the size of its first weight piece)
+            // ... and the K-chunks its weight stream holds (the size of its first weight piece; sn_consts.h: slab_next_o, slab_units)
             const int n_o = (bridge && !last_slab) ? (su_o + BSTEP) & (UM - 1) : 0;
             const int n_units = C::NTAP * nc8n - n_o + ((UM - ((C::NTAP * nc8n - n_o) & (UM - 1))) & ((bridge && !nlast) ? UM - 1 : 0));
             const int n_wchunk = SPLIT >= 2 ? ((n_units + 7) >> 3) << 1 : (n_units + 3) >> 2;
             const int nc0 = last_slab ? 0 : c0 + c8n;
             const size_t nwoff = last_slab ? 0 : woff + (size_t)wchunk * NF * C::FRAG;
-            if constexpr (!PP && !PWM) { if (have_next) write_koff(nc8n, xb ^ 1, nslab_i); }
+            if constexpr (LOOP == LOOP_PIPELINED) { if (have_next) write_koff(nc8n, xb ^ 1, nslab_i); }
             // the next halo tile is fetched in npiece-1 instalments, each issued right after a weight piece so that a
             // counted vmcnt can wait for the weights while the newest halo DMAs stay in flight
             // Instalment size HQ is a compile-time constant (sized for a full slab) so that the wait in front of the barrier is a
             // fixed s_waitcnt vmcnt(HQ) or vmcnt(0), one scalar branch; the last instalment of a short slab takes whatever is left.
             int hdone = 0;
 
-            if constexpr (PWM) {
+            if constexpr (LOOP == LOOP_ONE_WAVE) {
                 // ---- ONE WAVE PER SIMD (round 4): 4 waves x (8 voxel x NF cout) fragments, accumulators in AGPRs ------------------------------
                 // The ping-pong loops below put two waves on a SIMD and let one load while the other computes; every hand-over is a workgroup
                 // barrier (6 per weight piece, each ~100-190 clocks of idle matrix pipe), and a wave's (4 + NF) operand reads serve 4 NF MFMAs.
@@ -738,8 +747,8 @@ conv3d_f16_mfma(ConvArgs a)
                 // burst: by then every wave has read all it needs from the piece's weight buffer (so the piece after next may be fetched into
                 // it) and its share of the next piece's DMAs has landed (the MX burst reads the next piece's first fragments).
                 // Same K order, same MFMAs per accumulator as the ping-pong loop: bit-identical results.
-                static_assert(SPLIT >= 2 && C::PCH == 2 && BUFH && EPI != EPI_SIDEPOOL && C::NSEG % C::NW == 0 && C::XPLANE + C::xoff_of(MF - 1) < 65536,
-                              "one-wave-per-SIMD loop: f16m8 3x3x3 kernels");
+                static_assert(EPI != EPI_SIDEPOOL && C::NSEG % C::NW == 0 && C::XPLANE + C::xoff_of(MF - 1) < 65536,
+                              "one-wave-per-SIMD loop: store / final epilogues, equal DMA shares, fragments within the reads' 64 KiB immediate offset");
                 long long pws1 = 0;                    // SN_TIMING 4: per slab {everything in front of the piece loop since the previous slab's last piece, the piece loop}
                 constexpr int mxo = 2 * NF * 1024;
                 constexpr int WCNT = C::PCH * NF * NPL, WPW = (WCNT + C::NW - 1) / C::NW;      // 1 KiB DMAs per weight piece / per wave
@@ -747,8 +756,8 @@ conv3d_f16_mfma(ConvArgs a)
                 // burst A: behind its first 16 MFMAs (operand reads) one DMA slot every DSP MFMAs - the next weight piece's WPW and (a slab's first two pieces) HT / 2 halo DMAs
                 constexpr int DSP = (NM - 16) / (WPW + HT / 2) >= 3 ? 3 : 2;
                 static_assert(MF + NF <= 16 && 16 + DSP * (WPW + HT / 2 - 1) < NM && 4 + 2 * NF + 15 < NM, "filler schedule exceeds the burst");
-                const unsigned tab_a = kbuf_a + (unsigned)(C::pw_tab(xb, slab, last_slab) * (C::KOFF_N * 4));
-                const unsigned ntab_a = kbuf_a + (unsigned)(C::pw_tab(xb ^ 1, nslab_i, nlast) * (C::KOFF_N * 4));
+                const unsigned tab_a = kbuf_a + (unsigned)(C::tab(xb, slab, last_slab) * (C::KOFF_N * 4));
+                const unsigned ntab_a = kbuf_a + (unsigned)(C::tab(xb ^ 1, nslab_i, nlast) * (C::KOFF_N * 4));
                 const unsigned xs_a = xbuf_a + xb * C::XBUF + (unsigned)xbase[0];
                 const unsigned nxs_a = xbuf_a + (xb ^ 1) * C::XBUF + (unsigned)xbase[0];
                 // the halo tile staged during this slab's first two pieces: the next slab's / the next tile's first slab (carried pointers, see the tile loop)
@@ -765,37 +774,34 @@ conv3d_f16_mfma(ConvArgs a)
                     return __builtin_amdgcn_make_buffer_rsrc((void *)base, (short)0, __builtin_amdgcn_readfirstlane((int)VOL * 16), 0x00020000);
                 };
                 // halo descriptors of the slab staged during this one: the f16 plane goes out with the slab's first piece, the code plane with its second
-                static_assert(HT % 2 == 0 && C::NSEG * NPL == HT * C::NW && (HT / 2) * C::NW == C::NSEG && WCNT % C::NW == 0, "PWM DMA schedule");
+                static_assert(HT % 2 == 0 && C::NSEG * NPL == HT * C::NW && (HT / 2) * C::NW == C::NSEG && WCNT % C::NW == 0, "one-wave-per-SIMD loop: DMA schedule");
                 constexpr int HH = HT / 2;
                 const __amdgpu_buffer_rsrc_t rs_hi = halo_rsrc(0), rs_lo = halo_rsrc(1);
                 const unsigned hdst = lds_addr(xbuf) + (unsigned)((xb ^ 1) * C::XBUF + wave * 1024);      // + k * NW KiB: this wave's k-th halo segment
                 int p = 0;
                 if constexpr (SN_TIMING == 4) { pws1 = __builtin_readcyclecounter(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); if (t_rel != 0) t_vm += pws1 - t_rel; }
-                do {             // (launch_conv: every slab of a PWM layer has at least two pieces)
+                do {             // (launch_conv: every slab of a layer on this loop has at least two pieces)
                     // ONE loop body for all pieces (a second, specialised copy for the slab's first piece - written out, or peeled off by the optimiser when
                     // it can see "p == 0" - made hipcc spill 75 registers and shuffle accumulators between the register files around every MFMA)
                     int p_opaque = p;
                     asm volatile("" : "+s"(p_opaque));
                     const bool first = p_opaque == 0;
-                    const unsigned wp = wbuf_a + wbi * C::WBUF, wpn = wbuf_a + C::wb_next(wbi) * C::WBUF;
+                    const unsigned wp = wbuf_a + wbi * C::WBUF, wpn = wbuf_a + (wbi ^ 1) * C::WBUF;
                     const bool more = p + 1 < npiece;
                     // the piece after this one: the slab's next, else the first piece of the next slab / tile (tap table and halo tile of the OTHER buffer)
                     const unsigned nk_a = more ? tab_a + (unsigned)(8 * (p + 1)) * 4 : ntab_a;
                     const unsigned nx_a = more ? xs_a : nxs_a;
-                    // the weight piece fetched during this one: two buffers - the next piece; ring of three - the piece after next (the slab's, else piece 0 / 1 of the
-                    // next slab / tile: every slab holds at least two), into the buffer the PREVIOUS piece was read from (everybody left it at that piece's barrier)
-                    size_t w_off;
-                    if constexpr (C::NWB == 3) w_off = p + 2 < npiece ? woff + (size_t)(2 * p + 4) * NF * C::FRAG : (have_next ? nwoff : 0) + (size_t)(2 * (p + 2 - npiece)) * NF * C::FRAG;
-                    else w_off = more ? woff + (size_t)(2 * p + 2) * NF * C::FRAG : (have_next ? nwoff : 0);
+                    // the weight piece fetched during this one: the next piece (the slab's, else piece 0 of the next slab / tile), into the other buffer
+                    const size_t w_off = more ? woff + (size_t)(2 * p + 2) * NF * C::FRAG : (have_next ? nwoff : 0);
                     const char *const wsrc = wsrc0 + w_off;
-                    const unsigned wdst_a = lds_addr(wbuf) + (unsigned)((C::NWB == 3 ? C::wb_next(C::wb_next(wbi)) : (wbi ^ 1)) * C::WBUF + wave * 1024);
+                    const unsigned wdst_a = lds_addr(wbuf) + (unsigned)((wbi ^ 1) * C::WBUF + wave * 1024);
                     const bool halo_now = p_opaque < 2;           // (pieces 0 and 1 of the slab carry the next halo tile's DMAs)
                     __amdgpu_buffer_rsrc_t rs_p = first ? rs_hi : rs_lo;
                     unsigned hdst_p = hdst + (first ? 0u : (unsigned)(HH * C::NW * 1024));
                     asm volatile("" : "+s"(rs_p), "+s"(hdst_p));
                     half8 xfB[MF], wfB[NF];
                     int koA_n = 0;
-                    // SN_TIMING (diagnostic builds; PWM loop): 1 {burst A, burst B}, 2 {vmcnt wait, barrier}, 3 {burst M, whole piece} per piece
+                    // SN_TIMING (diagnostic builds; this loop): 1 {burst A, burst B}, 2 {vmcnt wait, barrier}, 3 {burst M, whole piece} per piece
                     long long pwt[6] = {0, 0, 0, 0, 0, 0};
 #define PW_T(i) do { if constexpr (SN_TIMING >= 1 && SN_TIMING <= 3) { pwt[i] = __builtin_readcyclecounter(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); } } while (0)
                     PW_T(0);
@@ -871,14 +877,6 @@ conv3d_f16_mfma(ConvArgs a)
                     // the one barrier of the piece: this wave's part of the next weight piece (issued a burst ago) and, from a slab's second piece on,
                     // of the next halo tile has landed; nobody reads this piece's weight buffer any more
                     PW_T(2);
-                    if constexpr (C::NWB == 3) {
-                        // the NEXT piece's weights were requested a whole piece ago; what this piece requested (WPW weight DMAs for the piece after next, and the HH halo
-                        // DMAs of a slab's first two pieces, interleaved with them) may stay in flight - the memory pipe returns in order. (A slab of only two pieces
-                        // must see its second halo plane before the next slab starts: no allowance there.)
-                        if (!halo_now) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(WPW) : "memory");
-                        else if (more) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(WPW + HH) : "memory");
-                        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    } else
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     PW_T(3);
                     wg_barrier();
@@ -887,16 +885,11 @@ conv3d_f16_mfma(ConvArgs a)
                     // ---- burst M: the MX step, voxel fragment m in the outer loop (NF MFMAs each). Behind group m: the code slots of fragment m + 2,
                     // two operand reads of the NEXT piece's first f16 chunk, the operand of fragment m + 1 formed (its slots were requested a
                     // group ago: counted wait - LDS returns in order), and (a slab's first piece) one DMA of the next halo tile
-                    typedef int v2i_ __attribute__((ext_vector_type(2)));
                     mx_op wa[NF];
 #pragma unroll
                     for (int n = 0; n < NF; ++n) {
                         if constexpr (FP8) wa[n] = __builtin_shufflevector(wa4[n], wa4b[n], 0, 1, 2, 3, 4, 5, 6, 7);
-                        else {
-                        const v2i_ b2 = __builtin_bit_cast(v2i_, wb2[n]);
-                        const v4i b4 = __builtin_shufflevector(b2, b2, 0, 1, -1, -1);
-                        wa[n] = __builtin_shufflevector(wa4[n], b4, 0, 1, 2, 3, 4, 5);
-                        }
+                        else wa[n] = sn_mx6_weight<mx_op>(wa4[n], wb2[n]);
                         asm volatile("" : "+v"(wa[n]));
                     }
                     int wsc_lo = FP8 ? 127 - 12 : (int)wsc, wsc_hi = (int)(wsc >> 32);      // (fp8: the lo parts of the plain weight codes carry 2^12: one E8M0 scale 2^-12 for all)
@@ -939,11 +932,11 @@ conv3d_f16_mfma(ConvArgs a)
                     if constexpr (SN_TIMING == 1) { t_vm += pwt[1] - pwt[0]; t_bar += pwt[2] - pwt[1]; ++n_piece; }
                     if constexpr (SN_TIMING == 2) { t_vm += pwt[3] - pwt[2]; t_bar += pwt[4] - pwt[3]; ++n_piece; }
                     if constexpr (SN_TIMING == 3) { t_vm += pwt[5] - pwt[4]; t_bar += pwt[5] - pwt[0]; ++n_piece; }
-                    wbi = C::wb_next(wbi);
+                    wbi ^= 1;
                 } while (++p < npiece);
                 if constexpr (SN_TIMING == 4) { t_rel = __builtin_readcyclecounter(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); t_bar += t_rel - pws1; ++n_piece; if (last_slab) t_rel = 0; }
             } else
-            if constexpr (PPX) {
+            if constexpr (LOOP == LOOP_PINGPONG) {
                 // ---- PING-PONG K loop, f16 / f16x3 kernels (round 3) ---------------------------------------------------
                 // Same structure as the f16m8 loop below: a segment = one K-chunk; its NPLM * (MF + NF) operand fragments are read into registers in
                 // the wave's LOAD slot (with the tap offset of the next segment and the wave's DMA duties), its (SPLIT ? 3 : 1) * MF * NF MFMAs run as
@@ -952,8 +945,7 @@ conv3d_f16_mfma(ConvArgs a)
                 // a piece, the wait for the weights with the piece's last segment (the halo, younger, may stay in flight: counted wait).
                 // Measured and dropped (profiles/r3, r4 README): halo DMAs dealt out over the load slots or issued inside the burst, two chunks per
                 // segment, a scheduling barrier between operand reads and DMA duties.
-                static_assert(C::PCH >= 2 && BUFH && SPLIT < 2 && C::PTAB, "ping-pong loop (f16 / f16x3): at least two chunks per weight piece");
-                const unsigned koff_a = kbuf_a + (unsigned)((xb * 8 + (last_slab ? 4 : 0) + (slab & 3)) * (C::KOFF_N * 4));
+                const unsigned koff_a = kbuf_a + (unsigned)(C::tab(xb, slab, last_slab) * (C::KOFF_N * 4));
                 const unsigned xslab = xbuf_a + xb * C::XBUF;
                 constexpr int NPLM = C::NPLM;
                 int ko, ko_n = 0;
@@ -1048,8 +1040,8 @@ conv3d_f16_mfma(ConvArgs a)
                     wbi ^= 1;
                 } while (++p < npiece);
             } else
-            if constexpr (PPM) {
-                // ---- PING-PONG K loop, f16m8 kernels launched as eight-wave workgroups (round 3; since round 4 only the all-MX mode's 3x3x3 layers) --
+            if constexpr (LOOP == LOOP_PINGPONG_MX) {
+                // ---- MX PING-PONG K loop: f16m8 kernels launched as eight-wave workgroups (round 3; since round 4 only the all-MX mode's 3x3x3 layers) --
                 // The two waves of a SIMD (wave w of group 0 = waves 0..3 and wave w + 4 of group 1) never compete for the matrix pipe: a
                 // SEGMENT (one K-chunk of f16 MFMAs, or one MX step) is LOADED - every operand fragment of the segment read from LDS into
                 // registers, plus this wave's share of the DMA issue - and then COMPUTED as one uninterrupted burst of MF*NF MFMAs whose operands are
@@ -1061,7 +1053,6 @@ conv3d_f16_mfma(ConvArgs a)
                 // Measured and dropped again (DESIGN.md sections 4.2 / 8; profiles/r3/README.md): one designated DMA wave per slot, halo DMAs spread
                 // over the pieces, the closing barrier in front of the burst's last MFMAs, both f16 chunks loaded in one slot, MX weights read with the
                 // f16 chunks' loads, 96-bit reads of the code slots, the next segment's weight fragments requested from inside the burst.
-                static_assert(SPLIT == 2 && C::PCH == 2 && SN_MX_FMT != 0 && BUFH, "ping-pong loop: f16m8 kernels with 6-bit MX operands");
                 const unsigned koff_a = kbuf_a + xb * (C::KOFF_N * 4);
                 const unsigned k2_a = koff_a + kq * 4;
                 const unsigned xslab = xbuf_a + xb * C::XBUF;       // (wave-uniform; the per-lane fragment offsets xbase[] stay the only address registers)
@@ -1097,7 +1088,6 @@ conv3d_f16_mfma(ConvArgs a)
                     constexpr int mxo = 2 * NF * 1024;
                     v4i wa4[NF];                                    // MX step: a lane's 192-bit weight operand = 128 + 64 bits ...
                     long long wb2[NF], wsc;                         // ... and the E8M0 block scales of its NF fragments
-                    typedef int v2i_ __attribute__((ext_vector_type(2)));
                     using I0 = std::integral_constant<int, 0>;
                     using I1 = std::integral_constant<int, 1>;
                     auto load_f16 = [&](auto ccc, int ko) {           // the activation and weight fragments of f16 chunk cc
@@ -1174,11 +1164,7 @@ conv3d_f16_mfma(ConvArgs a)
                             x8[m] = __builtin_shufflevector(x8h[m][0], x8h[m][1], 0, 1, 2, 4, 5, 6, -1, -1);
                         }
 #pragma unroll
-                        for (int n = 0; n < NF; ++n) {
-                            const v2i_ b2 = __builtin_bit_cast(v2i_, wb2[n]);
-                            const v4i b4 = __builtin_shufflevector(b2, b2, 0, 1, -1, -1);
-                            wa[n] = __builtin_shufflevector(wa4[n], b4, 0, 1, 2, 3, 4, 5, -1, -1);
-                        }
+                        for (int n = 0; n < NF; ++n) wa[n] = sn_mx6_weight<v8i>(wa4[n], wb2[n]);
                         if (p + 1 < npiece) { koA = koAn; koB = koBn; k2 = k2n; }
                         // (pins the operand tuples - and the register moves per activation fragment that forming them costs - in front of the barrier,
                         // i.e. into the load segment: instruction selection otherwise sinks them to their first use, the head of the MFMA burst)
@@ -1200,7 +1186,7 @@ conv3d_f16_mfma(ConvArgs a)
                     wbi ^= 1;
                 } while (++p < npiece);
             } else {
-            // ---- software-pipelined K loop (rounds 1-2) -------------------------------------------------------------
+            // ---- HAND-PIPELINED K loop (rounds 1-2) -------------------------------------------------------------
             // Still runs the kernels the newer loops do not cover: the 1x1x1 side convolutions (4-wave workgroups, every precision mode) and the 2-D
             // nets' one-plane f16 mode (generic halo path). One barrier per weight piece; inside a piece the loop is pipelined by hand:
             // X fragments of chunk c+1 and the tap offset of chunk c+2 are fetched while chunk c computes (the halo buffer is immutable for the
@@ -1208,7 +1194,7 @@ conv3d_f16_mfma(ConvArgs a)
             // fetched while fragment n's MFMAs issue. Every wait counts only the reads issued AFTER the one waited for (LDS returns in order).
             // (Its round-2 refinements for the 3x3x3 f16m8 kernels - the barrier in front of a piece's last two MFMA groups, prefetch reads spread
             // over the chunk, weight fragments two groups ahead - went with those kernels' move to the ping-pong loops: profiles/r2/README.md.)
-            static_assert((KS == 1 && SPLIT <= 2) || (K2D != 0 && SPLIT == 0), "legacy K loop: 1x1x1 layers and the 2-D one-plane f16 mode");
+            static_assert((KS == 1 && SPLIT <= 2) || (K2D != 0 && SPLIT == 0), "hand-pipelined loop: 1x1x1 layers and the 2-D one-plane f16 mode");
             const unsigned koff_a = kbuf_a + xb * (C::KOFF_N * 4);
             unsigned xaddr[MF];
 #pragma unroll
@@ -1369,11 +1355,11 @@ conv3d_f16_mfma(ConvArgs a)
             c0 += c8n;
             woff += (size_t)wchunk * NF * C::FRAG;
             sl_o = n_o;
-            if constexpr (PWM) pw_hptr += VOL * 16;
+            if constexpr (LOOP == LOOP_ONE_WAVE) pw_hptr += VOL * 16;
         }
 
-        if constexpr (PP) { if (wave < C::NW / 2) wg_barrier(); }     // pairs with group 1's last compute segment of the tile
-        if constexpr (PWM) {      // the loop's MFMAs are inline asm: the wait states between the last of them and the epilogue's accumulator reads, by hand
+        if constexpr (LOOP == LOOP_PINGPONG || LOOP == LOOP_PINGPONG_MX) { if (wave < C::NW / 2) wg_barrier(); }     // pairs with group 1's last compute segment of the tile
+        if constexpr (LOOP == LOOP_ONE_WAVE) {      // the loop's MFMAs are inline asm: the wait states between the last of them and the epilogue's accumulator reads, by hand
 #pragma unroll
             for (int m = 0; m < MF; ++m)
 #pragma unroll
@@ -1421,14 +1407,10 @@ conv3d_f16_mfma(ConvArgs a)
                         if constexpr (R2) y = fmaxf(y, fmaxf(t1, 0.f));
                         y = fmaxf(y, __shfl_xor(y, 1));
                         if constexpr (!R2) y = fmaxf(y, __shfl_xor(y, YX));
-                        if constexpr (OSPLIT == 1) {
-                            _Float16 hh, ll;
-                            sn_split(y, hh, ll);
-                            h[r] = hh; l[r] = ll;
-                        } else {
-                            h[r] = (_Float16)y;
-                            lo32[r] = (y - (float)h[r]) * kMxLoMul;
-                        }
+                        _Float16 hh, ll;
+                        sn_parts<OSPLIT == 1>(y, kMxLoMul, hh, ll, lo32[r]);
+                        h[r] = hh;
+                        if constexpr (OSPLIT == 1) l[r] = ll;
                     }
                     sn_track_acc(trk_acc, acc[m][n]);
                     if constexpr (R2) sn_track_acc(trk_acc, acc[m + 1 < MF ? m + 1 : m][n]);
@@ -1515,14 +1497,10 @@ conv3d_f16_mfma(ConvArgs a)
                         for (int r = 0; r < 4; ++r) {
                             const float pre = sacc[mp + e][r] * ssc[r] + ssh[r];
                             float t = a.side_act == 0 ? fmaxf(pre, 0.f) : sn_sigmoid(pre);
-                            if constexpr (OSPLIT == 1) {
-                                _Float16 hh, ll;
-                                sn_split(t, hh, ll);
-                                h[r] = hh; l[r] = ll;
-                            } else {
-                                h[r] = (_Float16)t;
-                                lo32[r] = (t - (float)h[r]) * kMxLoMul;
-                            }
+                            _Float16 hh, ll;
+                            sn_parts<OSPLIT == 1>(t, kMxLoMul, hh, ll, lo32[r]);
+                            h[r] = hh;
+                            if constexpr (OSPLIT == 1) l[r] = ll;
                         }
                         const uint2 hb = __builtin_bit_cast(uint2, h);
                         hw[e][0] = hb.x; hw[e][1] = hb.y;
@@ -1583,14 +1561,10 @@ conv3d_f16_mfma(ConvArgs a)
                         float t = fmaxf(y[mm][n][r], y[mm + 2][n][r]);
                         t = fmaxf(t, fmaxf(y[mset + 1][n][r], y[mset + 3][n][r]));
                         t = fmaxf(t, __shfl_xor(t, 1));
-                        if constexpr (SPLIT == 1) {
-                            _Float16 hh, ll;
-                            sn_split(t, hh, ll);
-                            h[r] = hh; l[r] = ll;
-                        } else {
-                            h[r] = (_Float16)t;
-                            lo32[r] = (t - (float)h[r]) * kMxLoMul;
-                        }
+                        _Float16 hh, ll;
+                        sn_parts<SPLIT == 1>(t, kMxLoMul, hh, ll, lo32[r]);
+                        h[r] = hh;
+                        if constexpr (SPLIT == 1) l[r] = ll;
                     }
                     const int ch = n * 16 + kq * 4;
                     { const uint2 hb = __builtin_bit_cast(uint2, h); sn_track_h2(trk_h, hb.x); sn_track_h2(trk_h, hb.y); }
@@ -1683,15 +1657,11 @@ conv3d_f16_mfma(ConvArgs a)
                         for (int r = 0; r < 4; ++r) {
                             const float pre = prev[r];
                             float y = ACT == 0 ? fmaxf(pre, 0.f) : sn_sigmoid(pre);
-                            if constexpr (OLO) {
-                                _Float16 hh, ll;
-                                sn_split(y, hh, ll);
-                                h[r] = hh; l[r] = ll;
-                                if constexpr (O8) lo32[r] = (y - (float)hh) * f8lo;
-                            } else {
-                                h[r] = (_Float16)y;
-                                lo32[r] = (y - (float)h[r]) * (O8 ? f8lo : kMxLoMul);
-                            }
+                            _Float16 hh, ll;
+                            sn_parts<OLO>(y, O8 ? f8lo : kMxLoMul, hh, ll, lo32[r]);
+                            h[r] = hh;
+                            if constexpr (OLO) l[r] = ll;
+                            if constexpr (OLO && O8) lo32[r] = (y - (float)hh) * f8lo;      // (three planes: the fp8 slots' lo part as well)
                         }
                         const uint2 hb = __builtin_bit_cast(uint2, h);
                         hw[e][0] = hb.x; hw[e][1] = hb.y;
@@ -1784,7 +1754,6 @@ conv3d_f16_mfma(ConvArgs a)
         }
         if constexpr (SN_TIMING == 10) { const long long t_tile2 = __builtin_readcyclecounter(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); t_vm += t_tile2 - t_tile1; t_bar += t_tile1 - t_tile0; ++n_piece; }
     }
-    if constexpr (C::NWB == 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the ring's look-ahead DMAs of the last pieces: nothing may land in LDS after the workgroup has left)
     bad |= sn_tracked_bad(trk_acc, trk_h);
     if (a.status && __builtin_amdgcn_ballot_w64(bad) != 0 && lane == 0) atomicOr(a.status, a.status_bit);
     if (a.status && a.mx_sat_bits != 0 && __builtin_amdgcn_ballot_w64(sn_tracked_max_bits(trk_h) > a.mx_sat_bits) != 0 && lane == 0) atomicOr(a.status + 1, a.status_bit);

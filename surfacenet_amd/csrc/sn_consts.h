@@ -29,4 +29,21 @@ constexpr int kMxX0E8 = 127 + 5;      // the network input (f16m8 mode only): me
 
 namespace sn {
 constexpr int kMaxSlab = 128;         // channel slabs of a layer at the most (conv3d_mfma.h; pack_conv_host refuses more)
+
+// ---- How a channel slab is cut into K-chunks and weight pieces: THE rule, for the kernels (conv3d_mfma.h) and the packer (sn_pack.h) -----------------
+// A slab of c8n channel groups holds gu = NTAP * c8n (tap, group) UNITS. The loops consume them `um` at a time - 4 per K-chunk (f16, f16x3), 8 per weight
+// piece (f16m8, f16m8e) - and gu is rarely a multiple of that. Without bridge chunks every slab is padded up with zero weights. A BRIDGED layer (all slabs
+// hold the same gu) fills a slab's last step with the first b units of the NEXT slab of the tile instead, which then starts at its unit o = b; only the
+// tile's last slab borrows nothing and pads. All arithmetic is mod um, a power of two.
+constexpr int slab_step(int split) { return split >= 2 ? 8 : 4; }                                    // um
+constexpr int slab_shift(int gu, int um) { return (um - (gu & (um - 1))) & (um - 1); }               // a bridged slab starts this many units later (mod um) than the slab before
+struct SlabUnits { int units, b; };                                                                  // units a slab runs (its own from o on, + b borrowed); a multiple of um unless b = 0
+constexpr SlabUnits slab_units(int gu, int o, bool bridge, bool last, int um)
+{
+    const int b = (um - ((gu - o) & (um - 1))) & ((bridge && !last) ? um - 1 : 0);
+    return {gu - o + b, b};
+}
+// first unit of the slab that follows one starting at o (= that slab's b), and of slab number `slab` of a tile (= slab_next_o applied `slab` times to 0)
+constexpr int slab_next_o(int o, int gu, bool bridge, bool last, int um) { return (bridge && !last) ? (o + slab_shift(gu, um)) & (um - 1) : 0; }
+constexpr int slab_first_o(int slab, int gu, bool bridge, int um) { return bridge ? (slab * slab_shift(gu, um)) & (um - 1) : 0; }
 }

@@ -376,7 +376,7 @@ struct ConvKernel {
         a.bridge = L.bridge;
         if (L.bridge && !geom.has_bridge)
             return fail(SN_ERR_STATE, "%s: packed with bridge chunks, launched on a kernel without them", L.name.c_str());
-        if (C::PWM) {      // one-wave-per-SIMD loop: a slab's first piece issues DMAs that its second piece waits for
+        if (C::LOOP == sn::LOOP_ONE_WAVE) {      // one-wave-per-SIMD loop: a slab's first piece issues DMAs that its second piece waits for
             for (unsigned char c8n : L.slab_c8)
                 if (C::NTAP * c8n < 9) return fail(SN_ERR_STATE, "%s: a channel slab of fewer than two weight pieces", L.name.c_str());
         }
@@ -394,7 +394,7 @@ struct ConvKernel {
         return SN_OK;
     }
     static constexpr ConvGeom geom = {KS, DIL, K2D != 0, NF, C::CS8MAX, SPLIT, OSPLIT < 0 ? SPLIT : OSPLIT, EPI,
-                                      sn::sn_conv_has_bridge<KS, SPLIT, NW, PCH, NF, K2D, MF>(), &launch};
+                                      C::HAS_BRIDGE, &launch};
 };
 
 // Temporary device arrays of one call (freed on scope exit: the stream must be done with them by then). out() allocates, up() allocates and

@@ -124,22 +124,21 @@ static int pack_conv_host(PackedConv &L, const float *W_in, const float *beta, c
         return (o < L.cout && ci < L.cin) ? W[((size_t)o * L.cin + ci) * ntap + tap] : 0.f;
     };
     h.clear();
-    // bridge chunks (conv3d_mfma.h, write_koff_part): asked for by the caller (L.bridge), granted to f16x3 3x3(x3) layers whose slabs all hold the
-    // same number of channel groups and whose units per slab are not a multiple of 4: the last K-chunk of a slab is filled up with the first
-    // b units of the next slab, which starts at its unit o = b
+    // bridge chunks (sn_consts.h, the slab rule; conv3d_mfma.h, write_koff_part): asked for by the caller (L.bridge), granted to f16x3 3x3(x3) layers
+    // (f16m8 / f16m8e: 3-D only) whose slabs all hold the same number of channel groups and whose units per slab are not a multiple of the step
     {
-        const int um = split >= 2 ? 8 : 4;                  // units per K-chunk (f16x3) / per weight piece (f16m8)
-        bool ok = L.bridge && (split == 1 || (split >= 2 && !L.k2d)) && L.ks == 3 && L.slab_c8.size() >= 2 && (ntap * cs8max) % um != 0;
+        bool ok = L.bridge && (split == 1 || (split >= 2 && !L.k2d)) && L.ks == 3 && L.slab_c8.size() >= 2 && sn::slab_shift(ntap * cs8max, sn::slab_step(split)) != 0;
         for (unsigned char c8n : L.slab_c8) ok = ok && c8n == cs8max;
         L.bridge = ok ? 1 : 0;
     }
     const int nslab = (int)L.slab_c8.size();
-    // units of slab si in its chunks / pieces: GU - o of its own + b of the next slab's (the kernel's slab_units)
+    // units of slab si in its chunks / pieces: GU - o of its own + b of the next slab's (sn_consts.h: the rule the kernels cut their slabs by)
     auto slab_units = [&](int si, int c8n, int &o, int &b) {
-        const int GU = ntap * c8n, um = split >= 2 ? 8 : 4;
-        o = 0; b = 0;
-        if (L.bridge) { o = (si * ((um - GU % um) % um)) % um; b = (si + 1 == nslab) ? 0 : (um - (GU - o) % um) % um; }
-        return GU - o + b;
+        const int GU = ntap * c8n, um = sn::slab_step(split);
+        o = sn::slab_first_o(si, GU, L.bridge != 0, um);
+        const sn::SlabUnits u = sn::slab_units(GU, o, L.bridge != 0, si + 1 == nslab, um);
+        b = u.b;
+        return u.units;
     };
     if (split < 2) {
         long long chunks = 0;

@@ -7,6 +7,8 @@
 // The packed stream is read back here the way the KERNELS address it (the layout comment above pack_conv_host; conv3d_mfma.h slab_units /
 // write_koff_part for the unit order and the bridge chunks), not by running the packer's loops backwards: splits -> slabs -> chunks or pieces ->
 // fragment -> lane -> element, every position mapped to (output channel, input channel, tap).
+// The rule both sides cut a slab by (sn_consts.h: slab_step, slab_units, slab_next_o, slab_first_o) is checked on its own against a walk that deals the
+// units out one at a time (check_slab_rule).
 #include "sn_pack.h"
 
 #include <cinttypes>
@@ -370,6 +372,55 @@ static void check_side(int cin, int producer_nf)
         for (int ci = 0; ci < cin; ++ci) CHECK(hits[(size_t)o * cin + ci] == (ci < 32 * nq ? 1 : 0));
 }
 
+// ---- 3g: the slab rule of sn_consts.h against a walk that deals the units out one at a time ---------------------------------------------------------
+// A tile's (tap, group) units, slab after slab, are put into steps of um units. A step belongs to the slab of its first unit. Where a slab ends, the open
+// step is closed and padded - unless the layer is bridged and another slab follows: then that slab's first units fill it. Counted per slab: the units in
+// its own steps, how many of them the next slab lent (b), and how many of its units went to the slab before (o). Bridged layers hold at least one step's
+// worth of units per full slab (the packer grants bridges to 3x3 taps only, 9 units and more), and the last slab must have a unit left to start on.
+static void check_slab_rule()
+{
+    int cases = 0, bridged_short = 0;
+    for (int ntap : {1, 9, 27})
+        for (int c8n = 1; c8n <= 8; ++c8n)
+            for (int c8_last = 1; c8_last <= c8n; ++c8_last)
+                for (int nslab = 1; nslab <= 16; ++nslab)
+                    for (int split : {1, 2})
+                        for (int bridge = 0; bridge < 2; ++bridge) {
+                            const int um = sn::slab_step(split), gu_full = ntap * c8n;
+                            CHECK(um == (split == 1 ? 4 : 8) && sn::slab_step(0) == 4 && sn::slab_step(3) == 8);
+                            if (bridge && gu_full < um) continue;
+                            snprintf(g_where, sizeof g_where, "slab rule: ntap %d c8n %d c8_last %d nslab %d um %d bridge %d", ntap, c8n, c8_last, nslab, um, bridge);
+                            int units[16] = {0}, o[16] = {0}, b[16] = {0}, steps[16] = {0}, fill = 0, owner = 0;
+                            for (int s = 0; s < nslab; ++s) {
+                                const int gu = ntap * (s + 1 == nslab ? c8_last : c8n);
+                                for (int u = 0; u < gu; ++u) {
+                                    if (fill == 0) { owner = s; ++steps[s]; }
+                                    if (owner != s) { ++o[s]; ++b[owner]; }
+                                    ++units[owner];
+                                    fill = (fill + 1) % um;
+                                }
+                                if (!bridge || s + 1 == nslab) fill = 0;
+                            }
+                            if (steps[nslab - 1] == 0) continue;       // (bridged, and the slab before took every unit of a shorter last slab)
+                            int oc = 0;                                // the carried o, as the kernels' slab loop has it
+                            for (int s = 0; s < nslab; ++s) {
+                                const bool last = s + 1 == nslab;
+                                const int gu = ntap * (last ? c8_last : c8n);
+                                const sn::SlabUnits su = sn::slab_units(gu, oc, bridge, last, um);
+                                CHECKF(oc == o[s] && su.units == units[s] && su.b == b[s], "slab %d: o %d units %d b %d, the walk has %d %d %d", s, oc, su.units, su.b, o[s], units[s], b[s]);
+                                CHECKF(sn::slab_first_o(s, gu_full, bridge, um) == o[s], "slab %d: slab_first_o %d, the walk has %d", s, sn::slab_first_o(s, gu_full, bridge, um), o[s]);
+                                CHECKF((su.units + um - 1) / um == steps[s] && (su.units % um == 0 || !bridge || last), "slab %d: %d units in %d steps", s, su.units, steps[s]);
+                                oc = sn::slab_next_o(oc, gu_full, bridge, last, um);
+                                CHECKF(oc == su.b, "slab %d: the next slab starts at %d, this one borrows %d", s, oc, su.b);
+                            }
+                            CHECK((sn::slab_shift(gu_full, um) != 0) == (gu_full % um != 0));
+                            ++cases;
+                            if (bridge && c8_last < c8n && nslab > 1) ++bridged_short;
+                        }
+    snprintf(g_where, sizeof g_where, "slab rule");
+    CHECKF(cases > 5000 && bridged_short > 500, "%d cases, %d of them bridged with a shorter last slab", cases, bridged_short);
+}
+
 // ---- 3f: refusals ---------------------------------------------------------------------------------------------------------------------------------
 static void check_errors()
 {
@@ -402,6 +453,7 @@ int main()
     check_encoder(kBf6, [](float v) { return mx6_encode(v, 3); }, 0);
     CHECK(mx6_max(2) == (float)kFp6.vmax && mx6_max(3) == (float)kBf6.vmax);
     check_errors();
+    check_slab_rule();
     check_side(32, 2); check_side(80, 5); check_side(160, 5); check_side(300, 5);
     Row r;
     int rows = 0;

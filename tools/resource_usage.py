@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """tools/resource_usage.py — registers / spills / LDS of every conv3d_f16_mfma instantiation, from `make -C surfacenet_amd/csrc asm`
-(/tmp/sn_asm/resource_usage.txt: hipcc -Rpass-analysis=kernel-resource-usage). Prints the kernels that spill or use scratch, and any whose
+(resource_usage.txt under its ASM_DIR, by default /tmp/sn_asm; another one: SN_ASM_DIR=... in the environment. hipcc
+-Rpass-analysis=kernel-resource-usage, every unit). Prints the kernels that spill or use scratch, and any whose
 template arguments contain one of the given substrings:   python tools/resource_usage.py ["3, 2, 4, 5" ...]"""
+import os
 import re
 import subprocess
 import sys
 
-t = open("/tmp/sn_asm/resource_usage.txt").read()
+t = open(os.path.join(os.environ.get("SN_ASM_DIR", "/tmp/sn_asm"), "resource_usage.txt")).read()
 blocks = re.split(r"remark: [^\n]*Function Name: ", t)[1:]
 want = sys.argv[1:]
 for b in blocks:
