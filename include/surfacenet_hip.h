@@ -28,7 +28,7 @@ extern "C" {
 /* Added since, without a version change (additions only): sn_ptcubes, sn_ptcubes_dev, sn_ptcubes_sparse_dev and sn_ptcubes_cfg - the
  * point-seeded cube list; sn_normals, sn_normals_dev, sn_unique_voxels, sn_unique_voxels_dev and sn_normals_cfg - oriented normals and
  * de-duplication of the output cloud; sn_gt_bind, sn_gt_bind_dev, sn_gt_cubes, sn_gt_cubes_dev, sn_weighted_accuracy and
- * sn_weighted_accuracy_dev - the ground-truth mode. */
+ * sn_weighted_accuracy_dev - the ground-truth mode; sn_mesh, sn_mesh_dev and sn_mesh_cfg - the surface-nets mesh of the oriented cloud. */
 
 /* The library is built with -fvisibility=hidden: the functions below are its WHOLE dynamic symbol table
  * (tests/test_abi.py compares `nm -D` with this header). */
@@ -272,6 +272,39 @@ SN_API int sn_unique_voxels(sn_ctx *ctx, int n, int stride_vox, const int64_t *o
                             const unsigned char *mask, unsigned char *keep);
 SN_API int sn_unique_voxels_dev(sn_ctx *ctx, int n, int stride_vox, long long total, const int64_t *offsets_dev, const unsigned char *ijk_dev,
                                 const uint32_t *cube_ijk_dev, const unsigned char *mask_dev, unsigned char *keep_dev);
+
+/* ---- surface mesh of the oriented output cloud: surface nets on the world lattice -------------------------------------
+ * On the packed sparse lists (offsets, ijk, cube_ijk, mask as the two entries above take them) plus normals (total,3) float32 as the normals entry
+ * writes them: zero = no normal. The oriented cells P are the world cells whose owner - the smallest packed index among the cell's masked
+ * voxels - has a normal with a non-zero component; nq = rint(float64(n) * 16384) per component. At a lattice point c,
+ * F(c) = sum over p in P, d = c - p in [-radius, radius]^3, of w(d) * (nq_p . d) and W(c) = sum of w(d), w(d) = prod (radius + 1 - |d_k|), both
+ * int64 and exact; c is defined iff W > 0 and inside iff F < 0. A lattice edge (c, c + e_a) is active iff both ends are defined and exactly one is
+ * inside; it emits a quad iff a cell of P lies within Chebyshev distance `reach` of an end. One vertex per 2x2x2 group of lattice points (dual
+ * cube m) that an emitted quad uses, at the float64 mean of the crossings t = F0 / (F0 - F1) of all its active edges. The order of vertices and
+ * quads, the winding (face normals point from inside to outside) and vert_src are canonical: the result equals the numpy restatement
+ * tests/mesh_ref.py, the integers exactly. Masked voxels: every normal component finite and |.| <= 2, cell + 8 < 2^21 per axis (SN_ERR_ARG).
+ *   verts_mm (V,3) float32 = float32(origin + resol * verts_lattice); verts_lattice (V,3) float64; vert_cell (V,3) int32 = m;
+ *   vert_src (V) int64: packed index of the owner of the cell of P nearest the dual cube's centre (-1: none within m + {-1..2}^3);
+ *   quads (Q,4) int32 vertex indices. Every output is optional (NULL). The caller sizes them: they hold cap_verts vertices and cap_quads quads;
+ *   n_verts / n_quads (required) receive V and Q. When a cap is short nothing is written, the counts say what is needed and the status is
+ *   SN_ERR_ARG. Vertex and quad indices are int32. The counts are kept below 2^31 by a limit on the scene, not on the counts themselves: the
+ *   oriented cells and their 26 neighbours may occupy at most 2^23 bricks of 4^3 lattice points (64 vertices and 192 quads a brick at most),
+ *   beyond that SN_ERR_ARG - a sufficient condition, so a scene past it is refused even if its mesh would have fitted.
+ *   Deterministic; the workspace belongs to the context (grown on demand); both forms return when the work is done. total <= 2^28. */
+typedef struct sn_mesh_cfg {
+    int radius;                /* window radius of the field: 1, 2 or 3 */
+    int reach;                 /* 0 .. radius: how far from a cell of P an active edge may lie and still emit its quad */
+    int stride_vox;            /* cube stride in voxels */
+    double origin[3];          /* mm position of lattice point (0,0,0) */
+    double resol;              /* mm per cell */
+} sn_mesh_cfg;
+SN_API int sn_mesh(sn_ctx *ctx, int n, const sn_mesh_cfg *cfg, const int64_t *offsets, const unsigned char *ijk, const uint32_t *cube_ijk,
+                   const unsigned char *mask, const float *normals, long long cap_verts, long long cap_quads, float *verts_mm, double *verts_lattice,
+                   int32_t *vert_cell, int64_t *vert_src, int32_t *quads, long long *n_verts, long long *n_quads);
+SN_API int sn_mesh_dev(sn_ctx *ctx, int n, const sn_mesh_cfg *cfg, long long total, const int64_t *offsets_dev, const unsigned char *ijk_dev,
+                       const uint32_t *cube_ijk_dev, const unsigned char *mask_dev, const float *normals_dev, long long cap_verts, long long cap_quads,
+                       float *verts_mm_dev, double *verts_lattice_dev, int32_t *vert_cell_dev, int64_t *vert_src_dev, int32_t *quads_dev,
+                       long long *n_verts, long long *n_quads);
 
 /* ---- DTU point-cloud evaluation (experiments/DTU/eval_ply.m -> PointCompareMain of the DTU kit) ----------------------
  * Points are (n,3) float64, row-major, finite. d^2 = (dx*dx + dy*dy) + dz*dz in float64 without contraction: the results are those of the numpy

@@ -508,6 +508,56 @@ class Context(object):
         _lib.check(self._lib.sn_unique_voxels(self._h, n, int(stride_vox), _lib.ptr(offsets), _lib.ptr(ijk), _lib.ptr(cube), _lib.ptr(m), _lib.ptr(keep)))
         return keep.view(bool)
 
+    def mesh(self, offsets, ijk, cube_ijk, mask, stride_vox, normals, radius=2, reach=0, origin=(0.0, 0.0, 0.0), resol=1.0, cap=None, device=False):
+        """Surface-nets mesh of the oriented cloud (sn_mesh): the packed lists unique_voxels takes plus normals (T,3)
+        float32 (zero = no normal), origin (3,) / resol the mm position of lattice point 0 and the cell size. Returns a dict: verts_mm (V,3)
+        float32, verts_lattice (V,3) float64, vert_cell (V,3) int32, vert_src (V,) int64, quads (Q,4) int32. cap = (vertices, quads) the first
+        call's arrays hold (a guess from the voxel count when None); a short guess costs one retry with the exact counts. device=True stages the
+        lists in device memory here and runs sn_mesh_dev on them: the same result."""
+        offsets, n, ijk, cube = self._packed(offsets, ijk, cube_ijk)
+        m = np.ascontiguousarray(mask, dtype=bool).reshape(-1).view(np.uint8)
+        T = int(offsets[-1])
+        nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        if ijk.shape[0] != T or m.size != T or nrm.shape[0] != T:
+            raise ValueError("offsets end at %d voxels: %d ijk rows, %d mask entries, %d normals" % (T, ijk.shape[0], m.size, nrm.shape[0]))
+        cfg = _lib.MeshCfg(int(radius), int(reach), int(stride_vox))
+        cfg.origin[:] = [float(v) for v in np.asarray(origin, dtype=np.float64).reshape(3)]
+        cfg.resol = float(resol)
+        caps = (2 * T + 64, 2 * T + 64) if cap is None else (int(cap[0]), int(cap[1]))
+        spec = (("verts_mm", 3, np.float32), ("verts_lattice", 3, np.float64), ("vert_cell", 3, np.int32), ("vert_src", 1, np.int64), ("quads", 4, np.int32))
+        nv, nq = ctypes.c_longlong(0), ctypes.c_longlong(0)
+        staged = []
+        try:
+            if device:
+                for a in (offsets, ijk, cube, m, nrm):
+                    staged.append(self.dev_alloc(max(a.nbytes, 16)))
+                    if a.nbytes:
+                        self.h2d(staged[-1], a)
+            for attempt in range(2):
+                rows = lambda name: caps[1] if name == "quads" else caps[0]
+                out = {name: np.empty((rows(name), w) if w > 1 else (rows(name),), dt) for name, w, dt in spec}
+                if device:
+                    bufs = [self.dev_alloc(max(out[name].nbytes, 16)) for name, _, _ in spec]
+                    staged.extend(bufs)
+                    rc = self._lib.sn_mesh_dev(self._h, n, ctypes.byref(cfg), T, *staged[:5], caps[0], caps[1], *bufs, ctypes.byref(nv), ctypes.byref(nq))
+                else:
+                    rc = self._lib.sn_mesh(self._h, n, ctypes.byref(cfg), _lib.ptr(offsets), _lib.ptr(ijk), _lib.ptr(cube), _lib.ptr(m), _lib.ptr(nrm),
+                                           caps[0], caps[1], *[_lib.ptr(out[name]) for name, _, _ in spec], ctypes.byref(nv), ctypes.byref(nq))
+                if rc == -1 and attempt == 0 and (nv.value > caps[0] or nq.value > caps[1]):
+                    caps = (nv.value, nq.value)      # the counts say what is needed: one retry at that size
+                    continue
+                _lib.check(rc)
+                break
+            for (name, _, _), k in zip(spec, range(5)):
+                rows = nq.value if name == "quads" else nv.value
+                if device and rows:
+                    self.d2h(out[name][:rows] if out[name].ndim == 1 else out[name][:rows, :], staged[-5 + k])
+                out[name] = out[name][:rows].copy()
+        finally:
+            for b in staged:
+                self.dev_free(b)
+        return out
+
     @staticmethod
     def _points(xyz):
         return np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))

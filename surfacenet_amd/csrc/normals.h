@@ -15,13 +15,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "nm_table.h"
+
 namespace sn {
 
-constexpr int NM_NT = 256;
-constexpr int NM_AXIS_BITS = 21;                     // cells per axis: 63-bit keys, as pointeval.h / ptcubes.h
-constexpr long long NM_AXIS_MAX = 1ll << NM_AXIS_BITS;
 constexpr int NM_SWEEPS = 12;                        // cyclic Jacobi sweeps (3 rotations each)
-constexpr unsigned long long NM_OWNER_TOP = 1ull << 62;
 // bits of the call's status word (read back by the host before the main kernel runs)
 constexpr int NM_FLAG_TABLE = 1, NM_FLAG_CELL = 2, NM_FLAG_VIEW = 4;
 
@@ -38,58 +36,9 @@ struct NMArgs {
     int n, stride, radius, min_nb;
 };
 
-__device__ inline unsigned nm_hash(unsigned long long k, unsigned mask)
-{
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    return (unsigned)k & mask;
-}
-
-__device__ inline unsigned long long nm_key(long long x, long long y, long long z) { return ((unsigned long long)x << 42) | ((unsigned long long)y << 21) | (unsigned long long)z; }
-
-// the cube that owns packed index t: the first c with off[c + 1] > t. Any table contents give an index in [0, n).
-__device__ inline int nm_cube_of(const int64_t *off, int n, long long t)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid + 1] <= t) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 __device__ inline void nm_cell(const NMArgs &a, int c, long long t, long long g[3])
 {
     for (int d = 0; d < 3; ++d) g[d] = (long long)a.cube_ijk[3 * c + d] * a.stride + (long long)a.ijk[3 * t + d];
-}
-
-// slot of `key` (stored as key + 1), claimed if absent
-__device__ inline unsigned nm_claim(unsigned long long *tab, unsigned hmask, unsigned long long key)
-{
-    const unsigned long long stored = key + 1ull;
-    unsigned h = nm_hash(key, hmask);
-    for (;;) {                                       // ends: the table holds at least twice the keys that can be inserted
-        unsigned long long cur = __hip_atomic_load(tab + 2 * (size_t)h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == 0ull) {
-            unsigned long long expected = 0ull;
-            if (__hip_atomic_compare_exchange_strong(tab + 2 * (size_t)h, &expected, stored, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return h;
-            cur = expected;
-        }
-        if (cur == stored) return h;
-        h = (h + 1) & hmask;
-    }
-}
-
-// value word of `key`, 0 if absent (read-only: after the insert kernel has finished)
-__device__ inline unsigned long long nm_find(const unsigned long long *tab, unsigned hmask, unsigned long long key)
-{
-    const unsigned long long stored = key + 1ull;
-    unsigned h = nm_hash(key, hmask);
-    for (;;) {
-        const unsigned long long cur = tab[2 * (size_t)h];
-        if (cur == stored) return tab[2 * (size_t)h + 1];
-        if (cur == 0ull) return 0ull;
-        h = (h + 1) & hmask;
-    }
 }
 
 // offsets table: starts at 0, non-decreasing, ends at total. Per cube (view_idx given): every view index in [0, V), cbar = mean camera centre,

@@ -1,0 +1,268 @@
+// sn_mesh.hip — C ABI of the surface mesh of the oriented output cloud (mesh.h). The device form works on the caller's
+// device arrays; the host form stages its arrays in temporary device memory and runs the same computation.
+#include "sn_internal.h"
+#include "mesh.h"
+#include "bitonic.h"
+#include "scan.h"
+
+namespace {
+
+constexpr long long MS_MAX_VOXELS = 1ll << 28;       // hash tables of >= 2 * total slots stay within 2^29
+constexpr unsigned long long MS_MAX_BRICKS = (1ull << 28) / 27;      // the candidate table of >= 2 * 27 * bricks slots stays within 2^29
+constexpr unsigned long long MS_MAX_CAND = 1ull << 23;               // candidate bricks: 64 lattice points each, 192 quads at most: int counts
+
+struct SyncOnExit {                                  // temporary device buffers are freed on return: the stream must be done with them
+    sn_ctx *c;
+    ~SyncOnExit() { (void)hipStreamSynchronize(c->stream); }
+};
+
+unsigned blocks(long long n) { return (unsigned)((n + MS_NT - 1) / MS_NT); }
+
+int ms_check_args(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long cap_verts, long long cap_quads, long long *n_verts, long long *n_quads)
+{
+    if (!c) return fail(SN_ERR_ARG, "null context");
+    if (!cfg || !n_verts || !n_quads) return fail(SN_ERR_ARG, "null argument");
+    *n_verts = *n_quads = 0;
+    if (cfg->radius < 1 || cfg->radius > 3) return fail(SN_ERR_ARG, "radius = %d: the window radius is 1, 2 or 3 cells", cfg->radius);
+    if (cfg->reach < 0 || cfg->reach > cfg->radius) return fail(SN_ERR_ARG, "reach = %d must lie in 0 .. radius = %d", cfg->reach, cfg->radius);
+    if (cfg->stride_vox < 1) return fail(SN_ERR_ARG, "stride_vox = %d must be a positive number of voxels", cfg->stride_vox);
+    if (!std::isfinite(cfg->resol) || !std::isfinite(cfg->origin[0]) || !std::isfinite(cfg->origin[1]) || !std::isfinite(cfg->origin[2]))
+        return fail(SN_ERR_ARG, "origin and resol must be finite");
+    if (n < 0) return fail(SN_ERR_ARG, "n must be >= 0");
+    if (cap_verts < 0 || cap_quads < 0) return fail(SN_ERR_ARG, "cap_verts and cap_quads must be >= 0");
+    return SN_OK;
+}
+
+int ms_check_total(int n, long long total)
+{
+    if (total > MS_MAX_VOXELS) return fail(SN_ERR_ARG, "total = %lld: at most %lld voxels", total, MS_MAX_VOXELS);
+    return pl_check_counts(n, total);
+}
+
+// The whole computation on device-resident lists. out_host: the outputs are host arrays (staged through temporary device buffers).
+int ms_run(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long total, const int64_t *off, const unsigned char *ijk, const uint32_t *cube_ijk,
+           const unsigned char *mask, const float *normals, long long cap_verts, long long cap_quads, bool out_host, MSOut o, long long *n_verts,
+           long long *n_quads)
+{
+    // ---- stage 1: the cell table (owners) and the brick table (occupancy of P) -------------------------------------------------------------
+    const unsigned cap = (unsigned)table_cap((unsigned long long)total, 2, 64);
+    MSIn in;
+    memset(&in, 0, sizeof in);
+    MSTab tb;
+    memset(&tb, 0, sizeof tb);
+    auto layout1 = [&](Carve &w) {
+        in.cnt = w.get<unsigned long long>(MS_CNT_WORDS);
+        in.cube_of = w.get<int>((size_t)total);
+        tb.cell = w.get<unsigned long long>(2 * (size_t)cap);
+        tb.brick = w.get<unsigned long long>(2 * (size_t)cap);
+    };
+    Carve measure;
+    layout1(measure);
+    int rc = dev_reserve(c, c->ms_ws, measure.off + 256);
+    if (rc != SN_OK) return rc;
+    Carve w1{c->ms_ws.as<unsigned char>()};
+    layout1(w1);
+    in.off = off; in.ijk = ijk; in.cube_ijk = cube_ijk; in.mask = mask; in.normals = normals; in.total = total; in.n = n; in.stride = cfg->stride_vox;
+    tb.cmask = tb.bmask = cap - 1;
+    unsigned long long cnt[MS_CNT_WORDS] = {0, 0, 0, 0};
+    HIPCHK(hipMemsetAsync(in.cnt, 0, sizeof cnt, c->stream));
+    {
+        ProfScope ps(c, "ms_check", 0, (double)n * 8.0);
+        hipLaunchKernelGGL(ms_check_kernel, dim3((unsigned)(n / MS_NT + 1)), dim3(MS_NT), 0, c->stream, off, n, total, in.cnt);
+        HIPCHK(hipGetLastError());
+    }
+    if (total > 0) {
+        ProfScope ps(c, "ms_cells", 0, (double)total * 28.0 + (double)cap * 32.0);
+        HIPCHK(hipMemsetAsync(tb.cell, 0, sizeof(unsigned long long) * 2 * (size_t)cap, c->stream));
+        HIPCHK(hipMemsetAsync(tb.brick, 0, sizeof(unsigned long long) * 2 * (size_t)cap, c->stream));
+        hipLaunchKernelGGL(ms_insert_kernel, dim3(blocks(total)), dim3(MS_NT), 0, c->stream, in, tb);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(cnt, in.cnt, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (cnt[MS_CNT_FLAGS] & MS_FLAG_TABLE) return fail(SN_ERR_ARG, "offsets table does not start at 0, decreases, or does not end at total = %lld", total);
+    if (cnt[MS_CNT_FLAGS] & MS_FLAG_NORMAL) return fail(SN_ERR_ARG, "a masked voxel's normal has a component that is not finite or exceeds 2 in magnitude");
+    if (cnt[MS_CNT_FLAGS] & MS_FLAG_CELL)
+        return fail(SN_ERR_ARG, "a masked voxel's world cell (cube_ijk * %d + vxl_ijk) plus %d reaches 2^%d on an axis", cfg->stride_vox, MS_MARGIN, NM_AXIS_BITS);
+    if (total == 0) return SN_OK;
+    {
+        ProfScope ps(c, "ms_bricks", 0, (double)total * 20.0 + (double)cap * 8.0);
+        hipLaunchKernelGGL(ms_bricks_kernel, dim3(blocks(total)), dim3(MS_NT), 0, c->stream, in, tb);
+        hipLaunchKernelGGL(ms_count_kernel, dim3(blocks(cap)), dim3(MS_NT), 0, c->stream, (const unsigned long long *)tb.brick, cap, in.cnt + MS_CNT_BRICKS);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(cnt, in.cnt, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const unsigned long long nb = cnt[MS_CNT_BRICKS];
+    if (nb == 0) return SN_OK;                       // no oriented cell: no mesh
+    if (nb > MS_MAX_BRICKS) return fail(SN_ERR_ARG, "the oriented cells occupy %llu bricks of 4^3 cells: at most %llu", nb, MS_MAX_BRICKS);
+
+    // ---- stage 2: the candidate bricks, sorted and ranked --------------------------------------------------------------------------------------
+    const unsigned kcap = (unsigned)table_cap(27ull * nb, 2, 2 * PC_TILE);
+    unsigned long long *list = nullptr;
+    auto layout2 = [&](Carve &w) {
+        tb.cand = w.get<unsigned long long>(2 * (size_t)kcap);
+        tb.rank = w.get<int>(kcap);
+        list = w.get<unsigned long long>(kcap / 2);  // >= 27 nb keys, a power of two >= PC_TILE: room for the sort's padding
+    };
+    Carve measure2;
+    layout2(measure2);
+    if ((rc = dev_reserve(c, c->ms_tab, measure2.off + 256)) != SN_OK) return rc;
+    Carve w2{c->ms_tab.as<unsigned char>()};
+    layout2(w2);
+    tb.kmask = kcap - 1;
+    {
+        ProfScope ps(c, "ms_cand", 0, (double)cap * 16.0 + (double)kcap * 40.0);
+        HIPCHK(hipMemsetAsync(tb.cand, 0, sizeof(unsigned long long) * 2 * (size_t)kcap, c->stream));
+        hipLaunchKernelGGL(ms_cand_kernel, dim3(blocks(cap)), dim3(MS_NT), 0, c->stream, tb);
+        hipLaunchKernelGGL(ms_list_kernel, dim3(blocks(kcap)), dim3(MS_NT), 0, c->stream, tb, list, in.cnt + MS_CNT_CAND);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(cnt, in.cnt, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const unsigned long long ncu = cnt[MS_CNT_CAND];
+    if (ncu > MS_MAX_CAND)
+        return fail(SN_ERR_ARG, "%llu candidate bricks: at most %llu (vertex and quad indices are int32: no more than 2^31 - 1 of either)", ncu, MS_MAX_CAND);
+    const int nc = (int)ncu;
+    {
+        const long long p2 = (long long)table_cap(ncu, 1, PC_TILE);
+        if (p2 > nc) {
+            ProfScope ps(c, "ms_pad", 0, (double)(p2 - nc) * 8.0);
+            hipLaunchKernelGGL(pc_pad_kernel, dim3(blocks(p2 - nc)), dim3(PC_NT), 0, c->stream, list, (long long)nc, p2);
+        }
+        if ((rc = pc_sort(c, list, p2)) != SN_OK) return rc;      // (its own profile tag, pc_sort)
+        ProfScope ps(c, "ms_rank", 0, (double)nc * 28.0);
+        hipLaunchKernelGGL(ms_rank_kernel, dim3(blocks(nc)), dim3(MS_NT), 0, c->stream, tb, (const unsigned long long *)list, nc);
+        HIPCHK(hipGetLastError());
+    }
+
+    // ---- stage 3: the field, the edges, the counts ---------------------------------------------------------------------------------------------
+    MSField f;
+    memset(&f, 0, sizeof f);
+    int *sums = nullptr;
+    const size_t ns = 64 * (size_t)nc;
+    auto layout3 = [&](Carve &w) {
+        f.F = w.get<long long>(ns);
+        f.W = w.get<int>(ns);
+        f.eflags = w.get<uint8_t>(ns);
+        f.vmask = w.get<unsigned long long>((size_t)nc);
+        f.vstart = w.get<int>((size_t)nc + 1);
+        f.qstart = w.get<int>((size_t)nc + 1);
+        sums = w.get<int>(scan_sums((size_t)nc + 1));
+    };
+    Carve measure3;
+    layout3(measure3);
+    if ((rc = dev_reserve(c, c->ms_field, measure3.off + 256)) != SN_OK) return rc;
+    Carve w3{c->ms_field.as<unsigned char>()};
+    layout3(w3);
+    f.list = list; f.radius = cfg->radius; f.reach = cfg->reach;
+    HIPCHK(hipMemsetAsync(f.vstart + nc, 0, sizeof(int), c->stream));
+    HIPCHK(hipMemsetAsync(f.qstart + nc, 0, sizeof(int), c->stream));
+    {
+        ProfScope ps(c, "ms_field", 0, (double)ns * 12.0 + (double)nc * 27.0 * 16.0);
+        hipLaunchKernelGGL(ms_field_kernel, dim3((unsigned)nc), dim3(64), 0, c->stream, tb, f, normals);
+        HIPCHK(hipGetLastError());
+    }
+    {
+        ProfScope ps(c, "ms_edges", 0, (double)ns * 14.0);
+        hipLaunchKernelGGL(ms_edge_kernel, dim3((unsigned)nc), dim3(64), 0, c->stream, tb, f);
+        hipLaunchKernelGGL(ms_vcount_kernel, dim3((unsigned)nc), dim3(64), 0, c->stream, tb, f);
+        HIPCHK(hipGetLastError());
+    }
+    int nv = 0, nq = 0;
+    {
+        ProfScope ps(c, "ms_scan", 0, (double)nc * 40.0);
+        if ((rc = scan_exclusive(c, f.vstart, f.vstart, nc + 1, sums)) != SN_OK) return rc;      // vstart[nc] = number of vertices
+        if ((rc = scan_exclusive(c, f.qstart, f.qstart, nc + 1, sums)) != SN_OK) return rc;
+    }
+    HIPCHK(hipMemcpyAsync(&nv, f.vstart + nc, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&nq, f.qstart + nc, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *n_verts = nv; *n_quads = nq;
+    if (nv > cap_verts || nq > cap_quads)
+        return fail(SN_ERR_ARG, "the outputs hold %lld vertices and %lld quads, %d and %d are needed", cap_verts, cap_quads, nv, nq);
+    if (nv == 0) return SN_OK;
+
+    // ---- emit ------------------------------------------------------------------------------------------------------------------------------------
+    TmpDev t;
+    SyncOnExit sync{c};
+    MSOut h = o;                                     // the caller's host arrays
+    if (out_host) {
+        if (h.verts_mm) o.verts_mm = t.out<float>(3 * (size_t)nv);
+        if (h.verts_lattice) o.verts_lattice = t.out<double>(3 * (size_t)nv);
+        if (h.vert_cell) o.vert_cell = t.out<int32_t>(3 * (size_t)nv);
+        if (h.vert_src) o.vert_src = t.out<int64_t>((size_t)nv);
+        if (h.quads) o.quads = t.out<int32_t>(4 * (size_t)nq);
+        if (!t.ok) return fail(SN_ERR_NOMEM, "sn_mesh: device allocation failed");
+    }
+    for (int d = 0; d < 3; ++d) o.origin[d] = cfg->origin[d];
+    o.resol = cfg->resol;
+    if (o.verts_mm || o.verts_lattice || o.vert_cell || o.vert_src) {
+        ProfScope ps(c, "ms_vertices", 0, (double)nv * 56.0 + (double)ns * 9.0);
+        hipLaunchKernelGGL(ms_vemit_kernel, dim3((unsigned)nc), dim3(64), 0, c->stream, tb, f, o);
+        HIPCHK(hipGetLastError());
+    }
+    if (o.quads) {
+        ProfScope ps(c, "ms_quads", 0, (double)nq * 16.0 + (double)ns * 9.0);
+        hipLaunchKernelGGL(ms_qemit_kernel, dim3((unsigned)nc), dim3(64), 0, c->stream, tb, f, o);
+        HIPCHK(hipGetLastError());
+    }
+    if (out_host) {
+        if (h.verts_mm) HIPCHK(hipMemcpyAsync(h.verts_mm, o.verts_mm, sizeof(float) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+        if (h.verts_lattice) HIPCHK(hipMemcpyAsync(h.verts_lattice, o.verts_lattice, sizeof(double) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+        if (h.vert_cell) HIPCHK(hipMemcpyAsync(h.vert_cell, o.vert_cell, sizeof(int32_t) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+        if (h.vert_src) HIPCHK(hipMemcpyAsync(h.vert_src, o.vert_src, sizeof(int64_t) * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+        if (h.quads && nq) HIPCHK(hipMemcpyAsync(h.quads, o.quads, sizeof(int32_t) * 4 * (size_t)nq, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return SN_OK;
+}
+
+MSOut ms_outputs(float *verts_mm, double *verts_lattice, int32_t *vert_cell, int64_t *vert_src, int32_t *quads)
+{
+    MSOut o;
+    memset(&o, 0, sizeof o);
+    o.verts_mm = verts_mm; o.verts_lattice = verts_lattice; o.vert_cell = vert_cell; o.vert_src = vert_src; o.quads = quads;
+    return o;
+}
+
+}  // namespace
+
+extern "C" int sn_mesh_dev(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long total, const int64_t *offsets_dev, const unsigned char *ijk_dev,
+                           const uint32_t *cube_ijk_dev, const unsigned char *mask_dev, const float *normals_dev, long long cap_verts, long long cap_quads,
+                           float *verts_mm_dev, double *verts_lattice_dev, int32_t *vert_cell_dev, int64_t *vert_src_dev, int32_t *quads_dev,
+                           long long *n_verts, long long *n_quads)
+{
+    int rc;
+    if ((rc = ms_check_args(c, n, cfg, cap_verts, cap_quads, n_verts, n_quads)) != SN_OK) return rc;
+    if ((rc = ms_check_total(n, total)) != SN_OK) return rc;
+    if (n == 0) return SN_OK;
+    if (!offsets_dev || !cube_ijk_dev || (total > 0 && (!ijk_dev || !mask_dev || !normals_dev))) return fail(SN_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(c->device));
+    return ms_run(c, n, cfg, total, offsets_dev, ijk_dev, cube_ijk_dev, mask_dev, normals_dev, cap_verts, cap_quads, false,
+                  ms_outputs(verts_mm_dev, verts_lattice_dev, vert_cell_dev, vert_src_dev, quads_dev), n_verts, n_quads);
+}
+
+extern "C" int sn_mesh(sn_ctx *c, int n, const sn_mesh_cfg *cfg, const int64_t *offsets, const unsigned char *ijk, const uint32_t *cube_ijk,
+                       const unsigned char *mask, const float *normals, long long cap_verts, long long cap_quads, float *verts_mm, double *verts_lattice,
+                       int32_t *vert_cell, int64_t *vert_src, int32_t *quads, long long *n_verts, long long *n_quads)
+{
+    int rc;
+    if ((rc = ms_check_args(c, n, cfg, cap_verts, cap_quads, n_verts, n_quads)) != SN_OK) return rc;
+    if (!offsets) return fail(SN_ERR_ARG, "null argument");
+    if ((rc = pl_check_host_offsets(n, offsets)) != SN_OK || n == 0) return rc;      // (no cubes: the table is its single entry)
+    const long long total = offsets[n];
+    if ((rc = ms_check_total(n, total)) != SN_OK) return rc;
+    if (!cube_ijk || (total > 0 && (!ijk || !mask || !normals))) return fail(SN_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(c->device));
+    TmpDev t;
+    SyncOnExit sync{c};
+    const size_t N = (size_t)n, T = (size_t)total;
+    const int64_t *d_off = t.up(c, offsets, N + 1);
+    const uint32_t *d_cube = t.up(c, cube_ijk, 3 * N);
+    const unsigned char *d_ijk = t.up(c, ijk, 3 * T), *d_mask = t.up(c, mask, T);
+    const float *d_nrm = t.up(c, normals, 3 * T);
+    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_mesh: device allocation failed");
+    return ms_run(c, n, cfg, total, d_off, d_ijk, d_cube, d_mask, d_nrm, cap_verts, cap_quads, true,
+                  ms_outputs(verts_mm, verts_lattice, vert_cell, vert_src, quads), n_verts, n_quads);
+}

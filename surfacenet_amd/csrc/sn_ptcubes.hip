@@ -16,20 +16,6 @@ struct SyncOnExit {                                  // temporary device buffers
 
 unsigned blocks(long long n) { return (unsigned)((n + PC_NT - 1) / PC_NT); }
 
-// ascending sort of list[0, n), n a power of two >= PC_TILE
-int pc_sort(sn_ctx *c, unsigned long long *list, long long n)
-{
-    ProfScope ps(c, "pc_sort", 0, 0.0);
-    hipLaunchKernelGGL(pc_bitonic_tile_kernel, dim3((unsigned)(n / PC_TILE)), dim3(PC_NT), 0, c->stream, list, 2ll, (long long)PC_TILE);
-    for (long long k = 2 * PC_TILE; k <= n; k <<= 1) {
-        for (long long j = k / 2; j >= PC_TILE; j >>= 1)
-            hipLaunchKernelGGL(pc_bitonic_global_kernel, dim3(blocks(n / 2)), dim3(PC_NT), 0, c->stream, list, n, j, k);
-        hipLaunchKernelGGL(pc_bitonic_tile_kernel, dim3((unsigned)(n / PC_TILE)), dim3(PC_NT), 0, c->stream, list, k, k);
-    }
-    HIPCHK(hipGetLastError());
-    return SN_OK;
-}
-
 int pc_check_cfg(const sn_ptcubes_cfg *cfg, long long n, long long cap, const long long *n_cells)
 {
     if (!cfg || !n_cells) return fail(SN_ERR_ARG, "null argument");

@@ -1,0 +1,120 @@
+"""Surface mesh of the oriented output cloud on the MI355X: surface nets on the world voxel lattice.
+
+    extract_mesh       vertices, quads and per-vertex source voxels from the per-cube lists plus normals.estimate_normals' normal_list
+    triangulate        quads -> triangles
+    save_mesh_2ply     binary little-endian PLY of a quad or triangle mesh
+
+The reference ends in a point cloud: its utils/mesh_util.py only reads and writes OBJ files. The mesher looks at the scene on the world voxel
+lattice - cell = cube_ijk * stride_vox + vxl_ijk - across cubes, in one GPU call (surfacenet_amd/csrc/mesh.h). Every argument check runs before
+the library is touched.
+"""
+import numpy as np
+
+from . import runtime
+from .normals import _pack, _stride
+
+
+def lattice_origin(cube_ijk_np, param_np, stride_vox):
+    """-> (origin (3,) float64, resol float): the mm position of world cell (0,0,0), float64(xyz[0]) - float64(cube_ijk[0] * stride_vox) *
+    float64(resol[0]). ValueError when the cubes' resol differ or a cube's own origin lies more than 0.05 * resol from it."""
+    resol32 = np.asarray(param_np['resol'], dtype=np.float32).reshape(-1)
+    if not np.all(resol32 == resol32[0]):
+        raise ValueError("cubes of different resol do not share one voxel lattice")
+    resol = float(np.float64(resol32[0]))
+    if not (np.isfinite(resol) and resol > 0):
+        raise ValueError("resol = %r must be finite and > 0" % (resol,))
+    cube = np.asarray(cube_ijk_np, dtype=np.int64).reshape(-1, 3)
+    origins = np.asarray(param_np['xyz'], dtype=np.float32).reshape(-1, 3).astype(np.float64) - (cube * int(stride_vox)).astype(np.float64) * resol
+    if not np.isfinite(origins).all():
+        raise ValueError("a cube's xyz is not finite")
+    dev = np.abs(origins - origins[0]).max()
+    if dev > 0.05 * resol:
+        raise ValueError("the cubes do not share one voxel lattice: their origins differ by up to %g mm (resol %g)" % (dev, resol))
+    return origins[0].copy(), resol
+
+
+def empty_mesh():
+    """extract_mesh's result for a scene without cubes."""
+    return dict(vertices=np.zeros((0, 3), np.float32), quads=np.zeros((0, 4), np.int32), vert_src=np.zeros((0,), np.int64),
+                vert_lattice=np.zeros((0, 3), np.float64))
+
+
+def extract_mesh(cube_ijk_np, vxl_ijk_list, vxl_mask_list, normal_list, param_np, stride_vox, radius=2, reach=0):
+    """cube_ijk_np (N,3), vxl_ijk_list[i] (iN,3) uint8, vxl_mask_list[i] (iN,) bool, normal_list[i] (iN,3) float32 as normals.estimate_normals
+    returns it (zero = no normal), param_np the cube table ('xyz', 'resol'), stride_vox = cube_Dcenter * cube_overlapping_ratio; radius 1..3 the
+    window of the implicit function, reach 0..radius how far from an oriented cell a face may lie.
+    -> dict: vertices (V,3) float32 in mm, quads (Q,4) int32 (counter-clockwise seen from outside), vert_src (V,) int64 index into the
+    concatenated voxel lists of the voxel whose colour / normal a vertex takes (-1: none), vert_lattice (V,3) float64 in cells."""
+    stride = _stride(stride_vox)
+    if int(radius) != radius or not 1 <= int(radius) <= 3:
+        raise ValueError("radius = %r: the window radius is 1, 2 or 3 cells" % (radius,))
+    if int(reach) != reach or not 0 <= int(reach) <= int(radius):
+        raise ValueError("reach = %r must be an integer in 0 .. radius = %d" % (reach, int(radius)))
+    offsets, ijk, mask = _pack(cube_ijk_np, vxl_ijk_list, vxl_mask_list)
+    n = len(vxl_ijk_list)
+    if len(normal_list) != n or len(param_np) != n:
+        raise ValueError("%d cubes: %d normal lists, %d parameter rows" % (n, len(normal_list), len(param_np)))
+    for i, (a, nrm) in enumerate(zip(vxl_ijk_list, normal_list)):
+        if np.asarray(nrm).shape != (len(a), 3):
+            raise ValueError("cube %d: %d voxels, normals of shape %r" % (i, len(a), np.asarray(nrm).shape))
+    if n == 0:
+        return empty_mesh()
+    normals = np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1, 3) for a in normal_list])
+    sel = normals[mask]
+    if not np.isfinite(sel).all() or (np.abs(sel) > 2).any():
+        raise ValueError("a masked voxel's normal is not finite or has a component beyond 2 in magnitude")
+    cube = np.asarray(cube_ijk_np, dtype=np.int64).reshape(n, 3)
+    if cube.min() < 0:
+        raise ValueError("cube ijk must be >= 0")
+    if mask.any():
+        top = (cube[np.repeat(np.arange(n), np.diff(offsets))[mask]] * stride + ijk[mask].astype(np.int64)).max()
+        if top + 8 >= 1 << 21:
+            raise ValueError("a masked voxel's world cell plus 8 reaches 2^21")
+    origin, resol = lattice_origin(cube, param_np, stride)
+    r = runtime.any_context().mesh(offsets, ijk, cube, mask, stride, normals, radius=int(radius), reach=int(reach), origin=origin, resol=resol)
+    return dict(vertices=r["verts_mm"], quads=r["quads"], vert_src=r["vert_src"], vert_lattice=r["verts_lattice"])
+
+
+def triangulate(quads):
+    """(Q,4) -> (2Q,3): triangles (0,1,2) and (0,2,3) of every quad, in quad order."""
+    q = np.asarray(quads).reshape(-1, 4)
+    return np.stack([q[:, [0, 1, 2]], q[:, [0, 2, 3]]], axis=1).reshape(-1, 3)
+
+
+def save_mesh_2ply(path, vertices, faces, normal_np=None, rgb_np=None):
+    """Binary little-endian PLY: vertices (V,3) float32 x y z [+ nx ny nz float32] [+ red green blue uchar], faces (F,3) or (F,4) as
+    `property list uchar int vertex_indices`."""
+    v = np.asarray(vertices, dtype=np.float32).reshape(-1, 3)
+    f = np.asarray(faces)
+    if f.ndim != 2 or f.shape[1] not in (3, 4):
+        raise ValueError("faces must be (F,3) or (F,4)")
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError("a face names a vertex outside [0, %d)" % v.shape[0])
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    header = ["ply", "format binary_little_endian 1.0", "element vertex %d" % v.shape[0], "property float x", "property float y", "property float z"]
+    if normal_np is not None:
+        nrm = np.asarray(normal_np, dtype=np.float32).reshape(-1, 3)
+        if nrm.shape[0] != v.shape[0]:
+            raise ValueError("%d vertices, %d normals" % (v.shape[0], nrm.shape[0]))
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += ["property float nx", "property float ny", "property float nz"]
+    if rgb_np is not None:
+        rgb = np.asarray(rgb_np, dtype=np.uint8).reshape(-1, 3)
+        if rgb.shape[0] != v.shape[0]:
+            raise ValueError("%d vertices, %d colours" % (v.shape[0], rgb.shape[0]))
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        header += ["property uchar red", "property uchar green", "property uchar blue"]
+    header += ["element face %d" % f.shape[0], "property list uchar int vertex_indices", "end_header"]
+    rec = np.zeros((v.shape[0],), dtype=fields)
+    rec["x"], rec["y"], rec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normal_np is not None:
+        rec["nx"], rec["ny"], rec["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
+    if rgb_np is not None:
+        rec["red"], rec["green"], rec["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    k = f.shape[1]
+    frec = np.zeros((f.shape[0],), dtype=[("n", "u1"), ("v", "<i4", (k,))])
+    frec["n"], frec["v"] = k, f.astype(np.int32)
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(rec.tobytes())
+        fh.write(frec.tobytes())

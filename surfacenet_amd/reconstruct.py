@@ -564,7 +564,8 @@ def reconstruct_scene(images_list, cameraPOs_np, cubes_param_np, cube_D_mm, cube
 
 
 def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, gamma=0.8, beta=6, N_refine_iter=8, init_probThresh=0.5,
-                   max_probThresh=0.9, keep_iterations=False, cameraTs_np=None, cube_overlapping_ratio=0.5, unique=False):
+                   max_probThresh=0.9, keep_iterations=False, cameraTs_np=None, cube_overlapping_ratio=0.5, unique=False, mesh=False, mesh_radius=2,
+                   mesh_reach=0, mesh_ply_prefix=None):
     """The reconstruction's last two stages on `reconstruct_scene`'s dict, in memory and on the GPU, as the reference runs them on its files:
       * main_reconstruct.py:172-175  thinning masks (prob >= tau, votes >= gamma * N_vp * 2), then denoise_crossCubes with D_cube = cube_D
       * main.py:37-43 -> utils/adapthresh.py  adaptive thresholding with D_cube = cube_Dcenter, init / max threshold init_probThresh /
@@ -577,10 +578,15 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
     Beyond the reference (nothing is added to the dict without these arguments):
       cameraTs_np (V,3): fixThresh_normal_list, adapt_normal_list - oriented normals of the two denoised masks (normals.estimate_normals with
         the cubes' view pairs out["viewPair_np"], cube stride cube_Dcenter * cube_overlapping_ratio), ready for save_sparseCubes_2ply(normal_list=)
-      unique=True: fixThresh_unique_list, adapt_unique_list - the two denoised masks with every world voxel kept once (normals.unique_voxels)."""
+      unique=True: fixThresh_unique_list, adapt_unique_list - the two denoised masks with every world voxel kept once (normals.unique_voxels).
+      mesh=True (needs cameraTs_np): fixThresh_mesh, adapt_mesh - mesh.extract_mesh of the two denoised masks with their
+        normal lists (window mesh_radius, mesh_reach), each a dict of vertices, quads, vert_src, vert_lattice; with mesh_ply_prefix also written
+        as <prefix>fixThresh_mesh.ply / <prefix>adapt_mesh.ply (quads, per-vertex normals, colours from out["rgb_list"] when it is there)."""
     from . import adapthresh, denoising, sparseCubes
     from . import normals as _normals
     N_vp = int(N_viewPairs4inference)
+    if mesh and cameraTs_np is None:
+        raise ValueError("mesh=True needs cameraTs_np: the mesher reads the oriented normals")
     extras = cameraTs_np is not None or unique
     stride_vox = _normals.stride_voxels(cube_Dcenter, cube_overlapping_ratio) if extras else None      # (fails here, before any stage has run)
     pred_l, ijk_l, votes_l = out["prediction_list"], out["vxl_ijk_list"], out["rayPooling_votes_list"]
@@ -594,6 +600,9 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
         res.update(fixThresh_normal_list=[], adapt_normal_list=[])
     if unique:
         res.update(fixThresh_unique_list=[], adapt_unique_list=[])
+    if mesh:
+        from . import mesh as _mesh
+        res.update(fixThresh_mesh=_mesh.empty_mesh(), adapt_mesh=_mesh.empty_mesh())
     if n == 0:
         return res
     cube_ijk = out["cube_ijk_np"]
@@ -620,6 +629,17 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
             res[name + "_normal_list"] = _normals.estimate_normals(cube_ijk, ijk_l, masks, out["param_np"], out["viewPair_np"], cameraTs_np, stride_vox)
         if unique:
             res[name + "_unique_list"] = _normals.unique_voxels(cube_ijk, ijk_l, masks, stride_vox)
+        if mesh:
+            m = _mesh.extract_mesh(cube_ijk, ijk_l, masks, res[name + "_normal_list"], out["param_np"], stride_vox, mesh_radius, mesh_reach)
+            res[name + "_mesh"] = m
+            if mesh_ply_prefix is not None:
+                src = m["vert_src"]
+                nrm = np.concatenate([np.asarray(a, np.float32).reshape(-1, 3) for a in res[name + "_normal_list"]])[src]
+                rgb = np.concatenate([np.asarray(a, np.uint8).reshape(-1, 3) for a in out["rgb_list"]])[src] if out.get("rgb_list") else None
+                nrm[src < 0] = 0                     # (mesh_reach > 0: a vertex with no oriented cell beside it: no normal, black)
+                if rgb is not None:
+                    rgb[src < 0] = 0
+                _mesh.save_mesh_2ply("%s%s_mesh.ply" % (mesh_ply_prefix, name), m["vertices"], m["quads"], normal_np=nrm, rgb_np=rgb)
     return res
 
 
