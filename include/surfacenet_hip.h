@@ -28,7 +28,8 @@ extern "C" {
 /* Added since, without a version change (additions only): sn_ptcubes, sn_ptcubes_dev, sn_ptcubes_sparse_dev and sn_ptcubes_cfg - the
  * point-seeded cube list; sn_normals, sn_normals_dev, sn_unique_voxels, sn_unique_voxels_dev and sn_normals_cfg - oriented normals and
  * de-duplication of the output cloud; sn_gt_bind, sn_gt_bind_dev, sn_gt_cubes, sn_gt_cubes_dev, sn_weighted_accuracy and
- * sn_weighted_accuracy_dev - the ground-truth mode; sn_mesh, sn_mesh_dev and sn_mesh_cfg - the surface-nets mesh of the oriented cloud. */
+ * sn_weighted_accuracy_dev - the ground-truth mode; sn_mesh, sn_mesh_dev and sn_mesh_cfg - the surface-nets mesh of the oriented cloud;
+ * sn_mesh_sample and sn_mesh_sample_dev - surface samples of a triangle mesh. */
 
 /* The library is built with -fvisibility=hidden: the functions below are its WHOLE dynamic symbol table
  * (tests/test_abi.py compares `nm -D` with this header). */
@@ -305,6 +306,24 @@ SN_API int sn_mesh_dev(sn_ctx *ctx, int n, const sn_mesh_cfg *cfg, long long tot
                        const uint32_t *cube_ijk_dev, const unsigned char *mask_dev, const float *normals_dev, long long cap_verts, long long cap_quads,
                        float *verts_mm_dev, double *verts_lattice_dev, int32_t *vert_cell_dev, int64_t *vert_src_dev, int32_t *quads_dev,
                        long long *n_verts, long long *n_quads);
+
+/* ---- surface samples of a triangle mesh at the evaluation density ----------------------------------------------------
+ * The first step of the DTU protocol for a mesh (sample, reduce, PointCompare). verts (n_verts,3) float64, faces (n_faces,3) int32, dst finite
+ * and > 0. Float arithmetic is fp64 without contraction; the squared length of an edge e is (ex*ex + ey*ey) + ez*ez. For face f with corners A,
+ * B, C in face order: L2 = the largest squared length of B-A, C-A, C-B; q = L2 / (dst*dst); n_f = the smallest integer >= 1 with
+ * float64(n*n) >= q. The face yields n_f^2 samples, the centroids of its n_f^2 congruent sub-triangles: for k in [0, n^2), t = isqrt(k),
+ * w = k - t^2, c = w >> 1; w even: beta = 3t - 3c + 1, gamma = 3c + 1; w odd: beta = 3t - 3c - 1, gamma = 3c + 2; u = float64(beta) /
+ * float64(3n), v = float64(gamma) / float64(3n); per component p = A + ((B-A)*u + (C-A)*v). Every point of the face lies within 2/3 dst of
+ * a sample. Samples come in face order, then k: points (M,3) float64, tri (M) int32 the face of each sample, M = sum n_f^2; either output may
+ * be NULL. The result equals the numpy restatement tests/meshsample_ref.py bit for bit.
+ *   SN_ERR_ARG, nothing written, the error text naming the first offending face: a face index outside [0, n_verts); a non-finite coordinate
+ *   of a referenced vertex; n_f > 32768; M > 2^31 - 1; also dst not finite or not > 0. A degenerate face is legal (n = 1, one sample at A);
+ *   n_faces = 0 gives M = 0. The outputs hold cap_points samples; *n_points (required) receives M. When cap_points < M nothing is written,
+ *   *n_points = M and the status is SN_ERR_ARG. Deterministic; the workspace belongs to the context; both forms return when the work is done. */
+SN_API int sn_mesh_sample(sn_ctx *ctx, int n_verts, const double *verts, int n_faces, const int32_t *faces, double dst, long long cap_points,
+                          double *points, int32_t *tri, long long *n_points);
+SN_API int sn_mesh_sample_dev(sn_ctx *ctx, int n_verts, const double *verts_dev, int n_faces, const int32_t *faces_dev, double dst,
+                              long long cap_points, double *points_dev, int32_t *tri_dev, long long *n_points);
 
 /* ---- DTU point-cloud evaluation (experiments/DTU/eval_ply.m -> PointCompareMain of the DTU kit) ----------------------
  * Points are (n,3) float64, row-major, finite. d^2 = (dx*dx + dy*dy) + dz*dz in float64 without contraction: the results are those of the numpy

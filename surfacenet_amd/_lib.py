@@ -21,7 +21,7 @@ ABI_SYMBOLS = [
     "sn_ray_pool", "sn_ray_pool_dev", "sn_dense2sparse", "sn_dense2sparse_dev",
     "sn_denoise", "sn_denoise_dev", "sn_adapthresh", "sn_adapthresh_dev",
     "sn_normals", "sn_normals_dev", "sn_unique_voxels", "sn_unique_voxels_dev",
-    "sn_mesh", "sn_mesh_dev",
+    "sn_mesh", "sn_mesh_dev", "sn_mesh_sample", "sn_mesh_sample_dev",
     "sn_point_reduce", "sn_nn_dist2", "sn_point_flags",
     "sn_ptcubes", "sn_ptcubes_dev", "sn_ptcubes_sparse_dev",
     "sn_gt_bind", "sn_gt_bind_dev", "sn_gt_cubes", "sn_gt_cubes_dev", "sn_weighted_accuracy", "sn_weighted_accuracy_dev",
@@ -140,6 +140,9 @@ def load():
         "sn_mesh": (c_int, [c_void_p, c_int, P(MeshCfg)] + [c_void_p] * 5 + [ctypes.c_longlong] * 2 + [c_void_p] * 5 + [P(ctypes.c_longlong)] * 2),
         "sn_mesh_dev": (c_int, [c_void_p, c_int, P(MeshCfg), ctypes.c_longlong] + [c_void_p] * 5 + [ctypes.c_longlong] * 2 + [c_void_p] * 5 +
                         [P(ctypes.c_longlong)] * 2),
+        "sn_mesh_sample": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_double, ctypes.c_longlong, c_void_p, c_void_p, P(ctypes.c_longlong)]),
+        "sn_mesh_sample_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_double, ctypes.c_longlong, c_void_p, c_void_p,
+                                       P(ctypes.c_longlong)]),
         "sn_point_reduce": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_double, c_void_p, P(c_int)]),
         "sn_nn_dist2": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_double, c_void_p]),
         "sn_point_flags": (c_int, [c_void_p, ctypes.c_longlong] + [c_void_p] * 4 + [ctypes.c_double] + [c_void_p] * 3),

@@ -558,6 +558,45 @@ class Context(object):
                 self.dev_free(b)
         return out
 
+    def mesh_sample(self, vertices, faces, dst, cap=None, device=False):
+        """Surface samples of a triangle mesh (sn_mesh_sample): vertices (V,3) float64, faces (F,3) int32, dst the
+        sampling density -> (points (M,3) float64, tri (M,) int32 the face of each sample). cap = the samples the first call's arrays hold (a
+        guess from the face count when None); a short guess costs one retry with the exact count. device=True stages the mesh in device memory
+        here and runs sn_mesh_sample_dev on it: the same result."""
+        v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
+        f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+        V, F = v.shape[0], f.shape[0]
+        cap = 16 * F + 64 if cap is None else int(cap)
+        m = ctypes.c_longlong(0)
+        staged = []
+        try:
+            if device:
+                for a in (v, f):
+                    staged.append(self.dev_alloc(max(a.nbytes, 16)))
+                    if a.nbytes:
+                        self.h2d(staged[-1], a)
+            for attempt in range(2):
+                points, tri = np.empty((cap, 3), np.float64), np.empty((cap,), np.int32)
+                if device:
+                    bufs = [self.dev_alloc(max(points.nbytes, 16)), self.dev_alloc(max(tri.nbytes, 16))]
+                    staged.extend(bufs)
+                    rc = self._lib.sn_mesh_sample_dev(self._h, V, staged[0], F, staged[1], float(dst), cap, bufs[0], bufs[1], ctypes.byref(m))
+                else:
+                    rc = self._lib.sn_mesh_sample(self._h, V, _lib.ptr(v), F, _lib.ptr(f), float(dst), cap, _lib.ptr(points), _lib.ptr(tri), ctypes.byref(m))
+                if rc == -1 and attempt == 0 and m.value > cap:
+                    cap = m.value                    # the count says what is needed: one retry at that size
+                    continue
+                _lib.check(rc)
+                break
+            M = m.value
+            if device and M:
+                self.d2h(points[:M], staged[-2])
+                self.d2h(tri[:M], staged[-1])
+        finally:
+            for b in staged:
+                self.dev_free(b)
+        return points[:M].copy(), tri[:M].copy()
+
     @staticmethod
     def _points(xyz):
         return np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))

@@ -7,6 +7,9 @@ MI355X. DESIGN.md section 4.7 states the contract and what of the kit (not part 
     point_compare    PointCompareMain: the BaseEval fields
     eval_acc_compl   eval_ply.m's four numbers from a BaseEval
     eval_ply         the drop-in for eval_ply.m: the DTU folder's files in, BaseEval .mat out, the four numbers back
+    read_ply_mesh    a PLY mesh's vertices and faces (what mesh.save_mesh_2ply writes)
+    mesh_compare     point_compare for a mesh: its surface sampled at the evaluation density first
+    eval_mesh_ply    eval_ply for a mesh PLY
 
 The reduction, the distances and the mask / plane flags run on the GPU (surfacenet_amd/csrc/pointeval.h); the statistics are numpy on the
 host. A scene is evaluated in memory with sparseCubes.sparse_xyz (the points save_sparseCubes_2ply would write). Only the .mat I/O of
@@ -22,7 +25,9 @@ _PLY_SCALARS = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short
                 "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def _ply_header(f):
+def _ply_header(f, lists=None):
+    """-> (format, [(element, count, [(property, numpy type or None for a list)])]); the (count type, item type) of every list property are
+    appended to `lists`, in file order, when it is given."""
     if f.readline().strip() != b"ply":
         raise ValueError("not a PLY file")
     fmt, elements = None, []
@@ -42,6 +47,8 @@ def _ply_header(f):
         elif tok[0] == "property":
             if tok[1] == "list":
                 elements[-1][2].append((tok[4], None))
+                if lists is not None:
+                    lists.append((_PLY_SCALARS[tok[2]], _PLY_SCALARS[tok[3]]))
             else:
                 elements[-1][2].append((tok[2], _PLY_SCALARS[tok[1]]))
 
@@ -77,6 +84,83 @@ def read_ply_xyz(path):
         v = np.frombuffer(body, dtype=dt, count=count, offset=skip)
         cols = [v[k].astype(v[k].dtype.newbyteorder("=")) for k in ("x", "y", "z")]
     return np.stack(cols, axis=1) if count else np.zeros((0, 3), np.result_type(*cols))
+
+
+def read_ply_mesh(path):
+    """-> (vertices (V,3), faces (F,3) or (F,4) int32) of a PLY mesh: the vertex element's x, y, z (dtype as stored) and the one list property
+    of the face element, in ascii and both binary byte orders; what mesh.save_mesh_2ply writes. Scalar properties beside them are skipped.
+    ValueError for faces of mixed size, faces that are neither triangles nor quads, or a list property anywhere else before the faces."""
+    lists = []
+    with open(path, "rb") as f:
+        fmt, elements = _ply_header(f, lists)
+        body = f.read()
+    if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
+        raise ValueError("unknown PLY format %r" % fmt)
+    ascii_ = fmt == "ascii"
+    end = "<" if fmt == "binary_little_endian" else ">"
+    if ascii_:
+        body = [ln.split() for ln in body.decode("ascii").splitlines() if ln.strip()]
+    pos, verts, faces = 0, None, None                        # pos: bytes (binary) or lines (ascii) consumed
+    for name, count, props in elements:
+        n_lists = sum(t is None for _, t in props)
+        if name == "face" and n_lists == 1:
+            ct, it = lists[0]
+            at = [t is None for _, t in props].index(True)   # scalar properties before the list
+            if count == 0:
+                faces = np.zeros((0, 3), np.int32)
+            elif ascii_:
+                rows = body[pos:pos + count]
+                if len(rows) != count:
+                    raise ValueError("PLY file ends inside the faces")
+                k = int(rows[0][at])
+                if any(len(r) != len(props) + k or int(r[at]) != k for r in rows):
+                    raise ValueError("faces of mixed size")
+                faces = np.asarray([r[at + 1:at + 1 + k] for r in rows], dtype=np.int64)
+            else:
+                head = sum(np.dtype(t).itemsize for _, t in props[:at])
+                if len(body) < pos + head + np.dtype(ct).itemsize:
+                    raise ValueError("PLY file ends inside the faces")
+                k = int(np.frombuffer(body, dtype=end + ct, count=1, offset=pos + head)[0])
+                dt = np.dtype([(p, end + t) if t else (p, [("n", end + ct), ("v", end + it, (k,))]) for p, t in props])
+                if len(body) < pos + count * dt.itemsize:
+                    raise ValueError("faces of mixed size, or a file that ends inside them")
+                rec = np.frombuffer(body, dtype=dt, count=count, offset=pos)[props[at][0]]
+                if (rec["n"] != k).any():
+                    raise ValueError("faces of mixed size")
+                faces = rec["v"].astype(np.int64)
+                pos += count * dt.itemsize
+            if count and faces.shape[1] not in (3, 4):
+                raise ValueError("faces of %d vertices: triangles and quads only" % faces.shape[1])
+            if count and (faces.min() < -(1 << 31) or faces.max() >= 1 << 31):
+                raise ValueError("a face index does not fit int32")
+            faces = np.ascontiguousarray(faces, dtype=np.int32)
+            if ascii_:
+                pos += count
+        elif n_lists:
+            if verts is not None and faces is not None:
+                break
+            raise ValueError("element %r has list properties: unsupported" % name)
+        else:
+            names = [p for p, _ in props]
+            if name == "vertex":
+                if ascii_:
+                    rows = body[pos:pos + count]
+                    if len(rows) != count:
+                        raise ValueError("PLY file ends inside the vertices")
+                    vals = np.asarray(rows, dtype=object).reshape(count, len(props))
+                    cols = [vals[:, names.index(c)].astype(np.float64).astype(dict(props)[c]) for c in ("x", "y", "z")]
+                else:
+                    dt = np.dtype([(p, end + t) for p, t in props])
+                    v = np.frombuffer(body, dtype=dt, count=count, offset=pos)
+                    cols = [v[c].astype(v[c].dtype.newbyteorder("=")) for c in ("x", "y", "z")]
+                verts = np.stack(cols, axis=1) if count else np.zeros((0, 3), np.result_type(*cols))
+            pos += count * (1 if ascii_ else sum(np.dtype(t).itemsize for _, t in props))
+        lists = lists[n_lists:]
+    if verts is None:
+        raise ValueError("PLY file without a vertex element")
+    if faces is None:
+        raise ValueError("PLY file without a face element that holds one list property")
+    return verts, faces
 
 
 def _points(a):
@@ -134,16 +218,50 @@ def eval_ply(cSet, DataInName, EvalName, dataPath, dst=0.2, max_dist=60.0, seed=
     """eval_ply.m (getPaths' dataPath passed in): reads DataInName (PLY), dataPath/Points/stl/stl{cSet:03d}_total.ply,
     dataPath/ObsMask/ObsMask{cSet}_10.mat (BB, Res, Margin, ObsMask) and dataPath/ObsMask/Plane{cSet}.mat (P); writes EvalName (.mat, variable
     BaseEval, point arrays 3 x N as MATLAB holds them); returns the four numbers of eval_acc_compl."""
-    import scipy.io as sio
     Qdata = read_ply_xyz(DataInName)
+    Qstl, m, P = _dtu_files(cSet, dataPath)
+    base = point_compare(Qdata, Qstl, m["ObsMask"], m["BB"], m["Res"], P, dst=dst, max_dist=max_dist, seed=seed, cSet=cSet,
+                         Margin=m["Margin"] if "Margin" in m else None)
+    _save_base_eval(EvalName, base, cSet)
+    return eval_acc_compl(base)
+
+
+def _dtu_files(cSet, dataPath):
+    """The DTU folder's files of scan cSet -> (Qstl, the ObsMask file's variables, P)."""
+    import scipy.io as sio
     Qstl = read_ply_xyz(os.path.join(dataPath, "Points", "stl", "stl%03d_total.ply" % cSet))
     m = sio.loadmat(os.path.join(dataPath, "ObsMask", "ObsMask%d_10.mat" % cSet))
     P = sio.loadmat(os.path.join(dataPath, "ObsMask", "Plane%d.mat" % cSet))["P"]
-    base = point_compare(Qdata, Qstl, m["ObsMask"], m["BB"], m["Res"], P, dst=dst, max_dist=max_dist, seed=seed, cSet=cSet,
-                         Margin=m["Margin"] if "Margin" in m else None)
+    return Qstl, m, P
+
+
+def _save_base_eval(EvalName, base, cSet):
+    import scipy.io as sio
     mat = dict(base)
     mat.update(cSet=float(cSet), Qdata=base["Qdata"].T, Qstl=base["Qstl"].T, GroundPlane=base["GroundPlane"].reshape(4, 1))
     if mat["Margin"] is None:
         del mat["Margin"]
     sio.savemat(EvalName, {"BaseEval": mat})
+
+
+def mesh_compare(vertices, faces, Qstl, obs_mask, BB, Res, plane, dst=0.2, sample_dst=None, max_dist=60.0, seed=0, order=None, cSet=None,
+                 Margin=None):
+    """The DTU practice for a mesh: sample its surface at sample_dst (default dst; mesh.sample_surface), then
+    point_compare on the samples, which reduces them at dst. vertices (V,3), faces (F,3) or (F,4). Returns point_compare's BaseEval fields plus
+    n_samples and n_faces."""
+    from . import mesh
+    points, _ = mesh.sample_surface(vertices, faces, dst if sample_dst is None else sample_dst)
+    base = point_compare(points, Qstl, obs_mask, BB, Res, plane, dst=dst, max_dist=max_dist, seed=seed, order=order, cSet=cSet, Margin=Margin)
+    base.update(n_samples=int(points.shape[0]), n_faces=int(np.asarray(faces).shape[0]))
+    return base
+
+
+def eval_mesh_ply(cSet, MeshInName, EvalName, dataPath, dst=0.2, sample_dst=None, max_dist=60.0, seed=0):
+    """eval_ply for a mesh PLY (read_ply_mesh): the same DTU files in, the same BaseEval .mat out (plus n_samples and n_faces), the four numbers
+    of eval_acc_compl back."""
+    vertices, faces = read_ply_mesh(MeshInName)
+    Qstl, m, P = _dtu_files(cSet, dataPath)
+    base = mesh_compare(vertices, faces, Qstl, m["ObsMask"], m["BB"], m["Res"], P, dst=dst, sample_dst=sample_dst, max_dist=max_dist, seed=seed,
+                        cSet=cSet, Margin=m["Margin"] if "Margin" in m else None)
+    _save_base_eval(EvalName, base, cSet)
     return eval_acc_compl(base)

@@ -2,6 +2,7 @@
 
     extract_mesh       vertices, quads and per-vertex source voxels from the per-cube lists plus normals.estimate_normals' normal_list
     triangulate        quads -> triangles
+    sample_surface     surface samples of a mesh at the evaluation density (evaluation.mesh_compare scores them)
     save_mesh_2ply     binary little-endian PLY of a quad or triangle mesh
 
 The reference ends in a point cloud: its utils/mesh_util.py only reads and writes OBJ files. The mesher looks at the scene on the world voxel
@@ -79,6 +80,34 @@ def triangulate(quads):
     """(Q,4) -> (2Q,3): triangles (0,1,2) and (0,2,3) of every quad, in quad order."""
     q = np.asarray(quads).reshape(-1, 4)
     return np.stack([q[:, [0, 1, 2]], q[:, [0, 2, 3]]], axis=1).reshape(-1, 3)
+
+
+def sample_surface(vertices, faces, dst=0.2):
+    """Surface samples of a mesh at density dst: vertices (V,3) float32 or float64 (converted to float64 exactly),
+    faces (F,3) triangles or (F,4) quads, which go through triangulate first. -> (points (M,3) float64, tri (M,) int32): every point of a
+    triangle lies within 2/3 dst of one of its samples; tri is the triangle a sample came from (tri // 2 the quad), so the colour or normal
+    of a sample is a gather by the caller. ValueError on bad shapes, dtypes or dst before the library is touched."""
+    v = np.asarray(vertices)
+    if v.dtype not in (np.float32, np.float64):
+        raise ValueError("vertices must be float32 or float64, not %s" % v.dtype)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError("vertices must be (V,3), not %r" % (v.shape,))
+    f = np.asarray(faces)
+    if f.ndim != 2 or f.shape[1] not in (3, 4):
+        raise ValueError("faces must be (F,3) or (F,4), not %r" % (f.shape,))
+    if f.dtype.kind not in "iu":
+        raise ValueError("faces must hold integers, not %s" % f.dtype)
+    if f.size and (f.min() < -(1 << 31) or f.max() >= 1 << 31):
+        raise ValueError("a face index does not fit int32")
+    try:
+        d = float(dst)
+    except (TypeError, ValueError):
+        raise ValueError("dst = %r must be a number" % (dst,))
+    if not (np.isfinite(d) and d > 0):
+        raise ValueError("dst = %r must be finite and > 0" % (dst,))
+    if f.shape[1] == 4:
+        f = triangulate(f)
+    return runtime.any_context().mesh_sample(v.astype(np.float64), f.astype(np.int32), d)
 
 
 def save_mesh_2ply(path, vertices, faces, normal_np=None, rgb_np=None):
