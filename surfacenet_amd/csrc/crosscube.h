@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lattice.h"
+
 namespace sn {
 
 constexpr int CC_NT = 256;              // grid / cost / mask kernels: one workgroup per cube
@@ -98,9 +100,8 @@ __device__ inline bool cc_range(const int64_t *off, int c, long long total, int 
 // ---- cube map -------------------------------------------------------------------------------------------------------------------------------
 __device__ inline unsigned cc_hash(unsigned long long i, unsigned long long j, unsigned long long k, unsigned mask)
 {
-    unsigned long long x = (i * 0x9E3779B97F4A7C15ull) ^ (j + 0x632BE59BD9B4E019ull) * 0xC2B2AE3D27D4EB4Full ^ (k * 0x165667B19E3779F9ull);
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
-    return (unsigned)x & mask;
+    const unsigned long long x = (i * 0x9E3779B97F4A7C15ull) ^ (j + 0x632BE59BD9B4E019ull) * 0xC2B2AE3D27D4EB4Full ^ (k * 0x165667B19E3779F9ull);
+    return (unsigned)lt_mix64(x) & mask;
 }
 
 __device__ inline bool cc_same(const uint32_t *cube_ijk, int a, int b)
@@ -491,8 +492,7 @@ __global__ void __launch_bounds__(256) cc_check_kernel(const int64_t *off, int n
 {
     const long long x = (long long)blockIdx.x * 256 + threadIdx.x;
     if (x <= n) {
-        const long long o = off[x];
-        if ((x == 0 && o != 0) || (x == n && o != total) || (x > 0 && o < off[x - 1])) *err = CC_ERR_INPUT;
+        if (lt_offsets_bad(off, x, n, total)) *err = CC_ERR_INPUT;
     }
     if (x < total && (ijk[3 * x] >= Dc || ijk[3 * x + 1] >= Dc || ijk[3 * x + 2] >= Dc)) *err = CC_ERR_INPUT;
 }

@@ -11,156 +11,32 @@
 // One workgroup per cube sets bits of an LDS bit-row of ceil(s^3 / 32) words and writes Y from it with 16-byte stores: no global atomics, the
 // result does not depend on the order of the points. Integer and fp32 / fp64 VALU work: no MFMA.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <string.h>
+#include "cellgrid.h"
 
 namespace sn {
 
 constexpr int GT_NT = 256;
-constexpr unsigned long long GT_EMPTY = ~0ull;         // free hash slot (keys are < 2^63)
-constexpr int GT_AXIS_BITS = 21;                       // cell indices are < 2^21 per axis
-constexpr long long GT_AXIS_MAX = 1ll << GT_AXIS_BITS;
 constexpr int GT_ERR_INPUT = 3;                        // value of the context's device error flag (sn_internal.h GT_ERR_INPUT_FLAG)
 constexpr int GT_ACC_CHUNK = 4096;                     // voxels per workgroup of the accuracy kernel (a multiple of 4 * GT_NT)
 constexpr double GT_WIDEN = 1e-5;                      // the candidate box exceeds the cube by this fraction of (|xyz| + side) on every face
-constexpr unsigned GT_FLAG_NONFINITE = 1;
 
-// order-preserving code of a float (a < b <=> code(a) < code(b); -0 < +0)
-__host__ __device__ inline unsigned gt_code(float v)
-{
-    unsigned u;
-    memcpy(&u, &v, 4);
-    return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-__host__ __device__ inline float gt_decode(unsigned c)
-{
-    const unsigned u = (c >> 31) ? (c & 0x7fffffffu) : ~c;
-    float v;
-    memcpy(&v, &u, 4);
-    return v;
-}
+// The bound cloud (cellgrid.h). A coordinate's cell index is a non-decreasing function of the coordinate (float64 subtraction, division by
+// cell > 0, floor, clamp), so the points of an interval lie in the cells between the cells of its ends.
+typedef CellGrid<float> GTGrid;
 
-struct GTStats { unsigned kmin[3], kmax[3], flags, pad; };
-
-// The bound cloud. A coordinate's cell index is a non-decreasing function of the coordinate (float64 subtraction, division by cell > 0, floor,
-// clamp), so the points of an interval lie in the cells between the cells of its ends.
-struct GTGrid {
-    const float *pts;                   // [n][3], cell by cell
-    const unsigned long long *keys;     // [mask + 1] hash slots: (i << 42 | j << 21 | k) of an occupied cell, or GT_EMPTY
-    const int *start, *count;           // [mask + 1] per slot: first point, number of points
-    unsigned mask;
-    long long n;
-    double o[3], cell;
-    long long dim[3];                   // cells per axis, < 2^21
+// the cloud as given, for the bounds pass of the bind (cg_bounds_kernel)
+struct GTPoints {
+    typedef float scalar;
+    const float *pts;                   // [n][3]
+    __device__ bool load(long long i, float *p, bool *bad) const
+    {
+        for (int d = 0; d < 3; ++d) p[d] = pts[3 * i + d];
+        const float inf = __builtin_inff();      // (no short-circuit: a test per load would wait for each load in turn)
+        const bool ok = ((int)(fabsf(p[0]) < inf) & (int)(fabsf(p[1]) < inf) & (int)(fabsf(p[2]) < inf)) != 0;
+        if (!ok) *bad = true;
+        return ok;
+    }
 };
-
-// cell index of coordinate v on an axis, clamped to [-1, dim] (-1: below the grid, dim: above it)
-__host__ __device__ inline long long gt_cell_of(double v, double o, double cell, long long dim)
-{
-    const double f = floor((v - o) / cell);
-    if (!(f >= 0.0)) return -1;
-    if (f >= (double)dim) return dim;
-    return (long long)f;
-}
-
-__host__ __device__ inline unsigned gt_hash(unsigned long long k)
-{
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    return (unsigned)k;
-}
-
-__global__ void gt_stats_init_kernel(GTStats *st)
-{
-    if (threadIdx.x < 3) { st->kmin[threadIdx.x] = ~0u; st->kmax[threadIdx.x] = 0u; }
-    if (threadIdx.x == 3) { st->flags = 0; st->pad = 0; }
-}
-
-// ---- bind, pass 1: per-axis minimum and maximum, non-finite flag ----------------------------------------------------------------------------
-__global__ void __launch_bounds__(GT_NT) gt_bounds_kernel(const float *pts, long long n, GTStats *st)
-{
-    __shared__ unsigned sh[GT_NT / 64][6];
-    unsigned kmin[3] = {~0u, ~0u, ~0u}, kmax[3] = {0, 0, 0};
-    bool bad = false;
-    for (long long i = (long long)blockIdx.x * GT_NT + threadIdx.x; i < n; i += (long long)gridDim.x * GT_NT)
-        for (int d = 0; d < 3; ++d) {
-            const float v = pts[3 * i + d];
-            if (!(fabsf(v) < __builtin_inff())) { bad = true; continue; }
-            const unsigned k = gt_code(v);
-            kmin[d] = k < kmin[d] ? k : kmin[d];
-            kmax[d] = k > kmax[d] ? k : kmax[d];
-        }
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&st->flags, GT_FLAG_NONFINITE);
-    for (int o = 32; o > 0; o >>= 1)
-        for (int d = 0; d < 3; ++d) {
-            const unsigned a = __shfl_xor(kmin[d], o), b = __shfl_xor(kmax[d], o);
-            kmin[d] = a < kmin[d] ? a : kmin[d];
-            kmax[d] = b > kmax[d] ? b : kmax[d];
-        }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-        for (int d = 0; d < 3; ++d) { sh[wave][d] = kmin[d]; sh[wave][3 + d] = kmax[d]; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int d = threadIdx.x;
-        unsigned lo = sh[0][d], hi = sh[0][3 + d];
-        for (int w = 1; w < GT_NT / 64; ++w) {
-            lo = sh[w][d] < lo ? sh[w][d] : lo;
-            hi = sh[w][3 + d] > hi ? sh[w][3 + d] : hi;
-        }
-        atomicMin(&st->kmin[d], lo);
-        atomicMax(&st->kmax[d], hi);
-    }
-}
-
-// ---- bind, pass 2 and 3: counting sort by cell ------------------------------------------------------------------------------------------------
-struct GTBuildArgs {
-    const float *pts;                   // [n][3] as given
-    long long n;
-    double o[3], cell;
-    long long dim[3];
-    unsigned long long *keys;           // [mask + 1], GT_EMPTY
-    int *count;                         // [mask + 1], 0
-    const int *start;                   // [mask + 1] exclusive scan of count (pass 3)
-    int *slot, *pos;                    // [n] the point's hash slot, its rank among the points of its cell
-    float *sorted;                      // [n][3]
-    unsigned mask;
-};
-
-__global__ void __launch_bounds__(GT_NT) gt_insert_kernel(GTBuildArgs a)
-{
-    const long long i = (long long)blockIdx.x * GT_NT + threadIdx.x;
-    if (i >= a.n) return;
-    unsigned long long key = 0;
-    for (int d = 0; d < 3; ++d) {
-        long long q = gt_cell_of((double)a.pts[3 * i + d], a.o[d], a.cell, a.dim[d]);
-        q = q < 0 ? 0 : (q >= a.dim[d] ? a.dim[d] - 1 : q);            // (the clamp keeps the index monotone in the coordinate)
-        key = (key << GT_AXIS_BITS) | (unsigned long long)q;
-    }
-    unsigned h = gt_hash(key) & a.mask;
-    for (;;) {                                          // ends: the table holds at least twice the keys that can be inserted
-        unsigned long long cur = __hip_atomic_load(a.keys + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == GT_EMPTY) {
-            unsigned long long expected = GT_EMPTY;
-            if (__hip_atomic_compare_exchange_strong(a.keys + h, &expected, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                cur = key;
-            else
-                cur = expected;
-        }
-        if (cur == key) break;
-        h = (h + 1) & a.mask;
-    }
-    a.slot[i] = (int)h;
-    a.pos[i] = atomicAdd(a.count + h, 1);
-}
-
-__global__ void __launch_bounds__(GT_NT) gt_scatter_kernel(GTBuildArgs a)
-{
-    const long long i = (long long)blockIdx.x * GT_NT + threadIdx.x;
-    if (i >= a.n) return;
-    const long long t = (long long)a.start[a.slot[i]] + a.pos[i];       // (< n: start + count of the last slot is n)
-    for (int d = 0; d < 3; ++d) a.sorted[3 * t + d] = a.pts[3 * i + d];
-}
 
 // ---- occupancy ----------------------------------------------------------------------------------------------------------------------------------
 struct GTCubesArgs {
@@ -198,8 +74,8 @@ __global__ void __launch_bounds__(GT_NT) gt_cubes_kernel(GTCubesArgs a)
         const double side = (double)s * (double)r;
         for (int d = 0; d < 3; ++d) {
             const double eps = GT_WIDEN * (fabs((double)x[d]) + side);
-            long long c0 = gt_cell_of((double)x[d] - eps, a.g.o[d], a.g.cell, a.g.dim[d]);
-            long long c1 = gt_cell_of((double)x[d] + side + eps, a.g.o[d], a.g.cell, a.g.dim[d]);
+            long long c0 = cg_cell((double)x[d] - eps, a.g.o[d], a.g.h, a.g.dim[d]);
+            long long c1 = cg_cell((double)x[d] + side + eps, a.g.o[d], a.g.h, a.g.dim[d]);
             c0 = c0 < 0 ? 0 : c0;
             c1 = c1 >= a.g.dim[d] ? a.g.dim[d] - 1 : c1;
             lo[d] = c0;
@@ -207,19 +83,18 @@ __global__ void __launch_bounds__(GT_NT) gt_cubes_kernel(GTCubesArgs a)
             nc *= ext[d];
         }
         if (nc > a.g.n) {                               // more cells than points (a cell far smaller than the cube): test every point
-            for (long long i = tid; i < a.g.n; i += GT_NT) gt_mark(a.g.pts + 3 * i, x, r, s, gt_bits);
+            for (long long i = tid; i < a.g.n; i += GT_NT) gt_mark(a.g.xyz + 3 * i, x, r, s, gt_bits);
         } else {
             const int wave = tid >> 6, lane = tid & 63; // a wave per cell, a lane per point of it
             for (long long t = wave; t < nc; t += GT_NT / 64) {
                 const long long k = t % ext[2], j = (t / ext[2]) % ext[1], i = t / (ext[2] * ext[1]);
-                const unsigned long long key = ((unsigned long long)(lo[0] + i) << (2 * GT_AXIS_BITS)) |
-                                               ((unsigned long long)(lo[1] + j) << GT_AXIS_BITS) | (unsigned long long)(lo[2] + k);
-                unsigned h = gt_hash(key) & a.g.mask;
+                const unsigned long long key = lt_key(lo[0] + i, lo[1] + j, lo[2] + k);
+                unsigned h = (unsigned)lt_mix64(key) & a.g.mask;
                 unsigned long long cur;
-                while ((cur = a.g.keys[h]) != key && cur != GT_EMPTY) h = (h + 1) & a.g.mask;      // (ends: at most half the slots are taken)
+                while ((cur = a.g.keys[h]) != key && cur != LtKeys::FREE) h = (h + 1) & a.g.mask;      // (ends: at most half the slots are taken)
                 if (cur != key) continue;
                 const int b = a.g.start[h], e = b + a.g.count[h];
-                for (int p = b + lane; p < e; p += 64) gt_mark(a.g.pts + 3 * (long long)p, x, r, s, gt_bits);
+                for (int p = b + lane; p < e; p += 64) gt_mark(a.g.xyz + 3 * (long long)p, x, r, s, gt_bits);
             }
         }
     }

@@ -8,7 +8,7 @@
 // Integer, latency-bound kernels: no MFMA. Needs -ffp-contract=off (the Makefile passes it).
 //
 // Representation. All coordinates are biased by one brick (+4 cells), so lattice points down to -4 have non-negative keys. Three hash tables of
-// nm_table.h: the cell table {cell key + 1, NM_OWNER_TOP - owner}; the brick table {brick key + 1, 64 occupancy bits of P}; the candidate table
+// lattice_table.h (LtPairs): the cell table {cell key + 1, LT_OWNER_TOP - owner}; the brick table {brick key + 1, 64 occupancy bits of P}; the candidate table
 // {brick key + 1, the same bits}, which also holds the 26 neighbours of every occupied brick: every lattice point that can be defined, and
 // every dual cube that can carry a vertex, lies in a candidate brick (r <= 3, bricks of 4^3). The candidates are listed, sorted by key and
 // ranked; the canonical order of vertices and quads is (brick key, local index[, axis]), so a per-brick count, an exclusive scan and an in-wave
@@ -19,14 +19,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "nm_table.h"
+#include "lattice_table.h"
 
 namespace sn {
 
 constexpr int MS_NT = 256;                           // the per-voxel and per-slot kernels
 constexpr int MS_BIAS = 4;                           // cells: one brick
 constexpr int MS_MARGIN = 8;                         // masked cells satisfy g + MS_MARGIN < 2^21: bias + radius + 1 stays below the key range
-constexpr long long MS_BRICK_MAX = NM_AXIS_MAX >> 2; // brick coordinates are < 2^19
+constexpr long long MS_BRICK_MAX = LT_AXIS_MAX >> 2; // brick coordinates are < 2^19
 constexpr double MS_QSCALE = 16384.0;
 constexpr unsigned long long MS_FLAG_TABLE = 1, MS_FLAG_CELL = 2, MS_FLAG_NORMAL = 4;
 // words of the call's counters
@@ -59,25 +59,6 @@ struct MSOut {
     double origin[3], resol;
 };
 
-__device__ inline void ms_unkey(unsigned long long key, long long b[3])
-{
-    const unsigned long long am = (unsigned long long)NM_AXIS_MAX - 1;
-    b[0] = (long long)(key >> (2 * NM_AXIS_BITS)); b[1] = (long long)((key >> NM_AXIS_BITS) & am); b[2] = (long long)(key & am);
-}
-
-// slot of `key`, -1 if absent (read-only: after the insert kernels have finished)
-__device__ inline int ms_slot(const unsigned long long *tab, unsigned hmask, unsigned long long key)
-{
-    const unsigned long long stored = key + 1ull;
-    unsigned h = nm_hash(key, hmask);
-    for (;;) {
-        const unsigned long long cur = tab[2 * (size_t)h];
-        if (cur == stored) return (int)h;
-        if (cur == 0ull) return -1;
-        h = (h + 1) & hmask;
-    }
-}
-
 // biased world cell of voxel t of cube c
 __device__ inline void ms_cell(const MSIn &a, int c, long long t, long long g[3])
 {
@@ -89,8 +70,7 @@ __global__ void __launch_bounds__(MS_NT) ms_check_kernel(const int64_t *off, int
 {
     const int c = blockIdx.x * MS_NT + threadIdx.x;
     if (c > n) return;
-    const long long o = off[c];
-    if ((c == 0 && o != 0) || (c == n && o != total) || (c > 0 && o < off[c - 1])) atomicOr(cnt + MS_CNT_FLAGS, MS_FLAG_TABLE);
+    if (lt_offsets_bad(off, c, n, total)) atomicOr(cnt + MS_CNT_FLAGS, MS_FLAG_TABLE);
 }
 
 // every voxel: its cube; every masked voxel: its normal and cell checked, its packed index into the cell table
@@ -98,7 +78,7 @@ __global__ void __launch_bounds__(MS_NT) ms_insert_kernel(MSIn a, MSTab tb)
 {
     const long long t = (long long)blockIdx.x * MS_NT + threadIdx.x;
     if (t >= a.total) return;
-    const int c = nm_cube_of(a.off, a.n, t);
+    const int c = lt_cube_of(a.off, a.n, t);
     a.cube_of[t] = c;
     if (!a.mask[t]) return;
     bool bad = false;
@@ -106,12 +86,12 @@ __global__ void __launch_bounds__(MS_NT) ms_insert_kernel(MSIn a, MSTab tb)
     if (bad) { atomicOr(a.cnt + MS_CNT_FLAGS, MS_FLAG_NORMAL); return; }
     long long g[3];
     ms_cell(a, c, t, g);
-    if (g[0] - MS_BIAS + MS_MARGIN >= NM_AXIS_MAX || g[1] - MS_BIAS + MS_MARGIN >= NM_AXIS_MAX || g[2] - MS_BIAS + MS_MARGIN >= NM_AXIS_MAX) {
+    if (g[0] - MS_BIAS + MS_MARGIN >= LT_AXIS_MAX || g[1] - MS_BIAS + MS_MARGIN >= LT_AXIS_MAX || g[2] - MS_BIAS + MS_MARGIN >= LT_AXIS_MAX) {
         atomicOr(a.cnt + MS_CNT_FLAGS, MS_FLAG_CELL);
         return;
     }
-    const unsigned h = nm_claim(tb.cell, tb.cmask, nm_key(g[0], g[1], g[2]));
-    atomicMax(tb.cell + 2 * (size_t)h + 1, NM_OWNER_TOP - (unsigned long long)t);      // the smallest index is the largest stored value
+    const unsigned h = lt_claim<LtPairs>(tb.cell, tb.cmask, lt_key(g[0], g[1], g[2]));
+    atomicMax(tb.cell + 2 * (size_t)h + 1, LT_OWNER_TOP - (unsigned long long)t);      // the smallest index is the largest stored value
 }
 
 // every owner with a non-zero normal: its cell's bit into the brick table (the host does not launch this after a flag)
@@ -122,8 +102,8 @@ __global__ void __launch_bounds__(MS_NT) ms_bricks_kernel(MSIn a, MSTab tb)
     if (a.normals[3 * t] == 0.f && a.normals[3 * t + 1] == 0.f && a.normals[3 * t + 2] == 0.f) return;
     long long g[3];
     ms_cell(a, a.cube_of[t], t, g);
-    if (nm_find(tb.cell, tb.cmask, nm_key(g[0], g[1], g[2])) != NM_OWNER_TOP - (unsigned long long)t) return;
-    const unsigned h = nm_claim(tb.brick, tb.bmask, nm_key(g[0] >> 2, g[1] >> 2, g[2] >> 2));
+    if (lt_value(tb.cell, tb.cmask, lt_key(g[0], g[1], g[2])) != LT_OWNER_TOP - (unsigned long long)t) return;
+    const unsigned h = lt_claim<LtPairs>(tb.brick, tb.bmask, lt_key(g[0] >> 2, g[1] >> 2, g[2] >> 2));
     atomicOr(tb.brick + 2 * (size_t)h + 1, 1ull << (((g[0] & 3) << 4) | ((g[1] & 3) << 2) | (g[2] & 3)));
 }
 
@@ -143,11 +123,11 @@ __global__ void __launch_bounds__(MS_NT) ms_cand_kernel(MSTab tb)
     const unsigned long long stored = tb.brick[2 * (size_t)s];
     if (stored == 0ull) return;
     long long b[3];
-    ms_unkey(stored - 1ull, b);
+    lt_unkey(stored - 1ull, b);
     for (int dx = -1; dx <= 1; ++dx)
         for (int dy = -1; dy <= 1; ++dy)
             for (int dz = -1; dz <= 1; ++dz) {
-                const unsigned h = nm_claim(tb.cand, tb.kmask, nm_key(b[0] + dx, b[1] + dy, b[2] + dz));
+                const unsigned h = lt_claim<LtPairs>(tb.cand, tb.kmask, lt_key(b[0] + dx, b[1] + dy, b[2] + dz));
                 if (dx == 0 && dy == 0 && dz == 0) tb.cand[2 * (size_t)h + 1] = tb.brick[2 * (size_t)s + 1];      // (the only writer of this word)
             }
 }
@@ -164,7 +144,7 @@ __global__ void __launch_bounds__(MS_NT) ms_rank_kernel(MSTab tb, const unsigned
 {
     const int i = blockIdx.x * MS_NT + threadIdx.x;
     if (i >= nc) return;
-    const int h = ms_slot(tb.cand, tb.kmask, list[i]);
+    const int h = lt_find<LtPairs>(tb.cand, tb.kmask, list[i]);
     if (h >= 0) tb.rank[h] = i;
 }
 
@@ -179,7 +159,7 @@ __device__ inline void ms_load_nbrs(const MSTab &tb, const long long b[3], MSNbr
         int r = -1;
         unsigned long long o = 0ull;
         if (x >= 0 && y >= 0 && z >= 0 && x < MS_BRICK_MAX && y < MS_BRICK_MAX && z < MS_BRICK_MAX) {
-            const int h = ms_slot(tb.cand, tb.kmask, nm_key(x, y, z));
+            const int h = lt_find<LtPairs>(tb.cand, tb.kmask, lt_key(x, y, z));
             if (h >= 0) { r = tb.rank[h]; o = tb.cand[2 * (size_t)h + 1]; }
         }
         nb.rank[lane] = r; nb.occ[lane] = o;
@@ -205,13 +185,13 @@ __global__ void __launch_bounds__(64) ms_field_kernel(MSTab tb, MSField f, const
     __shared__ int nq[27 * 3 * 64];
     const int lane = threadIdx.x, lx = lane >> 4, ly = (lane >> 2) & 3, lz = lane & 3;
     long long b[3];
-    ms_unkey(f.list[blockIdx.x], b);
+    lt_unkey(f.list[blockIdx.x], b);
     ms_load_nbrs(tb, b, nb);
     for (int ni = 0; ni < 27; ++ni) {
         if (!((nb.occ[ni] >> lane) & 1ull)) continue;
         const long long x = 4 * (b[0] + ni / 9 - 1) + lx, y = 4 * (b[1] + (ni / 3) % 3 - 1) + ly, z = 4 * (b[2] + ni % 3 - 1) + lz;
-        const unsigned long long own = nm_find(tb.cell, tb.cmask, nm_key(x, y, z));      // (a bit of P: the cell is in the table)
-        const unsigned long long t = NM_OWNER_TOP - own;
+        const unsigned long long own = lt_value(tb.cell, tb.cmask, lt_key(x, y, z));      // (a bit of P: the cell is in the table)
+        const unsigned long long t = LT_OWNER_TOP - own;
         for (int k = 0; k < 3; ++k) nq[(ni * 3 + k) * 64 + lane] = own ? (int)rint((double)normals[3 * t + k] * MS_QSCALE) : 0;
     }
     __syncthreads();
@@ -243,7 +223,7 @@ __global__ void __launch_bounds__(64) ms_edge_kernel(MSTab tb, MSField f)
     __shared__ MSNbr nb;
     const int lane = threadIdx.x, l[3] = {lane >> 4, (lane >> 2) & 3, lane & 3};
     long long b[3];
-    ms_unkey(f.list[blockIdx.x], b);
+    lt_unkey(f.list[blockIdx.x], b);
     ms_load_nbrs(tb, b, nb);
     const size_t s0 = (size_t)blockIdx.x * 64 + lane;
     const bool def0 = f.W[s0] > 0, in0 = f.F[s0] < 0;
@@ -273,7 +253,7 @@ __global__ void __launch_bounds__(64) ms_vcount_kernel(MSTab tb, MSField f)
     __shared__ MSNbr nb;
     const int lane = threadIdx.x, l[3] = {lane >> 4, (lane >> 2) & 3, lane & 3};
     long long b[3];
-    ms_unkey(f.list[blockIdx.x], b);
+    lt_unkey(f.list[blockIdx.x], b);
     ms_load_nbrs(tb, b, nb);
     bool used = false;
     for (int a = 0; a < 3; ++a) {
@@ -297,7 +277,7 @@ __global__ void __launch_bounds__(64) ms_vemit_kernel(MSTab tb, MSField f, MSOut
     __shared__ MSNbr nb;
     const int lane = threadIdx.x, l[3] = {lane >> 4, (lane >> 2) & 3, lane & 3};
     long long b[3];
-    ms_unkey(f.list[blockIdx.x], b);
+    lt_unkey(f.list[blockIdx.x], b);
     ms_load_nbrs(tb, b, nb);
     if (!((f.vmask[blockIdx.x] >> lane) & 1ull)) return;
     const size_t vi = (size_t)ms_vertex(f, blockIdx.x, lane);
@@ -338,8 +318,8 @@ __global__ void __launch_bounds__(64) ms_vemit_kernel(MSTab tb, MSField f, MSOut
                     if (dist < best && ms_in_P(nb, l[0] + dx, l[1] + dy, l[2] + dz)) { best = dist; bq[0] = l[0] + dx; bq[1] = l[1] + dy; bq[2] = l[2] + dz; }
                 }
         unsigned long long own = 0ull;
-        if (best != (1 << 30)) own = nm_find(tb.cell, tb.cmask, nm_key(4 * b[0] + bq[0], 4 * b[1] + bq[1], 4 * b[2] + bq[2]));
-        o.vert_src[vi] = own ? (int64_t)(NM_OWNER_TOP - own) : -1;
+        if (best != (1 << 30)) own = lt_value(tb.cell, tb.cmask, lt_key(4 * b[0] + bq[0], 4 * b[1] + bq[1], 4 * b[2] + bq[2]));
+        o.vert_src[vi] = own ? (int64_t)(LT_OWNER_TOP - own) : -1;
     }
 }
 
@@ -349,7 +329,7 @@ __global__ void __launch_bounds__(64) ms_qemit_kernel(MSTab tb, MSField f, MSOut
     __shared__ MSNbr nb;
     const int lane = threadIdx.x, l[3] = {lane >> 4, (lane >> 2) & 3, lane & 3};
     long long b[3];
-    ms_unkey(f.list[blockIdx.x], b);
+    lt_unkey(f.list[blockIdx.x], b);
     ms_load_nbrs(tb, b, nb);
     const size_t s0 = (size_t)blockIdx.x * 64 + lane;
     const unsigned fl = (f.eflags[s0] >> 3) & 7u;

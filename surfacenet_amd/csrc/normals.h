@@ -9,16 +9,17 @@
 // Representation: the scene's occupancy as a hash table of 4^3 bricks. Key = the brick's coordinates (g >> 2, 19 bits per axis), value = one
 // 64-bit word, bit (x&3)*16 + (y&3)*4 + (z&3) = cell occupied, filled with atomicOr. A window of radius <= 2 touches at most 2^3 bricks, of radius 3
 // at most 3^3: 8 or 27 probes instead of 125 or 343. A slot is two words {key + 1, occupancy}; key + 1 != 0, so an all-zero table is empty.
-// The unique-owner table is per cell: {cell key + 1, NM_OWNER_TOP - smallest packed index}: the value words start as 0 as well, so the minimum
+// The unique-owner table is per cell: {cell key + 1, LT_OWNER_TOP - smallest packed index}: the value words start as 0 as well, so the minimum
 // of the indices is kept as the atomicMax of their complements.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "nm_table.h"
+#include "lattice_table.h"
 
 namespace sn {
 
+constexpr int NM_NT = 256;
 constexpr int NM_SWEEPS = 12;                        // cyclic Jacobi sweeps (3 rotations each)
 // bits of the call's status word (read back by the host before the main kernel runs)
 constexpr int NM_FLAG_TABLE = 1, NM_FLAG_CELL = 2, NM_FLAG_VIEW = 4;
@@ -48,8 +49,7 @@ __global__ void __launch_bounds__(NM_NT) nm_check_kernel(const int64_t *off, int
 {
     const int c = blockIdx.x * NM_NT + threadIdx.x;
     if (c > n) return;
-    const long long o = off[c];
-    if ((c == 0 && o != 0) || (c == n && o != total) || (c > 0 && o < off[c - 1])) atomicOr(flags, NM_FLAG_TABLE);
+    if (lt_offsets_bad(off, c, n, total)) atomicOr(flags, NM_FLAG_TABLE);
     if (c == n || !view_idx) return;
     double s[3] = {0.0, 0.0, 0.0};
     bool bad = false;
@@ -68,17 +68,17 @@ __global__ void __launch_bounds__(NM_NT) nm_insert_kernel(NMArgs a)
 {
     const long long t = (long long)blockIdx.x * NM_NT + threadIdx.x;
     if (t >= a.total) return;
-    const int c = nm_cube_of(a.off, a.n, t);
+    const int c = lt_cube_of(a.off, a.n, t);
     a.cube_of[t] = c;
     if (!a.mask[t]) return;
     long long g[3];
     nm_cell(a, c, t, g);
-    if (g[0] + a.radius >= NM_AXIS_MAX || g[1] + a.radius >= NM_AXIS_MAX || g[2] + a.radius >= NM_AXIS_MAX) { atomicOr(a.flags, NM_FLAG_CELL); return; }
+    if (g[0] + a.radius >= LT_AXIS_MAX || g[1] + a.radius >= LT_AXIS_MAX || g[2] + a.radius >= LT_AXIS_MAX) { atomicOr(a.flags, NM_FLAG_CELL); return; }
     if (CELLS) {
-        const unsigned h = nm_claim(a.tab, a.hmask, nm_key(g[0], g[1], g[2]));
-        atomicMax(a.tab + 2 * (size_t)h + 1, NM_OWNER_TOP - (unsigned long long)t);      // the smallest index is the largest stored value
+        const unsigned h = lt_claim<LtPairs>(a.tab, a.hmask, lt_key(g[0], g[1], g[2]));
+        atomicMax(a.tab + 2 * (size_t)h + 1, LT_OWNER_TOP - (unsigned long long)t);      // the smallest index is the largest stored value
     } else {
-        const unsigned h = nm_claim(a.tab, a.hmask, nm_key(g[0] >> 2, g[1] >> 2, g[2] >> 2));
+        const unsigned h = lt_claim<LtPairs>(a.tab, a.hmask, lt_key(g[0] >> 2, g[1] >> 2, g[2] >> 2));
         const unsigned long long bit = 1ull << (((g[0] & 3) << 4) | ((g[1] & 3) << 2) | (g[2] & 3));
         unsigned long long *w = a.tab + 2 * (size_t)h + 1;
         if (!(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) atomicOr(w, bit);
@@ -167,7 +167,7 @@ __global__ void __launch_bounds__(NM_NT) nm_normals_kernel(NMArgs a)
                 for (long long bz = b0[2]; bz <= b1[2]; ++bz) {
                     if (bz < 0) continue;
                     const int oz = (int)(4 * bz - g[2]);
-                    unsigned long long w = nm_find(a.tab, a.hmask, nm_key(bx, by, bz)) & mxy & nm_axis_mask(max(0, -r - oz), min(3, r - oz), 2);
+                    unsigned long long w = lt_value(a.tab, a.hmask, lt_key(bx, by, bz)) & mxy & nm_axis_mask(max(0, -r - oz), min(3, r - oz), 2);
                     mom[0] += __popcll(w);
                     for (; w; w &= w - 1) {
                         const int b = __builtin_ctzll(w);
@@ -211,7 +211,7 @@ __global__ void __launch_bounds__(NM_NT) nm_owner_kernel(NMArgs a, uint8_t *keep
     if (a.mask[t]) {
         long long g[3];
         nm_cell(a, a.cube_of[t], t, g);
-        k = nm_find(a.tab, a.hmask, nm_key(g[0], g[1], g[2])) == NM_OWNER_TOP - (unsigned long long)t ? 1 : 0;
+        k = lt_value(a.tab, a.hmask, lt_key(g[0], g[1], g[2])) == LT_OWNER_TOP - (unsigned long long)t ? 1 : 0;
     }
     keep[t] = k;
 }

@@ -5,64 +5,16 @@
 // Integer and fp64 VALU work: no MFMA. d^2 = (dx*dx + dy*dy) + dz*dz in fp64 with no contraction (the Makefile passes -ffp-contract=off), so
 // the results equal the numpy restatement (tests/pointeval_ref.py) bit for bit (DESIGN.md section 4.7 states the contract).
 //
-// Every cloud is bucketed on a uniform grid: cell = floor((x - origin) / h) per axis (dims <= 2^21 per axis, so a cell key packs into 63 bits).
-// Occupied cells live in an open-addressing hash table (key -> slot, linear probing, as crosscube.h's ijk -> cube map); per-slot counts come from
-// wave-aggregated atomics (one atomic per run of equal slots in a wave), an exclusive scan gives each slot its range, and a scatter writes the
-// points cell-sorted (CSR). Neighbour and ring searches walk cells and read each occupied cell's contiguous run of points.
+// Every cloud is bucketed on a uniform grid (cellgrid.h: CellGrid<double>, cell = floor((x - origin) / h) per axis, the occupied cells in a
+// hash table, the points cell-sorted). Neighbour and ring searches walk cells and read each occupied cell's contiguous run of points.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "cellgrid.h"
 
 namespace sn {
 
 constexpr int PE_NT = 256;
-constexpr unsigned long long PE_EMPTY = ~0ull;        // free hash slot (cell keys are < 2^63)
 constexpr unsigned char PE_UND = 0, PE_IN = 1, PE_OUT = 2;   // reduction states
-
-// A cloud bucketed on a grid. xyz / idx are the cell-sorted points and their original indices; keys / start / count are indexed by hash slot.
-struct PEGrid {
-    double o[3], h;
-    double lo[3], hi[3];                // bounding box of the points (a lower bound for every distance to them)
-    long long dim[3];
-    const unsigned long long *keys;
-    const int *start, *count;
-    unsigned mask;                      // table capacity - 1
-    const double *xyz;
-    const int *idx;
-};
-
-__device__ inline unsigned pe_hash(unsigned long long k, unsigned mask)
-{
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    return (unsigned)k & mask;
-}
-
-__device__ inline unsigned long long pe_key(const long long *dim, long long x, long long y, long long z)
-{
-    return (unsigned long long)((x * dim[1] + y) * dim[2] + z);
-}
-
-// cell index of one coordinate, clamped to [-1, dim]: a query outside the grid sits in the layer of cells just outside it, which keeps the
-// shell bounds of pe_shell_bound valid (every point lies at index >= 0 resp. <= dim - 1).
-__device__ inline long long pe_cell(double x, double o, double h, long long dim)
-{
-    const double c = floor((x - o) / h);
-    return c < -1.0 ? -1 : (c > (double)dim ? dim : (long long)c);
-}
-
-// slot of a cell, -1 if the cell holds no point. The probe ends at a free slot: the table is at most half full.
-__device__ inline int pe_find(const PEGrid &g, long long x, long long y, long long z)
-{
-    if (x < 0 || y < 0 || z < 0 || x >= g.dim[0] || y >= g.dim[1] || z >= g.dim[2]) return -1;
-    const unsigned long long key = pe_key(g.dim, x, y, z);
-    unsigned h = pe_hash(key, g.mask);
-    for (;;) {
-        const unsigned long long cur = g.keys[h];
-        if (cur == key) return (int)h;
-        if (cur == PE_EMPTY) return -1;
-        h = (h + 1) & g.mask;
-    }
-}
+typedef CellGrid<double> PEGrid;
 
 __device__ inline double pe_d2(const double *a, const double *b)
 {
@@ -113,77 +65,10 @@ __device__ inline void pe_for_shell(const PEGrid &g, const long long *c, long lo
             const long long step = side || r == 0 ? 1 : 2 * r;          // off the x / y faces only the two z faces belong to the shell
             for (long long z = side ? z0 : c[2] - r; z <= (side ? z1 : c[2] + r); z += step) {
                 if (z < 0 || z >= g.dim[2]) continue;
-                const int s = pe_find(g, x, y, z);
+                const int s = cg_find(g, x, y, z);
                 if (s >= 0) f(s);
             }
         }
-}
-
-// ---- grid build ---------------------------------------------------------------------------------------------------------------------------
-struct PEBuildArgs {
-    const double *xyz;                  // [n][3], original order
-    const long long *rank;              // optional: per-point rank, scattered into rank_s
-    unsigned long long *keys;
-    int *start, *count, *slot, *pos, *idx, *rank_s;
-    double *xyz_s;
-    int *occupied;                      // number of distinct cells (counted at insertion)
-    double o[3], h;
-    long long dim[3];
-    unsigned mask;
-    int n;
-};
-
-// Inserts every point's cell and counts the points per cell; pos = the point's place in its cell's run. One atomic per run of equal
-// slots in a wave (input in spatial order - the data cloud of a reconstruction is - makes runs long).
-__global__ void __launch_bounds__(PE_NT) pe_insert_kernel(PEBuildArgs a)
-{
-    const int i = blockIdx.x * PE_NT + threadIdx.x, lane = threadIdx.x & 63;
-    int s = -1;
-    if (i < a.n) {
-        const double *p = a.xyz + 3 * (size_t)i;
-        long long c[3];
-        for (int d = 0; d < 3; ++d) {
-            const long long v = pe_cell(p[d], a.o[d], a.h, a.dim[d]);
-            c[d] = v < 0 ? 0 : (v >= a.dim[d] ? a.dim[d] - 1 : v);      // (host-sized dims hold every point; the clamp guards rounding only)
-        }
-        const unsigned long long key = pe_key(a.dim, c[0], c[1], c[2]);
-        unsigned h = pe_hash(key, a.mask);
-        for (;;) {
-            unsigned long long cur = __hip_atomic_load(a.keys + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cur == PE_EMPTY) {
-                unsigned long long expected = PE_EMPTY;
-                if (__hip_atomic_compare_exchange_strong(a.keys + h, &expected, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                    atomicAdd(a.occupied, 1);
-                    break;
-                }
-                cur = expected;
-            }
-            if (cur == key) break;
-            h = (h + 1) & a.mask;
-        }
-        s = (int)h;
-    }
-    // runs of equal slots: a lane heads a run when its slot differs from the lane before; the head adds the run's length
-    const int prev = __shfl_up(s, 1);
-    const unsigned long long heads = __ballot(lane == 0 || prev != s);
-    const unsigned long long upto = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
-    const int head = 63 - __clzll(heads & upto);
-    const unsigned long long above = heads & ~upto;
-    const int next = above ? __ffsll(above) - 1 : 64;
-    int base = 0;
-    if (lane == head && s >= 0) base = atomicAdd(a.count + s, next - lane);
-    base = __shfl(base, head);
-    if (i < a.n) { a.slot[i] = s; a.pos[i] = base + (lane - head); }
-}
-
-__global__ void __launch_bounds__(PE_NT) pe_scatter_kernel(PEBuildArgs a)
-{
-    const int i = blockIdx.x * PE_NT + threadIdx.x;
-    if (i >= a.n) return;
-    const int t = a.start[a.slot[i]] + a.pos[i];
-    a.idx[t] = i;
-    for (int d = 0; d < 3; ++d) a.xyz_s[3 * (size_t)t + d] = a.xyz[3 * (size_t)i + d];
-    if (a.rank) a.rank_s[t] = (int)a.rank[i];
 }
 
 // ---- density reduction (reducePts_haa): the parallel form of the greedy MIS --------------------------------------------------------------
@@ -208,9 +93,9 @@ __global__ void __launch_bounds__(PE_NT) pe_reduce_select_kernel(PEReduceArgs a)
     const double *q = g.xyz + 3 * (size_t)t;
     const int rk = a.rank[t];
     long long c[3];
-    for (int d = 0; d < 3; ++d) c[d] = pe_cell(q[d], g.o[d], g.h, g.dim[d]);
+    for (int d = 0; d < 3; ++d) c[d] = cg_cell(q[d], g.o[d], g.h, g.dim[d]);
     for (int nb = 0; nb < 27; ++nb) {
-        const int s = pe_find(g, c[0] + nb / 9 - 1, c[1] + (nb / 3) % 3 - 1, c[2] + nb % 3 - 1);
+        const int s = cg_find(g, c[0] + nb / 9 - 1, c[1] + (nb / 3) % 3 - 1, c[2] + nb % 3 - 1);
         if (s < 0) continue;
         const int e = g.start[s] + g.count[s];
         for (int j = g.start[s]; j < e; ++j)
@@ -227,9 +112,9 @@ __global__ void __launch_bounds__(PE_NT) pe_reduce_exclude_kernel(PEReduceArgs a
         const PEGrid &g = a.g;
         const double *q = g.xyz + 3 * (size_t)t;
         long long c[3];
-        for (int d = 0; d < 3; ++d) c[d] = pe_cell(q[d], g.o[d], g.h, g.dim[d]);
+        for (int d = 0; d < 3; ++d) c[d] = cg_cell(q[d], g.o[d], g.h, g.dim[d]);
         for (int nb = 0; nb < 27 && und; ++nb) {
-            const int s = pe_find(g, c[0] + nb / 9 - 1, c[1] + (nb / 3) % 3 - 1, c[2] + nb % 3 - 1);
+            const int s = cg_find(g, c[0] + nb / 9 - 1, c[1] + (nb / 3) % 3 - 1, c[2] + nb % 3 - 1);
             if (s < 0) continue;
             const int e = g.start[s] + g.count[s];
             for (int j = g.start[s]; j < e; ++j)
@@ -258,6 +143,7 @@ constexpr int PE_COARSE = 8;
 
 struct PENNArgs {
     PEGrid fine, coarse;
+    double lo[3], hi[3];                // bounding box of the "to" cloud (a lower bound for every distance to it)
     const double *q;                    // queries, cell-sorted
     const int *q_idx;                   // their original indices
     double *best;                       // [n_q] the near pass's best d^2 per sorted query (far queries)
@@ -279,12 +165,12 @@ __global__ void __launch_bounds__(PE_NT) pe_nn_near_kernel(PENNArgs a)
     const PEGrid &g = a.fine;
     const double *q = a.q + 3 * (size_t)t;
     const double slack = pe_query_slack(q, a.slack);
-    const double box = pe_box_bound2(q, g.lo, g.hi, slack);
+    const double box = pe_box_bound2(q, a.lo, a.hi, slack);
     double best = __builtin_inf();
     bool done = box >= a.lim;
     if (!done) {
         long long c[3];
-        for (int d = 0; d < 3; ++d) c[d] = pe_cell(q[d], g.o[d], g.h, g.dim[d]);
+        for (int d = 0; d < 3; ++d) c[d] = cg_cell(q[d], g.o[d], g.h, g.dim[d]);
         for (long long r = 0; r <= PE_NEAR_RINGS && !done; ++r) {
             pe_for_shell(g, c, r, [&](int s) {
                 const int e = g.start[s] + g.count[s];
@@ -310,17 +196,16 @@ __global__ void __launch_bounds__(PE_NT) pe_nn_far_kernel(PENNArgs a)
     const PEGrid &g = a.coarse;
     const double *q = a.q + 3 * (size_t)t;
     const double slack = pe_query_slack(q, a.slack);
-    const double box = pe_box_bound2(q, g.lo, g.hi, slack);
+    const double box = pe_box_bound2(q, a.lo, a.hi, slack);
     double best = a.best[t];
     long long c[3];
-    for (int d = 0; d < 3; ++d) c[d] = pe_cell(q[d], g.o[d], g.h, g.dim[d]);
+    for (int d = 0; d < 3; ++d) c[d] = cg_cell(q[d], g.o[d], g.h, g.dim[d]);
     const long long rmax = g.dim[0] + g.dim[1] + g.dim[2] + 2;     // past this ring no cell is left (the loop ends on the bound first)
     for (long long r = 0; r <= rmax; ++r) {
         pe_for_shell(g, c, r, [&](int s) {
             const int j0 = g.start[s];
-            const unsigned long long key = g.keys[s];       // the cell's box, from its key
-            const long long ci[3] = {(long long)(key / (unsigned long long)(g.dim[1] * g.dim[2])), (long long)((key / (unsigned long long)g.dim[2]) % (unsigned long long)g.dim[1]),
-                                     (long long)(key % (unsigned long long)g.dim[2])};
+            long long ci[3];
+            lt_unkey(g.keys[s], ci);                        // the cell's box, from its key
             double lo[3], hi[3];
             for (int d = 0; d < 3; ++d) {
                 lo[d] = g.o[d] + (double)ci[d] * g.h;

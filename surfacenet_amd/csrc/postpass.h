@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "cvc_warp.h"
+#include "lattice_table.h"
 
 namespace sn {
 
@@ -35,7 +36,7 @@ static_assert(RP_LDS_M * 4 <= RP_LDS_Q && RP_LDS_Q + RP_LDS_M * 4 <= RP_LDS_TAB 
 // LDS map: [0, 32 K) list of selected voxels (RP_LIST entries; with LDS tables only the first RP_LDS_M are in use), then either the cell slots of all
 // RP_LIST voxels [32 K, 64 K) or - LDS tables - the cell slots of RP_LDS_M voxels [14 K, 28 K) and the four tables [28 K, 28 K + 28 B x RP_LDS_CAP)
 constexpr int RP_LDS_BYTES = RP_LDS_TAB + RP_LDS_CAP * 28 > 2 * RP_LIST * 4 ? RP_LDS_TAB + RP_LDS_CAP * 28 : 2 * RP_LIST * 4;
-constexpr unsigned long long RP_EMPTY = ~0ull;
+constexpr unsigned long long RP_EMPTY = LtKeys::FREE;
 constexpr unsigned RP_NONE = 0xFFFFFFFFu;
 
 struct RayPoolArgs {
@@ -53,55 +54,15 @@ struct RayPoolArgs {
     float thresh;
 };
 
-__device__ __forceinline__ unsigned rp_hash(unsigned long long k, unsigned mask)
-{
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    return (unsigned)k & mask;
-}
-
-// insert-or-find; returns the slot. Table entries start as RP_EMPTY.
-// The tables live in LDS or in global memory; the helpers are templates over the pointer type so that each instantiation addresses ONE address space
-// (with generic pointers every access becomes a flat instruction behind a full s_waitcnt, and the lock-step passes below serialise again).
+// The tables (LtKeys of lattice_table.h, entries start as RP_EMPTY) live in LDS or in global memory; the helpers are templates over the pointer type so that
+// each instantiation addresses ONE address space (with generic pointers every access becomes a flat instruction behind a full s_waitcnt, and the
+// lock-step passes below serialise again).
 typedef __attribute__((address_space(3))) unsigned long long rp_lds_u64;
 typedef __attribute__((address_space(3))) unsigned rp_lds_u32;
 template <typename P>
 __device__ __forceinline__ auto rp_ld(P p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <typename P>
-__device__ __forceinline__ unsigned long long rp_cas(P p, unsigned long long expected, unsigned long long desired)
-{
-    __hip_atomic_compare_exchange_strong(p, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return expected;            // the value found (== the old `expected` on success)
-}
 template <typename P, typename T>
 __device__ __forceinline__ void rp_max(P p, T v) { (void)__hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// insert-or-find; returns the slot. Table entries start as RP_EMPTY.
-template <typename P>
-__device__ __forceinline__ unsigned rp_insert(P keys, unsigned mask, unsigned long long k)
-{
-    unsigned h = rp_hash(k, mask);
-    for (;;) {
-        unsigned long long cur = rp_ld(keys + h);
-        if (cur == k) return h;
-        if (cur == RP_EMPTY) {
-            unsigned long long prev = rp_cas(keys + h, RP_EMPTY, k);
-            if (prev == RP_EMPTY || prev == k) return h;
-        }
-        h = (h + 1) & mask;
-    }
-}
-
-template <typename P>
-__device__ __forceinline__ bool rp_find(P keys, unsigned mask, unsigned long long k)
-{
-    unsigned h = rp_hash(k, mask);
-    for (;;) {
-        unsigned long long cur = rp_ld(keys + h);
-        if (cur == k) return true;
-        if (cur == RP_EMPTY) return false;
-        h = (h + 1) & mask;
-    }
-}
 
 __device__ __forceinline__ void rp_vote(uint8_t *votes, unsigned i, unsigned mult)
 {
@@ -228,8 +189,8 @@ __global__ void __launch_bounds__(RP_NT) ray_pool_kernel(RayPoolArgs a)
                 *a.err = 1;
             } else {
                 const int wi = (int)w, hi = (int)h, di = (int)d;
-                const unsigned ps = rp_insert(pix_key, mask, ((unsigned long long)((unsigned)wi ^ 0x80000000u) << 32) | ((unsigned)hi ^ 0x80000000u));
-                q = rp_insert(cell_key, mask, ((unsigned long long)ps << 32) | (unsigned)di);
+                const unsigned ps = lt_claim<LtKeys>(pix_key, mask, ((unsigned long long)((unsigned)wi ^ 0x80000000u) << 32) | ((unsigned)hi ^ 0x80000000u));
+                q = lt_claim<LtKeys>(cell_key, mask, ((unsigned long long)ps << 32) | (unsigned)di);
                 rp_max(cell_idx + q, (unsigned)i);
                 dmin_t = min(dmin_t, di);
             }
@@ -273,7 +234,7 @@ __global__ void __launch_bounds__(RP_NT) ray_pool_kernel(RayPoolArgs a)
             if (best == packed_of(p, d)) target = i;
         } else if (best == 0) {                              // every stored value of this pixel is 0: argmax -> column 0
             if (d == dmin) target = i;
-            else if (!rp_find(cell_key, mask, ((unsigned long long)ps << 32) | (unsigned)dmin)) target = 0;
+            else if (lt_find<LtKeys, true>(cell_key, mask, ((unsigned long long)ps << 32) | (unsigned)dmin) < 0) target = 0;
         }
         if (target > 0) rp_vote(votes, (unsigned)target, mult);
         else if (target == 0) sh_i[2] = 1;                  // several pixels may elect voxel 0: count it once

@@ -12,18 +12,13 @@
 // 63-bit keys (i << 42 | j << 21 | k), every first insertion appended to a list, the list sorted by a bitonic network. Either way only the
 // first lane of a run of equal cells in a wave touches memory atomically (clouds come in spatial order: runs are long).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <string.h>
-
 #include "bitonic.h"
+#include "cellgrid.h"
 
 namespace sn {
 
-constexpr int PC_AXIS_BITS = 21;                       // cell indices are < 2^21 per axis
-constexpr long long PC_AXIS_MAX = 1ll << PC_AXIS_BITS;
-constexpr unsigned long long PC_DIAG = (1ull << (2 * PC_AXIS_BITS)) | (1ull << PC_AXIS_BITS) | 1ull;
-constexpr unsigned long long PC_FLAG_NONFINITE = 1, PC_FLAG_EXTENT = 2;      // PCStats::flags
+static_assert(PC_NT == CG_NT, "the bounds pass runs in cellgrid.h's workgroups");
+constexpr unsigned long long PC_FLAG_NONFINITE = CG_FLAG_NONFINITE, PC_FLAG_EXTENT = 2;      // PCStats::flags
 
 // numpy's floor_divide for floats (npy_divmod), b > 0 or b < 0, finite operands
 template <typename T>
@@ -38,115 +33,43 @@ __host__ __device__ inline T pc_floor_div(T a, T b)
     return fl;
 }
 
-// order-preserving code of a double (a < b <=> code(a) < code(b); -0 < +0)
-__host__ __device__ inline unsigned long long pc_code(double v)
-{
-    unsigned long long u;
-    memcpy(&u, &v, 8);
-    return (u >> 63) ? ~u : (u | (1ull << 63));
-}
-__host__ __device__ inline double pc_decode(unsigned long long c)
-{
-    const unsigned long long u = (c >> 63) ? (c & ~(1ull << 63)) : ~c;
-    double v;
-    memcpy(&v, &u, 8);
-    return v;
-}
-
-// What the first pass leaves for the host: codes of the per-axis minimum and maximum of the kept points, their number, flags.
-struct PCStats { unsigned long long kmin[3], kmax[3], kept, flags; };
+// What the first pass (cg_bounds_kernel) leaves for the host: codes of the per-axis minimum and maximum of the kept points, their number, flags.
+typedef CGStats<unsigned long long> PCStats;
 
 // The points: an (n,3) array of P, or - sparse lists of a scene (off != nullptr; P = float) - the masked voxels of every cube,
 // p = float32(ijk) * resol + xyz_min of the voxel's cube, as sparseCubes.sparse_xyz forms them.
 template <typename P>
 struct PCPoints {
     const P *xyz;
-    const long long *off;               // [n_cubes + 1] first voxel of every cube
+    const int64_t *off;                 // [n_cubes + 1] first voxel of every cube
     const unsigned char *vijk, *vmask;  // [n][3], [n]
     const float *cxyz, *cresol;         // [n_cubes][3], [n_cubes]
     int n_cubes;
     long long n;
     int has_box;
     double lo[3], hi[3];
+    typedef P scalar;
+
+    // point i -> p; false when it takes no part (unmasked voxel, outside the box). A non-finite coordinate sets *bad.
+    __device__ bool load(long long i, P *p, bool *bad) const
+    {
+        if (off) {
+            if (!vmask[i]) return false;
+            const int a = lt_cube_of(off, n_cubes, i);
+            const float r = cresol[a];
+            for (int d = 0; d < 3; ++d) p[d] = (P)((float)vijk[3 * i + d] * r + cxyz[3 * (size_t)a + d]);
+        } else {
+            for (int d = 0; d < 3; ++d) p[d] = xyz[3 * i + d];
+        }
+        bool in = true;
+        for (int d = 0; d < 3; ++d) {
+            const double v = (double)p[d];
+            if (!(fabs(v) < __builtin_inf())) { *bad = true; return false; }
+            if (has_box && !(v >= lo[d] && v <= hi[d])) in = false;
+        }
+        return in;
+    }
 };
-
-// point i -> p; false when it takes no part (unmasked voxel, outside the box). A non-finite coordinate sets *bad.
-template <typename P>
-__device__ inline bool pc_load(const PCPoints<P> &s, long long i, P *p, bool *bad)
-{
-    if (s.off) {
-        if (!s.vmask[i]) return false;
-        int a = 0, b = s.n_cubes;                       // the cube c with off[c] <= i < off[c + 1]: the last c in [0, n_cubes) with off[c] <= i
-        while (b - a > 1) {
-            const int m = (a + b) >> 1;
-            if (s.off[m] <= i) a = m; else b = m;
-        }
-        const float r = s.cresol[a];
-        for (int d = 0; d < 3; ++d) p[d] = (P)((float)s.vijk[3 * i + d] * r + s.cxyz[3 * (size_t)a + d]);
-    } else {
-        for (int d = 0; d < 3; ++d) p[d] = s.xyz[3 * i + d];
-    }
-    bool in = true;
-    for (int d = 0; d < 3; ++d) {
-        const double v = (double)p[d];
-        if (!(fabs(v) < __builtin_inf())) { *bad = true; return false; }
-        if (s.has_box && !(v >= s.lo[d] && v <= s.hi[d])) in = false;
-    }
-    return in;
-}
-
-__global__ void pc_stats_init_kernel(PCStats *st)
-{
-    if (threadIdx.x < 3) { st->kmin[threadIdx.x] = ~0ull; st->kmax[threadIdx.x] = 0ull; }
-    if (threadIdx.x == 3) { st->kept = 0; st->flags = 0; }
-}
-
-// ---- pass 1: per-axis minimum and maximum of the kept points ------------------------------------------------------------------------------
-template <typename P>
-__global__ void __launch_bounds__(PC_NT) pc_bounds_kernel(PCPoints<P> s, PCStats *st)
-{
-    __shared__ unsigned long long sh[PC_NT / 64][7];
-    unsigned long long kmin[3] = {~0ull, ~0ull, ~0ull}, kmax[3] = {0, 0, 0}, kept = 0;
-    bool bad = false;
-    for (long long i = (long long)blockIdx.x * PC_NT + threadIdx.x; i < s.n; i += (long long)gridDim.x * PC_NT) {
-        P p[3];
-        if (!pc_load(s, i, p, &bad)) continue;
-        ++kept;
-        for (int d = 0; d < 3; ++d) {
-            const unsigned long long k = pc_code((double)p[d]);
-            kmin[d] = k < kmin[d] ? k : kmin[d];
-            kmax[d] = k > kmax[d] ? k : kmax[d];
-        }
-    }
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&st->flags, PC_FLAG_NONFINITE);
-    for (int o = 32; o > 0; o >>= 1) {
-        for (int d = 0; d < 3; ++d) {
-            const unsigned long long a = __shfl_xor(kmin[d], o), b = __shfl_xor(kmax[d], o);
-            kmin[d] = a < kmin[d] ? a : kmin[d];
-            kmax[d] = b > kmax[d] ? b : kmax[d];
-        }
-        kept += __shfl_xor(kept, o);
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        for (int d = 0; d < 3; ++d) { sh[wave][d] = kmin[d]; sh[wave][3 + d] = kmax[d]; }
-        sh[wave][6] = kept;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < PC_NT / 64; ++w) {
-            for (int d = 0; d < 3; ++d) {
-                kmin[d] = sh[w][d] < kmin[d] ? sh[w][d] : kmin[d];
-                kmax[d] = sh[w][3 + d] > kmax[d] ? sh[w][3 + d] : kmax[d];
-            }
-            kept += sh[w][6];
-        }
-        if (kept) {
-            for (int d = 0; d < 3; ++d) { atomicMin(&st->kmin[d], kmin[d]); atomicMax(&st->kmax[d], kmax[d]); }
-            atomicAdd(&st->kept, kept);
-        }
-    }
-}
 
 // ---- pass 2: the cell set -----------------------------------------------------------------------------------------------------------------
 template <typename P, typename T>
@@ -168,7 +91,7 @@ __device__ inline bool pc_cell(const PCCellArgs<P, T> &a, long long i, long long
 {
     P p[3];
     bool bad = false;
-    if (i >= a.s.n || !pc_load(a.s, i, p, &bad)) return false;
+    if (i >= a.s.n || !a.s.load(i, p, &bad)) return false;
     bool ok = true;
     for (int d = 0; d < 3; ++d) {
         const P rel = p[d] - a.shift[d];
@@ -207,24 +130,12 @@ __global__ void __launch_bounds__(PC_NT) pc_mark_kernel(PCCellArgs<P, T> a)
     }
 }
 
+// first insertion of a key: appended to the list (at most 2 n distinct keys: the list holds them)
 __device__ inline void pc_hash_insert(unsigned long long *table, unsigned mask, unsigned long long *list, unsigned long long *n_list, unsigned long long key)
 {
-    unsigned long long k = key;
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    unsigned h = (unsigned)k & mask;
-    for (;;) {                                          // ends: the table holds at least twice the keys that can be inserted
-        unsigned long long cur = __hip_atomic_load(table + h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == PC_EMPTY) {
-            unsigned long long expected = PC_EMPTY;
-            if (__hip_atomic_compare_exchange_strong(table + h, &expected, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                list[atomicAdd(n_list, 1ull)] = key;    // (at most 2 n distinct keys: the list holds them)
-                return;
-            }
-            cur = expected;
-        }
-        if (cur == key) return;
-        h = (h + 1) & mask;
-    }
+    bool fresh;
+    lt_claim<LtKeys>(table, mask, key, &fresh);
+    if (fresh) list[atomicAdd(n_list, 1ull)] = key;
 }
 
 template <typename P, typename T>
@@ -233,10 +144,10 @@ __global__ void __launch_bounds__(PC_NT) pc_insert_kernel(PCCellArgs<P, T> a)
     const long long i = (long long)blockIdx.x * PC_NT + threadIdx.x;
     long long q[3];
     unsigned long long key = PC_EMPTY;
-    if (pc_cell(a, i, q)) key = ((unsigned long long)q[0] << (2 * PC_AXIS_BITS)) | ((unsigned long long)q[1] << PC_AXIS_BITS) | (unsigned long long)q[2];
+    if (pc_cell(a, i, q)) key = lt_key(q[0], q[1], q[2]);
     if (pc_run_head(key) && key != PC_EMPTY) {
         pc_hash_insert(a.table, a.mask, a.list, a.n_list, key);
-        pc_hash_insert(a.table, a.mask, a.list, a.n_list, key + PC_DIAG);
+        pc_hash_insert(a.table, a.mask, a.list, a.n_list, key + lt_key(1, 1, 1));      // the diagonal cell
     }
 }
 
@@ -286,8 +197,8 @@ __global__ void __launch_bounds__(PC_NT) pc_emit_keys_kernel(const unsigned long
 {
     const long long t = (long long)blockIdx.x * PC_NT + threadIdx.x;
     if (t >= m) return;
-    const unsigned long long key = list[t], am = (unsigned long long)PC_AXIS_MAX - 1;
-    const long long q[3] = {(long long)(key >> (2 * PC_AXIS_BITS)), (long long)((key >> PC_AXIS_BITS) & am), (long long)(key & am)};
+    long long q[3];
+    lt_unkey(list[t], q);
     pc_emit(e, t, q);
 }
 

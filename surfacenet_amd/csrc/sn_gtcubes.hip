@@ -3,25 +3,18 @@
 // the device forms of the two per-batch entries are asynchronous on the context's stream.
 #include "sn_internal.h"
 #include "gtcubes.h"
-#include "scan.h"
 
 namespace {
 
 constexpr long long GT_MAX_POINTS = 1ll << 27;       // hash tables of 2n slots stay within 2^28 (int32 indices and scan lengths)
 
-unsigned blocks(long long n) { return (unsigned)((n + GT_NT - 1) / GT_NT); }
-
 // The arrays of a bound cloud of n points inside the context's gt_ws; the same sequence sizes the buffer and places the arrays.
-struct GTBufs {
-    float *sorted; unsigned long long *keys; int *start, *count, *sums, *slot, *pos; GTStats *st;
-    unsigned cap;
-};
+struct GTBufs { CGBufs<float> g; CGStats<unsigned> *st; };
 
 void gt_layout(Carve &cv, GTBufs &b, long long n)
 {
-    b.cap = (unsigned)table_cap((unsigned long long)n, 2, 1024);
-    b.sorted = cv.get<float>(3 * (size_t)n); b.keys = cv.get<unsigned long long>(b.cap); b.start = cv.get<int>(b.cap); b.count = cv.get<int>(b.cap);
-    b.sums = cv.get<int>(scan_sums(b.cap)); b.slot = cv.get<int>(n); b.pos = cv.get<int>(n); b.st = cv.get<GTStats>(1);
+    grid_layout(cv, b.g, n, false, false);
+    b.st = cv.get<CGStats<unsigned>>(1);
 }
 
 int gt_bind_device(sn_ctx *c, long long n, const float *pts_dev, double cell)
@@ -33,45 +26,33 @@ int gt_bind_device(sn_ctx *c, long long n, const float *pts_dev, double cell)
     }
     int rc;
     GTBufs b;
-    Carve sizing;
-    gt_layout(sizing, b, n);
-    if ((rc = dev_reserve(c, c->gt_ws, sizing.off)) != SN_OK) return rc;
-    Carve cv{c->gt_ws.as<unsigned char>()};
-    gt_layout(cv, b, n);
-    GTStats st;
+    if ((rc = dev_carve(c, c->gt_ws, [&](Carve &cv) { gt_layout(cv, b, n); })) != SN_OK) return rc;
+    CGStats<unsigned> st;
     {
         ProfScope ps(c, "gt_bounds", 0, (double)n * 12.0);
-        hipLaunchKernelGGL(gt_stats_init_kernel, dim3(1), dim3(64), 0, c->stream, b.st);
-        hipLaunchKernelGGL(gt_bounds_kernel, dim3(std::min(blocks(n), 2048u)), dim3(GT_NT), 0, c->stream, pts_dev, n, b.st);
+        hipLaunchKernelGGL(cg_stats_init_kernel<unsigned>, dim3(1), dim3(64), 0, c->stream, b.st);
+        hipLaunchKernelGGL((cg_bounds_kernel<float, false, GTPoints>), dim3(std::min(blocks(n, CG_NT), 2048u)), dim3(CG_NT), 0, c->stream, GTPoints{pts_dev}, n, b.st);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipMemcpyAsync(&st, b.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (st.flags & GT_FLAG_NONFINITE) return fail(SN_ERR_ARG, "a coordinate is not finite");
-    GTBuildArgs a;
-    memset(&a, 0, sizeof a);
-    a.pts = pts_dev; a.n = n; a.cell = cell;
+    if (st.flags & CG_FLAG_NONFINITE) return fail(SN_ERR_ARG, "a coordinate is not finite");
+    double o[3];
+    long long dim[3];
     for (int d = 0; d < 3; ++d) {
-        a.o[d] = (double)gt_decode(st.kmin[d]);
-        const double top = std::floor(((double)gt_decode(st.kmax[d]) - a.o[d]) / cell);       // the largest cell index of the axis
-        if (!(top >= 0.0 && top + 1.0 < (double)GT_AXIS_MAX))
-            return fail(SN_ERR_ARG, "axis %d spans %g cells of edge %g: cell indices must stay below 2^%d", d, top + 1.0, cell, GT_AXIS_BITS);
-        a.dim[d] = (long long)top + 1;
+        o[d] = (double)lt_decode(st.kmin[d]);
+        const double top = std::floor(((double)lt_decode(st.kmax[d]) - o[d]) / cell);       // the largest cell index of the axis
+        if (!(top >= 0.0 && top + 1.0 < (double)LT_AXIS_MAX))
+            return fail(SN_ERR_ARG, "axis %d spans %g cells of edge %g: cell indices must stay below 2^%d", d, top + 1.0, cell, LT_AXIS_BITS);
+        dim[d] = (long long)top + 1;
     }
-    a.keys = b.keys; a.count = b.count; a.start = b.start; a.slot = b.slot; a.pos = b.pos; a.sorted = b.sorted; a.mask = b.cap - 1;
     {
-        ProfScope ps(c, "gt_bind", 0, (double)n * (12.0 * 3 + 16.0) + (double)b.cap * 24.0);
-        HIPCHK(hipMemsetAsync(b.keys, 0xff, sizeof(unsigned long long) * b.cap, c->stream));
-        HIPCHK(hipMemsetAsync(b.count, 0, sizeof(int) * b.cap, c->stream));
-        hipLaunchKernelGGL(gt_insert_kernel, dim3(blocks(n)), dim3(GT_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
-        if ((rc = scan_exclusive(c, b.count, b.start, (int)b.cap, b.sums)) != SN_OK) return rc;
-        hipLaunchKernelGGL(gt_scatter_kernel, dim3(blocks(n)), dim3(GT_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        ProfScope ps(c, "gt_bind", 0, (double)n * (12.0 * 3 + 16.0) + (double)b.g.cap * 24.0);
+        if ((rc = grid_build(c, b.g, grid_of(b.g, o, cell, dim), pts_dev, nullptr, nullptr, true)) != SN_OK) return rc;
     }
     HIPCHK(hipStreamSynchronize(c->stream));            // the caller's points may go once the call returns
     c->gt_n = n; c->gt_cell = cell;
-    for (int d = 0; d < 3; ++d) { c->gt_o[d] = a.o[d]; c->gt_dim[d] = a.dim[d]; }
+    for (int d = 0; d < 3; ++d) { c->gt_o[d] = o[d]; c->gt_dim[d] = dim[d]; }
     c->gt_bound = true;
     return SN_OK;
 }
@@ -95,10 +76,8 @@ int gt_cubes_device(sn_ctx *c, int n, const float *xyz_dev, const float *resol_d
         GTBufs b;
         Carve cv{c->gt_ws.as<unsigned char>()};
         gt_layout(cv, b, c->gt_n);
-        a.g.pts = b.sorted; a.g.keys = b.keys; a.g.start = b.start; a.g.count = b.count; a.g.mask = b.cap - 1;
+        a.g = grid_of(b.g, c->gt_o, c->gt_cell, c->gt_dim);
     }
-    a.g.n = c->gt_n; a.g.cell = c->gt_cell;
-    for (int d = 0; d < 3; ++d) { a.g.o[d] = c->gt_o[d]; a.g.dim[d] = c->gt_dim[d]; }
     const size_t s3 = (size_t)c->s * c->s * c->s;
     a.xyz = xyz_dev; a.resol = resol_dev; a.Y = Y_dev; a.s = c->s; a.err = c->d_err;
     a.vec = (s3 % 4 == 0 && (reinterpret_cast<uintptr_t>(Y_dev) & 15) == 0) ? 1 : 0;

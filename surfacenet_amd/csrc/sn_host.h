@@ -25,6 +25,9 @@ static int fail(int code, const char *fmt, ...)
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
+// workgroups of nt threads that cover n items
+static inline unsigned blocks(long long n, int nt) { return (unsigned)((n + nt - 1) / nt); }
+
 // Slots of an open-addressing hash table of n keys: the smallest power of two >= factor * n, at least min_cap (a power of two).
 static inline size_t table_cap(unsigned long long n, unsigned factor, size_t min_cap)
 {

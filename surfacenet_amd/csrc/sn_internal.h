@@ -5,7 +5,7 @@
 // the context, owned device memory and the buffers that grow on demand (DevBuf), temporary device arrays with their host staging (TmpDev),
 // HIP-event profiling, ConvKernel (one conv3d_f16_mfma instantiation as a type: its packing geometry and its launcher) and
 // the plan rows - which kernel runs which layer - that the weight packers and the forward passes walk. What needs no device is in two hip-free
-// headers: sn_host.h (error text, table sizes, Carve, the packed-list checks) and sn_pack.h (PackedConv and the host half of weight packing).
+// headers: sn_host.h (error text, table sizes, Carve, blocks, the packed-list checks) and sn_pack.h (PackedConv and the host half of weight packing).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -215,6 +215,20 @@ static int dev_reserve(sn_ctx *c, DevBuf &b, size_t need, size_t extra = 0)
     int rc = dev_alloc(c, &q, need + extra);
     if (rc != SN_OK) return rc;
     b.p = q; b.bytes = need + extra;
+    return SN_OK;
+}
+
+// Places a call's arrays in b. `layout(Carve &)` is the call's sequence of get(): it runs once without a base to measure, b grows to that size
+// (+ slack), and it runs again to place (sn_host.h, Carve).
+template <typename F>
+static int dev_carve(sn_ctx *c, DevBuf &b, F &&layout, size_t slack = 0)
+{
+    Carve measure;
+    layout(measure);
+    int rc = dev_reserve(c, b, measure.off + slack);
+    if (rc != SN_OK) return rc;
+    Carve place{b.as<unsigned char>()};
+    layout(place);
     return SN_OK;
 }
 

@@ -16,8 +16,6 @@ struct SyncOnExit {                                  // temporary device buffers
     ~SyncOnExit() { (void)hipStreamSynchronize(c->stream); }
 };
 
-unsigned blocks(long long n) { return (unsigned)((n + MS_NT - 1) / MS_NT); }
-
 int ms_check_args(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long cap_verts, long long cap_quads, long long *n_verts, long long *n_quads)
 {
     if (!c) return fail(SN_ERR_ARG, "null context");
@@ -56,12 +54,8 @@ int ms_run(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long total, const int6
         tb.cell = w.get<unsigned long long>(2 * (size_t)cap);
         tb.brick = w.get<unsigned long long>(2 * (size_t)cap);
     };
-    Carve measure;
-    layout1(measure);
-    int rc = dev_reserve(c, c->ms_ws, measure.off + 256);
+    int rc = dev_carve(c, c->ms_ws, layout1, 256);
     if (rc != SN_OK) return rc;
-    Carve w1{c->ms_ws.as<unsigned char>()};
-    layout1(w1);
     in.off = off; in.ijk = ijk; in.cube_ijk = cube_ijk; in.mask = mask; in.normals = normals; in.total = total; in.n = n; in.stride = cfg->stride_vox;
     tb.cmask = tb.bmask = cap - 1;
     unsigned long long cnt[MS_CNT_WORDS] = {0, 0, 0, 0};
@@ -75,7 +69,7 @@ int ms_run(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long total, const int6
         ProfScope ps(c, "ms_cells", 0, (double)total * 28.0 + (double)cap * 32.0);
         HIPCHK(hipMemsetAsync(tb.cell, 0, sizeof(unsigned long long) * 2 * (size_t)cap, c->stream));
         HIPCHK(hipMemsetAsync(tb.brick, 0, sizeof(unsigned long long) * 2 * (size_t)cap, c->stream));
-        hipLaunchKernelGGL(ms_insert_kernel, dim3(blocks(total)), dim3(MS_NT), 0, c->stream, in, tb);
+        hipLaunchKernelGGL(ms_insert_kernel, dim3(blocks(total, MS_NT)), dim3(MS_NT), 0, c->stream, in, tb);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipMemcpyAsync(cnt, in.cnt, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
@@ -83,12 +77,12 @@ int ms_run(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long total, const int6
     if (cnt[MS_CNT_FLAGS] & MS_FLAG_TABLE) return fail(SN_ERR_ARG, "offsets table does not start at 0, decreases, or does not end at total = %lld", total);
     if (cnt[MS_CNT_FLAGS] & MS_FLAG_NORMAL) return fail(SN_ERR_ARG, "a masked voxel's normal has a component that is not finite or exceeds 2 in magnitude");
     if (cnt[MS_CNT_FLAGS] & MS_FLAG_CELL)
-        return fail(SN_ERR_ARG, "a masked voxel's world cell (cube_ijk * %d + vxl_ijk) plus %d reaches 2^%d on an axis", cfg->stride_vox, MS_MARGIN, NM_AXIS_BITS);
+        return fail(SN_ERR_ARG, "a masked voxel's world cell (cube_ijk * %d + vxl_ijk) plus %d reaches 2^%d on an axis", cfg->stride_vox, MS_MARGIN, LT_AXIS_BITS);
     if (total == 0) return SN_OK;
     {
         ProfScope ps(c, "ms_bricks", 0, (double)total * 20.0 + (double)cap * 8.0);
-        hipLaunchKernelGGL(ms_bricks_kernel, dim3(blocks(total)), dim3(MS_NT), 0, c->stream, in, tb);
-        hipLaunchKernelGGL(ms_count_kernel, dim3(blocks(cap)), dim3(MS_NT), 0, c->stream, (const unsigned long long *)tb.brick, cap, in.cnt + MS_CNT_BRICKS);
+        hipLaunchKernelGGL(ms_bricks_kernel, dim3(blocks(total, MS_NT)), dim3(MS_NT), 0, c->stream, in, tb);
+        hipLaunchKernelGGL(ms_count_kernel, dim3(blocks(cap, MS_NT)), dim3(MS_NT), 0, c->stream, (const unsigned long long *)tb.brick, cap, in.cnt + MS_CNT_BRICKS);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipMemcpyAsync(cnt, in.cnt, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
@@ -105,17 +99,13 @@ int ms_run(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long total, const int6
         tb.rank = w.get<int>(kcap);
         list = w.get<unsigned long long>(kcap / 2);  // >= 27 nb keys, a power of two >= PC_TILE: room for the sort's padding
     };
-    Carve measure2;
-    layout2(measure2);
-    if ((rc = dev_reserve(c, c->ms_tab, measure2.off + 256)) != SN_OK) return rc;
-    Carve w2{c->ms_tab.as<unsigned char>()};
-    layout2(w2);
+    if ((rc = dev_carve(c, c->ms_tab, layout2, 256)) != SN_OK) return rc;
     tb.kmask = kcap - 1;
     {
         ProfScope ps(c, "ms_cand", 0, (double)cap * 16.0 + (double)kcap * 40.0);
         HIPCHK(hipMemsetAsync(tb.cand, 0, sizeof(unsigned long long) * 2 * (size_t)kcap, c->stream));
-        hipLaunchKernelGGL(ms_cand_kernel, dim3(blocks(cap)), dim3(MS_NT), 0, c->stream, tb);
-        hipLaunchKernelGGL(ms_list_kernel, dim3(blocks(kcap)), dim3(MS_NT), 0, c->stream, tb, list, in.cnt + MS_CNT_CAND);
+        hipLaunchKernelGGL(ms_cand_kernel, dim3(blocks(cap, MS_NT)), dim3(MS_NT), 0, c->stream, tb);
+        hipLaunchKernelGGL(ms_list_kernel, dim3(blocks(kcap, MS_NT)), dim3(MS_NT), 0, c->stream, tb, list, in.cnt + MS_CNT_CAND);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipMemcpyAsync(cnt, in.cnt, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
@@ -128,11 +118,11 @@ int ms_run(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long total, const int6
         const long long p2 = (long long)table_cap(ncu, 1, PC_TILE);
         if (p2 > nc) {
             ProfScope ps(c, "ms_pad", 0, (double)(p2 - nc) * 8.0);
-            hipLaunchKernelGGL(pc_pad_kernel, dim3(blocks(p2 - nc)), dim3(PC_NT), 0, c->stream, list, (long long)nc, p2);
+            hipLaunchKernelGGL(pc_pad_kernel, dim3(blocks(p2 - nc, PC_NT)), dim3(PC_NT), 0, c->stream, list, (long long)nc, p2);
         }
         if ((rc = pc_sort(c, list, p2)) != SN_OK) return rc;      // (its own profile tag, pc_sort)
         ProfScope ps(c, "ms_rank", 0, (double)nc * 28.0);
-        hipLaunchKernelGGL(ms_rank_kernel, dim3(blocks(nc)), dim3(MS_NT), 0, c->stream, tb, (const unsigned long long *)list, nc);
+        hipLaunchKernelGGL(ms_rank_kernel, dim3(blocks(nc, MS_NT)), dim3(MS_NT), 0, c->stream, tb, (const unsigned long long *)list, nc);
         HIPCHK(hipGetLastError());
     }
 
@@ -150,11 +140,7 @@ int ms_run(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long total, const int6
         f.qstart = w.get<int>((size_t)nc + 1);
         sums = w.get<int>(scan_sums((size_t)nc + 1));
     };
-    Carve measure3;
-    layout3(measure3);
-    if ((rc = dev_reserve(c, c->ms_field, measure3.off + 256)) != SN_OK) return rc;
-    Carve w3{c->ms_field.as<unsigned char>()};
-    layout3(w3);
+    if ((rc = dev_carve(c, c->ms_field, layout3, 256)) != SN_OK) return rc;
     f.list = list; f.radius = cfg->radius; f.reach = cfg->reach;
     HIPCHK(hipMemsetAsync(f.vstart + nc, 0, sizeof(int), c->stream));
     HIPCHK(hipMemsetAsync(f.qstart + nc, 0, sizeof(int), c->stream));

@@ -34,12 +34,8 @@ int msmp_run(sn_ctx *c, int V, const double *verts, int F, const int32_t *faces,
         off = w.get<int>((size_t)F + 1);
         sums = w.get<int>(scan_sums((size_t)F + 1));
     };
-    Carve measure;
-    layout(measure);
-    int rc = dev_reserve(c, c->msmp_ws, measure.off + 256);
+    int rc = dev_carve(c, c->msmp_ws, layout, 256);
     if (rc != SN_OK) return rc;
-    Carve w{c->msmp_ws.as<unsigned char>()};
-    layout(w);
     MsmpIn in;
     memset(&in, 0, sizeof in);
     in.verts = verts; in.faces = faces; in.V = V; in.F = F; in.dst2 = dst * dst;

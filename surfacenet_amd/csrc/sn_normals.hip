@@ -7,40 +7,46 @@ namespace {
 
 constexpr long long NM_MAX_VOXELS = 1ll << 28;       // hash tables of >= 2 * total slots stay within 2^29
 
-// One call's arrays: the inputs and outputs (the caller's device arrays, or staged copies of host arrays) and the work buffers.
+// One call's arrays: the inputs and outputs (the caller's device arrays; in a host form the caller's host arrays until nm_prepare has staged
+// them) and the work buffers.
 struct NMCall {
     int n = 0, K = 0, V = 0;
     long long total = 0;
-    bool host = false, unique = false;
+    bool host = false, unique = false, staged = true;      // staged: no upload has failed
     const int64_t *off = nullptr; const uint8_t *ijk = nullptr, *mask = nullptr; const uint32_t *cube_ijk = nullptr;
     const float *xyz = nullptr, *resol = nullptr; const int32_t *view = nullptr; const double *cams = nullptr;
     float *normals = nullptr; int32_t *moments = nullptr; uint8_t *keep = nullptr;
     // work
     unsigned cap = 0;
     int *flags = nullptr, *cube_of = nullptr; double *cbar = nullptr; unsigned long long *tab = nullptr;
-    // which staged arrays the host form needs
-    bool want_normals = false, want_moments = false;
 };
 
-template <typename T> void nm_stage(Carve &w, bool host, T *&p, size_t count, bool wanted = true)
+// Host forms stage their arrays in the context's workspace, not in temporary allocations: one buffer that grows serves normals and unique
+// voxels alike, call after call, with no allocation in the steady state (tests/test_gpu_workspace.py holds that up). A host array that was
+// given gets room in the workspace; the placing pass uploads it (an input) and swaps the pointer for the device copy.
+template <typename T> void nm_stage(sn_ctx *c, Carve &w, NMCall &k, T *&p, size_t count, bool input)
 {
-    if (host && wanted) p = w.get<typename std::remove_const<T>::type>(count);
+    if (!k.host || !p) return;
+    auto *d = w.get<typename std::remove_const<T>::type>(count);
+    if (!w.base) return;
+    if (input && count && hipMemcpyAsync(d, p, sizeof(T) * count, hipMemcpyHostToDevice, c->stream) != hipSuccess) k.staged = false;
+    p = d;
 }
 
-void nm_layout(Carve &w, NMCall &k)
+void nm_layout(sn_ctx *c, Carve &w, NMCall &k)
 {
     const size_t n = (size_t)k.n, T = (size_t)k.total;
-    nm_stage(w, k.host, k.off, n + 1);
-    nm_stage(w, k.host, k.cube_ijk, 3 * n);
-    nm_stage(w, k.host, k.ijk, 3 * T);
-    nm_stage(w, k.host, k.mask, T);
-    nm_stage(w, k.host, k.xyz, 3 * n, k.want_normals);
-    nm_stage(w, k.host, k.resol, n, k.want_normals);
-    nm_stage(w, k.host, k.view, n * (size_t)k.K, k.want_normals);
-    nm_stage(w, k.host, k.cams, 3 * (size_t)k.V, k.want_normals);
-    nm_stage(w, k.host, k.normals, 3 * T, k.want_normals);
-    nm_stage(w, k.host, k.moments, 10 * T, k.want_moments);
-    nm_stage(w, k.host, k.keep, T, k.unique);
+    nm_stage(c, w, k, k.off, n + 1, true);
+    nm_stage(c, w, k, k.cube_ijk, 3 * n, true);
+    nm_stage(c, w, k, k.ijk, 3 * T, true);
+    nm_stage(c, w, k, k.mask, T, true);
+    nm_stage(c, w, k, k.xyz, 3 * n, true);
+    nm_stage(c, w, k, k.resol, n, true);
+    nm_stage(c, w, k, k.view, n * (size_t)k.K, true);
+    nm_stage(c, w, k, k.cams, 3 * (size_t)k.V, true);
+    nm_stage(c, w, k, k.normals, 3 * T, false);
+    nm_stage(c, w, k, k.moments, 10 * T, false);
+    nm_stage(c, w, k, k.keep, T, false);
     k.flags = w.get<int>(1);
     k.cube_of = w.get<int>(T);
     k.cbar = w.get<double>(3 * n);
@@ -50,14 +56,9 @@ void nm_layout(Carve &w, NMCall &k)
 int nm_prepare(sn_ctx *c, NMCall &k)
 {
     k.cap = (unsigned)table_cap((unsigned long long)k.total, 2, 64);
-    Carve measure;
-    NMCall probe = k;
-    nm_layout(measure, probe);
-    int rc = dev_reserve(c, c->nm_ws, measure.off + 256);
-    if (rc != SN_OK) return rc;
-    Carve w{c->nm_ws.as<unsigned char>()};
-    nm_layout(w, k);
-    return SN_OK;
+    int rc = dev_carve(c, c->nm_ws, [&](Carve &w) { nm_layout(c, w, k); }, 256);
+    if (rc == SN_OK && !k.staged) { (void)hipStreamSynchronize(c->stream); rc = fail(SN_ERR_HIP, "staging the host arrays failed"); }
+    return rc;
 }
 
 int nm_check_common(sn_ctx *c, int n, int stride_vox)
@@ -99,7 +100,7 @@ int nm_run(sn_ctx *c, NMCall &k, const sn_normals_cfg *cfg, int stride_vox)
     a.off = k.off; a.ijk = k.ijk; a.cube_ijk = k.cube_ijk; a.mask = k.mask; a.cube_xyz = k.xyz; a.cube_resol = k.resol; a.cbar = k.cbar;
     a.cube_of = k.cube_of; a.tab = k.tab; a.flags = k.flags; a.normals = k.normals; a.moments = k.moments;
     a.total = total; a.hmask = k.cap - 1; a.n = n; a.stride = stride_vox; a.radius = cfg ? cfg->radius : 0; a.min_nb = cfg ? cfg->min_neighbours : 0;
-    const unsigned nb = (unsigned)((total + NM_NT - 1) / NM_NT);
+    const unsigned nb = blocks(total, NM_NT);
     if (total > 0) {
         ProfScope ps(c, k.unique ? "nm_cells" : "nm_bricks", 0, (double)total * 12.0 + (double)k.cap * 16.0);
         HIPCHK(hipMemsetAsync(k.tab, 0, sizeof(unsigned long long) * 2 * (size_t)k.cap, c->stream));
@@ -113,7 +114,7 @@ int nm_run(sn_ctx *c, NMCall &k, const sn_normals_cfg *cfg, int stride_vox)
     if (flags & NM_FLAG_TABLE) return fail(SN_ERR_ARG, "offsets table does not start at 0, decreases, or does not end at total = %lld", total);
     if (flags & NM_FLAG_VIEW) return fail(SN_ERR_ARG, "a view index lies outside [0, %d)", k.V);
     if (flags & NM_FLAG_CELL)
-        return fail(SN_ERR_ARG, "a masked voxel's world cell (cube_ijk * %d + vxl_ijk) plus the radius %d reaches 2^%d on an axis", stride_vox, a.radius, NM_AXIS_BITS);
+        return fail(SN_ERR_ARG, "a masked voxel's world cell (cube_ijk * %d + vxl_ijk) plus the radius %d reaches 2^%d on an axis", stride_vox, a.radius, LT_AXIS_BITS);
     if (total == 0) return SN_OK;
     if (k.unique) {
         ProfScope ps(c, "nm_owner", 0, (double)total * 10.0);
@@ -125,12 +126,6 @@ int nm_run(sn_ctx *c, NMCall &k, const sn_normals_cfg *cfg, int stride_vox)
         HIPCHK(hipGetLastError());
     }
     if (!k.host) HIPCHK(hipStreamSynchronize(c->stream));
-    return SN_OK;
-}
-
-template <typename T> int nm_upload(sn_ctx *c, const T *dst_dev, const T *src, size_t count)
-{
-    if (count) HIPCHK(hipMemcpyAsync(const_cast<T *>(dst_dev), src, sizeof(T) * count, hipMemcpyHostToDevice, c->stream));
     return SN_OK;
 }
 
@@ -176,16 +171,11 @@ extern "C" int sn_normals(sn_ctx *c, int n, const sn_normals_cfg *cfg, const int
     }
     HIPCHK(hipSetDevice(c->device));
     NMCall k;
-    k.host = true; k.want_normals = normals != nullptr; k.want_moments = moments != nullptr;
-    k.n = n; k.total = total; k.K = cfg->views_per_cube; k.V = cfg->n_views;
+    k.host = true; k.n = n; k.total = total; k.K = cfg->views_per_cube; k.V = cfg->n_views;
+    k.off = offsets; k.ijk = ijk; k.cube_ijk = cube_ijk; k.mask = mask; k.normals = normals; k.moments = moments;
+    if (normals) { k.xyz = cube_xyz; k.resol = cube_resol; k.view = view_idx; k.cams = cameraTs; }
     if ((rc = nm_prepare(c, k)) != SN_OK) return rc;
-    const size_t N = (size_t)n, T = (size_t)total;
-    if ((rc = nm_upload(c, k.off, offsets, N + 1)) != SN_OK || (rc = nm_upload(c, k.cube_ijk, cube_ijk, 3 * N)) != SN_OK ||
-        (rc = nm_upload(c, k.ijk, ijk, 3 * T)) != SN_OK || (rc = nm_upload(c, k.mask, mask, T)) != SN_OK)
-        return rc;
-    if (normals && ((rc = nm_upload(c, k.xyz, cube_xyz, 3 * N)) != SN_OK || (rc = nm_upload(c, k.resol, cube_resol, N)) != SN_OK ||
-                    (rc = nm_upload(c, k.view, view_idx, N * (size_t)k.K)) != SN_OK || (rc = nm_upload(c, k.cams, cameraTs, 3 * (size_t)k.V)) != SN_OK))
-        return rc;
+    const size_t T = (size_t)total;
     if ((rc = nm_run(c, k, cfg, cfg->stride_vox)) != SN_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
     if (normals && T) HIPCHK(hipMemcpyAsync(normals, k.normals, sizeof(float) * 3 * T, hipMemcpyDeviceToHost, c->stream));
     if (moments && T) HIPCHK(hipMemcpyAsync(moments, k.moments, sizeof(int32_t) * 10 * T, hipMemcpyDeviceToHost, c->stream));
@@ -222,11 +212,9 @@ extern "C" int sn_unique_voxels(sn_ctx *c, int n, int stride_vox, const int64_t 
     HIPCHK(hipSetDevice(c->device));
     NMCall k;
     k.host = true; k.unique = true; k.n = n; k.total = total;
+    k.off = offsets; k.ijk = ijk; k.cube_ijk = cube_ijk; k.mask = mask; k.keep = keep;
     if ((rc = nm_prepare(c, k)) != SN_OK) return rc;
-    const size_t N = (size_t)n, T = (size_t)total;
-    if ((rc = nm_upload(c, k.off, offsets, N + 1)) != SN_OK || (rc = nm_upload(c, k.cube_ijk, cube_ijk, 3 * N)) != SN_OK ||
-        (rc = nm_upload(c, k.ijk, ijk, 3 * T)) != SN_OK || (rc = nm_upload(c, k.mask, mask, T)) != SN_OK)
-        return rc;
+    const size_t T = (size_t)total;
     if ((rc = nm_run(c, k, nullptr, stride_vox)) != SN_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
     if (T) HIPCHK(hipMemcpyAsync(keep, k.keep, T, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

@@ -2,7 +2,6 @@
 // mask / plane flags of PointCompareMain (experiments/DTU/eval_ply.m). Host arrays in and out; the device workspace is the context's.
 #include "sn_internal.h"
 #include "pointeval.h"
-#include "scan.h"
 
 namespace {
 
@@ -33,50 +32,17 @@ double fit_h(double h, const Box &b)
     return (h > 0 && std::isfinite(h)) ? h : 1.0;
 }
 
-struct GridBufs {
-    unsigned long long *keys; int *start, *count, *slot, *pos, *idx, *rank_s, *sums; double *xyz_s;
-    unsigned cap; int n;
-};
+typedef CGBufs<double> GridBufs;
 
-void grid_carve(Carve &cv, GridBufs &b, long long n, bool with_rank)
-{
-    b.n = (int)n; b.cap = (unsigned)table_cap((unsigned long long)n, 2, 1024);
-    b.keys = cv.get<unsigned long long>(b.cap); b.start = cv.get<int>(b.cap); b.count = cv.get<int>(b.cap); b.sums = cv.get<int>(scan_sums(b.cap));
-    b.slot = cv.get<int>(n); b.pos = cv.get<int>(n); b.idx = cv.get<int>(n); b.xyz_s = cv.get<double>(3 * (size_t)n);
-    b.rank_s = with_rank ? cv.get<int>(n) : nullptr;
-}
-
-// Buckets xyz_dev (n points inside box) on cells of size h: the hash table and the per-cell counts; with `sort`, also the scan and the
-// cell-sorted copy (and ranks). occ_dev receives the number of occupied cells.
+// Buckets xyz_dev (n points inside box) on cells of size h (grid_build of cellgrid.h, as one "pe_grid" of the profile).
 int pe_build(sn_ctx *c, const GridBufs &b, const double *xyz_dev, const long long *rank_dev, const Box &box, double h, int *occ_dev, bool sort,
              PEGrid &g)
 {
-    memset(&g, 0, sizeof g);
-    PEBuildArgs a;
-    memset(&a, 0, sizeof a);
-    for (int d = 0; d < 3; ++d) {
-        g.o[d] = a.o[d] = box.lo[d];
-        g.lo[d] = box.lo[d]; g.hi[d] = box.hi[d];
-        g.dim[d] = a.dim[d] = (long long)std::floor((box.hi[d] - box.lo[d]) / h) + 1;
-    }
-    g.h = a.h = h;
-    g.mask = a.mask = b.cap - 1;
-    g.keys = b.keys; g.start = b.start; g.count = b.count; g.xyz = b.xyz_s; g.idx = b.idx;
-    a.xyz = xyz_dev; a.rank = rank_dev; a.keys = b.keys; a.start = b.start; a.count = b.count; a.slot = b.slot; a.pos = b.pos; a.idx = b.idx;
-    a.rank_s = b.rank_s; a.xyz_s = b.xyz_s; a.occupied = occ_dev; a.n = b.n;
-    const unsigned nb = (unsigned)((b.n + PE_NT - 1) / PE_NT);
+    long long dim[3];
+    for (int d = 0; d < 3; ++d) dim[d] = (long long)std::floor((box.hi[d] - box.lo[d]) / h) + 1;
+    g = grid_of(b, box.lo, h, dim);
     ProfScope ps(c, "pe_grid", 0, (double)b.n * (sort ? 24.0 * 2 + 20.0 : 24.0 + 12.0) + (double)b.cap * (sort ? 24.0 : 12.0));
-    HIPCHK(hipMemsetAsync(b.keys, 0xff, sizeof(unsigned long long) * b.cap, c->stream));
-    HIPCHK(hipMemsetAsync(b.count, 0, sizeof(int) * b.cap, c->stream));
-    HIPCHK(hipMemsetAsync(occ_dev, 0, sizeof(int), c->stream));
-    hipLaunchKernelGGL(pe_insert_kernel, dim3(nb), dim3(PE_NT), 0, c->stream, a);
-    HIPCHK(hipGetLastError());
-    if (!sort) return SN_OK;
-    int rc = scan_exclusive(c, b.count, b.start, (int)b.cap, b.sums);
-    if (rc != SN_OK) return rc;
-    hipLaunchKernelGGL(pe_scatter_kernel, dim3(nb), dim3(PE_NT), 0, c->stream, a);
-    HIPCHK(hipGetLastError());
-    return SN_OK;
+    return grid_build(c, b, g, xyz_dev, rank_dev, occ_dev, sort);
 }
 
 int read_int(sn_ctx *c, const int *dev, int *host)
@@ -119,13 +85,9 @@ extern "C" int sn_point_reduce(sn_ctx *c, long long n, const double *xyz, const 
     auto layout = [&](Carve &cv) {
         d_xyz = cv.get<double>(3 * (size_t)n); d_rank = cv.get<long long>(n); d_state = cv.get<unsigned char>(n); d_keep = cv.get<unsigned char>(n);
         d_occ = cv.get<int>(1); d_und = cv.get<unsigned long long>(1);
-        grid_carve(cv, gb, n, true);
+        grid_layout(cv, gb, n, true, true);
     };
-    Carve sizing;
-    layout(sizing);
-    if ((rc = dev_reserve(c, c->pe_ws, sizing.off)) != SN_OK) return rc;
-    Carve cv{c->pe_ws.as<unsigned char>()};
-    layout(cv);
+    if ((rc = dev_carve(c, c->pe_ws, layout)) != SN_OK) return rc;
     HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(d_rank, rank, sizeof(long long) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     // cells a little larger than dst: a pair at d^2 <= dst^2 is never more than one cell apart, whatever the rounding of the cell index
@@ -134,7 +96,7 @@ extern "C" int sn_point_reduce(sn_ctx *c, long long n, const double *xyz, const 
     HIPCHK(hipMemsetAsync(d_state, PE_UND, (size_t)n, c->stream));
     PEReduceArgs a;
     a.g = g; a.rank = gb.rank_s; a.state = d_state; a.undecided = d_und; a.dst2 = dst * dst; a.n = (int)n;
-    const unsigned nb = (unsigned)((n + PE_NT - 1) / PE_NT);
+    const unsigned nb = blocks(n, PE_NT);
     int r = 0;
     for (;;) {
         if (r >= PE_MAX_ROUNDS) { (void)hipStreamSynchronize(c->stream); return fail(SN_ERR_STATE, "point reduction: undecided points left after %d rounds", r); }
@@ -180,13 +142,9 @@ extern "C" int sn_nn_dist2(sn_ctx *c, long long n_to, const double *to, long lon
     auto layout = [&](Carve &cv) {
         d_to = cv.get<double>(3 * (size_t)n_to); d_from = cv.get<double>(3 * (size_t)n_from); d_best = cv.get<double>(n_from); d_d2 = cv.get<double>(n_from);
         d_far = cv.get<int>(n_from); d_nfar = cv.get<int>(1); d_occ = cv.get<int>(1);
-        grid_carve(cv, gf, n_to, false); grid_carve(cv, gc, n_to, false); grid_carve(cv, gq, n_from, false);
+        grid_layout(cv, gf, n_to, true, false); grid_layout(cv, gc, n_to, true, false); grid_layout(cv, gq, n_from, true, false);
     };
-    Carve sizing;
-    layout(sizing);
-    if ((rc = dev_reserve(c, c->pe_ws, sizing.off)) != SN_OK) return rc;
-    Carve cv{c->pe_ws.as<unsigned char>()};
-    layout(cv);
+    if ((rc = dev_carve(c, c->pe_ws, layout)) != SN_OK) return rc;
     HIPCHK(hipMemcpyAsync(d_to, to, sizeof(double) * 3 * (size_t)n_to, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(d_from, from, sizeof(double) * 3 * (size_t)n_from, hipMemcpyHostToDevice, c->stream));
     // fine cell size: a first bucketing at the box's mean spacing counts the occupied cells; the size is then scaled towards
@@ -212,11 +170,12 @@ extern "C" int sn_nn_dist2(sn_ctx *c, long long n_to, const double *to, long lon
     if ((rc = pe_build(c, gq, d_from, nullptr, bf, fit_h(a.coarse.h, bf), d_occ, true, qg)) != SN_OK) return rc;
     a.q = gq.xyz_s; a.q_idx = gq.idx; a.best = d_best; a.far_list = d_far; a.far_count = d_nfar; a.d2 = d_d2; a.n_q = (int)n_from;
     a.lim = max_dist * max_dist * (1.0 + 0x1p-40);
+    for (int d = 0; d < 3; ++d) { a.lo[d] = bt.lo[d]; a.hi[d] = bt.hi[d]; }
     double mag = 0;
     for (int d = 0; d < 3; ++d) mag = std::max({mag, std::fabs(bt.lo[d]), std::fabs(bt.hi[d])});
     a.slack = 1e-12 * (mag + 2.0 * a.coarse.h) + 1e-300;
     HIPCHK(hipMemsetAsync(d_nfar, 0, sizeof(int), c->stream));
-    const unsigned nb = (unsigned)((n_from + PE_NT - 1) / PE_NT);
+    const unsigned nb = blocks(n_from, PE_NT);
     {
         ProfScope ps(c, "pe_nn_near", 0, (double)n_from * 40.0);
         hipLaunchKernelGGL(pe_nn_near_kernel, dim3(nb), dim3(PE_NT), 0, c->stream, a);
@@ -254,11 +213,7 @@ extern "C" int sn_point_flags(sn_ctx *c, long long n, const double *xyz, const u
         d_xyz = cv.get<double>(3 * (size_t)n); d_mask = cv.get<unsigned char>(mbytes);
         d_in = cv.get<unsigned char>(in_mask ? n : 0); d_above = cv.get<unsigned char>(above ? n : 0);
     };
-    Carve sizing;
-    layout(sizing);
-    if ((rc = dev_reserve(c, c->pe_ws, sizing.off)) != SN_OK) return rc;
-    Carve cv{c->pe_ws.as<unsigned char>()};
-    layout(cv);
+    if ((rc = dev_carve(c, c->pe_ws, layout)) != SN_OK) return rc;
     HIPCHK(hipMemcpyAsync(d_xyz, xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
     if (mbytes) HIPCHK(hipMemcpyAsync(d_mask, mask, mbytes, hipMemcpyHostToDevice, c->stream));
     a.xyz = d_xyz; a.mask = d_mask; a.n = (int)n; a.res = res;
@@ -269,7 +224,7 @@ extern "C" int sn_point_flags(sn_ctx *c, long long n, const double *xyz, const u
     if (above) { a.above = d_above; for (int d = 0; d < 4; ++d) a.plane[d] = plane[d]; }
     {
         ProfScope ps(c, "pe_flags", 0, (double)n * 26.0);
-        hipLaunchKernelGGL(pe_flags_kernel, dim3((unsigned)((n + PE_NT - 1) / PE_NT)), dim3(PE_NT), 0, c->stream, a);
+        hipLaunchKernelGGL(pe_flags_kernel, dim3(blocks(n, PE_NT)), dim3(PE_NT), 0, c->stream, a);
         HIPCHK(hipGetLastError());
     }
     if (in_mask) HIPCHK(hipMemcpyAsync(in_mask, d_in, (size_t)n, hipMemcpyDeviceToHost, c->stream));

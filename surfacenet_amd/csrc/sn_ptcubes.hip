@@ -14,8 +14,6 @@ struct SyncOnExit {                                  // temporary device buffers
     ~SyncOnExit() { (void)hipStreamSynchronize(c->stream); }
 };
 
-unsigned blocks(long long n) { return (unsigned)((n + PC_NT - 1) / PC_NT); }
-
 int pc_check_cfg(const sn_ptcubes_cfg *cfg, long long n, long long cap, const long long *n_cells)
 {
     if (!cfg || !n_cells) return fail(SN_ERR_ARG, "null argument");
@@ -44,8 +42,8 @@ int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap,
     PCStats st;
     {
         ProfScope ps(c, "pc_bounds", 0, (double)n * 3.0 * sizeof(P));
-        hipLaunchKernelGGL(pc_stats_init_kernel, dim3(1), dim3(64), 0, c->stream, d_st);
-        hipLaunchKernelGGL((pc_bounds_kernel<P>), dim3(std::min(blocks(n), 2048u)), dim3(PC_NT), 0, c->stream, src, d_st);
+        hipLaunchKernelGGL(cg_stats_init_kernel<unsigned long long>, dim3(1), dim3(64), 0, c->stream, d_st);
+        hipLaunchKernelGGL((cg_bounds_kernel<double, true, PCPoints<P>>), dim3(std::min(blocks(n, CG_NT), 2048u)), dim3(CG_NT), 0, c->stream, src, n, d_st);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, c->stream));
@@ -60,12 +58,12 @@ int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap,
     memset(&e, 0, sizeof e);
     e.stride = cfg->stride_xyz; e.half = cfg->half;
     for (int d = 0; d < 3; ++d) {
-        a.shift[d] = (P)pc_decode(st.kmin[d]);
+        a.shift[d] = (P)lt_decode(st.kmin[d]);
         e.shift[d] = (double)a.shift[d];
-        const P rel = (P)pc_decode(st.kmax[d]) - a.shift[d];
+        const P rel = (P)lt_decode(st.kmax[d]) - a.shift[d];
         const T top = pc_floor_div<T>((T)rel, a.stride);       // floor_divide is monotone in its numerator: the largest index of the axis
-        if (!(top >= (T)0 && top + (T)1 < (T)PC_AXIS_MAX))
-            return fail(SN_ERR_ARG, "axis %d spans %g strides: cell indices must stay below 2^%d", d, (double)top + 2.0, PC_AXIS_BITS);
+        if (!(top >= (T)0 && top + (T)1 < (T)LT_AXIS_MAX))
+            return fail(SN_ERR_ARG, "axis %d spans %g strides: cell indices must stay below 2^%d", d, (double)top + 2.0, LT_AXIS_BITS);
         a.dim[d] = e.dim[d] = (long long)top + 2;
     }
     const bool dense = a.dim[0] * a.dim[1] <= PC_DENSE_CELLS && a.dim[0] * a.dim[1] * a.dim[2] <= PC_DENSE_CELLS;
@@ -83,11 +81,11 @@ int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap,
         HIPCHK(hipMemsetAsync(count + n_words, 0, sizeof(int), c->stream));
         {
             ProfScope ps(c, "pc_cells", 0, (double)n * 3.0 * sizeof(P) + (double)n_words * 8.0);
-            hipLaunchKernelGGL((pc_mark_kernel<P, T>), dim3(blocks(n)), dim3(PC_NT), 0, c->stream, a);
+            hipLaunchKernelGGL((pc_mark_kernel<P, T>), dim3(blocks(n, PC_NT)), dim3(PC_NT), 0, c->stream, a);
             HIPCHK(hipGetLastError());
         }
         ProfScope ps(c, "pc_scan", 0, (double)n_words * 20.0);
-        hipLaunchKernelGGL(pc_popc_kernel, dim3(blocks(n_words)), dim3(PC_NT), 0, c->stream, (const unsigned long long *)a.bitmap, n_words, count);
+        hipLaunchKernelGGL(pc_popc_kernel, dim3(blocks(n_words, PC_NT)), dim3(PC_NT), 0, c->stream, (const unsigned long long *)a.bitmap, n_words, count);
         int rc = scan_exclusive(c, count, start, n_words + 1, sums);       // start[n_words] = number of cells
         if (rc != SN_OK) return rc;
         int tot = 0;
@@ -106,7 +104,7 @@ int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap,
         HIPCHK(hipMemsetAsync(a.n_list, 0, sizeof(unsigned long long), c->stream));
         {
             ProfScope ps(c, "pc_cells", 0, (double)n * 3.0 * sizeof(P) + (double)tcap * 8.0);
-            hipLaunchKernelGGL((pc_insert_kernel<P, T>), dim3(blocks(n)), dim3(PC_NT), 0, c->stream, a);
+            hipLaunchKernelGGL((pc_insert_kernel<P, T>), dim3(blocks(n, PC_NT)), dim3(PC_NT), 0, c->stream, a);
             HIPCHK(hipGetLastError());
         }
         unsigned long long m = 0;
@@ -127,15 +125,15 @@ int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap,
     }
     if (dense) {
         ProfScope ps(c, "pc_emit", 0, (double)total * 24.0 + (double)n_words * 12.0);
-        hipLaunchKernelGGL(pc_emit_dense_kernel, dim3(blocks(n_words)), dim3(PC_NT), 0, c->stream, (const unsigned long long *)a.bitmap, (const int *)start, n_words, e);
+        hipLaunchKernelGGL(pc_emit_dense_kernel, dim3(blocks(n_words, PC_NT)), dim3(PC_NT), 0, c->stream, (const unsigned long long *)a.bitmap, (const int *)start, n_words, e);
         HIPCHK(hipGetLastError());
     } else {
         const long long p2 = (long long)table_cap((unsigned long long)total, 1, PC_TILE);
-        if (p2 > total) hipLaunchKernelGGL(pc_pad_kernel, dim3(blocks(p2 - total)), dim3(PC_NT), 0, c->stream, list, total, p2);
+        if (p2 > total) hipLaunchKernelGGL(pc_pad_kernel, dim3(blocks(p2 - total, PC_NT)), dim3(PC_NT), 0, c->stream, list, total, p2);
         int rc = pc_sort(c, list, p2);
         if (rc != SN_OK) return rc;
         ProfScope ps(c, "pc_emit", 0, (double)total * 32.0);
-        hipLaunchKernelGGL(pc_emit_keys_kernel, dim3(blocks(total)), dim3(PC_NT), 0, c->stream, (const unsigned long long *)list, total, e);
+        hipLaunchKernelGGL(pc_emit_keys_kernel, dim3(blocks(total, PC_NT)), dim3(PC_NT), 0, c->stream, (const unsigned long long *)list, total, e);
         HIPCHK(hipGetLastError());
     }
     if (out_host) {
@@ -206,7 +204,7 @@ extern "C" int sn_ptcubes_sparse_dev(sn_ctx *c, int n_cubes, long long total, co
     HIPCHK(hipSetDevice(c->device));
     PCPoints<float> s;
     memset(&s, 0, sizeof s);
-    s.off = reinterpret_cast<const long long *>(offsets_dev); s.vijk = vxl_ijk_dev; s.vmask = mask_dev; s.cxyz = cube_xyz_dev; s.cresol = cube_resol_dev;
+    s.off = offsets_dev; s.vijk = vxl_ijk_dev; s.vmask = mask_dev; s.cxyz = cube_xyz_dev; s.cresol = cube_resol_dev;
     s.n_cubes = n_cubes; s.n = total;
     return cfg->compute_f64 ? pc_run<float, double>(c, s, cfg, cap, false, ijk_dev, xyz_dev, n_cells)
                             : pc_run<float, float>(c, s, cfg, cap, false, ijk_dev, xyz_dev, n_cells);

@@ -54,12 +54,8 @@ int rt_step_device(sn_ctx *c, int n, int n_vp, const float *U, const float *F, c
     const size_t V = (size_t)c->s * c->s * c->s, chunks = rt_chunks(c);
     const int R = n * n_vp;
     const bool own_f = counts && !fused;                 // the counts are taken from f: it is kept in the workspace when the caller does not want it
-    Carve sizing;
     RTBufs b;
-    rt_layout(sizing, b, n, n_vp, chunks, own_f ? (size_t)n * V : 0);
-    if ((rc = dev_reserve(c, c->rt_ws, sizing.off)) != SN_OK) return rc;
-    Carve cv{c->rt_ws.as<unsigned char>()};
-    rt_layout(cv, b, n, n_vp, chunks, own_f ? (size_t)n * V : 0);
+    if ((rc = dev_carve(c, c->rt_ws, [&](Carve &cv) { rt_layout(cv, b, n, n_vp, chunks, own_f ? (size_t)n * V : 0); })) != SN_OK) return rc;
     const RTPar p = rt_par(c);
     float *f = own_f ? b.f : fused;
     const float nV = (float)((double)n * (double)V);
@@ -145,11 +141,8 @@ extern "C" int sn_relw_train_begin(sn_ctx *c, const sn_relw_train_cfg *cfg)
     int rc;
     if ((rc = relw_fresh_b2(c)) != SN_OK) return rc;     // (a session that follows another starts from what that one trained)
     c->rt_on = false;
-    Carve sizing;
     RTPar b;
-    rt_par_layout(sizing, b);
-    if ((rc = dev_reserve(c, c->rt_par, sizing.off)) != SN_OK) return rc;
-    b = rt_par(c);
+    if ((rc = dev_carve(c, c->rt_par, [&](Carve &cv) { rt_par_layout(cv, b); })) != SN_OK) return rc;
     HIPCHK(hipMemcpyAsync(b.P + RT_P_W1, c->relw_W1, sizeof(float) * RT_D * RT_H, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(b.P + RT_P_BETA, c->relw_bn, sizeof(float) * 4 * RT_H, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(b.P + RT_P_W2, c->relw_w2, sizeof(float) * RT_H, hipMemcpyDeviceToDevice, c->stream));

@@ -31,7 +31,7 @@ struct Rec {
     }
 };
 
-// the host form of sn_normals with normals and moments (sn_normals.hip nm_layout): n cubes, T voxels, K views per cube of V cameras
+// the host form of sn_normals with normals and moments (sn_normals.hip nm_layout, with every array staged): n cubes, T voxels, K views per cube of V cameras
 static void normals_layout(Rec &w, size_t n)
 {
     const size_t T = 7 * n, K = 5, V = 9, cap = table_cap(T, 2, 64);
@@ -41,7 +41,7 @@ static void normals_layout(Rec &w, size_t n)
     w.get<int>(1); w.get<int>(T); w.get<double>(3 * n); w.get<unsigned long long>(2 * cap);
 }
 
-// one cell grid of the point evaluation with ranks (sn_pointeval.hip grid_carve; the scan's block sums: one per 1024 slots, + 1)
+// one cell grid of the point evaluation with ranks (cellgrid.h grid_layout; the scan's block sums: one per 1024 slots, + 1)
 static void grid_layout(Rec &w, size_t n)
 {
     const size_t cap = table_cap(n, 2, 1024);

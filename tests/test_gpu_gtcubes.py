@@ -105,6 +105,27 @@ def test_one_point_and_no_points(ctxs, s):
     assert ctx.gt_cubes((xyz[:0], resol[:0])).shape == (0, 1, s, s, s)
 
 
+def test_one_point_per_cell_fills_half_of_the_smallest_table(ctxs):
+    """512 points in 512 distinct cells: the bound grid's hash table has its minimum capacity of 1,024 slots and is half full, the fullest
+    the capacity rule allows (probes walk past taken slots, also from the last slot on to slot 0)."""
+    s, cell = 8, 0.8
+    ctx = ctxs(s)
+    x0 = np.array([-3.0, 2.0, 640.0], np.float32)
+    side = R04 * np.float32(s)                                                        # four cells
+    f = np.arange(8) + np.where(np.arange(8) == 0, 0.0, 0.5)                          # the grid's origin itself, then the middle of every further cell
+    pts = x0 + (np.stack(np.meshgrid(f, f, f, indexing="ij"), -1).reshape(-1, 3) * cell).astype(np.float32)
+    assert pts.dtype == np.float32
+    cells = np.floor((pts.astype(np.float64) - pts.min(axis=0).astype(np.float64)) / cell)
+    assert np.unique(cells, axis=0).shape[0] == 512
+    offs = np.array([[i, j, k] for i in (0, 1) for j in (0, 1) for k in (0, 1)], np.float32)
+    xyz = np.concatenate([x0[None, :] + offs * side, x0[None, :] + side / 2, x0[None, :] - side / 4]).astype(np.float32)
+    resol = np.full((len(xyz),), R04, np.float32)
+    want = ref.gt_cubes(pts, xyz, resol, s)
+    assert want.sum() > 512                                                           # every point in a lattice cube, some in the two others too
+    assert ctx.gt_bind(pts, cell) == 512
+    assert np.array_equal(ctx.gt_cubes((xyz, resol)), want)
+
+
 SCALE_STEP, BATCH = 37, 64
 
 

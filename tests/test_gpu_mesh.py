@@ -83,6 +83,21 @@ def test_the_owners_normal_decides(ctx):
     assert mc["vert_src"].min() >= 25 and (mr.quad_normals(mc["verts_lattice"], mc["quads"])[:, 2] < 0).all()
 
 
+def test_half_full_tables_at_the_minimum_capacity(ctx):
+    """32 masked voxels in 32 distinct world cells of 32 distinct 4^3 bricks (the bias of one brick keeps 7|8 and 15|16 across brick
+    boundaries): the cell table and the brick table have their minimum capacity of 64 slots and are half full, the fullest the capacity rule
+    allows (probes walk past taken slots, also from the last slot on to slot 0). Two cubes, so the owner search runs as well."""
+    ax = (3, 4, 11, 12)
+    vox = np.asarray([(i, j, k) for i in ax for j in ax for k in (3, 4)], np.uint8)
+    off, ijk = nref.pack([vox[:16], vox[16:] - np.asarray([8, 0, 0], np.uint8)])                  # x = 11, 12 from a cube 8 cells along x
+    up = np.tile(np.asarray([0, 0, 1], np.float32), (32, 1))
+    s = dict(offsets=off, ijk=ijk, cube_ijk=np.asarray([[0, 0, 0], [1, 0, 0]], np.int64), mask=np.ones(32, bool), stride_vox=8, normals=up)
+    cells = mr.oriented_cells(*mr.scene_args(s))[0]
+    assert np.unique(cells, axis=0).shape[0] == 32 and np.unique((cells + 4) >> 2, axis=0).shape[0] == 32
+    for radius, reach in ((1, 0), (2, 1), (3, 3)):
+        assert _check(ctx, s, radius, reach)["quads"].shape[0] > 0
+
+
 @pytest.mark.parametrize("place", ["split", "zero", "top"])
 def test_sphere_placements(ctx, place):
     if place == "split":                                        # dealt to 4^3 cubes of stride 13: straddles cube and brick boundaries

@@ -97,6 +97,26 @@ def test_repeated_voxels_count_once_and_unique_keeps_the_first(ctx):
     _check(ctx, s2, ref.normals_ref(*ref.scene_args(s2)), min_compared=1.0)
 
 
+@pytest.mark.parametrize("cubes", [1, 2])
+def test_half_full_tables_at_the_minimum_capacity(ctx, cubes):
+    """32 masked voxels in 32 distinct world cells of 32 distinct 4^3 bricks: the brick table (normals) and the cell table (unique voxels)
+    have their minimum capacity of 64 slots and are half full, the fullest the capacity rule allows (probes walk past taken slots, also from
+    the last slot on to slot 0). Coordinates 3|4 and 11|12 are neighbours across a brick boundary, so the windows are not empty."""
+    ax = (3, 4, 11, 12)
+    vox = np.asarray([(i, j, k) for i in ax for j in ax for k in (3, 4)], np.uint8)
+    lists = [vox] if cubes == 1 else [vox[:16], vox[16:] - np.asarray([8, 0, 0], np.uint8)]      # x = 11, 12 from a cube 8 cells along x
+    s = ref.hand_scene([[0, 0, 0], [1, 0, 0]][:cubes], lists, stride_vox=8)
+    g = ref.world_cells(s["offsets"], s["ijk"], s["cube_ijk"], 8)
+    assert s["mask"].all() and np.unique(g, axis=0).shape[0] == 32 and np.unique(g >> 2, axis=0).shape[0] == 32
+    for radius in (1, 2, 3):
+        r = ref.normals_ref(*ref.scene_args(s), radius=radius, min_neighbours=4)
+        nrm, mom = _run(ctx, s, radius, 4)
+        assert np.array_equal(mom, r["moments"]) and mom[:, 0].min() >= 4
+        assert np.abs(nrm[r["comparable"]].astype(np.float64) - r["normals"][r["comparable"]].astype(np.float64)).max(initial=0.0) <= TOL
+        assert not nrm[~r["solved"]].any()
+    assert np.array_equal(_unique(ctx, s), ref.unique_ref(s["offsets"], s["ijk"], s["cube_ijk"], s["mask"], 8)) and _unique(ctx, s).all()
+
+
 def test_speck_empty_cube_unmasked_cube_and_no_voxels(ctx):
     lists = ref.sheet_5x5(z=7) + [np.zeros((0, 3), np.uint8), np.asarray([(20, 20, 20)], np.uint8), ref.sheet_5x5(z=9)[0]]
     s = ref.hand_scene([[0, 0, 0], [1, 1, 0], [4, 4, 4], [0, 0, 1]], lists)

@@ -88,6 +88,26 @@ def test_reduce_default_order_and_rounds(ev):
     assert np.array_equal(keep, ref.reduce_sequential(small, order, 0.2)) and 1 <= rounds < 100
 
 
+def test_one_point_per_cell_fills_half_of_the_smallest_table(ev):
+    """512 points in 512 distinct cells: the grid's hash table has its minimum capacity of 1,024 slots and is half full, the fullest the
+    capacity rule allows (probes walk past taken slots, also from the last slot on to slot 0)."""
+    evaluation, ctx = ev
+    ijk = np.stack(np.meshgrid(np.arange(8), np.arange(8), np.arange(8), indexing="ij"), -1).reshape(-1, 3)
+    p = ijk + 0.03 * (ijk.sum(1, keepdims=True) % 2)           # neighbours along an axis lie 0.971 or 1.031 apart
+    dst = 0.98
+    cells = np.floor((p - p.min(0)) / (dst * (1.0 + 1e-6)))    # the reduction's grid: cells a little larger than dst
+    assert np.unique(cells, axis=0).shape[0] == 512
+    order = np.random.RandomState(13).permutation(512)
+    want = ref.reduce_rounds(p, order, dst)
+    assert 0 < want.sum() < 512
+    got, idx = evaluation.reduce_points(p, dst=dst, order=order, return_index=True)
+    assert np.array_equal(idx, np.nonzero(want)[0]) and np.array_equal(got, p[want])
+    # nearest neighbours: the first bucketing of the 512 points, at their mean spacing, puts one point in every cell as well
+    frm = np.concatenate([p + [0.25, -0.125, 0.5], p[::7]])
+    _check_d2(ctx.nn_dist2(p, frm, 60.0), p, frm, 60.0)
+    _check_d2(ctx.nn_dist2(p, frm, 0.5), p, frm, 0.5)
+
+
 def test_flags_at_boundaries(ev):
     _, ctx = ev
     rs = np.random.RandomState(13)

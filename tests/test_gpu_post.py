@@ -71,6 +71,25 @@ def test_ray_pool_batch_vs_oracle(sn, D, thr, zero_frac, quant):
     assert (votes[0][votes[0] > 0] == 2 * n_vp).all()           # the repeated view votes with its multiplicity
 
 
+@pytest.mark.parametrize("m", [32, 2048, 3400, 4096])
+def test_ray_pool_tables_at_their_fullest(sn, m):
+    """m selected voxels of a 16^3 cube fill a workgroup's hash tables as far as their sizing allows: 2 m slots for m = 32 (the minimum of 64),
+    2048 (the 4096 LDS slots) and 4096 (global tables, all voxels selected); m = 3400, the most the LDS tables take, fills 83 % of them."""
+    D = 16
+    rs = np.random.RandomState(m)
+    pred = np.full(D ** 3, 0.1, np.float32)
+    pred[rs.permutation(D ** 3)[:m]] = (0.6 + 0.3 * rs.rand(m)).astype(np.float32)
+    pred = pred.reshape(1, D, D, D)
+    p16 = pred.astype(np.float16)
+    assert int((p16 > np.float16(0.5)).sum()) == m
+    pairs, xyz, resol = np.asarray([[[0, 1], [2, 0]]]), np.asarray([[-3.0, 2.0, 640.0]], np.float32), np.asarray([0.4], np.float32)
+    with sn.Context(cube_D=D, max_samples=4) as ctx:
+        ctx.set_cameras(P_DTU)
+        votes = ctx.ray_pool(pairs, xyz, resol, pred, 0.5)
+    want = post_oracle.ray_pool_1cube(P_DTU, p16[0], pairs[0], xyz[0], resol[0], 0.5)
+    assert want.any() and np.array_equal(votes[0], want.astype(np.uint8))
+
+
 def d2s_inputs(name):
     g = lambda k: POST[name + "/" + k]
     D, Dc, crop, rp_on, rp_thr = (int(v) for v in g("cfg"))

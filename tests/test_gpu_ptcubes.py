@@ -70,6 +70,21 @@ def test_cell_extents_beyond_the_dense_form(sn, dtype):
     _same(sn["scene"].quantizePts2Cubes(pts, **kw), want)
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+def test_hash_set_half_full_at_its_smallest(sn, dtype):
+    """512 points whose cells and diagonal cells are all distinct, too far apart for the occupancy bitmap: 1,024 keys in the hash set's minimum
+    of 2,048 slots, the fullest the capacity rule allows (probes walk past taken slots, also from the last slot on to slot 0)."""
+    kw = dict(resol=RESOL, cube_D=32, cube_Dcenter=26, cube_overlapping_ratio=0.5)
+    stride = float(sn["scene"]._plan(np.dtype(dtype), RESOL, 32, 26, 0.5, None)["stride_q"])
+    i = np.arange(512, dtype=np.float64)
+    along = np.where(i == 0, 0.0, (3 * i + 0.5) * stride)                                      # cell 3 i of the space diagonal (the first point is the shift)
+    pts = np.repeat(along[np.random.RandomState(5).permutation(512), None], 3, axis=1).astype(dtype)
+    want = ref.quantizePts2Cubes(pts, **kw)
+    ext = want[0]["ijk"].max(axis=0).astype(np.int64) + 1
+    assert ext.prod() > (1 << 27) and want[0].shape[0] == 1024
+    _same(sn["scene"].quantizePts2Cubes(pts, **kw), want)
+
+
 @pytest.mark.parametrize("far", [False, True], ids=["dense", "hashed"])
 def test_dev_entry_and_short_outputs_equal_host_entry(sn, far):
     scene = sn["scene"]

@@ -1,6 +1,6 @@
-"""CPU: csrc/sn_host.h — the entry points' host plumbing that needs no device (Carve, table_cap, the packed-list checks) — and csrc/sn_pack.h —
-the host half of weight packing — each compiled alone by a plain host C++17 compiler, with no hip/ include on its path, under the address and
-undefined-behaviour sanitizers, and run as a child process (tests/host/sn_host_check.cpp and sn_pack_check.cpp hold the checks). Nothing is
+"""CPU: csrc/sn_host.h — the entry points' host plumbing that needs no device (Carve, table_cap, the packed-list checks) — csrc/sn_pack.h —
+the host half of weight packing — and csrc/lattice.h — the keys, codes and table predicates of the lattice stages — each compiled alone by a plain host C++17 compiler, with no hip/ include on its path, under the address and
+undefined-behaviour sanitizers, and run as a child process (tests/host/sn_host_check.cpp, sn_pack_check.cpp and lattice_check.cpp hold the checks). Nothing is
 loaded into this interpreter."""
 import json
 import os
@@ -27,8 +27,8 @@ def _compile(src, exe):
 
 
 def test_sn_host_header_is_hip_free():
-    """sn_host.h, sn_pack.h and sn_consts.h include no HIP header and none of the project's headers that do."""
-    hip_free = ("sn_host.h", "sn_pack.h", "sn_consts.h")
+    """sn_host.h, sn_pack.h, sn_consts.h and lattice.h include no HIP header and none of the project's headers that do."""
+    hip_free = ("sn_host.h", "sn_pack.h", "sn_consts.h", "lattice.h")
     for name in hip_free:
         with open(os.path.join(CSRC, name)) as f:
             includes = [line.split()[1] for line in f if line.startswith("#include")]
@@ -42,6 +42,15 @@ def test_sn_host_check_under_sanitizers(tmp_path):
     _compile(SRC, exe)
     p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0 and "SN-HOST-CHECK-OK" in p.stdout, (p.returncode, p.stdout[-500:], p.stderr[-3000:])
+
+
+def test_lattice_check_under_sanitizers(tmp_path):
+    """lattice.h alone: key round trip and order, lt_cube_of against a linear scan, the offsets predicate, the ordered codes, and lt_mix64
+    against the values the hashes it replaced gave (tests/host/lattice_check.cpp)."""
+    exe = str(tmp_path / "lattice_check")
+    _compile(os.path.join(ROOT, "tests", "host", "lattice_check.cpp"), exe)
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "LATTICE-CHECK-OK" in p.stdout, (p.returncode, p.stdout[-500:], p.stderr[-3000:])
 
 
 def test_sn_pack_check_under_sanitizers(tmp_path):

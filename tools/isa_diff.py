@@ -5,7 +5,9 @@ A and B are two output directories of `make -C surfacenet_amd/csrc asm ASM_DIR=.
 *-gfx950.s present in both is cut at its function labels (`name:   ; @name`; what precedes the first label and the module's metadata block
 are two pieces of their own), lines containing __hip_cuid_ (a per-compilation id) are dropped, so are the assembler comments (`; ...`: they carry
 the compiler's names of IR blocks, which are numbered through the whole unit and move when an unrelated `if constexpr` goes; the register and
-scratch figures they also carry stay compared through the .amdhsa_ directives and the metadata), and the pieces are compared as text, kernel
+scratch figures they also carry stay compared through the .amdhsa_ directives and the metadata), the number of the function inside its unit is
+taken out of the local labels (.LBB<n>_k, .Lfunc_end<n>: it moves when a kernel joins or leaves the unit), what follows the last function is a
+piece of its own, a bare `.text` that ends a piece is dropped (it depends on what comes next), and the pieces are compared as text, kernel
 by kernel. Prints every kernel whose text differs, demangled, with both line counts. Exit status 1 if a kernel differs, if the two sides do
 not hold the same kernels, or if a unit is missing on one side; 0 otherwise. It compares text only and knows nothing about instructions."""
 import os
@@ -15,7 +17,8 @@ import sys
 
 LABEL = re.compile(r"^(\S+):\s*; @(\S+)\s*$")
 INTRO = re.compile(r"^\s*\.(section\s+\.text|protected|globl|weak|hidden|p2align|type)\b")      # a function's directives in front of its label
-HEAD, META = "(module header)", "(module metadata)"
+FUNC_NO = re.compile(r"\.(LBB|Lfunc_end|Lfunc_begin)\d+")
+HEAD, META, TAIL = "(module header)", "(module metadata)", "(module trailer)"
 
 
 def pieces(path):
@@ -34,9 +37,15 @@ def pieces(path):
         elif line.strip() == ".amdgpu_metadata":
             name = META
             out[name] = []
-        code = line.split(";", 1)[0].rstrip()
+        elif line.strip().startswith(".p2alignl") and name not in (HEAD, META):
+            name = TAIL
+            out[name] = []
+        code = FUNC_NO.sub(r".\1", line.split(";", 1)[0].rstrip())
         if code:
             out[name].append(code)
+    for text in out.values():
+        while text and text[-1].strip() == ".text":
+            text.pop()
     return out
 
 
@@ -68,12 +77,12 @@ def main():
         names = [n for n in pa if n in pb]
         odd = [n for n in list(pa) + list(pb) if (n in pa) != (n in pb)]
         diff = [n for n in names if pa[n] != pb[n]]
-        dem = demangle([n for n in odd + diff if n not in (HEAD, META)])
+        dem = demangle([n for n in odd + diff if n not in (HEAD, META, TAIL)])
         for n in odd:
             print("%s: only in %s: %s" % (f, a_dir if n in pa else b_dir, dem.get(n, n)))
         for n in diff:
             print("%s: DIFFERS (%d | %d lines): %s" % (f, len(pa[n]), len(pb[n]), dem.get(n, n)))
-        nk = len([n for n in names if n not in (HEAD, META)])
+        nk = len([n for n in names if n not in (HEAD, META, TAIL)])
         print("%-50s %4d kernels compared, %d changed" % (f, nk, len(diff)))
         total += nk
         changed += len(diff)
