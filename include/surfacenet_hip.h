@@ -29,7 +29,8 @@ extern "C" {
  * point-seeded cube list; sn_normals, sn_normals_dev, sn_unique_voxels, sn_unique_voxels_dev and sn_normals_cfg - oriented normals and
  * de-duplication of the output cloud; sn_gt_bind, sn_gt_bind_dev, sn_gt_cubes, sn_gt_cubes_dev, sn_weighted_accuracy and
  * sn_weighted_accuracy_dev - the ground-truth mode; sn_mesh, sn_mesh_dev and sn_mesh_cfg - the surface-nets mesh of the oriented cloud;
- * sn_mesh_sample and sn_mesh_sample_dev - surface samples of a triangle mesh. */
+ * sn_mesh_sample and sn_mesh_sample_dev - surface samples of a triangle mesh; sn_components, sn_components_dev and sn_components_cfg - connected
+ * components of the output cloud. */
 
 /* The library is built with -fvisibility=hidden: the functions below are its WHOLE dynamic symbol table
  * (tests/test_abi.py compares `nm -D` with this header). */
@@ -273,6 +274,31 @@ SN_API int sn_unique_voxels(sn_ctx *ctx, int n, int stride_vox, const int64_t *o
                             const unsigned char *mask, unsigned char *keep);
 SN_API int sn_unique_voxels_dev(sn_ctx *ctx, int n, int stride_vox, long long total, const int64_t *offsets_dev, const unsigned char *ijk_dev,
                                 const uint32_t *cube_ijk_dev, const unsigned char *mask_dev, unsigned char *keep_dev);
+
+/* ---- connected components of the output cloud: removing floaters ----------------------------------------------------
+ * On the packed sparse lists exactly as sn_unique_voxels takes them. World cell of a voxel: g = cube_ijk * stride_vox + ijk per axis; O holds the
+ * distinct cells of the masked voxels of all cubes. Two distinct cells are adjacent iff max |d| <= 1 per axis and sum |d| <= 1, 2 or 3 for
+ * connectivity 6, 18 or 26 (scipy.ndimage.generate_binary_structure(3, 1 | 2 | 3)); a component K is a class of the transitive closure on O -
+ * across cubes. first(K) = the smallest packed index among the masked voxels whose cell lies in K; the components are numbered 0 .. C-1 by
+ * ascending first(K).
+ *   label (total) int32: the component number of the voxel's cell, -1 for an unmasked voxel.
+ *   cells (total) int32: |K| counted in DISTINCT cells (a cell listed by several cubes, or twice in one cube, counts once); 0 for an unmasked voxel.
+ *   keep  (total) uint8: mask && cells >= min_cells.
+ *   n_components (required): C. label, cells and keep are each optional (NULL).
+ * SN_ERR_ARG, nothing written: a bad offsets table, connectivity not 6 / 18 / 26, min_cells < 1, stride_vox < 1, a masked cell with
+ * g + 1 >= 2^21 on an axis, total > 2^28. Cells with a negative coordinate do not exist: a neighbour probe there misses. n == 0, total == 0 or an
+ * all-false mask give C = 0. The result is a function of the partition only, so it is bit-identical from run to run. The workspace belongs to
+ * the context (grown on demand); both forms return when the work is done. */
+typedef struct sn_components_cfg {
+    int stride_vox;            /* cube stride in voxels */
+    int connectivity;          /* 6, 18 or 26 */
+    int min_cells;             /* >= 1: keep = the component has at least this many cells */
+} sn_components_cfg;
+SN_API int sn_components(sn_ctx *ctx, int n, const sn_components_cfg *cfg, const int64_t *offsets, const unsigned char *ijk, const uint32_t *cube_ijk,
+                         const unsigned char *mask, int32_t *label, int32_t *cells, unsigned char *keep, long long *n_components);
+SN_API int sn_components_dev(sn_ctx *ctx, int n, const sn_components_cfg *cfg, long long total, const int64_t *offsets_dev, const unsigned char *ijk_dev,
+                             const uint32_t *cube_ijk_dev, const unsigned char *mask_dev, int32_t *label_dev, int32_t *cells_dev,
+                             unsigned char *keep_dev, long long *n_components);
 
 /* ---- surface mesh of the oriented output cloud: surface nets on the world lattice -------------------------------------
  * On the packed sparse lists (offsets, ijk, cube_ijk, mask as the two entries above take them) plus normals (total,3) float32 as the normals entry

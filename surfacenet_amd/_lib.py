@@ -21,6 +21,7 @@ ABI_SYMBOLS = [
     "sn_ray_pool", "sn_ray_pool_dev", "sn_dense2sparse", "sn_dense2sparse_dev",
     "sn_denoise", "sn_denoise_dev", "sn_adapthresh", "sn_adapthresh_dev",
     "sn_normals", "sn_normals_dev", "sn_unique_voxels", "sn_unique_voxels_dev",
+    "sn_components", "sn_components_dev",
     "sn_mesh", "sn_mesh_dev", "sn_mesh_sample", "sn_mesh_sample_dev",
     "sn_point_reduce", "sn_nn_dist2", "sn_point_flags",
     "sn_ptcubes", "sn_ptcubes_dev", "sn_ptcubes_sparse_dev",
@@ -52,6 +53,10 @@ class AdapthreshCfg(ctypes.Structure):
 class NormalsCfg(ctypes.Structure):
     _fields_ = [("radius", ctypes.c_int), ("min_neighbours", ctypes.c_int), ("stride_vox", ctypes.c_int), ("n_views", ctypes.c_int),
                 ("views_per_cube", ctypes.c_int)]
+
+
+class ComponentsCfg(ctypes.Structure):
+    _fields_ = [("stride_vox", ctypes.c_int), ("connectivity", ctypes.c_int), ("min_cells", ctypes.c_int)]
 
 
 class MeshCfg(ctypes.Structure):
@@ -137,6 +142,8 @@ def load():
         "sn_normals_dev": (c_int, [c_void_p, c_int, P(NormalsCfg), ctypes.c_longlong] + [c_void_p] * 10),
         "sn_unique_voxels": (c_int, [c_void_p, c_int, c_int] + [c_void_p] * 5),
         "sn_unique_voxels_dev": (c_int, [c_void_p, c_int, c_int, ctypes.c_longlong] + [c_void_p] * 5),
+        "sn_components": (c_int, [c_void_p, c_int, P(ComponentsCfg)] + [c_void_p] * 7 + [P(ctypes.c_longlong)]),
+        "sn_components_dev": (c_int, [c_void_p, c_int, P(ComponentsCfg), ctypes.c_longlong] + [c_void_p] * 7 + [P(ctypes.c_longlong)]),
         "sn_mesh": (c_int, [c_void_p, c_int, P(MeshCfg)] + [c_void_p] * 5 + [ctypes.c_longlong] * 2 + [c_void_p] * 5 + [P(ctypes.c_longlong)] * 2),
         "sn_mesh_dev": (c_int, [c_void_p, c_int, P(MeshCfg), ctypes.c_longlong] + [c_void_p] * 5 + [ctypes.c_longlong] * 2 + [c_void_p] * 5 +
                         [P(ctypes.c_longlong)] * 2),

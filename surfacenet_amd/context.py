@@ -508,6 +508,38 @@ class Context(object):
         _lib.check(self._lib.sn_unique_voxels(self._h, n, int(stride_vox), _lib.ptr(offsets), _lib.ptr(ijk), _lib.ptr(cube), _lib.ptr(m), _lib.ptr(keep)))
         return keep.view(bool)
 
+    def components(self, offsets, ijk, cube_ijk, mask, stride_vox, connectivity=26, min_cells=1, device=False):
+        """Connected components of the masked voxels' world cells, across cubes (sn_components), on the packed lists
+        unique_voxels takes. Returns (label (T,) int32 - the component of the voxel's cell, numbered by the smallest packed index it holds, -1
+        unmasked; cells (T,) int32 - the component's size in distinct cells; keep (T,) bool - masked and cells >= min_cells; C). device=True
+        stages the lists in device memory here and runs sn_components_dev on them: the same result."""
+        offsets, n, ijk, cube = self._packed(offsets, ijk, cube_ijk)
+        m = np.ascontiguousarray(mask, dtype=bool).reshape(-1).view(np.uint8)
+        T = int(offsets[-1])
+        if ijk.shape[0] != T or m.size != T:
+            raise ValueError("offsets end at %d voxels: %d ijk rows, %d mask entries" % (T, ijk.shape[0], m.size))
+        cfg = _lib.ComponentsCfg(int(stride_vox), int(connectivity), int(min_cells))
+        label, cells, keep = np.full((T,), -1, np.int32), np.zeros((T,), np.int32), np.zeros((T,), np.uint8)
+        C = ctypes.c_longlong(0)
+        if not device:
+            _lib.check(self._lib.sn_components(self._h, n, ctypes.byref(cfg), _lib.ptr(offsets), _lib.ptr(ijk), _lib.ptr(cube), _lib.ptr(m),
+                                               _lib.ptr(label), _lib.ptr(cells), _lib.ptr(keep), ctypes.byref(C)))
+            return label, cells, keep.view(bool), int(C.value)
+        staged = []
+        try:
+            for a in (offsets, ijk, cube, m, label, cells, keep):
+                staged.append(self.dev_alloc(max(a.nbytes, 16)))
+                if a.nbytes:
+                    self.h2d(staged[-1], a)
+            _lib.check(self._lib.sn_components_dev(self._h, n, ctypes.byref(cfg), T, *staged, ctypes.byref(C)))
+            for a, b in zip((label, cells, keep), staged[4:]):
+                if a.nbytes:
+                    self.d2h(a, b)
+        finally:
+            for b in staged:
+                self.dev_free(b)
+        return label, cells, keep.view(bool), int(C.value)
+
     def mesh(self, offsets, ijk, cube_ijk, mask, stride_vox, normals, radius=2, reach=0, origin=(0.0, 0.0, 0.0), resol=1.0, cap=None, device=False):
         """Surface-nets mesh of the oriented cloud (sn_mesh): the packed lists unique_voxels takes plus normals (T,3)
         float32 (zero = no normal), origin (3,) / resol the mm position of lattice point 0 and the cell size. Returns a dict: verts_mm (V,3)

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "lattice.h"
+#include "unionfind.h"
 
 namespace sn {
 
@@ -257,33 +258,7 @@ struct CCDenoiseArgs {
     int n, Dc, h;                        // h = D_cube // 2: v of c and u of c + s coincide iff v == u + h * s
 };
 
-template <typename P>
-__device__ __forceinline__ unsigned cc_ld(P p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <typename P>
-__device__ __forceinline__ void cc_st(P p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-template <typename P>
-__device__ __forceinline__ unsigned cc_find(P parent, unsigned x)
-{
-    for (;;) {
-        const unsigned p = cc_ld(parent + x);
-        if (p == x) return x;
-        x = p;
-    }
-}
-
-// lock-free union: the larger root is linked below the smaller one, only while it is still a root (links always point to smaller cells: acyclic)
-template <typename P>
-__device__ __forceinline__ void cc_union(P parent, unsigned a, unsigned b)
-{
-    for (;;) {
-        a = cc_find(parent, a); b = cc_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const unsigned t = a; a = b; b = t; }
-        unsigned expected = a;
-        if (__hip_atomic_compare_exchange_strong(parent + a, &expected, b, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-    }
-}
+// cc_ld / cc_st / cc_find / cc_union: the lock-free union-find of unionfind.h
 
 // one cube: 26-connected components of its occupied cells (union-find over cells: repeated ijk share a cell, as in the reference's dense label
 // array), the components that hold a cell coinciding with a masked voxel of a mapped neighbour, then the voxels' verdicts

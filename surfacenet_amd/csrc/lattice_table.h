@@ -1,5 +1,5 @@
 // lattice_table.h — the open-addressing hash table of 64-bit keys (cell keys of lattice.h, ray pooling's pixel and cell keys) that normals.h,
-// mesh.h, ptcubes.h, cellgrid.h and postpass.h share: linear probing from lt_mix64(key) & mask, claim-or-find with relaxed agent-scope atomics for the kernels that fill a table,
+// components.h, mesh.h, ptcubes.h, cellgrid.h and postpass.h share: linear probing from lt_mix64(key) & mask, claim-or-find with relaxed agent-scope atomics for the kernels that fill a table,
 // and the read-only probe. Both return the SLOT; what a stage keeps per slot is its own business. Two slot layouts exist:
 //   LtKeys    a bare key array; a free slot holds ~0 (memset 0xff)
 //   LtPairs   two words {key + 1, value}; key + 1 != 0, so an all-zero table is empty and the value words start as 0 as well
@@ -48,6 +48,13 @@ __device__ __forceinline__ unsigned lt_claim(P tab, unsigned mask, unsigned long
         if (cur == stored) return h;
         h = (h + 1) & mask;
     }
+}
+
+// packed voxel t bids for its cell `key` in an owner table: the cell's slot is claimed if absent, the smallest index is the largest stored value
+__device__ __forceinline__ void lt_own(unsigned long long *tab, unsigned mask, unsigned long long key, long long t)
+{
+    const unsigned h = lt_claim<LtPairs>(tab, mask, key);
+    atomicMax(tab + 2 * (size_t)h + 1, LT_OWNER_TOP - (unsigned long long)t);
 }
 
 // slot of `key`, -1 if absent. Plain loads: for a table a finished kernel filled. COHERENT: relaxed agent-scope loads, for a table the same

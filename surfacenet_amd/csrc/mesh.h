@@ -90,8 +90,7 @@ __global__ void __launch_bounds__(MS_NT) ms_insert_kernel(MSIn a, MSTab tb)
         atomicOr(a.cnt + MS_CNT_FLAGS, MS_FLAG_CELL);
         return;
     }
-    const unsigned h = lt_claim<LtPairs>(tb.cell, tb.cmask, lt_key(g[0], g[1], g[2]));
-    atomicMax(tb.cell + 2 * (size_t)h + 1, LT_OWNER_TOP - (unsigned long long)t);      // the smallest index is the largest stored value
+    lt_own(tb.cell, tb.cmask, lt_key(g[0], g[1], g[2]), t);
 }
 
 // every owner with a non-zero normal: its cell's bit into the brick table (the host does not launch this after a flag)

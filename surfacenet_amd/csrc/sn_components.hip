@@ -1,0 +1,198 @@
+// sn_components.hip — C ABI of the connected components of the output cloud over the packed sparse voxel lists (components.h; DESIGN.md
+// section 4.14). The host form stages its arrays in the context's workspace and wraps the device form's computation.
+#include "sn_internal.h"
+#include "components.h"
+#include "scan.h"
+
+namespace {
+
+constexpr long long CP_MAX_VOXELS = 1ll << 28;       // a hash table of >= 2 * total slots stays within 2^29; total + 1 fits the scan's int
+
+// One call's arrays: the inputs and outputs (the caller's device arrays; in the host form the caller's host arrays until cp_prepare has staged
+// them) and the work buffers.
+struct CPCall {
+    int n = 0;
+    long long total = 0;
+    bool host = false, staged = true;                // staged: no upload has failed
+    const int64_t *off = nullptr; const uint8_t *ijk = nullptr, *mask = nullptr; const uint32_t *cube_ijk = nullptr;
+    int32_t *label = nullptr, *cells = nullptr; uint8_t *keep = nullptr;
+    // work
+    unsigned cap = 0;
+    int *flags = nullptr, *cube_of = nullptr; unsigned long long *tab = nullptr;
+    unsigned *own = nullptr, *parent = nullptr, *root = nullptr;
+    int *count = nullptr, *flag = nullptr, *number = nullptr, *sums = nullptr;      // count | flag are one region (one memset)
+};
+
+template <typename T> void cp_stage(sn_ctx *c, Carve &w, CPCall &k, T *&p, size_t count, bool input)
+{
+    if (!k.host || !p) return;
+    auto *d = w.get<typename std::remove_const<T>::type>(count);
+    if (!w.base) return;
+    if (input && count && hipMemcpyAsync(d, p, sizeof(T) * count, hipMemcpyHostToDevice, c->stream) != hipSuccess) k.staged = false;
+    p = d;
+}
+
+void cp_layout(sn_ctx *c, Carve &w, CPCall &k)
+{
+    const size_t n = (size_t)k.n, T = (size_t)k.total;
+    cp_stage(c, w, k, k.off, n + 1, true);
+    cp_stage(c, w, k, k.cube_ijk, 3 * n, true);
+    cp_stage(c, w, k, k.ijk, 3 * T, true);
+    cp_stage(c, w, k, k.mask, T, true);
+    cp_stage(c, w, k, k.label, T, false);
+    cp_stage(c, w, k, k.cells, T, false);
+    cp_stage(c, w, k, k.keep, T, false);
+    k.flags = w.get<int>(1);
+    k.cube_of = w.get<int>(T);
+    k.tab = w.get<unsigned long long>(2 * (size_t)k.cap);
+    k.own = w.get<unsigned>(T);
+    k.parent = w.get<unsigned>(T);
+    k.root = w.get<unsigned>(T);
+    k.count = w.get<int>(2 * T + 1);
+    k.flag = k.count ? k.count + T : nullptr;
+    k.number = w.get<int>(T + 1);
+    k.sums = w.get<int>(scan_sums(T + 1));
+}
+
+int cp_prepare(sn_ctx *c, CPCall &k)
+{
+    k.cap = (unsigned)table_cap((unsigned long long)k.total, 2, 64);
+    int rc = dev_carve(c, c->cp_ws, [&](Carve &w) { cp_layout(c, w, k); }, 256);
+    if (rc == SN_OK && !k.staged) { (void)hipStreamSynchronize(c->stream); rc = fail(SN_ERR_HIP, "staging the host arrays failed"); }
+    return rc;
+}
+
+int cp_check(sn_ctx *c, int n, const sn_components_cfg *cfg, const long long *n_components)
+{
+    if (!c) return fail(SN_ERR_ARG, "null context");
+    if (!cfg) return fail(SN_ERR_ARG, "null cfg");
+    if (!n_components) return fail(SN_ERR_ARG, "n_components is required");
+    if (n < 0) return fail(SN_ERR_ARG, "n must be >= 0");
+    if (cfg->stride_vox < 1) return fail(SN_ERR_ARG, "stride_vox = %d must be a positive number of voxels", cfg->stride_vox);
+    if (cfg->connectivity != 6 && cfg->connectivity != 18 && cfg->connectivity != 26)
+        return fail(SN_ERR_ARG, "connectivity = %d: 6, 18 or 26", cfg->connectivity);
+    if (cfg->min_cells < 1) return fail(SN_ERR_ARG, "min_cells = %d must be >= 1", cfg->min_cells);
+    return SN_OK;
+}
+
+int cp_check_total(int n, long long total)
+{
+    if (total > CP_MAX_VOXELS) return fail(SN_ERR_ARG, "total = %lld: at most %lld voxels", total, CP_MAX_VOXELS);
+    return pl_check_counts(n, total);
+}
+
+// The computation on device arrays. Returns when the stream is done; *C is written only on success.
+int cp_run(sn_ctx *c, CPCall &k, const sn_components_cfg *cfg, long long *C)
+{
+    const int n = k.n;
+    const long long total = k.total;
+    HIPCHK(hipMemsetAsync(k.flags, 0, sizeof(int), c->stream));
+    hipLaunchKernelGGL(nm_check_kernel, dim3((unsigned)(n / NM_NT + 1)), dim3(NM_NT), 0, c->stream, k.off, n, total, (const int32_t *)nullptr, 0,
+                       (const double *)nullptr, 0, (double *)nullptr, k.flags);
+    HIPCHK(hipGetLastError());
+    const unsigned nb = blocks(total, NM_NT);
+    if (total > 0) {
+        NMArgs a;
+        memset(&a, 0, sizeof a);
+        a.off = k.off; a.ijk = k.ijk; a.cube_ijk = k.cube_ijk; a.mask = k.mask; a.cube_of = k.cube_of; a.tab = k.tab; a.flags = k.flags;
+        a.total = total; a.hmask = k.cap - 1; a.n = n; a.stride = cfg->stride_vox; a.radius = 1;      // the link kernel probes g + 1
+        ProfScope ps(c, "cp_cells", 0, (double)total * 12.0 + (double)k.cap * 16.0);
+        HIPCHK(hipMemsetAsync(k.tab, 0, sizeof(unsigned long long) * 2 * (size_t)k.cap, c->stream));
+        hipLaunchKernelGGL(nm_insert_kernel<true>, dim3(nb), dim3(NM_NT), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    int flags = 0;
+    HIPCHK(hipMemcpyAsync(&flags, k.flags, sizeof flags, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (flags & NM_FLAG_TABLE) return fail(SN_ERR_ARG, "offsets table does not start at 0, decreases, or does not end at total = %lld", total);
+    if (flags & NM_FLAG_CELL)
+        return fail(SN_ERR_ARG, "a masked voxel's world cell (cube_ijk * %d + vxl_ijk) plus 1 reaches 2^%d on an axis", cfg->stride_vox, LT_AXIS_BITS);
+    if (total == 0) { *C = 0; return SN_OK; }
+    CPArgs a;
+    memset(&a, 0, sizeof a);
+    a.ijk = k.ijk; a.cube_ijk = k.cube_ijk; a.mask = k.mask; a.cube_of = k.cube_of; a.tab = k.tab;
+    a.own = k.own; a.parent = k.parent; a.root = k.root; a.count = k.count; a.flag = k.flag; a.number = k.number;
+    a.label = k.label; a.cells = k.cells; a.keep = k.keep;
+    a.total = total; a.hmask = k.cap - 1; a.stride = cfg->stride_vox; a.max_sum = cfg->connectivity == 6 ? 1 : (cfg->connectivity == 18 ? 2 : 3);
+    a.min_cells = cfg->min_cells;
+    {
+        ProfScope ps(c, "cp_init", 0, (double)total * 20.0);
+        HIPCHK(hipMemsetAsync(k.count, 0, sizeof(int) * (2 * (size_t)total + 1), c->stream));
+        hipLaunchKernelGGL(cp_init_kernel, dim3(nb), dim3(NM_NT), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    {
+        ProfScope ps(c, "cp_link", 0, (double)total * 8.0);
+        hipLaunchKernelGGL(cp_link_kernel, dim3(nb), dim3(NM_NT), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    {
+        ProfScope ps(c, "cp_root", 0, (double)total * 16.0);
+        hipLaunchKernelGGL(cp_root_kernel, dim3(nb), dim3(NM_NT), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    {
+        ProfScope ps(c, "cp_number", 0, (double)total * 8.0);
+        int rc = scan_exclusive(c, k.flag, k.number, (int)(total + 1), k.sums);
+        if (rc != SN_OK) return rc;
+    }
+    {
+        ProfScope ps(c, "cp_write", 0, (double)total * 21.0);
+        hipLaunchKernelGGL(cp_write_kernel, dim3(nb), dim3(NM_NT), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    int nc = 0;
+    HIPCHK(hipMemcpyAsync(&nc, k.number + total, sizeof nc, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *C = nc;
+    return SN_OK;
+}
+
+}  // namespace
+
+extern "C" int sn_components_dev(sn_ctx *c, int n, const sn_components_cfg *cfg, long long total, const int64_t *offsets_dev, const unsigned char *ijk_dev,
+                                 const uint32_t *cube_ijk_dev, const unsigned char *mask_dev, int32_t *label_dev, int32_t *cells_dev,
+                                 unsigned char *keep_dev, long long *n_components)
+{
+    int rc;
+    if ((rc = cp_check(c, n, cfg, n_components)) != SN_OK) return rc;
+    if ((rc = cp_check_total(n, total)) != SN_OK) return rc;
+    if (n == 0) { *n_components = 0; return SN_OK; }
+    if (!offsets_dev || !cube_ijk_dev || (total > 0 && (!ijk_dev || !mask_dev))) return fail(SN_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(c->device));
+    CPCall k;
+    k.n = n; k.total = total;
+    k.off = offsets_dev; k.ijk = ijk_dev; k.cube_ijk = cube_ijk_dev; k.mask = mask_dev; k.label = label_dev; k.cells = cells_dev; k.keep = keep_dev;
+    if ((rc = cp_prepare(c, k)) != SN_OK) return rc;
+    long long C = 0;
+    if ((rc = cp_run(c, k, cfg, &C)) != SN_OK) return rc;
+    *n_components = C;
+    return SN_OK;
+}
+
+extern "C" int sn_components(sn_ctx *c, int n, const sn_components_cfg *cfg, const int64_t *offsets, const unsigned char *ijk, const uint32_t *cube_ijk,
+                             const unsigned char *mask, int32_t *label, int32_t *cells, unsigned char *keep, long long *n_components)
+{
+    int rc;
+    if ((rc = cp_check(c, n, cfg, n_components)) != SN_OK) return rc;
+    if (!offsets) return fail(SN_ERR_ARG, "null argument");
+    if ((rc = pl_check_host_offsets(n, offsets)) != SN_OK) return rc;
+    if (n == 0) { *n_components = 0; return SN_OK; }      // (no cubes: the table is its single entry)
+    const long long total = offsets[n];
+    if ((rc = cp_check_total(n, total)) != SN_OK) return rc;
+    if (!cube_ijk || (total > 0 && (!ijk || !mask))) return fail(SN_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(c->device));
+    CPCall k;
+    k.host = true; k.n = n; k.total = total;
+    k.off = offsets; k.ijk = ijk; k.cube_ijk = cube_ijk; k.mask = mask; k.label = label; k.cells = cells; k.keep = keep;
+    if ((rc = cp_prepare(c, k)) != SN_OK) return rc;
+    const size_t T = (size_t)total;
+    long long C = 0;
+    if ((rc = cp_run(c, k, cfg, &C)) != SN_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if (label && T) HIPCHK(hipMemcpyAsync(label, k.label, sizeof(int32_t) * T, hipMemcpyDeviceToHost, c->stream));
+    if (cells && T) HIPCHK(hipMemcpyAsync(cells, k.cells, sizeof(int32_t) * T, hipMemcpyDeviceToHost, c->stream));
+    if (keep && T) HIPCHK(hipMemcpyAsync(keep, k.keep, T, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *n_components = C;
+    return SN_OK;
+}

@@ -565,7 +565,7 @@ def reconstruct_scene(images_list, cameraPOs_np, cubes_param_np, cube_D_mm, cube
 
 def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, gamma=0.8, beta=6, N_refine_iter=8, init_probThresh=0.5,
                    max_probThresh=0.9, keep_iterations=False, cameraTs_np=None, cube_overlapping_ratio=0.5, unique=False, mesh=False, mesh_radius=2,
-                   mesh_reach=0, mesh_ply_prefix=None):
+                   mesh_reach=0, mesh_ply_prefix=None, min_component=None, component_connectivity=26):
     """The reconstruction's last two stages on `reconstruct_scene`'s dict, in memory and on the GPU, as the reference runs them on its files:
       * main_reconstruct.py:172-175  thinning masks (prob >= tau, votes >= gamma * N_vp * 2), then denoise_crossCubes with D_cube = cube_D
       * main.py:37-43 -> utils/adapthresh.py  adaptive thresholding with D_cube = cube_Dcenter, init / max threshold init_probThresh /
@@ -581,13 +581,19 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
       unique=True: fixThresh_unique_list, adapt_unique_list - the two denoised masks with every world voxel kept once (normals.unique_voxels).
       mesh=True (needs cameraTs_np): fixThresh_mesh, adapt_mesh - mesh.extract_mesh of the two denoised masks with their
         normal lists (window mesh_radius, mesh_reach), each a dict of vertices, quads, vert_src, vert_lattice; with mesh_ply_prefix also written
-        as <prefix>fixThresh_mesh.ply / <prefix>adapt_mesh.ply (quads, per-vertex normals, colours from out["rgb_list"] when it is there)."""
+        as <prefix>fixThresh_mesh.ply / <prefix>adapt_mesh.ply (quads, per-vertex normals, colours from out["rgb_list"] when it is there).
+      min_component=k: fixThresh_clean_list, adapt_clean_list - the two denoised masks without the floaters, the
+        connected components (across cubes, component_connectivity 6 / 18 / 26) of fewer than k world cells (components.remove_floaters). The
+        normals, unique and mesh extras are then computed from the CLEAN masks; the denoised lists stay as they are."""
     from . import adapthresh, denoising, sparseCubes
     from . import normals as _normals
     N_vp = int(N_viewPairs4inference)
     if mesh and cameraTs_np is None:
         raise ValueError("mesh=True needs cameraTs_np: the mesher reads the oriented normals")
-    extras = cameraTs_np is not None or unique
+    if min_component is not None:
+        from . import components as _components
+        _components.check_args(min_component, None, component_connectivity)
+    extras = cameraTs_np is not None or unique or min_component is not None
     stride_vox = _normals.stride_voxels(cube_Dcenter, cube_overlapping_ratio) if extras else None      # (fails here, before any stage has run)
     pred_l, ijk_l, votes_l = out["prediction_list"], out["vxl_ijk_list"], out["rayPooling_votes_list"]
     n = len(ijk_l)
@@ -600,6 +606,8 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
         res.update(fixThresh_normal_list=[], adapt_normal_list=[])
     if unique:
         res.update(fixThresh_unique_list=[], adapt_unique_list=[])
+    if min_component is not None:
+        res.update(fixThresh_clean_list=[], adapt_clean_list=[])
     if mesh:
         from . import mesh as _mesh
         res.update(fixThresh_mesh=_mesh.empty_mesh(), adapt_mesh=_mesh.empty_mesh())
@@ -625,6 +633,9 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
                                        denoised_lists=[split(m) for m in a["denoised"]])
     for name in ("fixThresh", "adapt"):
         masks = res[name + "_denoised_list"]
+        if min_component is not None:
+            masks = res[name + "_clean_list"] = _components.remove_floaters(cube_ijk, ijk_l, masks, stride_vox, min_cells=min_component,
+                                                                            connectivity=component_connectivity)
         if cameraTs_np is not None:
             res[name + "_normal_list"] = _normals.estimate_normals(cube_ijk, ijk_l, masks, out["param_np"], out["viewPair_np"], cameraTs_np, stride_vox)
         if unique:
