@@ -30,7 +30,8 @@ extern "C" {
  * de-duplication of the output cloud; sn_gt_bind, sn_gt_bind_dev, sn_gt_cubes, sn_gt_cubes_dev, sn_weighted_accuracy and
  * sn_weighted_accuracy_dev - the ground-truth mode; sn_mesh, sn_mesh_dev and sn_mesh_cfg - the surface-nets mesh of the oriented cloud;
  * sn_mesh_sample and sn_mesh_sample_dev - surface samples of a triangle mesh; sn_components, sn_components_dev and sn_components_cfg - connected
- * components of the output cloud. */
+ * components of the output cloud; sn_mesh_simplify, sn_mesh_simplify_dev and sn_mesh_simplify_cfg - a triangle mesh made smaller by vertex
+ * clustering. */
 
 /* The library is built with -fvisibility=hidden: the functions below are its WHOLE dynamic symbol table
  * (tests/test_abi.py compares `nm -D` with this header). */
@@ -350,6 +351,42 @@ SN_API int sn_mesh_sample(sn_ctx *ctx, int n_verts, const double *verts, int n_f
                           double *points, int32_t *tri, long long *n_points);
 SN_API int sn_mesh_sample_dev(sn_ctx *ctx, int n_verts, const double *verts_dev, int n_faces, const int32_t *faces_dev, double dst,
                               long long cap_points, double *points_dev, int32_t *tri_dev, long long *n_points);
+
+/* ---- a triangle mesh made smaller: vertex clustering on a coarser lattice ---------------------------------------------
+ * verts (n_verts,3) float64 in lattice cells (sn_mesh's verts_lattice), faces (n_faces,3) int32; cfg->cell = k in 2..64 lattice cells per
+ * cluster cell and axis. A vertex is referenced iff a face names it; an unreferenced vertex is not looked at. Per component of a referenced
+ * vertex q = int64(rint(v * 256)) (requires -4 <= v < 2^21 - 8) and the cluster cell c = floor((q + 1024) / (256 k)). A cluster is the set of
+ * referenced vertices of one cell, its owner its smallest vertex index; clusters are numbered by ascending owner (P of them; P >= 2^21 is
+ * refused). Per cluster: S = the int64 sums of q, n = its size, rep = the member with the smallest (d, index), d = sum over the axes of
+ * (2 (q - o) - 256 k)^2 with o = c * 256 k - 1024: the member nearest the cell's centre. A face whose three cluster numbers are not distinct
+ * collapses; a surviving face is rotated to its smallest number first (orientation kept); of the faces with one rotated triple the smallest
+ * input index survives (the same clusters in the opposite orientation are another face). The output vertices are the clusters a surviving
+ * face uses, in number order; the output faces the surviving faces in input order:
+ *   verts_lattice (C,3) float64: placement 0 (float64(S) / float64(n)) / 256, placement 1 verts[rep] bit for bit;
+ *   verts_mm (C,3) float32 = float32(origin + resol * verts_lattice) in float64 without contraction; vert_rep (C) int32 = rep: colour,
+ *   normal and source voxel of an output vertex are a gather by the caller; vert_count (C) int32 = n; faces_out (G,3) int32; face_src (G)
+ *   int32 the input face; vert_cluster (n_verts) int32 the output vertex of an input vertex's cluster, -1 when it is unreferenced or its
+ *   cluster is used by no surviving face. Every member lies within sqrt(3) k + 1/256 cells of its output vertex.
+ * Every output is optional (NULL) except the two counts. The outputs hold cap_verts vertices and cap_faces faces; when one is short nothing is
+ * written, the counts say what is needed and the status is SN_ERR_ARG. SN_ERR_ARG too, nothing written, the text naming the first offending
+ * face: a face index outside [0, n_verts); a referenced coordinate outside the range (or not a number); also cell, placement, resol (finite,
+ * > 0), origin (finite), n_verts or n_faces > 2^28, P >= 2^21 (choose a larger cell). n_faces = 0 gives C = G = 0 and vert_cluster all -1.
+ * All sums are integers: the result equals the numpy restatement tests/meshsimplify_ref.py bit for bit, on every run. The workspace belongs to
+ * the context (grown on demand); both forms return when the work is done. */
+typedef struct sn_mesh_simplify_cfg {
+    int cell;                  /* k: lattice cells per cluster cell and axis, 2 .. 64 */
+    int placement;             /* 0: the mean of the members; 1: the member nearest the cell's centre */
+    double origin[3];          /* mm position of lattice point (0,0,0) */
+    double resol;              /* mm per cell */
+} sn_mesh_simplify_cfg;
+SN_API int sn_mesh_simplify(sn_ctx *ctx, const sn_mesh_simplify_cfg *cfg, int n_verts, const double *verts, int n_faces, const int32_t *faces,
+                            long long cap_verts, long long cap_faces, float *verts_mm, double *verts_lattice, int32_t *vert_rep,
+                            int32_t *vert_count, int32_t *faces_out, int32_t *face_src, int32_t *vert_cluster, long long *n_out_verts,
+                            long long *n_out_faces);
+SN_API int sn_mesh_simplify_dev(sn_ctx *ctx, const sn_mesh_simplify_cfg *cfg, int n_verts, const double *verts_dev, int n_faces,
+                                const int32_t *faces_dev, long long cap_verts, long long cap_faces, float *verts_mm_dev,
+                                double *verts_lattice_dev, int32_t *vert_rep_dev, int32_t *vert_count_dev, int32_t *faces_out_dev,
+                                int32_t *face_src_dev, int32_t *vert_cluster_dev, long long *n_out_verts, long long *n_out_faces);
 
 /* ---- DTU point-cloud evaluation (experiments/DTU/eval_ply.m -> PointCompareMain of the DTU kit) ----------------------
  * Points are (n,3) float64, row-major, finite. d^2 = (dx*dx + dy*dy) + dz*dz in float64 without contraction: the results are those of the numpy

@@ -629,6 +629,56 @@ class Context(object):
                 self.dev_free(b)
         return points[:M].copy(), tri[:M].copy()
 
+    def mesh_simplify(self, verts, faces, cell, placement=0, origin=(0.0, 0.0, 0.0), resol=1.0, cap=None, device=False):
+        """A triangle mesh made smaller by vertex clustering (sn_mesh_simplify): verts (V,3) float64 in lattice cells,
+        faces (F,3) int32, cell = lattice cells per cluster cell and axis (2..64), placement 0 (mean) / 1 (member), origin (3,) / resol as
+        Context.mesh takes them. Returns a dict: verts_mm (C,3) float32, verts_lattice (C,3) float64, vert_rep (C,) int32, vert_count (C,) int32,
+        faces (G,3) int32, face_src (G,) int32, vert_cluster (V,) int32. cap = (vertices, faces) the first call's arrays hold (the input's
+        counts when None, which always suffice); a short cap costs one retry with the exact counts. device=True stages the mesh in device
+        memory here and runs sn_mesh_simplify_dev on it: the same result."""
+        v = np.ascontiguousarray(verts, dtype=np.float64).reshape(-1, 3)
+        f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+        V, F = v.shape[0], f.shape[0]
+        cfg = _lib.MeshSimplifyCfg(int(cell), int(placement))
+        cfg.origin[:] = [float(x) for x in np.asarray(origin, dtype=np.float64).reshape(3)]
+        cfg.resol = float(resol)
+        caps = (min(V, 3 * F), F) if cap is None else (int(cap[0]), int(cap[1]))
+        spec = (("verts_mm", 3, np.float32), ("verts_lattice", 3, np.float64), ("vert_rep", 1, np.int32), ("vert_count", 1, np.int32),
+                ("faces", 3, np.int32), ("face_src", 1, np.int32), ("vert_cluster", 1, np.int32))
+        nv, nf = ctypes.c_longlong(0), ctypes.c_longlong(0)
+        staged = []
+        try:
+            if device:
+                for a in (v, f):
+                    staged.append(self.dev_alloc(max(a.nbytes, 16)))
+                    if a.nbytes:
+                        self.h2d(staged[-1], a)
+            for attempt in range(2):
+                rows = lambda name: V if name == "vert_cluster" else (caps[1] if name in ("faces", "face_src") else caps[0])
+                out = {name: np.empty((rows(name), w) if w > 1 else (rows(name),), dt) for name, w, dt in spec}
+                if device:
+                    bufs = [self.dev_alloc(max(out[name].nbytes, 16)) for name, _, _ in spec]
+                    staged.extend(bufs)
+                    rc = self._lib.sn_mesh_simplify_dev(self._h, ctypes.byref(cfg), V, staged[0], F, staged[1], caps[0], caps[1], *bufs,
+                                                        ctypes.byref(nv), ctypes.byref(nf))
+                else:
+                    rc = self._lib.sn_mesh_simplify(self._h, ctypes.byref(cfg), V, _lib.ptr(v), F, _lib.ptr(f), caps[0], caps[1],
+                                                    *[_lib.ptr(out[name]) for name, _, _ in spec], ctypes.byref(nv), ctypes.byref(nf))
+                if rc == -1 and attempt == 0 and (nv.value > caps[0] or nf.value > caps[1]):
+                    caps = (nv.value, nf.value)      # the counts say what is needed: one retry at that size
+                    continue
+                _lib.check(rc)
+                break
+            for k, (name, _, _) in enumerate(spec):
+                n = V if name == "vert_cluster" else (nf.value if name in ("faces", "face_src") else nv.value)
+                if device and n:
+                    self.d2h(out[name][:n], staged[-len(spec) + k])
+                out[name] = out[name][:n].copy()
+        finally:
+            for b in staged:
+                self.dev_free(b)
+        return out
+
     @staticmethod
     def _points(xyz):
         return np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))

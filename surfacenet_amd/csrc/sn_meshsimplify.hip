@@ -1,0 +1,225 @@
+// sn_meshsimplify.hip — C ABI of the mesh simplification by vertex clustering (meshsimplify.h). The device form works on
+// the caller's device arrays; the host form stages its arrays in temporary device memory and runs the same computation.
+#include "sn_internal.h"
+#include "meshsimplify.h"
+#include "scan.h"
+
+namespace {
+
+constexpr int MSIM_MAX_ITEMS = 1 << 28;              // vertices, faces: a table of >= 2 n slots stays within 2^29, n + 1 fits the scan's int
+
+struct SyncOnExit {                                  // temporary device buffers are freed on return: the stream must be done with them
+    sn_ctx *c;
+    ~SyncOnExit() { (void)hipStreamSynchronize(c->stream); }
+};
+
+// the caller's outputs: device arrays in the device form, host arrays in the host form
+struct MsimOut {
+    float *verts_mm; double *verts_lattice; int32_t *vert_rep, *vert_count, *faces, *face_src, *vert_cluster;
+};
+
+int msim_check_args(sn_ctx *c, const sn_mesh_simplify_cfg *cfg, int n_verts, int n_faces, long long cap_verts, long long cap_faces,
+                    long long *n_out_verts, long long *n_out_faces)
+{
+    if (!c) return fail(SN_ERR_ARG, "null context");
+    if (!cfg) return fail(SN_ERR_ARG, "null cfg");
+    if (!n_out_verts || !n_out_faces) return fail(SN_ERR_ARG, "n_out_verts and n_out_faces are required");
+    *n_out_verts = 0; *n_out_faces = 0;
+    if (n_verts < 0 || n_faces < 0) return fail(SN_ERR_ARG, "n_verts and n_faces must be >= 0");
+    if (n_verts > MSIM_MAX_ITEMS || n_faces > MSIM_MAX_ITEMS)
+        return fail(SN_ERR_ARG, "n_verts = %d, n_faces = %d: at most 2^28 of either", n_verts, n_faces);
+    if (cfg->cell < 2 || cfg->cell > 64) return fail(SN_ERR_ARG, "cell = %d: 2 .. 64 lattice cells per axis", cfg->cell);
+    if (cfg->placement != 0 && cfg->placement != 1) return fail(SN_ERR_ARG, "placement = %d: 0 (mean) or 1 (member)", cfg->placement);
+    if (!std::isfinite(cfg->resol) || !(cfg->resol > 0)) return fail(SN_ERR_ARG, "resol = %g must be finite and > 0", cfg->resol);
+    for (int d = 0; d < 3; ++d)
+        if (!std::isfinite(cfg->origin[d])) return fail(SN_ERR_ARG, "origin[%d] = %g is not finite", d, cfg->origin[d]);
+    if (cap_verts < 0 || cap_faces < 0) return fail(SN_ERR_ARG, "cap_verts and cap_faces must be >= 0");
+    return SN_OK;
+}
+
+template <typename T> int msim_down(sn_ctx *c, T *host, const T *dev, size_t count)
+{
+    if (host && count) HIPCHK(hipMemcpyAsync(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost, c->stream));
+    return SN_OK;
+}
+
+// The whole computation on device-resident verts and faces, F > 0. out_host: `o` names host arrays (staged through temporary device buffers).
+int msim_run(sn_ctx *c, const sn_mesh_simplify_cfg *cfg, int V, const double *verts, int F, const int32_t *faces, long long cap_verts,
+             long long cap_faces, bool out_host, const MsimOut &o, long long *n_out_verts, long long *n_out_faces)
+{
+    MsimArgs a;
+    memset(&a, 0, sizeof a);
+    a.verts = verts; a.faces = faces; a.V = V; a.F = F; a.cell = cfg->cell; a.placement = cfg->placement; a.resol = cfg->resol;
+    for (int d = 0; d < 3; ++d) a.origin[d] = cfg->origin[d];
+    const size_t vcap = table_cap((unsigned long long)V, 2, 64), fcap = table_cap((unsigned long long)F, 2, 64);
+    a.vmask = (unsigned)(vcap - 1); a.fmask = (unsigned)(fcap - 1);
+    int *vsums = nullptr, *fsums = nullptr;
+    auto layout = [&](Carve &w) {
+        a.st = w.get<MsimStat>(1);
+        a.vnum = w.get<int>((size_t)V);
+        a.vtab = w.get<unsigned long long>(2 * vcap);
+        a.sum = w.get<unsigned long long>(3 * vcap);
+        a.best = w.get<unsigned long long>(vcap);
+        a.count = w.get<unsigned>(vcap);
+        a.vflag = w.get<int>((size_t)V + 1);
+        a.vpos = w.get<int>((size_t)V + 1);
+        a.pslot = w.get<int>((size_t)V);
+        a.used = w.get<int>((size_t)V + 1);
+        a.cpos = w.get<int>((size_t)V + 1);
+        vsums = w.get<int>(scan_sums((size_t)V + 1));
+        a.ftab = w.get<unsigned long long>(2 * fcap);
+        a.fslot = w.get<int>((size_t)F);
+        a.ftri = w.get<int>(3 * (size_t)F);
+        a.fflag = w.get<int>((size_t)F + 1);
+        a.fpos = w.get<int>((size_t)F + 1);
+        fsums = w.get<int>(scan_sums((size_t)F + 1));
+    };
+    int rc = dev_carve(c, c->msim_ws, layout, 256);
+    if (rc != SN_OK) return rc;
+    const unsigned vb = blocks(V, MSIM_NT), vb1 = blocks((long long)V + 1, MSIM_NT), fb = blocks(F, MSIM_NT), fb1 = blocks((long long)F + 1, MSIM_NT);
+    const bool agg = !sn_ab_switch("SN_MSIM_NO_AGG");
+    HIPCHK(hipMemsetAsync(a.st, 0, sizeof(MsimStat), c->stream));
+    HIPCHK(hipMemsetAsync(&a.st->first_bad, 0xff, sizeof(unsigned long long), c->stream));
+    {
+        ProfScope ps(c, "msim_mark", 0, (double)F * 12.0 + (double)V * 4.0);
+        HIPCHK(hipMemsetAsync(a.vnum, 0xff, sizeof(int) * std::max<size_t>((size_t)V, 1), c->stream));      // MSIM_NONE
+        hipLaunchKernelGGL(msim_mark_kernel, dim3(fb), dim3(MSIM_NT), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    {
+        ProfScope ps(c, "msim_cluster", 0, (double)V * 28.0 + (double)vcap * 52.0);
+        HIPCHK(hipMemsetAsync(a.vtab, 0, sizeof(unsigned long long) * 2 * vcap, c->stream));
+        HIPCHK(hipMemsetAsync(a.sum, 0, sizeof(unsigned long long) * 3 * vcap, c->stream));
+        HIPCHK(hipMemsetAsync(a.best, 0xff, sizeof(unsigned long long) * vcap, c->stream));
+        HIPCHK(hipMemsetAsync(a.count, 0, sizeof(unsigned) * vcap, c->stream));
+        if (V > 0) {
+            if (agg) hipLaunchKernelGGL(msim_cluster_kernel<true>, dim3(vb), dim3(MSIM_NT), 0, c->stream, a);
+            else hipLaunchKernelGGL(msim_cluster_kernel<false>, dim3(vb), dim3(MSIM_NT), 0, c->stream, a);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    {
+        ProfScope ps(c, "msim_number", 0, (double)V * 24.0);
+        hipLaunchKernelGGL(msim_owner_kernel, dim3(vb1), dim3(MSIM_NT), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+        if ((rc = scan_exclusive(c, a.vflag, a.vpos, V + 1, vsums)) != SN_OK) return rc;      // vpos[V] = P
+        if (V > 0) {
+            hipLaunchKernelGGL(msim_number_kernel, dim3(vb), dim3(MSIM_NT), 0, c->stream, a);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    {
+        ProfScope ps(c, "msim_facekey", 0, (double)F * 40.0 + (double)fcap * 16.0);
+        HIPCHK(hipMemsetAsync(a.ftab, 0, sizeof(unsigned long long) * 2 * fcap, c->stream));
+        hipLaunchKernelGGL(msim_facekey_kernel, dim3(fb), dim3(MSIM_NT), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    {
+        ProfScope ps(c, "msim_faceown", 0, (double)F * 32.0 + (double)V * 16.0);
+        HIPCHK(hipMemsetAsync(a.used, 0, sizeof(int) * ((size_t)V + 1), c->stream));
+        hipLaunchKernelGGL(msim_faceown_kernel, dim3(fb1), dim3(MSIM_NT), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+        if ((rc = scan_exclusive(c, a.fflag, a.fpos, F + 1, fsums)) != SN_OK) return rc;      // fpos[F] = G
+        if ((rc = scan_exclusive(c, a.used, a.cpos, V + 1, vsums)) != SN_OK) return rc;       // cpos[V] = C
+        hipLaunchKernelGGL(msim_counts_kernel, dim3(1), dim3(64), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    // the one read before any output is touched: errors, then the cluster limit, then the caps
+    MsimStat st;
+    HIPCHK(hipMemcpyAsync(&st, a.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (st.first_bad != MSIM_NO_BAD) {
+        const long long f = (long long)(st.first_bad >> 3);
+        if ((st.first_bad & 7) == MSIM_ERR_INDEX) return fail(SN_ERR_ARG, "face %lld names a vertex outside [0, %d)", f, V);
+        return fail(SN_ERR_ARG, "face %lld: a coordinate of one of its vertices is outside [-4, 2^21 - 8) lattice cells (or not a number)", f);
+    }
+    if (st.P >= MSIM_MAX_CLUSTERS)
+        return fail(SN_ERR_ARG, "cell = %d gives %d clusters, at most 2^21 - 1 fit a face key: choose a larger cell", cfg->cell, st.P);
+    const size_t C = (size_t)st.C, G = (size_t)st.G;
+    *n_out_verts = st.C; *n_out_faces = st.G;
+    if (st.C > cap_verts || st.G > cap_faces)
+        return fail(SN_ERR_ARG, "the outputs hold %lld vertices and %lld faces, %d and %d are needed", cap_verts, cap_faces, st.C, st.G);
+    TmpDev t;
+    SyncOnExit sync{c};
+    MsimOut d = o;
+    if (out_host) {
+        if (o.verts_mm) d.verts_mm = t.out<float>(3 * C);
+        if (o.verts_lattice) d.verts_lattice = t.out<double>(3 * C);
+        if (o.vert_rep) d.vert_rep = t.out<int32_t>(C);
+        if (o.vert_count) d.vert_count = t.out<int32_t>(C);
+        if (o.faces) d.faces = t.out<int32_t>(3 * G);
+        if (o.face_src) d.face_src = t.out<int32_t>(G);
+        if (o.vert_cluster) d.vert_cluster = t.out<int32_t>((size_t)V);
+        if (!t.ok) return fail(SN_ERR_NOMEM, "sn_mesh_simplify: device allocation failed");
+    }
+    a.verts_mm = d.verts_mm; a.verts_lattice = d.verts_lattice; a.vert_rep = d.vert_rep; a.vert_count = d.vert_count;
+    a.faces_out = d.faces; a.face_src = d.face_src; a.vert_cluster = d.vert_cluster;
+    {
+        ProfScope ps(c, "msim_emit", 0, (double)C * 56.0 + (double)G * 16.0 + (double)F * 20.0 + (double)V * 12.0);
+        if (st.P > 0 && (a.verts_mm || a.verts_lattice || a.vert_rep || a.vert_count)) {
+            hipLaunchKernelGGL(msim_emit_verts_kernel, dim3(blocks(st.P, MSIM_NT)), dim3(MSIM_NT), 0, c->stream, a, st.P);
+            HIPCHK(hipGetLastError());
+        }
+        if (G > 0 && (a.faces_out || a.face_src)) {
+            hipLaunchKernelGGL(msim_emit_faces_kernel, dim3(fb), dim3(MSIM_NT), 0, c->stream, a);
+            HIPCHK(hipGetLastError());
+        }
+        if (V > 0 && a.vert_cluster) {
+            hipLaunchKernelGGL(msim_emit_map_kernel, dim3(vb), dim3(MSIM_NT), 0, c->stream, a);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    if (out_host) {
+        if ((rc = msim_down(c, o.verts_mm, d.verts_mm, 3 * C)) != SN_OK || (rc = msim_down(c, o.verts_lattice, d.verts_lattice, 3 * C)) != SN_OK ||
+            (rc = msim_down(c, o.vert_rep, d.vert_rep, C)) != SN_OK || (rc = msim_down(c, o.vert_count, d.vert_count, C)) != SN_OK ||
+            (rc = msim_down(c, o.faces, d.faces, 3 * G)) != SN_OK || (rc = msim_down(c, o.face_src, d.face_src, G)) != SN_OK ||
+            (rc = msim_down(c, o.vert_cluster, d.vert_cluster, (size_t)V)) != SN_OK)
+            return rc;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return SN_OK;
+}
+
+}  // namespace
+
+extern "C" int sn_mesh_simplify_dev(sn_ctx *c, const sn_mesh_simplify_cfg *cfg, int n_verts, const double *verts_dev, int n_faces,
+                                    const int32_t *faces_dev, long long cap_verts, long long cap_faces, float *verts_mm_dev,
+                                    double *verts_lattice_dev, int32_t *vert_rep_dev, int32_t *vert_count_dev, int32_t *faces_out_dev,
+                                    int32_t *face_src_dev, int32_t *vert_cluster_dev, long long *n_out_verts, long long *n_out_faces)
+{
+    int rc;
+    if ((rc = msim_check_args(c, cfg, n_verts, n_faces, cap_verts, cap_faces, n_out_verts, n_out_faces)) != SN_OK) return rc;
+    if (n_faces > 0 && (!faces_dev || (n_verts > 0 && !verts_dev))) return fail(SN_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(c->device));
+    if (n_faces == 0) {                                  // no face: no vertex is referenced
+        if (vert_cluster_dev && n_verts > 0) {
+            HIPCHK(hipMemsetAsync(vert_cluster_dev, 0xff, sizeof(int32_t) * (size_t)n_verts, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+        }
+        return SN_OK;
+    }
+    const MsimOut o = {verts_mm_dev, verts_lattice_dev, vert_rep_dev, vert_count_dev, faces_out_dev, face_src_dev, vert_cluster_dev};
+    return msim_run(c, cfg, n_verts, verts_dev, n_faces, faces_dev, cap_verts, cap_faces, false, o, n_out_verts, n_out_faces);
+}
+
+extern "C" int sn_mesh_simplify(sn_ctx *c, const sn_mesh_simplify_cfg *cfg, int n_verts, const double *verts, int n_faces, const int32_t *faces,
+                                long long cap_verts, long long cap_faces, float *verts_mm, double *verts_lattice, int32_t *vert_rep,
+                                int32_t *vert_count, int32_t *faces_out, int32_t *face_src, int32_t *vert_cluster, long long *n_out_verts,
+                                long long *n_out_faces)
+{
+    int rc;
+    if ((rc = msim_check_args(c, cfg, n_verts, n_faces, cap_verts, cap_faces, n_out_verts, n_out_faces)) != SN_OK) return rc;
+    if (n_faces > 0 && (!faces || (n_verts > 0 && !verts))) return fail(SN_ERR_ARG, "null argument");
+    if (n_faces == 0) {
+        if (vert_cluster) std::fill(vert_cluster, vert_cluster + n_verts, (int32_t)-1);
+        return SN_OK;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    TmpDev t;
+    SyncOnExit sync{c};
+    const double *d_verts = t.up(c, verts, 3 * (size_t)n_verts);
+    const int32_t *d_faces = t.up(c, faces, 3 * (size_t)n_faces);
+    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_mesh_simplify: device allocation failed");
+    const MsimOut o = {verts_mm, verts_lattice, vert_rep, vert_count, faces_out, face_src, vert_cluster};
+    return msim_run(c, cfg, n_verts, d_verts, n_faces, d_faces, cap_verts, cap_faces, true, o, n_out_verts, n_out_faces);
+}

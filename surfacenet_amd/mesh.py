@@ -3,6 +3,7 @@
     extract_mesh       vertices, quads and per-vertex source voxels from the per-cube lists plus normals.estimate_normals' normal_list
     triangulate        quads -> triangles
     sample_surface     surface samples of a mesh at the evaluation density (evaluation.mesh_compare scores them)
+    simplify_mesh      the mesh made smaller by vertex clustering on a coarser lattice
     save_mesh_2ply     binary little-endian PLY of a quad or triangle mesh
 
 The reference ends in a point cloud: its utils/mesh_util.py only reads and writes OBJ files. The mesher looks at the scene on the world voxel
@@ -108,6 +109,90 @@ def sample_surface(vertices, faces, dst=0.2):
     if f.shape[1] == 4:
         f = triangulate(f)
     return runtime.any_context().mesh_sample(v.astype(np.float64), f.astype(np.int32), d)
+
+
+PLACEMENTS = {"mean": 0, "member": 1}
+
+
+def check_simplify_args(cell, placement):
+    """-> (cell, placement code) of simplify_mesh's two settings, or ValueError."""
+    try:
+        k = int(cell)
+    except (TypeError, ValueError):
+        raise ValueError("cell = %r must be an integer" % (cell,))
+    if isinstance(cell, bool) or k != cell or not 2 <= k <= 64:
+        raise ValueError("cell = %r: an integer number of lattice cells in 2 .. 64" % (cell,))
+    if not isinstance(placement, str) or placement not in PLACEMENTS:
+        raise ValueError("placement = %r: 'mean' or 'member'" % (placement,))
+    return k, PLACEMENTS[placement]
+
+
+def simplify_mesh(vert_lattice, faces, cell, placement="mean", origin=(0.0, 0.0, 0.0), resol=1.0, vert_src=None):
+    """A mesh made smaller by vertex clustering on a lattice of `cell` lattice cells per axis: vert_lattice (V,3)
+    float32 or float64 in lattice cells as extract_mesh returns it, faces (F,3) triangles or (F,4) quads, which go through triangulate first;
+    placement "mean" (the mean of a cluster's members) or "member" (the member nearest the cluster cell's centre); origin / resol as
+    lattice_origin returns them. -> dict: vertices (C,3) float32 in mm, faces (G,3) int32, vert_lattice (C,3) float64, vert_rep (C,) int32 the
+    input vertex an output vertex stands for (colour and normal are a gather by the caller), vert_count (C,) int32, face_src (G,) int32 the
+    input triangle (face_src // 2 the quad), vert_cluster (V,) int32 the output vertex of an input vertex (-1: none); with vert_src (V,) also
+    vert_src = vert_src[vert_rep]. Every input vertex with a cluster lies within sqrt(3) cell + 1/256 cells of its output vertex. ValueError
+    on bad shapes, dtypes, settings, face indices or coordinates before the library is touched."""
+    v = np.asarray(vert_lattice)
+    if v.dtype not in (np.float32, np.float64):
+        raise ValueError("vert_lattice must be float32 or float64, not %s" % v.dtype)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError("vert_lattice must be (V,3), not %r" % (v.shape,))
+    f = np.asarray(faces)
+    if f.ndim != 2 or f.shape[1] not in (3, 4):
+        raise ValueError("faces must be (F,3) or (F,4), not %r" % (f.shape,))
+    if f.dtype.kind not in "iu":
+        raise ValueError("faces must hold integers, not %s" % f.dtype)
+    k, code = check_simplify_args(cell, placement)
+    try:
+        o = np.asarray(origin, dtype=np.float64).reshape(-1)
+        r = float(resol)
+    except (TypeError, ValueError):
+        raise ValueError("origin = %r, resol = %r must be numbers" % (origin, resol))
+    if o.shape != (3,) or not np.isfinite(o).all():
+        raise ValueError("origin = %r must be three finite numbers" % (origin,))
+    if not (np.isfinite(r) and r > 0):
+        raise ValueError("resol = %r must be finite and > 0" % (resol,))
+    if f.shape[1] == 4:
+        f = triangulate(f)
+    V, F = v.shape[0], f.shape[0]
+    if V > 1 << 28 or F > 1 << 28:
+        raise ValueError("%d vertices, %d triangles: at most 2^28 of either" % (V, F))
+    src = None
+    if vert_src is not None:
+        src = np.asarray(vert_src).reshape(-1)
+        if src.shape[0] != V:
+            raise ValueError("%d vertices, %d entries of vert_src" % (V, src.shape[0]))
+    if F:
+        bad = ((f < 0) | (f >= V)).any(axis=1)
+        if bad.any():
+            raise ValueError("face %d names a vertex outside [0, %d)" % (int(np.argmax(bad)), V))
+        referenced = np.zeros((V,), bool)
+        referenced[f.reshape(-1)] = True
+        with np.errstate(invalid="ignore"):
+            out_of_range = referenced & ~((v >= -4.0) & (v < 2097144.0)).all(axis=1)      # (NaN fails)
+        if out_of_range.any():
+            first = int(np.argmax(out_of_range[f].any(axis=1)))
+            raise ValueError("face %d: a coordinate of one of its vertices is outside [-4, 2^21 - 8) lattice cells" % first)
+        if int(referenced.sum()) >= 1 << 21:                    # only then can there be 2^21 clusters: count them (a sort of the cell keys)
+            c = (np.rint(v[referenced].astype(np.float64) * 256.0).astype(np.int64) + 1024) // (256 * k)
+            clusters = np.unique((c[:, 0] << 42) | (c[:, 1] << 21) | c[:, 2]).size
+            if clusters >= 1 << 21:
+                raise ValueError("cell = %d gives %d clusters, at most 2^21 - 1: choose a larger cell" % (k, clusters))
+    if F == 0:                                                  # no face, no referenced vertex: nothing for the library to do
+        m = dict(verts_mm=np.zeros((0, 3), np.float32), faces=np.zeros((0, 3), np.int32), verts_lattice=np.zeros((0, 3), np.float64),
+                 vert_rep=np.zeros((0,), np.int32), vert_count=np.zeros((0,), np.int32), face_src=np.zeros((0,), np.int32),
+                 vert_cluster=np.full((V,), -1, np.int32))
+    else:
+        m = runtime.any_context().mesh_simplify(v.astype(np.float64), f.astype(np.int32), k, code, origin=o, resol=r)
+    res = dict(vertices=m["verts_mm"], faces=m["faces"], vert_lattice=m["verts_lattice"], vert_rep=m["vert_rep"], vert_count=m["vert_count"],
+               face_src=m["face_src"], vert_cluster=m["vert_cluster"])
+    if src is not None:
+        res["vert_src"] = src[m["vert_rep"]]
+    return res
 
 
 def save_mesh_2ply(path, vertices, faces, normal_np=None, rgb_np=None):

@@ -565,7 +565,7 @@ def reconstruct_scene(images_list, cameraPOs_np, cubes_param_np, cube_D_mm, cube
 
 def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, gamma=0.8, beta=6, N_refine_iter=8, init_probThresh=0.5,
                    max_probThresh=0.9, keep_iterations=False, cameraTs_np=None, cube_overlapping_ratio=0.5, unique=False, mesh=False, mesh_radius=2,
-                   mesh_reach=0, mesh_ply_prefix=None, min_component=None, component_connectivity=26):
+                   mesh_reach=0, mesh_ply_prefix=None, min_component=None, component_connectivity=26, mesh_cell=None, mesh_placement="mean"):
     """The reconstruction's last two stages on `reconstruct_scene`'s dict, in memory and on the GPU, as the reference runs them on its files:
       * main_reconstruct.py:172-175  thinning masks (prob >= tau, votes >= gamma * N_vp * 2), then denoise_crossCubes with D_cube = cube_D
       * main.py:37-43 -> utils/adapthresh.py  adaptive thresholding with D_cube = cube_Dcenter, init / max threshold init_probThresh /
@@ -584,12 +584,21 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
         as <prefix>fixThresh_mesh.ply / <prefix>adapt_mesh.ply (quads, per-vertex normals, colours from out["rgb_list"] when it is there).
       min_component=k: fixThresh_clean_list, adapt_clean_list - the two denoised masks without the floaters, the
         connected components (across cubes, component_connectivity 6 / 18 / 26) of fewer than k world cells (components.remove_floaters). The
-        normals, unique and mesh extras are then computed from the CLEAN masks; the denoised lists stay as they are."""
+        normals, unique and mesh extras are then computed from the CLEAN masks; the denoised lists stay as they are.
+      mesh_cell=k (needs mesh=True): fixThresh_mesh_simplified, adapt_mesh_simplified - mesh.simplify_mesh of the two
+        triangulated meshes on a lattice of k cells per axis (mesh_placement "mean" / "member", origin and resol from mesh.lattice_origin), each
+        a dict of vertices, faces, vert_lattice, vert_rep, vert_count, face_src, vert_cluster, vert_src; with mesh_ply_prefix also written as
+        <prefix>fixThresh_mesh_c<k>.ply / <prefix>adapt_mesh_c<k>.ply (triangles, normals and colours gathered through vert_src)."""
     from . import adapthresh, denoising, sparseCubes
     from . import normals as _normals
     N_vp = int(N_viewPairs4inference)
     if mesh and cameraTs_np is None:
         raise ValueError("mesh=True needs cameraTs_np: the mesher reads the oriented normals")
+    if mesh_cell is not None:
+        if not mesh:
+            raise ValueError("mesh_cell needs mesh=True: it simplifies the mesh that mesh=True extracts")
+        from . import mesh as _mesh
+        mesh_cell = _mesh.check_simplify_args(mesh_cell, mesh_placement)[0]
     if min_component is not None:
         from . import components as _components
         _components.check_args(min_component, None, component_connectivity)
@@ -611,6 +620,11 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
     if mesh:
         from . import mesh as _mesh
         res.update(fixThresh_mesh=_mesh.empty_mesh(), adapt_mesh=_mesh.empty_mesh())
+        if mesh_cell is not None:
+            empty = _mesh.empty_mesh()
+            for name in ("fixThresh", "adapt"):
+                res[name + "_mesh_simplified"] = _mesh.simplify_mesh(empty["vert_lattice"], empty["quads"], mesh_cell, mesh_placement,
+                                                                     vert_src=empty["vert_src"])
     if n == 0:
         return res
     cube_ijk = out["cube_ijk_np"]
@@ -651,6 +665,13 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
                 if rgb is not None:
                     rgb[src < 0] = 0
                 _mesh.save_mesh_2ply("%s%s_mesh.ply" % (mesh_ply_prefix, name), m["vertices"], m["quads"], normal_np=nrm, rgb_np=rgb)
+            if mesh_cell is not None:
+                origin, resol = _mesh.lattice_origin(cube_ijk, out["param_np"], stride_vox)
+                sm = _mesh.simplify_mesh(m["vert_lattice"], m["quads"], mesh_cell, mesh_placement, origin=origin, resol=resol, vert_src=m["vert_src"])
+                res[name + "_mesh_simplified"] = sm
+                if mesh_ply_prefix is not None:
+                    _mesh.save_mesh_2ply("%s%s_mesh_c%d.ply" % (mesh_ply_prefix, name, mesh_cell), sm["vertices"], sm["faces"],
+                                         normal_np=nrm[sm["vert_rep"]], rgb_np=None if rgb is None else rgb[sm["vert_rep"]])
     return res
 
 
