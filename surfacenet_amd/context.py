@@ -1,4 +1,5 @@
 """`Context`: one GPU's SurfaceNet inference state (images, cameras, weights, workspace) over the C ABI."""
+import contextlib
 import ctypes
 
 import numpy as np
@@ -437,6 +438,66 @@ class Context(object):
             raise ValueError("cube ijk must lie in [0, 2^32)")
         return offsets, n, ijk, np.ascontiguousarray(cube, dtype=np.uint32)
 
+    @staticmethod
+    def _masked(offsets, ijk, mask, normals=None):
+        """(mask as (T,) uint8, T = offsets[-1]) of packed lists whose ijk, mask (and normals, when given) all have T rows."""
+        m = np.ascontiguousarray(mask, dtype=bool).reshape(-1).view(np.uint8)
+        T = int(offsets[-1])
+        rows = [(ijk.shape[0], "ijk rows"), (m.size, "mask entries")] + ([] if normals is None else [(normals.shape[0], "normals")])
+        if any(r != T for r, _ in rows):
+            raise ValueError("offsets end at %d voxels: %s" % (T, ", ".join("%d %s" % row for row in rows)))
+        return m, T
+
+    @contextlib.contextmanager
+    def _on_device(self, arrays, upload=True):
+        """The numpy arrays in device memory for the length of a `with` block: yields their device pointers (16 bytes at least each; upload=False:
+        room only, for outputs) and frees them on the way out."""
+        bufs = []
+        try:
+            for a in arrays:
+                bufs.append(self.dev_alloc(max(a.nbytes, 16)))
+                if upload and a.nbytes:
+                    self.h2d(bufs[-1], a)
+            yield bufs
+        finally:
+            for b in bufs:
+                self.dev_free(b)
+
+    def _sized(self, call, caps):
+        """Runs call(caps, counts) -> status for an entry whose outputs hold caps (a tuple) items and which writes what it needs to counts (as
+        many c_longlong). Outputs that are too short come back as SN_ERR_ARG with the counts needed: one retry at exactly those. Returns the
+        counts as ints."""
+        counts = tuple(ctypes.c_longlong(0) for _ in caps)
+        rc = call(caps, counts)
+        if rc == -1 and any(c.value > cap for c, cap in zip(counts, caps)):
+            rc = call(tuple(c.value for c in counts), counts)
+        _lib.check(rc)
+        return tuple(c.value for c in counts)
+
+    def _sized_outputs(self, run, spec, rows, caps, src=None):
+        """An entry with sized outputs, in its host form (src None) or its device form (src: the inputs' device pointers): spec = (name, width,
+        dtype) of each output in the entry's order, rows(name, sizes) its number of rows when the sizes are caps or counts, run(caps, srcs,
+        outs, counts) -> status the C call. Returns {name: the array at its exact rows}."""
+        out = {}
+
+        def call(caps, counts):
+            for name, w, dt in spec:
+                out[name] = np.empty((rows(name, caps), w) if w > 1 else (rows(name, caps),), dt)
+            if src is None:
+                return run(caps, (), [_lib.ptr(out[name]) for name, _, _ in spec], [ctypes.byref(c) for c in counts])
+            with self._on_device(out.values(), upload=False) as dst:
+                rc = run(caps, src, dst, [ctypes.byref(c) for c in counts])
+                for (name, _, _), b in zip(spec, dst):
+                    r = rows(name, [c.value for c in counts])
+                    if rc == 0 and r:
+                        self.d2h(out[name][:r], b)
+                return rc
+
+        counts = self._sized(call, caps)
+        for name, _, _ in spec:                      # one by one: each cap-sized array is released before the next copy is made
+            out[name] = out[name][:rows(name, counts)].copy()
+        return out
+
     def denoise(self, offsets, ijk, cube_ijk, mask, D_cube, Dc):
         """denoising.denoise_crossCubes (utils/denoising.py:150-184) on packed voxel lists: offsets (n+1,) int64, ijk (T,3) uint8 (each < Dc),
         cube_ijk (n,3), mask (T,) bool -> (T,) bool."""
@@ -474,10 +535,7 @@ class Context(object):
         cube_ijk (n,3), mask (T,) bool, stride_vox the cube stride in voxels; cube_xyz (n,3) / cube_resol (n,) float32, view_idx (n,K) int32 and
         cameraTs (V,3) float64 orient them (needed with return_normals). Returns normals (T,3) float32, moments (T,10) int32, or both as a tuple."""
         offsets, n, ijk, cube = self._packed(offsets, ijk, cube_ijk)
-        m = np.ascontiguousarray(mask, dtype=bool).reshape(-1).view(np.uint8)
-        T = int(offsets[-1])
-        if ijk.shape[0] != T or m.size != T:
-            raise ValueError("offsets end at %d voxels: %d ijk rows, %d mask entries" % (T, ijk.shape[0], m.size))
+        m, T = self._masked(offsets, ijk, mask)
         cx = cr = vi = cam = nrm = mom = None
         K = V = 0
         if return_normals:
@@ -500,10 +558,7 @@ class Context(object):
         """One voxel per world cell (sn_unique_voxels): (T,) bool, True for a masked voxel with the smallest packed index among the masked voxels
         that share its cell cube_ijk * stride_vox + ijk."""
         offsets, n, ijk, cube = self._packed(offsets, ijk, cube_ijk)
-        m = np.ascontiguousarray(mask, dtype=bool).reshape(-1).view(np.uint8)
-        T = int(offsets[-1])
-        if ijk.shape[0] != T or m.size != T:
-            raise ValueError("offsets end at %d voxels: %d ijk rows, %d mask entries" % (T, ijk.shape[0], m.size))
+        m, T = self._masked(offsets, ijk, mask)
         keep = np.zeros((T,), np.uint8)
         _lib.check(self._lib.sn_unique_voxels(self._h, n, int(stride_vox), _lib.ptr(offsets), _lib.ptr(ijk), _lib.ptr(cube), _lib.ptr(m), _lib.ptr(keep)))
         return keep.view(bool)
@@ -514,10 +569,7 @@ class Context(object):
         unmasked; cells (T,) int32 - the component's size in distinct cells; keep (T,) bool - masked and cells >= min_cells; C). device=True
         stages the lists in device memory here and runs sn_components_dev on them: the same result."""
         offsets, n, ijk, cube = self._packed(offsets, ijk, cube_ijk)
-        m = np.ascontiguousarray(mask, dtype=bool).reshape(-1).view(np.uint8)
-        T = int(offsets[-1])
-        if ijk.shape[0] != T or m.size != T:
-            raise ValueError("offsets end at %d voxels: %d ijk rows, %d mask entries" % (T, ijk.shape[0], m.size))
+        m, T = self._masked(offsets, ijk, mask)
         cfg = _lib.ComponentsCfg(int(stride_vox), int(connectivity), int(min_cells))
         label, cells, keep = np.full((T,), -1, np.int32), np.zeros((T,), np.int32), np.zeros((T,), np.uint8)
         C = ctypes.c_longlong(0)
@@ -525,19 +577,11 @@ class Context(object):
             _lib.check(self._lib.sn_components(self._h, n, ctypes.byref(cfg), _lib.ptr(offsets), _lib.ptr(ijk), _lib.ptr(cube), _lib.ptr(m),
                                                _lib.ptr(label), _lib.ptr(cells), _lib.ptr(keep), ctypes.byref(C)))
             return label, cells, keep.view(bool), int(C.value)
-        staged = []
-        try:
-            for a in (offsets, ijk, cube, m, label, cells, keep):
-                staged.append(self.dev_alloc(max(a.nbytes, 16)))
-                if a.nbytes:
-                    self.h2d(staged[-1], a)
+        with self._on_device((offsets, ijk, cube, m, label, cells, keep)) as staged:
             _lib.check(self._lib.sn_components_dev(self._h, n, ctypes.byref(cfg), T, *staged, ctypes.byref(C)))
             for a, b in zip((label, cells, keep), staged[4:]):
                 if a.nbytes:
                     self.d2h(a, b)
-        finally:
-            for b in staged:
-                self.dev_free(b)
         return label, cells, keep.view(bool), int(C.value)
 
     def mesh(self, offsets, ijk, cube_ijk, mask, stride_vox, normals, radius=2, reach=0, origin=(0.0, 0.0, 0.0), resol=1.0, cap=None, device=False):
@@ -547,48 +591,21 @@ class Context(object):
         call's arrays hold (a guess from the voxel count when None); a short guess costs one retry with the exact counts. device=True stages the
         lists in device memory here and runs sn_mesh_dev on them: the same result."""
         offsets, n, ijk, cube = self._packed(offsets, ijk, cube_ijk)
-        m = np.ascontiguousarray(mask, dtype=bool).reshape(-1).view(np.uint8)
-        T = int(offsets[-1])
         nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
-        if ijk.shape[0] != T or m.size != T or nrm.shape[0] != T:
-            raise ValueError("offsets end at %d voxels: %d ijk rows, %d mask entries, %d normals" % (T, ijk.shape[0], m.size, nrm.shape[0]))
+        m, T = self._masked(offsets, ijk, mask, nrm)
         cfg = _lib.MeshCfg(int(radius), int(reach), int(stride_vox))
         cfg.origin[:] = [float(v) for v in np.asarray(origin, dtype=np.float64).reshape(3)]
         cfg.resol = float(resol)
         caps = (2 * T + 64, 2 * T + 64) if cap is None else (int(cap[0]), int(cap[1]))
         spec = (("verts_mm", 3, np.float32), ("verts_lattice", 3, np.float64), ("vert_cell", 3, np.int32), ("vert_src", 1, np.int64), ("quads", 4, np.int32))
-        nv, nq = ctypes.c_longlong(0), ctypes.c_longlong(0)
-        staged = []
-        try:
-            if device:
-                for a in (offsets, ijk, cube, m, nrm):
-                    staged.append(self.dev_alloc(max(a.nbytes, 16)))
-                    if a.nbytes:
-                        self.h2d(staged[-1], a)
-            for attempt in range(2):
-                rows = lambda name: caps[1] if name == "quads" else caps[0]
-                out = {name: np.empty((rows(name), w) if w > 1 else (rows(name),), dt) for name, w, dt in spec}
-                if device:
-                    bufs = [self.dev_alloc(max(out[name].nbytes, 16)) for name, _, _ in spec]
-                    staged.extend(bufs)
-                    rc = self._lib.sn_mesh_dev(self._h, n, ctypes.byref(cfg), T, *staged[:5], caps[0], caps[1], *bufs, ctypes.byref(nv), ctypes.byref(nq))
-                else:
-                    rc = self._lib.sn_mesh(self._h, n, ctypes.byref(cfg), _lib.ptr(offsets), _lib.ptr(ijk), _lib.ptr(cube), _lib.ptr(m), _lib.ptr(nrm),
-                                           caps[0], caps[1], *[_lib.ptr(out[name]) for name, _, _ in spec], ctypes.byref(nv), ctypes.byref(nq))
-                if rc == -1 and attempt == 0 and (nv.value > caps[0] or nq.value > caps[1]):
-                    caps = (nv.value, nq.value)      # the counts say what is needed: one retry at that size
-                    continue
-                _lib.check(rc)
-                break
-            for (name, _, _), k in zip(spec, range(5)):
-                rows = nq.value if name == "quads" else nv.value
-                if device and rows:
-                    self.d2h(out[name][:rows] if out[name].ndim == 1 else out[name][:rows, :], staged[-5 + k])
-                out[name] = out[name][:rows].copy()
-        finally:
-            for b in staged:
-                self.dev_free(b)
-        return out
+        rows = lambda name, sizes: sizes[1] if name == "quads" else sizes[0]
+        if not device:
+            run = lambda caps, _, outs, counts: self._lib.sn_mesh(self._h, n, ctypes.byref(cfg), _lib.ptr(offsets), _lib.ptr(ijk), _lib.ptr(cube),
+                                                                  _lib.ptr(m), _lib.ptr(nrm), caps[0], caps[1], *outs, *counts)
+            return self._sized_outputs(run, spec, rows, caps)
+        run = lambda caps, src, outs, counts: self._lib.sn_mesh_dev(self._h, n, ctypes.byref(cfg), T, *src, caps[0], caps[1], *outs, *counts)
+        with self._on_device((offsets, ijk, cube, m, nrm)) as src:
+            return self._sized_outputs(run, spec, rows, caps, src)
 
     def mesh_sample(self, vertices, faces, dst, cap=None, device=False):
         """Surface samples of a triangle mesh (sn_mesh_sample): vertices (V,3) float64, faces (F,3) int32, dst the
@@ -598,36 +615,17 @@ class Context(object):
         v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
         f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
         V, F = v.shape[0], f.shape[0]
-        cap = 16 * F + 64 if cap is None else int(cap)
-        m = ctypes.c_longlong(0)
-        staged = []
-        try:
-            if device:
-                for a in (v, f):
-                    staged.append(self.dev_alloc(max(a.nbytes, 16)))
-                    if a.nbytes:
-                        self.h2d(staged[-1], a)
-            for attempt in range(2):
-                points, tri = np.empty((cap, 3), np.float64), np.empty((cap,), np.int32)
-                if device:
-                    bufs = [self.dev_alloc(max(points.nbytes, 16)), self.dev_alloc(max(tri.nbytes, 16))]
-                    staged.extend(bufs)
-                    rc = self._lib.sn_mesh_sample_dev(self._h, V, staged[0], F, staged[1], float(dst), cap, bufs[0], bufs[1], ctypes.byref(m))
-                else:
-                    rc = self._lib.sn_mesh_sample(self._h, V, _lib.ptr(v), F, _lib.ptr(f), float(dst), cap, _lib.ptr(points), _lib.ptr(tri), ctypes.byref(m))
-                if rc == -1 and attempt == 0 and m.value > cap:
-                    cap = m.value                    # the count says what is needed: one retry at that size
-                    continue
-                _lib.check(rc)
-                break
-            M = m.value
-            if device and M:
-                self.d2h(points[:M], staged[-2])
-                self.d2h(tri[:M], staged[-1])
-        finally:
-            for b in staged:
-                self.dev_free(b)
-        return points[:M].copy(), tri[:M].copy()
+        caps = (16 * F + 64 if cap is None else int(cap),)
+        spec = (("points", 3, np.float64), ("tri", 1, np.int32))
+        rows = lambda name, sizes: sizes[0]
+        if not device:
+            run = lambda caps, _, outs, counts: self._lib.sn_mesh_sample(self._h, V, _lib.ptr(v), F, _lib.ptr(f), float(dst), caps[0], *outs, *counts)
+            out = self._sized_outputs(run, spec, rows, caps)
+        else:
+            run = lambda caps, src, outs, counts: self._lib.sn_mesh_sample_dev(self._h, V, src[0], F, src[1], float(dst), caps[0], *outs, *counts)
+            with self._on_device((v, f)) as src:
+                out = self._sized_outputs(run, spec, rows, caps, src)
+        return out["points"], out["tri"]
 
     def mesh_simplify(self, verts, faces, cell, placement=0, origin=(0.0, 0.0, 0.0), resol=1.0, cap=None, device=False):
         """A triangle mesh made smaller by vertex clustering (sn_mesh_simplify): verts (V,3) float64 in lattice cells,
@@ -645,39 +643,15 @@ class Context(object):
         caps = (min(V, 3 * F), F) if cap is None else (int(cap[0]), int(cap[1]))
         spec = (("verts_mm", 3, np.float32), ("verts_lattice", 3, np.float64), ("vert_rep", 1, np.int32), ("vert_count", 1, np.int32),
                 ("faces", 3, np.int32), ("face_src", 1, np.int32), ("vert_cluster", 1, np.int32))
-        nv, nf = ctypes.c_longlong(0), ctypes.c_longlong(0)
-        staged = []
-        try:
-            if device:
-                for a in (v, f):
-                    staged.append(self.dev_alloc(max(a.nbytes, 16)))
-                    if a.nbytes:
-                        self.h2d(staged[-1], a)
-            for attempt in range(2):
-                rows = lambda name: V if name == "vert_cluster" else (caps[1] if name in ("faces", "face_src") else caps[0])
-                out = {name: np.empty((rows(name), w) if w > 1 else (rows(name),), dt) for name, w, dt in spec}
-                if device:
-                    bufs = [self.dev_alloc(max(out[name].nbytes, 16)) for name, _, _ in spec]
-                    staged.extend(bufs)
-                    rc = self._lib.sn_mesh_simplify_dev(self._h, ctypes.byref(cfg), V, staged[0], F, staged[1], caps[0], caps[1], *bufs,
-                                                        ctypes.byref(nv), ctypes.byref(nf))
-                else:
-                    rc = self._lib.sn_mesh_simplify(self._h, ctypes.byref(cfg), V, _lib.ptr(v), F, _lib.ptr(f), caps[0], caps[1],
-                                                    *[_lib.ptr(out[name]) for name, _, _ in spec], ctypes.byref(nv), ctypes.byref(nf))
-                if rc == -1 and attempt == 0 and (nv.value > caps[0] or nf.value > caps[1]):
-                    caps = (nv.value, nf.value)      # the counts say what is needed: one retry at that size
-                    continue
-                _lib.check(rc)
-                break
-            for k, (name, _, _) in enumerate(spec):
-                n = V if name == "vert_cluster" else (nf.value if name in ("faces", "face_src") else nv.value)
-                if device and n:
-                    self.d2h(out[name][:n], staged[-len(spec) + k])
-                out[name] = out[name][:n].copy()
-        finally:
-            for b in staged:
-                self.dev_free(b)
-        return out
+        rows = lambda name, sizes: V if name == "vert_cluster" else (sizes[1] if name in ("faces", "face_src") else sizes[0])
+        if not device:
+            run = lambda caps, _, outs, counts: self._lib.sn_mesh_simplify(self._h, ctypes.byref(cfg), V, _lib.ptr(v), F, _lib.ptr(f), caps[0], caps[1],
+                                                                           *outs, *counts)
+            return self._sized_outputs(run, spec, rows, caps)
+        run = lambda caps, src, outs, counts: self._lib.sn_mesh_simplify_dev(self._h, ctypes.byref(cfg), V, src[0], F, src[1], caps[0], caps[1],
+                                                                             *outs, *counts)
+        with self._on_device((v, f)) as src:
+            return self._sized_outputs(run, spec, rows, caps, src)
 
     @staticmethod
     def _points(xyz):
@@ -730,16 +704,7 @@ class Context(object):
             cfg.lo[:], cfg.hi[:] = b[0].tolist(), b[1].tolist()
         return cfg
 
-    def _ptcubes_sized(self, call, cap):
-        """Runs call(cap, n_cells) -> status; a list longer than cap comes back as SN_ERR_ARG with the length needed: one retry at that length.
-        Returns (n_cells, cap used)."""
-        n_cells = ctypes.c_longlong(0)
-        rc = call(cap, n_cells)
-        if rc == -1 and n_cells.value > cap:
-            cap = n_cells.value
-            rc = call(cap, n_cells)
-        _lib.check(rc)
-        return n_cells.value, cap
+    _PTCUBES_OUT = (("ijk", 3, np.uint32), ("xyz", 3, np.float32))
 
     def ptcubes(self, pts, stride_q, stride_xyz, half, compute_f64, box=None, cap=None):
         """The cell list of scene.quantizePts2Cubes (sn_ptcubes): pts (n,3) float32 or float64; stride_q the stride of the cell index (in the
@@ -751,41 +716,21 @@ class Context(object):
         p = np.ascontiguousarray(p.reshape(-1, 3))
         n = p.shape[0]
         cfg = self._ptcubes_cfg(p.dtype == np.float64, compute_f64, stride_q, stride_xyz, half, box)
-        out = {}
-
-        def call(cap, n_cells):
-            out["ijk"], out["xyz"] = np.empty((cap, 3), np.uint32), np.empty((cap, 3), np.float32)
-            return self._lib.sn_ptcubes(self._h, n, _lib.ptr(p), ctypes.byref(cfg), cap, _lib.ptr(out["ijk"]), _lib.ptr(out["xyz"]), ctypes.byref(n_cells))
-
-        m, _ = self._ptcubes_sized(call, min(2 * n, 1 << 22) if cap is None else int(cap))
-        return out["ijk"][:m].copy(), out["xyz"][:m].copy()
+        run = lambda caps, _, outs, counts: self._lib.sn_ptcubes(self._h, n, _lib.ptr(p), ctypes.byref(cfg), caps[0], *outs, *counts)
+        out = self._sized_outputs(run, self._PTCUBES_OUT, lambda name, sizes: sizes[0], (min(2 * n, 1 << 22) if cap is None else int(cap),))
+        return out["ijk"], out["xyz"]
 
     def _ptcubes_dev_sized(self, run, cap):
         """The device-output forms: run(cap, ijk_dev, xyz_dev, n_cells) -> status. Returns the arrays on the host."""
-        bufs = []
-
-        def call(cap, n_cells):
-            for b in bufs:
-                self.dev_free(b)
-            bufs[:] = [self.dev_alloc(max(12 * cap, 16)), self.dev_alloc(max(12 * cap, 16))]
-            return run(cap, bufs[0], bufs[1], n_cells)
-
-        try:
-            m, _ = self._ptcubes_sized(call, cap)
-            ijk, xyz = np.empty((m, 3), np.uint32), np.empty((m, 3), np.float32)
-            if m:
-                self.d2h(ijk, bufs[0])
-                self.d2h(xyz, bufs[1])
-        finally:
-            for b in bufs:
-                self.dev_free(b)
-        return ijk, xyz
+        call = lambda caps, _, outs, counts: run(caps[0], outs[0], outs[1], counts[0])
+        out = self._sized_outputs(call, self._PTCUBES_OUT, lambda name, sizes: sizes[0], (cap,), src=())
+        return out["ijk"], out["xyz"]
 
     def ptcubes_dev(self, n, pts_dev, pts_f64, stride_q, stride_xyz, half, compute_f64, box=None, cap=None):
         """ptcubes for n points already in HBM (sn_ptcubes_dev); the cell list is built in device memory and returned on the host."""
         cfg = self._ptcubes_cfg(pts_f64, compute_f64, stride_q, stride_xyz, half, box)
         run = lambda cap, ijk_dev, xyz_dev, n_cells: self._lib.sn_ptcubes_dev(self._h, int(n), pts_dev, ctypes.byref(cfg), cap, ijk_dev, xyz_dev,
-                                                                              ctypes.byref(n_cells))
+                                                                              n_cells)
         return self._ptcubes_dev_sized(run, min(2 * int(n), 1 << 22) if cap is None else int(cap))
 
     def ptcubes_sparse(self, offsets, vxl_ijk, mask, cube_xyz, cube_resol, stride_q, stride_xyz, half, compute_f64, box=None, cap=None):
@@ -795,17 +740,14 @@ class Context(object):
         offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
         n = offsets.size - 1
         ijk = np.ascontiguousarray(vxl_ijk, dtype=np.uint8).reshape(-1, 3)
-        m = np.ascontiguousarray(mask, dtype=bool).reshape(-1).view(np.uint8)
-        T = int(offsets[-1])
-        if ijk.shape[0] != T or m.size != T:
-            raise ValueError("offsets end at %d voxels: %d ijk rows, %d mask entries" % (T, ijk.shape[0], m.size))
+        m, T = self._masked(offsets, ijk, mask)
         cx = np.ascontiguousarray(cube_xyz, dtype=np.float32).reshape(n, 3)
         cr = np.ascontiguousarray(cube_resol, dtype=np.float32).reshape(n)
         cfg = self._ptcubes_cfg(False, compute_f64, stride_q, stride_xyz, half, box)
         dev = [self.upload(a) for a in (offsets, ijk, m, cx, cr)]
         try:
             run = lambda cap, ijk_dev, xyz_dev, n_cells: self._lib.sn_ptcubes_sparse_dev(self._h, n, T, dev[0], dev[1], dev[2], dev[3], dev[4],
-                                                                                         ctypes.byref(cfg), cap, ijk_dev, xyz_dev, ctypes.byref(n_cells))
+                                                                                         ctypes.byref(cfg), cap, ijk_dev, xyz_dev, n_cells)
             return self._ptcubes_dev_sized(run, min(2 * T, 1 << 22) if cap is None else int(cap))
         finally:
             for d in dev:

@@ -848,16 +848,17 @@ int sn_relative_weights(sn_ctx *c, int n, int n_vp, const float *features, float
     HIPCHK(hipSetDevice(c->device));
     { int rcb = relw_fresh_b2(c); if (rcb != SN_OK) return rcb; }
     const size_t rows = (size_t)n * n_vp;
-    TmpDev t;      // freed on every return path
-    float *d_f = t.up(c, features, rows * kDFeature), *d_z = t.out<float>(rows), *d_o = t.out<float>(rows);
-    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_relative_weights: device allocation failed");
-    hipLaunchKernelGGL(relw_mlp_kernel, dim3((unsigned)rows), dim3(128), 0, c->stream, d_f, c->relw_W1, c->relw_scale, c->relw_shift,
+    HostMirror m(c, true);
+    float *d_z = nullptr;                              // the logits: scratch
+    int rc = m.inputs([&](Carve &w) { m.in(w, features, rows * kDFeature); d_z = w.get<float>(rows); });
+    if (rc != SN_OK) return rc;
+    if ((rc = m.outputs([&](Carve &w) { m.out(w, weights, rows); })) != SN_OK) return rc;
+    hipLaunchKernelGGL(relw_mlp_kernel, dim3((unsigned)rows), dim3(128), 0, c->stream, features, c->relw_W1, c->relw_scale, c->relw_shift,
                        c->relw_w2, c->relw_b2, d_z, kDFeature, kHidden);
-    hipLaunchKernelGGL(relw_softmax_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, c->stream, d_z, d_o, n, n_vp);
+    hipLaunchKernelGGL(relw_softmax_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, c->stream, d_z, weights, n, n_vp);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(weights, d_o, rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return SN_OK;
+    if ((rc = m.back(weights, rows)) != SN_OK) return rc;
+    return m.finish();
 }
 
 // viewPairSelection's weight computation for EVERY 2-combination of views at once (utils/viewPairSelection.py:63-77): the
@@ -877,20 +878,24 @@ int sn_viewpair_weights(sn_ctx *c, int n_cubes, int n_views, const float *embedd
     for (int i = 0; i < n_views; ++i)
         for (int j = i + 1; j < n_views; ++j) { pairs.push_back(i); pairs.push_back(j); }
     const size_t rows = (size_t)n_cubes * P, ne = (size_t)n_cubes * n_views * 128;
-    TmpDev t;
-    float *d_e = t.up(c, embeddings, ne), *d_d = t.up(c, dissimilarity, rows), *d_t = t.up(c, theta, rows), *d_z = t.out<float>(rows), *d_o = t.out<float>(rows);
-    int *d_p = t.up(c, pairs.data(), pairs.size());
-    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_viewpair_weights: device allocation failed");
+    HostMirror m(c, true);
+    const int *d_p = pairs.data();
+    float *d_z = nullptr;                              // the logits: scratch
+    int rc = m.inputs([&](Carve &w) {
+        m.in(w, embeddings, ne); m.in(w, dissimilarity, rows); m.in(w, theta, rows); m.in(w, d_p, pairs.size());
+        d_z = w.get<float>(rows);
+    });
+    if (rc != SN_OK) return rc;
+    if ((rc = m.outputs([&](Carve &w) { m.out(w, weights, rows); })) != SN_OK) return rc;
     {
         ProfScope ps(c, "relw_mlp_pairs", 2.0 * rows * kDFeature * kHidden, (double)rows * 12.0 + (double)ne * 4.0);
-        hipLaunchKernelGGL(relw_mlp_pairs_kernel, dim3((unsigned)rows), dim3(128), 0, c->stream, d_e, d_p, d_d, d_t, n_views, P, c->relw_W1, c->relw_scale,
-                           c->relw_shift, c->relw_w2, c->relw_b2, d_z, kHidden);
-        hipLaunchKernelGGL(relw_softmax_kernel, dim3((unsigned)((n_cubes + 127) / 128)), dim3(128), 0, c->stream, d_z, d_o, n_cubes, P);
+        hipLaunchKernelGGL(relw_mlp_pairs_kernel, dim3((unsigned)rows), dim3(128), 0, c->stream, embeddings, d_p, dissimilarity, theta, n_views, P,
+                           c->relw_W1, c->relw_scale, c->relw_shift, c->relw_w2, c->relw_b2, d_z, kHidden);
+        hipLaunchKernelGGL(relw_softmax_kernel, dim3((unsigned)((n_cubes + 127) / 128)), dim3(128), 0, c->stream, d_z, weights, n_cubes, P);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipMemcpyAsync(weights, d_o, sizeof(float) * rows, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return SN_OK;
+    if ((rc = m.back(weights, rows)) != SN_OK) return rc;
+    return m.finish();
 }
 
 // utils.generate_voxelLevelWeighted_coloredCubes (utils/utils.py:8-42) on device-resident tensors
@@ -918,22 +923,13 @@ int sn_color_fuse(sn_ctx *c, int n, int n_vp, const float *cvc, const float *mea
     if (n < 0 || n_vp < 1) return fail(SN_ERR_ARG, "bad n / n_vp");
     if (n == 0) return SN_OK;
     HIPCHK(hipSetDevice(c->device));
-    const size_t s3 = (size_t)c->s * c->s * c->s;
-    float *d_c = nullptr, *d_u = nullptr, *d_wt = nullptr; unsigned char *d_r = nullptr;
-    hipError_t e = hipMalloc((void **)&d_c, sizeof(float) * 6 * s3 * n * n_vp);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_u, sizeof(float) * s3 * n * n_vp);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_wt, sizeof(float) * n * n_vp);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_r, 3 * s3 * n);
-    int rc = SN_OK;
-    if (e == hipSuccess) e = hipMemcpyAsync(d_c, cvc, sizeof(float) * 6 * s3 * n * n_vp, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_u, unfused, sizeof(float) * s3 * n * n_vp, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_wt, w, sizeof(float) * n * n_vp, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) rc = sn_color_fuse_dev(c, n, n_vp, d_c, mean6, d_u, d_wt, d_r);
-    if (e == hipSuccess && rc == SN_OK) e = hipMemcpyAsync(rgb, d_r, 3 * s3 * n, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_c); (void)hipFree(d_u); (void)hipFree(d_wt); (void)hipFree(d_r);
-    if (e != hipSuccess) return fail(SN_ERR_HIP, "sn_color_fuse: %s", hipGetErrorString(e));
-    return rc;
+    const size_t s3 = (size_t)c->s * c->s * c->s, R = (size_t)n * n_vp;
+    HostMirror m(c, true);
+    int rc = m.inputs([&](Carve &cv) { m.in(cv, cvc, 6 * s3 * R); m.in(cv, unfused, s3 * R); m.in(cv, w, R); });
+    if (rc != SN_OK) return rc;
+    if ((rc = m.outputs([&](Carve &cv) { m.out(cv, rgb, 3 * s3 * n); })) != SN_OK) return rc;
+    if ((rc = sn_color_fuse_dev(c, n, n_vp, cvc, mean6, unfused, w, rgb)) != SN_OK || (rc = m.back(rgb, 3 * s3 * n)) != SN_OK) return rc;
+    return m.finish();
 }
 
 // ---- multi-GPU exchange: RCCL all-gather over xGMI (the one collective of the path) ---------------------

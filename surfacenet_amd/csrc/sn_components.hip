@@ -1,5 +1,5 @@
 // sn_components.hip — C ABI of the connected components of the output cloud over the packed sparse voxel lists (components.h; DESIGN.md
-// section 4.14). The host form stages its arrays in the context's workspace and wraps the device form's computation.
+// section 4.14). The host form is the device form on the host mirror's device copies of its arrays (sn_internal.h HostMirror).
 #include "sn_internal.h"
 #include "components.h"
 #include "scan.h"
@@ -8,12 +8,10 @@ namespace {
 
 constexpr long long CP_MAX_VOXELS = 1ll << 28;       // a hash table of >= 2 * total slots stays within 2^29; total + 1 fits the scan's int
 
-// One call's arrays: the inputs and outputs (the caller's device arrays; in the host form the caller's host arrays until cp_prepare has staged
-// them) and the work buffers.
+// One call's arrays: the inputs and outputs (device arrays: the caller's, or the mirror's copies of the caller's host arrays) and the work buffers.
 struct CPCall {
     int n = 0;
     long long total = 0;
-    bool host = false, staged = true;                // staged: no upload has failed
     const int64_t *off = nullptr; const uint8_t *ijk = nullptr, *mask = nullptr; const uint32_t *cube_ijk = nullptr;
     int32_t *label = nullptr, *cells = nullptr; uint8_t *keep = nullptr;
     // work
@@ -23,25 +21,10 @@ struct CPCall {
     int *count = nullptr, *flag = nullptr, *number = nullptr, *sums = nullptr;      // count | flag are one region (one memset)
 };
 
-template <typename T> void cp_stage(sn_ctx *c, Carve &w, CPCall &k, T *&p, size_t count, bool input)
+// the work buffers, in the context's cp_ws
+void cp_layout(Carve &w, CPCall &k)
 {
-    if (!k.host || !p) return;
-    auto *d = w.get<typename std::remove_const<T>::type>(count);
-    if (!w.base) return;
-    if (input && count && hipMemcpyAsync(d, p, sizeof(T) * count, hipMemcpyHostToDevice, c->stream) != hipSuccess) k.staged = false;
-    p = d;
-}
-
-void cp_layout(sn_ctx *c, Carve &w, CPCall &k)
-{
-    const size_t n = (size_t)k.n, T = (size_t)k.total;
-    cp_stage(c, w, k, k.off, n + 1, true);
-    cp_stage(c, w, k, k.cube_ijk, 3 * n, true);
-    cp_stage(c, w, k, k.ijk, 3 * T, true);
-    cp_stage(c, w, k, k.mask, T, true);
-    cp_stage(c, w, k, k.label, T, false);
-    cp_stage(c, w, k, k.cells, T, false);
-    cp_stage(c, w, k, k.keep, T, false);
+    const size_t T = (size_t)k.total;
     k.flags = w.get<int>(1);
     k.cube_of = w.get<int>(T);
     k.tab = w.get<unsigned long long>(2 * (size_t)k.cap);
@@ -52,14 +35,6 @@ void cp_layout(sn_ctx *c, Carve &w, CPCall &k)
     k.flag = k.count ? k.count + T : nullptr;
     k.number = w.get<int>(T + 1);
     k.sums = w.get<int>(scan_sums(T + 1));
-}
-
-int cp_prepare(sn_ctx *c, CPCall &k)
-{
-    k.cap = (unsigned)table_cap((unsigned long long)k.total, 2, 64);
-    int rc = dev_carve(c, c->cp_ws, [&](Carve &w) { cp_layout(c, w, k); }, 256);
-    if (rc == SN_OK && !k.staged) { (void)hipStreamSynchronize(c->stream); rc = fail(SN_ERR_HIP, "staging the host arrays failed"); }
-    return rc;
 }
 
 int cp_check(sn_ctx *c, int n, const sn_components_cfg *cfg, const long long *n_components)
@@ -148,6 +123,25 @@ int cp_run(sn_ctx *c, CPCall &k, const sn_components_cfg *cfg, long long *C)
     return SN_OK;
 }
 
+// What both forms do once their arguments are checked. host: k names the caller's host arrays. *n_components is written only on success.
+int cp_call(sn_ctx *c, bool host, CPCall &k, const sn_components_cfg *cfg, long long *n_components)
+{
+    HIPCHK(hipSetDevice(c->device));
+    const size_t n = (size_t)k.n, T = (size_t)k.total;
+    HostMirror m(c, host);
+    int rc = m.inputs([&](Carve &w) { m.in(w, k.off, n + 1); m.in(w, k.cube_ijk, 3 * n); m.in(w, k.ijk, 3 * T); m.in(w, k.mask, T); });
+    if (rc != SN_OK) return rc;
+    if ((rc = m.outputs([&](Carve &w) { m.out(w, k.label, T); m.out(w, k.cells, T); m.out(w, k.keep, T); })) != SN_OK) return rc;
+    k.cap = (unsigned)table_cap((unsigned long long)k.total, 2, 64);
+    if ((rc = dev_carve(c, c->cp_ws, [&](Carve &w) { cp_layout(w, k); }, 256)) != SN_OK) return rc;
+    long long C = 0;
+    if ((rc = cp_run(c, k, cfg, &C)) != SN_OK) return rc;
+    if ((rc = m.back(k.label, T)) != SN_OK || (rc = m.back(k.cells, T)) != SN_OK || (rc = m.back(k.keep, T)) != SN_OK) return rc;
+    if ((rc = m.finish()) != SN_OK) return rc;
+    *n_components = C;
+    return SN_OK;
+}
+
 }  // namespace
 
 extern "C" int sn_components_dev(sn_ctx *c, int n, const sn_components_cfg *cfg, long long total, const int64_t *offsets_dev, const unsigned char *ijk_dev,
@@ -159,15 +153,10 @@ extern "C" int sn_components_dev(sn_ctx *c, int n, const sn_components_cfg *cfg,
     if ((rc = cp_check_total(n, total)) != SN_OK) return rc;
     if (n == 0) { *n_components = 0; return SN_OK; }
     if (!offsets_dev || !cube_ijk_dev || (total > 0 && (!ijk_dev || !mask_dev))) return fail(SN_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(c->device));
     CPCall k;
     k.n = n; k.total = total;
     k.off = offsets_dev; k.ijk = ijk_dev; k.cube_ijk = cube_ijk_dev; k.mask = mask_dev; k.label = label_dev; k.cells = cells_dev; k.keep = keep_dev;
-    if ((rc = cp_prepare(c, k)) != SN_OK) return rc;
-    long long C = 0;
-    if ((rc = cp_run(c, k, cfg, &C)) != SN_OK) return rc;
-    *n_components = C;
-    return SN_OK;
+    return cp_call(c, false, k, cfg, n_components);
 }
 
 extern "C" int sn_components(sn_ctx *c, int n, const sn_components_cfg *cfg, const int64_t *offsets, const unsigned char *ijk, const uint32_t *cube_ijk,
@@ -181,18 +170,8 @@ extern "C" int sn_components(sn_ctx *c, int n, const sn_components_cfg *cfg, con
     const long long total = offsets[n];
     if ((rc = cp_check_total(n, total)) != SN_OK) return rc;
     if (!cube_ijk || (total > 0 && (!ijk || !mask))) return fail(SN_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(c->device));
     CPCall k;
-    k.host = true; k.n = n; k.total = total;
+    k.n = n; k.total = total;
     k.off = offsets; k.ijk = ijk; k.cube_ijk = cube_ijk; k.mask = mask; k.label = label; k.cells = cells; k.keep = keep;
-    if ((rc = cp_prepare(c, k)) != SN_OK) return rc;
-    const size_t T = (size_t)total;
-    long long C = 0;
-    if ((rc = cp_run(c, k, cfg, &C)) != SN_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    if (label && T) HIPCHK(hipMemcpyAsync(label, k.label, sizeof(int32_t) * T, hipMemcpyDeviceToHost, c->stream));
-    if (cells && T) HIPCHK(hipMemcpyAsync(cells, k.cells, sizeof(int32_t) * T, hipMemcpyDeviceToHost, c->stream));
-    if (keep && T) HIPCHK(hipMemcpyAsync(keep, k.keep, T, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    *n_components = C;
-    return SN_OK;
+    return cp_call(c, true, k, cfg, n_components);
 }

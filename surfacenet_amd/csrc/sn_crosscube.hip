@@ -185,17 +185,16 @@ extern "C" int sn_denoise(sn_ctx *c, int n, int Dc, int D_cube, const int64_t *o
     if ((rc = pl_check_host_offsets(n, offsets)) != SN_OK || (rc = pl_check_host_ijk(offsets[n], ijk, Dc)) != SN_OK) return rc;
     HIPCHK(hipSetDevice(c->device));
     const long long total = offsets[n];
-    TmpDev t;
-    int64_t *d_off = t.up(c, offsets, (size_t)n + 1);
-    uint32_t *d_cube = t.up(c, cube_ijk, 3 * (size_t)n);
-    unsigned char *d_ijk = t.up(c, ijk, 3 * (size_t)total), *d_mask = t.up(c, mask, (size_t)total), *d_out = t.out<unsigned char>((size_t)total);
-    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_denoise: device allocation failed");
+    const size_t N = (size_t)n, T = (size_t)total;
+    CCWork w;                                          // (before the mirror: the mirror waits for the stream before the work buffers go)
+    HostMirror m(c, true);
+    if ((rc = m.inputs([&](Carve &cv) { m.in(cv, offsets, N + 1); m.in(cv, cube_ijk, 3 * N); m.in(cv, ijk, 3 * T); m.in(cv, mask, T); })) != SN_OK) return rc;
+    if ((rc = m.outputs([&](Carve &cv) { m.out(cv, out, T); })) != SN_OK) return rc;
     if ((rc = err_flag(c)) != SN_OK) return rc;
-    CCWork w;
     if ((rc = cc_work(c, w, n, Dc, false)) != SN_OK) return rc;
-    if ((rc = cc_denoise(c, w, D_cube, total, d_off, d_ijk, d_cube, d_mask, d_out, nullptr)) != SN_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    if (total) HIPCHK(hipMemcpyAsync(out, d_out, (size_t)total, hipMemcpyDeviceToHost, c->stream));
-    return sn_synchronize(c);
+    if ((rc = cc_denoise(c, w, D_cube, total, offsets, ijk, cube_ijk, mask, out, nullptr)) != SN_OK) return rc;
+    if ((rc = m.back(out, T)) != SN_OK) return rc;
+    return m.finish(true);
 }
 
 // ---- adapthresh.adapthresh (utils/adapthresh.py:91-178) -----------------------------------------------------------------------------------
@@ -238,23 +237,18 @@ extern "C" int sn_adapthresh(sn_ctx *c, int n, int Dc, const sn_adapthresh_cfg *
     HIPCHK(hipSetDevice(c->device));
     const long long total = offsets[n];
     const size_t T = (size_t)total, it = (size_t)cfg->N_refine_iter;
-    TmpDev t;
-    int64_t *d_off = t.up(c, offsets, (size_t)n + 1);
-    uint32_t *d_cube = t.up(c, cube_ijk, 3 * (size_t)n);
-    unsigned char *d_ijk = t.up(c, ijk, 3 * T), *d_votes = votes ? t.up(c, votes, T) : nullptr;
-    uint16_t *d_pred = t.up(c, pred16, T);
-    unsigned char *d_init = init_denoised ? t.out<unsigned char>(T) : nullptr, *d_masks = masks ? t.out<unsigned char>(it * T) : nullptr;
-    unsigned char *d_den = denoised ? t.out<unsigned char>(it * T) : nullptr;
-    double *d_thr = thresh ? t.out<double>(it * n) : nullptr;
-    signed char *d_ch = choice ? t.out<signed char>(it * n) : nullptr;
-    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_adapthresh: device allocation failed");
+    const size_t N = (size_t)n;
+    HostMirror m(c, true);
+    rc = m.inputs([&](Carve &w) { m.in(w, offsets, N + 1); m.in(w, cube_ijk, 3 * N); m.in(w, ijk, 3 * T); m.in(w, votes, T); m.in(w, pred16, T); });
+    if (rc != SN_OK) return rc;
+    rc = m.outputs([&](Carve &w) {
+        m.out(w, init_denoised, T); m.out(w, masks, it * T); m.out(w, denoised, it * T); m.out(w, thresh, it * N); m.out(w, choice, it * N);
+    });
+    if (rc != SN_OK) return rc;
     if ((rc = err_flag(c)) != SN_OK) return rc;
-    rc = cc_adapthresh(c, n, (int)Dc, cfg, total, d_off, d_ijk, d_pred, d_votes, d_cube, d_init, d_thr, d_masks, d_den, d_ch);
-    if (rc != SN_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    if (init_denoised && T) HIPCHK(hipMemcpyAsync(init_denoised, d_init, T, hipMemcpyDeviceToHost, c->stream));
-    if (masks && T && it) HIPCHK(hipMemcpyAsync(masks, d_masks, it * T, hipMemcpyDeviceToHost, c->stream));
-    if (denoised && T && it) HIPCHK(hipMemcpyAsync(denoised, d_den, it * T, hipMemcpyDeviceToHost, c->stream));
-    if (thresh && it) HIPCHK(hipMemcpyAsync(thresh, d_thr, sizeof(double) * it * n, hipMemcpyDeviceToHost, c->stream));
-    if (choice && it) HIPCHK(hipMemcpyAsync(choice, d_ch, it * n, hipMemcpyDeviceToHost, c->stream));
-    return sn_synchronize(c);
+    if ((rc = cc_adapthresh(c, n, Dc, cfg, total, offsets, ijk, pred16, votes, cube_ijk, init_denoised, thresh, masks, denoised, choice)) != SN_OK) return rc;
+    if ((rc = m.back(init_denoised, T)) != SN_OK || (rc = m.back(masks, it * T)) != SN_OK || (rc = m.back(denoised, it * T)) != SN_OK ||
+        (rc = m.back(thresh, it * N)) != SN_OK || (rc = m.back(choice, it * N)) != SN_OK)
+        return rc;
+    return m.finish(true);
 }

@@ -139,12 +139,10 @@ extern "C" int sn_gt_bind(sn_ctx *c, long long n, const float *pts, double cell)
     int rc;
     if ((rc = gt_check_bind(c, n, pts, cell)) != SN_OK) return rc;
     HIPCHK(hipSetDevice(c->device));
-    TmpDev t;
-    float *d_pts = t.up(c, pts, 3 * (size_t)n);
-    if (!t.ok) { (void)hipStreamSynchronize(c->stream); return fail(SN_ERR_NOMEM, "sn_gt_bind: device allocation failed"); }
-    rc = gt_bind_device(c, n, d_pts, cell);
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    HostMirror m(c, true);
+    if ((rc = m.inputs([&](Carve &w) { m.in(w, pts, 3 * (size_t)n); })) != SN_OK) return rc;
+    if ((rc = gt_bind_device(c, n, pts, cell)) != SN_OK) return rc;
+    return m.finish();
 }
 
 extern "C" int sn_gt_cubes_dev(sn_ctx *c, int n, const float *xyz_dev, const float *resol_dev, float *Y_dev)
@@ -166,14 +164,11 @@ extern "C" int sn_gt_cubes(sn_ctx *c, int n, const float *xyz, const float *reso
     }
     HIPCHK(hipSetDevice(c->device));
     const size_t s3 = (size_t)c->s * c->s * c->s;
-    TmpDev t;
-    float *d_xyz = t.up(c, xyz, 3 * (size_t)n), *d_resol = t.up(c, resol, (size_t)n), *d_Y = t.out<float>((size_t)n * s3);
-    if (!t.ok) { (void)hipStreamSynchronize(c->stream); return fail(SN_ERR_NOMEM, "sn_gt_cubes: device allocation failed"); }
-    rc = gt_cubes_device(c, n, d_xyz, d_resol, d_Y);
-    if (rc == SN_OK && hipMemcpyAsync(Y, d_Y, sizeof(float) * (size_t)n * s3, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
-        rc = fail(SN_ERR_HIP, "sn_gt_cubes: copying Y back failed");
-    (void)hipStreamSynchronize(c->stream);             // the temporary arrays are freed on return
-    return rc;
+    HostMirror m(c, true);
+    if ((rc = m.inputs([&](Carve &w) { m.in(w, xyz, 3 * (size_t)n); m.in(w, resol, (size_t)n); })) != SN_OK) return rc;
+    if ((rc = m.outputs([&](Carve &w) { m.out(w, Y, (size_t)n * s3); })) != SN_OK) return rc;
+    if ((rc = gt_cubes_device(c, n, xyz, resol, Y)) != SN_OK || (rc = m.back(Y, (size_t)n * s3)) != SN_OK) return rc;
+    return m.finish();
 }
 
 extern "C" int sn_weighted_accuracy_dev(sn_ctx *c, int n, const float *pred_dev, const float *Y_dev, float threshold, int64_t *counts_dev)
@@ -190,13 +185,9 @@ extern "C" int sn_weighted_accuracy(sn_ctx *c, int n, const float *pred, const f
     if ((rc = gt_check_accuracy(c, n, pred, Y, counts)) != SN_OK || n == 0) return rc;
     HIPCHK(hipSetDevice(c->device));
     const size_t s3 = (size_t)c->s * c->s * c->s;
-    TmpDev t;
-    float *d_pred = t.up(c, pred, (size_t)n * s3), *d_Y = t.up(c, Y, (size_t)n * s3);
-    int64_t *d_counts = t.out<int64_t>(4 * (size_t)n);
-    if (!t.ok) { (void)hipStreamSynchronize(c->stream); return fail(SN_ERR_NOMEM, "sn_weighted_accuracy: device allocation failed"); }
-    rc = gt_accuracy_device(c, n, d_pred, d_Y, threshold, d_counts);
-    if (rc == SN_OK && hipMemcpyAsync(counts, d_counts, sizeof(int64_t) * 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
-        rc = fail(SN_ERR_HIP, "sn_weighted_accuracy: copying the counts back failed");
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    HostMirror m(c, true);
+    if ((rc = m.inputs([&](Carve &w) { m.in(w, pred, (size_t)n * s3); m.in(w, Y, (size_t)n * s3); })) != SN_OK) return rc;
+    if ((rc = m.outputs([&](Carve &w) { m.out(w, counts, 4 * (size_t)n); })) != SN_OK) return rc;
+    if ((rc = gt_accuracy_device(c, n, pred, Y, threshold, counts)) != SN_OK || (rc = m.back(counts, 4 * (size_t)n)) != SN_OK) return rc;
+    return m.finish();
 }

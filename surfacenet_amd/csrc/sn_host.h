@@ -1,5 +1,6 @@
 // sn_host.h — the host plumbing of the C entry points that needs no device: the error text, sizes of hash tables, bump allocation from one
-// buffer, and the argument checks of the packed sparse voxel lists. Plain C++17, no hip/ include: tests/host/sn_host_check.cpp compiles it alone.
+// buffer (Carve), the plan of a call's host mirror (MirrorPlan: which host array got which region of that buffer), and the argument checks of
+// the packed sparse voxel lists. Plain C++17, no hip/ include: tests/host/sn_host_check.cpp compiles it alone.
 #pragma once
 #include <algorithm>
 #include <cstdarg>
@@ -7,6 +8,8 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
+#include <vector>
 
 #include "../../include/surfacenet_hip.h"
 
@@ -47,6 +50,41 @@ struct Carve {
         T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
         off += std::max<size_t>(n, 1) * sizeof(T);
         return p;
+    }
+};
+
+// The host mirror of one call, as bookkeeping: every entry `sn_X` that takes host arrays is `sn_X_dev` on device copies of them. in() / out()
+// are called from inside a Carve layout (so they run twice, as every get() does): a host array that was given takes a region; the placing pass
+// records {host array, region, bytes, input or output} and swaps the caller's pointer for the region's address. What copies - uploads of the
+// recorded inputs, the copy back of an output's first `count` elements once the counting kernels have said how many there are - walks `recs`
+// (sn_internal.h HostMirror; tests/host/sn_host_check.cpp does it with memcpy). With the mirror off (a device form) and for a null array
+// nothing happens: no region, no record, the pointer stays. Scratch may be taken from the same Carve between the arrays.
+//
+// The rules of a call: at most one layout of inputs and one of outputs (two buffers: placing the outputs cannot move the staged inputs), and a
+// host form never calls another host form - it runs the device form's computation on the swapped pointers.
+struct MirrorPlan {
+    struct Rec { void *host; void *dev; size_t bytes; bool input; };
+    bool on = false;
+    std::vector<Rec> recs;
+    template <typename T> void in(Carve &w, const T *&p, size_t count) { take(w, p, count, true); }
+    template <typename T> void out(Carve &w, T *&p, size_t count) { take(w, p, count, false); }
+    // the record of a swapped pointer (nullptr: not one of this call's regions)
+    const Rec *find(const void *dev) const
+    {
+        for (const Rec &r : recs)
+            if (r.dev == dev) return &r;
+        return nullptr;
+    }
+
+private:
+    template <typename T> void take(Carve &w, T *&p, size_t count, bool input)
+    {
+        if (!on || !p) return;
+        using U = typename std::remove_const<T>::type;
+        U *d = w.get<U>(count);
+        if (!w.base) return;
+        recs.push_back(Rec{const_cast<U *>(p), d, count * sizeof(T), input});
+        p = d;
     }
 };
 

@@ -2,10 +2,10 @@
 // sn_post.hip: ray pooling + dense2sparse; sn_simil.hip: similarityNet + patch cropping; sn_crosscube.hip: cross-cube denoising + adaptive
 // thresholding; sn_pointeval.hip: point-cloud evaluation; sn_ptcubes.hip: point-seeded cube list; sn_normals.hip: normals + de-duplication; sn_components.hip: connected components; sn_mesh.hip: surface mesh; sn_meshsample.hip: surface samples of a mesh; sn_meshsimplify.hip: mesh simplification;
 // sn_gtcubes.hip: ground-truth occupancy cubes + weighted accuracy; sn_relwtrain.hip: training of the view-pair weighting net):
-// the context, owned device memory and the buffers that grow on demand (DevBuf), temporary device arrays with their host staging (TmpDev),
+// the context, owned device memory and the buffers that grow on demand (DevBuf), temporary device work buffers (TmpDev), the host forms' device copies of their arrays (HostMirror),
 // HIP-event profiling, ConvKernel (one conv3d_f16_mfma instantiation as a type: its packing geometry and its launcher) and
 // the plan rows - which kernel runs which layer - that the weight packers and the forward passes walk. What needs no device is in two hip-free
-// headers: sn_host.h (error text, table sizes, Carve, blocks, the packed-list checks) and sn_pack.h (PackedConv and the host half of weight packing).
+// headers: sn_host.h (error text, table sizes, Carve, MirrorPlan, blocks, the packed-list checks) and sn_pack.h (PackedConv and the host half of weight packing).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -168,9 +168,10 @@ struct sn_ctx {
     std::vector<std::string> num_names;   // layer name of each status bit
     DevBuf rp_ws, d_counts;       // ray pooling's hash tables; dense2sparse's per-cube counts
     int *d_err = nullptr;         // device error flag (err_flag): 1 ray pooling range, CC_ERR_INPUT_FLAG post-pass input, GT_ERR_INPUT_FLAG GT cube parameters
+    DevBuf mir_in, mir_out;       // the host forms' device copies of their input and output arrays (HostMirror), kept until the context closes
     DevBuf pe_ws;                 // point-cloud evaluation workspace (sn_pointeval.hip)
-    DevBuf nm_ws;                 // normals / unique-voxel workspace: staged arrays, brick or cell table (sn_normals.hip)
-    DevBuf cp_ws;                 // connected components (sn_components.hip): staged arrays, owner table, union-find parents, roots, counts, scan
+    DevBuf nm_ws;                 // normals / unique-voxel workspace: brick or cell table (sn_normals.hip)
+    DevBuf cp_ws;                 // connected components (sn_components.hip): owner table, union-find parents, roots, counts, scan
     DevBuf ms_ws, ms_tab, ms_field;   // mesher (sn_mesh.hip): cell + brick tables | candidate bricks | per-sample field, flags, counts
     DevBuf msmp_ws;               // mesh sampling (sn_meshsample.hip): status words, per-face counts / offsets, scan scratch
     DevBuf msim_ws;               // mesh simplification (sn_meshsimplify.hip): status, cluster and face owner tables, per-slot sums, numbers, scans
@@ -415,13 +416,18 @@ struct ConvKernel {
                                       C::HAS_BRIDGE, &launch};
 };
 
-// Temporary device arrays of one call (freed on scope exit: the stream must be done with them by then). out() allocates, up() allocates and
-// copies a host array in on the context's stream. A failed allocation (or copy) clears `ok` for good: an entry stages all its arrays, then
-// tests `ok` once.
+// Temporary device work buffers of one call, freed on scope exit. The stream must be done with them by then: a routine that can return with
+// work in flight names its context in `sync`, and the buffers wait for that stream before they go. A failed allocation clears `ok` for good: a
+// routine takes all its buffers, then tests `ok` once.
 struct TmpDev {
     std::vector<void *> p;
     bool ok = true;
-    ~TmpDev() { for (void *q : p) (void)hipFree(q); }
+    sn_ctx *sync = nullptr;
+    ~TmpDev()
+    {
+        if (sync) (void)hipStreamSynchronize(sync->stream);
+        for (void *q : p) (void)hipFree(q);
+    }
     template <typename T> T *out(size_t count)
     {
         void *q = nullptr;
@@ -429,10 +435,51 @@ struct TmpDev {
         p.push_back(q);
         return static_cast<T *>(q);
     }
-    template <typename T> T *up(sn_ctx *c, const T *host, size_t count)
+};
+
+// The host mirror of one call (sn_host.h MirrorPlan holds the rules and the bookkeeping; this adds the context, whose mir_in / mir_out hold the
+// device copies and whose stream carries the copies). A host form and its device form run the same body: the device form's mirror is off, and
+// every member below then does nothing.
+//   HostMirror m(c, host);
+//   m.inputs([&](Carve &w) { m.in(w, off, n + 1); ... });         stage and upload the inputs
+//   ... the counting kernels ...
+//   m.outputs([&](Carve &w) { m.out(w, verts, 3 * nv); ... });    room for the outputs, at their exact counts
+//   ... the kernels that write them ...
+//   m.back(verts, 3 * nv); ...                                    copy the first `count` elements to the caller's array
+//   return m.finish();                                            the one synchronize
+// A return before finish() waits for the stream too, so no copy into the caller's arrays is in flight after any return.
+struct HostMirror : MirrorPlan {
+    sn_ctx *c;
+    bool done = false;
+    HostMirror(sn_ctx *ctx, bool host) : c(ctx) { on = host; }
+    HostMirror(const HostMirror &) = delete;
+    ~HostMirror() { if (on && !done) (void)hipStreamSynchronize(c->stream); }
+    template <typename F> int inputs(F &&layout)
     {
-        T *d = out<T>(count);
-        if (d && count && hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, c->stream) != hipSuccess) ok = false;
-        return d;
+        if (!on) return SN_OK;
+        int rc = dev_carve(c, c->mir_in, layout, 256);
+        if (rc != SN_OK) return rc;
+        for (const Rec &r : recs)
+            if (r.input && r.bytes && hipMemcpyAsync(r.dev, r.host, r.bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+                return fail(SN_ERR_HIP, "staging the host arrays failed");
+        return SN_OK;
+    }
+    template <typename F> int outputs(F &&layout) { return on ? dev_carve(c, c->mir_out, layout, 256) : SN_OK; }
+    template <typename T> int back(const T *dev, size_t count)
+    {
+        if (!on || !dev || !count) return SN_OK;
+        const Rec *r = find(dev);
+        if (!r || r->input || count * sizeof(T) > r->bytes) return fail(SN_ERR_STATE, "host mirror: not %zu elements of a staged output", count);
+        if (hipMemcpyAsync(r->host, dev, count * sizeof(T), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+            return fail(SN_ERR_HIP, "copying the results to the host arrays failed");
+        return SN_OK;
+    }
+    // report: also the device error words, as sn_synchronize reports them
+    int finish(bool report = false)
+    {
+        done = true;
+        if (report) return sn_synchronize(c);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return SN_OK;
     }
 };

@@ -1,5 +1,5 @@
 // sn_mesh.hip — C ABI of the surface mesh of the oriented output cloud (mesh.h). The device form works on the caller's
-// device arrays; the host form stages its arrays in temporary device memory and runs the same computation.
+// device arrays; the host form is the same computation on the host mirror's device copies of its arrays (sn_internal.h HostMirror).
 #include "sn_internal.h"
 #include "mesh.h"
 #include "bitonic.h"
@@ -10,11 +10,6 @@ namespace {
 constexpr long long MS_MAX_VOXELS = 1ll << 28;       // hash tables of >= 2 * total slots stay within 2^29
 constexpr unsigned long long MS_MAX_BRICKS = (1ull << 28) / 27;      // the candidate table of >= 2 * 27 * bricks slots stays within 2^29
 constexpr unsigned long long MS_MAX_CAND = 1ull << 23;               // candidate bricks: 64 lattice points each, 192 quads at most: int counts
-
-struct SyncOnExit {                                  // temporary device buffers are freed on return: the stream must be done with them
-    sn_ctx *c;
-    ~SyncOnExit() { (void)hipStreamSynchronize(c->stream); }
-};
 
 int ms_check_args(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long cap_verts, long long cap_quads, long long *n_verts, long long *n_quads)
 {
@@ -37,9 +32,10 @@ int ms_check_total(int n, long long total)
     return pl_check_counts(n, total);
 }
 
-// The whole computation on device-resident lists. out_host: the outputs are host arrays (staged through temporary device buffers).
+// The whole computation on device-resident lists. `o` names the caller's outputs: the mirror gives those of a host form their device copies
+// once the counts are known.
 int ms_run(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long total, const int64_t *off, const unsigned char *ijk, const uint32_t *cube_ijk,
-           const unsigned char *mask, const float *normals, long long cap_verts, long long cap_quads, bool out_host, MSOut o, long long *n_verts,
+           const unsigned char *mask, const float *normals, long long cap_verts, long long cap_quads, HostMirror &m, MSOut o, long long *n_verts,
            long long *n_quads)
 {
     // ---- stage 1: the cell table (owners) and the brick table (occupancy of P) -------------------------------------------------------------
@@ -170,17 +166,11 @@ int ms_run(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long total, const int6
     if (nv == 0) return SN_OK;
 
     // ---- emit ------------------------------------------------------------------------------------------------------------------------------------
-    TmpDev t;
-    SyncOnExit sync{c};
-    MSOut h = o;                                     // the caller's host arrays
-    if (out_host) {
-        if (h.verts_mm) o.verts_mm = t.out<float>(3 * (size_t)nv);
-        if (h.verts_lattice) o.verts_lattice = t.out<double>(3 * (size_t)nv);
-        if (h.vert_cell) o.vert_cell = t.out<int32_t>(3 * (size_t)nv);
-        if (h.vert_src) o.vert_src = t.out<int64_t>((size_t)nv);
-        if (h.quads) o.quads = t.out<int32_t>(4 * (size_t)nq);
-        if (!t.ok) return fail(SN_ERR_NOMEM, "sn_mesh: device allocation failed");
-    }
+    const size_t NV = (size_t)nv, NQ = (size_t)nq;
+    rc = m.outputs([&](Carve &w) {
+        m.out(w, o.verts_mm, 3 * NV); m.out(w, o.verts_lattice, 3 * NV); m.out(w, o.vert_cell, 3 * NV); m.out(w, o.vert_src, NV); m.out(w, o.quads, 4 * NQ);
+    });
+    if (rc != SN_OK) return rc;
     for (int d = 0; d < 3; ++d) o.origin[d] = cfg->origin[d];
     o.resol = cfg->resol;
     if (o.verts_mm || o.verts_lattice || o.vert_cell || o.vert_src) {
@@ -193,15 +183,23 @@ int ms_run(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long total, const int6
         hipLaunchKernelGGL(ms_qemit_kernel, dim3((unsigned)nc), dim3(64), 0, c->stream, tb, f, o);
         HIPCHK(hipGetLastError());
     }
-    if (out_host) {
-        if (h.verts_mm) HIPCHK(hipMemcpyAsync(h.verts_mm, o.verts_mm, sizeof(float) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-        if (h.verts_lattice) HIPCHK(hipMemcpyAsync(h.verts_lattice, o.verts_lattice, sizeof(double) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-        if (h.vert_cell) HIPCHK(hipMemcpyAsync(h.vert_cell, o.vert_cell, sizeof(int32_t) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-        if (h.vert_src) HIPCHK(hipMemcpyAsync(h.vert_src, o.vert_src, sizeof(int64_t) * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-        if (h.quads && nq) HIPCHK(hipMemcpyAsync(h.quads, o.quads, sizeof(int32_t) * 4 * (size_t)nq, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return SN_OK;
+    if ((rc = m.back(o.verts_mm, 3 * NV)) != SN_OK || (rc = m.back(o.verts_lattice, 3 * NV)) != SN_OK || (rc = m.back(o.vert_cell, 3 * NV)) != SN_OK ||
+        (rc = m.back(o.vert_src, NV)) != SN_OK || (rc = m.back(o.quads, 4 * NQ)) != SN_OK)
+        return rc;
+    return m.finish();
+}
+
+// What both forms do once their arguments are checked. host: the arrays are the caller's host arrays.
+int ms_call(sn_ctx *c, bool host, int n, const sn_mesh_cfg *cfg, long long total, const int64_t *off, const unsigned char *ijk, const uint32_t *cube_ijk,
+            const unsigned char *mask, const float *normals, long long cap_verts, long long cap_quads, const MSOut &o, long long *n_verts,
+            long long *n_quads)
+{
+    HIPCHK(hipSetDevice(c->device));
+    const size_t N = (size_t)n, T = (size_t)total;
+    HostMirror m(c, host);
+    int rc = m.inputs([&](Carve &w) { m.in(w, off, N + 1); m.in(w, cube_ijk, 3 * N); m.in(w, ijk, 3 * T); m.in(w, mask, T); m.in(w, normals, 3 * T); });
+    if (rc != SN_OK) return rc;
+    return ms_run(c, n, cfg, total, off, ijk, cube_ijk, mask, normals, cap_verts, cap_quads, m, o, n_verts, n_quads);
 }
 
 MSOut ms_outputs(float *verts_mm, double *verts_lattice, int32_t *vert_cell, int64_t *vert_src, int32_t *quads)
@@ -224,9 +222,8 @@ extern "C" int sn_mesh_dev(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long t
     if ((rc = ms_check_total(n, total)) != SN_OK) return rc;
     if (n == 0) return SN_OK;
     if (!offsets_dev || !cube_ijk_dev || (total > 0 && (!ijk_dev || !mask_dev || !normals_dev))) return fail(SN_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(c->device));
-    return ms_run(c, n, cfg, total, offsets_dev, ijk_dev, cube_ijk_dev, mask_dev, normals_dev, cap_verts, cap_quads, false,
-                  ms_outputs(verts_mm_dev, verts_lattice_dev, vert_cell_dev, vert_src_dev, quads_dev), n_verts, n_quads);
+    return ms_call(c, false, n, cfg, total, offsets_dev, ijk_dev, cube_ijk_dev, mask_dev, normals_dev, cap_verts, cap_quads,
+                   ms_outputs(verts_mm_dev, verts_lattice_dev, vert_cell_dev, vert_src_dev, quads_dev), n_verts, n_quads);
 }
 
 extern "C" int sn_mesh(sn_ctx *c, int n, const sn_mesh_cfg *cfg, const int64_t *offsets, const unsigned char *ijk, const uint32_t *cube_ijk,
@@ -240,15 +237,6 @@ extern "C" int sn_mesh(sn_ctx *c, int n, const sn_mesh_cfg *cfg, const int64_t *
     const long long total = offsets[n];
     if ((rc = ms_check_total(n, total)) != SN_OK) return rc;
     if (!cube_ijk || (total > 0 && (!ijk || !mask || !normals))) return fail(SN_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(c->device));
-    TmpDev t;
-    SyncOnExit sync{c};
-    const size_t N = (size_t)n, T = (size_t)total;
-    const int64_t *d_off = t.up(c, offsets, N + 1);
-    const uint32_t *d_cube = t.up(c, cube_ijk, 3 * N);
-    const unsigned char *d_ijk = t.up(c, ijk, 3 * T), *d_mask = t.up(c, mask, T);
-    const float *d_nrm = t.up(c, normals, 3 * T);
-    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_mesh: device allocation failed");
-    return ms_run(c, n, cfg, total, d_off, d_ijk, d_cube, d_mask, d_nrm, cap_verts, cap_quads, true,
-                  ms_outputs(verts_mm, verts_lattice, vert_cell, vert_src, quads), n_verts, n_quads);
+    return ms_call(c, true, n, cfg, total, offsets, ijk, cube_ijk, mask, normals, cap_verts, cap_quads,
+                   ms_outputs(verts_mm, verts_lattice, vert_cell, vert_src, quads), n_verts, n_quads);
 }

@@ -1,15 +1,10 @@
 // sn_meshsample.hip — C ABI of the surface sampling of a triangle mesh (meshsample.h). The device form works on the
-// caller's device arrays; the host form stages its arrays in temporary device memory and runs the same computation.
+// caller's device arrays; the host form is the same computation on the host mirror's device copies of its arrays (sn_internal.h HostMirror).
 #include "sn_internal.h"
 #include "meshsample.h"
 #include "scan.h"
 
 namespace {
-
-struct SyncOnExit {                                  // temporary device buffers are freed on return: the stream must be done with them
-    sn_ctx *c;
-    ~SyncOnExit() { (void)hipStreamSynchronize(c->stream); }
-};
 
 int msmp_check_args(sn_ctx *c, int n_verts, int n_faces, double dst, long long cap_points, long long *n_points)
 {
@@ -23,10 +18,15 @@ int msmp_check_args(sn_ctx *c, int n_verts, int n_faces, double dst, long long c
     return SN_OK;
 }
 
-// The whole computation on device-resident verts and faces. out_host: points / tri are host arrays (staged through temporary device buffers).
-int msmp_run(sn_ctx *c, int V, const double *verts, int F, const int32_t *faces, double dst, long long cap_points, bool out_host, double *points,
+// What both forms do once their arguments are checked: the whole computation on device-resident verts and faces. host: the arrays are the
+// caller's host arrays, and the mirror gives them their device copies (points / tri once the count is known).
+int msmp_run(sn_ctx *c, bool host, int V, const double *verts, int F, const int32_t *faces, double dst, long long cap_points, double *points,
              int32_t *tri, long long *n_points)
 {
+    HIPCHK(hipSetDevice(c->device));
+    HostMirror m(c, host);
+    int rc = m.inputs([&](Carve &w) { m.in(w, verts, 3 * (size_t)V); m.in(w, faces, 3 * (size_t)F); });
+    if (rc != SN_OK) return rc;
     MsmpStat *d_st = nullptr;
     int *off = nullptr, *sums = nullptr;
     auto layout = [&](Carve &w) {
@@ -34,8 +34,7 @@ int msmp_run(sn_ctx *c, int V, const double *verts, int F, const int32_t *faces,
         off = w.get<int>((size_t)F + 1);
         sums = w.get<int>(scan_sums((size_t)F + 1));
     };
-    int rc = dev_carve(c, c->msmp_ws, layout, 256);
-    if (rc != SN_OK) return rc;
+    if ((rc = dev_carve(c, c->msmp_ws, layout, 256)) != SN_OK) return rc;
     MsmpIn in;
     memset(&in, 0, sizeof in);
     in.verts = verts; in.faces = faces; in.V = V; in.F = F; in.dst2 = dst * dst;
@@ -74,27 +73,15 @@ int msmp_run(sn_ctx *c, int V, const double *verts, int F, const int32_t *faces,
         ProfScope ps(c, "msmp_scan", 0, (double)F * 12.0);
         if ((rc = scan_exclusive(c, off, off, F + 1, sums)) != SN_OK) return rc;      // off[F] = M
     }
-    TmpDev t;
-    SyncOnExit sync{c};
-    double *d_points = points;
-    int32_t *d_tri = tri;
-    if (out_host) {
-        if (points) d_points = t.out<double>(3 * (size_t)M);
-        if (tri) d_tri = t.out<int32_t>((size_t)M);
-        if (!t.ok) return fail(SN_ERR_NOMEM, "sn_mesh_sample: device allocation failed");
-    }
+    if ((rc = m.outputs([&](Carve &w) { m.out(w, points, 3 * (size_t)M); m.out(w, tri, (size_t)M); })) != SN_OK) return rc;
     {
         ProfScope ps(c, "msmp_emit", 0, (double)M * ((points ? 24.0 : 0.0) + (tri ? 4.0 : 0.0)));
         hipLaunchKernelGGL(msmp_emit_kernel, dim3((unsigned)(((long long)M + MSMP_RUN - 1) / MSMP_RUN)), dim3(MSMP_NT), 0, c->stream, in,
-                           (const int *)off, M, d_points, d_tri);
+                           (const int *)off, M, points, tri);
         HIPCHK(hipGetLastError());
     }
-    if (out_host) {
-        if (points) HIPCHK(hipMemcpyAsync(points, d_points, sizeof(double) * 3 * (size_t)M, hipMemcpyDeviceToHost, c->stream));
-        if (tri) HIPCHK(hipMemcpyAsync(tri, d_tri, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return SN_OK;
+    if ((rc = m.back(points, 3 * (size_t)M)) != SN_OK || (rc = m.back(tri, (size_t)M)) != SN_OK) return rc;
+    return m.finish();
 }
 
 }  // namespace
@@ -105,8 +92,7 @@ extern "C" int sn_mesh_sample_dev(sn_ctx *c, int n_verts, const double *verts_de
     int rc;
     if ((rc = msmp_check_args(c, n_verts, n_faces, dst, cap_points, n_points)) != SN_OK || n_faces == 0) return rc;
     if (!faces_dev || (n_verts > 0 && !verts_dev)) return fail(SN_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(c->device));
-    return msmp_run(c, n_verts, verts_dev, n_faces, faces_dev, dst, cap_points, false, points_dev, tri_dev, n_points);
+    return msmp_run(c, false, n_verts, verts_dev, n_faces, faces_dev, dst, cap_points, points_dev, tri_dev, n_points);
 }
 
 extern "C" int sn_mesh_sample(sn_ctx *c, int n_verts, const double *verts, int n_faces, const int32_t *faces, double dst, long long cap_points,
@@ -115,11 +101,5 @@ extern "C" int sn_mesh_sample(sn_ctx *c, int n_verts, const double *verts, int n
     int rc;
     if ((rc = msmp_check_args(c, n_verts, n_faces, dst, cap_points, n_points)) != SN_OK || n_faces == 0) return rc;
     if (!faces || (n_verts > 0 && !verts)) return fail(SN_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(c->device));
-    TmpDev t;
-    SyncOnExit sync{c};
-    const double *d_verts = t.up(c, verts, 3 * (size_t)n_verts);
-    const int32_t *d_faces = t.up(c, faces, 3 * (size_t)n_faces);
-    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_mesh_sample: device allocation failed");
-    return msmp_run(c, n_verts, d_verts, n_faces, d_faces, dst, cap_points, true, points, tri, n_points);
+    return msmp_run(c, true, n_verts, verts, n_faces, faces, dst, cap_points, points, tri, n_points);
 }

@@ -1,5 +1,5 @@
 // sn_meshsimplify.hip — C ABI of the mesh simplification by vertex clustering (meshsimplify.h). The device form works on
-// the caller's device arrays; the host form stages its arrays in temporary device memory and runs the same computation.
+// the caller's device arrays; the host form is the same computation on the host mirror's device copies of its arrays (sn_internal.h HostMirror).
 #include "sn_internal.h"
 #include "meshsimplify.h"
 #include "scan.h"
@@ -7,11 +7,6 @@
 namespace {
 
 constexpr int MSIM_MAX_ITEMS = 1 << 28;              // vertices, faces: a table of >= 2 n slots stays within 2^29, n + 1 fits the scan's int
-
-struct SyncOnExit {                                  // temporary device buffers are freed on return: the stream must be done with them
-    sn_ctx *c;
-    ~SyncOnExit() { (void)hipStreamSynchronize(c->stream); }
-};
 
 // the caller's outputs: device arrays in the device form, host arrays in the host form
 struct MsimOut {
@@ -37,16 +32,14 @@ int msim_check_args(sn_ctx *c, const sn_mesh_simplify_cfg *cfg, int n_verts, int
     return SN_OK;
 }
 
-template <typename T> int msim_down(sn_ctx *c, T *host, const T *dev, size_t count)
+// What both forms do once their arguments are checked: the whole computation on device-resident verts and faces, F > 0. host: the arrays are
+// the caller's host arrays, and the mirror gives them their device copies (those of `d` once the counts are known).
+int msim_run(sn_ctx *c, bool host, const sn_mesh_simplify_cfg *cfg, int V, const double *verts, int F, const int32_t *faces, long long cap_verts,
+             long long cap_faces, MsimOut d, long long *n_out_verts, long long *n_out_faces)
 {
-    if (host && count) HIPCHK(hipMemcpyAsync(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost, c->stream));
-    return SN_OK;
-}
-
-// The whole computation on device-resident verts and faces, F > 0. out_host: `o` names host arrays (staged through temporary device buffers).
-int msim_run(sn_ctx *c, const sn_mesh_simplify_cfg *cfg, int V, const double *verts, int F, const int32_t *faces, long long cap_verts,
-             long long cap_faces, bool out_host, const MsimOut &o, long long *n_out_verts, long long *n_out_faces)
-{
+    HostMirror m(c, host);
+    int rc = m.inputs([&](Carve &w) { m.in(w, verts, 3 * (size_t)V); m.in(w, faces, 3 * (size_t)F); });
+    if (rc != SN_OK) return rc;
     MsimArgs a;
     memset(&a, 0, sizeof a);
     a.verts = verts; a.faces = faces; a.V = V; a.F = F; a.cell = cfg->cell; a.placement = cfg->placement; a.resol = cfg->resol;
@@ -74,8 +67,7 @@ int msim_run(sn_ctx *c, const sn_mesh_simplify_cfg *cfg, int V, const double *ve
         a.fpos = w.get<int>((size_t)F + 1);
         fsums = w.get<int>(scan_sums((size_t)F + 1));
     };
-    int rc = dev_carve(c, c->msim_ws, layout, 256);
-    if (rc != SN_OK) return rc;
+    if ((rc = dev_carve(c, c->msim_ws, layout, 256)) != SN_OK) return rc;
     const unsigned vb = blocks(V, MSIM_NT), vb1 = blocks((long long)V + 1, MSIM_NT), fb = blocks(F, MSIM_NT), fb1 = blocks((long long)F + 1, MSIM_NT);
     const bool agg = !sn_ab_switch("SN_MSIM_NO_AGG");
     HIPCHK(hipMemsetAsync(a.st, 0, sizeof(MsimStat), c->stream));
@@ -139,19 +131,11 @@ int msim_run(sn_ctx *c, const sn_mesh_simplify_cfg *cfg, int V, const double *ve
     *n_out_verts = st.C; *n_out_faces = st.G;
     if (st.C > cap_verts || st.G > cap_faces)
         return fail(SN_ERR_ARG, "the outputs hold %lld vertices and %lld faces, %d and %d are needed", cap_verts, cap_faces, st.C, st.G);
-    TmpDev t;
-    SyncOnExit sync{c};
-    MsimOut d = o;
-    if (out_host) {
-        if (o.verts_mm) d.verts_mm = t.out<float>(3 * C);
-        if (o.verts_lattice) d.verts_lattice = t.out<double>(3 * C);
-        if (o.vert_rep) d.vert_rep = t.out<int32_t>(C);
-        if (o.vert_count) d.vert_count = t.out<int32_t>(C);
-        if (o.faces) d.faces = t.out<int32_t>(3 * G);
-        if (o.face_src) d.face_src = t.out<int32_t>(G);
-        if (o.vert_cluster) d.vert_cluster = t.out<int32_t>((size_t)V);
-        if (!t.ok) return fail(SN_ERR_NOMEM, "sn_mesh_simplify: device allocation failed");
-    }
+    rc = m.outputs([&](Carve &w) {
+        m.out(w, d.verts_mm, 3 * C); m.out(w, d.verts_lattice, 3 * C); m.out(w, d.vert_rep, C); m.out(w, d.vert_count, C);
+        m.out(w, d.faces, 3 * G); m.out(w, d.face_src, G); m.out(w, d.vert_cluster, (size_t)V);
+    });
+    if (rc != SN_OK) return rc;
     a.verts_mm = d.verts_mm; a.verts_lattice = d.verts_lattice; a.vert_rep = d.vert_rep; a.vert_count = d.vert_count;
     a.faces_out = d.faces; a.face_src = d.face_src; a.vert_cluster = d.vert_cluster;
     {
@@ -169,15 +153,11 @@ int msim_run(sn_ctx *c, const sn_mesh_simplify_cfg *cfg, int V, const double *ve
             HIPCHK(hipGetLastError());
         }
     }
-    if (out_host) {
-        if ((rc = msim_down(c, o.verts_mm, d.verts_mm, 3 * C)) != SN_OK || (rc = msim_down(c, o.verts_lattice, d.verts_lattice, 3 * C)) != SN_OK ||
-            (rc = msim_down(c, o.vert_rep, d.vert_rep, C)) != SN_OK || (rc = msim_down(c, o.vert_count, d.vert_count, C)) != SN_OK ||
-            (rc = msim_down(c, o.faces, d.faces, 3 * G)) != SN_OK || (rc = msim_down(c, o.face_src, d.face_src, G)) != SN_OK ||
-            (rc = msim_down(c, o.vert_cluster, d.vert_cluster, (size_t)V)) != SN_OK)
-            return rc;
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return SN_OK;
+    if ((rc = m.back(d.verts_mm, 3 * C)) != SN_OK || (rc = m.back(d.verts_lattice, 3 * C)) != SN_OK || (rc = m.back(d.vert_rep, C)) != SN_OK ||
+        (rc = m.back(d.vert_count, C)) != SN_OK || (rc = m.back(d.faces, 3 * G)) != SN_OK || (rc = m.back(d.face_src, G)) != SN_OK ||
+        (rc = m.back(d.vert_cluster, (size_t)V)) != SN_OK)
+        return rc;
+    return m.finish();
 }
 
 }  // namespace
@@ -199,7 +179,7 @@ extern "C" int sn_mesh_simplify_dev(sn_ctx *c, const sn_mesh_simplify_cfg *cfg, 
         return SN_OK;
     }
     const MsimOut o = {verts_mm_dev, verts_lattice_dev, vert_rep_dev, vert_count_dev, faces_out_dev, face_src_dev, vert_cluster_dev};
-    return msim_run(c, cfg, n_verts, verts_dev, n_faces, faces_dev, cap_verts, cap_faces, false, o, n_out_verts, n_out_faces);
+    return msim_run(c, false, cfg, n_verts, verts_dev, n_faces, faces_dev, cap_verts, cap_faces, o, n_out_verts, n_out_faces);
 }
 
 extern "C" int sn_mesh_simplify(sn_ctx *c, const sn_mesh_simplify_cfg *cfg, int n_verts, const double *verts, int n_faces, const int32_t *faces,
@@ -215,11 +195,6 @@ extern "C" int sn_mesh_simplify(sn_ctx *c, const sn_mesh_simplify_cfg *cfg, int 
         return SN_OK;
     }
     HIPCHK(hipSetDevice(c->device));
-    TmpDev t;
-    SyncOnExit sync{c};
-    const double *d_verts = t.up(c, verts, 3 * (size_t)n_verts);
-    const int32_t *d_faces = t.up(c, faces, 3 * (size_t)n_faces);
-    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_mesh_simplify: device allocation failed");
     const MsimOut o = {verts_mm, verts_lattice, vert_rep, vert_count, faces_out, face_src, vert_cluster};
-    return msim_run(c, cfg, n_verts, d_verts, n_faces, d_faces, cap_verts, cap_faces, true, o, n_out_verts, n_out_faces);
+    return msim_run(c, true, cfg, n_verts, verts, n_faces, faces, cap_verts, cap_faces, o, n_out_verts, n_out_faces);
 }

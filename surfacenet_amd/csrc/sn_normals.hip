@@ -1,5 +1,5 @@
 // sn_normals.hip — C ABI of the output cloud's oriented normals and de-duplication over the packed sparse voxel lists (normals.h; DESIGN.md
-// section 4.9). The host forms stage their arrays in the context's workspace and wrap the device forms' computation.
+// section 4.9). A host form is its device form on the host mirror's device copies of its arrays (sn_internal.h HostMirror).
 #include "sn_internal.h"
 #include "normals.h"
 
@@ -7,12 +7,11 @@ namespace {
 
 constexpr long long NM_MAX_VOXELS = 1ll << 28;       // hash tables of >= 2 * total slots stay within 2^29
 
-// One call's arrays: the inputs and outputs (the caller's device arrays; in a host form the caller's host arrays until nm_prepare has staged
-// them) and the work buffers.
+// One call's arrays: the inputs and outputs (device arrays: the caller's, or the mirror's copies of the caller's host arrays) and the work buffers.
 struct NMCall {
     int n = 0, K = 0, V = 0;
     long long total = 0;
-    bool host = false, unique = false, staged = true;      // staged: no upload has failed
+    bool unique = false;
     const int64_t *off = nullptr; const uint8_t *ijk = nullptr, *mask = nullptr; const uint32_t *cube_ijk = nullptr;
     const float *xyz = nullptr, *resol = nullptr; const int32_t *view = nullptr; const double *cams = nullptr;
     float *normals = nullptr; int32_t *moments = nullptr; uint8_t *keep = nullptr;
@@ -21,44 +20,14 @@ struct NMCall {
     int *flags = nullptr, *cube_of = nullptr; double *cbar = nullptr; unsigned long long *tab = nullptr;
 };
 
-// Host forms stage their arrays in the context's workspace, not in temporary allocations: one buffer that grows serves normals and unique
-// voxels alike, call after call, with no allocation in the steady state (tests/test_gpu_workspace.py holds that up). A host array that was
-// given gets room in the workspace; the placing pass uploads it (an input) and swaps the pointer for the device copy.
-template <typename T> void nm_stage(sn_ctx *c, Carve &w, NMCall &k, T *&p, size_t count, bool input)
+// The work buffers, in the context's nm_ws: one buffer that grows serves normals and unique voxels alike, call after call, with no allocation
+// in the steady state (tests/test_gpu_workspace.py holds that up).
+void nm_layout(Carve &w, NMCall &k)
 {
-    if (!k.host || !p) return;
-    auto *d = w.get<typename std::remove_const<T>::type>(count);
-    if (!w.base) return;
-    if (input && count && hipMemcpyAsync(d, p, sizeof(T) * count, hipMemcpyHostToDevice, c->stream) != hipSuccess) k.staged = false;
-    p = d;
-}
-
-void nm_layout(sn_ctx *c, Carve &w, NMCall &k)
-{
-    const size_t n = (size_t)k.n, T = (size_t)k.total;
-    nm_stage(c, w, k, k.off, n + 1, true);
-    nm_stage(c, w, k, k.cube_ijk, 3 * n, true);
-    nm_stage(c, w, k, k.ijk, 3 * T, true);
-    nm_stage(c, w, k, k.mask, T, true);
-    nm_stage(c, w, k, k.xyz, 3 * n, true);
-    nm_stage(c, w, k, k.resol, n, true);
-    nm_stage(c, w, k, k.view, n * (size_t)k.K, true);
-    nm_stage(c, w, k, k.cams, 3 * (size_t)k.V, true);
-    nm_stage(c, w, k, k.normals, 3 * T, false);
-    nm_stage(c, w, k, k.moments, 10 * T, false);
-    nm_stage(c, w, k, k.keep, T, false);
     k.flags = w.get<int>(1);
-    k.cube_of = w.get<int>(T);
-    k.cbar = w.get<double>(3 * n);
+    k.cube_of = w.get<int>((size_t)k.total);
+    k.cbar = w.get<double>(3 * (size_t)k.n);
     k.tab = w.get<unsigned long long>(2 * (size_t)k.cap);
-}
-
-int nm_prepare(sn_ctx *c, NMCall &k)
-{
-    k.cap = (unsigned)table_cap((unsigned long long)k.total, 2, 64);
-    int rc = dev_carve(c, c->nm_ws, [&](Carve &w) { nm_layout(c, w, k); }, 256);
-    if (rc == SN_OK && !k.staged) { (void)hipStreamSynchronize(c->stream); rc = fail(SN_ERR_HIP, "staging the host arrays failed"); }
-    return rc;
 }
 
 int nm_check_common(sn_ctx *c, int n, int stride_vox)
@@ -85,7 +54,7 @@ int nm_check_total(int n, long long total)
     return pl_check_counts(n, total);
 }
 
-// The computation on device arrays. Returns when the stream is done (the flags are read in between, the work buffers are the context's).
+// The computation on device arrays (the flags are read in between; the last kernel may still run on return).
 int nm_run(sn_ctx *c, NMCall &k, const sn_normals_cfg *cfg, int stride_vox)
 {
     const int n = k.n;
@@ -125,8 +94,26 @@ int nm_run(sn_ctx *c, NMCall &k, const sn_normals_cfg *cfg, int stride_vox)
         hipLaunchKernelGGL(nm_normals_kernel, dim3(nb), dim3(NM_NT), 0, c->stream, a);
         HIPCHK(hipGetLastError());
     }
-    if (!k.host) HIPCHK(hipStreamSynchronize(c->stream));
     return SN_OK;
+}
+
+// What both forms do once their arguments are checked. host: k names the caller's host arrays.
+int nm_call(sn_ctx *c, bool host, NMCall &k, const sn_normals_cfg *cfg, int stride_vox)
+{
+    HIPCHK(hipSetDevice(c->device));
+    const size_t n = (size_t)k.n, T = (size_t)k.total;
+    HostMirror m(c, host);
+    int rc = m.inputs([&](Carve &w) {
+        m.in(w, k.off, n + 1); m.in(w, k.cube_ijk, 3 * n); m.in(w, k.ijk, 3 * T); m.in(w, k.mask, T);
+        m.in(w, k.xyz, 3 * n); m.in(w, k.resol, n); m.in(w, k.view, n * (size_t)k.K); m.in(w, k.cams, 3 * (size_t)k.V);
+    });
+    if (rc != SN_OK) return rc;
+    if ((rc = m.outputs([&](Carve &w) { m.out(w, k.normals, 3 * T); m.out(w, k.moments, 10 * T); m.out(w, k.keep, T); })) != SN_OK) return rc;
+    k.cap = (unsigned)table_cap((unsigned long long)k.total, 2, 64);
+    if ((rc = dev_carve(c, c->nm_ws, [&](Carve &w) { nm_layout(w, k); }, 256)) != SN_OK) return rc;
+    if ((rc = nm_run(c, k, cfg, stride_vox)) != SN_OK) return rc;
+    if ((rc = m.back(k.normals, 3 * T)) != SN_OK || (rc = m.back(k.moments, 10 * T)) != SN_OK || (rc = m.back(k.keep, T)) != SN_OK) return rc;
+    return m.finish();
 }
 
 }  // namespace
@@ -142,13 +129,11 @@ extern "C" int sn_normals_dev(sn_ctx *c, int n, const sn_normals_cfg *cfg, long 
     if (n == 0) return SN_OK;
     if (!offsets_dev || !cube_ijk_dev || (total > 0 && (!ijk_dev || !mask_dev))) return fail(SN_ERR_ARG, "null argument");
     if (normals_dev && (!cube_xyz_dev || !cube_resol_dev || !view_idx_dev || !cameraTs_dev)) return fail(SN_ERR_ARG, "normals need the cubes' xyz, resol, view indices and the camera centres");
-    HIPCHK(hipSetDevice(c->device));
     NMCall k;
     k.n = n; k.total = total; k.K = cfg->views_per_cube; k.V = cfg->n_views;
     k.off = offsets_dev; k.ijk = ijk_dev; k.cube_ijk = cube_ijk_dev; k.mask = mask_dev; k.xyz = cube_xyz_dev; k.resol = cube_resol_dev;
     k.view = view_idx_dev; k.cams = cameraTs_dev; k.normals = normals_dev; k.moments = moments_dev;
-    if ((rc = nm_prepare(c, k)) != SN_OK) return rc;
-    return nm_run(c, k, cfg, cfg->stride_vox);
+    return nm_call(c, false, k, cfg, cfg->stride_vox);
 }
 
 extern "C" int sn_normals(sn_ctx *c, int n, const sn_normals_cfg *cfg, const int64_t *offsets, const unsigned char *ijk, const uint32_t *cube_ijk,
@@ -169,18 +154,11 @@ extern "C" int sn_normals(sn_ctx *c, int n, const sn_normals_cfg *cfg, const int
             if (cube_resol[i] != cube_resol[0])
                 return fail(SN_ERR_ARG, "cube %d has resol %g, cube 0 %g: a cell-space normal is a direction in mm only on an isotropic lattice", i, cube_resol[i], cube_resol[0]);
     }
-    HIPCHK(hipSetDevice(c->device));
     NMCall k;
-    k.host = true; k.n = n; k.total = total; k.K = cfg->views_per_cube; k.V = cfg->n_views;
+    k.n = n; k.total = total; k.K = cfg->views_per_cube; k.V = cfg->n_views;
     k.off = offsets; k.ijk = ijk; k.cube_ijk = cube_ijk; k.mask = mask; k.normals = normals; k.moments = moments;
     if (normals) { k.xyz = cube_xyz; k.resol = cube_resol; k.view = view_idx; k.cams = cameraTs; }
-    if ((rc = nm_prepare(c, k)) != SN_OK) return rc;
-    const size_t T = (size_t)total;
-    if ((rc = nm_run(c, k, cfg, cfg->stride_vox)) != SN_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    if (normals && T) HIPCHK(hipMemcpyAsync(normals, k.normals, sizeof(float) * 3 * T, hipMemcpyDeviceToHost, c->stream));
-    if (moments && T) HIPCHK(hipMemcpyAsync(moments, k.moments, sizeof(int32_t) * 10 * T, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return SN_OK;
+    return nm_call(c, true, k, cfg, cfg->stride_vox);
 }
 
 extern "C" int sn_unique_voxels_dev(sn_ctx *c, int n, int stride_vox, long long total, const int64_t *offsets_dev, const unsigned char *ijk_dev,
@@ -191,12 +169,10 @@ extern "C" int sn_unique_voxels_dev(sn_ctx *c, int n, int stride_vox, long long 
     if ((rc = nm_check_total(n, total)) != SN_OK) return rc;
     if (n == 0) return SN_OK;
     if (!offsets_dev || !cube_ijk_dev || (total > 0 && (!ijk_dev || !mask_dev || !keep_dev))) return fail(SN_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(c->device));
     NMCall k;
     k.unique = true; k.n = n; k.total = total;
     k.off = offsets_dev; k.ijk = ijk_dev; k.cube_ijk = cube_ijk_dev; k.mask = mask_dev; k.keep = keep_dev;
-    if ((rc = nm_prepare(c, k)) != SN_OK) return rc;
-    return nm_run(c, k, nullptr, stride_vox);
+    return nm_call(c, false, k, nullptr, stride_vox);
 }
 
 extern "C" int sn_unique_voxels(sn_ctx *c, int n, int stride_vox, const int64_t *offsets, const unsigned char *ijk, const uint32_t *cube_ijk,
@@ -209,14 +185,8 @@ extern "C" int sn_unique_voxels(sn_ctx *c, int n, int stride_vox, const int64_t 
     const long long total = offsets[n];
     if ((rc = nm_check_total(n, total)) != SN_OK) return rc;
     if (!cube_ijk || (total > 0 && (!ijk || !mask || !keep))) return fail(SN_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(c->device));
     NMCall k;
-    k.host = true; k.unique = true; k.n = n; k.total = total;
+    k.unique = true; k.n = n; k.total = total;
     k.off = offsets; k.ijk = ijk; k.cube_ijk = cube_ijk; k.mask = mask; k.keep = keep;
-    if ((rc = nm_prepare(c, k)) != SN_OK) return rc;
-    const size_t T = (size_t)total;
-    if ((rc = nm_run(c, k, nullptr, stride_vox)) != SN_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    if (T) HIPCHK(hipMemcpyAsync(keep, k.keep, T, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return SN_OK;
+    return nm_call(c, true, k, nullptr, stride_vox);
 }

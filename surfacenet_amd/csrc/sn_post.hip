@@ -108,7 +108,7 @@ extern "C" int sn_dense2sparse_dev(sn_ctx *c, int n, int n_vp, const int64_t *pa
     return SN_OK;
 }
 
-// Host-array forms: stage through temporary device buffers, synchronous.
+// Host-array forms: the device forms on the host mirror's device copies of their arrays, synchronous.
 extern "C" int sn_ray_pool(sn_ctx *c, int n, int n_vp, const int64_t *pairs, const float *xyz, const float *resol, const float *pred,
                            int use_thresh, float min_prob, unsigned char *votes)
 {
@@ -120,14 +120,13 @@ extern "C" int sn_ray_pool(sn_ctx *c, int n, int n_vp, const int64_t *pairs, con
     std::vector<int64_t> wp;
     int rc;
     if ((rc = check_pairs_cam(c, (long long)n * n_vp * 2, pairs, wp)) != SN_OK) return rc;
-    const size_t s3 = (size_t)c->s * c->s * c->s;
-    TmpDev t;
-    int64_t *d_p = t.up(c, wp.data(), (size_t)n * n_vp * 2); float *d_x = t.up(c, xyz, 3 * (size_t)n), *d_r = t.up(c, resol, (size_t)n), *d_pr = t.up(c, pred, n * s3);
-    unsigned char *d_v = t.out<unsigned char>(n * s3);
-    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_ray_pool: device allocation failed");
-    if ((rc = launch_ray_pool(c, n, n_vp, d_p, d_x, d_r, d_pr, use_thresh, min_prob, d_v)) != SN_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    HIPCHK(hipMemcpyAsync(votes, d_v, n * s3, hipMemcpyDeviceToHost, c->stream));
-    return sn_synchronize(c);
+    const size_t s3 = (size_t)c->s * c->s * c->s, N = (size_t)n;
+    HostMirror m(c, true);
+    const int64_t *d_p = wp.data();
+    if ((rc = m.inputs([&](Carve &w) { m.in(w, d_p, N * n_vp * 2); m.in(w, xyz, 3 * N); m.in(w, resol, N); m.in(w, pred, N * s3); })) != SN_OK) return rc;
+    if ((rc = m.outputs([&](Carve &w) { m.out(w, votes, N * s3); })) != SN_OK) return rc;
+    if ((rc = launch_ray_pool(c, n, n_vp, d_p, xyz, resol, pred, use_thresh, min_prob, votes)) != SN_OK || (rc = m.back(votes, N * s3)) != SN_OK) return rc;
+    return m.finish(true);
 }
 
 extern "C" int sn_dense2sparse(sn_ctx *c, int n, int n_vp, const int64_t *pairs, const float *xyz, const float *resol, const float *pred,
@@ -141,36 +140,34 @@ extern "C" int sn_dense2sparse(sn_ctx *c, int n, int n_vp, const int64_t *pairs,
     HIPCHK(hipSetDevice(c->device));
     int lo, dc, rc;
     if ((rc = sparse_geometry(c, cfg, lo, dc)) != SN_OK) return rc;
-    const size_t s3 = (size_t)c->s * c->s * c->s, cap = (size_t)n * dc * dc * dc;
-    TmpDev t;
-    int64_t *d_p = nullptr; float *d_x = nullptr, *d_r = nullptr; unsigned char *d_vws = nullptr;
+    const size_t s3 = (size_t)c->s * c->s * c->s, N = (size_t)n, cap = N * dc * dc * dc;
+    const int64_t *d_p = nullptr;
     std::vector<int64_t> wp;
     if (cfg->enable_rayPooling) {
         if (!pairs || !xyz || !resol) return fail(SN_ERR_ARG, "ray pooling needs view pairs, xyz and resol");
         if (!c->cams) return fail(SN_ERR_STATE, "sn_set_cameras must be called before ray pooling");
         if ((rc = check_pairs_cam(c, (long long)n * n_vp * 2, pairs, wp)) != SN_OK) return rc;
-        d_p = t.up(c, wp.data(), (size_t)n * n_vp * 2); d_x = t.up(c, xyz, 3 * (size_t)n); d_r = t.up(c, resol, (size_t)n); d_vws = t.out<unsigned char>(n * s3);
+        d_p = wp.data();
+    } else {
+        xyz = resol = nullptr; votes_out = nullptr;
     }
-    float *d_pr = t.up(c, pred, n * s3);
-    unsigned char *d_rgb = rgb_out ? t.up(c, rgb, 3 * n * s3) : nullptr;
-    int64_t *d_off = t.out<int64_t>((size_t)n + 1);
-    unsigned char *d_ijk = t.out<unsigned char>(3 * cap), *d_ro = rgb_out ? t.out<unsigned char>(3 * cap) : nullptr;
-    unsigned char *d_vo = (votes_out && cfg->enable_rayPooling) ? t.out<unsigned char>(cap) : nullptr;
-    uint16_t *d_p16 = t.out<uint16_t>(cap);
-    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_dense2sparse: device allocation failed");
-    rc = sn_dense2sparse_dev(c, n, n_vp, d_p, d_x, d_r, d_pr, d_rgb, cfg, d_vws, d_off, d_ijk, d_p16, d_ro, d_vo);
-    if (rc != SN_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-    HIPCHK(hipMemcpyAsync(offsets, d_off, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, c->stream));
-    if ((rc = sn_synchronize(c)) != SN_OK) return rc;
-    const size_t total = (size_t)offsets[n];
-    if (total) {
-        HIPCHK(hipMemcpyAsync(ijk, d_ijk, 3 * total, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(pred16, d_p16, 2 * total, hipMemcpyDeviceToHost, c->stream));
-        if (rgb_out) HIPCHK(hipMemcpyAsync(rgb_out, d_ro, 3 * total, hipMemcpyDeviceToHost, c->stream));
-        if (d_vo) HIPCHK(hipMemcpyAsync(votes_out, d_vo, total, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    return SN_OK;
+    if (!rgb_out) rgb = nullptr;
+    const int64_t *const h_off = offsets;              // (the caller's table: the mirror swaps `offsets` for its device copy)
+    HostMirror m(c, true);
+    rc = m.inputs([&](Carve &w) { m.in(w, d_p, N * n_vp * 2); m.in(w, xyz, 3 * N); m.in(w, resol, N); m.in(w, pred, N * s3); m.in(w, rgb, 3 * N * s3); });
+    if (rc != SN_OK) return rc;
+    unsigned char *d_vws = nullptr;                    // the votes of every voxel: scratch of the device form
+    rc = m.outputs([&](Carve &w) {                     // the lists at their upper bound: the counts come out of the same launch sequence as the lists
+        if (cfg->enable_rayPooling) d_vws = w.get<unsigned char>(N * s3);
+        m.out(w, offsets, N + 1); m.out(w, ijk, 3 * cap); m.out(w, pred16, cap); m.out(w, rgb_out, 3 * cap); m.out(w, votes_out, cap);
+    });
+    if (rc != SN_OK) return rc;
+    if ((rc = sn_dense2sparse_dev(c, n, n_vp, d_p, xyz, resol, pred, rgb, cfg, d_vws, offsets, ijk, pred16, rgb_out, votes_out)) != SN_OK) return rc;
+    if ((rc = m.back(offsets, N + 1)) != SN_OK || (rc = sn_synchronize(c)) != SN_OK) return rc;
+    const size_t T = (size_t)h_off[n];                 // the table has arrived: the lists' exact size
+    if ((rc = m.back(ijk, 3 * T)) != SN_OK || (rc = m.back(pred16, T)) != SN_OK || (rc = m.back(rgb_out, 3 * T)) != SN_OK || (rc = m.back(votes_out, T)) != SN_OK)
+        return rc;
+    return m.finish();
 }
 
 // camera.perspectiveProj (utils/camera.py:123-184): V cameras x n points in one launch (see project_points_kernel).
@@ -186,21 +183,18 @@ extern "C" int sn_project_points(sn_ctx *c, int V, const double *P, int n, const
     if (n == 0) return SN_OK;
     HIPCHK(hipSetDevice(c->device));
     const size_t tot = (size_t)V * n;
-    TmpDev t;
-    double *d_x = t.up(c, xyz, (size_t)n * 3), *d_h = t.out<double>(tot), *d_w = t.out<double>(tot), *d_d = depth ? t.out<double>(tot) : nullptr;
-    double *d_P = P ? t.up(c, P, (size_t)V * 12) : c->cams;
-    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_project_points: device allocation failed");
+    HostMirror m(c, true);
+    int rc = m.inputs([&](Carve &w) { m.in(w, xyz, (size_t)n * 3); m.in(w, P, (size_t)V * 12); });
+    if (rc != SN_OK) return rc;
+    if ((rc = m.outputs([&](Carve &w) { m.out(w, img_h, tot); m.out(w, img_w, tot); m.out(w, depth, tot); })) != SN_OK) return rc;
     {
         ProfScope ps(c, "project_points", 0, (double)n * 24.0 + (double)tot * (depth ? 24.0 : 16.0));
-        hipLaunchKernelGGL(project_points_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)V), dim3(256), 0, c->stream, d_P, d_x, n, round_int,
-                           d_h, d_w, d_d);
+        hipLaunchKernelGGL(project_points_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)V), dim3(256), 0, c->stream, P ? P : c->cams, xyz, n,
+                           round_int, img_h, img_w, depth);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipMemcpyAsync(img_h, d_h, sizeof(double) * tot, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(img_w, d_w, sizeof(double) * tot, hipMemcpyDeviceToHost, c->stream));
-    if (depth) HIPCHK(hipMemcpyAsync(depth, d_d, sizeof(double) * tot, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return SN_OK;
+    if ((rc = m.back(img_h, tot)) != SN_OK || (rc = m.back(img_w, tot)) != SN_OK || (rc = m.back(depth, tot)) != SN_OK) return rc;
+    return m.finish();
 }
 
 // ---- box-speed probe (include/surfacenet_hip.h: sn_mfma_probe) ------------------------------------------------------------------------

@@ -9,11 +9,6 @@ namespace {
 constexpr long long PC_MAX_POINTS = 1ll << 27;       // hash tables of 4n slots stay within 2^29
 constexpr long long PC_DENSE_CELLS = 1ll << 27;      // largest grid of cells the occupancy bitmap is used for (16 MiB of bits)
 
-struct SyncOnExit {                                  // temporary device buffers are freed on return: the stream must be done with them
-    sn_ctx *c;
-    ~SyncOnExit() { (void)hipStreamSynchronize(c->stream); }
-};
-
 int pc_check_cfg(const sn_ptcubes_cfg *cfg, long long n, long long cap, const long long *n_cells)
 {
     if (!cfg || !n_cells) return fail(SN_ERR_ARG, "null argument");
@@ -26,9 +21,10 @@ int pc_check_cfg(const sn_ptcubes_cfg *cfg, long long n, long long cap, const lo
     return SN_OK;
 }
 
-// The whole computation on device-resident points. out_host: ijk / xyz are host arrays (staged through temporary device buffers).
+// The whole computation on device-resident points. ijk / xyz are the caller's outputs: the mirror gives those of a host form their device
+// copies once the number of cells is known.
 template <typename P, typename T>
-int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap, bool out_host, uint32_t *ijk, float *xyz, long long *n_cells)
+int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap, HostMirror &m, uint32_t *ijk, float *xyz, long long *n_cells)
 {
     *n_cells = 0;
     const long long n = src.n;
@@ -36,7 +32,7 @@ int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap,
     src.has_box = cfg->has_box;
     for (int d = 0; d < 3; ++d) { src.lo[d] = cfg->lo[d]; src.hi[d] = cfg->hi[d]; }
     TmpDev t;
-    SyncOnExit sync{c};
+    t.sync = c;                                      // (the work buffers are freed on return, whatever is in flight then)
     PCStats *d_st = t.out<PCStats>(1);
     if (!t.ok) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
     PCStats st;
@@ -86,8 +82,8 @@ int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap,
         }
         ProfScope ps(c, "pc_scan", 0, (double)n_words * 20.0);
         hipLaunchKernelGGL(pc_popc_kernel, dim3(blocks(n_words, PC_NT)), dim3(PC_NT), 0, c->stream, (const unsigned long long *)a.bitmap, n_words, count);
-        int rc = scan_exclusive(c, count, start, n_words + 1, sums);       // start[n_words] = number of cells
-        if (rc != SN_OK) return rc;
+        const int rcs = scan_exclusive(c, count, start, n_words + 1, sums);       // start[n_words] = number of cells
+        if (rcs != SN_OK) return rcs;
         int tot = 0;
         HIPCHK(hipMemcpyAsync(&tot, start + n_words, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, c->stream));
@@ -117,12 +113,10 @@ int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap,
     *n_cells = total;
     if (total > cap) return fail(SN_ERR_ARG, "the outputs hold %lld cells, %lld are needed", cap, total);
     if (total == 0) return SN_OK;
-    if (!out_host && (!ijk || !xyz)) return fail(SN_ERR_ARG, "null output");
-    e.ijk = ijk; e.xyz = xyz; e.cap = cap;
-    if (out_host) {
-        e.ijk = t.out<uint32_t>(3 * (size_t)total); e.xyz = t.out<float>(3 * (size_t)total); e.cap = total;
-        if (!t.ok) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
-    }
+    if (!ijk || !xyz) return fail(SN_ERR_ARG, "null output");       // (a host form has tested its outputs for every cap > 0)
+    int rc = m.outputs([&](Carve &w) { m.out(w, ijk, 3 * (size_t)total); m.out(w, xyz, 3 * (size_t)total); });
+    if (rc != SN_OK) return rc;
+    e.ijk = ijk; e.xyz = xyz; e.cap = total;                        // (total <= cap: the kernels emit exactly `total` cells)
     if (dense) {
         ProfScope ps(c, "pc_emit", 0, (double)total * 24.0 + (double)n_words * 12.0);
         hipLaunchKernelGGL(pc_emit_dense_kernel, dim3(blocks(n_words, PC_NT)), dim3(PC_NT), 0, c->stream, (const unsigned long long *)a.bitmap, (const int *)start, n_words, e);
@@ -130,34 +124,29 @@ int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap,
     } else {
         const long long p2 = (long long)table_cap((unsigned long long)total, 1, PC_TILE);
         if (p2 > total) hipLaunchKernelGGL(pc_pad_kernel, dim3(blocks(p2 - total, PC_NT)), dim3(PC_NT), 0, c->stream, list, total, p2);
-        int rc = pc_sort(c, list, p2);
-        if (rc != SN_OK) return rc;
+        if ((rc = pc_sort(c, list, p2)) != SN_OK) return rc;
         ProfScope ps(c, "pc_emit", 0, (double)total * 32.0);
         hipLaunchKernelGGL(pc_emit_keys_kernel, dim3(blocks(total, PC_NT)), dim3(PC_NT), 0, c->stream, (const unsigned long long *)list, total, e);
         HIPCHK(hipGetLastError());
     }
-    if (out_host) {
-        HIPCHK(hipMemcpyAsync(ijk, e.ijk, sizeof(uint32_t) * 3 * (size_t)total, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(xyz, e.xyz, sizeof(float) * 3 * (size_t)total, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return SN_OK;
+    if ((rc = m.back(ijk, 3 * (size_t)total)) != SN_OK || (rc = m.back(xyz, 3 * (size_t)total)) != SN_OK) return rc;
+    return m.finish();
 }
 
-int pc_points(sn_ctx *c, long long n, const void *pts_dev, const sn_ptcubes_cfg *cfg, long long cap, bool out_host, uint32_t *ijk, float *xyz,
+int pc_points(sn_ctx *c, long long n, const void *pts_dev, const sn_ptcubes_cfg *cfg, long long cap, HostMirror &m, uint32_t *ijk, float *xyz,
               long long *n_cells)
 {
     if (cfg->pts_f64) {
         PCPoints<double> s;
         memset(&s, 0, sizeof s);
         s.xyz = static_cast<const double *>(pts_dev); s.n = n;
-        return pc_run<double, double>(c, s, cfg, cap, out_host, ijk, xyz, n_cells);
+        return pc_run<double, double>(c, s, cfg, cap, m, ijk, xyz, n_cells);
     }
     PCPoints<float> s;
     memset(&s, 0, sizeof s);
     s.xyz = static_cast<const float *>(pts_dev); s.n = n;
-    return cfg->compute_f64 ? pc_run<float, double>(c, s, cfg, cap, out_host, ijk, xyz, n_cells)
-                            : pc_run<float, float>(c, s, cfg, cap, out_host, ijk, xyz, n_cells);
+    return cfg->compute_f64 ? pc_run<float, double>(c, s, cfg, cap, m, ijk, xyz, n_cells)
+                            : pc_run<float, float>(c, s, cfg, cap, m, ijk, xyz, n_cells);
 }
 
 }  // namespace
@@ -170,7 +159,8 @@ extern "C" int sn_ptcubes_dev(sn_ctx *c, long long n, const void *pts_dev, const
     if ((rc = pc_check_cfg(cfg, n, cap, n_cells)) != SN_OK) return rc;
     if (n > 0 && !pts_dev) return fail(SN_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(c->device));
-    return pc_points(c, n, pts_dev, cfg, cap, false, ijk_dev, xyz_dev, n_cells);
+    HostMirror m(c, false);
+    return pc_points(c, n, pts_dev, cfg, cap, m, ijk_dev, xyz_dev, n_cells);
 }
 
 extern "C" int sn_ptcubes(sn_ctx *c, long long n, const void *pts, const sn_ptcubes_cfg *cfg, long long cap, uint32_t *ijk, float *xyz, long long *n_cells)
@@ -181,13 +171,11 @@ extern "C" int sn_ptcubes(sn_ctx *c, long long n, const void *pts, const sn_ptcu
     if (n > 0 && !pts) return fail(SN_ERR_ARG, "null argument");
     if (cap > 0 && (!ijk || !xyz)) return fail(SN_ERR_ARG, "null output");
     HIPCHK(hipSetDevice(c->device));
-    TmpDev t;
+    HostMirror m(c, true);
+    const unsigned char *d_pts = static_cast<const unsigned char *>(pts);
     const size_t bytes = 3 * (size_t)n * (cfg->pts_f64 ? sizeof(double) : sizeof(float));
-    unsigned char *d_pts = t.up(c, static_cast<const unsigned char *>(pts), bytes);
-    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
-    rc = pc_points(c, n, d_pts, cfg, cap, true, ijk, xyz, n_cells);
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    if ((rc = m.inputs([&](Carve &w) { m.in(w, d_pts, bytes); })) != SN_OK) return rc;
+    return pc_points(c, n, d_pts, cfg, cap, m, ijk, xyz, n_cells);
 }
 
 extern "C" int sn_ptcubes_sparse_dev(sn_ctx *c, int n_cubes, long long total, const int64_t *offsets_dev, const unsigned char *vxl_ijk_dev,
@@ -206,6 +194,7 @@ extern "C" int sn_ptcubes_sparse_dev(sn_ctx *c, int n_cubes, long long total, co
     memset(&s, 0, sizeof s);
     s.off = offsets_dev; s.vijk = vxl_ijk_dev; s.vmask = mask_dev; s.cxyz = cube_xyz_dev; s.cresol = cube_resol_dev;
     s.n_cubes = n_cubes; s.n = total;
-    return cfg->compute_f64 ? pc_run<float, double>(c, s, cfg, cap, false, ijk_dev, xyz_dev, n_cells)
-                            : pc_run<float, float>(c, s, cfg, cap, false, ijk_dev, xyz_dev, n_cells);
+    HostMirror m(c, false);
+    return cfg->compute_f64 ? pc_run<float, double>(c, s, cfg, cap, m, ijk_dev, xyz_dev, n_cells)
+                            : pc_run<float, float>(c, s, cfg, cap, m, ijk_dev, xyz_dev, n_cells);
 }

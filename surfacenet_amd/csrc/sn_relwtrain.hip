@@ -183,18 +183,13 @@ extern "C" int sn_relw_train_step(sn_ctx *c, int n, int n_vp, const float *unfus
     if ((rc = rt_check_step(c, n, n_vp, unfused, features, Y)) != SN_OK) return rc;
     HIPCHK(hipSetDevice(c->device));
     const size_t V = (size_t)c->s * c->s * c->s, R = (size_t)n * n_vp;
-    TmpDev t;
-    float *d_U = t.up(c, unfused, R * V), *d_F = t.up(c, features, R * RT_D), *d_Y = t.up(c, Y, (size_t)n * V);
-    float *d_f = fused ? t.out<float>((size_t)n * V) : nullptr, *d_w = weights ? t.out<float>(R) : nullptr;
-    int64_t *d_counts = counts ? t.out<int64_t>(4 * (size_t)n) : nullptr;
-    if (!t.ok) { (void)hipStreamSynchronize(c->stream); return fail(SN_ERR_NOMEM, "sn_relw_train_step: device allocation failed"); }
-    rc = rt_step_device(c, n, n_vp, d_U, d_F, d_Y, d_f, d_w, d_counts, loss);
-    if (rc == SN_OK && ((fused && hipMemcpyAsync(fused, d_f, sizeof(float) * (size_t)n * V, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-                        (weights && hipMemcpyAsync(weights, d_w, sizeof(float) * R, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-                        (counts && hipMemcpyAsync(counts, d_counts, sizeof(int64_t) * 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream) != hipSuccess)))
-        rc = fail(SN_ERR_HIP, "sn_relw_train_step: copying the results back failed");
-    (void)hipStreamSynchronize(c->stream);               // the temporary arrays are freed on return
-    return rc;
+    const size_t N = (size_t)n;
+    HostMirror m(c, true);
+    if ((rc = m.inputs([&](Carve &w) { m.in(w, unfused, R * V); m.in(w, features, R * RT_D); m.in(w, Y, N * V); })) != SN_OK) return rc;
+    if ((rc = m.outputs([&](Carve &w) { m.out(w, fused, N * V); m.out(w, weights, R); m.out(w, counts, 4 * N); })) != SN_OK) return rc;
+    if ((rc = rt_step_device(c, n, n_vp, unfused, features, Y, fused, weights, counts, loss)) != SN_OK) return rc;
+    if ((rc = m.back(fused, N * V)) != SN_OK || (rc = m.back(weights, R)) != SN_OK || (rc = m.back(counts, 4 * N)) != SN_OK) return rc;
+    return m.finish();
 }
 
 extern "C" int sn_relw_train_grads(sn_ctx *c, float *out)

@@ -301,17 +301,17 @@ extern "C" int sn_embeddingpair2simil(sn_ctx *c, int n_pairs, const float *emb_p
     if (n_pairs == 0) return SN_OK;
     if (!c->simil_loaded) return fail(SN_ERR_STATE, "sn_simil_load_weights has not been called");
     HIPCHK(hipSetDevice(c->device));
-    TmpDev t;
-    float *d_e = t.up(c, emb_pairs, (size_t)2 * n_pairs * kEmb), *d_s = t.out<float>(n_pairs);
-    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_embeddingpair2simil: device allocation failed");
+    HostMirror m(c, true);
+    int rc = m.inputs([&](Carve &w) { m.in(w, emb_pairs, (size_t)2 * n_pairs * kEmb); });
+    if (rc != SN_OK) return rc;
+    if ((rc = m.outputs([&](Carve &w) { m.out(w, similarity, (size_t)n_pairs); })) != SN_OK) return rc;
     {
         ProfScope ps(c, "pair_simil", 0, (double)n_pairs * (2.0 * kEmb + 1.0) * 4.0);
-        hipLaunchKernelGGL(pair_simil_kernel, dim3((unsigned)((n_pairs + 3) / 4)), dim3(256), 0, c->stream, d_e, d_s, n_pairs, c->ssim_w, c->ssim_b);
+        hipLaunchKernelGGL(pair_simil_kernel, dim3((unsigned)((n_pairs + 3) / 4)), dim3(256), 0, c->stream, emb_pairs, similarity, n_pairs, c->ssim_w, c->ssim_b);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipMemcpyAsync(similarity, d_s, sizeof(float) * n_pairs, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return SN_OK;
+    if ((rc = m.back(similarity, (size_t)n_pairs)) != SN_OK) return rc;
+    return m.finish();
 }
 
 extern "C" int sn_embeddings2simil(sn_ctx *c, int n_cubes, int n_views, const float *embeddings, float *similarity)
@@ -326,20 +326,20 @@ extern "C" int sn_embeddings2simil(sn_ctx *c, int n_cubes, int n_views, const fl
     pairs.reserve(2 * (size_t)P);
     for (int i = 0; i < n_views; ++i)
         for (int j = i + 1; j < n_views; ++j) { pairs.push_back(i); pairs.push_back(j); }      // itertools.combinations order
-    TmpDev t;
     const size_t ne = (size_t)n_cubes * n_views * kEmb, ns = (size_t)n_cubes * P;
-    float *d_e = t.up(c, embeddings, ne), *d_s = t.out<float>(ns);
-    int *d_p = t.up(c, pairs.data(), pairs.size());
-    if (!t.ok) return fail(SN_ERR_NOMEM, "sn_embeddings2simil: device allocation failed");
+    HostMirror m(c, true);
+    const int *d_p = pairs.data();
+    int rc = m.inputs([&](Carve &w) { m.in(w, embeddings, ne); m.in(w, d_p, pairs.size()); });
+    if (rc != SN_OK) return rc;
+    if ((rc = m.outputs([&](Carve &w) { m.out(w, similarity, ns); })) != SN_OK) return rc;
     {
         ProfScope ps(c, "pair_simil_all", 0, (double)ns * (2.0 * kEmb + 1.0) * 4.0);
-        hipLaunchKernelGGL(pair_simil_all_kernel, dim3((unsigned)((ns + 3) / 4)), dim3(256), 0, c->stream, d_e, d_p, d_s, (long long)ns, n_views, P,
+        hipLaunchKernelGGL(pair_simil_all_kernel, dim3((unsigned)((ns + 3) / 4)), dim3(256), 0, c->stream, embeddings, d_p, similarity, (long long)ns, n_views, P,
                            c->ssim_w, c->ssim_b);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipMemcpyAsync(similarity, d_s, sizeof(float) * ns, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return SN_OK;
+    if ((rc = m.back(similarity, ns)) != SN_OK) return rc;
+    return m.finish();
 }
 
 #ifdef SN_DEBUG_HOOKS     // test-only twin library (Makefile target dbg): not in the product .so, not in the ABI header

@@ -1,5 +1,5 @@
 // sn_host_check.cpp — stand-alone check of surfacenet_amd/csrc/sn_host.h, the part of the entry points' host plumbing that needs no device:
-// Carve, table_cap and the packed-list checks. tests/test_host_plumbing.py compiles it with a plain host compiler under the address and
+// Carve, MirrorPlan, table_cap and the packed-list checks. tests/test_host_plumbing.py compiles it with a plain host compiler under the address and
 // undefined-behaviour sanitizers and runs it; it prints SN-HOST-CHECK-OK, or the first failed check and exits 1.
 #include "sn_host.h"
 
@@ -31,7 +31,7 @@ struct Rec {
     }
 };
 
-// the host form of sn_normals with normals and moments (sn_normals.hip nm_layout, with every array staged): n cubes, T voxels, K views per cube of V cameras
+// a workspace of fourteen arrays of the sizes sn_normals handles: n cubes, T voxels, K views per cube of V cameras
 static void normals_layout(Rec &w, size_t n)
 {
     const size_t T = 7 * n, K = 5, V = 9, cap = table_cap(T, 2, 64);
@@ -81,6 +81,157 @@ static void check_carve_empty_get()
     CHECK(cv.off == 257);
     cv.get<int>(3);
     CHECK(cv.off == 512 + 12);
+}
+
+// ---- MirrorPlan: a host buffer as the "device", memcpy as the copy -----------------------------------------------------------------------------
+// What sn_internal.h's HostMirror does with a plan, without a device: one buffer per layout (measured, then placed), the recorded inputs
+// copied in, an output's first `count` elements copied back.
+struct HostExec {
+    MirrorPlan plan;
+    std::vector<unsigned char> buf[2];                           // the inputs' and the outputs' buffer
+    unsigned char *base[2] = {nullptr, nullptr};
+    size_t size[2] = {0, 0};
+    size_t scratch_off = 0, scratch_bytes = 0;                   // a scratch region taken between the arrays of the first layout
+    void carve(int which, const std::function<void(Carve &)> &layout)
+    {
+        Carve measure;
+        const size_t before = plan.recs.size();
+        layout(measure);
+        CHECK(plan.recs.size() == before);                       // the measuring pass records nothing
+        size[which] = measure.off;
+        buf[which].assign(measure.off + 512, 0xee);
+        base[which] = buf[which].data() + (256 - reinterpret_cast<uintptr_t>(buf[which].data()) % 256) % 256;
+        Carve place{base[which]};
+        layout(place);
+        CHECK(place.off == measure.off);                         // the two passes agree
+        if (which == 0)
+            for (const MirrorPlan::Rec &r : plan.recs)
+                if (r.input && r.bytes) memcpy(r.dev, r.host, r.bytes);
+    }
+    template <typename T> void back(const T *dev, size_t count)
+    {
+        if (!plan.on || !dev || !count) return;
+        const MirrorPlan::Rec *r = plan.find(dev);
+        CHECK(r && !r->input && count * sizeof(T) <= r->bytes);
+        memcpy(r->host, dev, count * sizeof(T));
+    }
+    // every recorded region: aligned, inside its buffer, apart from every other and from the scratch
+    void check_regions() const
+    {
+        for (size_t i = 0; i < plan.recs.size(); ++i) {
+            const MirrorPlan::Rec &r = plan.recs[i];
+            const int which = r.input ? 0 : 1;
+            const unsigned char *d = static_cast<const unsigned char *>(r.dev);
+            const size_t room = std::max<size_t>(r.bytes, 1);
+            CHECK(reinterpret_cast<uintptr_t>(d) % 256 == 0);
+            CHECK(d >= base[which] && d + room <= base[which] + size[which]);
+            if (r.input && scratch_bytes) CHECK(d + room <= base[0] + scratch_off || d >= base[0] + scratch_off + scratch_bytes);
+            for (size_t j = 0; j < i; ++j) {
+                const unsigned char *e = static_cast<const unsigned char *>(plan.recs[j].dev);
+                CHECK(d + room <= e || e + std::max<size_t>(plan.recs[j].bytes, 1) <= d);
+            }
+            CHECK(plan.find(r.dev) == &r);
+        }
+    }
+};
+
+template <typename T> static std::vector<T> pattern(size_t count, unsigned seed)
+{
+    std::vector<T> v(count + 1);                                 // (+ 1: data() of an empty array is still a pointer that was "given")
+    unsigned char *b = reinterpret_cast<unsigned char *>(v.data());
+    for (size_t i = 0; i < v.size() * sizeof(T); ++i) b[i] = (unsigned char)(seed * 131u + i * 7u + (i >> 8));
+    return v;
+}
+
+template <typename T> static void check_arrived(const HostExec &x, const T *dev, const std::vector<T> &host, size_t count)
+{
+    const MirrorPlan::Rec *r = x.plan.find(dev);
+    CHECK(r && r->input && r->host == host.data() && r->bytes == count * sizeof(T));
+    CHECK(count == 0 || memcmp(dev, host.data(), count * sizeof(T)) == 0);
+}
+
+// an output of `count` staged elements: the kernels "write" a pattern, back(m) copies the first m, the rest of the caller's array keeps its sentinel
+template <typename T> static void check_back(HostExec &x, T *dev, std::vector<T> &host, size_t count)
+{
+    const std::vector<T> wrote = pattern<T>(count, 77);
+    if (count) memcpy(dev, wrote.data(), count * sizeof(T));
+    for (size_t m : {(size_t)0, count / 2, count}) {
+        memset(host.data(), 0x5c, host.size() * sizeof(T));
+        x.back(dev, m);
+        const unsigned char *h = reinterpret_cast<const unsigned char *>(host.data());
+        CHECK(m == 0 || memcmp(h, wrote.data(), m * sizeof(T)) == 0);
+        for (size_t i = m * sizeof(T); i < host.size() * sizeof(T); ++i) CHECK(h[i] == 0x5c);
+    }
+}
+
+// sn_normals' arrays (sn_normals.hip nm_call): n cubes, T voxels, K views per cube of V cameras; the moments are not asked for (a null output)
+static void check_mirror_normals(size_t n, bool on)
+{
+    const size_t T = 7 * n, K = 5, V = 9;
+    std::vector<int64_t> off = pattern<int64_t>(n + 1, 1);
+    std::vector<uint32_t> cube = pattern<uint32_t>(3 * n, 2);
+    std::vector<uint8_t> ijk = pattern<uint8_t>(3 * T, 3), mask = pattern<uint8_t>(T, 4);
+    std::vector<float> xyz = pattern<float>(3 * n, 5), resol = pattern<float>(n, 6), normals(3 * T + 1);
+    std::vector<int32_t> view = pattern<int32_t>(n * K, 7);
+    std::vector<double> cams = pattern<double>(3 * V, 8);
+    const int64_t *p_off = off.data(); const uint32_t *p_cube = cube.data(); const uint8_t *p_ijk = ijk.data(), *p_mask = mask.data();
+    const float *p_xyz = xyz.data(), *p_resol = resol.data(); const int32_t *p_view = view.data(); const double *p_cams = cams.data();
+    float *p_normals = normals.data(); int32_t *p_moments = nullptr;
+    HostExec x;
+    x.plan.on = on;
+    float *scratch = nullptr;
+    x.carve(0, [&](Carve &w) {
+        x.plan.in(w, p_off, n + 1); x.plan.in(w, p_cube, 3 * n); x.plan.in(w, p_ijk, 3 * T); x.plan.in(w, p_mask, T);
+        scratch = w.get<float>(n);                               // scratch between the arrays, as the weight entries take their logits
+        if (w.base) { x.scratch_off = (size_t)(reinterpret_cast<unsigned char *>(scratch) - w.base); x.scratch_bytes = std::max<size_t>(n, 1) * sizeof(float); }
+        x.plan.in(w, p_xyz, 3 * n); x.plan.in(w, p_resol, n); x.plan.in(w, p_view, n * K); x.plan.in(w, p_cams, 3 * V);
+    });
+    x.carve(1, [&](Carve &w) { x.plan.out(w, p_normals, 3 * T); x.plan.out(w, p_moments, 10 * T); });
+    CHECK(p_moments == nullptr);                                 // a null array takes no region and stays null
+    if (!on) {                                                   // a device form: no pointer changes, no region is taken
+        CHECK(x.plan.recs.empty() && p_off == off.data() && p_cams == cams.data() && p_normals == normals.data());
+        CHECK(x.size[0] == std::max<size_t>(n, 1) * sizeof(float) && x.size[1] == 0);      // (the scratch alone)
+        x.back(p_normals, 3 * T);
+        return;
+    }
+    CHECK(x.plan.recs.size() == 9);
+    x.check_regions();
+    check_arrived(x, p_off, off, n + 1); check_arrived(x, p_cube, cube, 3 * n); check_arrived(x, p_ijk, ijk, 3 * T); check_arrived(x, p_mask, mask, T);
+    check_arrived(x, p_xyz, xyz, 3 * n); check_arrived(x, p_resol, resol, n); check_arrived(x, p_view, view, n * K); check_arrived(x, p_cams, cams, 3 * V);
+    CHECK(x.plan.find(scratch) == nullptr && x.plan.find(normals.data()) == nullptr);
+    check_back(x, p_normals, normals, 3 * T);
+}
+
+// sn_mesh's arrays (sn_mesh.hip ms_call / ms_run): the outputs are staged at the counts the kernels found, nv vertices and nq quads
+static void check_mirror_mesh(size_t n, bool on)
+{
+    const size_t T = 7 * n, nv = 3 * n, nq = 2 * n;
+    std::vector<int64_t> off = pattern<int64_t>(n + 1, 11), vsrc(nv + 1);
+    std::vector<uint32_t> cube = pattern<uint32_t>(3 * n, 12);
+    std::vector<uint8_t> ijk = pattern<uint8_t>(3 * T, 13), mask = pattern<uint8_t>(T, 14);
+    std::vector<float> nrm = pattern<float>(3 * T, 15), vmm(3 * nv + 1);
+    std::vector<double> vlat(3 * nv + 1);
+    std::vector<int32_t> quads(4 * nq + 1);
+    const int64_t *p_off = off.data(); const uint32_t *p_cube = cube.data(); const uint8_t *p_ijk = ijk.data(), *p_mask = mask.data();
+    const float *p_nrm = nrm.data();
+    float *p_vmm = vmm.data(); double *p_vlat = vlat.data(); int32_t *p_vcell = nullptr, *p_quads = quads.data(); int64_t *p_vsrc = vsrc.data();
+    HostExec x;
+    x.plan.on = on;
+    x.carve(0, [&](Carve &w) { x.plan.in(w, p_off, n + 1); x.plan.in(w, p_cube, 3 * n); x.plan.in(w, p_ijk, 3 * T); x.plan.in(w, p_mask, T); x.plan.in(w, p_nrm, 3 * T); });
+    x.carve(1, [&](Carve &w) {
+        x.plan.out(w, p_vmm, 3 * nv); x.plan.out(w, p_vlat, 3 * nv); x.plan.out(w, p_vcell, 3 * nv); x.plan.out(w, p_vsrc, nv); x.plan.out(w, p_quads, 4 * nq);
+    });
+    CHECK(p_vcell == nullptr);
+    if (!on) {
+        CHECK(x.plan.recs.empty() && x.size[0] == 0 && x.size[1] == 0);
+        CHECK(p_off == off.data() && p_nrm == nrm.data() && p_vmm == vmm.data() && p_quads == quads.data());
+        return;
+    }
+    CHECK(x.plan.recs.size() == 9);
+    x.check_regions();
+    check_arrived(x, p_off, off, n + 1); check_arrived(x, p_cube, cube, 3 * n); check_arrived(x, p_ijk, ijk, 3 * T); check_arrived(x, p_mask, mask, T);
+    check_arrived(x, p_nrm, nrm, 3 * T);
+    check_back(x, p_vmm, vmm, 3 * nv); check_back(x, p_vlat, vlat, 3 * nv); check_back(x, p_vsrc, vsrc, nv); check_back(x, p_quads, quads, 4 * nq);
 }
 
 // ---- table_cap: the five loops it replaced, as they stood -------------------------------------------------------------------------------------
@@ -137,6 +288,10 @@ int main()
     for (size_t n : {(size_t)0, (size_t)1, (size_t)1000}) {
         check_carve(normals_layout, n);
         check_carve(grid_layout, n);
+        for (bool on : {true, false}) {
+            check_mirror_normals(n, on);
+            check_mirror_mesh(n, on);
+        }
     }
     check_carve_empty_get();
     check_table_cap();

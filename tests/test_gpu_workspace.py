@@ -1,15 +1,24 @@
 """GPU (-m gpu): the context's device workspaces (sn_internal.h DevBuf / dev_reserve) through the entries that carve them. One context, and
 per entry three calls, small -> large -> small: the first allocates the workspace, the second has to grow it, the third runs in a buffer
 larger than it needs. Every result equals the entry's restatement (bit for bit, or within the tolerance the entry's own test module uses),
-and the third equals the first bit for bit. The packed-list entries also take a call without cubes and one without voxels in between."""
+and the third equals the first bit for bit. The packed-list entries also take a call without cubes and one without voxels in between. The
+host forms share two more buffers, the host mirror's (sn_internal.h HostMirror): the geometry stages and the post-pass entries run in turn
+on one scene per size, so that each call finds those buffers as another entry left them."""
 import os
 
 import numpy as np
 import pytest
 
+import components_ref
 import golden_util
+import gtcubes_ref
+import mesh_ref
+import meshsample_ref
+import meshsimplify_ref
 import normals_ref
 import pointeval_ref
+import postpass_ref
+import ptcubes_ref
 from oracle import post_oracle, simil_oracle
 
 pytestmark = pytest.mark.gpu
@@ -79,6 +88,108 @@ def test_normals_and_unique_share_a_growing_workspace(ctx):
     third = _normals_and_unique(ctx, small)
     assert _same(first, third)
     assert not first[2].all() and first[2].any()               # the overlap: some cells are listed by both cubes
+
+
+# ---- the host mirror: every host form stages in the same two buffers -----------------------------------------------------------------------------
+ORIGIN, RESOL = (-20.0, -20.0, -20.0), 0.4     # tests/test_gpu_mesh.py
+
+
+def _one_ulp(got, want):
+    """tests/test_gpu_mesh.py's bound on verts_mm: within one float32 ulp of the restatement's value."""
+    ulp = np.spacing(np.maximum(np.abs(got), np.abs(want))).astype(np.float64)
+    return got.dtype == np.float32 and got.shape == want.shape and bool((np.abs(got.astype(np.float64) - want.astype(np.float64)) <= ulp).all())
+
+
+def _geometry(ctx, s):
+    """normals, unique_voxels, components, mesh, mesh_sample and mesh_simplify in turn on one scene, each against its restatement as its own
+    test module compares them, and against its device=True form bit for bit."""
+    nrm, mom, keep = _normals_and_unique(ctx, s)
+    args = components_ref.scene_args(s)
+    comp = ctx.components(*args, connectivity=6, min_cells=2)
+    components_ref.compare(comp, components_ref.components_ref(*args, connectivity=6, min_cells=2))
+    assert _same(comp[:3], ctx.components(*args, connectivity=6, min_cells=2, device=True)[:3])
+    # the mesh of the normals just computed (tests/test_gpu_mesh.py _compare)
+    m = ctx.mesh(*args, nrm, origin=ORIGIN, resol=RESOL)
+    want = mesh_ref.mesh_ref(*args, nrm, origin=ORIGIN, resol=RESOL)
+    assert want["quads"].shape[0] > 0
+    for k in ("vert_cell", "quads", "vert_src"):
+        assert m[k].dtype == want[k].dtype and np.array_equal(m[k], want[k]), k
+    assert np.abs(m["verts_lattice"] - want["vert_lattice"]).max() <= 1e-9 and _one_ulp(m["verts_mm"], want["verts_mm"])
+    names = sorted(m)
+    T = s["ijk"].shape[0]
+    for kw in (dict(device=True), dict(cap=(4 * T + 1000, 4 * T + 1000)), dict(cap=(1, 1))):      # cap=None is (2 T + 64, 2 T + 64); (1, 1): the retry
+        other = ctx.mesh(*args, nrm, origin=ORIGIN, resol=RESOL, **kw)
+        assert _same([m[k] for k in names], [other[k] for k in names]), kw
+    # samples of that mesh, and the mesh made smaller (tests/test_gpu_meshsample.py _same, tests/test_gpu_meshsimplify.py _compare)
+    tris = meshsimplify_ref.triangulate(m["quads"]).astype(np.int32)
+    smp = ctx.mesh_sample(m["verts_lattice"], tris, 0.4)
+    assert _same(smp, meshsample_ref.sample(m["verts_lattice"], tris, 0.4)) and smp[0].shape[0] > tris.shape[0]
+    assert _same(smp, ctx.mesh_sample(m["verts_lattice"], tris, 0.4, device=True))
+    sim = ctx.mesh_simplify(m["verts_lattice"], tris, 2, origin=ORIGIN, resol=RESOL)
+    want = meshsimplify_ref.simplify(m["verts_lattice"], tris, 2, origin=ORIGIN, resol=RESOL)
+    for k in ("vert_rep", "vert_count", "faces", "face_src", "vert_cluster"):
+        assert sim[k].dtype == np.int32 and np.array_equal(sim[k], want[k]), k
+    assert np.array_equal(sim["verts_lattice"], want["vert_lattice"]) and _one_ulp(sim["verts_mm"], want["vertices"])
+    assert 0 < sim["faces"].shape[0] < tris.shape[0]
+    other = ctx.mesh_simplify(m["verts_lattice"], tris, 2, origin=ORIGIN, resol=RESOL, device=True)
+    assert _same([sim[k] for k in sorted(sim)], [other[k] for k in sorted(sim)])
+    return (nrm, mom, keep) + tuple(comp[:3]) + tuple(m[k] for k in names) + tuple(smp) + tuple(sim[k] for k in sorted(sim))
+
+
+def test_geometry_stages_share_the_host_mirror(ctx):
+    small, large = _stepped_sheet(2, 1), _stepped_sheet(8, 5)
+    first = _geometry(ctx, small)
+    _empty_packed_calls(ctx)
+    _geometry(ctx, large)
+    _empty_packed_calls(ctx)
+    assert _same(first, _geometry(ctx, small))
+
+
+def _postpass(ctx, s):
+    """denoise, adapthresh, ptcubes and gt_cubes / weighted_accuracy in turn on one scene: bit for bit their restatements (tests/test_gpu_postpass.py,
+    test_gpu_ptcubes.py, test_gpu_gtcubes.py)."""
+    off, ijk, cube = s["offsets"], s["ijk"], s["cube_ijk"]
+    n, T = len(cube), ijk.shape[0]
+    rs = np.random.RandomState(T)
+    split = lambda flat: postpass_ref.split(flat, off)
+    pred = (0.35 + 0.6 * rs.rand(T)).astype(np.float16)
+    votes = rs.randint(2, 7, T).astype(np.uint8)
+    mask = rs.rand(T) < 0.8
+    den = ctx.denoise(off, ijk, cube, mask, 8, 8)
+    assert np.array_equal(den, np.concatenate(postpass_ref.denoise_ref(cube, split(ijk), split(mask), 8, 8))) and den.any()
+    at = ctx.adapthresh(off, ijk, pred, votes, cube, 8, 2, 0.5, 0.9, 4, 2, 8)
+    want = postpass_ref.adapthresh_ref(split(pred), split(ijk), split(votes), cube, 2, 8, 0.5, 0.9, 4, 2, 8)
+    assert np.array_equal(at["init_denoised"], np.concatenate(want["init_denoised"]))
+    assert at["thresh"].dtype == np.float64 and np.array_equal(at["thresh"], want["thresh"]) and np.array_equal(at["choice"], want["choice"])
+    for k in range(2):
+        assert np.array_equal(at["masks"][k], np.concatenate(want["masks"][k])) and np.array_equal(at["denoised"][k], np.concatenate(want["denoised"][k]))
+    # the cubes around the voxels' points, as scene.quantizePts2Cubes asks for them
+    pts = normals_ref.voxel_points(off, ijk, s["cube_xyz"], s["cube_resol"]).astype(np.float32)
+    kw = dict(resol=np.float32(0.4), cube_D=8, cube_Dcenter=6, cube_overlapping_ratio=0.5)
+    from surfacenet_amd import scene
+    p = scene._plan(pts.dtype, BB=None, **kw)
+    cells = ctx.ptcubes(pts, p["stride_q"], p["stride_xyz"], p["half"], p["compute_f64"])
+    cubes = ptcubes_ref.quantizePts2Cubes(pts, **kw)[0]
+    assert np.array_equal(cells[0], cubes["ijk"]) and np.array_equal(cells[1], cubes["xyz"]) and len(cubes) > 1
+    assert _same(cells, ctx.ptcubes(pts, p["stride_q"], p["stride_xyz"], p["half"], p["compute_f64"], cap=1))      # the retry
+    # the occupancy of those cubes by those points, and a prediction's counts against it
+    assert ctx.gt_bind(pts, 0.8) == T
+    Y = ctx.gt_cubes(cubes)
+    assert np.array_equal(Y, gtcubes_ref.gt_cubes(pts, cubes["xyz"], cubes["resol"], S)) and Y.any()
+    guess = np.clip(0.6 * Y + 0.55 * rs.rand(*Y.shape), 0, 1).astype(np.float32)
+    counts = ctx.weighted_accuracy_counts(guess, Y)
+    assert np.array_equal(counts, gtcubes_ref.accuracy_counts(guess, Y))
+    return den, at["init_denoised"], at["thresh"], at["masks"], at["denoised"], at["choice"], cells[0], cells[1], Y, counts
+
+
+def test_postpass_entries_share_the_host_mirror(ctx):
+    small, large = _stepped_sheet(2, 1), _stepped_sheet(8, 5)
+    first = _postpass(ctx, small)
+    for e in (normals_ref.hand_scene(np.zeros((0, 3)), [], stride_vox=4), normals_ref.hand_scene([[0, 0, 0], [1, 0, 0]], [np.zeros((0, 3), np.uint8)] * 2, 4)):
+        assert ctx.denoise(e["offsets"], e["ijk"], e["cube_ijk"], e["mask"], 8, 8).shape == (0,)
+        assert ctx.adapthresh(e["offsets"], e["ijk"], np.zeros(0, np.float16), None, e["cube_ijk"], 8, 2, 0.5, 0.9, 0, 2, 8)["thresh"].shape == (2, len(e["cube_ijk"]))
+    _postpass(ctx, large)
+    assert _same(first, _postpass(ctx, small))
 
 
 # ---- point-cloud evaluation --------------------------------------------------------------------------------------------------------------------

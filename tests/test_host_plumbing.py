@@ -1,4 +1,4 @@
-"""CPU: csrc/sn_host.h — the entry points' host plumbing that needs no device (Carve, table_cap, the packed-list checks) — csrc/sn_pack.h —
+"""CPU: csrc/sn_host.h — the entry points' host plumbing that needs no device (Carve, the host mirror's plan, table_cap, the packed-list checks) — csrc/sn_pack.h —
 the host half of weight packing — and csrc/lattice.h — the keys, codes and table predicates of the lattice stages — each compiled alone by a plain host C++17 compiler, with no hip/ include on its path, under the address and
 undefined-behaviour sanitizers, and run as a child process (tests/host/sn_host_check.cpp, sn_pack_check.cpp and lattice_check.cpp hold the checks). Nothing is
 loaded into this interpreter."""
