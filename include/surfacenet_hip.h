@@ -31,7 +31,8 @@ extern "C" {
  * sn_weighted_accuracy_dev - the ground-truth mode; sn_mesh, sn_mesh_dev and sn_mesh_cfg - the surface-nets mesh of the oriented cloud;
  * sn_mesh_sample and sn_mesh_sample_dev - surface samples of a triangle mesh; sn_components, sn_components_dev and sn_components_cfg - connected
  * components of the output cloud; sn_mesh_simplify, sn_mesh_simplify_dev and sn_mesh_simplify_cfg - a triangle mesh made smaller by vertex
- * clustering. */
+ * clustering; sn_mesh_smooth, sn_mesh_smooth_dev and sn_mesh_smooth_cfg - Taubin smoothing of a triangle or quad mesh in fixed point, with
+ * the mesh's edge and boundary counts. */
 
 /* The library is built with -fvisibility=hidden: the functions below are its WHOLE dynamic symbol table
  * (tests/test_abi.py compares `nm -D` with this header). */
@@ -387,6 +388,42 @@ SN_API int sn_mesh_simplify_dev(sn_ctx *ctx, const sn_mesh_simplify_cfg *cfg, in
                                 const int32_t *faces_dev, long long cap_verts, long long cap_faces, float *verts_mm_dev,
                                 double *verts_lattice_dev, int32_t *vert_rep_dev, int32_t *vert_count_dev, int32_t *faces_out_dev,
                                 int32_t *face_src_dev, int32_t *vert_cluster_dev, long long *n_out_verts, long long *n_out_faces);
+
+/* ---- a mesh made smooth: Taubin lambda|mu smoothing with the uniform umbrella operator, in fixed point ----------------
+ * verts (n_verts,3) float64 in lattice cells (sn_mesh's or sn_mesh_simplify's verts_lattice), faces (n_faces,nv) int32 with nv = 3 or 4; a quad's
+ * four sides are its edges, no diagonal is invented. A vertex is referenced iff a face names it; an unreferenced vertex is not looked at (it may
+ * be NaN). Per component of a referenced vertex q = int64(rint(v * 65536)) (requires -4 <= v < 2^21 - 8); QMIN = -4 * 65536, QMAX =
+ * (2^21 - 8) * 65536 - 1. Every face gives the sides (f[i], f[(i + 1) % nv]); a side with equal ends is ignored; an edge is an unordered pair
+ * {a, b}, its count the number of sides on it in either direction; E edges; a boundary edge has count 1, a non-manifold one count > 2. Per
+ * vertex: degree = its edges, bdegree = its boundary edges, a boundary vertex has bdegree > 0. The neighbours N(i) of a vertex: boundary 2
+ * (free) all edge neighbours; 0 (fixed) the same, but a boundary vertex does not move; 1 (curve) a boundary vertex only its neighbours across
+ * boundary edges (d = bdegree), every other vertex all of them: the rim of an open sheet smooths as a curve. A vertex with d = 0 does not move.
+ * One pass with factor w is Jacobi - every vertex reads the positions of before the pass - and per axis, S = the sum of q over N(i):
+ *   mean = floor((2 S + d) / (2 d)),   q' = min(max(q + ((w * (mean - q) + 32768) >> 16), QMIN), QMAX)      (int64, arithmetic shift).
+ * One iteration is a pass with lam_q16, then one with mu_q16 unless that is 0 (plain Laplacian smoothing). Indices do not change: faces,
+ * colours and normals carry over. Outputs, each optional (NULL) except counts:
+ *   verts_lattice (n_verts,3) float64 = float64(q) / 65536 of a referenced vertex, the input's bits of an unreferenced one;
+ *   verts_mm (n_verts,3) float32 = float32(origin + resol * verts_lattice) in float64 without contraction; vert_degree (n_verts) int32;
+ *   vert_flags (n_verts) uint8: bit 0 referenced, bit 1 boundary vertex, bit 2 end of a non-manifold edge;
+ *   counts[4]: E, boundary edges, non-manifold edges, referenced vertices.
+ * iterations = 0 quantises and reports the topology. SN_ERR_ARG, nothing written but counts (zeros): a face index outside [0, n_verts) or a
+ * referenced coordinate outside the range (or not a number), the text naming the first offending face; iterations outside 0 .. 1000, a factor
+ * outside [-65536, 65536], boundary not 0 / 1 / 2, nv not 3 or 4, resol (finite, > 0), origin (finite), n_verts or n_faces > 2^28; a vertex
+ * of 2^24 or more edges (named; it keeps 2 S + d inside int64); 2^30 or more edges. n_faces = 0: nothing is referenced, verts_lattice is the
+ * input, the counts are 0. All sums are integers: the result equals the numpy restatement tests/meshsmooth_ref.py bit for bit, on every run.
+ * The workspace belongs to the context (grown on demand); both forms return when the work is done. */
+typedef struct sn_mesh_smooth_cfg {
+    int iterations;            /* 0 .. 1000 */
+    int lam_q16, mu_q16;       /* the two factors times 65536, each in [-65536, 65536]; mu_q16 = 0: no second pass */
+    int boundary;              /* 0: boundary vertices fixed; 1: they smooth along the boundary curve; 2: free */
+    double origin[3];          /* mm position of lattice point (0,0,0) */
+    double resol;              /* mm per cell */
+} sn_mesh_smooth_cfg;
+SN_API int sn_mesh_smooth(sn_ctx *ctx, const sn_mesh_smooth_cfg *cfg, int n_verts, const double *verts, int n_faces, int nv, const int32_t *faces,
+                          float *verts_mm, double *verts_lattice, int32_t *vert_degree, unsigned char *vert_flags, long long *counts);
+SN_API int sn_mesh_smooth_dev(sn_ctx *ctx, const sn_mesh_smooth_cfg *cfg, int n_verts, const double *verts_dev, int n_faces, int nv,
+                              const int32_t *faces_dev, float *verts_mm_dev, double *verts_lattice_dev, int32_t *vert_degree_dev,
+                              unsigned char *vert_flags_dev, long long *counts);
 
 /* ---- DTU point-cloud evaluation (experiments/DTU/eval_ply.m -> PointCompareMain of the DTU kit) ----------------------
  * Points are (n,3) float64, row-major, finite. d^2 = (dx*dx + dy*dy) + dz*dz in float64 without contraction: the results are those of the numpy

@@ -653,6 +653,35 @@ class Context(object):
         with self._on_device((v, f)) as src:
             return self._sized_outputs(run, spec, rows, caps, src)
 
+    def mesh_smooth(self, verts, faces, iterations=10, lam_q16=32768, mu_q16=-34734, boundary=1, origin=(0.0, 0.0, 0.0), resol=1.0, device=False):
+        """Taubin smoothing of a mesh in fixed point (sn_mesh_smooth): verts (V,3) float64 in lattice cells, faces (F,3)
+        or (F,4) int32, iterations 0..1000, the two factors times 65536, boundary 0 (fixed) / 1 (curve) / 2 (free), origin (3,) / resol as
+        Context.mesh takes them. Returns a dict: verts_mm (V,3) float32, verts_lattice (V,3) float64, vert_degree (V,) int32, vert_flags (V,)
+        uint8 (1 referenced, 2 boundary vertex, 4 end of a non-manifold edge), counts (4,) int64 = edges, boundary edges, non-manifold edges,
+        referenced vertices. device=True stages the mesh in device memory here and runs sn_mesh_smooth_dev on it: the same result."""
+        v = np.ascontiguousarray(verts, dtype=np.float64).reshape(-1, 3)
+        f = np.ascontiguousarray(faces, dtype=np.int32)
+        if f.ndim != 2:
+            raise ValueError("faces must be (F,3) or (F,4), not %r" % (f.shape,))
+        V, (F, nv) = v.shape[0], f.shape
+        cfg = _lib.MeshSmoothCfg(int(iterations), int(lam_q16), int(mu_q16), int(boundary))
+        cfg.origin[:] = [float(x) for x in np.asarray(origin, dtype=np.float64).reshape(3)]
+        cfg.resol = float(resol)
+        out = dict(verts_mm=np.empty((V, 3), np.float32), verts_lattice=np.empty((V, 3), np.float64), vert_degree=np.empty((V,), np.int32),
+                   vert_flags=np.empty((V,), np.uint8))
+        counts = (ctypes.c_longlong * 4)()
+        if not device:
+            _lib.check(self._lib.sn_mesh_smooth(self._h, ctypes.byref(cfg), V, _lib.ptr(v), F, nv, _lib.ptr(f), *[_lib.ptr(a) for a in out.values()],
+                                                counts))
+        else:
+            with self._on_device((v, f)) as src, self._on_device(out.values(), upload=False) as dst:
+                _lib.check(self._lib.sn_mesh_smooth_dev(self._h, ctypes.byref(cfg), V, src[0], F, nv, src[1], *dst, counts))
+                for a, b in zip(out.values(), dst):
+                    if a.nbytes:
+                        self.d2h(a, b)
+        out["counts"] = np.asarray(list(counts), np.int64)
+        return out
+
     @staticmethod
     def _points(xyz):
         return np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))

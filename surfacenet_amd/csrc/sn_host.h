@@ -1,8 +1,9 @@
 // sn_host.h — the host plumbing of the C entry points that needs no device: the error text, sizes of hash tables, bump allocation from one
 // buffer (Carve), the plan of a call's host mirror (MirrorPlan: which host array got which region of that buffer), and the argument checks of
-// the packed sparse voxel lists. Plain C++17, no hip/ include: tests/host/sn_host_check.cpp compiles it alone.
+// the packed sparse voxel lists and of the mesh smoother. Plain C++17, no hip/ include: tests/host/sn_host_check.cpp compiles it alone.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstddef>
 #include <cstdint>
@@ -112,5 +113,23 @@ static inline int pl_check_host_ijk(long long total, const unsigned char *ijk, i
 {
     for (long long v = 0; v < 3 * total; ++v)
         if (ijk[v] >= Dc) return fail(SN_ERR_ARG, "voxel %lld: ijk component %d >= Dc = %d", v / 3, (int)ijk[v], Dc);
+    return SN_OK;
+}
+
+// ---- sn_mesh_smooth / sn_mesh_smooth_dev: what of their arguments can be judged without a device (rule 10) ---------------
+static inline int msm_check_args(const sn_mesh_smooth_cfg *cfg, int n_verts, int n_faces, int nv)
+{
+    if (!cfg) return fail(SN_ERR_ARG, "null cfg");
+    if (n_verts < 0 || n_faces < 0) return fail(SN_ERR_ARG, "n_verts and n_faces must be >= 0");
+    if (n_verts > (1 << 28) || n_faces > (1 << 28))
+        return fail(SN_ERR_ARG, "n_verts = %d, n_faces = %d: at most 2^28 of either", n_verts, n_faces);
+    if (nv != 3 && nv != 4) return fail(SN_ERR_ARG, "nv = %d: faces are triangles (3) or quads (4)", nv);
+    if (cfg->iterations < 0 || cfg->iterations > 1000) return fail(SN_ERR_ARG, "iterations = %d: 0 .. 1000", cfg->iterations);
+    if (cfg->lam_q16 < -65536 || cfg->lam_q16 > 65536) return fail(SN_ERR_ARG, "lam_q16 = %d: -65536 .. 65536", cfg->lam_q16);
+    if (cfg->mu_q16 < -65536 || cfg->mu_q16 > 65536) return fail(SN_ERR_ARG, "mu_q16 = %d: -65536 .. 65536", cfg->mu_q16);
+    if (cfg->boundary < 0 || cfg->boundary > 2) return fail(SN_ERR_ARG, "boundary = %d: 0 (fixed), 1 (curve) or 2 (free)", cfg->boundary);
+    if (!std::isfinite(cfg->resol) || !(cfg->resol > 0)) return fail(SN_ERR_ARG, "resol = %g must be finite and > 0", cfg->resol);
+    for (int d = 0; d < 3; ++d)
+        if (!std::isfinite(cfg->origin[d])) return fail(SN_ERR_ARG, "origin[%d] = %g is not finite", d, cfg->origin[d]);
     return SN_OK;
 }

@@ -1,0 +1,169 @@
+// sn_meshsmooth.hip — C ABI of the mesh smoother (meshsmooth.h). The device form works on the caller's device arrays; the
+// host form is the same computation on the host mirror's device copies of its arrays (sn_internal.h HostMirror). The iteration loop is the
+// host's: plain launches on the context's stream, at most 2 * iterations of the pass kernel.
+#include "sn_internal.h"
+#include "meshsmooth.h"
+#include "scan.h"
+
+namespace {
+
+constexpr long long MSM_MAX_EDGES = 1ll << 30;         // 2 E row entries are addressed by the scan's int
+
+// the caller's outputs: device arrays in the device form, host arrays in the host form
+struct MsmOut { float *verts_mm; double *verts_lattice; int32_t *vert_degree; unsigned char *vert_flags; };
+
+int msm_check(sn_ctx *c, const sn_mesh_smooth_cfg *cfg, int n_verts, int n_faces, int nv, long long *counts)
+{
+    if (!c) return fail(SN_ERR_ARG, "null context");
+    if (!counts) return fail(SN_ERR_ARG, "counts is required");
+    for (int k = 0; k < 4; ++k) counts[k] = 0;
+    return msm_check_args(cfg, n_verts, n_faces, nv);
+}
+
+// What both forms do once their arguments are checked, V > 0 or F > 0. REC: int64 words per position record (meshsmooth.h).
+template <int REC>
+int msm_run(sn_ctx *c, bool host, const sn_mesh_smooth_cfg *cfg, int V, const double *verts, int F, int nv, const int32_t *faces, MsmOut d,
+            long long *counts)
+{
+    HostMirror m(c, host);
+    int rc = m.inputs([&](Carve &w) { m.in(w, verts, 3 * (size_t)V); m.in(w, faces, (size_t)nv * (size_t)F); });
+    if (rc != SN_OK) return rc;
+    MsmArgs a;
+    memset(&a, 0, sizeof a);
+    a.verts = verts; a.faces = faces; a.V = V; a.F = F; a.nv = nv; a.boundary = cfg->boundary; a.resol = cfg->resol;
+    for (int k = 0; k < 3; ++k) a.origin[k] = cfg->origin[k];
+    const size_t nsides = (size_t)nv * (size_t)F;
+    const size_t cap = table_cap((unsigned long long)nsides, 2, 64);      // at most 2^31 slots: the mask fits an unsigned
+    a.mask = (unsigned)(cap - 1);
+    int *sums = nullptr;
+    auto layout = [&](Carve &w) {
+        a.st = w.get<MsmStat>(1);
+        a.vfl = w.get<unsigned>((size_t)V);
+        a.deg = w.get<int>((size_t)V + 1);
+        a.row = w.get<int>((size_t)V + 1);
+        a.cursor = w.get<int>((size_t)V);
+        sums = w.get<int>(scan_sums((size_t)V + 1));
+        a.tab = w.get<unsigned long long>(2 * cap);
+        a.sides = w.get<unsigned>(cap);
+        a.nbr = w.get<unsigned>(2 * nsides);
+        a.pos[0] = w.get<long long>((size_t)REC * (size_t)V);
+        a.pos[1] = w.get<long long>((size_t)REC * (size_t)V);
+    };
+    if ((rc = dev_carve(c, c->msm_ws, layout, 256)) != SN_OK) return rc;
+    const unsigned vb = blocks(V, MSM_NT), fb = blocks(F, MSM_NT), sb = blocks((long long)cap, MSM_NT);
+    const unsigned loop_blocks = (unsigned)std::max(c->num_cus, 1) * 8u;      // the grid-stride kernels: eight workgroups per CU at most
+    HIPCHK(hipMemsetAsync(a.st, 0, sizeof(MsmStat), c->stream));
+    HIPCHK(hipMemsetAsync(a.st, 0xff, 2 * sizeof(unsigned long long), c->stream));      // first_bad, bad_vertex = MSM_NONE
+    {
+        ProfScope ps(c, "msm_mark", 0, (double)F * nv * 8.0 + (double)V * (28.0 + 8.0 * REC));
+        HIPCHK(hipMemsetAsync(a.vfl, 0, sizeof(unsigned) * std::max<size_t>((size_t)V, 1), c->stream));
+        if (F > 0) {
+            hipLaunchKernelGGL(msm_mark_kernel, dim3(fb), dim3(MSM_NT), 0, c->stream, a);
+            HIPCHK(hipGetLastError());
+        }
+        if (V > 0) {
+            hipLaunchKernelGGL(msm_quantise_kernel<REC>, dim3(std::min(vb, loop_blocks)), dim3(MSM_NT), 0, c->stream, a);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    {
+        ProfScope ps(c, "msm_edges", 0, (double)F * nv * 28.0 + (double)cap * 20.0);
+        HIPCHK(hipMemsetAsync(a.tab, 0, sizeof(unsigned long long) * 2 * cap, c->stream));
+        HIPCHK(hipMemsetAsync(a.sides, 0, sizeof(unsigned) * cap, c->stream));
+        if (F > 0) {
+            hipLaunchKernelGGL(msm_edges_kernel, dim3(fb), dim3(MSM_NT), 0, c->stream, a);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    {
+        ProfScope ps(c, "msm_degree", 0, (double)cap * 12.0 + (double)V * 12.0);
+        HIPCHK(hipMemsetAsync(a.deg, 0, sizeof(int) * ((size_t)V + 1), c->stream));
+        hipLaunchKernelGGL(msm_degree_kernel, dim3(std::min(sb, loop_blocks)), dim3(MSM_NT), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
+    }
+    // the one read before any output is touched: the first bad face, the degree limit, the counts
+    MsmStat st;
+    HIPCHK(hipMemcpyAsync(&st, a.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (st.first_bad != MSM_NONE) {
+        const long long f = (long long)(st.first_bad >> 3);
+        if ((st.first_bad & 7) == MSM_ERR_INDEX) return fail(SN_ERR_ARG, "face %lld names a vertex outside [0, %d)", f, V);
+        return fail(SN_ERR_ARG, "face %lld: a coordinate of one of its vertices is outside [-4, 2^21 - 8) lattice cells (or not a number)", f);
+    }
+    if (st.bad_vertex != MSM_NONE)
+        return fail(SN_ERR_ARG, "vertex %lld has 2^24 or more edges: at most 2^24 - 1", (long long)st.bad_vertex);
+    if ((long long)st.counts[0] >= MSM_MAX_EDGES) return fail(SN_ERR_ARG, "%lld edges: at most 2^30 - 1", (long long)st.counts[0]);
+    rc = m.outputs([&](Carve &w) {
+        m.out(w, d.verts_mm, 3 * (size_t)V); m.out(w, d.verts_lattice, 3 * (size_t)V); m.out(w, d.vert_degree, (size_t)V);
+        m.out(w, d.vert_flags, (size_t)V);
+    });
+    if (rc != SN_OK) return rc;
+    a.verts_mm = d.verts_mm; a.verts_lattice = d.verts_lattice; a.vert_degree = d.vert_degree; a.vert_flags = d.vert_flags;
+    const long long E = (long long)st.counts[0];
+    int cur = 0;
+    if (cfg->iterations > 0 && V > 0 && E > 0) {
+        {
+            ProfScope ps(c, "msm_rows", 0, (double)cap * 12.0 + (double)V * 16.0 + (double)E * 24.0);
+            if ((rc = scan_exclusive(c, a.deg, a.row, V + 1, sums)) != SN_OK) return rc;      // row[V] = 2 E
+            HIPCHK(hipMemsetAsync(a.cursor, 0, sizeof(int) * (size_t)V, c->stream));
+            hipLaunchKernelGGL(msm_rows_kernel, dim3(sb), dim3(MSM_NT), 0, c->stream, a);
+            HIPCHK(hipGetLastError());
+        }
+        // per vertex: its record, one record and one row word per neighbour, two row bounds, the flags, one write
+        const double pass_bytes = (double)st.counts[3] * (16.0 * REC + 12.0) + 2.0 * (double)E * (8.0 * REC + 4.0);
+        for (int it = 0; it < cfg->iterations; ++it)
+            for (int half = 0; half < 2; ++half) {
+                const int w = half ? cfg->mu_q16 : cfg->lam_q16;
+                if (half && w == 0) continue;
+                ProfScope ps(c, "msm_pass", 0, pass_bytes);
+                hipLaunchKernelGGL(msm_pass_kernel<REC>, dim3(vb), dim3(MSM_NT), 0, c->stream, a, (const long long *)a.pos[cur], a.pos[cur ^ 1], w);
+                HIPCHK(hipGetLastError());
+                cur ^= 1;
+            }
+    }
+    if (V > 0 && (a.verts_mm || a.verts_lattice || a.vert_degree || a.vert_flags)) {
+        ProfScope ps(c, "msm_emit", 0, (double)V * (8.0 * REC + 24.0 + 36.0 + 9.0));
+        hipLaunchKernelGGL(msm_emit_kernel<REC>, dim3(vb), dim3(MSM_NT), 0, c->stream, a, (const long long *)a.pos[cur]);
+        HIPCHK(hipGetLastError());
+    }
+    if ((rc = m.back(d.verts_mm, 3 * (size_t)V)) != SN_OK || (rc = m.back(d.verts_lattice, 3 * (size_t)V)) != SN_OK ||
+        (rc = m.back(d.vert_degree, (size_t)V)) != SN_OK || (rc = m.back(d.vert_flags, (size_t)V)) != SN_OK)
+        return rc;
+    if ((rc = m.finish()) != SN_OK) return rc;
+    for (int k = 0; k < 4; ++k) counts[k] = (long long)st.counts[k];
+    return SN_OK;
+}
+
+// The record the pass kernel runs on: 24 bytes, the faster of the two on an MI355X (tools/bench_meshsmooth.py, profiles/meshsmooth/). The
+// test-only twin reads SN_MSM_REC32 to run the padded 32-byte one for the A/B; the results are the same bits.
+int msm_dispatch(sn_ctx *c, bool host, const sn_mesh_smooth_cfg *cfg, int V, const double *verts, int F, int nv, const int32_t *faces, MsmOut d,
+                 long long *counts)
+{
+    if (F > 0 && (!faces || (V > 0 && !verts))) return fail(SN_ERR_ARG, "null argument");
+    if (F == 0 && V > 0 && !verts && (d.verts_mm || d.verts_lattice)) return fail(SN_ERR_ARG, "null argument");
+    if (V == 0 && F == 0) return SN_OK;
+    HIPCHK(hipSetDevice(c->device));
+    if (sn_ab_switch("SN_MSM_REC32")) return msm_run<4>(c, host, cfg, V, verts, F, nv, faces, d, counts);
+    return msm_run<3>(c, host, cfg, V, verts, F, nv, faces, d, counts);
+}
+
+}  // namespace
+
+extern "C" int sn_mesh_smooth_dev(sn_ctx *c, const sn_mesh_smooth_cfg *cfg, int n_verts, const double *verts_dev, int n_faces, int nv,
+                                  const int32_t *faces_dev, float *verts_mm_dev, double *verts_lattice_dev, int32_t *vert_degree_dev,
+                                  unsigned char *vert_flags_dev, long long *counts)
+{
+    int rc;
+    if ((rc = msm_check(c, cfg, n_verts, n_faces, nv, counts)) != SN_OK) return rc;
+    const MsmOut o = {verts_mm_dev, verts_lattice_dev, vert_degree_dev, vert_flags_dev};
+    return msm_dispatch(c, false, cfg, n_verts, verts_dev, n_faces, nv, faces_dev, o, counts);
+}
+
+extern "C" int sn_mesh_smooth(sn_ctx *c, const sn_mesh_smooth_cfg *cfg, int n_verts, const double *verts, int n_faces, int nv, const int32_t *faces,
+                              float *verts_mm, double *verts_lattice, int32_t *vert_degree, unsigned char *vert_flags, long long *counts)
+{
+    int rc;
+    if ((rc = msm_check(c, cfg, n_verts, n_faces, nv, counts)) != SN_OK) return rc;
+    const MsmOut o = {verts_mm, verts_lattice, vert_degree, vert_flags};
+    return msm_dispatch(c, true, cfg, n_verts, verts, n_faces, nv, faces, o, counts);
+}

@@ -4,6 +4,7 @@
     triangulate        quads -> triangles
     sample_surface     surface samples of a mesh at the evaluation density (evaluation.mesh_compare scores them)
     simplify_mesh      the mesh made smaller by vertex clustering on a coarser lattice
+    smooth_mesh        the mesh without its staircase: Taubin smoothing in fixed point, and its edge statistics
     save_mesh_2ply     binary little-endian PLY of a quad or triangle mesh
 
 The reference ends in a point cloud: its utils/mesh_util.py only reads and writes OBJ files. The mesher looks at the scene on the world voxel
@@ -193,6 +194,84 @@ def simplify_mesh(vert_lattice, faces, cell, placement="mean", origin=(0.0, 0.0,
     if src is not None:
         res["vert_src"] = src[m["vert_rep"]]
     return res
+
+
+BOUNDARIES = {"fixed": 0, "curve": 1, "free": 2}
+
+
+def check_smooth_args(iterations, lam, mu, boundary):
+    """-> (iterations, lam_q16, mu_q16, boundary code) of smooth_mesh's four settings, or ValueError. A factor becomes int(rint(x * 65536))."""
+    try:
+        n = int(iterations)
+    except (TypeError, ValueError):
+        raise ValueError("iterations = %r must be an integer" % (iterations,))
+    if isinstance(iterations, bool) or n != iterations or not 0 <= n <= 1000:
+        raise ValueError("iterations = %r: an integer in 0 .. 1000" % (iterations,))
+    q = []
+    for name, x in (("lam", lam), ("mu", mu)):
+        try:
+            w = float(x)
+        except (TypeError, ValueError):
+            raise ValueError("%s = %r must be a number" % (name, x))
+        if isinstance(x, bool) or not np.isfinite(w) or not -1.0 <= w <= 1.0:
+            raise ValueError("%s = %r: a factor in -1 .. 1" % (name, x))
+        q.append(int(np.rint(w * 65536.0)))
+    if not isinstance(boundary, str) or boundary not in BOUNDARIES:
+        raise ValueError("boundary = %r: 'fixed', 'curve' or 'free'" % (boundary,))
+    return n, q[0], q[1], BOUNDARIES[boundary]
+
+
+def smooth_mesh(vert_lattice, faces, iterations=10, lam=0.5, mu=-0.53, boundary="curve", origin=(0.0, 0.0, 0.0), resol=1.0):
+    """Taubin lambda|mu smoothing of a mesh with the uniform umbrella operator, in fixed point: vert_lattice (V,3)
+    float32 or float64 in lattice cells as extract_mesh or simplify_mesh return it, faces (F,3) triangles or (F,4) quads - quads stay quads,
+    their four sides are the edges; `iterations` times a pass with factor lam, then one with mu (mu = 0: plain Laplacian smoothing, which
+    shrinks); boundary "fixed" (boundary vertices stay), "curve" (they smooth along the boundary curve) or "free"; origin / resol as
+    lattice_origin returns them. -> dict: vertices (V,3) float32 in mm, vert_lattice (V,3) float64, vert_degree (V,) int32, vert_flags (V,)
+    uint8 (1 referenced, 2 boundary vertex, 4 end of a non-manifold edge), n_edges, n_boundary_edges, n_nonmanifold_edges, n_referenced.
+    Indices do not change: faces, colours, normals and vert_src carry over. iterations = 0 only reports the topology (n_boundary_edges = 0:
+    the mesh is closed). ValueError on bad shapes, dtypes, settings, face indices or coordinates before the library is touched."""
+    v = np.asarray(vert_lattice)
+    if v.dtype not in (np.float32, np.float64):
+        raise ValueError("vert_lattice must be float32 or float64, not %s" % v.dtype)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError("vert_lattice must be (V,3), not %r" % (v.shape,))
+    f = np.asarray(faces)
+    if f.ndim != 2 or f.shape[1] not in (3, 4):
+        raise ValueError("faces must be (F,3) or (F,4), not %r" % (f.shape,))
+    if f.dtype.kind not in "iu":
+        raise ValueError("faces must hold integers, not %s" % f.dtype)
+    n, lam_q16, mu_q16, code = check_smooth_args(iterations, lam, mu, boundary)
+    try:
+        o = np.asarray(origin, dtype=np.float64).reshape(-1)
+        r = float(resol)
+    except (TypeError, ValueError):
+        raise ValueError("origin = %r, resol = %r must be numbers" % (origin, resol))
+    if o.shape != (3,) or not np.isfinite(o).all():
+        raise ValueError("origin = %r must be three finite numbers" % (origin,))
+    if not (np.isfinite(r) and r > 0):
+        raise ValueError("resol = %r must be finite and > 0" % (resol,))
+    V, F = v.shape[0], f.shape[0]
+    if V > 1 << 28 or F > 1 << 28:
+        raise ValueError("%d vertices, %d faces: at most 2^28 of either" % (V, F))
+    if F:
+        bad = ((f < 0) | (f >= V)).any(axis=1)
+        if bad.any():
+            raise ValueError("face %d names a vertex outside [0, %d)" % (int(np.argmax(bad)), V))
+        referenced = np.zeros((V,), bool)
+        referenced[f.reshape(-1)] = True
+        with np.errstate(invalid="ignore"):
+            out_of_range = referenced & ~((v >= -4.0) & (v < 2097144.0)).all(axis=1)      # (NaN fails)
+        if out_of_range.any():
+            first = int(np.argmax(out_of_range[f].any(axis=1)))
+            raise ValueError("face %d: a coordinate of one of its vertices is outside [-4, 2^21 - 8) lattice cells" % first)
+    if V == 0:
+        m = dict(verts_mm=np.zeros((0, 3), np.float32), verts_lattice=np.zeros((0, 3), np.float64), vert_degree=np.zeros((0,), np.int32),
+                 vert_flags=np.zeros((0,), np.uint8), counts=np.zeros((4,), np.int64))
+    else:
+        m = runtime.any_context().mesh_smooth(v.astype(np.float64), f.astype(np.int32), n, lam_q16, mu_q16, code, origin=o, resol=r)
+    c = [int(x) for x in m["counts"]]
+    return dict(vertices=m["verts_mm"], vert_lattice=m["verts_lattice"], vert_degree=m["vert_degree"], vert_flags=m["vert_flags"],
+                n_edges=c[0], n_boundary_edges=c[1], n_nonmanifold_edges=c[2], n_referenced=c[3])
 
 
 def save_mesh_2ply(path, vertices, faces, normal_np=None, rgb_np=None):

@@ -563,9 +563,16 @@ def reconstruct_scene(images_list, cameraPOs_np, cubes_param_np, cube_D_mm, cube
     return out
 
 
+def _smoothed(_mesh, m, smooth_kw, origin, resol):
+    """extract_mesh's dict m with the positions smooth_mesh gives its quads, and smooth_mesh's statistics."""
+    s = _mesh.smooth_mesh(m["vert_lattice"], m["quads"], origin=origin, resol=resol, **smooth_kw)
+    return dict(m, vertices=s.pop("vertices"), vert_lattice=s.pop("vert_lattice"), **s)
+
+
 def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, gamma=0.8, beta=6, N_refine_iter=8, init_probThresh=0.5,
                    max_probThresh=0.9, keep_iterations=False, cameraTs_np=None, cube_overlapping_ratio=0.5, unique=False, mesh=False, mesh_radius=2,
-                   mesh_reach=0, mesh_ply_prefix=None, min_component=None, component_connectivity=26, mesh_cell=None, mesh_placement="mean"):
+                   mesh_reach=0, mesh_ply_prefix=None, min_component=None, component_connectivity=26, mesh_cell=None, mesh_placement="mean",
+                   mesh_smooth=None):
     """The reconstruction's last two stages on `reconstruct_scene`'s dict, in memory and on the GPU, as the reference runs them on its files:
       * main_reconstruct.py:172-175  thinning masks (prob >= tau, votes >= gamma * N_vp * 2), then denoise_crossCubes with D_cube = cube_D
       * main.py:37-43 -> utils/adapthresh.py  adaptive thresholding with D_cube = cube_Dcenter, init / max threshold init_probThresh /
@@ -588,7 +595,13 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
       mesh_cell=k (needs mesh=True): fixThresh_mesh_simplified, adapt_mesh_simplified - mesh.simplify_mesh of the two
         triangulated meshes on a lattice of k cells per axis (mesh_placement "mean" / "member", origin and resol from mesh.lattice_origin), each
         a dict of vertices, faces, vert_lattice, vert_rep, vert_count, face_src, vert_cluster, vert_src; with mesh_ply_prefix also written as
-        <prefix>fixThresh_mesh_c<k>.ply / <prefix>adapt_mesh_c<k>.ply (triangles, normals and colours gathered through vert_src)."""
+        <prefix>fixThresh_mesh_c<k>.ply / <prefix>adapt_mesh_c<k>.ply (triangles, normals and colours gathered through vert_src).
+      mesh_smooth=n or dict(iterations=, lam=, mu=, boundary=) (needs mesh=True): fixThresh_mesh_smoothed,
+        adapt_mesh_smoothed - the quad mesh of mesh=True with the positions mesh.smooth_mesh gives its quads (origin and resol from
+        mesh.lattice_origin): a dict of vertices, quads, vert_src, vert_lattice as the mesh's own, plus vert_degree, vert_flags, n_edges,
+        n_boundary_edges, n_nonmanifold_edges, n_referenced; with mesh_ply_prefix also written as <prefix>fixThresh_mesh_s<iterations>.ply /
+        <prefix>adapt_mesh_s<iterations>.ply with the unchanged normals and colours. With mesh_cell too the order is smooth, then decimate:
+        the simplified mesh is built from the SMOOTHED positions."""
     from . import adapthresh, denoising, sparseCubes
     from . import normals as _normals
     N_vp = int(N_viewPairs4inference)
@@ -599,6 +612,15 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
             raise ValueError("mesh_cell needs mesh=True: it simplifies the mesh that mesh=True extracts")
         from . import mesh as _mesh
         mesh_cell = _mesh.check_simplify_args(mesh_cell, mesh_placement)[0]
+    if mesh_smooth is not None:
+        if not mesh:
+            raise ValueError("mesh_smooth needs mesh=True: it smooths the mesh that mesh=True extracts")
+        from . import mesh as _mesh
+        smooth_kw = dict(mesh_smooth) if isinstance(mesh_smooth, dict) else dict(iterations=mesh_smooth)
+        if set(smooth_kw) - {"iterations", "lam", "mu", "boundary"}:
+            raise ValueError("mesh_smooth = %r: a number of iterations or a dict of iterations, lam, mu, boundary" % (mesh_smooth,))
+        smooth_kw = dict(dict(iterations=10, lam=0.5, mu=-0.53, boundary="curve"), **smooth_kw)
+        _mesh.check_smooth_args(**smooth_kw)
     if min_component is not None:
         from . import components as _components
         _components.check_args(min_component, None, component_connectivity)
@@ -620,6 +642,9 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
     if mesh:
         from . import mesh as _mesh
         res.update(fixThresh_mesh=_mesh.empty_mesh(), adapt_mesh=_mesh.empty_mesh())
+        if mesh_smooth is not None:
+            for name in ("fixThresh", "adapt"):
+                res[name + "_mesh_smoothed"] = _smoothed(_mesh, _mesh.empty_mesh(), smooth_kw, (0.0, 0.0, 0.0), 1.0)
         if mesh_cell is not None:
             empty = _mesh.empty_mesh()
             for name in ("fixThresh", "adapt"):
@@ -665,6 +690,12 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
                 if rgb is not None:
                     rgb[src < 0] = 0
                 _mesh.save_mesh_2ply("%s%s_mesh.ply" % (mesh_ply_prefix, name), m["vertices"], m["quads"], normal_np=nrm, rgb_np=rgb)
+            if mesh_smooth is not None:
+                origin, resol = _mesh.lattice_origin(cube_ijk, out["param_np"], stride_vox)
+                m = res[name + "_mesh_smoothed"] = _smoothed(_mesh, m, smooth_kw, origin, resol)      # (mesh_cell below decimates this one)
+                if mesh_ply_prefix is not None:
+                    _mesh.save_mesh_2ply("%s%s_mesh_s%d.ply" % (mesh_ply_prefix, name, int(smooth_kw["iterations"])), m["vertices"], m["quads"],
+                                         normal_np=nrm, rgb_np=rgb)
             if mesh_cell is not None:
                 origin, resol = _mesh.lattice_origin(cube_ijk, out["param_np"], stride_vox)
                 sm = _mesh.simplify_mesh(m["vert_lattice"], m["quads"], mesh_cell, mesh_placement, origin=origin, resol=resol, vert_src=m["vert_src"])
