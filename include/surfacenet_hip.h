@@ -32,7 +32,7 @@ extern "C" {
  * sn_mesh_sample and sn_mesh_sample_dev - surface samples of a triangle mesh; sn_components, sn_components_dev and sn_components_cfg - connected
  * components of the output cloud; sn_mesh_simplify, sn_mesh_simplify_dev and sn_mesh_simplify_cfg - a triangle mesh made smaller by vertex
  * clustering; sn_mesh_smooth, sn_mesh_smooth_dev and sn_mesh_smooth_cfg - Taubin smoothing of a triangle or quad mesh in fixed point, with
- * the mesh's edge and boundary counts. */
+ * the mesh's edge and boundary counts; sn_mesh_fill, sn_mesh_fill_dev and sn_mesh_fill_cfg - the mesh's small holes capped by centroid fans. */
 
 /* The library is built with -fvisibility=hidden: the functions below are its WHOLE dynamic symbol table
  * (tests/test_abi.py compares `nm -D` with this header). */
@@ -424,6 +424,46 @@ SN_API int sn_mesh_smooth(sn_ctx *ctx, const sn_mesh_smooth_cfg *cfg, int n_vert
 SN_API int sn_mesh_smooth_dev(sn_ctx *ctx, const sn_mesh_smooth_cfg *cfg, int n_verts, const double *verts_dev, int n_faces, int nv,
                               const int32_t *faces_dev, float *verts_mm_dev, double *verts_lattice_dev, int32_t *vert_degree_dev,
                               unsigned char *vert_flags_dev, long long *counts);
+
+/* ---- a mesh's small holes filled: closed boundary loops, each capped by a fan around its centroid ------------------------
+ * The inputs are sn_mesh_smooth's: verts (n_verts,3) float64 in lattice cells, faces (n_faces,nv) int32 with nv = 3 or 4, a quad's four sides
+ * its edges; referenced vertices, q = int64(rint(v * 65536)) and its range, sides, edges, counts, boundary (count 1) and non-manifold (count
+ * > 2) edges as there. A boundary half-edge is the one side (p -> r) on a boundary edge, in its face's direction; its third vertex s is the
+ * face's next corner after r (f[(k + 2) % nv] for side k). Per vertex out / in = the boundary half-edges leaving / entering it; a vertex is
+ * simple iff out = 1, in = 1 and it is no end of a non-manifold edge. A boundary component is a maximal set of vertices joined by boundary
+ * edges, its root its smallest vertex, its length n its number of boundary half-edges. It is a simple loop iff all its vertices are simple
+ * (then p -> r is one directed cycle of n vertices), else complex and left alone; a simple loop with n > max_len is long and left alone. Per
+ * axis the centroid c = floor((2 S + n) / (2 n)), S the int64 sum of q over the loop. With orientation 0 every half-edge of the loop votes:
+ * d1 = float64(q[r] - q[p]), d2 = float64(q[s] - q[p]), d3 = float64(c - q[p]), a = d1 x d2, b = d1 x d3 (x = y*z' - z*y', y = z*x' - x*z',
+ * z = x*y' - y*x'), dot = (a.x*b.x + a.y*b.y) + a.z*b.z in float64 without contraction; the vote is "hole" iff dot < 0 (the centroid lies
+ * across the edge from the face); the loop is a hole iff 2 * votes > n, else a rim and left alone. With orientation 1 every simple loop within
+ * max_len is filled. The filled loops, ranked by ascending root, give H new vertices n_verts + rank at c / 65536, and one triangle
+ * (r, p, n_verts + rank) per half-edge p -> r, ordered by ascending p (T of them). Outputs, each optional (NULL) except counts:
+ *   new_verts_lattice (H,3) float64; new_verts_mm (H,3) float32 = float32(origin + resol * lattice) in float64 without contraction;
+ *   loop_root (H) int32, loop_len (H) int32: colour, normal and source voxel of a new vertex are taken from its root by the caller;
+ *   new_faces (T,3) int32 into the concatenation [verts; new_verts]; the old vertices and faces are neither touched nor returned;
+ *   vert_loop (n_verts) uint8: 0 not on a boundary edge, 1 on a filled loop, 2 on a long loop, 3 on a rim, 4 on a complex component;
+ *   counts[8]: E, boundary edges, boundary components, filled loops H, long loops, rims, complex components, new triangles T.
+ * The outputs hold cap_verts new vertices and cap_faces new triangles (T <= nv * n_faces and H <= T / 3 always suffice); when one is short
+ * nothing is written, the counts say what is needed and the status is SN_ERR_ARG. SN_ERR_ARG too, nothing written but counts (zeros), in
+ * sn_mesh_smooth's words: a face index outside [0, n_verts) or a referenced coordinate outside the range (or not a number), the text naming
+ * the first offending face; nv not 3 or 4, resol, origin, n_verts or n_faces > 2^28, 2^30 or more edges; and max_len outside 3 .. 65536,
+ * orientation not 0 or 1, a negative cap. n_faces = 0: all counts 0, nothing written. Integers and one fixed-order float64 expression: the
+ * result equals the numpy restatement tests/meshfill_ref.py bit for bit, on every run. The workspace belongs to the context (grown on demand);
+ * both forms return when the work is done. */
+typedef struct sn_mesh_fill_cfg {
+    int max_len;               /* the longest loop that is filled, in edges: 3 .. 65536 */
+    int orientation;           /* 0: holes only (the vote); 1: any simple loop */
+    double origin[3];          /* mm position of lattice point (0,0,0) */
+    double resol;              /* mm per cell */
+} sn_mesh_fill_cfg;
+SN_API int sn_mesh_fill(sn_ctx *ctx, const sn_mesh_fill_cfg *cfg, int n_verts, const double *verts, int n_faces, int nv, const int32_t *faces,
+                        long long cap_verts, long long cap_faces, float *new_verts_mm, double *new_verts_lattice, int32_t *loop_root,
+                        int32_t *loop_len, int32_t *new_faces, unsigned char *vert_loop, long long *counts);
+SN_API int sn_mesh_fill_dev(sn_ctx *ctx, const sn_mesh_fill_cfg *cfg, int n_verts, const double *verts_dev, int n_faces, int nv,
+                            const int32_t *faces_dev, long long cap_verts, long long cap_faces, float *new_verts_mm_dev,
+                            double *new_verts_lattice_dev, int32_t *loop_root_dev, int32_t *loop_len_dev, int32_t *new_faces_dev,
+                            unsigned char *vert_loop_dev, long long *counts);
 
 /* ---- DTU point-cloud evaluation (experiments/DTU/eval_ply.m -> PointCompareMain of the DTU kit) ----------------------
  * Points are (n,3) float64, row-major, finite. d^2 = (dx*dx + dy*dy) + dz*dz in float64 without contraction: the results are those of the numpy

@@ -23,7 +23,7 @@ ABI_SYMBOLS = [
     "sn_normals", "sn_normals_dev", "sn_unique_voxels", "sn_unique_voxels_dev",
     "sn_components", "sn_components_dev",
     "sn_mesh", "sn_mesh_dev", "sn_mesh_sample", "sn_mesh_sample_dev", "sn_mesh_simplify", "sn_mesh_simplify_dev",
-    "sn_mesh_smooth", "sn_mesh_smooth_dev",
+    "sn_mesh_smooth", "sn_mesh_smooth_dev", "sn_mesh_fill", "sn_mesh_fill_dev",
     "sn_point_reduce", "sn_nn_dist2", "sn_point_flags",
     "sn_ptcubes", "sn_ptcubes_dev", "sn_ptcubes_sparse_dev",
     "sn_gt_bind", "sn_gt_bind_dev", "sn_gt_cubes", "sn_gt_cubes_dev", "sn_weighted_accuracy", "sn_weighted_accuracy_dev",
@@ -71,6 +71,10 @@ class MeshSimplifyCfg(ctypes.Structure):
 class MeshSmoothCfg(ctypes.Structure):
     _fields_ = [("iterations", ctypes.c_int), ("lam_q16", ctypes.c_int), ("mu_q16", ctypes.c_int), ("boundary", ctypes.c_int),
                 ("origin", ctypes.c_double * 3), ("resol", ctypes.c_double)]
+
+
+class MeshFillCfg(ctypes.Structure):
+    _fields_ = [("max_len", ctypes.c_int), ("orientation", ctypes.c_int), ("origin", ctypes.c_double * 3), ("resol", ctypes.c_double)]
 
 
 class PtCubesCfg(ctypes.Structure):
@@ -166,6 +170,10 @@ def load():
                                  [P(ctypes.c_longlong)] * 2),
         "sn_mesh_smooth": (c_int, [c_void_p, P(MeshSmoothCfg), c_int, c_void_p, c_int, c_int] + [c_void_p] * 5 + [P(ctypes.c_longlong)]),
         "sn_mesh_smooth_dev": (c_int, [c_void_p, P(MeshSmoothCfg), c_int, c_void_p, c_int, c_int] + [c_void_p] * 5 + [P(ctypes.c_longlong)]),
+        "sn_mesh_fill": (c_int, [c_void_p, P(MeshFillCfg), c_int, c_void_p, c_int, c_int, c_void_p] + [ctypes.c_longlong] * 2 + [c_void_p] * 6 +
+                         [P(ctypes.c_longlong)]),
+        "sn_mesh_fill_dev": (c_int, [c_void_p, P(MeshFillCfg), c_int, c_void_p, c_int, c_int, c_void_p] + [ctypes.c_longlong] * 2 + [c_void_p] * 6 +
+                             [P(ctypes.c_longlong)]),
         "sn_point_reduce": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_double, c_void_p, P(c_int)]),
         "sn_nn_dist2": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_double, c_void_p]),
         "sn_point_flags": (c_int, [c_void_p, ctypes.c_longlong] + [c_void_p] * 4 + [ctypes.c_double] + [c_void_p] * 3),

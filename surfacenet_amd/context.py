@@ -682,6 +682,53 @@ class Context(object):
         out["counts"] = np.asarray(list(counts), np.int64)
         return out
 
+    def mesh_fill(self, verts, faces, max_len=64, orientation=0, origin=(0.0, 0.0, 0.0), resol=1.0, cap=None, device=False):
+        """The small holes of a mesh capped by centroid fans (sn_mesh_fill): verts (V,3) float64 in lattice cells, faces
+        (F,3) or (F,4) int32, max_len 3..65536 the longest loop that is filled, orientation 0 (holes only) / 1 (any simple loop), origin (3,) /
+        resol as Context.mesh takes them. Returns a dict: new_verts_mm (H,3) float32, new_verts_lattice (H,3) float64, loop_root (H,) int32,
+        loop_len (H,) int32, new_faces (T,3) int32 into [verts; new_verts], vert_loop (V,) uint8 (0 none, 1 filled, 2 long, 3 rim, 4 complex),
+        counts (8,) int64 = edges, boundary edges, boundary components, filled loops, long loops, rims, complex components, new triangles.
+        cap = (new vertices, new triangles) the first call's arrays hold (nv * F // 3 and nv * F when None, which always suffice); a short cap
+        costs one retry with the exact counts. device=True stages the mesh in device memory here and runs sn_mesh_fill_dev on it: the same
+        result."""
+        v = np.ascontiguousarray(verts, dtype=np.float64).reshape(-1, 3)
+        f = np.ascontiguousarray(faces, dtype=np.int32)
+        if f.ndim != 2:
+            raise ValueError("faces must be (F,3) or (F,4), not %r" % (f.shape,))
+        V, (F, nv) = v.shape[0], f.shape
+        cfg = _lib.MeshFillCfg(int(max_len), int(orientation))
+        cfg.origin[:] = [float(x) for x in np.asarray(origin, dtype=np.float64).reshape(3)]
+        cfg.resol = float(resol)
+        caps = (nv * F // 3, nv * F) if cap is None else (int(cap[0]), int(cap[1]))
+        counts = (ctypes.c_longlong * 8)()
+
+        def call(caps):
+            H, T = caps
+            out = dict(new_verts_mm=np.empty((H, 3), np.float32), new_verts_lattice=np.empty((H, 3), np.float64), loop_root=np.empty((H,), np.int32),
+                       loop_len=np.empty((H,), np.int32), new_faces=np.empty((T, 3), np.int32), vert_loop=np.zeros((V,), np.uint8))
+            if not device:
+                rc = self._lib.sn_mesh_fill(self._h, ctypes.byref(cfg), V, _lib.ptr(v), F, nv, _lib.ptr(f), H, T, *[_lib.ptr(a) for a in out.values()],
+                                            counts)
+                return rc, out
+            with self._on_device((v, f)) as src, self._on_device(out.values(), upload=False) as dst:
+                rc = self._lib.sn_mesh_fill_dev(self._h, ctypes.byref(cfg), V, src[0], F, nv, src[1], H, T, *dst, counts)
+                if rc == 0 and F:
+                    rows = dict(new_faces=counts[7], vert_loop=V)
+                    for (name, a), b in zip(out.items(), dst):
+                        r = rows.get(name, counts[3])
+                        if r:
+                            self.d2h(a[:r], b)
+            return rc, out
+
+        rc, out = call(caps)
+        if rc == -1 and (counts[3] > caps[0] or counts[7] > caps[1]):
+            rc, out = call((counts[3], counts[7]))
+        _lib.check(rc)
+        H, T = counts[3], counts[7]
+        out = {name: (a if name == "vert_loop" else a[:T if name == "new_faces" else H].copy()) for name, a in out.items()}
+        out["counts"] = np.asarray(list(counts), np.int64)
+        return out
+
     @staticmethod
     def _points(xyz):
         return np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))

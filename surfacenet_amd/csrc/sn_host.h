@@ -1,6 +1,6 @@
 // sn_host.h — the host plumbing of the C entry points that needs no device: the error text, sizes of hash tables, bump allocation from one
 // buffer (Carve), the plan of a call's host mirror (MirrorPlan: which host array got which region of that buffer), and the argument checks of
-// the packed sparse voxel lists and of the mesh smoother. Plain C++17, no hip/ include: tests/host/sn_host_check.cpp compiles it alone.
+// the packed sparse voxel lists, of the mesh smoother and of the hole filler. Plain C++17, no hip/ include: tests/host/sn_host_check.cpp compiles it alone.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -131,5 +131,22 @@ static inline int msm_check_args(const sn_mesh_smooth_cfg *cfg, int n_verts, int
     if (!std::isfinite(cfg->resol) || !(cfg->resol > 0)) return fail(SN_ERR_ARG, "resol = %g must be finite and > 0", cfg->resol);
     for (int d = 0; d < 3; ++d)
         if (!std::isfinite(cfg->origin[d])) return fail(SN_ERR_ARG, "origin[%d] = %g is not finite", d, cfg->origin[d]);
+    return SN_OK;
+}
+
+// ---- sn_mesh_fill / sn_mesh_fill_dev: the same for the hole filler; the shared refusals in the smoother's words -------
+static inline int mfl_check_args(const sn_mesh_fill_cfg *cfg, int n_verts, int n_faces, int nv, long long cap_verts, long long cap_faces)
+{
+    if (!cfg) return fail(SN_ERR_ARG, "null cfg");
+    if (n_verts < 0 || n_faces < 0) return fail(SN_ERR_ARG, "n_verts and n_faces must be >= 0");
+    if (n_verts > (1 << 28) || n_faces > (1 << 28))
+        return fail(SN_ERR_ARG, "n_verts = %d, n_faces = %d: at most 2^28 of either", n_verts, n_faces);
+    if (nv != 3 && nv != 4) return fail(SN_ERR_ARG, "nv = %d: faces are triangles (3) or quads (4)", nv);
+    if (cfg->max_len < 3 || cfg->max_len > 65536) return fail(SN_ERR_ARG, "max_len = %d: 3 .. 65536", cfg->max_len);
+    if (cfg->orientation != 0 && cfg->orientation != 1) return fail(SN_ERR_ARG, "orientation = %d: 0 (holes) or 1 (any)", cfg->orientation);
+    if (!std::isfinite(cfg->resol) || !(cfg->resol > 0)) return fail(SN_ERR_ARG, "resol = %g must be finite and > 0", cfg->resol);
+    for (int d = 0; d < 3; ++d)
+        if (!std::isfinite(cfg->origin[d])) return fail(SN_ERR_ARG, "origin[%d] = %g is not finite", d, cfg->origin[d]);
+    if (cap_verts < 0 || cap_faces < 0) return fail(SN_ERR_ARG, "cap_verts and cap_faces must be >= 0");
     return SN_OK;
 }

@@ -3,11 +3,10 @@
 // host's: plain launches on the context's stream, at most 2 * iterations of the pass kernel.
 #include "sn_internal.h"
 #include "meshsmooth.h"
+#include "meshsmooth_build.h"
 #include "scan.h"
 
 namespace {
-
-constexpr long long MSM_MAX_EDGES = 1ll << 30;         // 2 E row entries are addressed by the scan's int
 
 // the caller's outputs: device arrays in the device form, host arrays in the host form
 struct MsmOut { float *verts_mm; double *verts_lattice; int32_t *vert_degree; unsigned char *vert_flags; };
@@ -28,71 +27,29 @@ int msm_run(sn_ctx *c, bool host, const sn_mesh_smooth_cfg *cfg, int V, const do
     HostMirror m(c, host);
     int rc = m.inputs([&](Carve &w) { m.in(w, verts, 3 * (size_t)V); m.in(w, faces, (size_t)nv * (size_t)F); });
     if (rc != SN_OK) return rc;
-    MsmArgs a;
-    memset(&a, 0, sizeof a);
-    a.verts = verts; a.faces = faces; a.V = V; a.F = F; a.nv = nv; a.boundary = cfg->boundary; a.resol = cfg->resol;
-    for (int k = 0; k < 3; ++k) a.origin[k] = cfg->origin[k];
     const size_t nsides = (size_t)nv * (size_t)F;
-    const size_t cap = table_cap((unsigned long long)nsides, 2, 64);      // at most 2^31 slots: the mask fits an unsigned
-    a.mask = (unsigned)(cap - 1);
+    const size_t cap = msm_table_cap(F, nv);
+    MsmArgs a;
+    msm_set_inputs(a, V, verts, F, nv, faces, cfg->origin, cfg->resol, cap);
+    a.boundary = cfg->boundary;
     int *sums = nullptr;
     auto layout = [&](Carve &w) {
         a.st = w.get<MsmStat>(1);
-        a.vfl = w.get<unsigned>((size_t)V);
-        a.deg = w.get<int>((size_t)V + 1);
+        msm_carve_build<REC>(w, a, cap);
         a.row = w.get<int>((size_t)V + 1);
         a.cursor = w.get<int>((size_t)V);
         sums = w.get<int>(scan_sums((size_t)V + 1));
-        a.tab = w.get<unsigned long long>(2 * cap);
-        a.sides = w.get<unsigned>(cap);
         a.nbr = w.get<unsigned>(2 * nsides);
-        a.pos[0] = w.get<long long>((size_t)REC * (size_t)V);
         a.pos[1] = w.get<long long>((size_t)REC * (size_t)V);
     };
     if ((rc = dev_carve(c, c->msm_ws, layout, 256)) != SN_OK) return rc;
-    const unsigned vb = blocks(V, MSM_NT), fb = blocks(F, MSM_NT), sb = blocks((long long)cap, MSM_NT);
-    const unsigned loop_blocks = (unsigned)std::max(c->num_cus, 1) * 8u;      // the grid-stride kernels: eight workgroups per CU at most
-    HIPCHK(hipMemsetAsync(a.st, 0, sizeof(MsmStat), c->stream));
-    HIPCHK(hipMemsetAsync(a.st, 0xff, 2 * sizeof(unsigned long long), c->stream));      // first_bad, bad_vertex = MSM_NONE
-    {
-        ProfScope ps(c, "msm_mark", 0, (double)F * nv * 8.0 + (double)V * (28.0 + 8.0 * REC));
-        HIPCHK(hipMemsetAsync(a.vfl, 0, sizeof(unsigned) * std::max<size_t>((size_t)V, 1), c->stream));
-        if (F > 0) {
-            hipLaunchKernelGGL(msm_mark_kernel, dim3(fb), dim3(MSM_NT), 0, c->stream, a);
-            HIPCHK(hipGetLastError());
-        }
-        if (V > 0) {
-            hipLaunchKernelGGL(msm_quantise_kernel<REC>, dim3(std::min(vb, loop_blocks)), dim3(MSM_NT), 0, c->stream, a);
-            HIPCHK(hipGetLastError());
-        }
-    }
-    {
-        ProfScope ps(c, "msm_edges", 0, (double)F * nv * 28.0 + (double)cap * 20.0);
-        HIPCHK(hipMemsetAsync(a.tab, 0, sizeof(unsigned long long) * 2 * cap, c->stream));
-        HIPCHK(hipMemsetAsync(a.sides, 0, sizeof(unsigned) * cap, c->stream));
-        if (F > 0) {
-            hipLaunchKernelGGL(msm_edges_kernel, dim3(fb), dim3(MSM_NT), 0, c->stream, a);
-            HIPCHK(hipGetLastError());
-        }
-    }
-    {
-        ProfScope ps(c, "msm_degree", 0, (double)cap * 12.0 + (double)V * 12.0);
-        HIPCHK(hipMemsetAsync(a.deg, 0, sizeof(int) * ((size_t)V + 1), c->stream));
-        hipLaunchKernelGGL(msm_degree_kernel, dim3(std::min(sb, loop_blocks)), dim3(MSM_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
-    }
+    const unsigned vb = blocks(V, MSM_NT), sb = blocks((long long)cap, MSM_NT);
+    if ((rc = msm_build<REC>(c, a, cap)) != SN_OK) return rc;
     // the one read before any output is touched: the first bad face, the degree limit, the counts
     MsmStat st;
     HIPCHK(hipMemcpyAsync(&st, a.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (st.first_bad != MSM_NONE) {
-        const long long f = (long long)(st.first_bad >> 3);
-        if ((st.first_bad & 7) == MSM_ERR_INDEX) return fail(SN_ERR_ARG, "face %lld names a vertex outside [0, %d)", f, V);
-        return fail(SN_ERR_ARG, "face %lld: a coordinate of one of its vertices is outside [-4, 2^21 - 8) lattice cells (or not a number)", f);
-    }
-    if (st.bad_vertex != MSM_NONE)
-        return fail(SN_ERR_ARG, "vertex %lld has 2^24 or more edges: at most 2^24 - 1", (long long)st.bad_vertex);
-    if ((long long)st.counts[0] >= MSM_MAX_EDGES) return fail(SN_ERR_ARG, "%lld edges: at most 2^30 - 1", (long long)st.counts[0]);
+    if ((rc = msm_report(st, V, true)) != SN_OK) return rc;
     rc = m.outputs([&](Carve &w) {
         m.out(w, d.verts_mm, 3 * (size_t)V); m.out(w, d.verts_lattice, 3 * (size_t)V); m.out(w, d.vert_degree, (size_t)V);
         m.out(w, d.vert_flags, (size_t)V);

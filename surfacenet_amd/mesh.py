@@ -5,6 +5,7 @@
     sample_surface     surface samples of a mesh at the evaluation density (evaluation.mesh_compare scores them)
     simplify_mesh      the mesh made smaller by vertex clustering on a coarser lattice
     smooth_mesh        the mesh without its staircase: Taubin smoothing in fixed point, and its edge statistics
+    fill_holes         the mesh with its small holes capped: boundary loops and centroid fans
     save_mesh_2ply     binary little-endian PLY of a quad or triangle mesh
 
 The reference ends in a point cloud: its utils/mesh_util.py only reads and writes OBJ files. The mesher looks at the scene on the world voxel
@@ -272,6 +273,97 @@ def smooth_mesh(vert_lattice, faces, iterations=10, lam=0.5, mu=-0.53, boundary=
     c = [int(x) for x in m["counts"]]
     return dict(vertices=m["verts_mm"], vert_lattice=m["verts_lattice"], vert_degree=m["vert_degree"], vert_flags=m["vert_flags"],
                 n_edges=c[0], n_boundary_edges=c[1], n_nonmanifold_edges=c[2], n_referenced=c[3])
+
+
+_triangles_of = triangulate                                   # (fill_holes has an argument of that name)
+ORIENTATIONS = {"holes": 0, "any": 1}
+FILL_COUNTS = ("n_edges", "n_boundary_edges", "n_boundary_components", "n_filled", "n_long", "n_rims", "n_complex", "n_new_faces")
+
+
+def check_fill_args(max_len, orientation):
+    """-> (max_len, orientation code) of fill_holes' two settings, or ValueError."""
+    try:
+        n = int(max_len)
+    except (TypeError, ValueError):
+        raise ValueError("max_len = %r must be an integer" % (max_len,))
+    if isinstance(max_len, bool) or n != max_len or not 3 <= n <= 65536:
+        raise ValueError("max_len = %r: an integer number of edges in 3 .. 65536" % (max_len,))
+    if not isinstance(orientation, str) or orientation not in ORIENTATIONS:
+        raise ValueError("orientation = %r: 'holes' or 'any'" % (orientation,))
+    return n, ORIENTATIONS[orientation]
+
+
+def fill_holes(vert_lattice, faces, max_len=64, orientation="holes", origin=(0.0, 0.0, 0.0), resol=1.0, vert_src=None, triangulate=True):
+    """The small holes of a mesh, capped: vert_lattice (V,3) float32 or float64 in lattice cells as extract_mesh,
+    smooth_mesh or simplify_mesh return it, faces (F,3) triangles or (F,4) quads, whose four sides are the edges. A closed loop of boundary
+    edges whose vertices each have one boundary edge in and one out is a simple loop; one of at most max_len edges is capped by a fan of
+    triangles around one new vertex at its centroid - with orientation "holes" only when the faces around it say it is a hole and not the rim
+    of an open piece, with "any" always. origin / resol as lattice_origin returns them. -> dict of the concatenated mesh: vertices (V + H,3)
+    float32 in mm (the old ones float32(origin + resol * vert_lattice)), vert_lattice (V + H,3) float64, faces - the old faces, triangulated
+    when they are quads and triangulate is True, followed by the new triangles; with triangulate=False on quads, faces are the untouched quads
+    and new_faces (T,3) stands beside them -, loop_root (H,) int32 the old vertex a new vertex takes colour and normal from, loop_len (H,)
+    int32, vert_loop (V,) uint8 (0 not on a boundary edge, 1 on a filled loop, 2 on a long loop, 3 on a rim, 4 on a complex component),
+    n_edges, n_boundary_edges, n_boundary_components, n_filled, n_long, n_rims, n_complex, n_new_faces; with vert_src (V,) also vert_src
+    extended by vert_src[loop_root]. ValueError on bad shapes, dtypes, settings, face indices or coordinates before the library is touched."""
+    v = np.asarray(vert_lattice)
+    if v.dtype not in (np.float32, np.float64):
+        raise ValueError("vert_lattice must be float32 or float64, not %s" % v.dtype)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError("vert_lattice must be (V,3), not %r" % (v.shape,))
+    f = np.asarray(faces)
+    if f.ndim != 2 or f.shape[1] not in (3, 4):
+        raise ValueError("faces must be (F,3) or (F,4), not %r" % (f.shape,))
+    if f.dtype.kind not in "iu":
+        raise ValueError("faces must hold integers, not %s" % f.dtype)
+    n, code = check_fill_args(max_len, orientation)
+    try:
+        o = np.asarray(origin, dtype=np.float64).reshape(-1)
+        r = float(resol)
+    except (TypeError, ValueError):
+        raise ValueError("origin = %r, resol = %r must be numbers" % (origin, resol))
+    if o.shape != (3,) or not np.isfinite(o).all():
+        raise ValueError("origin = %r must be three finite numbers" % (origin,))
+    if not (np.isfinite(r) and r > 0):
+        raise ValueError("resol = %r must be finite and > 0" % (resol,))
+    V, F = v.shape[0], f.shape[0]
+    if V > 1 << 28 or F > 1 << 28:
+        raise ValueError("%d vertices, %d faces: at most 2^28 of either" % (V, F))
+    src = None
+    if vert_src is not None:
+        src = np.asarray(vert_src).reshape(-1)
+        if src.shape[0] != V:
+            raise ValueError("%d vertices, %d entries of vert_src" % (V, src.shape[0]))
+    if F:
+        bad = ((f < 0) | (f >= V)).any(axis=1)
+        if bad.any():
+            raise ValueError("face %d names a vertex outside [0, %d)" % (int(np.argmax(bad)), V))
+        referenced = np.zeros((V,), bool)
+        referenced[f.reshape(-1)] = True
+        with np.errstate(invalid="ignore"):
+            out_of_range = referenced & ~((v >= -4.0) & (v < 2097144.0)).all(axis=1)      # (NaN fails)
+        if out_of_range.any():
+            first = int(np.argmax(out_of_range[f].any(axis=1)))
+            raise ValueError("face %d: a coordinate of one of its vertices is outside [-4, 2^21 - 8) lattice cells" % first)
+    v64 = v.astype(np.float64)
+    if F == 0:                                                  # no face: no loop, nothing for the library to do
+        m = dict(new_verts_mm=np.zeros((0, 3), np.float32), new_verts_lattice=np.zeros((0, 3), np.float64), loop_root=np.zeros((0,), np.int32),
+                 loop_len=np.zeros((0,), np.int32), new_faces=np.zeros((0, 3), np.int32), vert_loop=np.zeros((V,), np.uint8),
+                 counts=np.zeros((8,), np.int64))
+    else:
+        m = runtime.any_context().mesh_fill(v64, f.astype(np.int32), n, code, origin=o, resol=r)
+    with np.errstate(invalid="ignore"):
+        old_mm = (o + r * v64).astype(np.float32)               # (an unreferenced vertex may be anything)
+    res = dict(vertices=np.concatenate([old_mm, m["new_verts_mm"]]), vert_lattice=np.concatenate([v64, m["new_verts_lattice"]]))
+    old = f.astype(np.int32)
+    if f.shape[1] == 4 and not triangulate:
+        res.update(faces=old, new_faces=m["new_faces"])
+    else:
+        res["faces"] = np.concatenate([_triangles_of(old).astype(np.int32) if f.shape[1] == 4 else old, m["new_faces"]])
+    res.update(loop_root=m["loop_root"], loop_len=m["loop_len"], vert_loop=m["vert_loop"])
+    if src is not None:
+        res["vert_src"] = np.concatenate([src, src[m["loop_root"]]])
+    res.update({k: int(c) for k, c in zip(FILL_COUNTS, m["counts"])})
+    return res
 
 
 def save_mesh_2ply(path, vertices, faces, normal_np=None, rgb_np=None):

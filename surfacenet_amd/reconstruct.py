@@ -563,16 +563,27 @@ def reconstruct_scene(images_list, cameraPOs_np, cubes_param_np, cube_D_mm, cube
     return out
 
 
-def _smoothed(_mesh, m, smooth_kw, origin, resol):
-    """extract_mesh's dict m with the positions smooth_mesh gives its quads, and smooth_mesh's statistics."""
-    s = _mesh.smooth_mesh(m["vert_lattice"], m["quads"], origin=origin, resol=resol, **smooth_kw)
+def _smoothed(_mesh, m, smooth_kw, origin, resol, fkey="quads"):
+    """extract_mesh's dict m (or the filled mesh, its triangles under fkey = "faces") with the positions smooth_mesh gives its faces, and
+    smooth_mesh's statistics."""
+    s = _mesh.smooth_mesh(m["vert_lattice"], m[fkey], origin=origin, resol=resol, **smooth_kw)
     return dict(m, vertices=s.pop("vertices"), vert_lattice=s.pop("vert_lattice"), **s)
+
+
+def _filled(_mesh, m, fill_kw, origin, resol):
+    """mesh.fill_holes of extract_mesh's dict m: the triangulated mesh with its small holes capped."""
+    return _mesh.fill_holes(m["vert_lattice"], m["quads"], origin=origin, resol=resol, vert_src=m["vert_src"], **fill_kw)
+
+
+def _work_mesh(fm):
+    """What the stages after the filling read of the filled mesh."""
+    return dict(vertices=fm["vertices"], vert_lattice=fm["vert_lattice"], faces=fm["faces"], vert_src=fm["vert_src"])
 
 
 def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, gamma=0.8, beta=6, N_refine_iter=8, init_probThresh=0.5,
                    max_probThresh=0.9, keep_iterations=False, cameraTs_np=None, cube_overlapping_ratio=0.5, unique=False, mesh=False, mesh_radius=2,
                    mesh_reach=0, mesh_ply_prefix=None, min_component=None, component_connectivity=26, mesh_cell=None, mesh_placement="mean",
-                   mesh_smooth=None):
+                   mesh_smooth=None, mesh_fill=None):
     """The reconstruction's last two stages on `reconstruct_scene`'s dict, in memory and on the GPU, as the reference runs them on its files:
       * main_reconstruct.py:172-175  thinning masks (prob >= tau, votes >= gamma * N_vp * 2), then denoise_crossCubes with D_cube = cube_D
       * main.py:37-43 -> utils/adapthresh.py  adaptive thresholding with D_cube = cube_Dcenter, init / max threshold init_probThresh /
@@ -601,7 +612,13 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
         mesh.lattice_origin): a dict of vertices, quads, vert_src, vert_lattice as the mesh's own, plus vert_degree, vert_flags, n_edges,
         n_boundary_edges, n_nonmanifold_edges, n_referenced; with mesh_ply_prefix also written as <prefix>fixThresh_mesh_s<iterations>.ply /
         <prefix>adapt_mesh_s<iterations>.ply with the unchanged normals and colours. With mesh_cell too the order is smooth, then decimate:
-        the simplified mesh is built from the SMOOTHED positions."""
+        the simplified mesh is built from the SMOOTHED positions.
+      mesh_fill=max_len or dict(max_len=, orientation=) (needs mesh=True): fixThresh_mesh_filled, adapt_mesh_filled -
+        mesh.fill_holes of the quad mesh of mesh=True (origin and resol from mesh.lattice_origin): the triangulated mesh with its holes of at
+        most max_len edges capped, a dict of vertices, vert_lattice, faces, vert_src, loop_root, loop_len, vert_loop and the counts; with
+        mesh_ply_prefix also written as <prefix>fixThresh_mesh_f<max_len>.ply / <prefix>adapt_mesh_f<max_len>.ply, a new vertex with its
+        loop root's normal and colour. With mesh_smooth and / or mesh_cell too the order is fill, smooth, decimate, on the FILLED triangle
+        mesh: the smoothed dict then holds faces (triangles) in the place of quads."""
     from . import adapthresh, denoising, sparseCubes
     from . import normals as _normals
     N_vp = int(N_viewPairs4inference)
@@ -621,6 +638,15 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
             raise ValueError("mesh_smooth = %r: a number of iterations or a dict of iterations, lam, mu, boundary" % (mesh_smooth,))
         smooth_kw = dict(dict(iterations=10, lam=0.5, mu=-0.53, boundary="curve"), **smooth_kw)
         _mesh.check_smooth_args(**smooth_kw)
+    if mesh_fill is not None:
+        if not mesh:
+            raise ValueError("mesh_fill needs mesh=True: it fills the holes of the mesh that mesh=True extracts")
+        from . import mesh as _mesh
+        fill_kw = dict(mesh_fill) if isinstance(mesh_fill, dict) else dict(max_len=mesh_fill)
+        if set(fill_kw) - {"max_len", "orientation"}:
+            raise ValueError("mesh_fill = %r: a largest loop length or a dict of max_len, orientation" % (mesh_fill,))
+        fill_kw = dict(dict(max_len=64, orientation="holes"), **fill_kw)
+        _mesh.check_fill_args(**fill_kw)
     if min_component is not None:
         from . import components as _components
         _components.check_args(min_component, None, component_connectivity)
@@ -642,9 +668,14 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
     if mesh:
         from . import mesh as _mesh
         res.update(fixThresh_mesh=_mesh.empty_mesh(), adapt_mesh=_mesh.empty_mesh())
+        fkey = "quads" if mesh_fill is None else "faces"        # the faces of the mesh the later stages work on
+        if mesh_fill is not None:
+            for name in ("fixThresh", "adapt"):
+                res[name + "_mesh_filled"] = _filled(_mesh, _mesh.empty_mesh(), fill_kw, (0.0, 0.0, 0.0), 1.0)
         if mesh_smooth is not None:
             for name in ("fixThresh", "adapt"):
-                res[name + "_mesh_smoothed"] = _smoothed(_mesh, _mesh.empty_mesh(), smooth_kw, (0.0, 0.0, 0.0), 1.0)
+                empty = _mesh.empty_mesh() if mesh_fill is None else _work_mesh(res[name + "_mesh_filled"])
+                res[name + "_mesh_smoothed"] = _smoothed(_mesh, empty, smooth_kw, (0.0, 0.0, 0.0), 1.0, fkey)
         if mesh_cell is not None:
             empty = _mesh.empty_mesh()
             for name in ("fixThresh", "adapt"):
@@ -690,15 +721,24 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
                 if rgb is not None:
                     rgb[src < 0] = 0
                 _mesh.save_mesh_2ply("%s%s_mesh.ply" % (mesh_ply_prefix, name), m["vertices"], m["quads"], normal_np=nrm, rgb_np=rgb)
+            if mesh_fill is not None:
+                origin, resol = _mesh.lattice_origin(cube_ijk, out["param_np"], stride_vox)
+                fm = res[name + "_mesh_filled"] = _filled(_mesh, m, fill_kw, origin, resol)
+                m = _work_mesh(fm)                              # (mesh_smooth and mesh_cell below work on this one)
+                if mesh_ply_prefix is not None:
+                    nrm = np.concatenate([nrm, nrm[fm["loop_root"]]])
+                    rgb = None if rgb is None else np.concatenate([rgb, rgb[fm["loop_root"]]])
+                    _mesh.save_mesh_2ply("%s%s_mesh_f%d.ply" % (mesh_ply_prefix, name, int(fill_kw["max_len"])), fm["vertices"], fm["faces"],
+                                         normal_np=nrm, rgb_np=rgb)
             if mesh_smooth is not None:
                 origin, resol = _mesh.lattice_origin(cube_ijk, out["param_np"], stride_vox)
-                m = res[name + "_mesh_smoothed"] = _smoothed(_mesh, m, smooth_kw, origin, resol)      # (mesh_cell below decimates this one)
+                m = res[name + "_mesh_smoothed"] = _smoothed(_mesh, m, smooth_kw, origin, resol, fkey)      # (mesh_cell below decimates this one)
                 if mesh_ply_prefix is not None:
-                    _mesh.save_mesh_2ply("%s%s_mesh_s%d.ply" % (mesh_ply_prefix, name, int(smooth_kw["iterations"])), m["vertices"], m["quads"],
+                    _mesh.save_mesh_2ply("%s%s_mesh_s%d.ply" % (mesh_ply_prefix, name, int(smooth_kw["iterations"])), m["vertices"], m[fkey],
                                          normal_np=nrm, rgb_np=rgb)
             if mesh_cell is not None:
                 origin, resol = _mesh.lattice_origin(cube_ijk, out["param_np"], stride_vox)
-                sm = _mesh.simplify_mesh(m["vert_lattice"], m["quads"], mesh_cell, mesh_placement, origin=origin, resol=resol, vert_src=m["vert_src"])
+                sm = _mesh.simplify_mesh(m["vert_lattice"], m[fkey], mesh_cell, mesh_placement, origin=origin, resol=resol, vert_src=m["vert_src"])
                 res[name + "_mesh_simplified"] = sm
                 if mesh_ply_prefix is not None:
                     _mesh.save_mesh_2ply("%s%s_mesh_c%d.ply" % (mesh_ply_prefix, name, mesh_cell), sm["vertices"], sm["faces"],
