@@ -463,40 +463,70 @@ class Context(object):
             for b in bufs:
                 self.dev_free(b)
 
-    def _sized(self, call, caps):
-        """Runs call(caps, counts) -> status for an entry whose outputs hold caps (a tuple) items and which writes what it needs to counts (as
-        many c_longlong). Outputs that are too short come back as SN_ERR_ARG with the counts needed: one retry at exactly those. Returns the
-        counts as ints."""
-        counts = tuple(ctypes.c_longlong(0) for _ in caps)
-        rc = call(caps, counts)
-        if rc == -1 and any(c.value > cap for c, cap in zip(counts, caps)):
-            rc = call(tuple(c.value for c in counts), counts)
-        _lib.check(rc)
-        return tuple(c.value for c in counts)
-
-    def _sized_outputs(self, run, spec, rows, caps, src=None):
+    def _sized_outputs(self, run, spec, rows, caps, src=None, words=0, sized=()):
         """An entry with sized outputs, in its host form (src None) or its device form (src: the inputs' device pointers): spec = (name, width,
         dtype) of each output in the entry's order, rows(name, sizes) its number of rows when the sizes are caps or counts, run(caps, srcs,
-        outs, counts) -> status the C call. Returns {name: the array at its exact rows}."""
+        outs, counts) -> status the C call. The outputs hold caps (a tuple) items and the entry writes what it needs to counts: one c_longlong
+        per cap, or (words = N) one array of N of which the words `sized` are those, in the caps' order, and which comes back as "counts" (N,)
+        int64. Outputs that are too short come back as SN_ERR_ARG with the counts needed: one retry at exactly those. An entry without caps
+        (caps = sized = ()) has every row known up front. Returns {name: the array at its exact rows}; what the entry leaves unwritten is 0."""
         out = {}
+        counts = (ctypes.c_longlong * (words or len(caps)))()
+        need = lambda: tuple(counts[i] for i in (sized if words else range(len(caps))))
+        ptrs = [counts] if words else [ctypes.pointer(ctypes.c_longlong.from_buffer(counts, 8 * i)) for i in range(len(caps))]
 
-        def call(caps, counts):
+        def call(caps):
             for name, w, dt in spec:
-                out[name] = np.empty((rows(name, caps), w) if w > 1 else (rows(name, caps),), dt)
+                out[name] = np.zeros((rows(name, caps), w) if w > 1 else (rows(name, caps),), dt)
             if src is None:
-                return run(caps, (), [_lib.ptr(out[name]) for name, _, _ in spec], [ctypes.byref(c) for c in counts])
+                return run(caps, (), [_lib.ptr(out[name]) for name, _, _ in spec], ptrs)
             with self._on_device(out.values(), upload=False) as dst:
-                rc = run(caps, src, dst, [ctypes.byref(c) for c in counts])
+                rc = run(caps, src, dst, ptrs)
                 for (name, _, _), b in zip(spec, dst):
-                    r = rows(name, [c.value for c in counts])
+                    r = rows(name, need())
                     if rc == 0 and r:
                         self.d2h(out[name][:r], b)
                 return rc
 
-        counts = self._sized(call, caps)
+        rc = call(caps)
+        if rc == -1 and any(n > cap for n, cap in zip(need(), caps)):
+            rc = call(need())
+        _lib.check(rc)
         for name, _, _ in spec:                      # one by one: each cap-sized array is released before the next copy is made
-            out[name] = out[name][:rows(name, counts)].copy()
+            r = rows(name, need())
+            out[name] = out[name] if r == out[name].shape[0] else out[name][:r].copy()
+        if words:
+            out["counts"] = np.asarray(list(counts), np.int64)
         return out
+
+    def _mesh_stage(self, entry, device, arrays, run, spec, rows, caps, **counts):
+        """A mesh stage on the arrays (verts, faces) of _mesh_arrays: its host form sn_<entry> or, device=True, sn_<entry>_dev on copies staged
+        in device memory here - the same result. run(fn, caps, ins, outs, counts) -> status calls fn, one of the two, on the inputs' pointers;
+        the rest as _sized_outputs takes it."""
+        fn = getattr(self._lib, entry + "_dev" if device else entry)
+        if not device:
+            ins = [_lib.ptr(a) for a in arrays]
+            return self._sized_outputs(lambda caps, _, outs, n: run(fn, caps, ins, outs, n), spec, rows, caps, **counts)
+        with self._on_device(arrays) as src:
+            return self._sized_outputs(lambda caps, ins, outs, n: run(fn, caps, ins, outs, n), spec, rows, caps, src, **counts)
+
+    @staticmethod
+    def _mesh_arrays(verts, faces, nv=None):
+        """-> (verts (V,3) float64, faces (F,nv) int32; nv None: (F,3) or (F,4) as given), both contiguous."""
+        v = np.ascontiguousarray(verts, dtype=np.float64).reshape(-1, 3)
+        f = np.ascontiguousarray(faces, dtype=np.int32)
+        if nv is not None:
+            f = f.reshape(-1, nv)
+        elif f.ndim != 2:
+            raise ValueError("faces must be (F,3) or (F,4), not %r" % (f.shape,))
+        return v, f
+
+    @staticmethod
+    def _on_lattice(cfg, origin, resol):
+        """cfg with its origin[3] / resol filled: the mm position of lattice point 0 and the cell size."""
+        cfg.origin[:] = [float(x) for x in np.asarray(origin, dtype=np.float64).reshape(3)]
+        cfg.resol = float(resol)
+        return cfg
 
     def denoise(self, offsets, ijk, cube_ijk, mask, D_cube, Dc):
         """denoising.denoise_crossCubes (utils/denoising.py:150-184) on packed voxel lists: offsets (n+1,) int64, ijk (T,3) uint8 (each < Dc),
@@ -593,9 +623,7 @@ class Context(object):
         offsets, n, ijk, cube = self._packed(offsets, ijk, cube_ijk)
         nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
         m, T = self._masked(offsets, ijk, mask, nrm)
-        cfg = _lib.MeshCfg(int(radius), int(reach), int(stride_vox))
-        cfg.origin[:] = [float(v) for v in np.asarray(origin, dtype=np.float64).reshape(3)]
-        cfg.resol = float(resol)
+        cfg = self._on_lattice(_lib.MeshCfg(int(radius), int(reach), int(stride_vox)), origin, resol)
         caps = (2 * T + 64, 2 * T + 64) if cap is None else (int(cap[0]), int(cap[1]))
         spec = (("verts_mm", 3, np.float32), ("verts_lattice", 3, np.float64), ("vert_cell", 3, np.int32), ("vert_src", 1, np.int64), ("quads", 4, np.int32))
         rows = lambda name, sizes: sizes[1] if name == "quads" else sizes[0]
@@ -612,19 +640,11 @@ class Context(object):
         sampling density -> (points (M,3) float64, tri (M,) int32 the face of each sample). cap = the samples the first call's arrays hold (a
         guess from the face count when None); a short guess costs one retry with the exact count. device=True stages the mesh in device memory
         here and runs sn_mesh_sample_dev on it: the same result."""
-        v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
-        f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+        v, f = self._mesh_arrays(vertices, faces, 3)
         V, F = v.shape[0], f.shape[0]
-        caps = (16 * F + 64 if cap is None else int(cap),)
-        spec = (("points", 3, np.float64), ("tri", 1, np.int32))
-        rows = lambda name, sizes: sizes[0]
-        if not device:
-            run = lambda caps, _, outs, counts: self._lib.sn_mesh_sample(self._h, V, _lib.ptr(v), F, _lib.ptr(f), float(dst), caps[0], *outs, *counts)
-            out = self._sized_outputs(run, spec, rows, caps)
-        else:
-            run = lambda caps, src, outs, counts: self._lib.sn_mesh_sample_dev(self._h, V, src[0], F, src[1], float(dst), caps[0], *outs, *counts)
-            with self._on_device((v, f)) as src:
-                out = self._sized_outputs(run, spec, rows, caps, src)
+        run = lambda fn, caps, ins, outs, counts: fn(self._h, V, ins[0], F, ins[1], float(dst), caps[0], *outs, *counts)
+        out = self._mesh_stage("sn_mesh_sample", device, (v, f), run, (("points", 3, np.float64), ("tri", 1, np.int32)),
+                               lambda name, sizes: sizes[0], (16 * F + 64 if cap is None else int(cap),))
         return out["points"], out["tri"]
 
     def mesh_simplify(self, verts, faces, cell, placement=0, origin=(0.0, 0.0, 0.0), resol=1.0, cap=None, device=False):
@@ -634,24 +654,15 @@ class Context(object):
         faces (G,3) int32, face_src (G,) int32, vert_cluster (V,) int32. cap = (vertices, faces) the first call's arrays hold (the input's
         counts when None, which always suffice); a short cap costs one retry with the exact counts. device=True stages the mesh in device
         memory here and runs sn_mesh_simplify_dev on it: the same result."""
-        v = np.ascontiguousarray(verts, dtype=np.float64).reshape(-1, 3)
-        f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+        v, f = self._mesh_arrays(verts, faces, 3)
         V, F = v.shape[0], f.shape[0]
-        cfg = _lib.MeshSimplifyCfg(int(cell), int(placement))
-        cfg.origin[:] = [float(x) for x in np.asarray(origin, dtype=np.float64).reshape(3)]
-        cfg.resol = float(resol)
+        cfg = self._on_lattice(_lib.MeshSimplifyCfg(int(cell), int(placement)), origin, resol)
         caps = (min(V, 3 * F), F) if cap is None else (int(cap[0]), int(cap[1]))
         spec = (("verts_mm", 3, np.float32), ("verts_lattice", 3, np.float64), ("vert_rep", 1, np.int32), ("vert_count", 1, np.int32),
                 ("faces", 3, np.int32), ("face_src", 1, np.int32), ("vert_cluster", 1, np.int32))
         rows = lambda name, sizes: V if name == "vert_cluster" else (sizes[1] if name in ("faces", "face_src") else sizes[0])
-        if not device:
-            run = lambda caps, _, outs, counts: self._lib.sn_mesh_simplify(self._h, ctypes.byref(cfg), V, _lib.ptr(v), F, _lib.ptr(f), caps[0], caps[1],
-                                                                           *outs, *counts)
-            return self._sized_outputs(run, spec, rows, caps)
-        run = lambda caps, src, outs, counts: self._lib.sn_mesh_simplify_dev(self._h, ctypes.byref(cfg), V, src[0], F, src[1], caps[0], caps[1],
-                                                                             *outs, *counts)
-        with self._on_device((v, f)) as src:
-            return self._sized_outputs(run, spec, rows, caps, src)
+        run = lambda fn, caps, ins, outs, counts: fn(self._h, ctypes.byref(cfg), V, ins[0], F, ins[1], caps[0], caps[1], *outs, *counts)
+        return self._mesh_stage("sn_mesh_simplify", device, (v, f), run, spec, rows, caps)
 
     def mesh_smooth(self, verts, faces, iterations=10, lam_q16=32768, mu_q16=-34734, boundary=1, origin=(0.0, 0.0, 0.0), resol=1.0, device=False):
         """Taubin smoothing of a mesh in fixed point (sn_mesh_smooth): verts (V,3) float64 in lattice cells, faces (F,3)
@@ -659,28 +670,12 @@ class Context(object):
         Context.mesh takes them. Returns a dict: verts_mm (V,3) float32, verts_lattice (V,3) float64, vert_degree (V,) int32, vert_flags (V,)
         uint8 (1 referenced, 2 boundary vertex, 4 end of a non-manifold edge), counts (4,) int64 = edges, boundary edges, non-manifold edges,
         referenced vertices. device=True stages the mesh in device memory here and runs sn_mesh_smooth_dev on it: the same result."""
-        v = np.ascontiguousarray(verts, dtype=np.float64).reshape(-1, 3)
-        f = np.ascontiguousarray(faces, dtype=np.int32)
-        if f.ndim != 2:
-            raise ValueError("faces must be (F,3) or (F,4), not %r" % (f.shape,))
+        v, f = self._mesh_arrays(verts, faces)
         V, (F, nv) = v.shape[0], f.shape
-        cfg = _lib.MeshSmoothCfg(int(iterations), int(lam_q16), int(mu_q16), int(boundary))
-        cfg.origin[:] = [float(x) for x in np.asarray(origin, dtype=np.float64).reshape(3)]
-        cfg.resol = float(resol)
-        out = dict(verts_mm=np.empty((V, 3), np.float32), verts_lattice=np.empty((V, 3), np.float64), vert_degree=np.empty((V,), np.int32),
-                   vert_flags=np.empty((V,), np.uint8))
-        counts = (ctypes.c_longlong * 4)()
-        if not device:
-            _lib.check(self._lib.sn_mesh_smooth(self._h, ctypes.byref(cfg), V, _lib.ptr(v), F, nv, _lib.ptr(f), *[_lib.ptr(a) for a in out.values()],
-                                                counts))
-        else:
-            with self._on_device((v, f)) as src, self._on_device(out.values(), upload=False) as dst:
-                _lib.check(self._lib.sn_mesh_smooth_dev(self._h, ctypes.byref(cfg), V, src[0], F, nv, src[1], *dst, counts))
-                for a, b in zip(out.values(), dst):
-                    if a.nbytes:
-                        self.d2h(a, b)
-        out["counts"] = np.asarray(list(counts), np.int64)
-        return out
+        cfg = self._on_lattice(_lib.MeshSmoothCfg(int(iterations), int(lam_q16), int(mu_q16), int(boundary)), origin, resol)
+        spec = (("verts_mm", 3, np.float32), ("verts_lattice", 3, np.float64), ("vert_degree", 1, np.int32), ("vert_flags", 1, np.uint8))
+        run = lambda fn, _, ins, outs, counts: fn(self._h, ctypes.byref(cfg), V, ins[0], F, nv, ins[1], *outs, *counts)
+        return self._mesh_stage("sn_mesh_smooth", device, (v, f), run, spec, lambda name, sizes: V, (), words=4)
 
     def mesh_fill(self, verts, faces, max_len=64, orientation=0, origin=(0.0, 0.0, 0.0), resol=1.0, cap=None, device=False):
         """The small holes of a mesh capped by centroid fans (sn_mesh_fill): verts (V,3) float64 in lattice cells, faces
@@ -691,43 +686,16 @@ class Context(object):
         cap = (new vertices, new triangles) the first call's arrays hold (nv * F // 3 and nv * F when None, which always suffice); a short cap
         costs one retry with the exact counts. device=True stages the mesh in device memory here and runs sn_mesh_fill_dev on it: the same
         result."""
-        v = np.ascontiguousarray(verts, dtype=np.float64).reshape(-1, 3)
-        f = np.ascontiguousarray(faces, dtype=np.int32)
-        if f.ndim != 2:
-            raise ValueError("faces must be (F,3) or (F,4), not %r" % (f.shape,))
+        v, f = self._mesh_arrays(verts, faces)
         V, (F, nv) = v.shape[0], f.shape
-        cfg = _lib.MeshFillCfg(int(max_len), int(orientation))
-        cfg.origin[:] = [float(x) for x in np.asarray(origin, dtype=np.float64).reshape(3)]
-        cfg.resol = float(resol)
+        cfg = self._on_lattice(_lib.MeshFillCfg(int(max_len), int(orientation)), origin, resol)
         caps = (nv * F // 3, nv * F) if cap is None else (int(cap[0]), int(cap[1]))
-        counts = (ctypes.c_longlong * 8)()
-
-        def call(caps):
-            H, T = caps
-            out = dict(new_verts_mm=np.empty((H, 3), np.float32), new_verts_lattice=np.empty((H, 3), np.float64), loop_root=np.empty((H,), np.int32),
-                       loop_len=np.empty((H,), np.int32), new_faces=np.empty((T, 3), np.int32), vert_loop=np.zeros((V,), np.uint8))
-            if not device:
-                rc = self._lib.sn_mesh_fill(self._h, ctypes.byref(cfg), V, _lib.ptr(v), F, nv, _lib.ptr(f), H, T, *[_lib.ptr(a) for a in out.values()],
-                                            counts)
-                return rc, out
-            with self._on_device((v, f)) as src, self._on_device(out.values(), upload=False) as dst:
-                rc = self._lib.sn_mesh_fill_dev(self._h, ctypes.byref(cfg), V, src[0], F, nv, src[1], H, T, *dst, counts)
-                if rc == 0 and F:
-                    rows = dict(new_faces=counts[7], vert_loop=V)
-                    for (name, a), b in zip(out.items(), dst):
-                        r = rows.get(name, counts[3])
-                        if r:
-                            self.d2h(a[:r], b)
-            return rc, out
-
-        rc, out = call(caps)
-        if rc == -1 and (counts[3] > caps[0] or counts[7] > caps[1]):
-            rc, out = call((counts[3], counts[7]))
-        _lib.check(rc)
-        H, T = counts[3], counts[7]
-        out = {name: (a if name == "vert_loop" else a[:T if name == "new_faces" else H].copy()) for name, a in out.items()}
-        out["counts"] = np.asarray(list(counts), np.int64)
-        return out
+        spec = (("new_verts_mm", 3, np.float32), ("new_verts_lattice", 3, np.float64), ("loop_root", 1, np.int32), ("loop_len", 1, np.int32),
+                ("new_faces", 3, np.int32), ("vert_loop", 1, np.uint8))
+        rows = lambda name, sizes: V if name == "vert_loop" else (sizes[1] if name == "new_faces" else sizes[0])
+        run = lambda fn, caps, ins, outs, counts: fn(self._h, ctypes.byref(cfg), V, ins[0], F, nv, ins[1], caps[0], caps[1], *outs, *counts)
+        # (no face: either form returns at once and writes nothing, so there is nothing to stage or to copy back)
+        return self._mesh_stage("sn_mesh_fill", device and F > 0, (v, f), run, spec, rows, caps, words=8, sized=(3, 7))
 
     @staticmethod
     def _points(xyz):

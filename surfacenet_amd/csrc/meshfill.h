@@ -87,7 +87,7 @@ static __global__ void __launch_bounds__(MFL_NT) mfl_halfedge_kernel(MsmArgs a, 
     int idx[4];
     for (int k = 0; k < a.nv; ++k) {
         idx[k] = a.faces[(size_t)a.nv * f + k];
-        if (!msm_index_ok(a, idx[k])) return;                   // the build has reported it (and has not entered its sides)
+        if (!mesh_index_ok(idx[k], a.V)) return;                // the build has reported it (and has not entered its sides)
     }
     for (int k = 0; k < a.nv; ++k)
         if (a.vfl[idx[k]] & MSM_BAD) return;

@@ -1,12 +1,14 @@
 // meshsample.h — surface samples of a triangle mesh at a given density, the first step of the DTU protocol for a mesh (sample, reduce,
 // PointCompare; the other two are pointeval.h). DESIGN.md section 4.13 states the contract; tests/meshsample_ref.py restates it in numpy.
-//   count   per face: index and finiteness checks, n = the smallest integer >= 1 with float64(n*n) >= L2 / dst^2, n*n samples
+//   count   per face: index (mesh_input.h) and finiteness checks, n = the smallest integer >= 1 with float64(n*n) >= L2 / dst^2, n*n samples
 //   emit    per sample k of face f: row t = isqrt(k), w = k - t*t, the centroid of sub-triangle (t, w) of the n*n congruent ones
 // Every quantity a decision hangs on is an exact integer (sqrt only estimates, an integer predicate corrects by +-1); the float arithmetic is
 // fp64 with no contraction (the Makefile passes -ffp-contract=off) and IEEE division, so points and tri equal the restatement bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "mesh_input.h"
 
 namespace sn {
 
@@ -15,14 +17,13 @@ constexpr int MSMP_FACES = 8;                            // faces per lane of th
 constexpr int MSMP_ITEMS = 8;                            // samples per lane of the emit kernel
 constexpr int MSMP_RUN = MSMP_NT * MSMP_ITEMS;           // consecutive samples one workgroup owns
 constexpr int MSMP_MAX_N = 32768;                        // n*n <= 2^30: an int32 count, exact in fp64
-constexpr unsigned MSMP_ERR_INDEX = 1, MSMP_ERR_FINITE = 2, MSMP_ERR_N = 4;      // error kinds (bits of MsmpStat::err, low 3 bits of first_bad)
-constexpr unsigned long long MSMP_NO_BAD = ~0ull;
+constexpr unsigned MSMP_ERR_FINITE = 2, MSMP_ERR_N = 4;  // the sampler's own error kinds beside MESH_ERR_INDEX
 
 // What the host reads after the count kernel: 24 bytes.
 struct MsmpStat {
     unsigned long long total;           // sum of n*n over the good faces
-    unsigned long long first_bad;       // min over the bad faces of face * 8 + kind (MSMP_NO_BAD: none)
-    unsigned err, pad;                  // OR of the kinds met
+    unsigned long long first_bad;       // min over the bad faces of mesh_first_bad(face, kind) (MESH_NO_BAD: none)
+    unsigned long long pad;
 };
 
 struct MsmpIn {
@@ -58,7 +59,7 @@ static __global__ void __launch_bounds__(MSMP_NT) msmp_count_kernel(MsmpIn in, i
         unsigned long long cnt = 0;
         unsigned kind = 0;
         const int ia = in.faces[3 * f], ib = in.faces[3 * f + 1], ic = in.faces[3 * f + 2];
-        if (ia < 0 || ia >= in.V || ib < 0 || ib >= in.V || ic < 0 || ic >= in.V) kind = MSMP_ERR_INDEX;
+        if (!mesh_index_ok(ia, in.V) || !mesh_index_ok(ib, in.V) || !mesh_index_ok(ic, in.V)) kind = MESH_ERR_INDEX;
         else {
             double A[3], B[3], C[3];
             bool finite = true;
@@ -82,10 +83,7 @@ static __global__ void __launch_bounds__(MSMP_NT) msmp_count_kernel(MsmpIn in, i
         }
         counts[f] = (int)cnt;
         sum += cnt;
-        if (kind) {
-            atomicOr(&st->err, kind);
-            atomicMin(&st->first_bad, (unsigned long long)f * 8ull + kind);
-        }
+        if (kind) atomicMin(&st->first_bad, mesh_first_bad(f, kind));
     }
     // the total: reduced over the wave, then over the workgroup's waves - one atomic per MSMP_NT * MSMP_FACES faces (a wave's own atomic on
     // the one word would serialise: 16 k of them for a million faces)

@@ -8,7 +8,7 @@
 //             and sends one set of atomics per run
 //   owner     per vertex: the owners (smallest index of a cluster) flag themselves; a scan numbers the clusters by ascending owner
 //   number    per vertex: its cluster's provisional number; the owner records the cluster's slot under that number
-//   facekey   per face: the error checks; three numbers, collapse test, rotation to the smallest number first, lt_key of the triple bid for in
+//   facekey   per face: the error checks (mesh_input.h); three numbers, collapse test, rotation to the smallest number first, lt_key of the triple bid for in
 //             a second owner table with the face index
 //   faceown   per face: a face that owns its key flags itself and marks its three clusters used; two scans number faces and clusters
 //   emit      per used cluster, per owning face, per vertex: the outputs, by plain stores
@@ -19,22 +19,20 @@
 #include <stdint.h>
 
 #include "lattice_table.h"
+#include "mesh_input.h"
 
 namespace sn {
 
 constexpr int MSIM_NT = 256;
 constexpr int MSIM_FIX = 256;                             // fixed point: q = rint(v * 256)
 constexpr long long MSIM_BIAS = 4 * MSIM_FIX;             // 4 cells: the mesher's vertices go down to about -1, cluster cells stay >= 0
-constexpr double MSIM_LO = -4.0, MSIM_HI = 2097144.0;     // a referenced coordinate: -4 <= v < 2^21 - 8 (the mesher's own range)
 constexpr int MSIM_MAX_CLUSTERS = 1 << LT_AXIS_BITS;      // a face key packs three cluster numbers of 21 bits
 constexpr int MSIM_NONE = -1, MSIM_MARK = -2, MSIM_BAD = -3;      // MsimArgs::vnum before a vertex has a slot / number
-constexpr unsigned MSIM_ERR_INDEX = 1, MSIM_ERR_RANGE = 2;        // error kinds (bits of MsimStat::err, low 3 bits of first_bad)
-constexpr unsigned long long MSIM_NO_BAD = ~0ull;
 
 // What the host reads once, after the counting kernels: 24 bytes.
 struct MsimStat {
-    unsigned long long first_bad;       // min over the bad faces of face * 8 + kind (MSIM_NO_BAD: none)
-    unsigned err;                       // OR of the kinds met
+    unsigned long long first_bad;       // min over the bad faces of mesh_first_bad(face, kind) (MESH_NO_BAD: none)
+    unsigned pad;
     int P, C, G;                        // clusters, output vertices, output faces
 };
 
@@ -62,14 +60,12 @@ struct MsimArgs {
     float *verts_mm; double *verts_lattice; int32_t *vert_rep, *vert_count, *faces_out, *face_src, *vert_cluster;
 };
 
-__device__ inline bool msim_index_ok(const MsimArgs &a, int i) { return i >= 0 && i < a.V; }
-
 static __global__ void __launch_bounds__(MSIM_NT) msim_mark_kernel(MsimArgs a)
 {
     const long long f = (long long)blockIdx.x * MSIM_NT + threadIdx.x;
     if (f >= a.F) return;
     const int ia = a.faces[3 * f], ib = a.faces[3 * f + 1], ic = a.faces[3 * f + 2];
-    if (!msim_index_ok(a, ia) || !msim_index_ok(a, ib) || !msim_index_ok(a, ic)) return;      // (facekey reports it)
+    if (!mesh_index_ok(ia, a.V) || !mesh_index_ok(ib, a.V) || !mesh_index_ok(ic, a.V)) return;      // (facekey reports it)
     a.vnum[ia] = MSIM_MARK; a.vnum[ib] = MSIM_MARK; a.vnum[ic] = MSIM_MARK;                  // every writer stores the same value
 }
 
@@ -87,7 +83,7 @@ static __global__ void __launch_bounds__(MSIM_NT) msim_cluster_kernel(MsimArgs a
         bool ok = true;
         for (int d = 0; d < 3; ++d) {
             p[d] = a.verts[3 * v + d];
-            ok = ok && p[d] >= MSIM_LO && p[d] < MSIM_HI;       // (NaN fails)
+            ok = ok && mesh_coord_ok(p[d]);
         }
         if (!ok) a.vnum[v] = MSIM_BAD;
         else {
@@ -164,16 +160,14 @@ static __global__ void __launch_bounds__(MSIM_NT) msim_facekey_kernel(MsimArgs a
     const int ia = a.faces[3 * f], ib = a.faces[3 * f + 1], ic = a.faces[3 * f + 2];
     unsigned kind = 0;
     int t[3] = {0, 0, 0};
-    if (!msim_index_ok(a, ia) || !msim_index_ok(a, ib) || !msim_index_ok(a, ic)) kind = MSIM_ERR_INDEX;
+    if (!mesh_index_ok(ia, a.V) || !mesh_index_ok(ib, a.V) || !mesh_index_ok(ic, a.V)) kind = MESH_ERR_INDEX;
     else {
         t[0] = a.vnum[ia]; t[1] = a.vnum[ib]; t[2] = a.vnum[ic];
-        if (t[0] == MSIM_BAD || t[1] == MSIM_BAD || t[2] == MSIM_BAD) kind = MSIM_ERR_RANGE;
+        if (t[0] == MSIM_BAD || t[1] == MSIM_BAD || t[2] == MSIM_BAD) kind = MESH_ERR_RANGE;
     }
     int slot = -1;
-    if (kind) {
-        atomicOr(&a.st->err, kind);
-        atomicMin(&a.st->first_bad, (unsigned long long)f * 8ull + kind);
-    } else if (a.vpos[a.V] < MSIM_MAX_CLUSTERS && t[0] != t[1] && t[1] != t[2] && t[0] != t[2]) {      // (too many clusters: the host refuses)
+    if (kind) atomicMin(&a.st->first_bad, mesh_first_bad(f, kind));
+    else if (a.vpos[a.V] < MSIM_MAX_CLUSTERS && t[0] != t[1] && t[1] != t[2] && t[0] != t[2]) {      // (too many clusters: the host refuses)
         // the smallest number first, orientation kept
         const int m = t[0] < t[1] ? (t[0] < t[2] ? 0 : 2) : (t[1] < t[2] ? 1 : 2);
         const int r0 = m == 0 ? t[0] : (m == 1 ? t[1] : t[2]);

@@ -3,7 +3,7 @@
 //   mark      per face: the corners of a face with valid indices become referenced
 //   quantise  per referenced vertex: range check, q = rint(v * 65536) into position buffer 0; a wave counts its referenced vertices in a
 //             register over a grid-stride loop and sends one atomic at its end
-//   edges     per face: the error checks; every side with distinct ends claims or finds (min << 28 | max) in an LtPairs table (lattice_table.h)
+//   edges     per face: the error checks (mesh_input.h); every side with distinct ends claims or finds (min << 28 | max) in an LtPairs table (lattice_table.h)
 //             and counts itself in the slot's side counter
 //   degree    per slot (grid-stride): an occupied slot adds 1 to the degree of both ends and ORs the boundary / non-manifold flags into
 //             them; a wave counts its edges, boundary edges and non-manifold edges in registers and touches the global counters once
@@ -20,24 +20,22 @@
 #include <stdint.h>
 
 #include "lattice_table.h"
+#include "mesh_input.h"
 #include "meshsmooth_round.h"
 
 namespace sn {
 
 constexpr int MSM_NT = 256;
-constexpr double MSM_LO = -4.0, MSM_HI = 2097144.0;
 constexpr int MSM_INDEX_BITS = 28;                                // V <= 2^28: an edge key is 56 bits, a neighbour word keeps 4 bits spare
 constexpr unsigned MSM_INDEX_MASK = (1u << MSM_INDEX_BITS) - 1u;
 constexpr unsigned MSM_NBR_BOUNDARY = 1u << 31;                   // neighbour word: the edge to this neighbour is a boundary edge
 constexpr unsigned MSM_REF = 1, MSM_BND = 2, MSM_NONMAN = 4;      // vert_flags
 constexpr unsigned MSM_BAD = 0x80;                                // work flag: a referenced vertex out of range
-constexpr unsigned MSM_ERR_INDEX = 1, MSM_ERR_RANGE = 2;          // error kinds, as meshsimplify.h's: the low 3 bits of first_bad
-constexpr unsigned long long MSM_NONE = ~0ull;
 
 // What the host reads once, after the counting kernels and before any output is touched: 48 bytes.
 struct MsmStat {
-    unsigned long long first_bad;       // min over the bad faces of face * 8 + kind (MSM_NONE: none)
-    unsigned long long bad_vertex;      // min over the vertices whose degree reached MSM_MAX_DEGREE (MSM_NONE: none)
+    unsigned long long first_bad;       // min over the bad faces of mesh_first_bad(face, kind) (MESH_NO_BAD: none)
+    unsigned long long bad_vertex;      // min over the vertices whose degree reached MSM_MAX_DEGREE (MESH_NO_BAD: none)
     unsigned long long counts[4];       // E, boundary edges, non-manifold edges, referenced vertices
 };
 
@@ -60,8 +58,6 @@ struct MsmArgs {
     // outputs (each optional)
     float *verts_mm; double *verts_lattice; int32_t *vert_degree; unsigned char *vert_flags;
 };
-
-__device__ inline bool msm_index_ok(const MsmArgs &a, int i) { return i >= 0 && i < a.V; }
 
 // A position record of REC int64: 3 (24 bytes, the product's: the faster pass on an MI355X, profiles/meshsmooth/) or 4 (32 bytes, two aligned
 // 16-byte halves of one 32-byte sector; the fourth word is padding).
@@ -95,7 +91,7 @@ static __global__ void __launch_bounds__(MSM_NT) msm_mark_kernel(MsmArgs a)
     int idx[4];
     for (int k = 0; k < a.nv; ++k) {
         idx[k] = a.faces[(size_t)a.nv * f + k];
-        if (!msm_index_ok(a, idx[k])) return;                   // (the edge kernel reports it)
+        if (!mesh_index_ok(idx[k], a.V)) return;                // (the edge kernel reports it)
     }
     for (int k = 0; k < a.nv; ++k) a.vfl[idx[k]] = MSM_REF;    // every writer stores the same value
 }
@@ -114,7 +110,7 @@ static __global__ void __launch_bounds__(MSM_NT) msm_quantise_kernel(MsmArgs a)
             bool ok = true;
             for (int d = 0; d < 3; ++d) {
                 const double p = a.verts[3 * v + d];
-                ok = ok && p >= MSM_LO && p < MSM_HI;           // (NaN fails)
+                ok = ok && mesh_coord_ok(p);
                 q[d] = ok ? (long long)rint(p * (double)MSM_FIX) : 0;      // ties to even; exact: |p| < 2^21 leaves 31 bits below the point
             }
             if (!ok) a.vfl[v] = MSM_REF | MSM_BAD;
@@ -133,13 +129,13 @@ static __global__ void __launch_bounds__(MSM_NT) msm_edges_kernel(MsmArgs a)
     unsigned kind = 0;
     for (int k = 0; k < a.nv; ++k) {
         idx[k] = a.faces[(size_t)a.nv * f + k];
-        if (!msm_index_ok(a, idx[k])) kind = MSM_ERR_INDEX;
+        if (!mesh_index_ok(idx[k], a.V)) kind = MESH_ERR_INDEX;
     }
     if (!kind)
         for (int k = 0; k < a.nv; ++k)
-            if (a.vfl[idx[k]] & MSM_BAD) kind = MSM_ERR_RANGE;
+            if (a.vfl[idx[k]] & MSM_BAD) kind = MESH_ERR_RANGE;
     if (kind) {
-        atomicMin(&a.st->first_bad, (unsigned long long)f * 8ull + kind);
+        atomicMin(&a.st->first_bad, mesh_first_bad(f, kind));
         return;
     }
     for (int k = 0; k < a.nv; ++k) {

@@ -40,7 +40,7 @@ int msm_build(sn_ctx *c, const MsmArgs &a, size_t cap)
     const unsigned vb = blocks(V, MSM_NT), fb = blocks(F, MSM_NT), sb = blocks((long long)cap, MSM_NT);
     const unsigned loop_blocks = (unsigned)std::max(c->num_cus, 1) * 8u;      // the grid-stride kernels: eight workgroups per CU at most
     HIPCHK(hipMemsetAsync(a.st, 0, sizeof(MsmStat), c->stream));
-    HIPCHK(hipMemsetAsync(a.st, 0xff, 2 * sizeof(unsigned long long), c->stream));      // first_bad, bad_vertex = MSM_NONE
+    HIPCHK(hipMemsetAsync(a.st, 0xff, 2 * sizeof(unsigned long long), c->stream));      // first_bad, bad_vertex = MESH_NO_BAD
     {
         ProfScope ps(c, "msm_mark", 0, (double)F * nv * 8.0 + (double)V * (28.0 + 8.0 * REC));
         HIPCHK(hipMemsetAsync(a.vfl, 0, sizeof(unsigned) * std::max<size_t>((size_t)V, 1), c->stream));
@@ -74,12 +74,9 @@ int msm_build(sn_ctx *c, const MsmArgs &a, size_t cap)
 // what the status block says of the input, in the words both entries refuse with (SN_OK: nothing)
 inline int msm_report(const MsmStat &st, int V, bool degree_limit)
 {
-    if (st.first_bad != MSM_NONE) {
-        const long long f = (long long)(st.first_bad >> 3);
-        if ((st.first_bad & 7) == MSM_ERR_INDEX) return fail(SN_ERR_ARG, "face %lld names a vertex outside [0, %d)", f, V);
-        return fail(SN_ERR_ARG, "face %lld: a coordinate of one of its vertices is outside [-4, 2^21 - 8) lattice cells (or not a number)", f);
-    }
-    if (degree_limit && st.bad_vertex != MSM_NONE)
+    int rc;
+    if ((rc = mesh_report_bad(st.first_bad, V)) != SN_OK) return rc;
+    if (degree_limit && st.bad_vertex != MESH_NO_BAD)
         return fail(SN_ERR_ARG, "vertex %lld has 2^24 or more edges: at most 2^24 - 1", (long long)st.bad_vertex);
     if ((long long)st.counts[0] >= MSM_MAX_EDGES) return fail(SN_ERR_ARG, "%lld edges: at most 2^30 - 1", (long long)st.counts[0]);
     return SN_OK;

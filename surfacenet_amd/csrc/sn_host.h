@@ -1,6 +1,6 @@
 // sn_host.h — the host plumbing of the C entry points that needs no device: the error text, sizes of hash tables, bump allocation from one
 // buffer (Carve), the plan of a call's host mirror (MirrorPlan: which host array got which region of that buffer), and the argument checks of
-// the packed sparse voxel lists, of the mesh smoother and of the hole filler. Plain C++17, no hip/ include: tests/host/sn_host_check.cpp compiles it alone.
+// the packed sparse voxel lists and of the mesh stages. Plain C++17, no hip/ include: tests/host/sn_host_check.cpp compiles it alone.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/surfacenet_hip.h"
+#include "mesh_input.h"
 
 inline thread_local std::string g_err;   // one per thread for the whole library (C++17 inline variable)
 
@@ -116,37 +117,73 @@ static inline int pl_check_host_ijk(long long total, const unsigned char *ijk, i
     return SN_OK;
 }
 
-// ---- sn_mesh_smooth / sn_mesh_smooth_dev: what of their arguments can be judged without a device (rule 10) ---------------
-static inline int msm_check_args(const sn_mesh_smooth_cfg *cfg, int n_verts, int n_faces, int nv)
+// ---- the mesh stages: what of their arguments can be judged without a device (mesh_input.h) ------------------------
+// An entry tests, in this order: a null cfg; mesh_check_common; its own settings; mesh_check_caps where it has sized outputs. nv = 3 where the
+// entry takes triangles only.
+static inline int mesh_check_common(int n_verts, int n_faces, int nv, const double *origin, double resol)
 {
-    if (!cfg) return fail(SN_ERR_ARG, "null cfg");
     if (n_verts < 0 || n_faces < 0) return fail(SN_ERR_ARG, "n_verts and n_faces must be >= 0");
-    if (n_verts > (1 << 28) || n_faces > (1 << 28))
+    if (n_verts > sn::MESH_MAX_ITEMS || n_faces > sn::MESH_MAX_ITEMS)
         return fail(SN_ERR_ARG, "n_verts = %d, n_faces = %d: at most 2^28 of either", n_verts, n_faces);
     if (nv != 3 && nv != 4) return fail(SN_ERR_ARG, "nv = %d: faces are triangles (3) or quads (4)", nv);
+    if (!std::isfinite(resol) || !(resol > 0)) return fail(SN_ERR_ARG, "resol = %g must be finite and > 0", resol);
+    for (int d = 0; d < 3; ++d)
+        if (!std::isfinite(origin[d])) return fail(SN_ERR_ARG, "origin[%d] = %g is not finite", d, origin[d]);
+    return SN_OK;
+}
+
+static inline int mesh_check_caps(long long cap_verts, long long cap_faces)
+{
+    if (cap_verts < 0 || cap_faces < 0) return fail(SN_ERR_ARG, "cap_verts and cap_faces must be >= 0");
+    return SN_OK;
+}
+
+// the context and the required array of n counts of an entry that returns its counts in one array; the counts are zeroed
+static inline int mesh_check_counts(const void *ctx, long long *counts, int n)
+{
+    if (!ctx) return fail(SN_ERR_ARG, "null context");
+    if (!counts) return fail(SN_ERR_ARG, "counts is required");
+    std::fill(counts, counts + n, 0ll);
+    return SN_OK;
+}
+
+// the refusal a status block's first_bad word asks for (SN_OK: MESH_NO_BAD, no bad face)
+static inline int mesh_report_bad(unsigned long long first_bad, int V)
+{
+    if (first_bad == sn::MESH_NO_BAD) return SN_OK;
+    const long long f = (long long)(first_bad >> 3);
+    if ((first_bad & 7) == sn::MESH_ERR_INDEX) return fail(SN_ERR_ARG, "face %lld names a vertex outside [0, %d)", f, V);
+    return fail(SN_ERR_ARG, "face %lld: a coordinate of one of its vertices is outside [-4, 2^21 - 8) lattice cells (or not a number)", f);
+}
+
+static inline int msim_check_args(const sn_mesh_simplify_cfg *cfg, int n_verts, int n_faces, long long cap_verts, long long cap_faces)
+{
+    int rc;
+    if (!cfg) return fail(SN_ERR_ARG, "null cfg");
+    if ((rc = mesh_check_common(n_verts, n_faces, 3, cfg->origin, cfg->resol)) != SN_OK) return rc;
+    if (cfg->cell < 2 || cfg->cell > 64) return fail(SN_ERR_ARG, "cell = %d: 2 .. 64 lattice cells per axis", cfg->cell);
+    if (cfg->placement != 0 && cfg->placement != 1) return fail(SN_ERR_ARG, "placement = %d: 0 (mean) or 1 (member)", cfg->placement);
+    return mesh_check_caps(cap_verts, cap_faces);
+}
+
+static inline int msm_check_args(const sn_mesh_smooth_cfg *cfg, int n_verts, int n_faces, int nv)
+{
+    int rc;
+    if (!cfg) return fail(SN_ERR_ARG, "null cfg");
+    if ((rc = mesh_check_common(n_verts, n_faces, nv, cfg->origin, cfg->resol)) != SN_OK) return rc;
     if (cfg->iterations < 0 || cfg->iterations > 1000) return fail(SN_ERR_ARG, "iterations = %d: 0 .. 1000", cfg->iterations);
     if (cfg->lam_q16 < -65536 || cfg->lam_q16 > 65536) return fail(SN_ERR_ARG, "lam_q16 = %d: -65536 .. 65536", cfg->lam_q16);
     if (cfg->mu_q16 < -65536 || cfg->mu_q16 > 65536) return fail(SN_ERR_ARG, "mu_q16 = %d: -65536 .. 65536", cfg->mu_q16);
     if (cfg->boundary < 0 || cfg->boundary > 2) return fail(SN_ERR_ARG, "boundary = %d: 0 (fixed), 1 (curve) or 2 (free)", cfg->boundary);
-    if (!std::isfinite(cfg->resol) || !(cfg->resol > 0)) return fail(SN_ERR_ARG, "resol = %g must be finite and > 0", cfg->resol);
-    for (int d = 0; d < 3; ++d)
-        if (!std::isfinite(cfg->origin[d])) return fail(SN_ERR_ARG, "origin[%d] = %g is not finite", d, cfg->origin[d]);
     return SN_OK;
 }
 
-// ---- sn_mesh_fill / sn_mesh_fill_dev: the same for the hole filler; the shared refusals in the smoother's words -------
 static inline int mfl_check_args(const sn_mesh_fill_cfg *cfg, int n_verts, int n_faces, int nv, long long cap_verts, long long cap_faces)
 {
+    int rc;
     if (!cfg) return fail(SN_ERR_ARG, "null cfg");
-    if (n_verts < 0 || n_faces < 0) return fail(SN_ERR_ARG, "n_verts and n_faces must be >= 0");
-    if (n_verts > (1 << 28) || n_faces > (1 << 28))
-        return fail(SN_ERR_ARG, "n_verts = %d, n_faces = %d: at most 2^28 of either", n_verts, n_faces);
-    if (nv != 3 && nv != 4) return fail(SN_ERR_ARG, "nv = %d: faces are triangles (3) or quads (4)", nv);
+    if ((rc = mesh_check_common(n_verts, n_faces, nv, cfg->origin, cfg->resol)) != SN_OK) return rc;
     if (cfg->max_len < 3 || cfg->max_len > 65536) return fail(SN_ERR_ARG, "max_len = %d: 3 .. 65536", cfg->max_len);
     if (cfg->orientation != 0 && cfg->orientation != 1) return fail(SN_ERR_ARG, "orientation = %d: 0 (holes) or 1 (any)", cfg->orientation);
-    if (!std::isfinite(cfg->resol) || !(cfg->resol > 0)) return fail(SN_ERR_ARG, "resol = %g must be finite and > 0", cfg->resol);
-    for (int d = 0; d < 3; ++d)
-        if (!std::isfinite(cfg->origin[d])) return fail(SN_ERR_ARG, "origin[%d] = %g is not finite", d, cfg->origin[d]);
-    if (cap_verts < 0 || cap_faces < 0) return fail(SN_ERR_ARG, "cap_verts and cap_faces must be >= 0");
-    return SN_OK;
+    return mesh_check_caps(cap_verts, cap_faces);
 }

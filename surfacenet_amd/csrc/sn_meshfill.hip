@@ -13,10 +13,8 @@ struct MflOut { float *new_verts_mm; double *new_verts_lattice; int32_t *loop_ro
 
 int mfl_check(sn_ctx *c, const sn_mesh_fill_cfg *cfg, int n_verts, int n_faces, int nv, long long cap_verts, long long cap_faces, long long *counts)
 {
-    if (!c) return fail(SN_ERR_ARG, "null context");
-    if (!counts) return fail(SN_ERR_ARG, "counts is required");
-    for (int k = 0; k < 8; ++k) counts[k] = 0;
-    return mfl_check_args(cfg, n_verts, n_faces, nv, cap_verts, cap_faces);
+    const int rc = mesh_check_counts(c, counts, 8);
+    return rc != SN_OK ? rc : mfl_check_args(cfg, n_verts, n_faces, nv, cap_verts, cap_faces);
 }
 
 // What both forms do once their arguments are checked, F > 0.

@@ -50,10 +50,10 @@ int msmp_run(sn_ctx *c, bool host, int V, const double *verts, int F, const int3
     }
     HIPCHK(hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (st.first_bad != MSMP_NO_BAD) {
+    if (st.first_bad != MESH_NO_BAD) {
         const long long f = (long long)(st.first_bad >> 3);
         const unsigned kind = (unsigned)(st.first_bad & 7);
-        if (kind == MSMP_ERR_INDEX) return fail(SN_ERR_ARG, "face %lld names a vertex outside [0, %d)", f, V);
+        if (kind == MESH_ERR_INDEX) return mesh_report_bad(st.first_bad, V);
         if (kind == MSMP_ERR_FINITE) return fail(SN_ERR_ARG, "face %lld: a coordinate of one of its vertices is not finite", f);
         return fail(SN_ERR_ARG, "face %lld needs more than %d subdivisions at dst = %g", f, MSMP_MAX_N, dst);
     }

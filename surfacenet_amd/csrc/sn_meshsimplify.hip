@@ -6,30 +6,19 @@
 
 namespace {
 
-constexpr int MSIM_MAX_ITEMS = 1 << 28;              // vertices, faces: a table of >= 2 n slots stays within 2^29, n + 1 fits the scan's int
-
 // the caller's outputs: device arrays in the device form, host arrays in the host form
 struct MsimOut {
     float *verts_mm; double *verts_lattice; int32_t *vert_rep, *vert_count, *faces, *face_src, *vert_cluster;
 };
 
-int msim_check_args(sn_ctx *c, const sn_mesh_simplify_cfg *cfg, int n_verts, int n_faces, long long cap_verts, long long cap_faces,
-                    long long *n_out_verts, long long *n_out_faces)
+int msim_check(sn_ctx *c, const sn_mesh_simplify_cfg *cfg, int n_verts, int n_faces, long long cap_verts, long long cap_faces,
+               long long *n_out_verts, long long *n_out_faces)
 {
     if (!c) return fail(SN_ERR_ARG, "null context");
     if (!cfg) return fail(SN_ERR_ARG, "null cfg");
     if (!n_out_verts || !n_out_faces) return fail(SN_ERR_ARG, "n_out_verts and n_out_faces are required");
     *n_out_verts = 0; *n_out_faces = 0;
-    if (n_verts < 0 || n_faces < 0) return fail(SN_ERR_ARG, "n_verts and n_faces must be >= 0");
-    if (n_verts > MSIM_MAX_ITEMS || n_faces > MSIM_MAX_ITEMS)
-        return fail(SN_ERR_ARG, "n_verts = %d, n_faces = %d: at most 2^28 of either", n_verts, n_faces);
-    if (cfg->cell < 2 || cfg->cell > 64) return fail(SN_ERR_ARG, "cell = %d: 2 .. 64 lattice cells per axis", cfg->cell);
-    if (cfg->placement != 0 && cfg->placement != 1) return fail(SN_ERR_ARG, "placement = %d: 0 (mean) or 1 (member)", cfg->placement);
-    if (!std::isfinite(cfg->resol) || !(cfg->resol > 0)) return fail(SN_ERR_ARG, "resol = %g must be finite and > 0", cfg->resol);
-    for (int d = 0; d < 3; ++d)
-        if (!std::isfinite(cfg->origin[d])) return fail(SN_ERR_ARG, "origin[%d] = %g is not finite", d, cfg->origin[d]);
-    if (cap_verts < 0 || cap_faces < 0) return fail(SN_ERR_ARG, "cap_verts and cap_faces must be >= 0");
-    return SN_OK;
+    return msim_check_args(cfg, n_verts, n_faces, cap_verts, cap_faces);
 }
 
 // What both forms do once their arguments are checked: the whole computation on device-resident verts and faces, F > 0. host: the arrays are
@@ -120,11 +109,7 @@ int msim_run(sn_ctx *c, bool host, const sn_mesh_simplify_cfg *cfg, int V, const
     MsimStat st;
     HIPCHK(hipMemcpyAsync(&st, a.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (st.first_bad != MSIM_NO_BAD) {
-        const long long f = (long long)(st.first_bad >> 3);
-        if ((st.first_bad & 7) == MSIM_ERR_INDEX) return fail(SN_ERR_ARG, "face %lld names a vertex outside [0, %d)", f, V);
-        return fail(SN_ERR_ARG, "face %lld: a coordinate of one of its vertices is outside [-4, 2^21 - 8) lattice cells (or not a number)", f);
-    }
+    if ((rc = mesh_report_bad(st.first_bad, V)) != SN_OK) return rc;
     if (st.P >= MSIM_MAX_CLUSTERS)
         return fail(SN_ERR_ARG, "cell = %d gives %d clusters, at most 2^21 - 1 fit a face key: choose a larger cell", cfg->cell, st.P);
     const size_t C = (size_t)st.C, G = (size_t)st.G;
@@ -168,7 +153,7 @@ extern "C" int sn_mesh_simplify_dev(sn_ctx *c, const sn_mesh_simplify_cfg *cfg, 
                                     int32_t *face_src_dev, int32_t *vert_cluster_dev, long long *n_out_verts, long long *n_out_faces)
 {
     int rc;
-    if ((rc = msim_check_args(c, cfg, n_verts, n_faces, cap_verts, cap_faces, n_out_verts, n_out_faces)) != SN_OK) return rc;
+    if ((rc = msim_check(c, cfg, n_verts, n_faces, cap_verts, cap_faces, n_out_verts, n_out_faces)) != SN_OK) return rc;
     if (n_faces > 0 && (!faces_dev || (n_verts > 0 && !verts_dev))) return fail(SN_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(c->device));
     if (n_faces == 0) {                                  // no face: no vertex is referenced
@@ -188,7 +173,7 @@ extern "C" int sn_mesh_simplify(sn_ctx *c, const sn_mesh_simplify_cfg *cfg, int 
                                 long long *n_out_faces)
 {
     int rc;
-    if ((rc = msim_check_args(c, cfg, n_verts, n_faces, cap_verts, cap_faces, n_out_verts, n_out_faces)) != SN_OK) return rc;
+    if ((rc = msim_check(c, cfg, n_verts, n_faces, cap_verts, cap_faces, n_out_verts, n_out_faces)) != SN_OK) return rc;
     if (n_faces > 0 && (!faces || (n_verts > 0 && !verts))) return fail(SN_ERR_ARG, "null argument");
     if (n_faces == 0) {
         if (vert_cluster) std::fill(vert_cluster, vert_cluster + n_verts, (int32_t)-1);

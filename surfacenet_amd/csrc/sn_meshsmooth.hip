@@ -2,7 +2,6 @@
 // host form is the same computation on the host mirror's device copies of its arrays (sn_internal.h HostMirror). The iteration loop is the
 // host's: plain launches on the context's stream, at most 2 * iterations of the pass kernel.
 #include "sn_internal.h"
-#include "meshsmooth.h"
 #include "meshsmooth_build.h"
 #include "scan.h"
 
@@ -13,10 +12,8 @@ struct MsmOut { float *verts_mm; double *verts_lattice; int32_t *vert_degree; un
 
 int msm_check(sn_ctx *c, const sn_mesh_smooth_cfg *cfg, int n_verts, int n_faces, int nv, long long *counts)
 {
-    if (!c) return fail(SN_ERR_ARG, "null context");
-    if (!counts) return fail(SN_ERR_ARG, "counts is required");
-    for (int k = 0; k < 4; ++k) counts[k] = 0;
-    return msm_check_args(cfg, n_verts, n_faces, nv);
+    const int rc = mesh_check_counts(c, counts, 4);
+    return rc != SN_OK ? rc : msm_check_args(cfg, n_verts, n_faces, nv);
 }
 
 // What both forms do once their arguments are checked, V > 0 or F > 0. REC: int64 words per position record (meshsmooth.h).

@@ -85,21 +85,65 @@ def triangulate(quads):
     return np.stack([q[:, [0, 1, 2]], q[:, [0, 2, 3]]], axis=1).reshape(-1, 3)
 
 
-def sample_surface(vertices, faces, dst=0.2):
-    """Surface samples of a mesh at density dst (DESIGN.md section 4.13): vertices (V,3) float32 or float64 (converted to float64 exactly),
-    faces (F,3) triangles or (F,4) quads, which go through triangulate first. -> (points (M,3) float64, tri (M,) int32): every point of a
-    triangle lies within 2/3 dst of one of its samples; tri is the triangle a sample came from (tri // 2 the quad), so the colour or normal
-    of a sample is a gather by the caller. ValueError on bad shapes, dtypes or dst before the library is touched."""
+def _mesh_arrays(vertices, faces, name="vert_lattice"):
+    """-> (vertices, faces) as arrays, as given, or ValueError: `name` must be float32 or float64 (V,3), faces integers (F,3) or (F,4)."""
     v = np.asarray(vertices)
     if v.dtype not in (np.float32, np.float64):
-        raise ValueError("vertices must be float32 or float64, not %s" % v.dtype)
+        raise ValueError("%s must be float32 or float64, not %s" % (name, v.dtype))
     if v.ndim != 2 or v.shape[1] != 3:
-        raise ValueError("vertices must be (V,3), not %r" % (v.shape,))
+        raise ValueError("%s must be (V,3), not %r" % (name, v.shape))
     f = np.asarray(faces)
     if f.ndim != 2 or f.shape[1] not in (3, 4):
         raise ValueError("faces must be (F,3) or (F,4), not %r" % (f.shape,))
     if f.dtype.kind not in "iu":
         raise ValueError("faces must hold integers, not %s" % f.dtype)
+    return v, f
+
+
+def _mesh_args(v, f, origin, resol, vert_src, noun):
+    """What simplify_mesh, smooth_mesh and fill_holes ask of a mesh beyond _mesh_arrays, in the order the three refuse in (their own settings
+    come between the two): origin three finite numbers, resol finite and > 0, at most 2^28 vertices and `noun` ("faces" / "triangles"),
+    vert_src (or None) one entry per vertex, every face index in [0, V), every coordinate of a referenced vertex in [-4, 2^21 - 8) - the
+    first offending face is named, as the library names it. -> (origin (3,) float64, resol, V, F, vert_src as an array or None, referenced
+    (V,) bool - None without faces), or ValueError."""
+    try:
+        o = np.asarray(origin, dtype=np.float64).reshape(-1)
+        r = float(resol)
+    except (TypeError, ValueError):
+        raise ValueError("origin = %r, resol = %r must be numbers" % (origin, resol))
+    if o.shape != (3,) or not np.isfinite(o).all():
+        raise ValueError("origin = %r must be three finite numbers" % (origin,))
+    if not (np.isfinite(r) and r > 0):
+        raise ValueError("resol = %r must be finite and > 0" % (resol,))
+    V, F = v.shape[0], f.shape[0]
+    if V > 1 << 28 or F > 1 << 28:
+        raise ValueError("%d vertices, %d %s: at most 2^28 of either" % (V, F, noun))
+    src = None
+    if vert_src is not None:
+        src = np.asarray(vert_src).reshape(-1)
+        if src.shape[0] != V:
+            raise ValueError("%d vertices, %d entries of vert_src" % (V, src.shape[0]))
+    referenced = None
+    if F:
+        bad = ((f < 0) | (f >= V)).any(axis=1)
+        if bad.any():
+            raise ValueError("face %d names a vertex outside [0, %d)" % (int(np.argmax(bad)), V))
+        referenced = np.zeros((V,), bool)
+        referenced[f.reshape(-1)] = True
+        with np.errstate(invalid="ignore"):
+            out_of_range = referenced & ~((v >= -4.0) & (v < 2097144.0)).all(axis=1)      # (NaN fails)
+        if out_of_range.any():
+            first = int(np.argmax(out_of_range[f].any(axis=1)))
+            raise ValueError("face %d: a coordinate of one of its vertices is outside [-4, 2^21 - 8) lattice cells" % first)
+    return o, r, V, F, src, referenced
+
+
+def sample_surface(vertices, faces, dst=0.2):
+    """Surface samples of a mesh at density dst (DESIGN.md section 4.13): vertices (V,3) float32 or float64 (converted to float64 exactly),
+    faces (F,3) triangles or (F,4) quads, which go through triangulate first. -> (points (M,3) float64, tri (M,) int32): every point of a
+    triangle lies within 2/3 dst of one of its samples; tri is the triangle a sample came from (tri // 2 the quad), so the colour or normal
+    of a sample is a gather by the caller. ValueError on bad shapes, dtypes or dst before the library is touched."""
+    v, f = _mesh_arrays(vertices, faces, "vertices")
     if f.size and (f.min() < -(1 << 31) or f.max() >= 1 << 31):
         raise ValueError("a face index does not fit int32")
     try:
@@ -138,52 +182,16 @@ def simplify_mesh(vert_lattice, faces, cell, placement="mean", origin=(0.0, 0.0,
     input triangle (face_src // 2 the quad), vert_cluster (V,) int32 the output vertex of an input vertex (-1: none); with vert_src (V,) also
     vert_src = vert_src[vert_rep]. Every input vertex with a cluster lies within sqrt(3) cell + 1/256 cells of its output vertex. ValueError
     on bad shapes, dtypes, settings, face indices or coordinates before the library is touched."""
-    v = np.asarray(vert_lattice)
-    if v.dtype not in (np.float32, np.float64):
-        raise ValueError("vert_lattice must be float32 or float64, not %s" % v.dtype)
-    if v.ndim != 2 or v.shape[1] != 3:
-        raise ValueError("vert_lattice must be (V,3), not %r" % (v.shape,))
-    f = np.asarray(faces)
-    if f.ndim != 2 or f.shape[1] not in (3, 4):
-        raise ValueError("faces must be (F,3) or (F,4), not %r" % (f.shape,))
-    if f.dtype.kind not in "iu":
-        raise ValueError("faces must hold integers, not %s" % f.dtype)
+    v, f = _mesh_arrays(vert_lattice, faces)
     k, code = check_simplify_args(cell, placement)
-    try:
-        o = np.asarray(origin, dtype=np.float64).reshape(-1)
-        r = float(resol)
-    except (TypeError, ValueError):
-        raise ValueError("origin = %r, resol = %r must be numbers" % (origin, resol))
-    if o.shape != (3,) or not np.isfinite(o).all():
-        raise ValueError("origin = %r must be three finite numbers" % (origin,))
-    if not (np.isfinite(r) and r > 0):
-        raise ValueError("resol = %r must be finite and > 0" % (resol,))
     if f.shape[1] == 4:
         f = triangulate(f)
-    V, F = v.shape[0], f.shape[0]
-    if V > 1 << 28 or F > 1 << 28:
-        raise ValueError("%d vertices, %d triangles: at most 2^28 of either" % (V, F))
-    src = None
-    if vert_src is not None:
-        src = np.asarray(vert_src).reshape(-1)
-        if src.shape[0] != V:
-            raise ValueError("%d vertices, %d entries of vert_src" % (V, src.shape[0]))
-    if F:
-        bad = ((f < 0) | (f >= V)).any(axis=1)
-        if bad.any():
-            raise ValueError("face %d names a vertex outside [0, %d)" % (int(np.argmax(bad)), V))
-        referenced = np.zeros((V,), bool)
-        referenced[f.reshape(-1)] = True
-        with np.errstate(invalid="ignore"):
-            out_of_range = referenced & ~((v >= -4.0) & (v < 2097144.0)).all(axis=1)      # (NaN fails)
-        if out_of_range.any():
-            first = int(np.argmax(out_of_range[f].any(axis=1)))
-            raise ValueError("face %d: a coordinate of one of its vertices is outside [-4, 2^21 - 8) lattice cells" % first)
-        if int(referenced.sum()) >= 1 << 21:                    # only then can there be 2^21 clusters: count them (a sort of the cell keys)
-            c = (np.rint(v[referenced].astype(np.float64) * 256.0).astype(np.int64) + 1024) // (256 * k)
-            clusters = np.unique((c[:, 0] << 42) | (c[:, 1] << 21) | c[:, 2]).size
-            if clusters >= 1 << 21:
-                raise ValueError("cell = %d gives %d clusters, at most 2^21 - 1: choose a larger cell" % (k, clusters))
+    o, r, V, F, src, referenced = _mesh_args(v, f, origin, resol, vert_src, "triangles")
+    if F and int(referenced.sum()) >= 1 << 21:                  # only then can there be 2^21 clusters: count them (a sort of the cell keys)
+        c = (np.rint(v[referenced].astype(np.float64) * 256.0).astype(np.int64) + 1024) // (256 * k)
+        clusters = np.unique((c[:, 0] << 42) | (c[:, 1] << 21) | c[:, 2]).size
+        if clusters >= 1 << 21:
+            raise ValueError("cell = %d gives %d clusters, at most 2^21 - 1: choose a larger cell" % (k, clusters))
     if F == 0:                                                  # no face, no referenced vertex: nothing for the library to do
         m = dict(verts_mm=np.zeros((0, 3), np.float32), faces=np.zeros((0, 3), np.int32), verts_lattice=np.zeros((0, 3), np.float64),
                  vert_rep=np.zeros((0,), np.int32), vert_count=np.zeros((0,), np.int32), face_src=np.zeros((0,), np.int32),
@@ -231,40 +239,9 @@ def smooth_mesh(vert_lattice, faces, iterations=10, lam=0.5, mu=-0.53, boundary=
     uint8 (1 referenced, 2 boundary vertex, 4 end of a non-manifold edge), n_edges, n_boundary_edges, n_nonmanifold_edges, n_referenced.
     Indices do not change: faces, colours, normals and vert_src carry over. iterations = 0 only reports the topology (n_boundary_edges = 0:
     the mesh is closed). ValueError on bad shapes, dtypes, settings, face indices or coordinates before the library is touched."""
-    v = np.asarray(vert_lattice)
-    if v.dtype not in (np.float32, np.float64):
-        raise ValueError("vert_lattice must be float32 or float64, not %s" % v.dtype)
-    if v.ndim != 2 or v.shape[1] != 3:
-        raise ValueError("vert_lattice must be (V,3), not %r" % (v.shape,))
-    f = np.asarray(faces)
-    if f.ndim != 2 or f.shape[1] not in (3, 4):
-        raise ValueError("faces must be (F,3) or (F,4), not %r" % (f.shape,))
-    if f.dtype.kind not in "iu":
-        raise ValueError("faces must hold integers, not %s" % f.dtype)
+    v, f = _mesh_arrays(vert_lattice, faces)
     n, lam_q16, mu_q16, code = check_smooth_args(iterations, lam, mu, boundary)
-    try:
-        o = np.asarray(origin, dtype=np.float64).reshape(-1)
-        r = float(resol)
-    except (TypeError, ValueError):
-        raise ValueError("origin = %r, resol = %r must be numbers" % (origin, resol))
-    if o.shape != (3,) or not np.isfinite(o).all():
-        raise ValueError("origin = %r must be three finite numbers" % (origin,))
-    if not (np.isfinite(r) and r > 0):
-        raise ValueError("resol = %r must be finite and > 0" % (resol,))
-    V, F = v.shape[0], f.shape[0]
-    if V > 1 << 28 or F > 1 << 28:
-        raise ValueError("%d vertices, %d faces: at most 2^28 of either" % (V, F))
-    if F:
-        bad = ((f < 0) | (f >= V)).any(axis=1)
-        if bad.any():
-            raise ValueError("face %d names a vertex outside [0, %d)" % (int(np.argmax(bad)), V))
-        referenced = np.zeros((V,), bool)
-        referenced[f.reshape(-1)] = True
-        with np.errstate(invalid="ignore"):
-            out_of_range = referenced & ~((v >= -4.0) & (v < 2097144.0)).all(axis=1)      # (NaN fails)
-        if out_of_range.any():
-            first = int(np.argmax(out_of_range[f].any(axis=1)))
-            raise ValueError("face %d: a coordinate of one of its vertices is outside [-4, 2^21 - 8) lattice cells" % first)
+    o, r, V, F, _, _ = _mesh_args(v, f, origin, resol, None, "faces")
     if V == 0:
         m = dict(verts_mm=np.zeros((0, 3), np.float32), verts_lattice=np.zeros((0, 3), np.float64), vert_degree=np.zeros((0,), np.int32),
                  vert_flags=np.zeros((0,), np.uint8), counts=np.zeros((4,), np.int64))
@@ -305,45 +282,9 @@ def fill_holes(vert_lattice, faces, max_len=64, orientation="holes", origin=(0.0
     int32, vert_loop (V,) uint8 (0 not on a boundary edge, 1 on a filled loop, 2 on a long loop, 3 on a rim, 4 on a complex component),
     n_edges, n_boundary_edges, n_boundary_components, n_filled, n_long, n_rims, n_complex, n_new_faces; with vert_src (V,) also vert_src
     extended by vert_src[loop_root]. ValueError on bad shapes, dtypes, settings, face indices or coordinates before the library is touched."""
-    v = np.asarray(vert_lattice)
-    if v.dtype not in (np.float32, np.float64):
-        raise ValueError("vert_lattice must be float32 or float64, not %s" % v.dtype)
-    if v.ndim != 2 or v.shape[1] != 3:
-        raise ValueError("vert_lattice must be (V,3), not %r" % (v.shape,))
-    f = np.asarray(faces)
-    if f.ndim != 2 or f.shape[1] not in (3, 4):
-        raise ValueError("faces must be (F,3) or (F,4), not %r" % (f.shape,))
-    if f.dtype.kind not in "iu":
-        raise ValueError("faces must hold integers, not %s" % f.dtype)
+    v, f = _mesh_arrays(vert_lattice, faces)
     n, code = check_fill_args(max_len, orientation)
-    try:
-        o = np.asarray(origin, dtype=np.float64).reshape(-1)
-        r = float(resol)
-    except (TypeError, ValueError):
-        raise ValueError("origin = %r, resol = %r must be numbers" % (origin, resol))
-    if o.shape != (3,) or not np.isfinite(o).all():
-        raise ValueError("origin = %r must be three finite numbers" % (origin,))
-    if not (np.isfinite(r) and r > 0):
-        raise ValueError("resol = %r must be finite and > 0" % (resol,))
-    V, F = v.shape[0], f.shape[0]
-    if V > 1 << 28 or F > 1 << 28:
-        raise ValueError("%d vertices, %d faces: at most 2^28 of either" % (V, F))
-    src = None
-    if vert_src is not None:
-        src = np.asarray(vert_src).reshape(-1)
-        if src.shape[0] != V:
-            raise ValueError("%d vertices, %d entries of vert_src" % (V, src.shape[0]))
-    if F:
-        bad = ((f < 0) | (f >= V)).any(axis=1)
-        if bad.any():
-            raise ValueError("face %d names a vertex outside [0, %d)" % (int(np.argmax(bad)), V))
-        referenced = np.zeros((V,), bool)
-        referenced[f.reshape(-1)] = True
-        with np.errstate(invalid="ignore"):
-            out_of_range = referenced & ~((v >= -4.0) & (v < 2097144.0)).all(axis=1)      # (NaN fails)
-        if out_of_range.any():
-            first = int(np.argmax(out_of_range[f].any(axis=1)))
-            raise ValueError("face %d: a coordinate of one of its vertices is outside [-4, 2^21 - 8) lattice cells" % first)
+    o, r, V, F, src, _ = _mesh_args(v, f, origin, resol, vert_src, "faces")
     v64 = v.astype(np.float64)
     if F == 0:                                                  # no face: no loop, nothing for the library to do
         m = dict(new_verts_mm=np.zeros((0, 3), np.float32), new_verts_lattice=np.zeros((0, 3), np.float64), loop_root=np.zeros((0,), np.int32),

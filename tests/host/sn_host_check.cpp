@@ -1,5 +1,6 @@
 // sn_host_check.cpp — stand-alone check of surfacenet_amd/csrc/sn_host.h, the part of the entry points' host plumbing that needs no device:
-// Carve, MirrorPlan, table_cap and the packed-list checks. tests/test_host_plumbing.py compiles it with a plain host compiler under the address and
+// Carve, MirrorPlan, table_cap, the packed-list checks and the mesh stages' shared checks (mesh_check_common, mesh_check_caps, mesh_report_bad,
+// the simplifier's msim_check_args). tests/test_host_plumbing.py compiles it with a plain host compiler under the address and
 // undefined-behaviour sanitizers and runs it; it prints SN-HOST-CHECK-OK, or the first failed check and exits 1.
 #include "sn_host.h"
 
@@ -283,6 +284,73 @@ static void check_packed_lists()
     CHECK(pl_check_host_ijk(5, ijk, 7) == SN_ERR_ARG && err_is("voxel 2: ijk component 7 >= Dc = 7"));      // a component == Dc
 }
 
+// ---- the mesh stages' shared checks --------------------------------------------------------------------------------------------------------------
+static void check_mesh_stages()
+{
+    using namespace sn;
+    static_assert(MESH_MAX_ITEMS == 1 << 28 && MESH_LO == -4.0 && MESH_HI == 2097144.0 && MESH_ERR_INDEX == 1 && MESH_ERR_RANGE == 2 &&
+                  MESH_NO_BAD == ~0ull && mesh_first_bad(5, MESH_ERR_RANGE) == 42, "the shared input contract");
+    const double origin[3] = {0.0, -20.0, 3.5};
+    g_err = "untouched";
+    CHECK(mesh_check_common(100, 50, 3, origin, 0.4) == SN_OK && mesh_check_common(1 << 28, 1 << 28, 4, origin, 0.4) == SN_OK);
+    CHECK(mesh_check_common(0, 0, 3, origin, 0.4) == SN_OK && mesh_check_caps(0, 0) == SN_OK && mesh_check_caps(1ll << 40, 7) == SN_OK);
+    CHECK(mesh_report_bad(MESH_NO_BAD, 16) == SN_OK);           // the sentinel: no bad face
+    CHECK(err_is("untouched"));
+    CHECK(mesh_check_common(-1, 1, 3, origin, 0.4) == SN_ERR_ARG && err_is("n_verts and n_faces must be >= 0"));
+    CHECK(mesh_check_common((1 << 28) + 1, 1, 3, origin, 0.4) == SN_ERR_ARG && err_is("n_verts = 268435457, n_faces = 1: at most 2^28 of either"));
+    CHECK(mesh_check_common(1, 1, 5, origin, 0.4) == SN_ERR_ARG && err_is("nv = 5: faces are triangles (3) or quads (4)"));
+    CHECK(mesh_check_common(1, 1, 3, origin, 0.0) == SN_ERR_ARG && err_is("resol = 0 must be finite and > 0"));
+    const double bad_origin[3] = {0.0, NAN, 3.5};
+    CHECK(mesh_check_common(1, 1, 3, bad_origin, 0.4) == SN_ERR_ARG && err_is("origin[1] = nan is not finite"));
+    CHECK(mesh_check_common(-1, 1, 5, bad_origin, 0.0) == SN_ERR_ARG && err_is("n_verts and n_faces must be >= 0"));      // the order
+    CHECK(mesh_check_caps(-1, 1) == SN_ERR_ARG && err_is("cap_verts and cap_faces must be >= 0"));
+    CHECK(mesh_check_caps(1, -1) == SN_ERR_ARG && err_is("cap_verts and cap_faces must be >= 0"));
+    long long counts[8] = {5, 5, 5, 5, 5, 5, 5, 5};
+    CHECK(mesh_check_counts(nullptr, counts, 8) == SN_ERR_ARG && err_is("null context") && counts[0] == 5);
+    CHECK(mesh_check_counts(counts, nullptr, 8) == SN_ERR_ARG && err_is("counts is required"));
+    CHECK(mesh_check_counts(counts, counts, 4) == SN_OK && counts[0] == 0 && counts[3] == 0 && counts[4] == 5);
+    static_assert(mesh_index_ok(0, 1) && !mesh_index_ok(1, 1) && !mesh_index_ok(-1, 1) && !mesh_index_ok(0, 0), "an index lies in [0, V)");
+    static_assert(mesh_coord_ok(-4.0) && !mesh_coord_ok(-4.000001) && mesh_coord_ok(2097143.999) && !mesh_coord_ok(2097144.0) && !mesh_coord_ok(NAN),
+                  "a coordinate lies in [-4, 2^21 - 8)");
+
+    // the first bad face a kernel reported: both kinds, the largest face there can be, and the smaller face winning the minimum
+    CHECK(mesh_report_bad(mesh_first_bad(5, MESH_ERR_INDEX), 16) == SN_ERR_ARG && err_is("face 5 names a vertex outside [0, 16)"));
+    CHECK(mesh_report_bad(mesh_first_bad(3, MESH_ERR_RANGE), 16) == SN_ERR_ARG &&
+          err_is("face 3: a coordinate of one of its vertices is outside [-4, 2^21 - 8) lattice cells (or not a number)"));
+    CHECK(mesh_report_bad(mesh_first_bad((1 << 28) - 1, MESH_ERR_INDEX), 1 << 28) == SN_ERR_ARG &&
+          err_is("face 268435455 names a vertex outside [0, 268435456)"));
+    CHECK(mesh_report_bad(mesh_first_bad((1 << 28) - 1, MESH_ERR_RANGE), 1 << 28) == SN_ERR_ARG &&
+          err_is("face 268435455: a coordinate of one of its vertices is outside [-4, 2^21 - 8) lattice cells (or not a number)"));
+    CHECK(mesh_first_bad(2, MESH_ERR_RANGE) < mesh_first_bad(5, MESH_ERR_INDEX) && mesh_first_bad((1 << 28) - 1, 7) < MESH_NO_BAD);
+
+    // the simplifier's arguments: every end of every range is legal, one step beyond is SN_ERR_ARG and names the argument
+    const sn_mesh_simplify_cfg ok = {8, 0, {0.0, -20.0, 3.5}, 0.4};
+    CHECK(msim_check_args(&ok, 100, 50, 100, 50) == SN_OK && msim_check_args(&ok, 1 << 28, 1 << 28, 0, 0) == SN_OK);
+    CHECK(msim_check_args(&ok, 0, 0, 0, 0) == SN_OK);
+    CHECK(msim_check_args(nullptr, 1, 1, 1, 1) == SN_ERR_ARG && err_is("null cfg"));
+    auto refused = [&](sn_mesh_simplify_cfg c, int V, int F, long long cv, long long cf, const char *word) {
+        CHECK(msim_check_args(&c, V, F, cv, cf) == SN_ERR_ARG && g_err.find(word) != std::string::npos);
+    };
+    refused(ok, (1 << 28) + 1, 1, 1, 1, "n_verts"); refused(ok, 1, (1 << 28) + 1, 1, 1, "n_faces");
+    refused(ok, -1, 1, 1, 1, "n_verts"); refused(ok, 1, -1, 1, 1, "n_faces");
+    refused(ok, 1, 1, -1, 1, "cap_verts"); refused(ok, 1, 1, 1, -1, "cap_faces");
+    sn_mesh_simplify_cfg c = ok;
+    c.cell = 2; CHECK(msim_check_args(&c, 8, 4, 8, 4) == SN_OK); c.cell = 64; CHECK(msim_check_args(&c, 8, 4, 8, 4) == SN_OK);
+    c.cell = 1; refused(c, 8, 4, 8, 4, "cell"); c.cell = 65; refused(c, 8, 4, 8, 4, "cell"); c.cell = -8; refused(c, 8, 4, 8, 4, "cell");
+    c = ok; c.placement = 1; CHECK(msim_check_args(&c, 8, 4, 8, 4) == SN_OK);
+    c.placement = 2; refused(c, 8, 4, 8, 4, "placement"); c.placement = -1; refused(c, 8, 4, 8, 4, "placement");
+    c = ok; c.resol = 0.0; refused(c, 8, 4, 8, 4, "resol"); c.resol = -0.4; refused(c, 8, 4, 8, 4, "resol");
+    c.resol = INFINITY; refused(c, 8, 4, 8, 4, "resol"); c.resol = NAN; refused(c, 8, 4, 8, 4, "resol");
+    c = ok; c.origin[1] = NAN; refused(c, 8, 4, 8, 4, "origin[1]"); c = ok; c.origin[2] = -INFINITY; refused(c, 8, 4, 8, 4, "origin[2]");
+    // the shared refusals read as the smoother's and the filler's do
+    const sn_mesh_smooth_cfg s = {1, 0, 0, 1, {0.0, 0.0, 0.0}, 1.0};
+    const sn_mesh_fill_cfg f = {64, 0, {0.0, 0.0, 0.0}, 1.0};
+    CHECK(msm_check_args(&s, (1 << 28) + 1, 1, 3) == SN_ERR_ARG);
+    const std::string words = g_err;
+    CHECK(mfl_check_args(&f, (1 << 28) + 1, 1, 3, 1, 1) == SN_ERR_ARG && g_err == words);
+    CHECK(msim_check_args(&ok, (1 << 28) + 1, 1, 1, 1) == SN_ERR_ARG && g_err == words);
+}
+
 int main()
 {
     for (size_t n : {(size_t)0, (size_t)1, (size_t)1000}) {
@@ -296,6 +364,7 @@ int main()
     check_carve_empty_get();
     check_table_cap();
     check_packed_lists();
+    check_mesh_stages();
     CHECK(round_up(0, 8) == 0 && round_up(1, 8) == 8 && round_up(8, 8) == 8 && round_up(9, 8) == 16);
     CHECK(fail(SN_ERR_STATE, "%s %d", "text", 3) == SN_ERR_STATE && err_is("text 3"));
     printf("SN-HOST-CHECK-OK\n");

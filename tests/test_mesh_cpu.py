@@ -181,3 +181,146 @@ def test_extract_mesh_checks_its_arguments_before_the_library(monkeypatch):
     assert e["vertices"].shape == (0, 3) and e["quads"].shape == (0, 4) and e["vert_src"].shape == (0,) and e["vert_lattice"].shape == (0, 3)
     o, r = mesh.lattice_origin(cube, param, 13)
     assert r == float(np.float64(param["resol"][0])) and np.array_equal(o, param["xyz"][0].astype(np.float64) - (cube[0].astype(np.int64) * 13) * r)
+
+
+def test_the_three_mesh_stages_refuse_a_bad_mesh_in_the_same_words(monkeypatch):
+    """One table of bad arguments through simplify_mesh, smooth_mesh and fill_holes (surfacenet_amd/mesh.py _mesh_arrays, _mesh_args): the
+    same exception text from all three - up to the noun of the 2^28 limit -, raised before the library is touched. The texts are written
+    out as the three said them when each had its own copy of the checks."""
+    import mesh_refusals as bad
+    from surfacenet_amd import mesh, runtime
+
+    def no_library():
+        raise AssertionError("the library was touched")
+    monkeypatch.setattr(runtime, "any_context", no_library)
+    v, f = bad.sheet()
+    v = np.concatenate([v, [[0.0, 0.0, 0.0]]])                  # vertex 16: no face names it
+    assert v.shape == (17, 3) and f.shape == (18, 3)
+    stages = dict(simplify=lambda v, f, **kw: mesh.simplify_mesh(v, f, 2, **kw), smooth=lambda v, f, **kw: mesh.smooth_mesh(v, f, **kw),
+                  fill=lambda v, f, **kw: mesh.fill_holes(v, f, **kw))
+    nouns = dict(simplify="triangles", smooth="faces", fill="faces")
+
+    def refused(text, v, f, only=stages, **kw):
+        for name in only:
+            with pytest.raises(ValueError) as e:
+                stages[name](v, f, **kw)
+            assert str(e.value) == text.replace("NOUN", nouns[name]), name
+
+    def accepted(v, f, **kw):
+        for name, run in stages.items():
+            with pytest.raises(AssertionError, match="library was touched"):
+                run(v, f, **kw)
+
+    accepted(v, f)
+    accepted(v.astype(np.float32), f.astype(np.int64), origin=(-20.0, 3.0, 0.5), resol=0.4)
+    refused("vert_lattice must be float32 or float64, not int32", v.astype(np.int32), f)
+    refused("vert_lattice must be (V,3), not (17, 2)", v[:, :2], f)
+    refused("faces must be (F,3) or (F,4), not (18, 5)", v, np.zeros((18, 5), np.int32))
+    refused("faces must hold integers, not float64", v, f.astype(np.float64))
+    refused("face 2 names a vertex outside [0, 17)", *bad.bad_index(v, f, 2, 5)[:2])
+    assert bad.bad_index(v, f, 2, 5)[2] == "face 2 names a vertex outside [0, 17)"
+    for value in (np.nan, 2097144.0):
+        far, _, text = bad.bad_coordinate(v, f, 3, value)
+        assert text == "face 3: a coordinate of one of its vertices is outside [-4, 2^21 - 8) lattice cells" and not np.array_equal(far[6], v[6])
+        refused(text, far, f)
+        far = v.copy()
+        far[16] = value                                         # the same on the unreferenced vertex: not looked at
+        accepted(far, f)
+    both = bad.bad_coordinate(*bad.bad_index(v, f, 4, 5)[:2], 3, np.nan)[0]
+    refused("face 4 names a vertex outside [0, 17)", both, bad.bad_index(v, f, 4, 5)[1])      # a bad index anywhere comes before the coordinates
+    refused("origin = (0.0, nan, 0.0) must be three finite numbers", v, f, origin=(0.0, float("nan"), 0.0))
+    refused("origin = (0.0, 1.0) must be three finite numbers", v, f, origin=(0.0, 1.0))
+    refused("resol = 0 must be finite and > 0", v, f, resol=0)
+    refused("origin = 'here', resol = 1.0 must be numbers", v, f, origin="here")
+    refused("17 vertices, 5 entries of vert_src", v, f, only=("simplify", "fill"), vert_src=np.arange(5))
+    many = np.broadcast_to(np.zeros((1, 3), np.int32), ((1 << 28) + 1, 3))      # (no memory behind it: it is refused by its shape)
+    refused("17 vertices, 268435457 NOUN: at most 2^28 of either", v, many)
+    # which refusal wins: the arrays, then the stage's own settings, then origin / resol, then the counts, vert_src, the faces
+    refused("resol = 0 must be finite and > 0", v, many, resol=0)
+    refused("17 vertices, 268435457 NOUN: at most 2^28 of either", v, many, only=("simplify", "fill"), vert_src=np.arange(5))
+    refused("17 vertices, 5 entries of vert_src", *bad.bad_index(v, f, 2, 5)[:2], only=("simplify", "fill"), vert_src=np.arange(5))
+    with pytest.raises(ValueError, match="cell = 1"):
+        mesh.simplify_mesh(v, f, 1, resol=0)
+    with pytest.raises(ValueError, match="iterations"):
+        mesh.smooth_mesh(v, f, iterations=-1, resol=0)
+    with pytest.raises(ValueError, match="max_len"):
+        mesh.fill_holes(v, f, max_len=2, resol=0)
+    with pytest.raises(ValueError, match="faces must hold integers"):
+        mesh.simplify_mesh(v, f.astype(np.float64), 1)
+
+
+def _offline_context():
+    """A Context that was never opened: the library is loaded, the handle is null, and "device memory" is host memory - enough to follow a
+    Context.mesh_* call through _mesh_stage and _sized_outputs up to the entry's first check, with every argument converted."""
+    import contextlib
+    import ctypes
+    from surfacenet_amd import _lib
+    from surfacenet_amd.context import Context
+    ctx = Context.__new__(Context)
+    ctx._lib, ctx._h, ctx._closed = _lib.load(), None, True
+    keep = []
+
+    @contextlib.contextmanager
+    def on_device(arrays, upload=True):
+        keep.append([np.ascontiguousarray(a) for a in arrays])
+        yield [ctypes.c_void_p(a.ctypes.data) for a in keep[-1]]
+    ctx._on_device = on_device
+    ctx.d2h = lambda dst, src: ctypes.memmove(dst.ctypes.data, src, dst.nbytes)
+    return ctx
+
+
+def test_context_mesh_wrappers_reach_their_entries_in_both_forms():
+    """Context.mesh_sample, mesh_simplify, mesh_smooth and mesh_fill, host form and device form, convert every argument and call their entry:
+    with a null context handle each entry refuses at its first check, and says so."""
+    import mesh_refusals as bad
+    from surfacenet_amd import SurfaceNetHipError
+    ctx = _offline_context()
+    v, f = bad.sheet()
+    calls = (lambda d: ctx.mesh_sample(v, f, 0.5, device=d), lambda d: ctx.mesh_simplify(v, f, 2, device=d),
+             lambda d: ctx.mesh_smooth(v, f, 2, device=d), lambda d: ctx.mesh_fill(v, f, device=d), lambda d: ctx.mesh_fill(v, f[:, [0, 1, 2, 2]], device=d))
+    for call in calls:
+        for device in (False, True):
+            with pytest.raises(SurfaceNetHipError, match="null context"):
+                call(device)
+    with pytest.raises(ValueError, match="faces must be"):
+        ctx.mesh_smooth(v, f.reshape(-1))
+
+
+def test_sized_outputs_retries_once_copies_back_and_trims():
+    """Context._sized_outputs against an entry played in Python: caps that suffice, a short cap (one retry at the counts), separate count words
+    and one array of them, the host form and the device form, an entry without caps, a refusal."""
+    import ctypes
+    from surfacenet_amd import SurfaceNetHipError
+    ctx = _offline_context()
+    spec = (("a", 3, np.float32), ("b", 1, np.int32), ("whole", 1, np.uint8))
+    rows = lambda name, sizes: 5 if name == "whole" else sizes[0 if name == "a" else 1]
+    log = []
+
+    def entry(words, na, nb):
+        def run(caps, src, outs, counts):
+            log.append(caps)
+            if words:
+                counts[0][1], counts[0][2] = na, nb
+            else:
+                counts[0][0], counts[1][0] = na, nb
+            if na > caps[0] or nb > caps[1]:
+                return -1
+            for p, arr in zip(outs, (np.arange(3 * na, dtype=np.float32), np.arange(nb, dtype=np.int32) + 7, np.full((5,), 9, np.uint8))):
+                ctypes.memmove(p, arr.ctypes.data, arr.nbytes)
+            return 0
+        return run
+    for words, kw in ((0, {}), (4, dict(words=4, sized=(1, 2)))):
+        for src in (None, ()):
+            for caps, tries in (((6, 8), 1), ((4, 3), 1), ((3, 3), 2), ((0, 0), 2)):
+                del log[:]
+                got = ctx._sized_outputs(entry(words, 4, 3), spec, rows, caps, src, **kw)
+                assert log == [caps, (4, 3)][:tries] and set(got) == {"a", "b", "whole"} | ({"counts"} if words else set())
+                assert np.array_equal(got["a"], np.arange(12, dtype=np.float32).reshape(4, 3)) and got["b"].tolist() == [7, 8, 9]
+                assert got["whole"].tolist() == [9] * 5 and all(a.flags["OWNDATA"] or a.base.shape == a.shape for a in got.values())
+                if words:
+                    assert got["counts"].tolist() == [0, 4, 3, 0] and got["counts"].dtype == np.int64
+    got = ctx._sized_outputs(lambda caps, src, outs, counts: 0, spec[2:], rows, (), words=2)      # no caps: nothing to retry; unwritten is 0
+    assert got["whole"].tolist() == [0] * 5 and got["counts"].tolist() == [0, 0]
+    with pytest.raises(SurfaceNetHipError):
+        ctx._sized_outputs(lambda caps, src, outs, counts: -1, spec, rows, (6, 8))                # SN_ERR_ARG that no count explains
+    assert len(log) <= 2
