@@ -499,10 +499,10 @@ class Context(object):
             out["counts"] = np.asarray(list(counts), np.int64)
         return out
 
-    def _mesh_stage(self, entry, device, arrays, run, spec, rows, caps, **counts):
-        """A mesh stage on the arrays (verts, faces) of _mesh_arrays: its host form sn_<entry> or, device=True, sn_<entry>_dev on copies staged
-        in device memory here - the same result. run(fn, caps, ins, outs, counts) -> status calls fn, one of the two, on the inputs' pointers;
-        the rest as _sized_outputs takes it."""
+    def _host_or_device(self, entry, device, arrays, run, spec, rows, caps, **counts):
+        """An entry with sized outputs on its input arrays (a mesh's verts and faces, packed voxel lists): its host form <entry> or, device=True,
+        <entry>_dev on copies staged in device memory here - the same result. run(fn, caps, ins, outs, counts) -> status calls fn, one of the
+        two, on the inputs' pointers; the rest as _sized_outputs takes it."""
         fn = getattr(self._lib, entry + "_dev" if device else entry)
         if not device:
             ins = [_lib.ptr(a) for a in arrays]
@@ -627,13 +627,9 @@ class Context(object):
         caps = (2 * T + 64, 2 * T + 64) if cap is None else (int(cap[0]), int(cap[1]))
         spec = (("verts_mm", 3, np.float32), ("verts_lattice", 3, np.float64), ("vert_cell", 3, np.int32), ("vert_src", 1, np.int64), ("quads", 4, np.int32))
         rows = lambda name, sizes: sizes[1] if name == "quads" else sizes[0]
-        if not device:
-            run = lambda caps, _, outs, counts: self._lib.sn_mesh(self._h, n, ctypes.byref(cfg), _lib.ptr(offsets), _lib.ptr(ijk), _lib.ptr(cube),
-                                                                  _lib.ptr(m), _lib.ptr(nrm), caps[0], caps[1], *outs, *counts)
-            return self._sized_outputs(run, spec, rows, caps)
-        run = lambda caps, src, outs, counts: self._lib.sn_mesh_dev(self._h, n, ctypes.byref(cfg), T, *src, caps[0], caps[1], *outs, *counts)
-        with self._on_device((offsets, ijk, cube, m, nrm)) as src:
-            return self._sized_outputs(run, spec, rows, caps, src)
+        size = (T,) if device else ()                           # (the device form takes the number of voxels after cfg)
+        run = lambda fn, caps, ins, outs, counts: fn(self._h, n, ctypes.byref(cfg), *size, *ins, caps[0], caps[1], *outs, *counts)
+        return self._host_or_device("sn_mesh", device, (offsets, ijk, cube, m, nrm), run, spec, rows, caps)
 
     def mesh_sample(self, vertices, faces, dst, cap=None, device=False):
         """Surface samples of a triangle mesh (sn_mesh_sample): vertices (V,3) float64, faces (F,3) int32, dst the
@@ -643,7 +639,7 @@ class Context(object):
         v, f = self._mesh_arrays(vertices, faces, 3)
         V, F = v.shape[0], f.shape[0]
         run = lambda fn, caps, ins, outs, counts: fn(self._h, V, ins[0], F, ins[1], float(dst), caps[0], *outs, *counts)
-        out = self._mesh_stage("sn_mesh_sample", device, (v, f), run, (("points", 3, np.float64), ("tri", 1, np.int32)),
+        out = self._host_or_device("sn_mesh_sample", device, (v, f), run, (("points", 3, np.float64), ("tri", 1, np.int32)),
                                lambda name, sizes: sizes[0], (16 * F + 64 if cap is None else int(cap),))
         return out["points"], out["tri"]
 
@@ -662,7 +658,7 @@ class Context(object):
                 ("faces", 3, np.int32), ("face_src", 1, np.int32), ("vert_cluster", 1, np.int32))
         rows = lambda name, sizes: V if name == "vert_cluster" else (sizes[1] if name in ("faces", "face_src") else sizes[0])
         run = lambda fn, caps, ins, outs, counts: fn(self._h, ctypes.byref(cfg), V, ins[0], F, ins[1], caps[0], caps[1], *outs, *counts)
-        return self._mesh_stage("sn_mesh_simplify", device, (v, f), run, spec, rows, caps)
+        return self._host_or_device("sn_mesh_simplify", device, (v, f), run, spec, rows, caps)
 
     def mesh_smooth(self, verts, faces, iterations=10, lam_q16=32768, mu_q16=-34734, boundary=1, origin=(0.0, 0.0, 0.0), resol=1.0, device=False):
         """Taubin smoothing of a mesh in fixed point (sn_mesh_smooth): verts (V,3) float64 in lattice cells, faces (F,3)
@@ -675,7 +671,7 @@ class Context(object):
         cfg = self._on_lattice(_lib.MeshSmoothCfg(int(iterations), int(lam_q16), int(mu_q16), int(boundary)), origin, resol)
         spec = (("verts_mm", 3, np.float32), ("verts_lattice", 3, np.float64), ("vert_degree", 1, np.int32), ("vert_flags", 1, np.uint8))
         run = lambda fn, _, ins, outs, counts: fn(self._h, ctypes.byref(cfg), V, ins[0], F, nv, ins[1], *outs, *counts)
-        return self._mesh_stage("sn_mesh_smooth", device, (v, f), run, spec, lambda name, sizes: V, (), words=4)
+        return self._host_or_device("sn_mesh_smooth", device, (v, f), run, spec, lambda name, sizes: V, (), words=4)
 
     def mesh_fill(self, verts, faces, max_len=64, orientation=0, origin=(0.0, 0.0, 0.0), resol=1.0, cap=None, device=False):
         """The small holes of a mesh capped by centroid fans (sn_mesh_fill): verts (V,3) float64 in lattice cells, faces
@@ -695,7 +691,7 @@ class Context(object):
         rows = lambda name, sizes: V if name == "vert_loop" else (sizes[1] if name == "new_faces" else sizes[0])
         run = lambda fn, caps, ins, outs, counts: fn(self._h, ctypes.byref(cfg), V, ins[0], F, nv, ins[1], caps[0], caps[1], *outs, *counts)
         # (no face: either form returns at once and writes nothing, so there is nothing to stage or to copy back)
-        return self._mesh_stage("sn_mesh_fill", device and F > 0, (v, f), run, spec, rows, caps, words=8, sized=(3, 7))
+        return self._host_or_device("sn_mesh_fill", device and F > 0, (v, f), run, spec, rows, caps, words=8, sized=(3, 7))
 
     @staticmethod
     def _points(xyz):

@@ -6,12 +6,17 @@
     simplify_mesh      the mesh made smaller by vertex clustering on a coarser lattice
     smooth_mesh        the mesh without its staircase: Taubin smoothing in fixed point, and its edge statistics
     fill_holes         the mesh with its small holes capped: boundary loops and centroid fans
+    chain_settings     the checked keywords of the stages that follow extract_mesh in a scene: fill, smooth, decimate
+    run_chain          those stages, each on the result of the one before it
     save_mesh_2ply     binary little-endian PLY of a quad or triangle mesh
+    save_stage_2ply    the same of a stage's mesh, normals and colours gathered through its vert_src (stage_tag: the file's tag)
 
 The reference ends in a point cloud: its utils/mesh_util.py only reads and writes OBJ files. The mesher looks at the scene on the world voxel
 lattice - cell = cube_ijk * stride_vox + vxl_ijk - across cubes, in one GPU call (surfacenet_amd/csrc/mesh.h). Every argument check runs before
 the library is touched.
 """
+import collections
+
 import numpy as np
 
 from . import runtime
@@ -307,6 +312,69 @@ def fill_holes(vert_lattice, faces, max_len=64, orientation="holes", origin=(0.0
     return res
 
 
+# The chain that follows extract_mesh, in its order. A row: the key of the stage's result, reconstruct.scene_postpass's
+# argument, the keyword a bare number stands for, the defaults (their keys are the allowed ones), what a refusal says the argument is, the
+# check of the keywords, the stage, the letter of its PLY file's tag. mesh_cell is a number only: its second keyword is mesh_placement.
+_Stage = collections.namedtuple("_Stage", "key arg first defaults words check run letter")
+_CHAIN = (
+    _Stage("filled", "mesh_fill", "max_len", dict(max_len=64, orientation="holes"), "a largest loop length or a dict of max_len, orientation",
+           check_fill_args, fill_holes, "f"),
+    _Stage("smoothed", "mesh_smooth", "iterations", dict(iterations=10, lam=0.5, mu=-0.53, boundary="curve"),
+           "a number of iterations or a dict of iterations, lam, mu, boundary", check_smooth_args, smooth_mesh, "s"),
+    _Stage("simplified", "mesh_cell", "cell", None, None, check_simplify_args, simplify_mesh, "c"),
+)
+_STAGES = {row.key: row for row in _CHAIN}
+
+
+def _stage_keywords(row, value):
+    """A stage's argument - a number (the row's first keyword) or a dict of keywords - as all of its keywords, or ValueError."""
+    kw = dict(value) if isinstance(value, dict) else {row.first: value}
+    if set(kw) - set(row.defaults):
+        raise ValueError("%s = %r: %s" % (row.arg, value, row.words))
+    return dict(row.defaults, **kw)
+
+
+def chain_settings(mesh_fill=None, mesh_smooth=None, mesh_cell=None, mesh_placement="mean"):
+    """scene_postpass's mesh_fill, mesh_smooth and mesh_cell / mesh_placement -> [(key, keywords), ...]: the stages asked for (not None) in the
+    chain's order - "filled", "smoothed", "simplified" - each with the checked keywords of fill_holes, smooth_mesh, simplify_mesh. ValueError
+    for the first bad argument in the order mesh_cell, mesh_smooth, mesh_fill; the library is not touched."""
+    given = dict(mesh_fill=mesh_fill, mesh_smooth=mesh_smooth, mesh_cell=mesh_cell)
+    stages = []
+    for row in reversed(_CHAIN):
+        value = given[row.arg]
+        if value is not None:
+            kw = dict(cell=value, placement=mesh_placement) if row.defaults is None else _stage_keywords(row, value)
+            row.check(**kw)
+            stages.insert(0, (row.key, kw))
+    return stages
+
+
+def stage_tag(key, kw):
+    """The tag of a chain stage's PLY file, <prefix><name>_mesh<tag>.ply: "_f<max_len>", "_s<iterations>", "_c<cell>"."""
+    return "_%s%d" % (_STAGES[key].letter, int(kw[_STAGES[key].first]))
+
+
+def _faces(m):
+    """A stage's faces: triangles under "faces", or extract_mesh's "quads"."""
+    return m["faces"] if "faces" in m else m["quads"]
+
+
+def run_chain(m, stages, origin, resol):
+    """extract_mesh's dict m (empty_mesh() too) through chain_settings' stages, each on the result of the one before it: fill, smooth,
+    decimate; origin / resol as lattice_origin returns them. -> {key: the stage's result}: fill_holes' and simplify_mesh's dicts as they
+    are, both with vert_src; "smoothed" the mesh that went in - m, or vertices, vert_lattice, faces, vert_src of the filled one - with
+    smooth_mesh's positions and statistics, so it holds quads without a fill and faces after one."""
+    res = {}
+    for key, kw in stages:
+        run = _STAGES[key].run
+        if run is smooth_mesh:                                  # indices stay: the mesh's other keys carry over
+            m = res[key] = dict(m, **run(m["vert_lattice"], _faces(m), origin=origin, resol=resol, **kw))
+        else:                                                   # a new mesh: the next stage reads these four of it
+            res[key] = run(m["vert_lattice"], _faces(m), origin=origin, resol=resol, vert_src=m["vert_src"], **kw)
+            m = {k: res[key][k] for k in ("vertices", "vert_lattice", "faces", "vert_src")}
+    return res
+
+
 def save_mesh_2ply(path, vertices, faces, normal_np=None, rgb_np=None):
     """Binary little-endian PLY: vertices (V,3) float32 x y z [+ nx ny nz float32] [+ red green blue uchar], faces (F,3) or (F,4) as
     `property list uchar int vertex_indices`."""
@@ -344,3 +412,16 @@ def save_mesh_2ply(path, vertices, faces, normal_np=None, rgb_np=None):
         fh.write(("\n".join(header) + "\n").encode("ascii"))
         fh.write(rec.tobytes())
         fh.write(frec.tobytes())
+
+
+def save_stage_2ply(path, m, normal_list, rgb_list=None):
+    """save_mesh_2ply of a stage's mesh m - extract_mesh's dict or one of run_chain's - with the attributes of its vertices: every stage keeps
+    vert_src, so a vertex's normal and colour are row vert_src of the concatenated per-voxel normal_list / rgb_list (None or empty: no
+    colours), and zero where vert_src < 0 (mesh_reach > 0: a vertex with no oriented cell beside it)."""
+    src = m["vert_src"]
+
+    def gather(lists, dtype):
+        a = np.concatenate([np.asarray(x, dtype).reshape(-1, 3) for x in lists])[src]
+        a[src < 0] = 0
+        return a
+    save_mesh_2ply(path, m["vertices"], _faces(m), normal_np=gather(normal_list, np.float32), rgb_np=gather(rgb_list, np.uint8) if rgb_list else None)

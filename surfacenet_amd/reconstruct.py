@@ -563,23 +563,6 @@ def reconstruct_scene(images_list, cameraPOs_np, cubes_param_np, cube_D_mm, cube
     return out
 
 
-def _smoothed(_mesh, m, smooth_kw, origin, resol, fkey="quads"):
-    """extract_mesh's dict m (or the filled mesh, its triangles under fkey = "faces") with the positions smooth_mesh gives its faces, and
-    smooth_mesh's statistics."""
-    s = _mesh.smooth_mesh(m["vert_lattice"], m[fkey], origin=origin, resol=resol, **smooth_kw)
-    return dict(m, vertices=s.pop("vertices"), vert_lattice=s.pop("vert_lattice"), **s)
-
-
-def _filled(_mesh, m, fill_kw, origin, resol):
-    """mesh.fill_holes of extract_mesh's dict m: the triangulated mesh with its small holes capped."""
-    return _mesh.fill_holes(m["vert_lattice"], m["quads"], origin=origin, resol=resol, vert_src=m["vert_src"], **fill_kw)
-
-
-def _work_mesh(fm):
-    """What the stages after the filling read of the filled mesh."""
-    return dict(vertices=fm["vertices"], vert_lattice=fm["vert_lattice"], faces=fm["faces"], vert_src=fm["vert_src"])
-
-
 def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, gamma=0.8, beta=6, N_refine_iter=8, init_probThresh=0.5,
                    max_probThresh=0.9, keep_iterations=False, cameraTs_np=None, cube_overlapping_ratio=0.5, unique=False, mesh=False, mesh_radius=2,
                    mesh_reach=0, mesh_ply_prefix=None, min_component=None, component_connectivity=26, mesh_cell=None, mesh_placement="mean",
@@ -620,33 +603,16 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
         loop root's normal and colour. With mesh_smooth and / or mesh_cell too the order is fill, smooth, decimate, on the FILLED triangle
         mesh: the smoothed dict then holds faces (triangles) in the place of quads."""
     from . import adapthresh, denoising, sparseCubes
+    from . import mesh as _mesh
     from . import normals as _normals
     N_vp = int(N_viewPairs4inference)
     if mesh and cameraTs_np is None:
         raise ValueError("mesh=True needs cameraTs_np: the mesher reads the oriented normals")
-    if mesh_cell is not None:
-        if not mesh:
-            raise ValueError("mesh_cell needs mesh=True: it simplifies the mesh that mesh=True extracts")
-        from . import mesh as _mesh
-        mesh_cell = _mesh.check_simplify_args(mesh_cell, mesh_placement)[0]
-    if mesh_smooth is not None:
-        if not mesh:
-            raise ValueError("mesh_smooth needs mesh=True: it smooths the mesh that mesh=True extracts")
-        from . import mesh as _mesh
-        smooth_kw = dict(mesh_smooth) if isinstance(mesh_smooth, dict) else dict(iterations=mesh_smooth)
-        if set(smooth_kw) - {"iterations", "lam", "mu", "boundary"}:
-            raise ValueError("mesh_smooth = %r: a number of iterations or a dict of iterations, lam, mu, boundary" % (mesh_smooth,))
-        smooth_kw = dict(dict(iterations=10, lam=0.5, mu=-0.53, boundary="curve"), **smooth_kw)
-        _mesh.check_smooth_args(**smooth_kw)
-    if mesh_fill is not None:
-        if not mesh:
-            raise ValueError("mesh_fill needs mesh=True: it fills the holes of the mesh that mesh=True extracts")
-        from . import mesh as _mesh
-        fill_kw = dict(mesh_fill) if isinstance(mesh_fill, dict) else dict(max_len=mesh_fill)
-        if set(fill_kw) - {"max_len", "orientation"}:
-            raise ValueError("mesh_fill = %r: a largest loop length or a dict of max_len, orientation" % (mesh_fill,))
-        fill_kw = dict(dict(max_len=64, orientation="holes"), **fill_kw)
-        _mesh.check_fill_args(**fill_kw)
+    for arg, value, does in (("mesh_cell", mesh_cell, "simplifies"), ("mesh_smooth", mesh_smooth, "smooths"), ("mesh_fill", mesh_fill, "fills the holes of")):
+        if value is not None and not mesh:
+            raise ValueError("%s needs mesh=True: it %s the mesh that mesh=True extracts" % (arg, does))
+    stages = _mesh.chain_settings(mesh_fill, mesh_smooth, mesh_cell, mesh_placement)      # fill, smooth, decimate: those asked for
+    ply_tags = dict([("", "")] + [("_" + key, _mesh.stage_tag(key, kw)) for key, kw in stages])      # result key's ending -> file name's
     if min_component is not None:
         from . import components as _components
         _components.check_args(min_component, None, component_connectivity)
@@ -659,90 +625,47 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
     if keep_iterations:
         res["adapt_iterations"] = dict(thresh=np.zeros((int(N_refine_iter), n)), choice=np.zeros((int(N_refine_iter), n), np.int8),
                                        mask_lists=[], denoised_lists=[])
-    if cameraTs_np is not None:
-        res.update(fixThresh_normal_list=[], adapt_normal_list=[])
-    if unique:
-        res.update(fixThresh_unique_list=[], adapt_unique_list=[])
-    if min_component is not None:
-        res.update(fixThresh_clean_list=[], adapt_clean_list=[])
-    if mesh:
-        from . import mesh as _mesh
-        res.update(fixThresh_mesh=_mesh.empty_mesh(), adapt_mesh=_mesh.empty_mesh())
-        fkey = "quads" if mesh_fill is None else "faces"        # the faces of the mesh the later stages work on
-        if mesh_fill is not None:
-            for name in ("fixThresh", "adapt"):
-                res[name + "_mesh_filled"] = _filled(_mesh, _mesh.empty_mesh(), fill_kw, (0.0, 0.0, 0.0), 1.0)
-        if mesh_smooth is not None:
-            for name in ("fixThresh", "adapt"):
-                empty = _mesh.empty_mesh() if mesh_fill is None else _work_mesh(res[name + "_mesh_filled"])
-                res[name + "_mesh_smoothed"] = _smoothed(_mesh, empty, smooth_kw, (0.0, 0.0, 0.0), 1.0, fkey)
-        if mesh_cell is not None:
-            empty = _mesh.empty_mesh()
-            for name in ("fixThresh", "adapt"):
-                res[name + "_mesh_simplified"] = _mesh.simplify_mesh(empty["vert_lattice"], empty["quads"], mesh_cell, mesh_placement,
-                                                                     vert_src=empty["vert_src"])
-    if n == 0:
-        return res
-    cube_ijk = out["cube_ijk_np"]
-    res["fixThresh_mask_list"] = sparseCubes.filter_voxels(vxl_mask_list=[], prediction_list=pred_l, prob_thresh=tau, rayPooling_votes_list=votes_l,
-                                                           rayPool_thresh=gamma * N_vp * 2)
-    res["fixThresh_denoised_list"] = denoising.denoise_crossCubes(cube_ijk, ijk_l, res["fixThresh_mask_list"], cube_D)
-    a = adapthresh.adapthresh_lists(pred_l, ijk_l, votes_l, cube_ijk, N_refine_iter, cube_Dcenter, init_probThresh, max_probThresh,
-                                    int(round(gamma * N_vp * 2)), beta)
-    off = a["offsets"]
-    split = lambda flat: [x.copy() for x in denoising.split_lists(flat, off)]
-    res["adapt_init_denoised_list"] = split(a["init_denoised"])
-    if N_refine_iter > 0:
-        res.update(adapt_thresh=a["thresh"][-1].copy(), adapt_mask_list=split(a["masks"][-1]), adapt_denoised_list=split(a["denoised"][-1]))
-    else:
-        init_mask = sparseCubes.filter_voxels(vxl_mask_list=[], prediction_list=pred_l, prob_thresh=init_probThresh, rayPooling_votes_list=votes_l,
-                                              rayPool_thresh=int(round(gamma * N_vp * 2)))
-        res.update(adapt_mask_list=init_mask, adapt_denoised_list=res["adapt_init_denoised_list"])
-    if keep_iterations:
-        res["adapt_iterations"] = dict(thresh=a["thresh"], choice=a["choice"], mask_lists=[split(m) for m in a["masks"]],
-                                       denoised_lists=[split(m) for m in a["denoised"]])
+    cube_ijk = out["cube_ijk_np"] if n else None
+    if n:
+        res["fixThresh_mask_list"] = sparseCubes.filter_voxels(vxl_mask_list=[], prediction_list=pred_l, prob_thresh=tau, rayPooling_votes_list=votes_l,
+                                                               rayPool_thresh=gamma * N_vp * 2)
+        res["fixThresh_denoised_list"] = denoising.denoise_crossCubes(cube_ijk, ijk_l, res["fixThresh_mask_list"], cube_D)
+        a = adapthresh.adapthresh_lists(pred_l, ijk_l, votes_l, cube_ijk, N_refine_iter, cube_Dcenter, init_probThresh, max_probThresh,
+                                        int(round(gamma * N_vp * 2)), beta)
+        off = a["offsets"]
+        split = lambda flat: [x.copy() for x in denoising.split_lists(flat, off)]
+        res["adapt_init_denoised_list"] = split(a["init_denoised"])
+        if N_refine_iter > 0:
+            res.update(adapt_thresh=a["thresh"][-1].copy(), adapt_mask_list=split(a["masks"][-1]), adapt_denoised_list=split(a["denoised"][-1]))
+        else:
+            init_mask = sparseCubes.filter_voxels(vxl_mask_list=[], prediction_list=pred_l, prob_thresh=init_probThresh, rayPooling_votes_list=votes_l,
+                                                  rayPool_thresh=int(round(gamma * N_vp * 2)))
+            res.update(adapt_mask_list=init_mask, adapt_denoised_list=res["adapt_init_denoised_list"])
+        if keep_iterations:
+            res["adapt_iterations"] = dict(thresh=a["thresh"], choice=a["choice"], mask_lists=[split(m) for m in a["masks"]],
+                                           denoised_lists=[split(m) for m in a["denoised"]])
+    # the extras of a mask: clean, normals, unique, mesh, chain, PLY files. An empty scene (its dict may lack the cube tables) takes the same
+    # path with empty lists and the empty mesh, which every chain stage passes on without the library; it writes no file.
+    lattice = None
     for name in ("fixThresh", "adapt"):
         masks = res[name + "_denoised_list"]
         if min_component is not None:
             masks = res[name + "_clean_list"] = _components.remove_floaters(cube_ijk, ijk_l, masks, stride_vox, min_cells=min_component,
-                                                                            connectivity=component_connectivity)
+                                                                            connectivity=component_connectivity) if n else []
         if cameraTs_np is not None:
-            res[name + "_normal_list"] = _normals.estimate_normals(cube_ijk, ijk_l, masks, out["param_np"], out["viewPair_np"], cameraTs_np, stride_vox)
+            normal_l = res[name + "_normal_list"] = _normals.estimate_normals(cube_ijk, ijk_l, masks, out["param_np"], out["viewPair_np"],
+                                                                              cameraTs_np, stride_vox) if n else []
         if unique:
-            res[name + "_unique_list"] = _normals.unique_voxels(cube_ijk, ijk_l, masks, stride_vox)
+            res[name + "_unique_list"] = _normals.unique_voxels(cube_ijk, ijk_l, masks, stride_vox) if n else []
         if mesh:
-            m = _mesh.extract_mesh(cube_ijk, ijk_l, masks, res[name + "_normal_list"], out["param_np"], stride_vox, mesh_radius, mesh_reach)
-            res[name + "_mesh"] = m
-            if mesh_ply_prefix is not None:
-                src = m["vert_src"]
-                nrm = np.concatenate([np.asarray(a, np.float32).reshape(-1, 3) for a in res[name + "_normal_list"]])[src]
-                rgb = np.concatenate([np.asarray(a, np.uint8).reshape(-1, 3) for a in out["rgb_list"]])[src] if out.get("rgb_list") else None
-                nrm[src < 0] = 0                     # (mesh_reach > 0: a vertex with no oriented cell beside it: no normal, black)
-                if rgb is not None:
-                    rgb[src < 0] = 0
-                _mesh.save_mesh_2ply("%s%s_mesh.ply" % (mesh_ply_prefix, name), m["vertices"], m["quads"], normal_np=nrm, rgb_np=rgb)
-            if mesh_fill is not None:
-                origin, resol = _mesh.lattice_origin(cube_ijk, out["param_np"], stride_vox)
-                fm = res[name + "_mesh_filled"] = _filled(_mesh, m, fill_kw, origin, resol)
-                m = _work_mesh(fm)                              # (mesh_smooth and mesh_cell below work on this one)
-                if mesh_ply_prefix is not None:
-                    nrm = np.concatenate([nrm, nrm[fm["loop_root"]]])
-                    rgb = None if rgb is None else np.concatenate([rgb, rgb[fm["loop_root"]]])
-                    _mesh.save_mesh_2ply("%s%s_mesh_f%d.ply" % (mesh_ply_prefix, name, int(fill_kw["max_len"])), fm["vertices"], fm["faces"],
-                                         normal_np=nrm, rgb_np=rgb)
-            if mesh_smooth is not None:
-                origin, resol = _mesh.lattice_origin(cube_ijk, out["param_np"], stride_vox)
-                m = res[name + "_mesh_smoothed"] = _smoothed(_mesh, m, smooth_kw, origin, resol, fkey)      # (mesh_cell below decimates this one)
-                if mesh_ply_prefix is not None:
-                    _mesh.save_mesh_2ply("%s%s_mesh_s%d.ply" % (mesh_ply_prefix, name, int(smooth_kw["iterations"])), m["vertices"], m[fkey],
-                                         normal_np=nrm, rgb_np=rgb)
-            if mesh_cell is not None:
-                origin, resol = _mesh.lattice_origin(cube_ijk, out["param_np"], stride_vox)
-                sm = _mesh.simplify_mesh(m["vert_lattice"], m[fkey], mesh_cell, mesh_placement, origin=origin, resol=resol, vert_src=m["vert_src"])
-                res[name + "_mesh_simplified"] = sm
-                if mesh_ply_prefix is not None:
-                    _mesh.save_mesh_2ply("%s%s_mesh_c%d.ply" % (mesh_ply_prefix, name, mesh_cell), sm["vertices"], sm["faces"],
-                                         normal_np=nrm[sm["vert_rep"]], rgb_np=None if rgb is None else rgb[sm["vert_rep"]])
+            m = _mesh.extract_mesh(cube_ijk, ijk_l, masks, normal_l, out["param_np"], stride_vox, mesh_radius, mesh_reach) if n else _mesh.empty_mesh()
+            if n and stages and lattice is None:                # (once: the lattice that extract_mesh has just accepted)
+                lattice = _mesh.lattice_origin(cube_ijk, out["param_np"], stride_vox)
+            chain = _mesh.run_chain(m, stages, *(lattice or ((0.0, 0.0, 0.0), 1.0)))
+            for end, stage_mesh in [("", m)] + [("_" + key, chain[key]) for key in chain]:
+                res[name + "_mesh" + end] = stage_mesh
+                if mesh_ply_prefix is not None and n:
+                    _mesh.save_stage_2ply("%s%s_mesh%s.ply" % (mesh_ply_prefix, name, ply_tags[end]), stage_mesh, normal_l, out.get("rgb_list"))
     return res
 
 

@@ -251,7 +251,7 @@ def test_the_three_mesh_stages_refuse_a_bad_mesh_in_the_same_words(monkeypatch):
 
 def _offline_context():
     """A Context that was never opened: the library is loaded, the handle is null, and "device memory" is host memory - enough to follow a
-    Context.mesh_* call through _mesh_stage and _sized_outputs up to the entry's first check, with every argument converted."""
+    Context.mesh_* call through _host_or_device and _sized_outputs up to the entry's first check, with every argument converted."""
     import contextlib
     import ctypes
     from surfacenet_amd import _lib
@@ -284,6 +284,37 @@ def test_context_mesh_wrappers_reach_their_entries_in_both_forms():
                 call(device)
     with pytest.raises(ValueError, match="faces must be"):
         ctx.mesh_smooth(v, f.reshape(-1))
+
+
+def test_context_mesh_reaches_its_entry_in_both_forms_and_only_the_device_form_takes_T():
+    """Context.mesh on packed lists, host form and device form: every argument is converted and the entry - sn_mesh, sn_mesh_dev - refuses the
+    null context handle at its first check. The two calls differ in one argument: the device form has T, the number of voxels, after cfg."""
+    import ctypes
+    from surfacenet_amd import SurfaceNetHipError
+    ctx = _offline_context()
+    real, calls = ctx._lib, []
+
+    class Spy:
+        def __getattr__(self, name):
+            def entry(*args):
+                calls.append((name, args))
+                return getattr(real, name)(*args)
+            return entry
+    ctx._lib = Spy()
+    s = mr.sheet_scene()
+    T = len(s["ijk"])
+    for device in (False, True):
+        with pytest.raises(SurfaceNetHipError, match="null context"):
+            ctx.mesh(*mr.scene_args(s), radius=2, reach=1, origin=(1.0, 2.0, 3.0), resol=0.4, cap=(7, 9), device=device)
+    (host_name, host), (dev_name, dev) = calls
+    assert (host_name, dev_name) == ("sn_mesh", "sn_mesh_dev") and len(host) == 17 and len(dev) == 18
+    assert dev[3] == T == 25 and dev[:2] == host[:2] == (None, 1)      # handle, n cubes, cfg; then T in the device form alone
+    for cfg in (host[2]._obj, dev[2]._obj):
+        assert (cfg.radius, cfg.reach, cfg.stride_vox, list(cfg.origin), cfg.resol) == (2, 1, 13, [1.0, 2.0, 3.0], 0.4)
+    assert host[8:10] == dev[9:11] == (7, 9)                    # the caps, after the five inputs
+    for a, b in ((host[3:8], dev[4:9]), (host[10:15], dev[11:16])):      # five inputs, five outputs: pointers in both forms
+        assert all(isinstance(p, ctypes.c_void_p) and p.value for p in a + b)
+    assert all(isinstance(p, ctypes.POINTER(ctypes.c_longlong)) for p in host[15:] + dev[16:])
 
 
 def test_sized_outputs_retries_once_copies_back_and_trims():
