@@ -32,7 +32,8 @@ extern "C" {
  * sn_mesh_sample and sn_mesh_sample_dev - surface samples of a triangle mesh; sn_components, sn_components_dev and sn_components_cfg - connected
  * components of the output cloud; sn_mesh_simplify, sn_mesh_simplify_dev and sn_mesh_simplify_cfg - a triangle mesh made smaller by vertex
  * clustering; sn_mesh_smooth, sn_mesh_smooth_dev and sn_mesh_smooth_cfg - Taubin smoothing of a triangle or quad mesh in fixed point, with
- * the mesh's edge and boundary counts; sn_mesh_fill, sn_mesh_fill_dev and sn_mesh_fill_cfg - the mesh's small holes capped by centroid fans. */
+ * the mesh's edge and boundary counts; sn_mesh_fill, sn_mesh_fill_dev and sn_mesh_fill_cfg - the mesh's small holes capped by centroid fans;
+ * sn_mesh_normals and sn_mesh_normals_dev - a mesh's own area-weighted normals with its exact area and volume. */
 
 /* The library is built with -fvisibility=hidden: the functions below are its WHOLE dynamic symbol table
  * (tests/test_abi.py compares `nm -D` with this header). */
@@ -464,6 +465,30 @@ SN_API int sn_mesh_fill_dev(sn_ctx *ctx, const sn_mesh_fill_cfg *cfg, int n_vert
                             const int32_t *faces_dev, long long cap_verts, long long cap_faces, float *new_verts_mm_dev,
                             double *new_verts_lattice_dev, int32_t *loop_root_dev, int32_t *loop_len_dev, int32_t *new_faces_dev,
                             unsigned char *vert_loop_dev, long long *counts);
+
+/* ---- a mesh's own normals, area-weighted, with its exact area and volume --------------------------------------------------
+ * The inputs are sn_mesh_smooth's: verts (n_verts,3) float64 in lattice cells, faces (n_faces,nv) int32 with nv = 3 or 4; referenced vertices and
+ * q = int64(rint(v * 65536)) with its range as there. No origin or cell size: unit normals do not depend on them, and the caller scales the two
+ * measures. Face vector N_f, exact integers below 2^78: a triangle's (q_b - q_a) x (q_c - q_a), a quad's (q_c - q_a) x (q_d - q_b) - the sum of
+ * the vectors of the triangles (a,b,c), (a,c,d). Vertex vector N_v = the sum of N_f over every corner that names the vertex (a face that names
+ * it twice adds twice): area weights, exact. The unit rule, for faces and vertices alike, of an integer triple: m = the largest magnitude; m = 0
+ * gives (0,0,0); else s = max(0, bitlength(m) - 52), the components shifted right by s (floor) are exact float64 x, y, z,
+ * l = sqrt((x*x + y*y) + z*z) in this order without contraction, the normal is float32(x / l), float32(y / l), float32(z / l).
+ * area2 = the sum over the faces of int(rint(l_f)) << s_f, twice the area in units of 2^-32 cell^2, an integer by rule: the sum does not depend
+ * on the order. vol6 = the sum of q_a . (q_b x q_c) over the triangles, a quad's being (a,b,c) and (a,c,d): six times the signed volume in
+ * units of 2^-48 cell^3. Outputs, the two arrays optional (NULL):
+ *   face_normals (n_faces,3) float32; vert_normals (n_verts,3) float32, zero rows for unreferenced vertices;
+ *   counts[4]: faces with N_f = 0, referenced vertices with N_v = 0, referenced vertices, triangles n_faces * (nv - 2);
+ *   sums[6]: area2, then vol6, each three 64-bit limbs, least significant first, two's complement.
+ * n_faces = 0: counts and sums 0, vert_normals all zero, nothing else written. SN_ERR_ARG, nothing written but counts and sums (zeros), in
+ * sn_mesh_smooth's words: a face index outside [0, n_verts) or a referenced coordinate outside the range (or not a number), the text naming the
+ * first offending face; nv not 3 or 4, n_verts or n_faces > 2^28. Every sum is an integer: the result equals the restatement
+ * tests/meshnormals_ref.py bit for bit, on every run. The workspace belongs to the context (grown on demand); both forms return when the work is
+ * done. */
+SN_API int sn_mesh_normals(sn_ctx *ctx, int n_verts, const double *verts, int n_faces, int nv, const int32_t *faces, float *face_normals,
+                           float *vert_normals, long long *counts, unsigned long long *sums);
+SN_API int sn_mesh_normals_dev(sn_ctx *ctx, int n_verts, const double *verts_dev, int n_faces, int nv, const int32_t *faces_dev,
+                               float *face_normals_dev, float *vert_normals_dev, long long *counts, unsigned long long *sums);
 
 /* ---- DTU point-cloud evaluation (experiments/DTU/eval_ply.m -> PointCompareMain of the DTU kit) ----------------------
  * Points are (n,3) float64, row-major, finite. d^2 = (dx*dx + dy*dy) + dz*dz in float64 without contraction: the results are those of the numpy

@@ -693,6 +693,21 @@ class Context(object):
         # (no face: either form returns at once and writes nothing, so there is nothing to stage or to copy back)
         return self._host_or_device("sn_mesh_fill", device and F > 0, (v, f), run, spec, rows, caps, words=8, sized=(3, 7))
 
+    def mesh_normals(self, verts, faces, device=False):
+        """A mesh's own area-weighted normals with its exact area and volume (sn_mesh_normals): verts (V,3) float64 in
+        lattice cells, faces (F,3) or (F,4) int32. Returns a dict: face_normals (F,3) float32, vert_normals (V,3) float32 (zero rows for
+        unreferenced vertices), counts (4,) int64 = faces with a zero vector, referenced vertices with a zero vector, referenced vertices,
+        triangles, sums (6,) uint64 = the limbs of area2, then of vol6, least significant first. device=True stages the mesh in device memory
+        here and runs sn_mesh_normals_dev on it: the same result."""
+        v, f = self._mesh_arrays(verts, faces)
+        V, (F, nv) = v.shape[0], f.shape
+        sums = (ctypes.c_ulonglong * 6)()
+        spec = (("face_normals", 3, np.float32), ("vert_normals", 3, np.float32))
+        run = lambda fn, _, ins, outs, counts: fn(self._h, V, ins[0], F, nv, ins[1], *outs, *counts, sums)
+        out = self._host_or_device("sn_mesh_normals", device, (v, f), run, spec, lambda name, sizes: F if name == "face_normals" else V, (), words=4)
+        out["sums"] = np.asarray(list(sums), np.uint64)
+        return out
+
     @staticmethod
     def _points(xyz):
         return np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))

@@ -178,6 +178,13 @@ static inline int msm_check_args(const sn_mesh_smooth_cfg *cfg, int n_verts, int
     return SN_OK;
 }
 
+// (sn_mesh_normals has no cfg, no lattice and no sized outputs: the counts and nv are all there is to judge)
+static inline int mnr_check_args(int n_verts, int n_faces, int nv)
+{
+    const double origin[3] = {0.0, 0.0, 0.0};
+    return mesh_check_common(n_verts, n_faces, nv, origin, 1.0);
+}
+
 static inline int mfl_check_args(const sn_mesh_fill_cfg *cfg, int n_verts, int n_faces, int nv, long long cap_verts, long long cap_faces)
 {
     int rc;

@@ -6,10 +6,12 @@
     simplify_mesh      the mesh made smaller by vertex clustering on a coarser lattice
     smooth_mesh        the mesh without its staircase: Taubin smoothing in fixed point, and its edge statistics
     fill_holes         the mesh with its small holes capped: boundary loops and centroid fans
+    mesh_normals       the normals of a mesh from the mesh itself, area-weighted, with its exact area and volume
     chain_settings     the checked keywords of the stages that follow extract_mesh in a scene: fill, smooth, decimate
     run_chain          those stages, each on the result of the one before it
     save_mesh_2ply     binary little-endian PLY of a quad or triangle mesh
-    save_stage_2ply    the same of a stage's mesh, normals and colours gathered through its vert_src (stage_tag: the file's tag)
+    save_stage_2ply    the same of a stage's mesh, normals and colours gathered through its vert_src (stage_tag: the file's tag), or with
+                       the mesh's own normals
 
 The reference ends in a point cloud: its utils/mesh_util.py only reads and writes OBJ files. The mesher looks at the scene on the world voxel
 lattice - cell = cube_ijk * stride_vox + vxl_ijk - across cubes, in one GPU call (surfacenet_amd/csrc/mesh.h). Every argument check runs before
@@ -312,6 +314,45 @@ def fill_holes(vert_lattice, faces, max_len=64, orientation="holes", origin=(0.0
     return res
 
 
+NORMAL_COUNTS = ("n_zero_faces", "n_zero_vertices", "n_referenced", "n_triangles")
+NORMAL_SOURCES = ("source", "mesh")
+
+
+def check_normals_arg(normals, name="normals"):
+    """-> normals, one of "source" (a vertex takes its source voxel's normal) or "mesh" (mesh_normals' vert_normals), or ValueError."""
+    if not isinstance(normals, str) or normals not in NORMAL_SOURCES:
+        raise ValueError("%s = %r: 'source' or 'mesh'" % (name, normals))
+    return normals
+
+
+def _limbs(words):
+    """Three 64-bit limbs, least significant first, two's complement -> the Python int."""
+    x = sum(int(w) << (64 * k) for k, w in enumerate(words))
+    return x - (1 << 192) if x >> 191 else x
+
+
+def mesh_normals(vert_lattice, faces, resol=1.0):
+    """The normals of a mesh from the mesh itself, with its exact area and volume: vert_lattice (V,3) float32 or
+    float64 in lattice cells as any stage returns it, faces (F,3) triangles or (F,4) quads - a quad's vector is the sum of its two
+    triangles'. A vertex's normal is the unit vector of the sum of its faces' vectors, once per corner: area weights. -> dict: vert_normals
+    (V,3) float32 (zero for an unreferenced vertex and where the sum is zero), face_normals (F,3) float32, n_zero_faces, n_zero_vertices,
+    n_referenced, n_triangles, area2 and vol6 as Python ints (twice the area in 2^-32 cell^2, six times the signed volume in 2^-48 cell^3:
+    exact, the same for any order of the faces), area = area2 / 2 / 2^32 * resol^2 and volume = vol6 / 6 / 2^48 * resol^3 as floats.
+    ValueError on bad shapes, dtypes, resol, face indices or coordinates before the library is touched."""
+    v, f = _mesh_arrays(vert_lattice, faces)
+    _, r, V, F, _, _ = _mesh_args(v, f, (0.0, 0.0, 0.0), resol, None, "faces")
+    if V == 0 or F == 0:                                        # nothing is referenced: nothing for the library to do
+        m = dict(vert_normals=np.zeros((V, 3), np.float32), face_normals=np.zeros((F, 3), np.float32), counts=np.zeros((4,), np.int64),
+                 sums=np.zeros((6,), np.uint64))
+    else:
+        m = runtime.any_context().mesh_normals(v.astype(np.float64), f.astype(np.int32))
+    res = dict(vert_normals=m["vert_normals"], face_normals=m["face_normals"])
+    res.update({k: int(c) for k, c in zip(NORMAL_COUNTS, m["counts"])})
+    res.update(area2=_limbs(m["sums"][:3]), vol6=_limbs(m["sums"][3:]))
+    res.update(area=res["area2"] / 2 / 2 ** 32 * r ** 2, volume=res["vol6"] / 6 / 2 ** 48 * r ** 3)
+    return res
+
+
 # The chain that follows extract_mesh, in its order (DESIGN.md section 4.19). A row: the key of the stage's result, reconstruct.scene_postpass's
 # argument, the keyword a bare number stands for, the defaults (their keys are the allowed ones), what a refusal says the argument is, the
 # check of the keywords, the stage, the letter of its PLY file's tag. mesh_cell is a number only: its second keyword is mesh_placement.
@@ -414,14 +455,18 @@ def save_mesh_2ply(path, vertices, faces, normal_np=None, rgb_np=None):
         fh.write(frec.tobytes())
 
 
-def save_stage_2ply(path, m, normal_list, rgb_list=None):
+def save_stage_2ply(path, m, normal_list, rgb_list=None, normals="source"):
     """save_mesh_2ply of a stage's mesh m - extract_mesh's dict or one of run_chain's - with the attributes of its vertices: every stage keeps
     vert_src, so a vertex's normal and colour are row vert_src of the concatenated per-voxel normal_list / rgb_list (None or empty: no
-    colours), and zero where vert_src < 0 (mesh_reach > 0: a vertex with no oriented cell beside it)."""
+    colours), and zero where vert_src < 0 (mesh_reach > 0: a vertex with no oriented cell beside it). normals="mesh" writes the mesh's own
+    normals in their place: mesh_normals of the stage's vert_lattice and faces, zero where that is zero; the
+    colours stay gathered. ValueError for any other value before a file is opened."""
+    check_normals_arg(normals)
     src = m["vert_src"]
 
     def gather(lists, dtype):
         a = np.concatenate([np.asarray(x, dtype).reshape(-1, 3) for x in lists])[src]
         a[src < 0] = 0
         return a
-    save_mesh_2ply(path, m["vertices"], _faces(m), normal_np=gather(normal_list, np.float32), rgb_np=gather(rgb_list, np.uint8) if rgb_list else None)
+    nrm = mesh_normals(m["vert_lattice"], _faces(m))["vert_normals"] if normals == "mesh" else gather(normal_list, np.float32)
+    save_mesh_2ply(path, m["vertices"], _faces(m), normal_np=nrm, rgb_np=gather(rgb_list, np.uint8) if rgb_list else None)

@@ -566,7 +566,7 @@ def reconstruct_scene(images_list, cameraPOs_np, cubes_param_np, cube_D_mm, cube
 def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, gamma=0.8, beta=6, N_refine_iter=8, init_probThresh=0.5,
                    max_probThresh=0.9, keep_iterations=False, cameraTs_np=None, cube_overlapping_ratio=0.5, unique=False, mesh=False, mesh_radius=2,
                    mesh_reach=0, mesh_ply_prefix=None, min_component=None, component_connectivity=26, mesh_cell=None, mesh_placement="mean",
-                   mesh_smooth=None, mesh_fill=None):
+                   mesh_smooth=None, mesh_fill=None, mesh_normals="source"):
     """The reconstruction's last two stages on `reconstruct_scene`'s dict, in memory and on the GPU, as the reference runs them on its files:
       * main_reconstruct.py:172-175  thinning masks (prob >= tau, votes >= gamma * N_vp * 2), then denoise_crossCubes with D_cube = cube_D
       * main.py:37-43 -> utils/adapthresh.py  adaptive thresholding with D_cube = cube_Dcenter, init / max threshold init_probThresh /
@@ -601,17 +601,22 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
         most max_len edges capped, a dict of vertices, vert_lattice, faces, vert_src, loop_root, loop_len, vert_loop and the counts; with
         mesh_ply_prefix also written as <prefix>fixThresh_mesh_f<max_len>.ply / <prefix>adapt_mesh_f<max_len>.ply, a new vertex with its
         loop root's normal and colour. With mesh_smooth and / or mesh_cell too the order is fill, smooth, decimate, on the FILLED triangle
-        mesh: the smoothed dict then holds faces (triangles) in the place of quads."""
+        mesh: the smoothed dict then holds faces (triangles) in the place of quads.
+      mesh_normals="mesh" (needs mesh=True; the default "source" adds no key and changes no file): every
+        <name>_mesh* dict also carries vert_normals (V,3) float32, area (mm^2) and volume (mm^3, signed) - mesh.mesh_normals of the stage's
+        vert_lattice and faces with the lattice's resol -, and the PLY files hold those normals in the place of the source voxels'."""
     from . import adapthresh, denoising, sparseCubes
     from . import mesh as _mesh
     from . import normals as _normals
     N_vp = int(N_viewPairs4inference)
     if mesh and cameraTs_np is None:
         raise ValueError("mesh=True needs cameraTs_np: the mesher reads the oriented normals")
-    for arg, value, does in (("mesh_cell", mesh_cell, "simplifies"), ("mesh_smooth", mesh_smooth, "smooths"), ("mesh_fill", mesh_fill, "fills the holes of")):
+    for arg, value, does in (("mesh_cell", mesh_cell, "simplifies"), ("mesh_smooth", mesh_smooth, "smooths"), ("mesh_fill", mesh_fill, "fills the holes of"),
+                             ("mesh_normals", None if mesh_normals == "source" else mesh_normals, "takes its normals from")):
         if value is not None and not mesh:
             raise ValueError("%s needs mesh=True: it %s the mesh that mesh=True extracts" % (arg, does))
     stages = _mesh.chain_settings(mesh_fill, mesh_smooth, mesh_cell, mesh_placement)      # fill, smooth, decimate: those asked for
+    _mesh.check_normals_arg(mesh_normals, "mesh_normals")
     ply_tags = dict([("", "")] + [("_" + key, _mesh.stage_tag(key, kw)) for key, kw in stages])      # result key's ending -> file name's
     if min_component is not None:
         from . import components as _components
@@ -659,13 +664,17 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
             res[name + "_unique_list"] = _normals.unique_voxels(cube_ijk, ijk_l, masks, stride_vox) if n else []
         if mesh:
             m = _mesh.extract_mesh(cube_ijk, ijk_l, masks, normal_l, out["param_np"], stride_vox, mesh_radius, mesh_reach) if n else _mesh.empty_mesh()
-            if n and stages and lattice is None:                # (once: the lattice that extract_mesh has just accepted)
+            if n and (stages or mesh_normals == "mesh") and lattice is None:                # (once: the lattice that extract_mesh has just accepted)
                 lattice = _mesh.lattice_origin(cube_ijk, out["param_np"], stride_vox)
             chain = _mesh.run_chain(m, stages, *(lattice or ((0.0, 0.0, 0.0), 1.0)))
             for end, stage_mesh in [("", m)] + [("_" + key, chain[key]) for key in chain]:
+                if mesh_normals == "mesh":                      # (a copy: a later stage's dict may share this one's arrays, not its keys)
+                    own = _mesh.mesh_normals(stage_mesh["vert_lattice"], _mesh._faces(stage_mesh), resol=lattice[1] if lattice else 1.0)
+                    stage_mesh = dict(stage_mesh, vert_normals=own["vert_normals"], area=own["area"], volume=own["volume"])
                 res[name + "_mesh" + end] = stage_mesh
                 if mesh_ply_prefix is not None and n:
-                    _mesh.save_stage_2ply("%s%s_mesh%s.ply" % (mesh_ply_prefix, name, ply_tags[end]), stage_mesh, normal_l, out.get("rgb_list"))
+                    _mesh.save_stage_2ply("%s%s_mesh%s.ply" % (mesh_ply_prefix, name, ply_tags[end]), stage_mesh, normal_l, out.get("rgb_list"),
+                                          normals=mesh_normals)
     return res
 
 
