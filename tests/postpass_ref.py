@@ -52,11 +52,14 @@ def cube_map(cube_ijk_np, vxl_mask_list):
     return m
 
 
-def denoise_ref(cube_ijk_np, vxl_ijk_list, vxl_mask_list, D_cube, Dc=None):
+def denoise_ref(cube_ijk_np, vxl_ijk_list, vxl_mask_list, D_cube, Dc=None, fault=None):
+    """fault = (c, i, j, k) plants a kernel's slip for tests/test_postpass_cpu.py: cube c's bit row (i, j) loses bit k."""
     Dc = Dc or _dc(vxl_ijk_list)
     mp = cube_map(cube_ijk_np, vxl_mask_list)
     keys = [tuple(k) for k in np.asarray(cube_ijk_np).reshape(-1, 3).tolist()]
     occ = {c: _dense(np.asarray(vxl_ijk_list[c])[np.asarray(vxl_mask_list[c], bool)], Dc) for c in set(mp.values())}
+    if fault is not None:
+        occ[fault[0]][fault[1], fault[2], fault[3]] = False
     h = D_cube // 2
     out = []
     for c, key in enumerate(keys):
@@ -104,8 +107,10 @@ def _half_count(ijk, s, D_cube):
 
 
 def adapthresh_ref(prediction_list, vxl_ijk_list, rayPooling_votes_list, cube_ijk_np, N_refine_iter, D_cube, init_probThresh, max_probThresh,
-                   rayPool_thresh, beta, Dc=None, exact_cost=False):
-    """-> dict(init_denoised, thresh (N,n), masks, denoised (lists per iteration), choice (N,n) int8, cost (N,n,3))"""
+                   rayPool_thresh, beta, Dc=None, exact_cost=False, fault=None):
+    """-> dict(init_denoised, thresh (N,n), masks, denoised (lists per iteration), choice (N,n) int8, cost (N,n,3))
+    fault = (c, g, g_from) plants a kernel's slip for tests/test_postpass_cpu.py: cube c's grid g is built with the threshold of grid g_from,
+    or stays empty (g_from None: a pass that never ran)."""
     Dc = Dc or _dc(vxl_ijk_list)
     n = len(vxl_ijk_list)
     keys = [tuple(k) for k in np.asarray(cube_ijk_np).reshape(-1, 3).tolist()]
@@ -119,6 +124,8 @@ def adapthresh_ref(prediction_list, vxl_ijk_list, rayPooling_votes_list, cube_ij
         def occupied(c, g):
             if (c, g) not in sel:
                 m = masks[c] & (np.asarray(prediction_list[c]) >= t[c] + THRESH_PERTURB[g])
+                if fault is not None and (c, g) == tuple(fault[:2]):
+                    m = m & False if fault[2] is None else masks[c] & (np.asarray(prediction_list[c]) >= t[c] + THRESH_PERTURB[fault[2]])
                 ijk = np.asarray(vxl_ijk_list[c])[m]
                 sel[(c, g)] = (ijk, _dense(ijk, Dc))
             return sel[(c, g)]
@@ -157,8 +164,9 @@ def adapthresh_ref(prediction_list, vxl_ijk_list, rayPooling_votes_list, cube_ij
     return out
 
 
-# ---- tests/golden/postpass_cases.npz (tools/gen_golden_postpass.py) ------------------------------------------------------------------------
+# ---- tests/golden/postpass_cases.npz, postpass_edge_cases.npz (tools/gen_golden_postpass.py) ------------------------------------------------
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "postpass_cases.npz")
+GOLDEN_EDGE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "postpass_edge_cases.npz")
 
 
 def decode_ijk(delta, Dc):
@@ -171,8 +179,17 @@ def split(flat, offsets):
 
 
 def load_cases():
-    """-> (denoise cases {name: dict(cube_ijk, ijk_list, mask_list, D_cube, out_list)}, adapthresh cases {name: dict(...)})"""
-    z = np.load(GOLDEN)
+    """-> (denoise cases {name: dict(cube_ijk, ijk_list, mask_list, D_cube, out_list)}, adapthresh cases {name: dict(...)}) of both files"""
+    dn, at = {}, {}
+    for path in (GOLDEN, GOLDEN_EDGE):
+        d, a = _load(path)
+        assert not (set(d) & set(dn)) and not (set(a) & set(at)), "a case name in both golden files"
+        dn.update(d); at.update(a)
+    return dn, at
+
+
+def _load(path):
+    z = np.load(path)
     dn, at = {}, {}
     names = sorted({k.split("/")[1] for k in z.files if k.startswith("dn/")})
     for nm in names:

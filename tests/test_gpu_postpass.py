@@ -1,11 +1,13 @@
 """GPU (-m gpu): the cross-cube post-pass (surfacenet_amd/csrc/crosscube.h) through the drop-ins denoising.denoise_crossCubes and
 adapthresh.adapthresh and the in-memory reconstruct.scene_postpass: bit-identical to the goldens recorded from the reference
-(tests/golden/postpass_cases.npz), to the CPU restatement (tests/postpass_ref.py) at scale, and to the drop-ins called one by one."""
+(tests/golden/postpass_cases.npz, postpass_edge_cases.npz), to the CPU restatement (tests/postpass_ref.py) at scale and at every cube width
+where the kernels take another path (tests/postpass_cases.py), and to the drop-ins called one by one."""
 import os
 
 import numpy as np
 import pytest
 
+import postpass_cases as cases
 import postpass_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -206,3 +208,99 @@ def test_scene_postpass_equals_dropins_one_by_one(sn, tmp_path):
     _same_lists(post["adapt_mask_list"], post["adapt_iterations"]["mask_lists"][-1])
     assert np.array_equal(post["adapt_thresh"], post["adapt_iterations"]["thresh"][-1])
     sn["runtime"].reset()
+
+
+# ---- the kernel paths that depend on the cube width Dc, and D_cube != Dc (tests/postpass_cases.py) ------------------------------------------
+def _check_case(sn, c):
+    """denoise at the case's D_cube and every result of adapthresh against the restatement, np.array_equal throughout"""
+    d = c["d"]
+    got = sn["denoising"].denoise_crossCubes(d["cube_ijk_np"], d["vxl_ijk_list"], c["masks"], c["D_cube"])
+    assert cases.list_differences(got, c["dn_ref"]) == []
+    r = sn["adapthresh"].adapthresh_lists(*cases.at_args(d, c["D_cube"]))
+    assert cases.adapthresh_differences(r, cases.packed(c["at_ref"])) == []
+
+
+@pytest.mark.parametrize("name", sorted(cases.TABLE))
+def test_edge_case_equals_restatement(sn, name):
+    c = cases.case(name)
+    assert sn["denoising"].pack_lists(c["d"]["vxl_ijk_list"])[2] == c["Dc"]
+    _check_case(sn, c)
+
+
+@pytest.mark.parametrize("name", ["w53", "w64"])
+def test_grid_passes_change_within_one_context(sn, name):
+    """two and three passes of cc_grid_kernel before and after a one-pass call (Dc = 26) in the same context: the work buffers are carved anew"""
+    c, small = cases.case(name), AT["s32"]
+    _check_case(sn, c)
+    r = _at_lists(sn, small)
+    assert np.array_equal(r["thresh"], small["thresh"]) and np.array_equal(r["masks"], small["masks"]) and np.array_equal(r["denoised"], small["denoised"])
+    _check_case(sn, c)
+
+
+def test_many_cubes_second_cube_per_workgroup(sn):
+    """577 cubes on 512 workgroups of cc_denoise_global_kernel, unmapped cubes on either trip; the same bytes from a second call"""
+    c = cases.many_cubes()
+    d = c["d"]
+    want = ref.denoise_ref(d["cube_ijk_np"], d["vxl_ijk_list"], c["masks"], c["D_cube"])
+    got = sn["denoising"].denoise_crossCubes(d["cube_ijk_np"], d["vxl_ijk_list"], c["masks"], c["D_cube"])
+    assert cases.list_differences(got, want) == []
+    assert np.concatenate(want).any() and not any(want[e].any() for e in c["emptied"] + (c["repeated"],))
+    again = sn["denoising"].denoise_crossCubes(d["cube_ijk_np"], d["vxl_ijk_list"], c["masks"], c["D_cube"])
+    assert np.concatenate(again).tobytes() == np.concatenate(got).tobytes()
+
+
+def test_extreme_cube_ijk_does_not_wrap(sn):
+    c = cases.extreme_ijk()
+    d = c["d"]
+    got = sn["denoising"].denoise_crossCubes(d["cube_ijk_np"], d["vxl_ijk_list"], c["masks"], c["D_cube"])
+    assert cases.list_differences(got, ref.denoise_ref(d["cube_ijk_np"], d["vxl_ijk_list"], c["masks"], c["D_cube"])) == []
+    args = cases.at_args(d, c["D_cube"], 1)
+    assert cases.adapthresh_differences(sn["adapthresh"].adapthresh_lists(*args), cases.packed(ref.adapthresh_ref(*args))) == []
+
+
+def test_w64_dev_entries_equal_host_entries(sn):
+    """sn_adapthresh_dev / sn_denoise_dev at Dc = 64 (three grid passes, bit 63) on device arrays give the host forms' results"""
+    import ctypes
+    from surfacenet_amd import _lib
+    ctx = sn["runtime"].any_context()
+    c = cases.case("w64")
+    d = c["d"]
+    host = sn["adapthresh"].adapthresh_lists(*cases.at_args(d, c["D_cube"]))
+    assert cases.adapthresh_differences(host, cases.packed(c["at_ref"])) == []
+    off, ijk, Dc = sn["denoising"].pack_lists(d["vxl_ijk_list"])
+    p16, votes = np.concatenate(d["prediction_list"]).view(np.uint16), np.concatenate(d["rayPooling_votes_list"])
+    T, n, N = ijk.shape[0], len(d["vxl_ijk_list"]), cases.ARGS["N_refine_iter"]
+    assert Dc == 64
+    bufs = []
+
+    def up(a):
+        a = np.ascontiguousarray(a)
+        p = ctx.dev_alloc(max(a.nbytes, 1))
+        bufs.append(p)
+        ctx.h2d(p, a)
+        return p
+
+    def alloc(nbytes):
+        p = ctx.dev_alloc(nbytes)
+        bufs.append(p)
+        return p
+    try:
+        d_off, d_ijk, d_p, d_v, d_cube = up(off), up(ijk), up(p16), up(votes), up(d["cube_ijk_np"].astype(np.uint32))
+        d_init, d_thr, d_m, d_den, d_ch = alloc(T), alloc(8 * N * n), alloc(N * T), alloc(N * T), alloc(N * n)
+        a = cases.ARGS
+        cfg = _lib.AdapthreshCfg(N, c["D_cube"], a["init_probThresh"], a["max_probThresh"], float(a["rayPool_thresh"]), float(a["beta"]))
+        _lib.check(ctx._lib.sn_adapthresh_dev(ctx._h, n, Dc, ctypes.byref(cfg), T, d_off, d_ijk, d_p, d_v, d_cube, d_init, d_thr, d_m, d_den, d_ch))
+        ctx.synchronize()
+        got = dict(init_denoised=np.empty(T, np.uint8), thresh=np.empty((N, n)), masks=np.empty((N, T), np.uint8), denoised=np.empty((N, T), np.uint8),
+                   choice=np.empty((N, n), np.int8))
+        for k, p in (("init_denoised", d_init), ("thresh", d_thr), ("masks", d_m), ("denoised", d_den), ("choice", d_ch)):
+            ctx.d2h(got[k], p)
+            assert np.array_equal(got[k].view(host[k].dtype) if host[k].dtype == bool else got[k], host[k]), k
+        d_mask, d_out = up(np.concatenate(c["masks"]).view(np.uint8)), alloc(T)
+        _lib.check(ctx._lib.sn_denoise_dev(ctx._h, n, Dc, c["D_cube"], T, d_off, d_ijk, d_cube, d_mask, d_out))
+        out = np.empty(T, np.uint8)
+        ctx.d2h(out, d_out)
+        assert np.array_equal(out.view(bool), np.concatenate(c["dn_ref"]))
+    finally:
+        for p in bufs:
+            ctx.dev_free(p)

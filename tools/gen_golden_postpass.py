@@ -1,7 +1,8 @@
-"""Records tests/golden/postpass_cases.npz from the REFERENCE's own cross-cube post-pass (utils/denoising.py, utils/adapthresh.py,
-utils/sparseCubes.py of mjiUST/SurfaceNet), run under Python 3 / numpy 2 in memory:
+"""Records tests/golden/postpass_cases.npz and tests/golden/postpass_edge_cases.npz (the cases of tests/postpass_cases.py) from the REFERENCE's
+own cross-cube post-pass (utils/denoising.py, utils/adapthresh.py, utils/sparseCubes.py of mjiUST/SurfaceNet), run under Python 3 / numpy 2 in
+memory:
 
-    python tools/gen_golden_postpass.py --reference /path/to/SurfaceNet [--out tests/golden/postpass_cases.npz]
+    python tools/gen_golden_postpass.py --reference /path/to/SurfaceNet [--out tests/golden/postpass_cases.npz] [--out-edge ...]
 
 The three modules are read as text and executed with these Python-2 accommodations, nothing else changed: `d.has_key(k)` -> `(k) in d`,
 integer `/` -> `//` (denoising.py:104,127, adapthresh.py:42, sparseCubes.py:53), print statements -> print(), load_sparseCubes opens its
@@ -26,7 +27,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from surfacenet_amd import synthetic  # noqa: E402
+import postpass_cases  # noqa: E402
 import postpass_ref  # noqa: E402
+from postpass_cases import mixed_votes  # noqa: E402
 
 
 def _has_key(src):
@@ -114,14 +117,6 @@ def docstring_cases():
     doc_cubes = np.asarray([[1, 6, 8], [2, 6, 8], [2, 7, 8], [2, 5, 8]], np.uint32)
     return [("doc_cluster", np.asarray([[0, 0, 0], [1, 0, 0], [0, 0, 1], [1, 1, 1]], np.uint32), cluster[0], cluster[1], 4),
             ("doc_mark", doc_cubes, mark[0], mark[1], 4), ("doc_denoise", doc_cubes, den[0], den[1], 4)]
-
-
-def mixed_votes(d, seed):
-    """votes that pass rayPool_thresh = 4 for about a third of the voxels, independently per cube: the overlap of neighbours then thins
-    out at the margin and the three threshold perturbations compete"""
-    rs = np.random.RandomState(seed)
-    d["rayPooling_votes_list"] = [np.where(rs.rand(len(v)) < 0.35, 6, 2).astype(np.uint8) for v in d["rayPooling_votes_list"]]
-    return d
 
 
 def edge_scene(lattice, Dc, seed, thickness=2, amplitude=6.0):
@@ -233,6 +228,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", required=True, help="root of a mjiUST/SurfaceNet checkout")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "postpass_cases.npz"))
+    ap.add_argument("--out-edge", default=os.path.join(ROOT, "tests", "golden", "postpass_edge_cases.npz"))
     args = ap.parse_args()
     mods, calls = load_reference(args.reference)
     out = {}
@@ -255,6 +251,17 @@ def main():
     record_adapthresh(mods, calls, out, "s64", mixed_votes(edge_scene((2, 2, 1), 52, 9, thickness=3), 9), 2, 52, beta=2)
     np.savez_compressed(args.out, **out)
     print("wrote %s (%d bytes)" % (args.out, os.path.getsize(args.out)))
+    # the cases of tests/postpass_cases.py TABLE: the kernel paths that depend on the cube width, and D_cube != Dc
+    edge = {}
+    for name in postpass_cases.TABLE:
+        d, D_cube, _ = postpass_cases.build(name, postpass_cases.GOLDEN_LATTICE.get(name))
+        record_denoise(mods, edge, name, d["cube_ijk_np"], d["vxl_ijk_list"], postpass_cases.denoise_masks(d), D_cube)
+        a = postpass_cases.ARGS
+        record_adapthresh(mods, calls, edge, name, d, a["N_refine_iter"], D_cube, init=a["init_probThresh"], max_t=a["max_probThresh"],
+                          rayPool=a["rayPool_thresh"], beta=a["beta"])
+    np.savez_compressed(args.out_edge, **edge)
+    print("wrote %s (%d bytes)" % (args.out_edge, os.path.getsize(args.out_edge)))
+    assert os.path.getsize(args.out_edge) < 700 * 1000
 
 
 if __name__ == "__main__":
