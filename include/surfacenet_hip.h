@@ -33,7 +33,8 @@ extern "C" {
  * components of the output cloud; sn_mesh_simplify, sn_mesh_simplify_dev and sn_mesh_simplify_cfg - a triangle mesh made smaller by vertex
  * clustering; sn_mesh_smooth, sn_mesh_smooth_dev and sn_mesh_smooth_cfg - Taubin smoothing of a triangle or quad mesh in fixed point, with
  * the mesh's edge and boundary counts; sn_mesh_fill, sn_mesh_fill_dev and sn_mesh_fill_cfg - the mesh's small holes capped by centroid fans;
- * sn_mesh_normals and sn_mesh_normals_dev - a mesh's own area-weighted normals with its exact area and volume. */
+ * sn_mesh_normals and sn_mesh_normals_dev - a mesh's own area-weighted normals with its exact area and volume;
+ * sn_mesh_orient, sn_mesh_orient_dev and sn_mesh_orient_cfg - a mesh's faces made to turn one way, its pieces and their exact volumes. */
 
 /* The library is built with -fvisibility=hidden: the functions below are its WHOLE dynamic symbol table
  * (tests/test_abi.py compares `nm -D` with this header). */
@@ -489,6 +490,47 @@ SN_API int sn_mesh_normals(sn_ctx *ctx, int n_verts, const double *verts, int n_
                            float *vert_normals, long long *counts, unsigned long long *sums);
 SN_API int sn_mesh_normals_dev(sn_ctx *ctx, int n_verts, const double *verts_dev, int n_faces, int nv, const int32_t *faces_dev,
                                float *face_normals_dev, float *vert_normals_dev, long long *counts, unsigned long long *sums);
+
+/* ---- a mesh's faces made to turn one way, its pieces, their exact volumes, small pieces removed ---------------------------
+ * The inputs are sn_mesh_smooth's: verts (n_verts,3) float64 in lattice cells, faces (n_faces,nv) int32 with nv = 3 or 4; referenced vertices,
+ * q = int64(rint(v * 65536)) and its range, sides, edges and side counts as there. Side k of a face is p -> r = f[k] -> f[(k + 1) % nv]
+ * (p = r: no side), its direction bit d = (p < r), its code 2 * face + d. A link is an edge with exactly two sides that belong to two
+ * different faces f < g; it is inconsistent iff the two direction bits are equal. Boundary edges, edges with more than two sides and an edge
+ * whose two sides are one face's are no links: pieces end there. Double cover: face f is the two nodes 2f (as given) and 2f + 1 (reversed);
+ * every link with r = inconsistent unites (2f, 2g + r) and (2f + 1, 2g + 1 - r); root = the smallest node of a class. Per face comp =
+ * root(2f) >> 1, the smallest face of its piece, rel = root(2f) & 1; the piece is non-orientable iff root(2f) = root(2f + 1) (then rel = 0
+ * throughout and no face of it is flipped). Per piece: n_faces; n_rel = its faces with rel = 1; closed iff orientable and every one of the nv
+ * corners of every face starts a side that lies on a link; vol6' = the sum over its faces of s * t, t = q_a . (q_b x q_c) of a triangle, of
+ * (a,b,c) plus (a,c,d) for a quad, s = -1 iff rel: an exact integer. Sign of an orientable piece: sign 0 (majority) flipc = (n_rel >
+ * n_faces - n_rel) - the fewer faces turn, a tie leaves the smallest face as it is; sign 1 (outward) flipc = (vol6' < 0) on a closed piece
+ * with vol6' != 0, the majority rule on every other. flip(f) = rel ^ flipc. A flipped face keeps its first corner and reverses the rest,
+ * (a,b,c) -> (a,c,b), (a,b,c,d) -> (a,d,c,b); an unflipped face is copied; face order and vertices are untouched. A piece is kept iff n_faces
+ * >= min_faces; with keep_largest the piece with the most faces (the smallest id among equals) is kept as well. Outputs, each optional (NULL)
+ * except counts:
+ *   faces_out (n_faces,nv) int32; face_flip (n_faces) uint8; face_component (n_faces) int32; face_keep (n_faces) uint8;
+ *   per piece at row comp, zero in the rows that are no piece's id: comp_faces (n_faces) int32; comp_flags (n_faces) uint8: 1 orientable,
+ *   2 closed, 4 flipped, 8 kept; comp_vol6 (n_faces,3) uint64: vol6' negated iff flipc (a non-orientable piece: the sum of its faces as
+ *   given), three 64-bit limbs, least significant first, two's complement, six times the signed volume in units of 2^-48 cell^3;
+ *   counts[12]: E, boundary edges, non-manifold edges, links, inconsistent links, pieces, non-orientable pieces, closed pieces, flipped
+ *   faces, flipped pieces, kept faces, kept pieces.
+ * n_faces = 0: counts 0, nothing written. SN_ERR_ARG, nothing written but counts (zeros), in sn_mesh_smooth's words: a face index outside
+ * [0, n_verts) or a referenced coordinate outside the range (or not a number), the text naming the first offending face; nv not 3 or 4,
+ * n_verts or n_faces > 2^28, 2^30 or more edges; and sign not 0 or 1, min_faces < 0, keep_largest not 0 or 1. Non-manifold edges are not
+ * split or paired, non-orientable pieces are reported and left alone, an open piece has no outward test, vertices that lose all their faces
+ * stay, and nothing looks for self-intersections. Everything is an integer: the result equals the numpy restatement tests/meshorient_ref.py
+ * byte for byte, on every run. The workspace belongs to the context (grown on demand); both forms return when the work is done. */
+typedef struct sn_mesh_orient_cfg {
+    int sign;                  /* 0: majority - the fewer faces of a piece turn; 1: outward - a closed piece turns iff its volume is negative */
+    int min_faces;             /* >= 0: a piece of fewer faces is not kept */
+    int keep_largest;          /* 0 / 1: the piece with the most faces is kept whatever min_faces says */
+} sn_mesh_orient_cfg;
+SN_API int sn_mesh_orient(sn_ctx *ctx, const sn_mesh_orient_cfg *cfg, int n_verts, const double *verts, int n_faces, int nv, const int32_t *faces,
+                          int32_t *faces_out, unsigned char *face_flip, int32_t *face_component, unsigned char *face_keep, int32_t *comp_faces,
+                          unsigned char *comp_flags, unsigned long long *comp_vol6, long long *counts);
+SN_API int sn_mesh_orient_dev(sn_ctx *ctx, const sn_mesh_orient_cfg *cfg, int n_verts, const double *verts_dev, int n_faces, int nv,
+                              const int32_t *faces_dev, int32_t *faces_out_dev, unsigned char *face_flip_dev, int32_t *face_component_dev,
+                              unsigned char *face_keep_dev, int32_t *comp_faces_dev, unsigned char *comp_flags_dev,
+                              unsigned long long *comp_vol6_dev, long long *counts);
 
 /* ---- DTU point-cloud evaluation (experiments/DTU/eval_ply.m -> PointCompareMain of the DTU kit) ----------------------
  * Points are (n,3) float64, row-major, finite. d^2 = (dx*dx + dy*dy) + dz*dz in float64 without contraction: the results are those of the numpy

@@ -708,6 +708,24 @@ class Context(object):
         out["sums"] = np.asarray(list(sums), np.uint64)
         return out
 
+    def mesh_orient(self, verts, faces, sign=0, min_faces=0, keep_largest=False, device=False):
+        """A mesh's faces made to turn one way, its pieces and their exact volumes (sn_mesh_orient): verts (V,3) float64
+        in lattice cells, faces (F,3) or (F,4) int32, sign 0 (majority) / 1 (outward), min_faces >= 0 the smallest piece that is kept,
+        keep_largest the piece with the most faces is kept as well. Returns a dict: faces_out (F,nv) int32, face_flip (F,) uint8,
+        face_component (F,) int32 the smallest face of the face's piece, face_keep (F,) uint8, and per piece at the row of its id (zero
+        elsewhere) comp_faces (F,) int32, comp_flags (F,) uint8 (1 orientable, 2 closed, 4 flipped, 8 kept), comp_vol6 (F,3) uint64 limbs,
+        least significant first; counts (12,) int64 = edges, boundary edges, non-manifold edges, links, inconsistent links, pieces,
+        non-orientable, closed, flipped faces, flipped pieces, kept faces, kept pieces. device=True stages the mesh in device memory here and
+        runs sn_mesh_orient_dev on it: the same result."""
+        v, f = self._mesh_arrays(verts, faces)
+        V, (F, nv) = v.shape[0], f.shape
+        cfg = _lib.MeshOrientCfg(int(sign), int(min_faces), int(keep_largest))
+        spec = (("faces_out", nv, np.int32), ("face_flip", 1, np.uint8), ("face_component", 1, np.int32), ("face_keep", 1, np.uint8),
+                ("comp_faces", 1, np.int32), ("comp_flags", 1, np.uint8), ("comp_vol6", 3, np.uint64))
+        run = lambda fn, _, ins, outs, counts: fn(self._h, ctypes.byref(cfg), V, ins[0], F, nv, ins[1], *outs, *counts)
+        # (no face: either form returns at once and writes nothing, so there is nothing to stage or to copy back)
+        return self._host_or_device("sn_mesh_orient", device and F > 0, (v, f), run, spec, lambda name, sizes: F, (), words=12)
+
     @staticmethod
     def _points(xyz):
         return np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))

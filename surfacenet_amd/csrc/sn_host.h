@@ -194,3 +194,16 @@ static inline int mfl_check_args(const sn_mesh_fill_cfg *cfg, int n_verts, int n
     if (cfg->orientation != 0 && cfg->orientation != 1) return fail(SN_ERR_ARG, "orientation = %d: 0 (holes) or 1 (any)", cfg->orientation);
     return mesh_check_caps(cap_verts, cap_faces);
 }
+
+// (sn_mesh_orient has no lattice and no sized outputs: every array has n_faces rows)
+static inline int mor_check_args(const sn_mesh_orient_cfg *cfg, int n_verts, int n_faces, int nv)
+{
+    int rc;
+    if (!cfg) return fail(SN_ERR_ARG, "null cfg");
+    const double origin[3] = {0.0, 0.0, 0.0};
+    if ((rc = mesh_check_common(n_verts, n_faces, nv, origin, 1.0)) != SN_OK) return rc;
+    if (cfg->sign != 0 && cfg->sign != 1) return fail(SN_ERR_ARG, "sign = %d: 0 (majority) or 1 (outward)", cfg->sign);
+    if (cfg->min_faces < 0) return fail(SN_ERR_ARG, "min_faces = %d must be >= 0", cfg->min_faces);
+    if (cfg->keep_largest != 0 && cfg->keep_largest != 1) return fail(SN_ERR_ARG, "keep_largest = %d: 0 or 1", cfg->keep_largest);
+    return SN_OK;
+}

@@ -1,0 +1,149 @@
+// sn_meshorient.hip — C ABI of the mesh orientation stage (meshorient.h). The device form works on the caller's device
+// arrays; the host form is the same computation on the host mirror's device copies of its arrays (sn_internal.h HostMirror). The edge table is
+// the smoother's, built by the sequence the smoother runs (meshsmooth_build.h); everything after it is plain launches on the context's stream,
+// one read of the status block, then the kernel that writes the outputs.
+#include "sn_internal.h"
+#include "meshorient.h"
+#include "meshsmooth_build.h"
+
+namespace {
+
+// the caller's outputs: device arrays in the device form, host arrays in the host form
+struct MorOut {
+    int32_t *faces_out; unsigned char *face_flip; int32_t *face_component; unsigned char *face_keep;
+    int32_t *comp_faces; unsigned char *comp_flags; unsigned long long *comp_vol6;
+};
+
+int mor_check(sn_ctx *c, const sn_mesh_orient_cfg *cfg, int n_verts, int n_faces, int nv, long long *counts)
+{
+    const int rc = mesh_check_counts(c, counts, 12);
+    return rc != SN_OK ? rc : mor_check_args(cfg, n_verts, n_faces, nv);
+}
+
+// What both forms do once their arguments are checked, F > 0.
+int mor_run(sn_ctx *c, bool host, const sn_mesh_orient_cfg *cfg, int V, const double *verts, int F, int nv, const int32_t *faces, MorOut d,
+            long long *counts)
+{
+    HostMirror m(c, host);
+    int rc = m.inputs([&](Carve &w) { m.in(w, verts, 3 * (size_t)V); m.in(w, faces, (size_t)nv * (size_t)F); });
+    if (rc != SN_OK) return rc;
+    const size_t cap = msm_table_cap(F, nv), n = (size_t)F;
+    const double origin[3] = {0.0, 0.0, 0.0};
+    MsmArgs a;
+    msm_set_inputs(a, V, verts, F, nv, faces, origin, 1.0, cap);
+    MorArgs b;
+    memset(&b, 0, sizeof b);
+    b.sign = cfg->sign; b.min_faces = cfg->min_faces; b.keep_largest = cfg->keep_largest;
+    // One giant piece is the common case: a workgroup whose faces name one piece sums in LDS and sends one set of atomics. The faster of the
+    // two on an MI355X (tools/bench_meshorient.py, profiles/meshorient/); the test-only twin reads SN_MOR_NO_REDUCE to send per lane for the
+    // A/B. The results are the same bits.
+    b.reduce = sn_ab_switch("SN_MOR_NO_REDUCE") ? 0 : 1;
+    auto layout = [&](Carve &w) {
+        b.st = w.get<MorStat>(1);
+        a.st = b.st ? &b.st->msm : nullptr;                     // the build writes into the head of the one block the host reads
+        msm_carve_build<MOR_REC>(w, a, cap);
+        b.slot_lo = w.get<unsigned>(cap);
+        b.slot_hi = w.get<unsigned>(cap);
+        b.parent = w.get<unsigned>(2 * n);
+        b.linked = w.get<unsigned>(n);
+        b.root = w.get<unsigned>(n);
+        b.rec_faces = w.get<unsigned>(n);
+        b.rec_rel = w.get<unsigned>(n);
+        b.rec_bits = w.get<unsigned>(n);
+        b.rec_vol = w.get<unsigned long long>(3 * n);
+        b.flags = w.get<unsigned char>(n);
+    };
+    if ((rc = dev_carve(c, c->mor_ws, layout, 256)) != SN_OK) return rc;
+    const unsigned fb = blocks(F, MOR_NT), sb = blocks((long long)cap, MOR_NT);
+    const unsigned loop_blocks = (unsigned)std::max(c->num_cus, 1) * 8u;      // the grid-stride kernels: eight workgroups per CU at most
+    HIPCHK(hipMemsetAsync(b.st, 0, sizeof(MorStat), c->stream));
+    if ((rc = msm_build<MOR_REC>(c, a, cap)) != SN_OK) return rc;
+    {
+        // per side: its face's indices, a probe, the slot's count, two atomics
+        ProfScope ps(c, "mor_sides", 0, (double)F * (nv * (4.0 + 4.0 + 16.0 + 4.0 + 8.0) + 8.0) + (double)cap * 8.0);
+        HIPCHK(hipMemsetAsync(b.slot_lo, 0xff, sizeof(unsigned) * cap, c->stream));
+        HIPCHK(hipMemsetAsync(b.slot_hi, 0, sizeof(unsigned) * cap, c->stream));
+        hipLaunchKernelGGL(mor_sides_kernel, dim3(fb), dim3(MOR_NT), 0, c->stream, a, b);
+        HIPCHK(hipGetLastError());
+    }
+    {
+        ProfScope ps(c, "mor_links", 0, (double)cap * 20.0 + (double)F * nv * 0.5 * (8.0 + 32.0) + (double)F * 4.0);
+        HIPCHK(hipMemsetAsync(b.linked, 0, sizeof(unsigned) * n, c->stream));
+        hipLaunchKernelGGL(mor_links_kernel, dim3(std::min(sb, loop_blocks)), dim3(MOR_NT), 0, c->stream, a, b);
+        HIPCHK(hipGetLastError());
+    }
+    {
+        // per face: two walks to the root, its indices, its corners' records, the piece's record
+        ProfScope ps(c, "mor_faces", 0, (double)F * (16.0 + 4.0 + nv * (4.0 + 4.0 + 24.0) + 8.0 + 36.0));
+        HIPCHK(hipMemsetAsync(b.rec_faces, 0, sizeof(unsigned) * n, c->stream));
+        HIPCHK(hipMemsetAsync(b.rec_rel, 0, sizeof(unsigned) * n, c->stream));
+        HIPCHK(hipMemsetAsync(b.rec_bits, 0, sizeof(unsigned) * n, c->stream));
+        HIPCHK(hipMemsetAsync(b.rec_vol, 0, sizeof(unsigned long long) * 3 * n, c->stream));
+        hipLaunchKernelGGL(mor_faces_kernel, dim3(fb), dim3(MOR_NT), 0, c->stream, a, b);
+        HIPCHK(hipGetLastError());
+    }
+    {
+        ProfScope ps(c, "mor_pieces", 0, (double)F * 8.0);
+        hipLaunchKernelGGL(mor_pieces_kernel, dim3(std::min(fb, loop_blocks)), dim3(MOR_NT), 0, c->stream, a, b);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(mor_keep_kernel, dim3(std::min(fb, loop_blocks)), dim3(MOR_NT), 0, c->stream, a, b);
+        HIPCHK(hipGetLastError());
+    }
+    // the one read, before any output is touched: the first bad face, the edge limit, the counts
+    MorStat st;
+    HIPCHK(hipMemcpyAsync(&st, b.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = msm_report(st.msm, V, false)) != SN_OK) return rc;
+    rc = m.outputs([&](Carve &w) {
+        m.out(w, d.faces_out, (size_t)nv * n); m.out(w, d.face_flip, n); m.out(w, d.face_component, n); m.out(w, d.face_keep, n);
+        m.out(w, d.comp_faces, n); m.out(w, d.comp_flags, n); m.out(w, d.comp_vol6, 3 * n);
+    });
+    if (rc != SN_OK) return rc;
+    b.faces_out = d.faces_out; b.face_flip = d.face_flip; b.face_component = d.face_component; b.face_keep = d.face_keep;
+    b.comp_faces = d.comp_faces; b.comp_flags = d.comp_flags; b.comp_vol6 = d.comp_vol6;
+    if (b.faces_out || b.face_flip || b.face_component || b.face_keep || b.comp_faces || b.comp_flags || b.comp_vol6) {
+        ProfScope ps(c, "mor_emit", 0, (double)F * (8.0 + nv * 8.0 + 6.0 + 5.0 + 24.0));
+        hipLaunchKernelGGL(mor_emit_kernel, dim3(fb), dim3(MOR_NT), 0, c->stream, a, b);
+        HIPCHK(hipGetLastError());
+    }
+    if ((rc = m.back(d.faces_out, (size_t)nv * n)) != SN_OK || (rc = m.back(d.face_flip, n)) != SN_OK ||
+        (rc = m.back(d.face_component, n)) != SN_OK || (rc = m.back(d.face_keep, n)) != SN_OK || (rc = m.back(d.comp_faces, n)) != SN_OK ||
+        (rc = m.back(d.comp_flags, n)) != SN_OK || (rc = m.back(d.comp_vol6, 3 * n)) != SN_OK)
+        return rc;
+    if ((rc = m.finish()) != SN_OK) return rc;
+    for (int k = 0; k < 3; ++k) counts[k] = (long long)st.msm.counts[k];
+    for (int k = 0; k < 9; ++k) counts[3 + k] = (long long)st.counts[k];
+    return SN_OK;
+}
+
+int mor_dispatch(sn_ctx *c, bool host, const sn_mesh_orient_cfg *cfg, int V, const double *verts, int F, int nv, const int32_t *faces, MorOut d,
+                 long long *counts)
+{
+    if (F == 0) return SN_OK;                                   // no face: all counts 0, nothing written
+    if (!faces || (V > 0 && !verts)) return fail(SN_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(c->device));
+    return mor_run(c, host, cfg, V, verts, F, nv, faces, d, counts);
+}
+
+}  // namespace
+
+extern "C" int sn_mesh_orient_dev(sn_ctx *c, const sn_mesh_orient_cfg *cfg, int n_verts, const double *verts_dev, int n_faces, int nv,
+                                  const int32_t *faces_dev, int32_t *faces_out_dev, unsigned char *face_flip_dev, int32_t *face_component_dev,
+                                  unsigned char *face_keep_dev, int32_t *comp_faces_dev, unsigned char *comp_flags_dev,
+                                  unsigned long long *comp_vol6_dev, long long *counts)
+{
+    int rc;
+    if ((rc = mor_check(c, cfg, n_verts, n_faces, nv, counts)) != SN_OK) return rc;
+    const MorOut o = {faces_out_dev, face_flip_dev, face_component_dev, face_keep_dev, comp_faces_dev, comp_flags_dev, comp_vol6_dev};
+    return mor_dispatch(c, false, cfg, n_verts, verts_dev, n_faces, nv, faces_dev, o, counts);
+}
+
+extern "C" int sn_mesh_orient(sn_ctx *c, const sn_mesh_orient_cfg *cfg, int n_verts, const double *verts, int n_faces, int nv, const int32_t *faces,
+                              int32_t *faces_out, unsigned char *face_flip, int32_t *face_component, unsigned char *face_keep, int32_t *comp_faces,
+                              unsigned char *comp_flags, unsigned long long *comp_vol6, long long *counts)
+{
+    int rc;
+    if ((rc = mor_check(c, cfg, n_verts, n_faces, nv, counts)) != SN_OK) return rc;
+    const MorOut o = {faces_out, face_flip, face_component, face_keep, comp_faces, comp_flags, comp_vol6};
+    return mor_dispatch(c, true, cfg, n_verts, verts, n_faces, nv, faces, o, counts);
+}

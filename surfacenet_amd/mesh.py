@@ -7,7 +7,8 @@
     smooth_mesh        the mesh without its staircase: Taubin smoothing in fixed point, and its edge statistics
     fill_holes         the mesh with its small holes capped: boundary loops and centroid fans
     mesh_normals       the normals of a mesh from the mesh itself, area-weighted, with its exact area and volume
-    chain_settings     the checked keywords of the stages that follow extract_mesh in a scene: fill, smooth, decimate
+    orient_mesh        the faces of a mesh made to turn one way, its pieces with their exact volumes, small pieces removed
+    chain_settings     the checked keywords of the stages that follow extract_mesh in a scene: fill, smooth, decimate, orient
     run_chain          those stages, each on the result of the one before it
     save_mesh_2ply     binary little-endian PLY of a quad or triangle mesh
     save_stage_2ply    the same of a stage's mesh, normals and colours gathered through its vert_src (stage_tag: the file's tag), or with
@@ -353,16 +354,77 @@ def mesh_normals(vert_lattice, faces, resol=1.0):
     return res
 
 
+SIGNS = {"majority": 0, "outward": 1}
+ORIENT_COUNTS = ("n_edges", "n_boundary_edges", "n_nonmanifold_edges", "n_links", "n_inconsistent", "n_components", "n_nonorientable", "n_closed",
+                 "n_flipped_faces", "n_flipped_components", "n_kept_faces", "n_kept_components")
+
+
+def check_orient_args(sign, min_faces, keep_largest):
+    """-> (sign code, min_faces, keep_largest as 0 / 1) of orient_mesh's three settings, or ValueError."""
+    if not isinstance(sign, str) or sign not in SIGNS:
+        raise ValueError("sign = %r: 'majority' or 'outward'" % (sign,))
+    try:
+        n = int(min_faces)
+    except (TypeError, ValueError):
+        raise ValueError("min_faces = %r must be an integer" % (min_faces,))
+    if isinstance(min_faces, bool) or n != min_faces or not 0 <= n < 1 << 31:
+        raise ValueError("min_faces = %r: an integer number of faces >= 0" % (min_faces,))
+    if not isinstance(keep_largest, (bool, np.bool_)):
+        raise ValueError("keep_largest = %r: True or False" % (keep_largest,))
+    return SIGNS[sign], n, int(keep_largest)
+
+
+def orient_mesh(vert_lattice, faces, sign="majority", min_faces=0, keep_largest=False, resol=1.0):
+    """The faces of a mesh made to turn one way, piece by piece, its pieces, and the mesh without its small pieces:
+    vert_lattice (V,3) float32 or float64 in lattice cells as any stage returns it, faces (F,3) triangles or (F,4) quads - quads stay
+    quads. Two faces across an edge that exactly the two of them share belong to one piece; within a piece every face is brought to the
+    orientation of the piece's smallest face, then the piece as a whole turns by `sign`: "majority" - the fewer faces turn - or "outward" -
+    a closed piece turns iff its volume is negative (an open one: the majority rule). A non-orientable piece is reported and left alone. A
+    piece of fewer than min_faces faces is dropped, with keep_largest never the one with the most faces. -> dict: faces (G,nv) int32 the
+    kept, oriented faces in input order, face_src (G,) int32 their input faces, and over all F input faces face_flip (F,) bool,
+    face_component (F,) int32 (the smallest face of the face's piece), face_keep (F,) bool; n_edges, n_boundary_edges,
+    n_nonmanifold_edges, n_links, n_inconsistent, n_components, n_nonorientable, n_closed, n_flipped_faces, n_flipped_components,
+    n_kept_faces, n_kept_components; components, a dict of arrays over the pieces in ascending id: id, n_faces, orientable, closed,
+    flipped, kept, and vol6 a list of Python ints (six times the signed volume in 2^-48 cell^3 after the turn, exact), volume = vol6 / 6 /
+    2^48 * resol^3 as floats. Vertices are untouched: positions, vert_src, colours carry over. ValueError on bad shapes, dtypes, settings,
+    face indices or coordinates before the library is touched."""
+    v, f = _mesh_arrays(vert_lattice, faces)
+    code, n, largest = check_orient_args(sign, min_faces, keep_largest)
+    _, r, V, F, _, _ = _mesh_args(v, f, (0.0, 0.0, 0.0), resol, None, "faces")
+    nv = f.shape[1]
+    if V == 0 or F == 0:                                        # no face (V = 0 with faces was refused): nothing for the library to do
+        m = dict(faces_out=np.zeros((F, nv), np.int32), face_flip=np.zeros((F,), np.uint8), face_component=np.zeros((F,), np.int32),
+                 face_keep=np.zeros((F,), np.uint8), comp_faces=np.zeros((F,), np.int32), comp_flags=np.zeros((F,), np.uint8),
+                 comp_vol6=np.zeros((F, 3), np.uint64), counts=np.zeros((12,), np.int64))
+    else:
+        m = runtime.any_context().mesh_orient(v.astype(np.float64), f.astype(np.int32), code, n, largest)
+    keep = m["face_keep"].astype(bool)
+    res = dict(faces=m["faces_out"][keep], face_src=np.flatnonzero(keep).astype(np.int32), face_flip=m["face_flip"].astype(bool),
+               face_component=m["face_component"], face_keep=keep)
+    res.update({k: int(c) for k, c in zip(ORIENT_COUNTS, m["counts"])})
+    ids = np.flatnonzero(m["comp_faces"] > 0)
+    fl = m["comp_flags"][ids]
+    vol6 = [_limbs(row) for row in m["comp_vol6"][ids]]
+    res["components"] = dict(id=ids.astype(np.int32), n_faces=m["comp_faces"][ids], orientable=(fl & 1) != 0, closed=(fl & 2) != 0,
+                             flipped=(fl & 4) != 0, kept=(fl & 8) != 0, vol6=vol6,
+                             volume=np.asarray([x / 6 / 2 ** 48 * r ** 3 for x in vol6], np.float64))
+    return res
+
+
 # The chain that follows extract_mesh, in its order (DESIGN.md section 4.19). A row: the key of the stage's result, reconstruct.scene_postpass's
-# argument, the keyword a bare number stands for, the defaults (their keys are the allowed ones), what a refusal says the argument is, the
-# check of the keywords, the stage, the letter of its PLY file's tag. mesh_cell is a number only: its second keyword is mesh_placement.
-_Stage = collections.namedtuple("_Stage", "key arg first defaults words check run letter")
+# argument, the keyword a bare value stands for (a number, or orient's sign word), the defaults (their keys are the allowed ones), what a
+# refusal says the argument is, the check of the keywords, the stage, the letter of its PLY file's tag, and what the stage keeps of the mesh
+# that goes in: None - nothing, its result is a new mesh with its own vert_src -, "faces" - it moves the vertices -, "vertices" - it
+# replaces the faces under the key they came in. mesh_cell is a number only: its second keyword is mesh_placement.
+_Stage = collections.namedtuple("_Stage", "key arg first defaults words check run letter keeps")
 _CHAIN = (
     _Stage("filled", "mesh_fill", "max_len", dict(max_len=64, orientation="holes"), "a largest loop length or a dict of max_len, orientation",
-           check_fill_args, fill_holes, "f"),
+           check_fill_args, fill_holes, "f", None),
     _Stage("smoothed", "mesh_smooth", "iterations", dict(iterations=10, lam=0.5, mu=-0.53, boundary="curve"),
-           "a number of iterations or a dict of iterations, lam, mu, boundary", check_smooth_args, smooth_mesh, "s"),
-    _Stage("simplified", "mesh_cell", "cell", None, None, check_simplify_args, simplify_mesh, "c"),
+           "a number of iterations or a dict of iterations, lam, mu, boundary", check_smooth_args, smooth_mesh, "s", "faces"),
+    _Stage("simplified", "mesh_cell", "cell", None, None, check_simplify_args, simplify_mesh, "c", None),
+    _Stage("oriented", "mesh_orient", "sign", dict(sign="majority", min_faces=0, keep_largest=False),
+           "a sign word or a dict of sign, min_faces, keep_largest", check_orient_args, orient_mesh, "o", "vertices"),
 )
 _STAGES = {row.key: row for row in _CHAIN}
 
@@ -375,11 +437,12 @@ def _stage_keywords(row, value):
     return dict(row.defaults, **kw)
 
 
-def chain_settings(mesh_fill=None, mesh_smooth=None, mesh_cell=None, mesh_placement="mean"):
-    """scene_postpass's mesh_fill, mesh_smooth and mesh_cell / mesh_placement -> [(key, keywords), ...]: the stages asked for (not None) in the
-    chain's order - "filled", "smoothed", "simplified" - each with the checked keywords of fill_holes, smooth_mesh, simplify_mesh. ValueError
-    for the first bad argument in the order mesh_cell, mesh_smooth, mesh_fill; the library is not touched."""
-    given = dict(mesh_fill=mesh_fill, mesh_smooth=mesh_smooth, mesh_cell=mesh_cell)
+def chain_settings(mesh_fill=None, mesh_smooth=None, mesh_cell=None, mesh_placement="mean", mesh_orient=None):
+    """scene_postpass's mesh_fill, mesh_smooth, mesh_cell / mesh_placement and mesh_orient -> [(key, keywords), ...]: the stages asked for
+    (not None) in the chain's order - "filled", "smoothed", "simplified", "oriented" - each with the checked keywords of fill_holes,
+    smooth_mesh, simplify_mesh, orient_mesh. ValueError for the first bad argument in the order mesh_orient, mesh_cell, mesh_smooth,
+    mesh_fill; the library is not touched."""
+    given = dict(mesh_fill=mesh_fill, mesh_smooth=mesh_smooth, mesh_cell=mesh_cell, mesh_orient=mesh_orient)
     stages = []
     for row in reversed(_CHAIN):
         value = given[row.arg]
@@ -391,8 +454,10 @@ def chain_settings(mesh_fill=None, mesh_smooth=None, mesh_cell=None, mesh_placem
 
 
 def stage_tag(key, kw):
-    """The tag of a chain stage's PLY file, <prefix><name>_mesh<tag>.ply: "_f<max_len>", "_s<iterations>", "_c<cell>"."""
-    return "_%s%d" % (_STAGES[key].letter, int(kw[_STAGES[key].first]))
+    """The tag of a chain stage's PLY file, <prefix><name>_mesh<tag>.ply: "_f<max_len>", "_s<iterations>", "_c<cell>", and "_o" - the letter
+    alone where the stage's first keyword is a word."""
+    first = kw[_STAGES[key].first]
+    return "_" + _STAGES[key].letter + ("" if isinstance(first, str) else "%d" % int(first))
 
 
 def _faces(m):
@@ -402,14 +467,19 @@ def _faces(m):
 
 def run_chain(m, stages, origin, resol):
     """extract_mesh's dict m (empty_mesh() too) through chain_settings' stages, each on the result of the one before it: fill, smooth,
-    decimate; origin / resol as lattice_origin returns them. -> {key: the stage's result}: fill_holes' and simplify_mesh's dicts as they
-    are, both with vert_src; "smoothed" the mesh that went in - m, or vertices, vert_lattice, faces, vert_src of the filled one - with
-    smooth_mesh's positions and statistics, so it holds quads without a fill and faces after one."""
+    decimate, orient; origin / resol as lattice_origin returns them. -> {key: the stage's result}: fill_holes' and simplify_mesh's dicts as
+    they are, both with vert_src; "smoothed" the mesh that went in - m, or vertices, vert_lattice, faces, vert_src of the filled one - with
+    smooth_mesh's positions and statistics, so it holds quads without a fill and faces after one; "oriented" the mesh that went in with
+    orient_mesh's kept, oriented faces under the key its faces came in (quads or faces) and the rest of orient_mesh's dict beside them."""
     res = {}
     for key, kw in stages:
-        run = _STAGES[key].run
-        if run is smooth_mesh:                                  # indices stay: the mesh's other keys carry over
+        run, keeps = _STAGES[key].run, _STAGES[key].keeps
+        if keeps == "faces":                                    # indices stay: the mesh's other keys carry over
             m = res[key] = dict(m, **run(m["vert_lattice"], _faces(m), origin=origin, resol=resol, **kw))
+        elif keeps == "vertices":                               # vertices stay: the new faces take the place of the old
+            r = run(m["vert_lattice"], _faces(m), resol=resol, **kw)
+            r["faces" if "faces" in m else "quads"] = r.pop("faces")
+            m = res[key] = dict(m, **r)
         else:                                                   # a new mesh: the next stage reads these four of it
             res[key] = run(m["vert_lattice"], _faces(m), origin=origin, resol=resol, vert_src=m["vert_src"], **kw)
             m = {k: res[key][k] for k in ("vertices", "vert_lattice", "faces", "vert_src")}

@@ -566,7 +566,7 @@ def reconstruct_scene(images_list, cameraPOs_np, cubes_param_np, cube_D_mm, cube
 def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, gamma=0.8, beta=6, N_refine_iter=8, init_probThresh=0.5,
                    max_probThresh=0.9, keep_iterations=False, cameraTs_np=None, cube_overlapping_ratio=0.5, unique=False, mesh=False, mesh_radius=2,
                    mesh_reach=0, mesh_ply_prefix=None, min_component=None, component_connectivity=26, mesh_cell=None, mesh_placement="mean",
-                   mesh_smooth=None, mesh_fill=None, mesh_normals="source"):
+                   mesh_smooth=None, mesh_fill=None, mesh_normals="source", mesh_orient=None):
     """The reconstruction's last two stages on `reconstruct_scene`'s dict, in memory and on the GPU, as the reference runs them on its files:
       * main_reconstruct.py:172-175  thinning masks (prob >= tau, votes >= gamma * N_vp * 2), then denoise_crossCubes with D_cube = cube_D
       * main.py:37-43 -> utils/adapthresh.py  adaptive thresholding with D_cube = cube_Dcenter, init / max threshold init_probThresh /
@@ -604,7 +604,12 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
         mesh: the smoothed dict then holds faces (triangles) in the place of quads.
       mesh_normals="mesh" (needs mesh=True; the default "source" adds no key and changes no file): every
         <name>_mesh* dict also carries vert_normals (V,3) float32, area (mm^2) and volume (mm^3, signed) - mesh.mesh_normals of the stage's
-        vert_lattice and faces with the lattice's resol -, and the PLY files hold those normals in the place of the source voxels'."""
+        vert_lattice and faces with the lattice's resol -, and the PLY files hold those normals in the place of the source voxels'.
+      mesh_orient="majority" / "outward" or dict(sign=, min_faces=, keep_largest=) (needs mesh=True; the default None
+        adds no key and writes no file): fixThresh_mesh_oriented, adapt_mesh_oriented - the last mesh of the chain (fill, smooth, decimate,
+        then orient) with mesh.orient_mesh's kept, oriented faces in the place of its faces (quads stay quads) and orient_mesh's other keys
+        beside them: n_inconsistent = 0 and n_flipped_faces = 0 say that the chain kept the mesher's orientation; with mesh_ply_prefix also
+        written as <prefix>fixThresh_mesh_o.ply / <prefix>adapt_mesh_o.ply."""
     from . import adapthresh, denoising, sparseCubes
     from . import mesh as _mesh
     from . import normals as _normals
@@ -612,10 +617,11 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
     if mesh and cameraTs_np is None:
         raise ValueError("mesh=True needs cameraTs_np: the mesher reads the oriented normals")
     for arg, value, does in (("mesh_cell", mesh_cell, "simplifies"), ("mesh_smooth", mesh_smooth, "smooths"), ("mesh_fill", mesh_fill, "fills the holes of"),
-                             ("mesh_normals", None if mesh_normals == "source" else mesh_normals, "takes its normals from")):
+                             ("mesh_normals", None if mesh_normals == "source" else mesh_normals, "takes its normals from"),
+                             ("mesh_orient", mesh_orient, "orients")):
         if value is not None and not mesh:
             raise ValueError("%s needs mesh=True: it %s the mesh that mesh=True extracts" % (arg, does))
-    stages = _mesh.chain_settings(mesh_fill, mesh_smooth, mesh_cell, mesh_placement)      # fill, smooth, decimate: those asked for
+    stages = _mesh.chain_settings(mesh_fill, mesh_smooth, mesh_cell, mesh_placement, mesh_orient)      # fill, smooth, decimate, orient: those asked for
     _mesh.check_normals_arg(mesh_normals, "mesh_normals")
     ply_tags = dict([("", "")] + [("_" + key, _mesh.stage_tag(key, kw)) for key, kw in stages])      # result key's ending -> file name's
     if min_component is not None:
