@@ -34,7 +34,9 @@ extern "C" {
  * clustering; sn_mesh_smooth, sn_mesh_smooth_dev and sn_mesh_smooth_cfg - Taubin smoothing of a triangle or quad mesh in fixed point, with
  * the mesh's edge and boundary counts; sn_mesh_fill, sn_mesh_fill_dev and sn_mesh_fill_cfg - the mesh's small holes capped by centroid fans;
  * sn_mesh_normals and sn_mesh_normals_dev - a mesh's own area-weighted normals with its exact area and volume;
- * sn_mesh_orient, sn_mesh_orient_dev and sn_mesh_orient_cfg - a mesh's faces made to turn one way, its pieces and their exact volumes. */
+ * sn_mesh_orient, sn_mesh_orient_dev and sn_mesh_orient_cfg - a mesh's faces made to turn one way, its pieces and their exact volumes;
+ * sn_mesh_render, sn_mesh_render_dev, sn_mesh_vertex_colors, sn_mesh_vertex_colors_dev and sn_mesh_render_cfg - a mesh rendered back into its
+ * views: depth maps, face ids, visibility, vertex colours. */
 
 /* The library is built with -fvisibility=hidden: the functions below are its WHOLE dynamic symbol table
  * (tests/test_abi.py compares `nm -D` with this header). */
@@ -531,6 +533,60 @@ SN_API int sn_mesh_orient_dev(sn_ctx *ctx, const sn_mesh_orient_cfg *cfg, int n_
                               const int32_t *faces_dev, int32_t *faces_out_dev, unsigned char *face_flip_dev, int32_t *face_component_dev,
                               unsigned char *face_keep_dev, int32_t *comp_faces_dev, unsigned char *comp_flags_dev,
                               unsigned long long *comp_vol6_dev, long long *counts);
+
+/* ---- the mesh back in its views: depth maps, face ids, visibility, colours --------------------------------------------
+ * sn_mesh_render rasterises a mesh into V views of one size: verts (n_verts,3) float64 in WORLD coordinates (as sn_mesh_sample's), faces
+ * (n_faces,nv) int32, nv = 3 or 4 - a quad (a,b,c,d) is the triangles (a,b,c), (a,c,d) in that order, triangle t = f for nv = 3 and t = 2 f +
+ * half for nv = 4 -, P (V,3,4) float64 or NULL for the cameras of sn_set_cameras (V is then theirs). Pixel (i, j) has its centre at h = i,
+ * w = j. All float arithmetic is fp64 without contraction; everything that is summed or compared across lanes is an integer.
+ *   1 projection  per view and vertex (h, w, z) are what sn_project_points returns as img_h, img_w, depth (round_int = 0).
+ *   2 snap        X = int64(rint(w * 256)), Y = int64(rint(h * 256)). A triangle is CLIPPED when one of its corners has a non-finite h, w or z,
+ *                 z <= near, or |X| or |Y| >= 2^25: it is dropped whole and counted. Nothing is clipped against the camera plane.
+ *   3 edges       corners 0, 1, 2 in face order; E_k belongs to the edge from corner (k+1)%3 to corner (k+2)%3; for a -> b E(p) = (bx-ax) *
+ *                 (py-ay) - (by-ay) * (px-ax), exact in int64. A2 = E_0(corner 0); A2 = 0: DEGENERATE, dropped and counted. s = sign(A2);
+ *                 every E_k and every edge direction (dx, dy) is multiplied by s (negated, the corners are not swapped).
+ *   4 coverage    pixel (i, j), sampled at (256 j, 256 i), is covered iff for every k: s E_k > 0, or s E_k = 0 and edge k owns its line: s dy >
+ *                 0, or s dy = 0 and s dx > 0. Of two triangles that share an edge exactly one owns a centre on it.
+ *   5 depth       r_k = 1.0 / z_k; S = (double(s E_0) * r_0 + double(s E_1) * r_1) + double(s E_2) * r_2; zpix = double(s A2) / S: finite, > 0.
+ *   6 resolve     depth[v,i,j] = the least zpix over the covering triangles, face[v,i,j] = the face (t for nv = 3, t >> 1 for nv = 4) of the
+ *                 smallest triangle index among those that attain it; an empty pixel has depth 0.0 and face -1.
+ *   7 face_pixels (V,n_faces) int32: the pixels the face wins in view v.
+ *   8 vert_visible (V,n_verts) uint8, for every vertex, referenced or not: 1 iff h, w, z are finite, z > near, |h|, |w| < 2^25; the nearest
+ *                 pixel (rint(h), rint(w)) lies in the image; and of the four pixels (floor(h) + {0,1}, floor(w) + {0,1}) at least one is empty
+ *                 or outside the image, or z - tol <= the largest of their four depths.
+ *   9 counts[8]   summed over the views: triangles, clipped, degenerate, rasterised, covering (triangle, pixel) pairs, non-empty pixels, visible
+ *                 (view, vertex) pairs, 0.
+ * Outputs, each optional (NULL) except counts: depth (V,H,W) float64, face (V,H,W) int32, face_pixels, vert_visible. n_faces = 0: depth 0.0,
+ * face -1, vert_visible by rule 8 with every pixel empty. SN_ERR_ARG with nothing written but counts (zeros): a face index outside [0,
+ * n_verts) or a non-finite coordinate of a referenced vertex (the text names the first offending face, in sn_mesh_sample's words), nv not 3 or
+ * 4, n_verts or n_faces > 2^28, H or W outside 1 .. 16384, V < 1, near or tol negative or not finite, a non-finite entry of P; SN_ERR_STATE:
+ * P = NULL before sn_set_cameras. Limits: no clipping at the camera plane (a triangle with a corner at z <= near vanishes whole), one image
+ * size per call, vertices next to the silhouette count as visible, no anti-aliasing. The workspace belongs to the context and holds ONE
+ * view's z-buffer whatever V is; the host form copies each view out as it is done. The result equals tests/meshrender_ref.py byte for byte.
+ *
+ * sn_mesh_vertex_colors: the same mesh, cameras and size, vert_visible (V,n_verts) uint8 as INPUT (the render's, or any other), and the
+ * images of sn_set_images, which must be exactly V images of H x W (none set: SN_ERR_STATE; another count or size: SN_ERR_ARG). View v
+ * contributes to vertex a iff vert_visible[v,a] != 0, (h, w, z) are finite and the nearest pixel (rint(h), rint(w)) lies in the image.
+ * vert_views (n_verts) int32 = the number n of contributing views; vert_rgb (n_verts,3) uint8 = (2 sum + n) / (2 n), rounded down, of those
+ * pixels' RGB per channel, (0,0,0) for n = 0: nearest pixel, equal weights. counts[2] = vertices with n > 0, contributing (view, vertex)
+ * pairs. cfg's near and tol are checked and otherwise unused. */
+typedef struct sn_mesh_render_cfg {
+    int H, W;                  /* 1 .. 16384: the one image size of all views */
+    double near;               /* >= 0, finite: a corner at z <= near clips its triangle; a vertex at z <= near is not visible */
+    double tol;                /* >= 0, finite: rule 8's depth tolerance, in the units of z (about half a voxel for concave detail) */
+} sn_mesh_render_cfg;
+SN_API int sn_mesh_render(sn_ctx *ctx, const sn_mesh_render_cfg *cfg, int n_verts, const double *verts, int n_faces, int nv, const int32_t *faces,
+                          int V, const double *P, double *depth, int32_t *face, int32_t *face_pixels, unsigned char *vert_visible,
+                          long long *counts);
+SN_API int sn_mesh_render_dev(sn_ctx *ctx, const sn_mesh_render_cfg *cfg, int n_verts, const double *verts_dev, int n_faces, int nv,
+                              const int32_t *faces_dev, int V, const double *P_dev, double *depth_dev, int32_t *face_dev,
+                              int32_t *face_pixels_dev, unsigned char *vert_visible_dev, long long *counts);
+SN_API int sn_mesh_vertex_colors(sn_ctx *ctx, const sn_mesh_render_cfg *cfg, int n_verts, const double *verts, int n_faces, int nv,
+                                 const int32_t *faces, int V, const double *P, const unsigned char *vert_visible, int32_t *vert_views,
+                                 unsigned char *vert_rgb, long long *counts);
+SN_API int sn_mesh_vertex_colors_dev(sn_ctx *ctx, const sn_mesh_render_cfg *cfg, int n_verts, const double *verts_dev, int n_faces, int nv,
+                                     const int32_t *faces_dev, int V, const double *P_dev, const unsigned char *vert_visible_dev,
+                                     int32_t *vert_views_dev, unsigned char *vert_rgb_dev, long long *counts);
 
 /* ---- DTU point-cloud evaluation (experiments/DTU/eval_ply.m -> PointCompareMain of the DTU kit) ----------------------
  * Points are (n,3) float64, row-major, finite. d^2 = (dx*dx + dy*dy) + dz*dz in float64 without contraction: the results are those of the numpy

@@ -726,6 +726,61 @@ class Context(object):
         # (no face: either form returns at once and writes nothing, so there is nothing to stage or to copy back)
         return self._host_or_device("sn_mesh_orient", device and F > 0, (v, f), run, spec, lambda name, sizes: F, (), words=12)
 
+    def _render_args(self, verts, faces, cameraPOs, shape, near, tol):
+        """-> (verts, faces, P or None, V, cfg) of mesh_render and mesh_vertex_colors: cameraPOs (V,3,4), None = the cameras of set_cameras."""
+        v, f = self._mesh_arrays(verts, faces)
+        P = None if cameraPOs is None else np.ascontiguousarray(cameraPOs, dtype=np.float64)
+        if P is not None and (P.ndim != 3 or P.shape[1:] != (3, 4)):
+            raise ValueError("cameraPOs must have shape (V, 3, 4), got %s" % (P.shape,))
+        V = getattr(self, "n_cameras", 0) if P is None else P.shape[0]
+        return v, f, P, V, _lib.MeshRenderCfg(int(shape[0]), int(shape[1]), float(near), float(tol))
+
+    RENDER_OUTPUTS = ("depth", "face", "face_pixels", "vert_visible")
+
+    def mesh_render(self, verts, faces, cameraPOs, shape, near=0.0, tol=0.0, outputs=RENDER_OUTPUTS, device=False):
+        """A mesh rendered into V views of one size (sn_mesh_render): verts (n,3) float64 in world coordinates, faces
+        (F,3) or (F,4) int32, cameraPOs (V,3,4) float64 or None for the cameras of set_cameras, shape = (H, W), near >= 0, tol >= 0. Returns a
+        dict of those of `outputs` that were asked for - depth (V,H,W) float64 (0.0: empty), face (V,H,W) int32 (-1: empty), face_pixels (V,F)
+        int32, vert_visible (V,n) uint8 - and counts (8,) int64 = triangles, clipped, degenerate, rasterised, covering pairs, non-empty
+        pixels, visible (view, vertex) pairs, 0, summed over the views. device=True stages the mesh and the cameras in device memory here and
+        runs sn_mesh_render_dev on them: the same result."""
+        v, f, P, V, cfg = self._render_args(verts, faces, cameraPOs, shape, near, tol)
+        n, (F, nv), (H, W) = v.shape[0], f.shape, (cfg.H, cfg.W)
+        if set(outputs) - set(self.RENDER_OUTPUTS):
+            raise ValueError("outputs = %r: of %r" % (outputs, self.RENDER_OUTPUTS))
+        size = dict(depth=max(V, 0) * max(H, 0) * max(W, 0), face=max(V, 0) * max(H, 0) * max(W, 0), face_pixels=max(V, 0) * F, vert_visible=max(V, 0) * n)
+        shapes = dict(depth=(V, H, W), face=(V, H, W), face_pixels=(V, F), vert_visible=(V, n))
+        dtypes = dict(depth=np.float64, face=np.int32, face_pixels=np.int32, vert_visible=np.uint8)
+        spec = tuple((name, 1, dtypes[name]) for name in self.RENDER_OUTPUTS if name in outputs)
+
+        def run(fn, _, ins, outs, counts):
+            given = dict(zip([name for name, _, _ in spec], outs))
+            return fn(self._h, ctypes.byref(cfg), n, ins[0], F, nv, ins[1], V, ins[2] if P is not None else None,
+                      *[given.get(name) for name in self.RENDER_OUTPUTS], *counts)
+        out = self._host_or_device("sn_mesh_render", device, (v, f) + (() if P is None else (P,)), run, spec, lambda name, sizes: size[name], (), words=8)
+        for name, _, _ in spec:
+            out[name] = out[name].reshape(shapes[name])
+        return out
+
+    def mesh_vertex_colors(self, verts, faces, cameraPOs, shape, vert_visible, near=0.0, tol=0.0, device=False):
+        """The colour of every vertex from the views that see it (sn_mesh_vertex_colors): the mesh, cameras and shape
+        of mesh_render, vert_visible (V,n) - mesh_render's, or any other -, the images of set_images, which must be V images of H x W.
+        Returns a dict: vert_views (n,) int32 the contributing views, vert_rgb (n,3) uint8 the rounded mean of their nearest pixels ((0,0,0)
+        without a view), counts (2,) int64 = coloured vertices, contributing (view, vertex) pairs. device=True: sn_mesh_vertex_colors_dev."""
+        v, f, P, V, cfg = self._render_args(verts, faces, cameraPOs, shape, near, tol)
+        n, (F, nv) = v.shape[0], f.shape
+        vis = np.ascontiguousarray(vert_visible, dtype=np.uint8)
+        if vis.shape != (V, n):
+            raise ValueError("vert_visible must have shape (V, n_verts) = (%d, %d), got %s" % (V, n, vis.shape))
+        spec = (("vert_views", 1, np.int32), ("vert_rgb", 3, np.uint8))
+        k = 2 if P is None else 3
+
+        def run(fn, _, ins, outs, counts):
+            return fn(self._h, ctypes.byref(cfg), n, ins[0], F, nv, ins[1], V, ins[2] if P is not None else None, ins[k], *outs, *counts)
+        out = self._host_or_device("sn_mesh_vertex_colors", device, (v, f) + (() if P is None else (P,)) + (vis,), run, spec, lambda name, sizes: n, (), words=2)
+        out["vert_rgb"] = out["vert_rgb"].reshape(n, 3)
+        return out
+
     @staticmethod
     def _points(xyz):
         return np.ascontiguousarray(np.asarray(xyz, dtype=np.float64).reshape(-1, 3))

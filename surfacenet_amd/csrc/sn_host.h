@@ -207,3 +207,18 @@ static inline int mor_check_args(const sn_mesh_orient_cfg *cfg, int n_verts, int
     if (cfg->keep_largest != 0 && cfg->keep_largest != 1) return fail(SN_ERR_ARG, "keep_largest = %d: 0 or 1", cfg->keep_largest);
     return SN_OK;
 }
+
+// (sn_mesh_render and sn_mesh_vertex_colors have no lattice: world coordinates, one image size, V views; have_P: the caller gave cameras, so
+// V is the caller's - without them V is the context's and is judged there)
+static inline int mrd_check_args(const sn_mesh_render_cfg *cfg, int n_verts, int n_faces, int nv, bool have_P, int V)
+{
+    int rc;
+    if (!cfg) return fail(SN_ERR_ARG, "null cfg");
+    const double origin[3] = {0.0, 0.0, 0.0};
+    if ((rc = mesh_check_common(n_verts, n_faces, nv, origin, 1.0)) != SN_OK) return rc;
+    if (cfg->H < 1 || cfg->H > 16384 || cfg->W < 1 || cfg->W > 16384) return fail(SN_ERR_ARG, "H = %d, W = %d: 1 .. 16384 each", cfg->H, cfg->W);
+    if (have_P && V < 1) return fail(SN_ERR_ARG, "V = %d must be >= 1", V);
+    if (!std::isfinite(cfg->near) || !(cfg->near >= 0)) return fail(SN_ERR_ARG, "near = %g must be finite and >= 0", cfg->near);
+    if (!std::isfinite(cfg->tol) || !(cfg->tol >= 0)) return fail(SN_ERR_ARG, "tol = %g must be finite and >= 0", cfg->tol);
+    return SN_OK;
+}

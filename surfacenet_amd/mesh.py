@@ -8,6 +8,8 @@
     fill_holes         the mesh with its small holes capped: boundary loops and centroid fans
     mesh_normals       the normals of a mesh from the mesh itself, area-weighted, with its exact area and volume
     orient_mesh        the faces of a mesh made to turn one way, its pieces with their exact volumes, small pieces removed
+    render_mesh        the mesh back in its views: depth maps, face ids, the pixels of every face, the visible vertices
+    colour_vertices    the colour of every vertex from the views that see it
     chain_settings     the checked keywords of the stages that follow extract_mesh in a scene: fill, smooth, decimate, orient
     run_chain          those stages, each on the result of the one before it
     save_mesh_2ply     binary little-endian PLY of a quad or triangle mesh
@@ -411,6 +413,137 @@ def orient_mesh(vert_lattice, faces, sign="majority", min_faces=0, keep_largest=
     return res
 
 
+RENDER_COUNTS = ("n_triangles", "n_clipped", "n_degenerate", "n_rasterised", "n_pairs", "n_pixels", "n_visible")
+MAX_IMAGE_DIM = 16384
+
+
+def check_render_args(cameraPOs, shape, near=0.0, tol=0.0, views=None):
+    """-> (P (V',3,4) float64 - the cameras of `views`, all of them for None -, (H, W), near, tol, the views as a list) of render_mesh's
+    settings, or ValueError: cameraPOs (V,3,4) finite numbers, shape two integers in 1 .. 16384, near and tol finite and >= 0, views
+    distinct or not, each in [0, V), at least one."""
+    try:
+        P = np.asarray(cameraPOs, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("cameraPOs must be numbers of shape (V, 3, 4)")
+    if P.ndim != 3 or P.shape[1:] != (3, 4) or P.shape[0] < 1:
+        raise ValueError("cameraPOs must have shape (V, 3, 4) with V >= 1, got %r" % (P.shape,))
+    try:
+        H, W = shape
+        hw = (int(H), int(W))
+    except (TypeError, ValueError):
+        raise ValueError("shape = %r must be two integers (H, W)" % (shape,))
+    if isinstance(H, bool) or isinstance(W, bool) or hw != (H, W) or not (1 <= hw[0] <= MAX_IMAGE_DIM and 1 <= hw[1] <= MAX_IMAGE_DIM):
+        raise ValueError("shape = %r: (H, W), integers in 1 .. %d" % (shape, MAX_IMAGE_DIM))
+    out = []
+    for name, x in (("near", near), ("tol", tol)):
+        try:
+            val = float(x)
+        except (TypeError, ValueError):
+            raise ValueError("%s = %r must be a number" % (name, x))
+        if isinstance(x, bool) or not np.isfinite(val) or val < 0:
+            raise ValueError("%s = %r must be finite and >= 0" % (name, x))
+        out.append(val)
+    if views is None:
+        sel = list(range(P.shape[0]))
+    else:
+        try:
+            sel = [int(v) for v in views]
+        except (TypeError, ValueError):
+            raise ValueError("views = %r must be a sequence of view indices" % (views,))
+        if not sel or any(int(v) != v or isinstance(v, bool) or not 0 <= int(v) < P.shape[0] for v in views):
+            raise ValueError("views = %r: at least one index, each in [0, %d)" % (views, P.shape[0]))
+    P = np.ascontiguousarray(P[sel])
+    if not np.isfinite(P).all():
+        raise ValueError("cameraPOs of view %d is not finite" % sel[int(np.argmax(~np.isfinite(P).all(axis=(1, 2))))])
+    return P, hw, out[0], out[1], sel
+
+
+_RENDER_SETTING = dict(cameraPOs=None, shape=None, views=None, near=0.0, tol=None, images=None)
+
+
+def check_render_setting(value):
+    """reconstruct.scene_postpass's mesh_render -> all of its keywords, checked (check_render_args; tol None stays None: half the lattice's
+    resol; images: one (H,W,3) uint8 array of `shape` per camera), or ValueError. The library is not touched."""
+    words = "mesh_render = %r: a dict of cameraPOs, shape and optionally views, near, tol, images"
+    if not isinstance(value, dict) or set(value) - set(_RENDER_SETTING) or "cameraPOs" not in value or "shape" not in value:
+        raise ValueError(words % (value if not isinstance(value, dict) else sorted(value),))
+    kw = dict(_RENDER_SETTING, **value)
+    _, hw, _, _, _ = check_render_args(kw["cameraPOs"], kw["shape"], kw["near"], 0.0 if kw["tol"] is None else kw["tol"], kw["views"])
+    if kw["images"] is not None:
+        imgs = [np.asarray(im) for im in kw["images"]]
+        if len(imgs) != np.asarray(kw["cameraPOs"]).shape[0] or any(im.shape != hw + (3,) or im.dtype != np.uint8 for im in imgs):
+            raise ValueError("mesh_render: images must be one (%d, %d, 3) uint8 array per camera" % hw)
+    return kw
+
+
+def _world_mesh(vertices, faces):
+    """What render_mesh and colour_vertices ask of a mesh in world coordinates: _mesh_arrays, at most 2^28 of either, every face index in
+    [0, V), every coordinate of a referenced vertex finite - the first offending face is named, as the library names it."""
+    v, f = _mesh_arrays(vertices, faces, "vertices")
+    V, F = v.shape[0], f.shape[0]
+    if V > 1 << 28 or F > 1 << 28:
+        raise ValueError("%d vertices, %d faces: at most 2^28 of either" % (V, F))
+    if F:
+        bad = ((f < 0) | (f >= V)).any(axis=1)
+        if bad.any():
+            raise ValueError("face %d names a vertex outside [0, %d)" % (int(np.argmax(bad)), V))
+        bad = ~np.isfinite(v).all(axis=1)[f].all(axis=1)
+        if bad.any():
+            raise ValueError("face %d: a coordinate of one of its vertices is not finite" % int(np.argmax(bad)))
+    return v.astype(np.float64), f.astype(np.int32)
+
+
+def render_mesh(vertices, faces, cameraPOs, shape, near=0.0, tol=0.0, views=None):
+    """A mesh rendered back into the views it came from: vertices (n,3) float32 or float64 in WORLD coordinates (a
+    stage's "vertices", in mm), faces (F,3) triangles or (F,4) quads - a quad is its two triangles, face ids stay the quads' -, cameraPOs
+    (V,3,4), shape = (H, W) the one size of all views, near >= 0 (a triangle with a corner at z <= near vanishes whole), tol >= 0 the depth
+    tolerance of the vertex test (about half a voxel for concave detail), views the indices of the cameras to render (None: all). An
+    integer rasteriser with a watertight fill rule, perspective-correct depth in fp64: the result is the same on every run. -> dict: depth
+    (V',H,W) float64 (0.0 where no face is), face (V',H,W) int32 (-1 there), face_pixels (V',F) int32 the pixels a face wins, vert_visible
+    (V',n) bool, views the list of rendered views, and n_triangles, n_clipped, n_degenerate, n_rasterised, n_pairs, n_pixels, n_visible
+    summed over them. Limits: no clipping at the camera plane, one image size, vertices next to the silhouette count as visible, no
+    anti-aliasing. ValueError on bad shapes, dtypes, settings, face indices or coordinates before the library is touched."""
+    v, f = _world_mesh(vertices, faces)
+    P, (H, W), near, tol, sel = check_render_args(cameraPOs, shape, near, tol, views)
+    V = P.shape[0]
+    if v.shape[0] == 0:                                         # no vertex, so no face: nothing for the library to do
+        m = dict(depth=np.zeros((V, H, W), np.float64), face=np.full((V, H, W), -1, np.int32), face_pixels=np.zeros((V, f.shape[0]), np.int32),
+                 vert_visible=np.zeros((V, 0), np.uint8), counts=np.zeros((8,), np.int64))
+    else:
+        m = runtime.any_context().mesh_render(v, f, P, (H, W), near, tol)
+    res = dict(depth=m["depth"], face=m["face"], face_pixels=m["face_pixels"], vert_visible=m["vert_visible"].astype(bool), views=sel)
+    res.update({k: int(c) for k, c in zip(RENDER_COUNTS, m["counts"])})
+    return res
+
+
+def colour_vertices(vertices, faces, cameraPOs, images, vert_visible=None, near=0.0, tol=0.0, views=None):
+    """The colour of every vertex from the views that see it: the mesh and cameras of render_mesh, images a
+    sequence of V (H,W,3) uint8 RGB images of one size, one per camera, vert_visible (V',n) - render_mesh's for the same views, or any other
+    array; None renders first with near and tol. A view contributes the pixel nearest the vertex's projection when the vertex is visible in
+    it: equal weights, rounded mean. -> dict: vert_rgb (n,3) uint8 ((0,0,0) without a view), vert_views (n,) int32, n_coloured. The images
+    of `views` become the shared context's (Context.set_images). ValueError before the library is touched."""
+    v, f = _world_mesh(vertices, faces)
+    imgs = [np.asarray(im) for im in images]
+    if not imgs or any(im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8 or im.shape != imgs[0].shape for im in imgs):
+        raise ValueError("images must be (H, W, 3) uint8 RGB arrays of one size")
+    P, (H, W), near, tol, sel = check_render_args(cameraPOs, imgs[0].shape[:2], near, tol, views)
+    if len(imgs) != np.asarray(cameraPOs).shape[0]:
+        raise ValueError("%d images for %d cameras" % (len(imgs), np.asarray(cameraPOs).shape[0]))
+    n = v.shape[0]
+    if vert_visible is not None:
+        vis = np.asarray(vert_visible)
+        if vis.shape != (len(sel), n):
+            raise ValueError("vert_visible must have shape (%d, %d), not %r" % (len(sel), n, vis.shape))
+    if n == 0:
+        return dict(vert_rgb=np.zeros((0, 3), np.uint8), vert_views=np.zeros((0,), np.int32), n_coloured=0)
+    ctx = runtime.any_context()
+    if vert_visible is None:
+        vis = ctx.mesh_render(v, f, P, (H, W), near, tol, outputs=("vert_visible",))["vert_visible"]
+    ctx.set_images([imgs[k] for k in sel])
+    m = ctx.mesh_vertex_colors(v, f, P, (H, W), vis != 0, near, tol)
+    return dict(vert_rgb=m["vert_rgb"], vert_views=m["vert_views"], n_coloured=int(m["counts"][0]))
+
+
 # The chain that follows extract_mesh, in its order (DESIGN.md section 4.19). A row: the key of the stage's result, reconstruct.scene_postpass's
 # argument, the keyword a bare value stands for (a number, or orient's sign word), the defaults (their keys are the allowed ones), what a
 # refusal says the argument is, the check of the keywords, the stage, the letter of its PLY file's tag, and what the stage keeps of the mesh
@@ -525,12 +658,13 @@ def save_mesh_2ply(path, vertices, faces, normal_np=None, rgb_np=None):
         fh.write(frec.tobytes())
 
 
-def save_stage_2ply(path, m, normal_list, rgb_list=None, normals="source"):
+def save_stage_2ply(path, m, normal_list, rgb_list=None, normals="source", rgb_np=None):
     """save_mesh_2ply of a stage's mesh m - extract_mesh's dict or one of run_chain's - with the attributes of its vertices: every stage keeps
     vert_src, so a vertex's normal and colour are row vert_src of the concatenated per-voxel normal_list / rgb_list (None or empty: no
     colours), and zero where vert_src < 0 (mesh_reach > 0: a vertex with no oriented cell beside it). normals="mesh" writes the mesh's own
     normals in their place: mesh_normals of the stage's vert_lattice and faces, zero where that is zero; the
-    colours stay gathered. ValueError for any other value before a file is opened."""
+    colours stay gathered. ValueError for any other value before a file is opened. rgb_np (V,3) uint8 - colour_vertices' vert_rgb - is
+    written as the vertices' colours in the place of the gathered ones; None: as before."""
     check_normals_arg(normals)
     src = m["vert_src"]
 
@@ -539,4 +673,4 @@ def save_stage_2ply(path, m, normal_list, rgb_list=None, normals="source"):
         a[src < 0] = 0
         return a
     nrm = mesh_normals(m["vert_lattice"], _faces(m))["vert_normals"] if normals == "mesh" else gather(normal_list, np.float32)
-    save_mesh_2ply(path, m["vertices"], _faces(m), normal_np=nrm, rgb_np=gather(rgb_list, np.uint8) if rgb_list else None)
+    save_mesh_2ply(path, m["vertices"], _faces(m), normal_np=nrm, rgb_np=rgb_np if rgb_np is not None else (gather(rgb_list, np.uint8) if rgb_list else None))

@@ -566,7 +566,7 @@ def reconstruct_scene(images_list, cameraPOs_np, cubes_param_np, cube_D_mm, cube
 def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, gamma=0.8, beta=6, N_refine_iter=8, init_probThresh=0.5,
                    max_probThresh=0.9, keep_iterations=False, cameraTs_np=None, cube_overlapping_ratio=0.5, unique=False, mesh=False, mesh_radius=2,
                    mesh_reach=0, mesh_ply_prefix=None, min_component=None, component_connectivity=26, mesh_cell=None, mesh_placement="mean",
-                   mesh_smooth=None, mesh_fill=None, mesh_normals="source", mesh_orient=None):
+                   mesh_smooth=None, mesh_fill=None, mesh_normals="source", mesh_orient=None, mesh_render=None):
     """The reconstruction's last two stages on `reconstruct_scene`'s dict, in memory and on the GPU, as the reference runs them on its files:
       * main_reconstruct.py:172-175  thinning masks (prob >= tau, votes >= gamma * N_vp * 2), then denoise_crossCubes with D_cube = cube_D
       * main.py:37-43 -> utils/adapthresh.py  adaptive thresholding with D_cube = cube_Dcenter, init / max threshold init_probThresh /
@@ -609,7 +609,12 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
         adds no key and writes no file): fixThresh_mesh_oriented, adapt_mesh_oriented - the last mesh of the chain (fill, smooth, decimate,
         then orient) with mesh.orient_mesh's kept, oriented faces in the place of its faces (quads stay quads) and orient_mesh's other keys
         beside them: n_inconsistent = 0 and n_flipped_faces = 0 say that the chain kept the mesher's orientation; with mesh_ply_prefix also
-        written as <prefix>fixThresh_mesh_o.ply / <prefix>adapt_mesh_o.ply."""
+        written as <prefix>fixThresh_mesh_o.ply / <prefix>adapt_mesh_o.ply.
+      mesh_render=dict(cameraPOs=, shape=(H, W), views=None, near=0.0, tol=None, images=None) (needs mesh=True; the
+        default None adds no key and writes no file): fixThresh_mesh_render, adapt_mesh_render - mesh.render_mesh of the LAST mesh of the chain
+        (the mesh of mesh=True without a chain) in world mm: depth, face, face_pixels, vert_visible, views and the counts; tol=None is half
+        the lattice's resol. With images (one (H,W,3) uint8 per camera) also vert_rgb and vert_views of mesh.colour_vertices with that
+        visibility, and with mesh_ply_prefix too <prefix>fixThresh_mesh_v.ply / <prefix>adapt_mesh_v.ply: the last mesh with those colours."""
     from . import adapthresh, denoising, sparseCubes
     from . import mesh as _mesh
     from . import normals as _normals
@@ -618,11 +623,12 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
         raise ValueError("mesh=True needs cameraTs_np: the mesher reads the oriented normals")
     for arg, value, does in (("mesh_cell", mesh_cell, "simplifies"), ("mesh_smooth", mesh_smooth, "smooths"), ("mesh_fill", mesh_fill, "fills the holes of"),
                              ("mesh_normals", None if mesh_normals == "source" else mesh_normals, "takes its normals from"),
-                             ("mesh_orient", mesh_orient, "orients")):
+                             ("mesh_orient", mesh_orient, "orients"), ("mesh_render", mesh_render, "renders")):
         if value is not None and not mesh:
             raise ValueError("%s needs mesh=True: it %s the mesh that mesh=True extracts" % (arg, does))
     stages = _mesh.chain_settings(mesh_fill, mesh_smooth, mesh_cell, mesh_placement, mesh_orient)      # fill, smooth, decimate, orient: those asked for
     _mesh.check_normals_arg(mesh_normals, "mesh_normals")
+    render = None if mesh_render is None else _mesh.check_render_setting(mesh_render)
     ply_tags = dict([("", "")] + [("_" + key, _mesh.stage_tag(key, kw)) for key, kw in stages])      # result key's ending -> file name's
     if min_component is not None:
         from . import components as _components
@@ -670,7 +676,7 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
             res[name + "_unique_list"] = _normals.unique_voxels(cube_ijk, ijk_l, masks, stride_vox) if n else []
         if mesh:
             m = _mesh.extract_mesh(cube_ijk, ijk_l, masks, normal_l, out["param_np"], stride_vox, mesh_radius, mesh_reach) if n else _mesh.empty_mesh()
-            if n and (stages or mesh_normals == "mesh") and lattice is None:                # (once: the lattice that extract_mesh has just accepted)
+            if n and (stages or mesh_normals == "mesh" or render is not None) and lattice is None:      # (once: the lattice that extract_mesh has just accepted)
                 lattice = _mesh.lattice_origin(cube_ijk, out["param_np"], stride_vox)
             chain = _mesh.run_chain(m, stages, *(lattice or ((0.0, 0.0, 0.0), 1.0)))
             for end, stage_mesh in [("", m)] + [("_" + key, chain[key]) for key in chain]:
@@ -681,6 +687,17 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
                 if mesh_ply_prefix is not None and n:
                     _mesh.save_stage_2ply("%s%s_mesh%s.ply" % (mesh_ply_prefix, name, ply_tags[end]), stage_mesh, normal_l, out.get("rgb_list"),
                                           normals=mesh_normals)
+            if render is not None:                              # the last mesh of the chain, back in its views
+                last = chain[stages[-1][0]] if stages else m
+                tol = render["tol"] if render["tol"] is not None else (0.5 * lattice[1] if lattice else 0.0)
+                r = _mesh.render_mesh(last["vertices"], _mesh._faces(last), render["cameraPOs"], render["shape"], render["near"], tol, render["views"])
+                if render["images"] is not None:
+                    col = _mesh.colour_vertices(last["vertices"], _mesh._faces(last), render["cameraPOs"], render["images"], r["vert_visible"],
+                                                render["near"], tol, render["views"])
+                    r.update(vert_rgb=col["vert_rgb"], vert_views=col["vert_views"])
+                    if mesh_ply_prefix is not None and n:
+                        _mesh.save_stage_2ply("%s%s_mesh_v.ply" % (mesh_ply_prefix, name), last, normal_l, normals=mesh_normals, rgb_np=r["vert_rgb"])
+                res[name + "_mesh_render"] = r
     return res
 
 
