@@ -55,12 +55,11 @@ static __global__ void __launch_bounds__(PC_NT) pc_bitonic_tile_kernel(unsigned 
 static int pc_sort(sn_ctx *c, unsigned long long *list, long long n)
 {
     ProfScope ps(c, "pc_sort", 0, 0.0);
-    hipLaunchKernelGGL(pc_bitonic_tile_kernel, dim3((unsigned)(n / PC_TILE)), dim3(PC_NT), 0, c->stream, list, 2ll, (long long)PC_TILE);
+    LAUNCH(pc_bitonic_tile_kernel, dim3((unsigned)(n / PC_TILE)), dim3(PC_NT), list, 2ll, (long long)PC_TILE);
     for (long long k = 2 * PC_TILE; k <= n; k <<= 1) {
         for (long long j = k / 2; j >= PC_TILE; j >>= 1)
-            hipLaunchKernelGGL(pc_bitonic_global_kernel, dim3((unsigned)((n / 2 + PC_NT - 1) / PC_NT)), dim3(PC_NT), 0, c->stream, list, n, j, k);
-        hipLaunchKernelGGL(pc_bitonic_tile_kernel, dim3((unsigned)(n / PC_TILE)), dim3(PC_NT), 0, c->stream, list, k, k);
+            LAUNCH(pc_bitonic_global_kernel, dim3((unsigned)((n / 2 + PC_NT - 1) / PC_NT)), dim3(PC_NT), list, n, j, k);
+        LAUNCH(pc_bitonic_tile_kernel, dim3((unsigned)(n / PC_TILE)), dim3(PC_NT), list, k, k);
     }
-    HIPCHK(hipGetLastError());
     return SN_OK;
 }

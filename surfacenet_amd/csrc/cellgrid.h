@@ -202,15 +202,13 @@ static int grid_build(sn_ctx *c, const CGBufs<S> &b, const CellGrid<S> &g, const
     a.h = g.h; a.mask = g.mask; a.n = b.n;
     a.xyz = xyz_dev; a.rank = rank_dev; a.keys = b.keys; a.start = b.start; a.count = b.count; a.slot = b.slot; a.pos = b.pos; a.idx = b.idx;
     a.rank_s = b.rank_s; a.xyz_s = b.xyz_s; a.occupied = occ_dev;
-    HIPCHK(hipMemsetAsync(b.keys, 0xff, sizeof(unsigned long long) * b.cap, c->stream));
-    HIPCHK(hipMemsetAsync(b.count, 0, sizeof(int) * b.cap, c->stream));
-    if (occ_dev) HIPCHK(hipMemsetAsync(occ_dev, 0, sizeof(int), c->stream));
-    hipLaunchKernelGGL(cg_insert_kernel<S>, dim3(blocks(b.n, CG_NT)), dim3(CG_NT), 0, c->stream, a);
-    HIPCHK(hipGetLastError());
+    HIPCHK(dev_fill(c, b.keys, 0xff, b.cap));
+    HIPCHK(dev_fill(c, b.count, 0, b.cap));
+    if (occ_dev) HIPCHK(dev_fill(c, occ_dev, 0, 1));
+    LAUNCH(cg_insert_kernel<S>, dim3(blocks(b.n, CG_NT)), dim3(CG_NT), a);
     if (!sort) return SN_OK;
     int rc = scan_exclusive(c, b.count, b.start, (int)b.cap, b.sums);
     if (rc != SN_OK) return rc;
-    hipLaunchKernelGGL(cg_scatter_kernel<S>, dim3(blocks(b.n, CG_NT)), dim3(CG_NT), 0, c->stream, a);
-    HIPCHK(hipGetLastError());
+    LAUNCH(cg_scatter_kernel<S>, dim3(blocks(b.n, CG_NT)), dim3(CG_NT), a);
     return SN_OK;
 }

@@ -39,34 +39,30 @@ int msm_build(sn_ctx *c, const MsmArgs &a, size_t cap)
     const int V = a.V, F = a.F, nv = a.nv;
     const unsigned vb = blocks(V, MSM_NT), fb = blocks(F, MSM_NT), sb = blocks((long long)cap, MSM_NT);
     const unsigned loop_blocks = (unsigned)std::max(c->num_cus, 1) * 8u;      // the grid-stride kernels: eight workgroups per CU at most
-    HIPCHK(hipMemsetAsync(a.st, 0, sizeof(MsmStat), c->stream));
+    HIPCHK(dev_fill(c, a.st, 0, 1));
     HIPCHK(hipMemsetAsync(a.st, 0xff, 2 * sizeof(unsigned long long), c->stream));      // first_bad, bad_vertex = MESH_NO_BAD
     {
         ProfScope ps(c, "msm_mark", 0, (double)F * nv * 8.0 + (double)V * (28.0 + 8.0 * REC));
-        HIPCHK(hipMemsetAsync(a.vfl, 0, sizeof(unsigned) * std::max<size_t>((size_t)V, 1), c->stream));
+        HIPCHK(dev_fill(c, a.vfl, 0, std::max<size_t>((size_t)V, 1)));
         if (F > 0) {
-            hipLaunchKernelGGL(msm_mark_kernel, dim3(fb), dim3(MSM_NT), 0, c->stream, a);
-            HIPCHK(hipGetLastError());
+            LAUNCH(msm_mark_kernel, dim3(fb), dim3(MSM_NT), a);
         }
         if (V > 0) {
-            hipLaunchKernelGGL(msm_quantise_kernel<REC>, dim3(std::min(vb, loop_blocks)), dim3(MSM_NT), 0, c->stream, a);
-            HIPCHK(hipGetLastError());
+            LAUNCH(msm_quantise_kernel<REC>, dim3(std::min(vb, loop_blocks)), dim3(MSM_NT), a);
         }
     }
     {
         ProfScope ps(c, "msm_edges", 0, (double)F * nv * 28.0 + (double)cap * 20.0);
-        HIPCHK(hipMemsetAsync(a.tab, 0, sizeof(unsigned long long) * 2 * cap, c->stream));
-        HIPCHK(hipMemsetAsync(a.sides, 0, sizeof(unsigned) * cap, c->stream));
+        HIPCHK(dev_fill(c, a.tab, 0, 2 * cap));
+        HIPCHK(dev_fill(c, a.sides, 0, cap));
         if (F > 0) {
-            hipLaunchKernelGGL(msm_edges_kernel, dim3(fb), dim3(MSM_NT), 0, c->stream, a);
-            HIPCHK(hipGetLastError());
+            LAUNCH(msm_edges_kernel, dim3(fb), dim3(MSM_NT), a);
         }
     }
     {
         ProfScope ps(c, "msm_degree", 0, (double)cap * 12.0 + (double)V * 12.0);
-        HIPCHK(hipMemsetAsync(a.deg, 0, sizeof(int) * ((size_t)V + 1), c->stream));
-        hipLaunchKernelGGL(msm_degree_kernel, dim3(std::min(sb, loop_blocks)), dim3(MSM_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        HIPCHK(dev_fill(c, a.deg, 0, (size_t)V + 1));
+        LAUNCH(msm_degree_kernel, dim3(std::min(sb, loop_blocks)), dim3(MSM_NT), a);
     }
     return SN_OK;
 }

@@ -53,15 +53,12 @@ static int scan_exclusive(sn_ctx *c, const int *in, int *out, int n, int *sums)
 {
     const int nb = (n + SCAN_ELEMS - 1) / SCAN_ELEMS;
     if (nb <= 1) {
-        hipLaunchKernelGGL(scan_block_kernel, dim3(1), dim3(SCAN_NT), 0, c->stream, in, out, n, (int *)nullptr);
-        HIPCHK(hipGetLastError());
+        LAUNCH(scan_block_kernel, dim3(1), dim3(SCAN_NT), in, out, n, (int *)nullptr);
         return SN_OK;
     }
-    hipLaunchKernelGGL(scan_block_kernel, dim3((unsigned)nb), dim3(SCAN_NT), 0, c->stream, in, out, n, sums);
-    HIPCHK(hipGetLastError());
+    LAUNCH(scan_block_kernel, dim3((unsigned)nb), dim3(SCAN_NT), in, out, n, sums);
     int rc = scan_exclusive(c, sums, sums, nb, sums + nb);
     if (rc != SN_OK) return rc;
-    hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)((n + SCAN_NT - 1) / SCAN_NT)), dim3(SCAN_NT), 0, c->stream, out, n, (const int *)sums);
-    HIPCHK(hipGetLastError());
+    LAUNCH(scan_add_kernel, dim3((unsigned)((n + SCAN_NT - 1) / SCAN_NT)), dim3(SCAN_NT), out, n, (const int *)sums);
     return SN_OK;
 }

@@ -63,9 +63,7 @@ static int launch_pool(sn_ctx *c, const char *tag, Act in, Act out, int B, int D
 {
     const long long total = (long long)B * (D / 2) * (D / 2) * (D / 2) * (C / 8);
     ProfScope ps(c, tag, 0, (double)B * D * D * D * C * 2.0 * 1.125 * (SPLIT ? 2 : 1));
-    hipLaunchKernelGGL((maxpool2_kernel<SPLIT>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, in.p, out.p, D, C,
-                       total, in.lo, out.lo);
-    HIPCHK(hipGetLastError());
+    LAUNCH((maxpool2_kernel<SPLIT>), dim3((unsigned)((total + 255) / 256)), dim3(256), in.p, out.p, D, C, total, in.lo, out.lo);
     return SN_OK;
 }
 
@@ -76,12 +74,11 @@ static int launch_up3(sn_ctx *c, Act s2, Act s3, Act s4, Act cat, int B, int Do,
     ProfScope ps(c, "side_op234_deconv", 0, (double)B * Do * Do * Do * 48 * 2.0 * (SPLIT ? 2 : 1));
     static const bool per_voxel = sn_ab_switch("SN_UPSAMPLE_PER_VOXEL") != nullptr;       // A/B: the round-1 kernel (one thread per output voxel, corners from L2)
     if (Do % 8 == 0 && Do <= 64 && !per_voxel)
-        hipLaunchKernelGGL((upsample3_cat_tiled_kernel<SPLIT, OSPLIT>), dim3((unsigned)(B * 6 * (Do / 8) * (Do / 8))), dim3(256), 0, c->stream, s2.p, s3.p, s4.p,
-                           cat.p, Do, cat_cs, s2.lo, s3.lo, s4.lo, cat.lo, c->mx_cat_e8);
+        LAUNCH((upsample3_cat_tiled_kernel<SPLIT, OSPLIT>), dim3((unsigned)(B * 6 * (Do / 8) * (Do / 8))), dim3(256), s2.p, s3.p, s4.p,
+               cat.p, Do, cat_cs, s2.lo, s3.lo, s4.lo, cat.lo, c->mx_cat_e8);
     else
-    hipLaunchKernelGGL((upsample3_cat_kernel<SPLIT, OSPLIT>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, s2.p, s3.p, s4.p,
-                       cat.p, Do, cat_cs, total, s2.lo, s3.lo, s4.lo, cat.lo, c->mx_cat_e8);
-    HIPCHK(hipGetLastError());
+        LAUNCH((upsample3_cat_kernel<SPLIT, OSPLIT>), dim3((unsigned)((total + 255) / 256)), dim3(256), s2.p, s3.p, s4.p,
+               cat.p, Do, cat_cs, total, s2.lo, s3.lo, s4.lo, cat.lo, c->mx_cat_e8);
     return SN_OK;
 }
 
@@ -226,9 +223,8 @@ static int launch_fuse(sn_ctx *c, const float *unf, const float *w_dev, float *f
     const int s3 = c->s * c->s * c->s;
     const long long total = (long long)n * s3;
     ProfScope ps(c, "fusion", 0, (double)total * 4.0 * (n_vp + 1));
-    hipLaunchKernelGGL(fuse_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, unf,
-                       n_vp == 1 ? (const float *)nullptr : w_dev, fused, n_vp, s3, total);
-    HIPCHK(hipGetLastError());
+    LAUNCH(fuse_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), unf,
+           n_vp == 1 ? (const float *)nullptr : w_dev, fused, n_vp, s3, total);
     return SN_OK;
 }
 
@@ -253,8 +249,7 @@ static int launch_cvc(sn_ctx *c, int n, int n_vp, const int64_t *pairs_dev, cons
     // algorithmic bytes: 2 views x s^3 x 3 B gathered + written planes
     const double bytes = samples * s3 * (6.0 + (out_ncdhw ? 24.0 : 0.0) + (out_x0 ? 16.0 * (c->split ? 2 : 1) : 0.0));
     ProfScope ps(c, "cvc_warp", 0, bytes);
-    hipLaunchKernelGGL(cvc_warp_kernel, dim3((unsigned)((s3 + 255) / 256), (unsigned)(n * n_vp)), dim3(256), 0, c->stream, a);
-    HIPCHK(hipGetLastError());
+    LAUNCH(cvc_warp_kernel, dim3((unsigned)((s3 + 255) / 256), (unsigned)(n * n_vp)), dim3(256), a);
     return SN_OK;
 }
 
@@ -478,13 +473,12 @@ int sn_calibrate_dev(sn_ctx *c, int n_samples, double max_sat_fraction, sn_calib
     TmpDev tmp;
     unsigned long long *d_hist = tmp.out<unsigned long long>(NT * HB);
     if (!tmp.ok) return fail(SN_ERR_HIP, "out of device memory");
-    HIPCHK(hipMemsetAsync(d_hist, 0, sizeof(unsigned long long) * NT * HB, c->stream));
+    HIPCHK(dev_fill(c, d_hist, 0, NT * HB));
     const _Float16 *tens[NT] = {c->ma, c->cat};
     const long long halfs[NT] = {(long long)n_samples * vox * 104, (long long)n_samples * vox * 64};
     for (int t = 0; t < NT; ++t)
-        hipLaunchKernelGGL(mx_scan_kernel, dim3((unsigned)std::min<long long>(2048, (halfs[t] / 8 + 255) / 256)), dim3(256), 0, c->stream, tens[t], halfs[t], lim,
-                           d_hist + t * HB);
-    HIPCHK(hipGetLastError());
+        LAUNCH(mx_scan_kernel, dim3((unsigned)std::min<long long>(2048, (halfs[t] / 8 + 255) / 256)), dim3(256), tens[t], halfs[t], lim,
+               d_hist + t * HB);
     unsigned long long h[NT][HB];
     HIPCHK(hipMemcpyAsync(h, d_hist, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -709,9 +703,8 @@ int sn_forward_dev(sn_ctx *c, int n, int n_vp, const float *X_dev, const float *
     const int S = n * n_vp, s3 = c->s * c->s * c->s;
     {
         ProfScope ps(c, "ncdhw_to_x0", 0, (double)S * s3 * (24.0 + 16.0));
-        hipLaunchKernelGGL(ncdhw_to_x0_kernel, dim3((unsigned)((s3 + 255) / 256), (unsigned)S), dim3(256), 0, c->stream, X_dev, c->x0, s3, S,
-                           c->split ? (long long)c->max_samples * s3 * 8 : 0LL, c->split);
-        HIPCHK(hipGetLastError());
+        LAUNCH(ncdhw_to_x0_kernel, dim3((unsigned)((s3 + 255) / 256), (unsigned)S), dim3(256), X_dev, c->x0, s3, S,
+               c->split ? (long long)c->max_samples * s3 * 8 : 0LL, c->split);
     }
     float *unf = unfused_dev ? unfused_dev : c->unf_ws;
     if ((rc = run_net(c, S, unf)) != SN_OK) return rc;
@@ -853,11 +846,9 @@ int sn_relative_weights(sn_ctx *c, int n, int n_vp, const float *features, float
     int rc = m.inputs([&](Carve &w) { m.in(w, features, rows * kDFeature); d_z = w.get<float>(rows); });
     if (rc != SN_OK) return rc;
     if ((rc = m.outputs([&](Carve &w) { m.out(w, weights, rows); })) != SN_OK) return rc;
-    hipLaunchKernelGGL(relw_mlp_kernel, dim3((unsigned)rows), dim3(128), 0, c->stream, features, c->relw_W1, c->relw_scale, c->relw_shift,
-                       c->relw_w2, c->relw_b2, d_z, kDFeature, kHidden);
-    hipLaunchKernelGGL(relw_softmax_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, c->stream, d_z, weights, n, n_vp);
-    HIPCHK(hipGetLastError());
-    if ((rc = m.back(weights, rows)) != SN_OK) return rc;
+    LAUNCH(relw_mlp_kernel, dim3((unsigned)rows), dim3(128), features, c->relw_W1, c->relw_scale, c->relw_shift,
+           c->relw_w2, c->relw_b2, d_z, kDFeature, kHidden);
+    LAUNCH(relw_softmax_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), d_z, weights, n, n_vp);
     return m.finish();
 }
 
@@ -889,12 +880,10 @@ int sn_viewpair_weights(sn_ctx *c, int n_cubes, int n_views, const float *embedd
     if ((rc = m.outputs([&](Carve &w) { m.out(w, weights, rows); })) != SN_OK) return rc;
     {
         ProfScope ps(c, "relw_mlp_pairs", 2.0 * rows * kDFeature * kHidden, (double)rows * 12.0 + (double)ne * 4.0);
-        hipLaunchKernelGGL(relw_mlp_pairs_kernel, dim3((unsigned)rows), dim3(128), 0, c->stream, embeddings, d_p, dissimilarity, theta, n_views, P,
-                           c->relw_W1, c->relw_scale, c->relw_shift, c->relw_w2, c->relw_b2, d_z, kHidden);
-        hipLaunchKernelGGL(relw_softmax_kernel, dim3((unsigned)((n_cubes + 127) / 128)), dim3(128), 0, c->stream, d_z, weights, n_cubes, P);
-        HIPCHK(hipGetLastError());
+        LAUNCH(relw_mlp_pairs_kernel, dim3((unsigned)rows), dim3(128), embeddings, d_p, dissimilarity, theta, n_views, P,
+               c->relw_W1, c->relw_scale, c->relw_shift, c->relw_w2, c->relw_b2, d_z, kHidden);
+        LAUNCH(relw_softmax_kernel, dim3((unsigned)((n_cubes + 127) / 128)), dim3(128), d_z, weights, n_cubes, P);
     }
-    if ((rc = m.back(weights, rows)) != SN_OK) return rc;
     return m.finish();
 }
 
@@ -910,9 +899,8 @@ int sn_color_fuse_dev(sn_ctx *c, int n, int n_vp, const float *cvc_dev, const fl
     const int s3 = c->s * c->s * c->s;
     const long long total = (long long)n * s3;
     ProfScope ps(c, "color_fuse", 0, (double)total * (n_vp * 28.0 + 3.0));
-    hipLaunchKernelGGL(color_fuse_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, cvc_dev, unfused_dev, w_dev,
-                       rgb_dev, n_vp, s3, total, m[0], m[1], m[2], m[3], m[4], m[5]);
-    HIPCHK(hipGetLastError());
+    LAUNCH(color_fuse_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), cvc_dev, unfused_dev, w_dev,
+           rgb_dev, n_vp, s3, total, m[0], m[1], m[2], m[3], m[4], m[5]);
     return SN_OK;
 }
 
@@ -928,7 +916,7 @@ int sn_color_fuse(sn_ctx *c, int n, int n_vp, const float *cvc, const float *mea
     int rc = m.inputs([&](Carve &cv) { m.in(cv, cvc, 6 * s3 * R); m.in(cv, unfused, s3 * R); m.in(cv, w, R); });
     if (rc != SN_OK) return rc;
     if ((rc = m.outputs([&](Carve &cv) { m.out(cv, rgb, 3 * s3 * n); })) != SN_OK) return rc;
-    if ((rc = sn_color_fuse_dev(c, n, n_vp, cvc, mean6, unfused, w, rgb)) != SN_OK || (rc = m.back(rgb, 3 * s3 * n)) != SN_OK) return rc;
+    if ((rc = sn_color_fuse_dev(c, n, n_vp, cvc, mean6, unfused, w, rgb)) != SN_OK) return rc;
     return m.finish();
 }
 

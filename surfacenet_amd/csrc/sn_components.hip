@@ -61,10 +61,9 @@ int cp_run(sn_ctx *c, CPCall &k, const sn_components_cfg *cfg, long long *C)
 {
     const int n = k.n;
     const long long total = k.total;
-    HIPCHK(hipMemsetAsync(k.flags, 0, sizeof(int), c->stream));
-    hipLaunchKernelGGL(nm_check_kernel, dim3((unsigned)(n / NM_NT + 1)), dim3(NM_NT), 0, c->stream, k.off, n, total, (const int32_t *)nullptr, 0,
-                       (const double *)nullptr, 0, (double *)nullptr, k.flags);
-    HIPCHK(hipGetLastError());
+    HIPCHK(dev_fill(c, k.flags, 0, 1));
+    LAUNCH(nm_check_kernel, dim3((unsigned)(n / NM_NT + 1)), dim3(NM_NT), k.off, n, total, (const int32_t *)nullptr, 0,
+           (const double *)nullptr, 0, (double *)nullptr, k.flags);
     const unsigned nb = blocks(total, NM_NT);
     if (total > 0) {
         NMArgs a;
@@ -72,13 +71,11 @@ int cp_run(sn_ctx *c, CPCall &k, const sn_components_cfg *cfg, long long *C)
         a.off = k.off; a.ijk = k.ijk; a.cube_ijk = k.cube_ijk; a.mask = k.mask; a.cube_of = k.cube_of; a.tab = k.tab; a.flags = k.flags;
         a.total = total; a.hmask = k.cap - 1; a.n = n; a.stride = cfg->stride_vox; a.radius = 1;      // the link kernel probes g + 1
         ProfScope ps(c, "cp_cells", 0, (double)total * 12.0 + (double)k.cap * 16.0);
-        HIPCHK(hipMemsetAsync(k.tab, 0, sizeof(unsigned long long) * 2 * (size_t)k.cap, c->stream));
-        hipLaunchKernelGGL(nm_insert_kernel<true>, dim3(nb), dim3(NM_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        HIPCHK(dev_fill(c, k.tab, 0, 2 * (size_t)k.cap));
+        LAUNCH(nm_insert_kernel<true>, dim3(nb), dim3(NM_NT), a);
     }
     int flags = 0;
-    HIPCHK(hipMemcpyAsync(&flags, k.flags, sizeof flags, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(read_status(c, &flags, k.flags));
     if (flags & NM_FLAG_TABLE) return fail(SN_ERR_ARG, "offsets table does not start at 0, decreases, or does not end at total = %lld", total);
     if (flags & NM_FLAG_CELL)
         return fail(SN_ERR_ARG, "a masked voxel's world cell (cube_ijk * %d + vxl_ijk) plus 1 reaches 2^%d on an axis", cfg->stride_vox, LT_AXIS_BITS);
@@ -92,19 +89,16 @@ int cp_run(sn_ctx *c, CPCall &k, const sn_components_cfg *cfg, long long *C)
     a.min_cells = cfg->min_cells;
     {
         ProfScope ps(c, "cp_init", 0, (double)total * 20.0);
-        HIPCHK(hipMemsetAsync(k.count, 0, sizeof(int) * (2 * (size_t)total + 1), c->stream));
-        hipLaunchKernelGGL(cp_init_kernel, dim3(nb), dim3(NM_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        HIPCHK(dev_fill(c, k.count, 0, 2 * (size_t)total + 1));
+        LAUNCH(cp_init_kernel, dim3(nb), dim3(NM_NT), a);
     }
     {
         ProfScope ps(c, "cp_link", 0, (double)total * 8.0);
-        hipLaunchKernelGGL(cp_link_kernel, dim3(nb), dim3(NM_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        LAUNCH(cp_link_kernel, dim3(nb), dim3(NM_NT), a);
     }
     {
         ProfScope ps(c, "cp_root", 0, (double)total * 16.0);
-        hipLaunchKernelGGL(cp_root_kernel, dim3(nb), dim3(NM_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        LAUNCH(cp_root_kernel, dim3(nb), dim3(NM_NT), a);
     }
     {
         ProfScope ps(c, "cp_number", 0, (double)total * 8.0);
@@ -113,12 +107,10 @@ int cp_run(sn_ctx *c, CPCall &k, const sn_components_cfg *cfg, long long *C)
     }
     {
         ProfScope ps(c, "cp_write", 0, (double)total * 21.0);
-        hipLaunchKernelGGL(cp_write_kernel, dim3(nb), dim3(NM_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        LAUNCH(cp_write_kernel, dim3(nb), dim3(NM_NT), a);
     }
     int nc = 0;
-    HIPCHK(hipMemcpyAsync(&nc, k.number + total, sizeof nc, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(read_status(c, &nc, k.number + total));
     *C = nc;
     return SN_OK;
 }
@@ -136,7 +128,6 @@ int cp_call(sn_ctx *c, bool host, CPCall &k, const sn_components_cfg *cfg, long 
     if ((rc = dev_carve(c, c->cp_ws, [&](Carve &w) { cp_layout(w, k); }, 256)) != SN_OK) return rc;
     long long C = 0;
     if ((rc = cp_run(c, k, cfg, &C)) != SN_OK) return rc;
-    if ((rc = m.back(k.label, T)) != SN_OK || (rc = m.back(k.cells, T)) != SN_OK || (rc = m.back(k.keep, T)) != SN_OK) return rc;
     if ((rc = m.finish()) != SN_OK) return rc;
     *n_components = C;
     return SN_OK;

@@ -49,15 +49,13 @@ int cc_denoise(sn_ctx *c, CCWork &w, int D_cube, long long total, const int64_t 
     const unsigned nb256 = (unsigned)((n + 255) / 256);
     {
         ProfScope ps(c, "cc_grid", 0, (double)total * 5.0 + (double)n * Dc * Dc * 8.0);
-        hipLaunchKernelGGL(cc_grid_kernel, dim3((unsigned)n), dim3(CC_NT), (size_t)Dc * Dc * 8, c->stream, g);
-        HIPCHK(hipGetLastError());
+        LAUNCH_LDS(cc_grid_kernel, dim3((unsigned)n), dim3(CC_NT), (size_t)Dc * Dc * 8, g);
     }
-    HIPCHK(hipMemsetAsync(w.tab, 0xff, sizeof(int) * (size_t)w.cap, c->stream));
+    HIPCHK(dev_fill(c, w.tab, 0xff, (size_t)w.cap));
     {
         ProfScope ps(c, "cc_map", 0, (double)n * 27.0 * 16.0);
-        hipLaunchKernelGGL(cc_map_insert_kernel, dim3(nb256), dim3(256), 0, c->stream, cube_ijk, w.nonempty, n, w.tab, w.hmask);
-        hipLaunchKernelGGL(cc_map_neighbours_kernel, dim3(nb256), dim3(256), 0, c->stream, cube_ijk, w.tab, w.hmask, n, w.mapped, w.nbr26, face6);
-        HIPCHK(hipGetLastError());
+        LAUNCH(cc_map_insert_kernel, dim3(nb256), dim3(256), cube_ijk, w.nonempty, n, w.tab, w.hmask);
+        LAUNCH(cc_map_neighbours_kernel, dim3(nb256), dim3(256), cube_ijk, w.tab, w.hmask, n, w.mapped, w.nbr26, face6);
     }
     CCDenoiseArgs a;
     memset(&a, 0, sizeof a);
@@ -65,10 +63,9 @@ int cc_denoise(sn_ctx *c, CCWork &w, int D_cube, long long total, const int64_t 
     a.total = total; a.n = n; a.Dc = Dc; a.h = D_cube / 2;
     ProfScope ps(c, "cc_denoise", 0, (double)total * 6.0 + (double)n * Dc * Dc * 8.0 * 27.0);
     if ((size_t)Dc * Dc * Dc <= (size_t)DN_LDS_CELLS)
-        hipLaunchKernelGGL(cc_denoise_lds_kernel, dim3((unsigned)n), dim3(DN_NT), 0, c->stream, a);
+        LAUNCH(cc_denoise_lds_kernel, dim3((unsigned)n), dim3(DN_NT), a);
     else
-        hipLaunchKernelGGL(cc_denoise_global_kernel, dim3((unsigned)w.dn_blocks), dim3(DN_NT), 0, c->stream, a);
-    HIPCHK(hipGetLastError());
+        LAUNCH(cc_denoise_global_kernel, dim3((unsigned)w.dn_blocks), dim3(DN_NT), a);
     return SN_OK;
 }
 
@@ -83,8 +80,7 @@ int cc_check_args(int n, int Dc, int D_cube)
 int cc_check_dev(sn_ctx *c, int n, int Dc, long long total, const int64_t *off, const unsigned char *ijk)
 {
     const long long m = std::max<long long>(n + 1, total);
-    hipLaunchKernelGGL(cc_check_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c->stream, off, n, total, ijk, Dc, c->d_err);
-    HIPCHK(hipGetLastError());
+    LAUNCH(cc_check_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), off, n, total, ijk, Dc, c->d_err);
     return SN_OK;
 }
 
@@ -101,9 +97,8 @@ int cc_adapthresh(sn_ctx *c, int n, int Dc, const sn_adapthresh_cfg *cfg, long l
     signed char *ch = w.t.out<signed char>(n);
     if (!w.t.ok) return fail(SN_ERR_NOMEM, "sn_adapthresh: device allocation failed");
     if (total > 0) {
-        hipLaunchKernelGGL(cc_init_mask_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, total, pred16, votes, cfg->init_probThresh,
-                           cfg->rayPool_thresh, mask);
-        HIPCHK(hipGetLastError());
+        LAUNCH(cc_init_mask_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), total, pred16, votes, cfg->init_probThresh,
+               cfg->rayPool_thresh, mask);
     }
     // the initial denoise builds the map of the initial masks: it is the active set and neighbourhood of every iteration
     if ((rc = cc_denoise(c, w, cfg->D_cube, total, off, ijk, cube_ijk, mask, init_denoised ? init_denoised : scratch, face6)) != SN_OK) return rc;
@@ -128,19 +123,16 @@ int cc_adapthresh(sn_ctx *c, int n, int Dc, const sn_adapthresh_cfg *cfg, long l
         if (n > 0) {
             {
                 ProfScope ps(c, "cc_grid3", 0, (double)total * 7.0 + 3.0 * n * D2 * 8.0);
-                hipLaunchKernelGGL(cc_grid_kernel, dim3((unsigned)n), dim3(CC_NT), (size_t)per_pass * D2 * 8, c->stream, g);
-                HIPCHK(hipGetLastError());
+                LAUNCH_LDS(cc_grid_kernel, dim3((unsigned)n), dim3(CC_NT), (size_t)per_pass * D2 * 8, g);
             }
             {
                 ProfScope ps(c, "cc_cost", 0, (double)n * D2 * 8.0 * 6.0);
-                hipLaunchKernelGGL(cc_cost_kernel, dim3((unsigned)n), dim3(CC_NT), 0, c->stream, a);
-                HIPCHK(hipGetLastError());
+                LAUNCH(cc_cost_kernel, dim3((unsigned)n), dim3(CC_NT), a);
             }
             {
                 ProfScope ps(c, "cc_mask_update", 0, (double)total * (masks ? 4.0 : 3.0));
-                hipLaunchKernelGGL(cc_mask_update_kernel, dim3((unsigned)n), dim3(CC_NT), 0, c->stream, off, total, pred16, t_new, mask,
-                                   masks ? masks + (size_t)it * total : nullptr, c->d_err);
-                HIPCHK(hipGetLastError());
+                LAUNCH(cc_mask_update_kernel, dim3((unsigned)n), dim3(CC_NT), off, total, pred16, t_new, mask,
+                       masks ? masks + (size_t)it * total : nullptr, c->d_err);
             }
             if (denoised && (rc = cc_denoise(c, w, cfg->D_cube, total, off, ijk, cube_ijk, mask, denoised + (size_t)it * total, nullptr)) != SN_OK) return rc;
             if (thresh) HIPCHK(hipMemcpyAsync(thresh + (size_t)it * n, t_new, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
@@ -193,7 +185,6 @@ extern "C" int sn_denoise(sn_ctx *c, int n, int Dc, int D_cube, const int64_t *o
     if ((rc = err_flag(c)) != SN_OK) return rc;
     if ((rc = cc_work(c, w, n, Dc, false)) != SN_OK) return rc;
     if ((rc = cc_denoise(c, w, D_cube, total, offsets, ijk, cube_ijk, mask, out, nullptr)) != SN_OK) return rc;
-    if ((rc = m.back(out, T)) != SN_OK) return rc;
     return m.finish(true);
 }
 
@@ -247,8 +238,5 @@ extern "C" int sn_adapthresh(sn_ctx *c, int n, int Dc, const sn_adapthresh_cfg *
     if (rc != SN_OK) return rc;
     if ((rc = err_flag(c)) != SN_OK) return rc;
     if ((rc = cc_adapthresh(c, n, Dc, cfg, total, offsets, ijk, pred16, votes, cube_ijk, init_denoised, thresh, masks, denoised, choice)) != SN_OK) return rc;
-    if ((rc = m.back(init_denoised, T)) != SN_OK || (rc = m.back(masks, it * T)) != SN_OK || (rc = m.back(denoised, it * T)) != SN_OK ||
-        (rc = m.back(thresh, it * N)) != SN_OK || (rc = m.back(choice, it * N)) != SN_OK)
-        return rc;
     return m.finish(true);
 }

@@ -30,12 +30,10 @@ int gt_bind_device(sn_ctx *c, long long n, const float *pts_dev, double cell)
     CGStats<unsigned> st;
     {
         ProfScope ps(c, "gt_bounds", 0, (double)n * 12.0);
-        hipLaunchKernelGGL(cg_stats_init_kernel<unsigned>, dim3(1), dim3(64), 0, c->stream, b.st);
-        hipLaunchKernelGGL((cg_bounds_kernel<float, false, GTPoints>), dim3(std::min(blocks(n, CG_NT), 2048u)), dim3(CG_NT), 0, c->stream, GTPoints{pts_dev}, n, b.st);
-        HIPCHK(hipGetLastError());
+        LAUNCH(cg_stats_init_kernel<unsigned>, dim3(1), dim3(64), b.st);
+        LAUNCH((cg_bounds_kernel<float, false, GTPoints>), dim3(std::min(blocks(n, CG_NT), 2048u)), dim3(CG_NT), GTPoints{pts_dev}, n, b.st);
     }
-    HIPCHK(hipMemcpyAsync(&st, b.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(read_status(c, &st, b.st));
     if (st.flags & CG_FLAG_NONFINITE) return fail(SN_ERR_ARG, "a coordinate is not finite");
     double o[3];
     long long dim[3];
@@ -82,8 +80,7 @@ int gt_cubes_device(sn_ctx *c, int n, const float *xyz_dev, const float *resol_d
     a.xyz = xyz_dev; a.resol = resol_dev; a.Y = Y_dev; a.s = c->s; a.err = c->d_err;
     a.vec = (s3 % 4 == 0 && (reinterpret_cast<uintptr_t>(Y_dev) & 15) == 0) ? 1 : 0;
     ProfScope ps(c, "gt_cubes", 0, (double)n * (s3 * 4.0 + 16.0));
-    hipLaunchKernelGGL(gt_cubes_kernel, dim3((unsigned)n), dim3(GT_NT), ((s3 + 31) / 32) * sizeof(unsigned), c->stream, a);
-    HIPCHK(hipGetLastError());
+    LAUNCH_LDS(gt_cubes_kernel, dim3((unsigned)n), dim3(GT_NT), ((s3 + 31) / 32) * sizeof(unsigned), a);
     return SN_OK;
 }
 
@@ -108,9 +105,8 @@ int gt_accuracy_device(sn_ctx *c, int n, const float *pred_dev, const float *Y_d
     a.pred = pred_dev; a.Y = Y_dev; a.counts = reinterpret_cast<unsigned long long *>(counts_dev); a.s3 = (int)s3; a.thr = threshold;
     a.vec = (s3 % 4 == 0 && ((reinterpret_cast<uintptr_t>(pred_dev) | reinterpret_cast<uintptr_t>(Y_dev)) & 15) == 0) ? 1 : 0;
     ProfScope ps(c, "gt_accuracy", 0, (double)n * (s3 * 8.0 + 32.0));
-    HIPCHK(hipMemsetAsync(counts_dev, 0, sizeof(int64_t) * 4 * (size_t)n, c->stream));
-    hipLaunchKernelGGL(gt_accuracy_kernel, dim3((unsigned)((s3 + GT_ACC_CHUNK - 1) / GT_ACC_CHUNK), (unsigned)n), dim3(GT_NT), 0, c->stream, a);
-    HIPCHK(hipGetLastError());
+    HIPCHK(dev_fill(c, counts_dev, 0, 4 * (size_t)n));
+    LAUNCH(gt_accuracy_kernel, dim3((unsigned)((s3 + GT_ACC_CHUNK - 1) / GT_ACC_CHUNK), (unsigned)n), dim3(GT_NT), a);
     return SN_OK;
 }
 
@@ -167,7 +163,7 @@ extern "C" int sn_gt_cubes(sn_ctx *c, int n, const float *xyz, const float *reso
     HostMirror m(c, true);
     if ((rc = m.inputs([&](Carve &w) { m.in(w, xyz, 3 * (size_t)n); m.in(w, resol, (size_t)n); })) != SN_OK) return rc;
     if ((rc = m.outputs([&](Carve &w) { m.out(w, Y, (size_t)n * s3); })) != SN_OK) return rc;
-    if ((rc = gt_cubes_device(c, n, xyz, resol, Y)) != SN_OK || (rc = m.back(Y, (size_t)n * s3)) != SN_OK) return rc;
+    if ((rc = gt_cubes_device(c, n, xyz, resol, Y)) != SN_OK) return rc;
     return m.finish();
 }
 
@@ -188,6 +184,6 @@ extern "C" int sn_weighted_accuracy(sn_ctx *c, int n, const float *pred, const f
     HostMirror m(c, true);
     if ((rc = m.inputs([&](Carve &w) { m.in(w, pred, (size_t)n * s3); m.in(w, Y, (size_t)n * s3); })) != SN_OK) return rc;
     if ((rc = m.outputs([&](Carve &w) { m.out(w, counts, 4 * (size_t)n); })) != SN_OK) return rc;
-    if ((rc = gt_accuracy_device(c, n, pred, Y, threshold, counts)) != SN_OK || (rc = m.back(counts, 4 * (size_t)n)) != SN_OK) return rc;
+    if ((rc = gt_accuracy_device(c, n, pred, Y, threshold, counts)) != SN_OK) return rc;
     return m.finish();
 }

@@ -57,15 +57,17 @@ struct Carve {
 
 // The host mirror of one call, as bookkeeping: every entry `sn_X` that takes host arrays is `sn_X_dev` on device copies of them. in() / out()
 // are called from inside a Carve layout (so they run twice, as every get() does): a host array that was given takes a region; the placing pass
-// records {host array, region, bytes, input or output} and swaps the caller's pointer for the region's address. What copies - uploads of the
-// recorded inputs, the copy back of an output's first `count` elements once the counting kernels have said how many there are - walks `recs`
-// (sn_internal.h HostMirror; tests/host/sn_host_check.cpp does it with memcpy). With the mirror off (a device form) and for a null array
-// nothing happens: no region, no record, the pointer stays. Scratch may be taken from the same Carve between the arrays.
+// records {host array, region, bytes, input or output} and swaps the caller's pointer for the region's address. What copies walks `recs`
+// (sn_internal.h HostMirror; tests/host/sn_host_check.cpp does it with memcpy): the recorded inputs are uploaded, and every output goes back
+// once, at the size it was staged with, when the call finishes (each_pending) - unless the call returned it earlier or shorter itself
+// (note_back: a list staged at its upper bound, of which the first rows are valid). `pending` holds what an output still owes; an input owes
+// nothing. With the mirror off (a device form) and for a null array nothing happens: no region, no record, the pointer stays. Scratch may be
+// taken from the same Carve between the arrays.
 //
 // The rules of a call: at most one layout of inputs and one of outputs (two buffers: placing the outputs cannot move the staged inputs), and a
 // host form never calls another host form - it runs the device form's computation on the swapped pointers.
 struct MirrorPlan {
-    struct Rec { void *host; void *dev; size_t bytes; bool input; };
+    struct Rec { void *host; void *dev; size_t bytes; bool input; size_t pending; };
     bool on = false;
     std::vector<Rec> recs;
     template <typename T> void in(Carve &w, const T *&p, size_t count) { take(w, p, count, true); }
@@ -77,6 +79,24 @@ struct MirrorPlan {
             if (r.dev == dev) return &r;
         return nullptr;
     }
+    // The call itself returns the first `bytes` of an output now: its record, which then owes nothing (nullptr: not that much of a staged output).
+    const Rec *note_back(const void *dev, size_t bytes)
+    {
+        Rec *r = const_cast<Rec *>(find(dev));
+        if (!r || r->input || bytes > r->bytes) return nullptr;
+        r->pending = 0;
+        return r;
+    }
+    // Returns what is still owed, in the order of recs: copy(host, dev, bytes) -> bool. Stops at the first copy that fails.
+    template <typename F> bool each_pending(F &&copy)
+    {
+        for (Rec &r : recs) {
+            if (!r.pending) continue;
+            if (!copy(r.host, r.dev, r.pending)) return false;
+            r.pending = 0;
+        }
+        return true;
+    }
 
 private:
     template <typename T> void take(Carve &w, T *&p, size_t count, bool input)
@@ -85,7 +105,7 @@ private:
         using U = typename std::remove_const<T>::type;
         U *d = w.get<U>(count);
         if (!w.base) return;
-        recs.push_back(Rec{const_cast<U *>(p), d, count * sizeof(T), input});
+        recs.push_back(Rec{const_cast<U *>(p), d, count * sizeof(T), input, input ? 0 : count * sizeof(T)});
         p = d;
     }
 };

@@ -3,6 +3,7 @@
 // thresholding; sn_pointeval.hip: point-cloud evaluation; sn_ptcubes.hip: point-seeded cube list; sn_normals.hip: normals + de-duplication; sn_components.hip: connected components; sn_mesh.hip: surface mesh; sn_meshsample.hip: surface samples of a mesh; sn_meshsimplify.hip: mesh simplification; sn_meshsmooth.hip: mesh smoothing; sn_meshfill.hip: hole filling; sn_meshnormals.hip: the mesh's own normals, area and volume; sn_meshorient.hip: consistent orientation, pieces and their volumes; sn_meshrender.hip: the mesh rendered into its views, vertex colours;
 // sn_gtcubes.hip: ground-truth occupancy cubes + weighted accuracy; sn_relwtrain.hip: training of the view-pair weighting net):
 // the context, owned device memory and the buffers that grow on demand (DevBuf), temporary device work buffers (TmpDev), the host forms' device copies of their arrays (HostMirror),
+// the checked launch (LAUNCH), typed fills and status reads (dev_fill, read_status),
 // HIP-event profiling, ConvKernel (one conv3d_f16_mfma instantiation as a type: its packing geometry and its launcher) and
 // the plan rows - which kernel runs which layer - that the weight packers and the forward passes walk. What needs no device is in two hip-free
 // headers: sn_host.h (error text, table sizes, Carve, MirrorPlan, blocks, the packed-list checks) and sn_pack.h (PackedConv and the host half of weight packing).
@@ -36,6 +37,17 @@ using namespace sn;
         hipError_t e_ = (expr);                                                                            \
         if (e_ != hipSuccess) return fail(SN_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
+
+// The one way to launch a kernel: on the stream of the enclosing function's context `c`, checked on the spot - a launch that fails ends the
+// function as HIPCHK does, with the file and line of the launch. The kernel may be a parenthesised template instantiation, (k<A, B>).
+// LAUNCH_LDS says how many bytes of dynamic LDS the workgroups get; LAUNCH gives them none.
+#define LAUNCH_LDS(kernel, grid, block, lds_bytes, ...)                                                    \
+    do {                                                                                                   \
+        hipLaunchKernelGGL(kernel, grid, block, lds_bytes, c->stream, __VA_ARGS__);                        \
+        hipError_t e_ = hipGetLastError();                                                                 \
+        if (e_ != hipSuccess) return fail(SN_ERR_HIP, "launch of %s failed: %s (%s:%d)", #kernel, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+#define LAUNCH(kernel, grid, block, ...) LAUNCH_LDS(kernel, grid, block, 0, __VA_ARGS__)
 
 // ------------------------------------------------------------------------------------------------
 // kernel choice and layer plan
@@ -240,13 +252,28 @@ static int dev_carve(sn_ctx *c, DevBuf &b, F &&layout, size_t slack = 0)
     return SN_OK;
 }
 
+// Sets every byte of p[0 .. count) on the context's stream, sized by the array's own element type: HIPCHK(dev_fill(c, p, byte, count)).
+template <typename T>
+static inline hipError_t dev_fill(sn_ctx *c, T *p, int byte, size_t count)
+{
+    return hipMemsetAsync(p, byte, sizeof(T) * count, c->stream);
+}
+
+// A stage's status block (or one word of its counts) on the host, once the stream has done everything up to it: HIPCHK(read_status(c, &st, a.st)).
+template <typename S>
+static inline hipError_t read_status(sn_ctx *c, S *host, const S *dev)
+{
+    const hipError_t e = hipMemcpyAsync(host, dev, sizeof(S), hipMemcpyDeviceToHost, c->stream);
+    return e != hipSuccess ? e : hipStreamSynchronize(c->stream);
+}
+
 // The device error flag sn_synchronize reports (sn_ctx::d_err), allocated and cleared on first use.
 static int err_flag(sn_ctx *c)
 {
     if (!c->d_err) {
         int rc = dev_alloc(c, &c->d_err, 1);
         if (rc != SN_OK) return rc;
-        HIPCHK(hipMemsetAsync(c->d_err, 0, sizeof(int), c->stream));
+        HIPCHK(dev_fill(c, c->d_err, 0, 1));
     }
     return SN_OK;
 }
@@ -255,8 +282,7 @@ static int err_flag(sn_ctx *c)
 static int relw_fresh_b2(sn_ctx *c)
 {
     if (!c->relw_b2_stale || !c->relw_b2_dev) return SN_OK;
-    HIPCHK(hipMemcpyAsync(&c->relw_b2, c->relw_b2_dev, sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(read_status(c, &c->relw_b2, c->relw_b2_dev));
     c->relw_b2_stale = false;
     return SN_OK;
 }
@@ -413,8 +439,7 @@ struct ConvKernel {
         // persistent workgroups: one resident set, each walking tiles blockIdx.x, +gridDim.x, ...
         const int resident = std::max(1, c->num_cus * C::WG_PER_CU / L.nsplit);
         dim3 grid((unsigned)std::min(a.total_tiles, resident), (unsigned)L.nsplit);
-        hipLaunchKernelGGL((conv3d_f16_mfma<KS, DIL, MF, NF, EPI, SPLIT, CS8, PCH, NW, PADV, K2D, OSPLIT>), grid, dim3(NW * 64), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        LAUNCH((conv3d_f16_mfma<KS, DIL, MF, NF, EPI, SPLIT, CS8, PCH, NW, PADV, K2D, OSPLIT>), grid, dim3(NW * 64), a);
         return SN_OK;
     }
     static constexpr ConvGeom geom = {KS, DIL, K2D != 0, NF, C::CS8MAX, SPLIT, OSPLIT < 0 ? SPLIT : OSPLIT, EPI,
@@ -450,9 +475,11 @@ struct TmpDev {
 //   ... the counting kernels ...
 //   m.outputs([&](Carve &w) { m.out(w, verts, 3 * nv); ... });    room for the outputs, at their exact counts
 //   ... the kernels that write them ...
-//   m.back(verts, 3 * nv); ...                                    copy the first `count` elements to the caller's array
-//   return m.finish();                                            the one synchronize
-// A return before finish() waits for the stream too, so no copy into the caller's arrays is in flight after any return.
+//   return m.finish();                                            every output to the caller's array at its staged count, the one synchronize
+// An output is named once, in outputs(). Only a call that cannot stage an output at its exact count returns it itself: back(p, count) copies
+// the first `count` elements now, and finish() leaves that output alone (sn_dense2sparse: its lists are staged at their upper bound, and how
+// many rows hold something is known once the offsets table has come back). A return before finish() copies no output and waits for the
+// stream too, so no copy into the caller's arrays is in flight after any return.
 struct HostMirror : MirrorPlan {
     sn_ctx *c;
     bool done = false;
@@ -472,19 +499,22 @@ struct HostMirror : MirrorPlan {
     template <typename F> int outputs(F &&layout) { return on ? dev_carve(c, c->mir_out, layout, 256) : SN_OK; }
     template <typename T> int back(const T *dev, size_t count)
     {
-        if (!on || !dev || !count) return SN_OK;
-        const Rec *r = find(dev);
-        if (!r || r->input || count * sizeof(T) > r->bytes) return fail(SN_ERR_STATE, "host mirror: not %zu elements of a staged output", count);
-        if (hipMemcpyAsync(r->host, dev, count * sizeof(T), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
-            return fail(SN_ERR_HIP, "copying the results to the host arrays failed");
-        return SN_OK;
+        if (!on || !dev) return SN_OK;
+        const Rec *r = note_back(dev, count * sizeof(T));
+        if (!r) return fail(SN_ERR_STATE, "host mirror: not %zu elements of a staged output", count);
+        return count == 0 || to_host(r->host, dev, count * sizeof(T)) ? SN_OK : fail(SN_ERR_HIP, "copying the results to the host arrays failed");
     }
     // report: also the device error words, as sn_synchronize reports them
     int finish(bool report = false)
     {
+        if (!each_pending([&](void *host, const void *dev, size_t bytes) { return to_host(host, dev, bytes); }))
+            return fail(SN_ERR_HIP, "copying the results to the host arrays failed");
         done = true;
         if (report) return sn_synchronize(c);
         HIPCHK(hipStreamSynchronize(c->stream));
         return SN_OK;
     }
+
+private:
+    bool to_host(void *host, const void *dev, size_t bytes) { return hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream) == hipSuccess; }
 };

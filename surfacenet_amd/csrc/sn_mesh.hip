@@ -55,18 +55,16 @@ int ms_run(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long total, const int6
     in.off = off; in.ijk = ijk; in.cube_ijk = cube_ijk; in.mask = mask; in.normals = normals; in.total = total; in.n = n; in.stride = cfg->stride_vox;
     tb.cmask = tb.bmask = cap - 1;
     unsigned long long cnt[MS_CNT_WORDS] = {0, 0, 0, 0};
-    HIPCHK(hipMemsetAsync(in.cnt, 0, sizeof cnt, c->stream));
+    HIPCHK(dev_fill(c, in.cnt, 0, MS_CNT_WORDS));
     {
         ProfScope ps(c, "ms_check", 0, (double)n * 8.0);
-        hipLaunchKernelGGL(ms_check_kernel, dim3((unsigned)(n / MS_NT + 1)), dim3(MS_NT), 0, c->stream, off, n, total, in.cnt);
-        HIPCHK(hipGetLastError());
+        LAUNCH(ms_check_kernel, dim3((unsigned)(n / MS_NT + 1)), dim3(MS_NT), off, n, total, in.cnt);
     }
     if (total > 0) {
         ProfScope ps(c, "ms_cells", 0, (double)total * 28.0 + (double)cap * 32.0);
-        HIPCHK(hipMemsetAsync(tb.cell, 0, sizeof(unsigned long long) * 2 * (size_t)cap, c->stream));
-        HIPCHK(hipMemsetAsync(tb.brick, 0, sizeof(unsigned long long) * 2 * (size_t)cap, c->stream));
-        hipLaunchKernelGGL(ms_insert_kernel, dim3(blocks(total, MS_NT)), dim3(MS_NT), 0, c->stream, in, tb);
-        HIPCHK(hipGetLastError());
+        HIPCHK(dev_fill(c, tb.cell, 0, 2 * (size_t)cap));
+        HIPCHK(dev_fill(c, tb.brick, 0, 2 * (size_t)cap));
+        LAUNCH(ms_insert_kernel, dim3(blocks(total, MS_NT)), dim3(MS_NT), in, tb);
     }
     HIPCHK(hipMemcpyAsync(cnt, in.cnt, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -77,9 +75,8 @@ int ms_run(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long total, const int6
     if (total == 0) return SN_OK;
     {
         ProfScope ps(c, "ms_bricks", 0, (double)total * 20.0 + (double)cap * 8.0);
-        hipLaunchKernelGGL(ms_bricks_kernel, dim3(blocks(total, MS_NT)), dim3(MS_NT), 0, c->stream, in, tb);
-        hipLaunchKernelGGL(ms_count_kernel, dim3(blocks(cap, MS_NT)), dim3(MS_NT), 0, c->stream, (const unsigned long long *)tb.brick, cap, in.cnt + MS_CNT_BRICKS);
-        HIPCHK(hipGetLastError());
+        LAUNCH(ms_bricks_kernel, dim3(blocks(total, MS_NT)), dim3(MS_NT), in, tb);
+        LAUNCH(ms_count_kernel, dim3(blocks(cap, MS_NT)), dim3(MS_NT), (const unsigned long long *)tb.brick, cap, in.cnt + MS_CNT_BRICKS);
     }
     HIPCHK(hipMemcpyAsync(cnt, in.cnt, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -99,10 +96,9 @@ int ms_run(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long total, const int6
     tb.kmask = kcap - 1;
     {
         ProfScope ps(c, "ms_cand", 0, (double)cap * 16.0 + (double)kcap * 40.0);
-        HIPCHK(hipMemsetAsync(tb.cand, 0, sizeof(unsigned long long) * 2 * (size_t)kcap, c->stream));
-        hipLaunchKernelGGL(ms_cand_kernel, dim3(blocks(cap, MS_NT)), dim3(MS_NT), 0, c->stream, tb);
-        hipLaunchKernelGGL(ms_list_kernel, dim3(blocks(kcap, MS_NT)), dim3(MS_NT), 0, c->stream, tb, list, in.cnt + MS_CNT_CAND);
-        HIPCHK(hipGetLastError());
+        HIPCHK(dev_fill(c, tb.cand, 0, 2 * (size_t)kcap));
+        LAUNCH(ms_cand_kernel, dim3(blocks(cap, MS_NT)), dim3(MS_NT), tb);
+        LAUNCH(ms_list_kernel, dim3(blocks(kcap, MS_NT)), dim3(MS_NT), tb, list, in.cnt + MS_CNT_CAND);
     }
     HIPCHK(hipMemcpyAsync(cnt, in.cnt, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -114,12 +110,11 @@ int ms_run(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long total, const int6
         const long long p2 = (long long)table_cap(ncu, 1, PC_TILE);
         if (p2 > nc) {
             ProfScope ps(c, "ms_pad", 0, (double)(p2 - nc) * 8.0);
-            hipLaunchKernelGGL(pc_pad_kernel, dim3(blocks(p2 - nc, PC_NT)), dim3(PC_NT), 0, c->stream, list, (long long)nc, p2);
+            LAUNCH(pc_pad_kernel, dim3(blocks(p2 - nc, PC_NT)), dim3(PC_NT), list, (long long)nc, p2);
         }
         if ((rc = pc_sort(c, list, p2)) != SN_OK) return rc;      // (its own profile tag, pc_sort)
         ProfScope ps(c, "ms_rank", 0, (double)nc * 28.0);
-        hipLaunchKernelGGL(ms_rank_kernel, dim3(blocks(nc, MS_NT)), dim3(MS_NT), 0, c->stream, tb, (const unsigned long long *)list, nc);
-        HIPCHK(hipGetLastError());
+        LAUNCH(ms_rank_kernel, dim3(blocks(nc, MS_NT)), dim3(MS_NT), tb, (const unsigned long long *)list, nc);
     }
 
     // ---- stage 3: the field, the edges, the counts ---------------------------------------------------------------------------------------------
@@ -138,18 +133,16 @@ int ms_run(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long total, const int6
     };
     if ((rc = dev_carve(c, c->ms_field, layout3, 256)) != SN_OK) return rc;
     f.list = list; f.radius = cfg->radius; f.reach = cfg->reach;
-    HIPCHK(hipMemsetAsync(f.vstart + nc, 0, sizeof(int), c->stream));
-    HIPCHK(hipMemsetAsync(f.qstart + nc, 0, sizeof(int), c->stream));
+    HIPCHK(dev_fill(c, f.vstart + nc, 0, 1));
+    HIPCHK(dev_fill(c, f.qstart + nc, 0, 1));
     {
         ProfScope ps(c, "ms_field", 0, (double)ns * 12.0 + (double)nc * 27.0 * 16.0);
-        hipLaunchKernelGGL(ms_field_kernel, dim3((unsigned)nc), dim3(64), 0, c->stream, tb, f, normals);
-        HIPCHK(hipGetLastError());
+        LAUNCH(ms_field_kernel, dim3((unsigned)nc), dim3(64), tb, f, normals);
     }
     {
         ProfScope ps(c, "ms_edges", 0, (double)ns * 14.0);
-        hipLaunchKernelGGL(ms_edge_kernel, dim3((unsigned)nc), dim3(64), 0, c->stream, tb, f);
-        hipLaunchKernelGGL(ms_vcount_kernel, dim3((unsigned)nc), dim3(64), 0, c->stream, tb, f);
-        HIPCHK(hipGetLastError());
+        LAUNCH(ms_edge_kernel, dim3((unsigned)nc), dim3(64), tb, f);
+        LAUNCH(ms_vcount_kernel, dim3((unsigned)nc), dim3(64), tb, f);
     }
     int nv = 0, nq = 0;
     {
@@ -158,8 +151,7 @@ int ms_run(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long total, const int6
         if ((rc = scan_exclusive(c, f.qstart, f.qstart, nc + 1, sums)) != SN_OK) return rc;
     }
     HIPCHK(hipMemcpyAsync(&nv, f.vstart + nc, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&nq, f.qstart + nc, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(read_status(c, &nq, f.qstart + nc));
     *n_verts = nv; *n_quads = nq;
     if (nv > cap_verts || nq > cap_quads)
         return fail(SN_ERR_ARG, "the outputs hold %lld vertices and %lld quads, %d and %d are needed", cap_verts, cap_quads, nv, nq);
@@ -175,17 +167,12 @@ int ms_run(sn_ctx *c, int n, const sn_mesh_cfg *cfg, long long total, const int6
     o.resol = cfg->resol;
     if (o.verts_mm || o.verts_lattice || o.vert_cell || o.vert_src) {
         ProfScope ps(c, "ms_vertices", 0, (double)nv * 56.0 + (double)ns * 9.0);
-        hipLaunchKernelGGL(ms_vemit_kernel, dim3((unsigned)nc), dim3(64), 0, c->stream, tb, f, o);
-        HIPCHK(hipGetLastError());
+        LAUNCH(ms_vemit_kernel, dim3((unsigned)nc), dim3(64), tb, f, o);
     }
     if (o.quads) {
         ProfScope ps(c, "ms_quads", 0, (double)nq * 16.0 + (double)ns * 9.0);
-        hipLaunchKernelGGL(ms_qemit_kernel, dim3((unsigned)nc), dim3(64), 0, c->stream, tb, f, o);
-        HIPCHK(hipGetLastError());
+        LAUNCH(ms_qemit_kernel, dim3((unsigned)nc), dim3(64), tb, f, o);
     }
-    if ((rc = m.back(o.verts_mm, 3 * NV)) != SN_OK || (rc = m.back(o.verts_lattice, 3 * NV)) != SN_OK || (rc = m.back(o.vert_cell, 3 * NV)) != SN_OK ||
-        (rc = m.back(o.vert_src, NV)) != SN_OK || (rc = m.back(o.quads, 4 * NQ)) != SN_OK)
-        return rc;
     return m.finish();
 }
 

@@ -56,49 +56,40 @@ int mfl_run(sn_ctx *c, bool host, const sn_mesh_fill_cfg *cfg, int V, const doub
     if ((rc = dev_carve(c, c->mfl_ws, layout, 256)) != SN_OK) return rc;
     const unsigned vb = blocks(V, MFL_NT), vb1 = blocks((long long)V + 1, MFL_NT), fb = blocks(F, MFL_NT);
     const unsigned loop_blocks = (unsigned)std::max(c->num_cus, 1) * 8u;      // the grid-stride kernel: eight workgroups per CU at most
-    HIPCHK(hipMemsetAsync(b.st, 0, sizeof(MflStat), c->stream));
+    HIPCHK(dev_fill(c, b.st, 0, 1));
     if ((rc = msm_build<MFL_REC>(c, a, cap)) != SN_OK) return rc;
     if (V > 0) {
         {
             ProfScope ps(c, "mfl_halfedge", 0, (double)F * nv * 24.0 + (double)V * 28.0);
-            HIPCHK(hipMemsetAsync(b.out, 0, sizeof(int) * n, c->stream));
-            HIPCHK(hipMemsetAsync(b.in, 0, sizeof(int) * n, c->stream));
-            hipLaunchKernelGGL(mfl_init_kernel, dim3(vb), dim3(MFL_NT), 0, c->stream, a, b);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(mfl_halfedge_kernel, dim3(fb), dim3(MFL_NT), 0, c->stream, a, b);
-            HIPCHK(hipGetLastError());
+            HIPCHK(dev_fill(c, b.out, 0, n));
+            HIPCHK(dev_fill(c, b.in, 0, n));
+            LAUNCH(mfl_init_kernel, dim3(vb), dim3(MFL_NT), a, b);
+            LAUNCH(mfl_halfedge_kernel, dim3(fb), dim3(MFL_NT), a, b);
         }
         {
             ProfScope ps(c, "mfl_loops", 0, (double)V * 80.0);
-            HIPCHK(hipMemsetAsync(b.rlen, 0, sizeof(unsigned) * n, c->stream));
-            HIPCHK(hipMemsetAsync(b.rflag, 0, sizeof(unsigned) * n, c->stream));
-            HIPCHK(hipMemsetAsync(b.rvotes, 0, sizeof(unsigned) * n, c->stream));
-            HIPCHK(hipMemsetAsync(b.rsum, 0, sizeof(unsigned long long) * 3 * n, c->stream));
-            hipLaunchKernelGGL(mfl_measure_kernel, dim3(vb), dim3(MFL_NT), 0, c->stream, a, b);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(mfl_sum_kernel, dim3(vb), dim3(MFL_NT), 0, c->stream, a, b);
-            HIPCHK(hipGetLastError());
+            HIPCHK(dev_fill(c, b.rlen, 0, n));
+            HIPCHK(dev_fill(c, b.rflag, 0, n));
+            HIPCHK(dev_fill(c, b.rvotes, 0, n));
+            HIPCHK(dev_fill(c, b.rsum, 0, 3 * n));
+            LAUNCH(mfl_measure_kernel, dim3(vb), dim3(MFL_NT), a, b);
+            LAUNCH(mfl_sum_kernel, dim3(vb), dim3(MFL_NT), a, b);
             if (b.orientation == 0) {
-                hipLaunchKernelGGL(mfl_vote_kernel, dim3(vb), dim3(MFL_NT), 0, c->stream, a, b);
-                HIPCHK(hipGetLastError());
+                LAUNCH(mfl_vote_kernel, dim3(vb), dim3(MFL_NT), a, b);
             }
         }
     }
     {
         ProfScope ps(c, "mfl_place", 0, (double)V * 40.0);
-        hipLaunchKernelGGL(mfl_classify_kernel, dim3(std::min(vb1, loop_blocks)), dim3(MFL_NT), 0, c->stream, a, b);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(mfl_flag_kernel, dim3(vb1), dim3(MFL_NT), 0, c->stream, a, b);
-        HIPCHK(hipGetLastError());
+        LAUNCH(mfl_classify_kernel, dim3(std::min(vb1, loop_blocks)), dim3(MFL_NT), a, b);
+        LAUNCH(mfl_flag_kernel, dim3(vb1), dim3(MFL_NT), a, b);
         if ((rc = scan_exclusive(c, b.hflag, b.hpos, V + 1, sums)) != SN_OK) return rc;      // hpos[V] = H
         if ((rc = scan_exclusive(c, b.tflag, b.tpos, V + 1, sums)) != SN_OK) return rc;      // tpos[V] = T
-        hipLaunchKernelGGL(mfl_counts_kernel, dim3(1), dim3(64), 0, c->stream, a, b);
-        HIPCHK(hipGetLastError());
+        LAUNCH(mfl_counts_kernel, dim3(1), dim3(64), a, b);
     }
     // the one read before any output is touched: the first bad face, the edge limit, the counts, then the caps
     MflStat st;
-    HIPCHK(hipMemcpyAsync(&st, b.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(read_status(c, &st, b.st));
     if ((rc = msm_report(st.msm, V, false)) != SN_OK) return rc;
     for (int k = 0; k < 8; ++k) counts[k] = (long long)st.counts[k];
     const size_t H = (size_t)st.counts[3], T = (size_t)st.counts[7];
@@ -113,13 +104,8 @@ int mfl_run(sn_ctx *c, bool host, const sn_mesh_fill_cfg *cfg, int V, const doub
     b.new_faces = d.new_faces; b.vert_loop = d.vert_loop;
     if (V > 0 && (b.vert_loop || (H > 0 && (b.new_verts_mm || b.new_verts_lattice || b.loop_root || b.loop_len || b.new_faces)))) {
         ProfScope ps(c, "mfl_emit", 0, (double)V * 9.0 + (double)T * 28.0 + (double)H * 80.0);
-        hipLaunchKernelGGL(mfl_emit_kernel, dim3(vb), dim3(MFL_NT), 0, c->stream, a, b);
-        HIPCHK(hipGetLastError());
+        LAUNCH(mfl_emit_kernel, dim3(vb), dim3(MFL_NT), a, b);
     }
-    if ((rc = m.back(d.new_verts_mm, 3 * H)) != SN_OK || (rc = m.back(d.new_verts_lattice, 3 * H)) != SN_OK ||
-        (rc = m.back(d.loop_root, H)) != SN_OK || (rc = m.back(d.loop_len, H)) != SN_OK || (rc = m.back(d.new_faces, 3 * T)) != SN_OK ||
-        (rc = m.back(d.vert_loop, (size_t)V)) != SN_OK)
-        return rc;
     return m.finish();
 }
 

@@ -34,32 +34,28 @@ int mnr_run(sn_ctx *c, bool host, int V, const double *verts, int F, int nv, con
     };
     if ((rc = dev_carve(c, c->mnr_ws, layout, 256)) != SN_OK) return rc;
     const unsigned loop_blocks = (unsigned)std::max(c->num_cus, 1) * 8u;      // grid-stride kernels: eight workgroups per CU at most
-    HIPCHK(hipMemsetAsync(a.st, 0, sizeof(MnrStat), c->stream));
-    HIPCHK(hipMemsetAsync(a.st, 0xff, sizeof(unsigned long long), c->stream));      // first_bad = MESH_NO_BAD
+    HIPCHK(dev_fill(c, a.st, 0, 1));
+    HIPCHK(dev_fill(c, &a.st->first_bad, 0xff, 1));      // MESH_NO_BAD
     {
         // per face: its indices, its corners' coordinates, its normal; per corner and axis up to two atomics on 16 bytes
         ProfScope ps(c, "mnr_faces", 0, (double)F * (nv * (4.0 + 24.0 + 48.0) + 12.0) + (double)V * 49.0);
-        HIPCHK(hipMemsetAsync(a.ref, 0, std::max<size_t>((size_t)V, 1), c->stream));
-        HIPCHK(hipMemsetAsync(a.acc, 0, sizeof(unsigned long long) * 6 * std::max<size_t>((size_t)V, 1), c->stream));
-        hipLaunchKernelGGL(mnr_faces_kernel, dim3(std::min(blocks(F, MNR_NT), loop_blocks)), dim3(MNR_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        HIPCHK(dev_fill(c, a.ref, 0, std::max<size_t>((size_t)V, 1)));
+        HIPCHK(dev_fill(c, a.acc, 0, 6 * std::max<size_t>((size_t)V, 1)));
+        LAUNCH(mnr_faces_kernel, dim3(std::min(blocks(F, MNR_NT), loop_blocks)), dim3(MNR_NT), a);
     }
     if (V > 0) {
         ProfScope ps(c, "mnr_verts", 0, (double)V * (1.0 + 48.0 + 12.0));
-        hipLaunchKernelGGL(mnr_verts_kernel, dim3(std::min(blocks(V, MNR_NT), loop_blocks)), dim3(MNR_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        LAUNCH(mnr_verts_kernel, dim3(std::min(blocks(V, MNR_NT), loop_blocks)), dim3(MNR_NT), a);
     }
     // the one read, before any output is touched: the first bad face, the counts, the sums
     MnrStat st;
-    HIPCHK(hipMemcpyAsync(&st, a.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(read_status(c, &st, a.st));
     if ((rc = mesh_report_bad(st.first_bad, V)) != SN_OK) return rc;
     rc = m.outputs([&](Carve &w) { m.out(w, face_normals, 3 * (size_t)F); m.out(w, vert_normals, 3 * (size_t)V); });
     if (rc != SN_OK) return rc;
     if (face_normals) HIPCHK(hipMemcpyAsync(face_normals, a.fn, sizeof(float) * 3 * (size_t)F, hipMemcpyDeviceToDevice, c->stream));
     if (vert_normals && V > 0)
         HIPCHK(hipMemcpyAsync(vert_normals, a.vn, sizeof(float) * 3 * (size_t)V, hipMemcpyDeviceToDevice, c->stream));
-    if ((rc = m.back(face_normals, 3 * (size_t)F)) != SN_OK || (rc = m.back(vert_normals, 3 * (size_t)V)) != SN_OK) return rc;
     if ((rc = m.finish()) != SN_OK) return rc;
     for (int k = 0; k < 3; ++k) counts[k] = (long long)st.counts[k];
     counts[3] = (long long)F * (nv - 2);

@@ -56,43 +56,37 @@ int mor_run(sn_ctx *c, bool host, const sn_mesh_orient_cfg *cfg, int V, const do
     if ((rc = dev_carve(c, c->mor_ws, layout, 256)) != SN_OK) return rc;
     const unsigned fb = blocks(F, MOR_NT), sb = blocks((long long)cap, MOR_NT);
     const unsigned loop_blocks = (unsigned)std::max(c->num_cus, 1) * 8u;      // the grid-stride kernels: eight workgroups per CU at most
-    HIPCHK(hipMemsetAsync(b.st, 0, sizeof(MorStat), c->stream));
+    HIPCHK(dev_fill(c, b.st, 0, 1));
     if ((rc = msm_build<MOR_REC>(c, a, cap)) != SN_OK) return rc;
     {
         // per side: its face's indices, a probe, the slot's count, two atomics
         ProfScope ps(c, "mor_sides", 0, (double)F * (nv * (4.0 + 4.0 + 16.0 + 4.0 + 8.0) + 8.0) + (double)cap * 8.0);
-        HIPCHK(hipMemsetAsync(b.slot_lo, 0xff, sizeof(unsigned) * cap, c->stream));
-        HIPCHK(hipMemsetAsync(b.slot_hi, 0, sizeof(unsigned) * cap, c->stream));
-        hipLaunchKernelGGL(mor_sides_kernel, dim3(fb), dim3(MOR_NT), 0, c->stream, a, b);
-        HIPCHK(hipGetLastError());
+        HIPCHK(dev_fill(c, b.slot_lo, 0xff, cap));
+        HIPCHK(dev_fill(c, b.slot_hi, 0, cap));
+        LAUNCH(mor_sides_kernel, dim3(fb), dim3(MOR_NT), a, b);
     }
     {
         ProfScope ps(c, "mor_links", 0, (double)cap * 20.0 + (double)F * nv * 0.5 * (8.0 + 32.0) + (double)F * 4.0);
-        HIPCHK(hipMemsetAsync(b.linked, 0, sizeof(unsigned) * n, c->stream));
-        hipLaunchKernelGGL(mor_links_kernel, dim3(std::min(sb, loop_blocks)), dim3(MOR_NT), 0, c->stream, a, b);
-        HIPCHK(hipGetLastError());
+        HIPCHK(dev_fill(c, b.linked, 0, n));
+        LAUNCH(mor_links_kernel, dim3(std::min(sb, loop_blocks)), dim3(MOR_NT), a, b);
     }
     {
         // per face: two walks to the root, its indices, its corners' records, the piece's record
         ProfScope ps(c, "mor_faces", 0, (double)F * (16.0 + 4.0 + nv * (4.0 + 4.0 + 24.0) + 8.0 + 36.0));
-        HIPCHK(hipMemsetAsync(b.rec_faces, 0, sizeof(unsigned) * n, c->stream));
-        HIPCHK(hipMemsetAsync(b.rec_rel, 0, sizeof(unsigned) * n, c->stream));
-        HIPCHK(hipMemsetAsync(b.rec_bits, 0, sizeof(unsigned) * n, c->stream));
-        HIPCHK(hipMemsetAsync(b.rec_vol, 0, sizeof(unsigned long long) * 3 * n, c->stream));
-        hipLaunchKernelGGL(mor_faces_kernel, dim3(fb), dim3(MOR_NT), 0, c->stream, a, b);
-        HIPCHK(hipGetLastError());
+        HIPCHK(dev_fill(c, b.rec_faces, 0, n));
+        HIPCHK(dev_fill(c, b.rec_rel, 0, n));
+        HIPCHK(dev_fill(c, b.rec_bits, 0, n));
+        HIPCHK(dev_fill(c, b.rec_vol, 0, 3 * n));
+        LAUNCH(mor_faces_kernel, dim3(fb), dim3(MOR_NT), a, b);
     }
     {
         ProfScope ps(c, "mor_pieces", 0, (double)F * 8.0);
-        hipLaunchKernelGGL(mor_pieces_kernel, dim3(std::min(fb, loop_blocks)), dim3(MOR_NT), 0, c->stream, a, b);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(mor_keep_kernel, dim3(std::min(fb, loop_blocks)), dim3(MOR_NT), 0, c->stream, a, b);
-        HIPCHK(hipGetLastError());
+        LAUNCH(mor_pieces_kernel, dim3(std::min(fb, loop_blocks)), dim3(MOR_NT), a, b);
+        LAUNCH(mor_keep_kernel, dim3(std::min(fb, loop_blocks)), dim3(MOR_NT), a, b);
     }
     // the one read, before any output is touched: the first bad face, the edge limit, the counts
     MorStat st;
-    HIPCHK(hipMemcpyAsync(&st, b.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(read_status(c, &st, b.st));
     if ((rc = msm_report(st.msm, V, false)) != SN_OK) return rc;
     rc = m.outputs([&](Carve &w) {
         m.out(w, d.faces_out, (size_t)nv * n); m.out(w, d.face_flip, n); m.out(w, d.face_component, n); m.out(w, d.face_keep, n);
@@ -103,13 +97,8 @@ int mor_run(sn_ctx *c, bool host, const sn_mesh_orient_cfg *cfg, int V, const do
     b.comp_faces = d.comp_faces; b.comp_flags = d.comp_flags; b.comp_vol6 = d.comp_vol6;
     if (b.faces_out || b.face_flip || b.face_component || b.face_keep || b.comp_faces || b.comp_flags || b.comp_vol6) {
         ProfScope ps(c, "mor_emit", 0, (double)F * (8.0 + nv * 8.0 + 6.0 + 5.0 + 24.0));
-        hipLaunchKernelGGL(mor_emit_kernel, dim3(fb), dim3(MOR_NT), 0, c->stream, a, b);
-        HIPCHK(hipGetLastError());
+        LAUNCH(mor_emit_kernel, dim3(fb), dim3(MOR_NT), a, b);
     }
-    if ((rc = m.back(d.faces_out, (size_t)nv * n)) != SN_OK || (rc = m.back(d.face_flip, n)) != SN_OK ||
-        (rc = m.back(d.face_component, n)) != SN_OK || (rc = m.back(d.face_keep, n)) != SN_OK || (rc = m.back(d.comp_faces, n)) != SN_OK ||
-        (rc = m.back(d.comp_flags, n)) != SN_OK || (rc = m.back(d.comp_vol6, 3 * n)) != SN_OK)
-        return rc;
     if ((rc = m.finish()) != SN_OK) return rc;
     for (int k = 0; k < 3; ++k) counts[k] = (long long)st.msm.counts[k];
     for (int k = 0; k < 9; ++k) counts[3 + k] = (long long)st.counts[k];

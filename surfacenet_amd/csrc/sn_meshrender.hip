@@ -29,16 +29,14 @@ int mrd_front(sn_ctx *c, const sn_mesh_render_cfg *cfg, int n_verts, const doubl
 // The check kernel, the one read of its two words, the refusals. a.st is placed; nothing of the caller's has been written.
 int mrd_check_inputs(sn_ctx *c, const MrdArgs &a, const double *cams, int V)
 {
-    HIPCHK(hipMemsetAsync(a.st, 0, sizeof(MrdStat), c->stream));
+    HIPCHK(dev_fill(c, a.st, 0, 1));
     HIPCHK(hipMemsetAsync(a.st, 0xff, 2 * sizeof(unsigned long long), c->stream));      // first_bad, bad_p
     {
         ProfScope ps(c, "mrd_check", 0, (double)a.F * a.nv * 28.0 + (double)V * 96.0);
-        hipLaunchKernelGGL(mrd_check_kernel, dim3(blocks(std::max<long long>(a.F, 12ll * V), MRD_NT)), dim3(MRD_NT), 0, c->stream, a, cams, 12 * V);
-        HIPCHK(hipGetLastError());
+        LAUNCH(mrd_check_kernel, dim3(blocks(std::max<long long>(a.F, 12ll * V), MRD_NT)), dim3(MRD_NT), a, cams, 12 * V);
     }
     MrdStat st;
-    HIPCHK(hipMemcpyAsync(&st, a.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(read_status(c, &st, a.st));
     if (st.bad_p != ~0ull)
         return fail(SN_ERR_ARG, "P: entry %d of view %d is not finite", (int)(st.bad_p % 12), (int)(st.bad_p / 12));
     if (st.first_bad != MESH_NO_BAD) {
@@ -94,55 +92,47 @@ int mrd_render(sn_ctx *c, bool host, const sn_mesh_render_cfg *cfg, int n_verts,
         a.vis = host ? s.vis : (o.vis ? o.vis + (size_t)v * nV : nullptr);
         {
             ProfScope ps(c, "mrd_clear", 0, (double)npix * (ids ? 12.0 : 8.0) + (a.face_pixels ? (double)nF * 4.0 : 0.0));
-            HIPCHK(hipMemsetAsync(a.zbuf, 0xff, sizeof(unsigned long long) * npix, c->stream));
-            if (ids) HIPCHK(hipMemsetAsync(a.idbuf, 0xff, sizeof(unsigned) * npix, c->stream));
-            if (a.face_pixels && nF) HIPCHK(hipMemsetAsync(a.face_pixels, 0, sizeof(int32_t) * nF, c->stream));
-            HIPCHK(hipMemsetAsync(&a.st->big_pack, 0, sizeof(unsigned long long), c->stream));
+            HIPCHK(dev_fill(c, a.zbuf, 0xff, npix));
+            if (ids) HIPCHK(dev_fill(c, a.idbuf, 0xff, npix));
+            if (a.face_pixels && nF) HIPCHK(dev_fill(c, a.face_pixels, 0, nF));
+            HIPCHK(dev_fill(c, &a.st->big_pack, 0, 1));
         }
         if (n_verts > 0) {
             ProfScope ps(c, "mrd_project", 0, (double)nV * (24.0 + 33.0));
-            hipLaunchKernelGGL(mrd_project_kernel, dim3(vb), dim3(MRD_NT), 0, c->stream, a);
-            HIPCHK(hipGetLastError());
+            LAUNCH(mrd_project_kernel, dim3(vb), dim3(MRD_NT), a);
         }
         if (T > 0) {
             {
                 ProfScope ps(c, "mrd_setup", 0, (double)T * (12.0 + 3.0 * 9.0 + 1.0));
-                hipLaunchKernelGGL(mrd_setup_kernel, dim3(tb), dim3(MRD_NT), 0, c->stream, a);
-                HIPCHK(hipGetLastError());
+                LAUNCH(mrd_setup_kernel, dim3(tb), dim3(MRD_NT), a);
             }
             {
                 ProfScope ps(c, "mrd_raster_small", 0, (double)T * (1.0 + 12.0 + 3.0 * 17.0));
-                hipLaunchKernelGGL(mrd_raster_small_kernel<1>, dim3(tb), dim3(MRD_NT), 0, c->stream, a);
-                HIPCHK(hipGetLastError());
+                LAUNCH(mrd_raster_small_kernel<1>, dim3(tb), dim3(MRD_NT), a);
             }
             {
                 ProfScope ps(c, "mrd_raster_big", 0, 0.0);
-                hipLaunchKernelGGL(mrd_raster_big_kernel<1>, big_grid, dim3(MRD_NT), 0, c->stream, a);
-                HIPCHK(hipGetLastError());
+                LAUNCH(mrd_raster_big_kernel<1>, big_grid, dim3(MRD_NT), a);
             }
             if (ids) {
                 {
                     ProfScope ps(c, "mrd_ids_small", 0, (double)T * (1.0 + 12.0 + 3.0 * 17.0));
-                    hipLaunchKernelGGL(mrd_raster_small_kernel<2>, dim3(tb), dim3(MRD_NT), 0, c->stream, a);
-                    HIPCHK(hipGetLastError());
+                    LAUNCH(mrd_raster_small_kernel<2>, dim3(tb), dim3(MRD_NT), a);
                 }
                 {
                     ProfScope ps(c, "mrd_ids_big", 0, 0.0);
-                    hipLaunchKernelGGL(mrd_raster_big_kernel<2>, big_grid, dim3(MRD_NT), 0, c->stream, a);
-                    HIPCHK(hipGetLastError());
+                    LAUNCH(mrd_raster_big_kernel<2>, big_grid, dim3(MRD_NT), a);
                 }
             }
         }
         {
             // per pixel: its z word, its id word, the depth and the face
             ProfScope ps(c, "mrd_resolve", 0, (double)npix * (8.0 + (ids ? 4.0 : 0.0) + (a.depth ? 8.0 : 0.0) + (a.face ? 4.0 : 0.0)));
-            hipLaunchKernelGGL(mrd_resolve_kernel, dim3(pb), dim3(MRD_NT), 0, c->stream, a, ids ? 1 : 0);
-            HIPCHK(hipGetLastError());
+            LAUNCH(mrd_resolve_kernel, dim3(pb), dim3(MRD_NT), a, ids ? 1 : 0);
         }
         if (n_verts > 0) {
             ProfScope ps(c, "mrd_visible", 0, (double)nV * (24.0 + 32.0 + 1.0));
-            hipLaunchKernelGGL(mrd_visible_kernel, dim3(vb), dim3(MRD_NT), 0, c->stream, a);
-            HIPCHK(hipGetLastError());
+            LAUNCH(mrd_visible_kernel, dim3(vb), dim3(MRD_NT), a);
         }
         if (host) {                                             // this view's rows of the host arrays; the next view's launches follow on the stream
             if (o.depth) HIPCHK(hipMemcpyAsync(o.depth + (size_t)v * npix, s.depth, sizeof(double) * npix, hipMemcpyDeviceToHost, c->stream));
@@ -153,8 +143,7 @@ int mrd_render(sn_ctx *c, bool host, const sn_mesh_render_cfg *cfg, int n_verts,
         }
     }
     MrdStat st;
-    HIPCHK(hipMemcpyAsync(&st, a.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(read_status(c, &st, a.st));
     if ((rc = m.finish()) != SN_OK) return rc;
     for (int k = 0; k < 8; ++k) counts[k] = (long long)st.counts[k];
     return SN_OK;
@@ -191,13 +180,10 @@ int mrd_colors(sn_ctx *c, bool host, const sn_mesh_render_cfg *cfg, int n_verts,
         b.n_verts = n_verts; b.V = V; b.H = cfg->H; b.W = cfg->W; b.verts = verts; b.P = cams; b.vis = vis;
         b.img_base = c->img_base; b.img_off = c->img_off; b.views = views; b.rgb = rgb; b.counts = a.st->counts;
         ProfScope ps(c, "mrd_colors", 0, (double)nV * (24.0 + (double)V * 4.0 + 7.0));
-        hipLaunchKernelGGL(mrd_colors_kernel, dim3(blocks(n_verts, MRD_NT)), dim3(MRD_NT), 0, c->stream, b);
-        HIPCHK(hipGetLastError());
+        LAUNCH(mrd_colors_kernel, dim3(blocks(n_verts, MRD_NT)), dim3(MRD_NT), b);
     }
-    if ((rc = m.back(views, nV)) != SN_OK || (rc = m.back(rgb, 3 * nV)) != SN_OK) return rc;
     MrdStat st;
-    HIPCHK(hipMemcpyAsync(&st, a.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(read_status(c, &st, a.st));
     if ((rc = m.finish()) != SN_OK) return rc;
     counts[0] = (long long)st.counts[0]; counts[1] = (long long)st.counts[1];
     return SN_OK;

@@ -39,17 +39,14 @@ int msmp_run(sn_ctx *c, bool host, int V, const double *verts, int F, const int3
     memset(&in, 0, sizeof in);
     in.verts = verts; in.faces = faces; in.V = V; in.F = F; in.dst2 = dst * dst;
     MsmpStat st;
-    HIPCHK(hipMemsetAsync(d_st, 0, sizeof st, c->stream));
-    HIPCHK(hipMemsetAsync(&d_st->first_bad, 0xff, sizeof st.first_bad, c->stream));
-    HIPCHK(hipMemsetAsync(off + F, 0, sizeof(int), c->stream));
+    HIPCHK(dev_fill(c, d_st, 0, 1));
+    HIPCHK(dev_fill(c, &d_st->first_bad, 0xff, 1));
+    HIPCHK(dev_fill(c, off + F, 0, 1));
     {
         ProfScope ps(c, "msmp_count", 0, (double)F * 16.0);
-        hipLaunchKernelGGL(msmp_count_kernel, dim3((unsigned)(((long long)F + MSMP_NT * MSMP_FACES - 1) / (MSMP_NT * MSMP_FACES))), dim3(MSMP_NT), 0,
-                           c->stream, in, off, d_st);
-        HIPCHK(hipGetLastError());
+        LAUNCH(msmp_count_kernel, dim3((unsigned)(((long long)F + MSMP_NT * MSMP_FACES - 1) / (MSMP_NT * MSMP_FACES))), dim3(MSMP_NT), in, off, d_st);
     }
-    HIPCHK(hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(read_status(c, &st, d_st));
     if (st.first_bad != MESH_NO_BAD) {
         const long long f = (long long)(st.first_bad >> 3);
         const unsigned kind = (unsigned)(st.first_bad & 7);
@@ -76,11 +73,9 @@ int msmp_run(sn_ctx *c, bool host, int V, const double *verts, int F, const int3
     if ((rc = m.outputs([&](Carve &w) { m.out(w, points, 3 * (size_t)M); m.out(w, tri, (size_t)M); })) != SN_OK) return rc;
     {
         ProfScope ps(c, "msmp_emit", 0, (double)M * ((points ? 24.0 : 0.0) + (tri ? 4.0 : 0.0)));
-        hipLaunchKernelGGL(msmp_emit_kernel, dim3((unsigned)(((long long)M + MSMP_RUN - 1) / MSMP_RUN)), dim3(MSMP_NT), 0, c->stream, in,
-                           (const int *)off, M, points, tri);
-        HIPCHK(hipGetLastError());
+        LAUNCH(msmp_emit_kernel, dim3((unsigned)(((long long)M + MSMP_RUN - 1) / MSMP_RUN)), dim3(MSMP_NT), in,
+               (const int *)off, M, points, tri);
     }
-    if ((rc = m.back(points, 3 * (size_t)M)) != SN_OK || (rc = m.back(tri, (size_t)M)) != SN_OK) return rc;
     return m.finish();
 }
 

@@ -59,56 +59,48 @@ int msim_run(sn_ctx *c, bool host, const sn_mesh_simplify_cfg *cfg, int V, const
     if ((rc = dev_carve(c, c->msim_ws, layout, 256)) != SN_OK) return rc;
     const unsigned vb = blocks(V, MSIM_NT), vb1 = blocks((long long)V + 1, MSIM_NT), fb = blocks(F, MSIM_NT), fb1 = blocks((long long)F + 1, MSIM_NT);
     const bool agg = !sn_ab_switch("SN_MSIM_NO_AGG");
-    HIPCHK(hipMemsetAsync(a.st, 0, sizeof(MsimStat), c->stream));
-    HIPCHK(hipMemsetAsync(&a.st->first_bad, 0xff, sizeof(unsigned long long), c->stream));
+    HIPCHK(dev_fill(c, a.st, 0, 1));
+    HIPCHK(dev_fill(c, &a.st->first_bad, 0xff, 1));
     {
         ProfScope ps(c, "msim_mark", 0, (double)F * 12.0 + (double)V * 4.0);
-        HIPCHK(hipMemsetAsync(a.vnum, 0xff, sizeof(int) * std::max<size_t>((size_t)V, 1), c->stream));      // MSIM_NONE
-        hipLaunchKernelGGL(msim_mark_kernel, dim3(fb), dim3(MSIM_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        HIPCHK(dev_fill(c, a.vnum, 0xff, std::max<size_t>((size_t)V, 1)));      // MSIM_NONE
+        LAUNCH(msim_mark_kernel, dim3(fb), dim3(MSIM_NT), a);
     }
     {
         ProfScope ps(c, "msim_cluster", 0, (double)V * 28.0 + (double)vcap * 52.0);
-        HIPCHK(hipMemsetAsync(a.vtab, 0, sizeof(unsigned long long) * 2 * vcap, c->stream));
-        HIPCHK(hipMemsetAsync(a.sum, 0, sizeof(unsigned long long) * 3 * vcap, c->stream));
-        HIPCHK(hipMemsetAsync(a.best, 0xff, sizeof(unsigned long long) * vcap, c->stream));
-        HIPCHK(hipMemsetAsync(a.count, 0, sizeof(unsigned) * vcap, c->stream));
+        HIPCHK(dev_fill(c, a.vtab, 0, 2 * vcap));
+        HIPCHK(dev_fill(c, a.sum, 0, 3 * vcap));
+        HIPCHK(dev_fill(c, a.best, 0xff, vcap));
+        HIPCHK(dev_fill(c, a.count, 0, vcap));
         if (V > 0) {
-            if (agg) hipLaunchKernelGGL(msim_cluster_kernel<true>, dim3(vb), dim3(MSIM_NT), 0, c->stream, a);
-            else hipLaunchKernelGGL(msim_cluster_kernel<false>, dim3(vb), dim3(MSIM_NT), 0, c->stream, a);
-            HIPCHK(hipGetLastError());
+            if (agg) LAUNCH(msim_cluster_kernel<true>, dim3(vb), dim3(MSIM_NT), a);
+            else LAUNCH(msim_cluster_kernel<false>, dim3(vb), dim3(MSIM_NT), a);
         }
     }
     {
         ProfScope ps(c, "msim_number", 0, (double)V * 24.0);
-        hipLaunchKernelGGL(msim_owner_kernel, dim3(vb1), dim3(MSIM_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        LAUNCH(msim_owner_kernel, dim3(vb1), dim3(MSIM_NT), a);
         if ((rc = scan_exclusive(c, a.vflag, a.vpos, V + 1, vsums)) != SN_OK) return rc;      // vpos[V] = P
         if (V > 0) {
-            hipLaunchKernelGGL(msim_number_kernel, dim3(vb), dim3(MSIM_NT), 0, c->stream, a);
-            HIPCHK(hipGetLastError());
+            LAUNCH(msim_number_kernel, dim3(vb), dim3(MSIM_NT), a);
         }
     }
     {
         ProfScope ps(c, "msim_facekey", 0, (double)F * 40.0 + (double)fcap * 16.0);
-        HIPCHK(hipMemsetAsync(a.ftab, 0, sizeof(unsigned long long) * 2 * fcap, c->stream));
-        hipLaunchKernelGGL(msim_facekey_kernel, dim3(fb), dim3(MSIM_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        HIPCHK(dev_fill(c, a.ftab, 0, 2 * fcap));
+        LAUNCH(msim_facekey_kernel, dim3(fb), dim3(MSIM_NT), a);
     }
     {
         ProfScope ps(c, "msim_faceown", 0, (double)F * 32.0 + (double)V * 16.0);
-        HIPCHK(hipMemsetAsync(a.used, 0, sizeof(int) * ((size_t)V + 1), c->stream));
-        hipLaunchKernelGGL(msim_faceown_kernel, dim3(fb1), dim3(MSIM_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        HIPCHK(dev_fill(c, a.used, 0, (size_t)V + 1));
+        LAUNCH(msim_faceown_kernel, dim3(fb1), dim3(MSIM_NT), a);
         if ((rc = scan_exclusive(c, a.fflag, a.fpos, F + 1, fsums)) != SN_OK) return rc;      // fpos[F] = G
         if ((rc = scan_exclusive(c, a.used, a.cpos, V + 1, vsums)) != SN_OK) return rc;       // cpos[V] = C
-        hipLaunchKernelGGL(msim_counts_kernel, dim3(1), dim3(64), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        LAUNCH(msim_counts_kernel, dim3(1), dim3(64), a);
     }
     // the one read before any output is touched: errors, then the cluster limit, then the caps
     MsimStat st;
-    HIPCHK(hipMemcpyAsync(&st, a.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(read_status(c, &st, a.st));
     if ((rc = mesh_report_bad(st.first_bad, V)) != SN_OK) return rc;
     if (st.P >= MSIM_MAX_CLUSTERS)
         return fail(SN_ERR_ARG, "cell = %d gives %d clusters, at most 2^21 - 1 fit a face key: choose a larger cell", cfg->cell, st.P);
@@ -126,22 +118,15 @@ int msim_run(sn_ctx *c, bool host, const sn_mesh_simplify_cfg *cfg, int V, const
     {
         ProfScope ps(c, "msim_emit", 0, (double)C * 56.0 + (double)G * 16.0 + (double)F * 20.0 + (double)V * 12.0);
         if (st.P > 0 && (a.verts_mm || a.verts_lattice || a.vert_rep || a.vert_count)) {
-            hipLaunchKernelGGL(msim_emit_verts_kernel, dim3(blocks(st.P, MSIM_NT)), dim3(MSIM_NT), 0, c->stream, a, st.P);
-            HIPCHK(hipGetLastError());
+            LAUNCH(msim_emit_verts_kernel, dim3(blocks(st.P, MSIM_NT)), dim3(MSIM_NT), a, st.P);
         }
         if (G > 0 && (a.faces_out || a.face_src)) {
-            hipLaunchKernelGGL(msim_emit_faces_kernel, dim3(fb), dim3(MSIM_NT), 0, c->stream, a);
-            HIPCHK(hipGetLastError());
+            LAUNCH(msim_emit_faces_kernel, dim3(fb), dim3(MSIM_NT), a);
         }
         if (V > 0 && a.vert_cluster) {
-            hipLaunchKernelGGL(msim_emit_map_kernel, dim3(vb), dim3(MSIM_NT), 0, c->stream, a);
-            HIPCHK(hipGetLastError());
+            LAUNCH(msim_emit_map_kernel, dim3(vb), dim3(MSIM_NT), a);
         }
     }
-    if ((rc = m.back(d.verts_mm, 3 * C)) != SN_OK || (rc = m.back(d.verts_lattice, 3 * C)) != SN_OK || (rc = m.back(d.vert_rep, C)) != SN_OK ||
-        (rc = m.back(d.vert_count, C)) != SN_OK || (rc = m.back(d.faces, 3 * G)) != SN_OK || (rc = m.back(d.face_src, G)) != SN_OK ||
-        (rc = m.back(d.vert_cluster, (size_t)V)) != SN_OK)
-        return rc;
     return m.finish();
 }
 
@@ -158,7 +143,7 @@ extern "C" int sn_mesh_simplify_dev(sn_ctx *c, const sn_mesh_simplify_cfg *cfg, 
     HIPCHK(hipSetDevice(c->device));
     if (n_faces == 0) {                                  // no face: no vertex is referenced
         if (vert_cluster_dev && n_verts > 0) {
-            HIPCHK(hipMemsetAsync(vert_cluster_dev, 0xff, sizeof(int32_t) * (size_t)n_verts, c->stream));
+            HIPCHK(dev_fill(c, vert_cluster_dev, 0xff, (size_t)n_verts));
             HIPCHK(hipStreamSynchronize(c->stream));
         }
         return SN_OK;

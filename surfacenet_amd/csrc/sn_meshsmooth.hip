@@ -44,8 +44,7 @@ int msm_run(sn_ctx *c, bool host, const sn_mesh_smooth_cfg *cfg, int V, const do
     if ((rc = msm_build<REC>(c, a, cap)) != SN_OK) return rc;
     // the one read before any output is touched: the first bad face, the degree limit, the counts
     MsmStat st;
-    HIPCHK(hipMemcpyAsync(&st, a.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(read_status(c, &st, a.st));
     if ((rc = msm_report(st, V, true)) != SN_OK) return rc;
     rc = m.outputs([&](Carve &w) {
         m.out(w, d.verts_mm, 3 * (size_t)V); m.out(w, d.verts_lattice, 3 * (size_t)V); m.out(w, d.vert_degree, (size_t)V);
@@ -59,9 +58,8 @@ int msm_run(sn_ctx *c, bool host, const sn_mesh_smooth_cfg *cfg, int V, const do
         {
             ProfScope ps(c, "msm_rows", 0, (double)cap * 12.0 + (double)V * 16.0 + (double)E * 24.0);
             if ((rc = scan_exclusive(c, a.deg, a.row, V + 1, sums)) != SN_OK) return rc;      // row[V] = 2 E
-            HIPCHK(hipMemsetAsync(a.cursor, 0, sizeof(int) * (size_t)V, c->stream));
-            hipLaunchKernelGGL(msm_rows_kernel, dim3(sb), dim3(MSM_NT), 0, c->stream, a);
-            HIPCHK(hipGetLastError());
+            HIPCHK(dev_fill(c, a.cursor, 0, (size_t)V));
+            LAUNCH(msm_rows_kernel, dim3(sb), dim3(MSM_NT), a);
         }
         // per vertex: its record, one record and one row word per neighbour, two row bounds, the flags, one write
         const double pass_bytes = (double)st.counts[3] * (16.0 * REC + 12.0) + 2.0 * (double)E * (8.0 * REC + 4.0);
@@ -70,19 +68,14 @@ int msm_run(sn_ctx *c, bool host, const sn_mesh_smooth_cfg *cfg, int V, const do
                 const int w = half ? cfg->mu_q16 : cfg->lam_q16;
                 if (half && w == 0) continue;
                 ProfScope ps(c, "msm_pass", 0, pass_bytes);
-                hipLaunchKernelGGL(msm_pass_kernel<REC>, dim3(vb), dim3(MSM_NT), 0, c->stream, a, (const long long *)a.pos[cur], a.pos[cur ^ 1], w);
-                HIPCHK(hipGetLastError());
+                LAUNCH(msm_pass_kernel<REC>, dim3(vb), dim3(MSM_NT), a, (const long long *)a.pos[cur], a.pos[cur ^ 1], w);
                 cur ^= 1;
             }
     }
     if (V > 0 && (a.verts_mm || a.verts_lattice || a.vert_degree || a.vert_flags)) {
         ProfScope ps(c, "msm_emit", 0, (double)V * (8.0 * REC + 24.0 + 36.0 + 9.0));
-        hipLaunchKernelGGL(msm_emit_kernel<REC>, dim3(vb), dim3(MSM_NT), 0, c->stream, a, (const long long *)a.pos[cur]);
-        HIPCHK(hipGetLastError());
+        LAUNCH(msm_emit_kernel<REC>, dim3(vb), dim3(MSM_NT), a, (const long long *)a.pos[cur]);
     }
-    if ((rc = m.back(d.verts_mm, 3 * (size_t)V)) != SN_OK || (rc = m.back(d.verts_lattice, 3 * (size_t)V)) != SN_OK ||
-        (rc = m.back(d.vert_degree, (size_t)V)) != SN_OK || (rc = m.back(d.vert_flags, (size_t)V)) != SN_OK)
-        return rc;
     if ((rc = m.finish()) != SN_OK) return rc;
     for (int k = 0; k < 4; ++k) counts[k] = (long long)st.counts[k];
     return SN_OK;

@@ -60,10 +60,9 @@ int nm_run(sn_ctx *c, NMCall &k, const sn_normals_cfg *cfg, int stride_vox)
     const int n = k.n;
     const long long total = k.total;
     const bool normals = k.normals != nullptr;
-    HIPCHK(hipMemsetAsync(k.flags, 0, sizeof(int), c->stream));
-    hipLaunchKernelGGL(nm_check_kernel, dim3((unsigned)(n / NM_NT + 1)), dim3(NM_NT), 0, c->stream, k.off, n, total, normals ? k.view : nullptr, k.K, k.cams, k.V,
-                       k.cbar, k.flags);
-    HIPCHK(hipGetLastError());
+    HIPCHK(dev_fill(c, k.flags, 0, 1));
+    LAUNCH(nm_check_kernel, dim3((unsigned)(n / NM_NT + 1)), dim3(NM_NT), k.off, n, total, normals ? k.view : nullptr, k.K, k.cams, k.V,
+           k.cbar, k.flags);
     NMArgs a;
     memset(&a, 0, sizeof a);
     a.off = k.off; a.ijk = k.ijk; a.cube_ijk = k.cube_ijk; a.mask = k.mask; a.cube_xyz = k.xyz; a.cube_resol = k.resol; a.cbar = k.cbar;
@@ -72,14 +71,12 @@ int nm_run(sn_ctx *c, NMCall &k, const sn_normals_cfg *cfg, int stride_vox)
     const unsigned nb = blocks(total, NM_NT);
     if (total > 0) {
         ProfScope ps(c, k.unique ? "nm_cells" : "nm_bricks", 0, (double)total * 12.0 + (double)k.cap * 16.0);
-        HIPCHK(hipMemsetAsync(k.tab, 0, sizeof(unsigned long long) * 2 * (size_t)k.cap, c->stream));
-        if (k.unique) hipLaunchKernelGGL(nm_insert_kernel<true>, dim3(nb), dim3(NM_NT), 0, c->stream, a);
-        else hipLaunchKernelGGL(nm_insert_kernel<false>, dim3(nb), dim3(NM_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        HIPCHK(dev_fill(c, k.tab, 0, 2 * (size_t)k.cap));
+        if (k.unique) LAUNCH(nm_insert_kernel<true>, dim3(nb), dim3(NM_NT), a);
+        else LAUNCH(nm_insert_kernel<false>, dim3(nb), dim3(NM_NT), a);
     }
     int flags = 0;
-    HIPCHK(hipMemcpyAsync(&flags, k.flags, sizeof flags, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(read_status(c, &flags, k.flags));
     if (flags & NM_FLAG_TABLE) return fail(SN_ERR_ARG, "offsets table does not start at 0, decreases, or does not end at total = %lld", total);
     if (flags & NM_FLAG_VIEW) return fail(SN_ERR_ARG, "a view index lies outside [0, %d)", k.V);
     if (flags & NM_FLAG_CELL)
@@ -87,12 +84,10 @@ int nm_run(sn_ctx *c, NMCall &k, const sn_normals_cfg *cfg, int stride_vox)
     if (total == 0) return SN_OK;
     if (k.unique) {
         ProfScope ps(c, "nm_owner", 0, (double)total * 10.0);
-        hipLaunchKernelGGL(nm_owner_kernel, dim3(nb), dim3(NM_NT), 0, c->stream, a, k.keep);
-        HIPCHK(hipGetLastError());
+        LAUNCH(nm_owner_kernel, dim3(nb), dim3(NM_NT), a, k.keep);
     } else {
         ProfScope ps(c, "nm_normals", 0, (double)total * (9.0 + (normals ? 12.0 : 0.0) + (k.moments ? 40.0 : 0.0)));
-        hipLaunchKernelGGL(nm_normals_kernel, dim3(nb), dim3(NM_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        LAUNCH(nm_normals_kernel, dim3(nb), dim3(NM_NT), a);
     }
     return SN_OK;
 }
@@ -112,7 +107,6 @@ int nm_call(sn_ctx *c, bool host, NMCall &k, const sn_normals_cfg *cfg, int stri
     k.cap = (unsigned)table_cap((unsigned long long)k.total, 2, 64);
     if ((rc = dev_carve(c, c->nm_ws, [&](Carve &w) { nm_layout(w, k); }, 256)) != SN_OK) return rc;
     if ((rc = nm_run(c, k, cfg, stride_vox)) != SN_OK) return rc;
-    if ((rc = m.back(k.normals, 3 * T)) != SN_OK || (rc = m.back(k.moments, 10 * T)) != SN_OK || (rc = m.back(k.keep, T)) != SN_OK) return rc;
     return m.finish();
 }
 

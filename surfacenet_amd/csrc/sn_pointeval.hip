@@ -45,13 +45,6 @@ int pe_build(sn_ctx *c, const GridBufs &b, const double *xyz_dev, const long lon
     return grid_build(c, b, g, xyz_dev, rank_dev, occ_dev, sort);
 }
 
-int read_int(sn_ctx *c, const int *dev, int *host)
-{
-    HIPCHK(hipMemcpyAsync(host, dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return SN_OK;
-}
-
 int check_points(long long n, const char *what)
 {
     if (n < 0 || n > PE_MAX_POINTS) return fail(SN_ERR_ARG, "%s = %lld: 0 <= n <= %lld points", what, n, PE_MAX_POINTS);
@@ -93,7 +86,7 @@ extern "C" int sn_point_reduce(sn_ctx *c, long long n, const double *xyz, const 
     // cells a little larger than dst: a pair at d^2 <= dst^2 is never more than one cell apart, whatever the rounding of the cell index
     PEGrid g;
     if ((rc = pe_build(c, gb, d_xyz, d_rank, box, fit_h(dst * (1.0 + 1e-6), box), d_occ, true, g)) != SN_OK) return rc;
-    HIPCHK(hipMemsetAsync(d_state, PE_UND, (size_t)n, c->stream));
+    HIPCHK(dev_fill(c, d_state, PE_UND, (size_t)n));
     PEReduceArgs a;
     a.g = g; a.rank = gb.rank_s; a.state = d_state; a.undecided = d_und; a.dst2 = dst * dst; a.n = (int)n;
     const unsigned nb = blocks(n, PE_NT);
@@ -102,19 +95,16 @@ extern "C" int sn_point_reduce(sn_ctx *c, long long n, const double *xyz, const 
         if (r >= PE_MAX_ROUNDS) { (void)hipStreamSynchronize(c->stream); return fail(SN_ERR_STATE, "point reduction: undecided points left after %d rounds", r); }
         {
             ProfScope ps(c, "pe_reduce", 0, (double)n * 2.0);
-            hipLaunchKernelGGL(pe_reduce_select_kernel, dim3(nb), dim3(PE_NT), 0, c->stream, a);
-            HIPCHK(hipMemsetAsync(d_und, 0, sizeof(unsigned long long), c->stream));
-            hipLaunchKernelGGL(pe_reduce_exclude_kernel, dim3(nb), dim3(PE_NT), 0, c->stream, a);
-            HIPCHK(hipGetLastError());
+            LAUNCH(pe_reduce_select_kernel, dim3(nb), dim3(PE_NT), a);
+            HIPCHK(dev_fill(c, d_und, 0, 1));
+            LAUNCH(pe_reduce_exclude_kernel, dim3(nb), dim3(PE_NT), a);
         }
         ++r;
         unsigned long long und = 0;
-        HIPCHK(hipMemcpyAsync(&und, d_und, sizeof und, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(read_status(c, &und, d_und));
         if (und == 0) break;
     }
-    hipLaunchKernelGGL(pe_reduce_keep_kernel, dim3(nb), dim3(PE_NT), 0, c->stream, (const int *)gb.idx, (const unsigned char *)d_state, (int)n, d_keep);
-    HIPCHK(hipGetLastError());
+    LAUNCH(pe_reduce_keep_kernel, dim3(nb), dim3(PE_NT), (const int *)gb.idx, (const unsigned char *)d_state, (int)n, d_keep);
     HIPCHK(hipMemcpyAsync(keep, d_keep, (size_t)n, hipMemcpyDeviceToHost, c->stream));
     if (rounds) *rounds = r;
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -158,7 +148,7 @@ extern "C" int sn_nn_dist2(sn_ctx *c, long long n_to, const double *to, long lon
         PEGrid g0;
         if ((rc = pe_build(c, gf, d_to, nullptr, bt, h0, d_occ, false, g0)) != SN_OK) return rc;
         int occ = 0;
-        if ((rc = read_int(c, d_occ, &occ)) != SN_OK) return rc;
+        HIPCHK(read_status(c, &occ, d_occ));
         const double m0 = (double)n_to / std::max(occ, 1);
         h = fit_h(m0 > PE_CELL_TARGET ? h0 * std::sqrt(PE_CELL_TARGET / m0) : h0 * std::cbrt(PE_CELL_TARGET / m0), bt);
     }
@@ -174,19 +164,17 @@ extern "C" int sn_nn_dist2(sn_ctx *c, long long n_to, const double *to, long lon
     double mag = 0;
     for (int d = 0; d < 3; ++d) mag = std::max({mag, std::fabs(bt.lo[d]), std::fabs(bt.hi[d])});
     a.slack = 1e-12 * (mag + 2.0 * a.coarse.h) + 1e-300;
-    HIPCHK(hipMemsetAsync(d_nfar, 0, sizeof(int), c->stream));
+    HIPCHK(dev_fill(c, d_nfar, 0, 1));
     const unsigned nb = blocks(n_from, PE_NT);
     {
         ProfScope ps(c, "pe_nn_near", 0, (double)n_from * 40.0);
-        hipLaunchKernelGGL(pe_nn_near_kernel, dim3(nb), dim3(PE_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        LAUNCH(pe_nn_near_kernel, dim3(nb), dim3(PE_NT), a);
     }
     {
         ProfScope ps(c, "pe_nn_far", 0, 0.0);
-        hipLaunchKernelGGL(pe_nn_far_kernel, dim3(nb), dim3(PE_NT), 0, c->stream, a);   // (threads past the far count return at once)
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipMemcpyAsync(d2, d_d2, sizeof(double) * (size_t)n_from, hipMemcpyDeviceToHost, c->stream));
+        LAUNCH(pe_nn_far_kernel, dim3(nb), dim3(PE_NT), a);   // (threads past the far count return at once)
+               }
+               HIPCHK(hipMemcpyAsync(d2, d_d2, sizeof(double) * (size_t)n_from, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return SN_OK;
 }
@@ -224,8 +212,7 @@ extern "C" int sn_point_flags(sn_ctx *c, long long n, const double *xyz, const u
     if (above) { a.above = d_above; for (int d = 0; d < 4; ++d) a.plane[d] = plane[d]; }
     {
         ProfScope ps(c, "pe_flags", 0, (double)n * 26.0);
-        hipLaunchKernelGGL(pe_flags_kernel, dim3(blocks(n, PE_NT)), dim3(PE_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        LAUNCH(pe_flags_kernel, dim3(blocks(n, PE_NT)), dim3(PE_NT), a);
     }
     if (in_mask) HIPCHK(hipMemcpyAsync(in_mask, d_in, (size_t)n, hipMemcpyDeviceToHost, c->stream));
     if (above) HIPCHK(hipMemcpyAsync(above, d_above, (size_t)n, hipMemcpyDeviceToHost, c->stream));

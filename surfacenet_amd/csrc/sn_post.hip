@@ -29,7 +29,7 @@ static int launch_ray_pool(sn_ctx *c, int n, int n_vp, const int64_t *pairs_dev,
     const size_t need = per_wg * E * cubes;
     int rc;
     if ((rc = err_flag(c)) != SN_OK || (rc = dev_reserve(c, c->rp_ws, need)) != SN_OK) return rc;
-    HIPCHK(hipMemsetAsync(votes_dev, 0, (size_t)n * s3, c->stream));
+    HIPCHK(dev_fill(c, votes_dev, 0, (size_t)n * s3));
     for (int i0 = 0; i0 < n; i0 += cubes) {
         const int m = std::min(cubes, n - i0);
         const size_t wgs = (size_t)m * E;
@@ -47,8 +47,7 @@ static int launch_ray_pool(sn_ctx *c, int n, int n_vp, const int64_t *pairs_dev,
         a.n_vp = n_vp; a.s = c->s; a.V = c->V_cam; a.cap_max = (int)cap; a.use_thresh = use_thresh; a.thresh = min_prob;
         // algorithmic bytes: the prediction cube is read once per distinct view (<= E), the votes are written once
         ProfScope ps(c, "ray_pool", 0, (double)m * s3 * (4.0 * E + 1.0));
-        hipLaunchKernelGGL(ray_pool_kernel, dim3((unsigned)E, (unsigned)m), dim3(RP_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        LAUNCH(ray_pool_kernel, dim3((unsigned)E, (unsigned)m), dim3(RP_NT), a);
     }
     return SN_OK;
 }
@@ -101,10 +100,9 @@ extern "C" int sn_dense2sparse_dev(sn_ctx *c, int n, int n_vp, const int64_t *pa
     const double vox = (double)n * dc * dc * dc;
     // algorithmic bytes: the keep rule reads 4 B (pred) or 1 B (votes) per voxel twice (count + write); kept voxels add <= 9 B
     ProfScope ps(c, "dense2sparse", 0, vox * (by_votes ? 1.0 : 4.0) * 2.0);
-    hipLaunchKernelGGL(d2s_count_kernel, dim3((unsigned)n), dim3(D2S_NT), 0, c->stream, a);
-    hipLaunchKernelGGL(d2s_scan_kernel, dim3(1), dim3(64), 0, c->stream, a.counts, a.offsets, n);
-    hipLaunchKernelGGL(d2s_write_kernel, dim3((unsigned)n), dim3(D2S_NT), 0, c->stream, a);
-    HIPCHK(hipGetLastError());
+    LAUNCH(d2s_count_kernel, dim3((unsigned)n), dim3(D2S_NT), a);
+    LAUNCH(d2s_scan_kernel, dim3(1), dim3(64), a.counts, a.offsets, n);
+    LAUNCH(d2s_write_kernel, dim3((unsigned)n), dim3(D2S_NT), a);
     return SN_OK;
 }
 
@@ -125,7 +123,7 @@ extern "C" int sn_ray_pool(sn_ctx *c, int n, int n_vp, const int64_t *pairs, con
     const int64_t *d_p = wp.data();
     if ((rc = m.inputs([&](Carve &w) { m.in(w, d_p, N * n_vp * 2); m.in(w, xyz, 3 * N); m.in(w, resol, N); m.in(w, pred, N * s3); })) != SN_OK) return rc;
     if ((rc = m.outputs([&](Carve &w) { m.out(w, votes, N * s3); })) != SN_OK) return rc;
-    if ((rc = launch_ray_pool(c, n, n_vp, d_p, xyz, resol, pred, use_thresh, min_prob, votes)) != SN_OK || (rc = m.back(votes, N * s3)) != SN_OK) return rc;
+    if ((rc = launch_ray_pool(c, n, n_vp, d_p, xyz, resol, pred, use_thresh, min_prob, votes)) != SN_OK) return rc;
     return m.finish(true);
 }
 
@@ -164,7 +162,7 @@ extern "C" int sn_dense2sparse(sn_ctx *c, int n, int n_vp, const int64_t *pairs,
     if (rc != SN_OK) return rc;
     if ((rc = sn_dense2sparse_dev(c, n, n_vp, d_p, xyz, resol, pred, rgb, cfg, d_vws, offsets, ijk, pred16, rgb_out, votes_out)) != SN_OK) return rc;
     if ((rc = m.back(offsets, N + 1)) != SN_OK || (rc = sn_synchronize(c)) != SN_OK) return rc;
-    const size_t T = (size_t)h_off[n];                 // the table has arrived: the lists' exact size
+    const size_t T = (size_t)h_off[n];                 // the table has arrived: the lists' exact size, which is what goes back (not what was staged)
     if ((rc = m.back(ijk, 3 * T)) != SN_OK || (rc = m.back(pred16, T)) != SN_OK || (rc = m.back(rgb_out, 3 * T)) != SN_OK || (rc = m.back(votes_out, T)) != SN_OK)
         return rc;
     return m.finish();
@@ -189,11 +187,9 @@ extern "C" int sn_project_points(sn_ctx *c, int V, const double *P, int n, const
     if ((rc = m.outputs([&](Carve &w) { m.out(w, img_h, tot); m.out(w, img_w, tot); m.out(w, depth, tot); })) != SN_OK) return rc;
     {
         ProfScope ps(c, "project_points", 0, (double)n * 24.0 + (double)tot * (depth ? 24.0 : 16.0));
-        hipLaunchKernelGGL(project_points_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)V), dim3(256), 0, c->stream, P ? P : c->cams, xyz, n,
-                           round_int, img_h, img_w, depth);
-        HIPCHK(hipGetLastError());
+        LAUNCH(project_points_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)V), dim3(256), P ? P : c->cams, xyz, n,
+               round_int, img_h, img_w, depth);
     }
-    if ((rc = m.back(img_h, tot)) != SN_OK || (rc = m.back(img_w, tot)) != SN_OK || (rc = m.back(depth, tot)) != SN_OK) return rc;
     return m.finish();
 }
 
@@ -249,17 +245,21 @@ extern "C" int sn_mfma_probe(sn_ctx *c, double target_ms, double *tflops, double
     int iters = (int)(target_ms * 1e-3 * 2.0e9 / (56.0 * 16.1));
     if (iters < 100) iters = 100;
     float ms = 0.f;
-    for (int rep = 0; rep < 4; ++rep) {
-        hipError_t e = hipEventRecord(e0, c->stream);
-        hipLaunchKernelGGL(mfma_probe_kernel, dim3(cus), dim3(256), 0, c->stream, out, iters, clk);
-        if (e == hipSuccess) e = hipEventRecord(e1, c->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (e != hipSuccess) { cleanup(); return fail(SN_ERR_HIP, "sn_mfma_probe: %s", hipGetErrorString(e)); }
-    }
     unsigned long long h = 0;
-    if (hipMemcpy(&h, clk, 8, hipMemcpyDeviceToHost) != hipSuccess) { cleanup(); return fail(SN_ERR_HIP, "sn_mfma_probe: copy failed"); }
+    auto timed = [&]() -> int {                          // (a lambda: whatever ends it, cleanup() runs)
+        for (int rep = 0; rep < 4; ++rep) {
+            HIPCHK(hipEventRecord(e0, c->stream));
+            LAUNCH(mfma_probe_kernel, dim3(cus), dim3(256), out, iters, clk);
+            HIPCHK(hipEventRecord(e1, c->stream));
+            HIPCHK(hipEventSynchronize(e1));
+            HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+        }
+        HIPCHK(hipMemcpy(&h, clk, 8, hipMemcpyDeviceToHost));
+        return SN_OK;
+    };
+    rc = timed();
     cleanup();
+    if (rc != SN_OK) return rc;
     if (!(ms > 0.f)) return fail(SN_ERR_HIP, "sn_mfma_probe: no elapsed time");
     *tflops = flop_iter * iters / (ms * 1e-3) / 1e12;
     if (ghz) *ghz = (double)h / (ms * 1e-3) / 1e9;

@@ -38,12 +38,10 @@ int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap,
     PCStats st;
     {
         ProfScope ps(c, "pc_bounds", 0, (double)n * 3.0 * sizeof(P));
-        hipLaunchKernelGGL(cg_stats_init_kernel<unsigned long long>, dim3(1), dim3(64), 0, c->stream, d_st);
-        hipLaunchKernelGGL((cg_bounds_kernel<double, true, PCPoints<P>>), dim3(std::min(blocks(n, CG_NT), 2048u)), dim3(CG_NT), 0, c->stream, src, n, d_st);
-        HIPCHK(hipGetLastError());
+        LAUNCH(cg_stats_init_kernel<unsigned long long>, dim3(1), dim3(64), d_st);
+        LAUNCH((cg_bounds_kernel<double, true, PCPoints<P>>), dim3(std::min(blocks(n, CG_NT), 2048u)), dim3(CG_NT), src, n, d_st);
     }
-    HIPCHK(hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(read_status(c, &st, d_st));
     if (st.flags & PC_FLAG_NONFINITE) return fail(SN_ERR_ARG, "a coordinate is not finite");
     if (st.kept == 0) return SN_OK;                  // no point (left by the box): no cell
 
@@ -73,21 +71,19 @@ int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap,
         int *count = t.out<int>((size_t)n_words + 1), *sums = t.out<int>(scan_sums((size_t)n_words + 1));
         start = t.out<int>((size_t)n_words + 1);
         if (!t.ok) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
-        HIPCHK(hipMemsetAsync(a.bitmap, 0, sizeof(unsigned long long) * (size_t)n_words, c->stream));
-        HIPCHK(hipMemsetAsync(count + n_words, 0, sizeof(int), c->stream));
+        HIPCHK(dev_fill(c, a.bitmap, 0, (size_t)n_words));
+        HIPCHK(dev_fill(c, count + n_words, 0, 1));
         {
             ProfScope ps(c, "pc_cells", 0, (double)n * 3.0 * sizeof(P) + (double)n_words * 8.0);
-            hipLaunchKernelGGL((pc_mark_kernel<P, T>), dim3(blocks(n, PC_NT)), dim3(PC_NT), 0, c->stream, a);
-            HIPCHK(hipGetLastError());
+            LAUNCH((pc_mark_kernel<P, T>), dim3(blocks(n, PC_NT)), dim3(PC_NT), a);
         }
         ProfScope ps(c, "pc_scan", 0, (double)n_words * 20.0);
-        hipLaunchKernelGGL(pc_popc_kernel, dim3(blocks(n_words, PC_NT)), dim3(PC_NT), 0, c->stream, (const unsigned long long *)a.bitmap, n_words, count);
+        LAUNCH(pc_popc_kernel, dim3(blocks(n_words, PC_NT)), dim3(PC_NT), (const unsigned long long *)a.bitmap, n_words, count);
         const int rcs = scan_exclusive(c, count, start, n_words + 1, sums);       // start[n_words] = number of cells
         if (rcs != SN_OK) return rcs;
         int tot = 0;
         HIPCHK(hipMemcpyAsync(&tot, start + n_words, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(read_status(c, &st, d_st));
         total = tot;
     } else {
         const unsigned tcap = (unsigned)table_cap((unsigned long long)n, 4, 2048);
@@ -96,17 +92,15 @@ int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap,
         a.list = list = t.out<unsigned long long>(tcap / 2);       // >= 2n keys, a power of two >= PC_TILE: room for the sort's padding
         a.n_list = t.out<unsigned long long>(1);
         if (!t.ok) return fail(SN_ERR_NOMEM, "sn_ptcubes: device allocation failed");
-        HIPCHK(hipMemsetAsync(a.table, 0xff, sizeof(unsigned long long) * (size_t)tcap, c->stream));
-        HIPCHK(hipMemsetAsync(a.n_list, 0, sizeof(unsigned long long), c->stream));
+        HIPCHK(dev_fill(c, a.table, 0xff, (size_t)tcap));
+        HIPCHK(dev_fill(c, a.n_list, 0, 1));
         {
             ProfScope ps(c, "pc_cells", 0, (double)n * 3.0 * sizeof(P) + (double)tcap * 8.0);
-            hipLaunchKernelGGL((pc_insert_kernel<P, T>), dim3(blocks(n, PC_NT)), dim3(PC_NT), 0, c->stream, a);
-            HIPCHK(hipGetLastError());
+            LAUNCH((pc_insert_kernel<P, T>), dim3(blocks(n, PC_NT)), dim3(PC_NT), a);
         }
         unsigned long long m = 0;
         HIPCHK(hipMemcpyAsync(&m, a.n_list, sizeof m, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(read_status(c, &st, d_st));
         total = (long long)m;
     }
     if (st.flags & PC_FLAG_EXTENT) return fail(SN_ERR_STATE, "sn_ptcubes: a cell index left the extent computed from the cloud's bounds");
@@ -119,17 +113,14 @@ int pc_run(sn_ctx *c, PCPoints<P> src, const sn_ptcubes_cfg *cfg, long long cap,
     e.ijk = ijk; e.xyz = xyz; e.cap = total;                        // (total <= cap: the kernels emit exactly `total` cells)
     if (dense) {
         ProfScope ps(c, "pc_emit", 0, (double)total * 24.0 + (double)n_words * 12.0);
-        hipLaunchKernelGGL(pc_emit_dense_kernel, dim3(blocks(n_words, PC_NT)), dim3(PC_NT), 0, c->stream, (const unsigned long long *)a.bitmap, (const int *)start, n_words, e);
-        HIPCHK(hipGetLastError());
+        LAUNCH(pc_emit_dense_kernel, dim3(blocks(n_words, PC_NT)), dim3(PC_NT), (const unsigned long long *)a.bitmap, (const int *)start, n_words, e);
     } else {
         const long long p2 = (long long)table_cap((unsigned long long)total, 1, PC_TILE);
-        if (p2 > total) hipLaunchKernelGGL(pc_pad_kernel, dim3(blocks(p2 - total, PC_NT)), dim3(PC_NT), 0, c->stream, list, total, p2);
+        if (p2 > total) LAUNCH(pc_pad_kernel, dim3(blocks(p2 - total, PC_NT)), dim3(PC_NT), list, total, p2);
         if ((rc = pc_sort(c, list, p2)) != SN_OK) return rc;
         ProfScope ps(c, "pc_emit", 0, (double)total * 32.0);
-        hipLaunchKernelGGL(pc_emit_keys_kernel, dim3(blocks(total, PC_NT)), dim3(PC_NT), 0, c->stream, (const unsigned long long *)list, total, e);
-        HIPCHK(hipGetLastError());
+        LAUNCH(pc_emit_keys_kernel, dim3(blocks(total, PC_NT)), dim3(PC_NT), (const unsigned long long *)list, total, e);
     }
-    if ((rc = m.back(ijk, 3 * (size_t)total)) != SN_OK || (rc = m.back(xyz, 3 * (size_t)total)) != SN_OK) return rc;
     return m.finish();
 }
 

@@ -62,11 +62,10 @@ int rt_step_device(sn_ctx *c, int n, int n_vp, const float *U, const float *F, c
     c->rt_n = 0;                                         // (a failed step leaves no gradients to read)
     {
         ProfScope ps(c, "relwtrain_forward", 2.0 * R * RT_D * RT_H, (double)R * (RT_D + 3.0 * RT_H) * 4.0);
-        hipLaunchKernelGGL(rt_fc1_kernel, dim3((unsigned)R), dim3(128), 0, c->stream, F, p.P, b.a);
-        hipLaunchKernelGGL(rt_bnstats_kernel, dim3(RT_H), dim3(RT_NT), 0, c->stream, b.a, R, cfg.bn_eps, p.G);
-        hipLaunchKernelGGL(rt_hidden_kernel, dim3((unsigned)R), dim3(128), 0, c->stream, b.a, p.P, p.G, b.h, b.z);
-        hipLaunchKernelGGL(rt_softmax_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, c->stream, b.z, b.w, n, n_vp);
-        HIPCHK(hipGetLastError());
+        LAUNCH(rt_fc1_kernel, dim3((unsigned)R), dim3(128), F, p.P, b.a);
+        LAUNCH(rt_bnstats_kernel, dim3(RT_H), dim3(RT_NT), b.a, R, cfg.bn_eps, p.G);
+        LAUNCH(rt_hidden_kernel, dim3((unsigned)R), dim3(128), b.a, p.P, p.G, b.h, b.z);
+        LAUNCH(rt_softmax_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), b.z, b.w, n, n_vp);
     }
     {
         RTVoxArgs a;
@@ -75,35 +74,31 @@ int rt_step_device(sn_ctx *c, int n, int n_vp, const float *U, const float *F, c
         const uintptr_t bits = reinterpret_cast<uintptr_t>(U) | reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(f);
         a.vec = (V % 4 == 0 && (bits & 15) == 0) ? 1 : 0;
         ProfScope ps(c, "relwtrain_voxel", 0, (double)n * V * 4.0 * (n_vp + 1 + (f ? 1 : 0)));
-        hipLaunchKernelGGL(rt_voxel_kernel, dim3((unsigned)chunks, (unsigned)n), dim3(RT_NT), 0, c->stream, a);
-        HIPCHK(hipGetLastError());
+        LAUNCH(rt_voxel_kernel, dim3((unsigned)chunks, (unsigned)n), dim3(RT_NT), a);
     }
     {
         ProfScope ps(c, "relwtrain_backward", 2.0 * R * RT_D * RT_H, (double)R * (RT_D + 4.0 * RT_H) * 4.0);
-        hipLaunchKernelGGL(rt_dw_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, c->stream, b.part, b.w, n, n_vp, (int)chunks, nV, b.dw, b.dz);
-        if (cfg.l2 != 0.f) hipLaunchKernelGGL(rt_sqsum_kernel, dim3(1), dim3(RT_NT), 0, c->stream, p.P, b.sq);
-        hipLaunchKernelGGL(rt_loss_kernel, dim3(1), dim3(RT_NT), 0, c->stream, b.part, (long long)n * (long long)chunks, n_vp, nV, cfg.l2, b.sq, b.loss);
-        hipLaunchKernelGGL(rt_colsum_kernel, dim3(RT_H + 1), dim3(RT_NT), 0, c->stream, b.a, b.h, b.dz, p.P, R, cfg.l2, p.G, b.S);
-        hipLaunchKernelGGL(rt_da_kernel, dim3((unsigned)R), dim3(128), 0, c->stream, b.a, b.h, b.dz, p.P, p.G, b.S, R, b.da);
-        hipLaunchKernelGGL(rt_dW1_kernel, dim3(RT_D), dim3(128), 0, c->stream, F, b.da, p.P, R, cfg.l2, p.G);
-        HIPCHK(hipGetLastError());
+        LAUNCH(rt_dw_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), b.part, b.w, n, n_vp, (int)chunks, nV, b.dw, b.dz);
+        if (cfg.l2 != 0.f) LAUNCH(rt_sqsum_kernel, dim3(1), dim3(RT_NT), p.P, b.sq);
+        LAUNCH(rt_loss_kernel, dim3(1), dim3(RT_NT), b.part, (long long)n * (long long)chunks, n_vp, nV, cfg.l2, b.sq, b.loss);
+        LAUNCH(rt_colsum_kernel, dim3(RT_H + 1), dim3(RT_NT), b.a, b.h, b.dz, p.P, R, cfg.l2, p.G, b.S);
+        LAUNCH(rt_da_kernel, dim3((unsigned)R), dim3(128), b.a, b.h, b.dz, p.P, p.G, b.S, R, b.da);
+        LAUNCH(rt_dW1_kernel, dim3(RT_D), dim3(128), F, b.da, p.P, R, cfg.l2, p.G);
     }
     if (weights) HIPCHK(hipMemcpyAsync(weights, b.w, sizeof(float) * (size_t)R, hipMemcpyDeviceToDevice, c->stream));
     if (cfg.update != 0) {
         ProfScope ps(c, "relwtrain_update", 0, (double)RT_NP * 4.0 * 6.0);
-        hipLaunchKernelGGL(rt_update_kernel, dim3((RT_NG + 2 * RT_H + 255) / 256), dim3(256), 0, c->stream, p.P, p.Vel, p.G, cfg.lr, cfg.momentum,
-                           cfg.bn_alpha, cfg.update);
-        hipLaunchKernelGGL(rt_fold_kernel, dim3((RT_D * RT_H + 255) / 256), dim3(256), 0, c->stream, p.P, c->relw_W1, c->relw_scale, c->relw_shift,
-                           c->relw_w2, c->relw_bn);
-        HIPCHK(hipGetLastError());
+        LAUNCH(rt_update_kernel, dim3((RT_NG + 2 * RT_H + 255) / 256), dim3(256), p.P, p.Vel, p.G, cfg.lr, cfg.momentum,
+               cfg.bn_alpha, cfg.update);
+        LAUNCH(rt_fold_kernel, dim3((RT_D * RT_H + 255) / 256), dim3(256), p.P, c->relw_W1, c->relw_scale, c->relw_shift,
+               c->relw_w2, c->relw_bn);
         c->relw_b2_stale = true;
     }
     if (counts && (rc = gt_accuracy_device(c, n, f, Y, 0.5f, counts)) != SN_OK) return rc;
     c->rt_n = n; c->rt_nvp = n_vp;
     if (loss) {
         float l = 0.f;
-        HIPCHK(hipMemcpyAsync(&l, b.loss, sizeof l, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(read_status(c, &l, b.loss));
         *loss = (double)l;
     }
     return SN_OK;
@@ -147,8 +142,8 @@ extern "C" int sn_relw_train_begin(sn_ctx *c, const sn_relw_train_cfg *cfg)
     HIPCHK(hipMemcpyAsync(b.P + RT_P_BETA, c->relw_bn, sizeof(float) * 4 * RT_H, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(b.P + RT_P_W2, c->relw_w2, sizeof(float) * RT_H, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(b.P + RT_P_B2, &c->relw_b2, sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemsetAsync(b.Vel, 0, sizeof(float) * RT_NG, c->stream));
-    HIPCHK(hipMemsetAsync(b.G, 0, sizeof(float) * RT_NG_ALL, c->stream));
+    HIPCHK(dev_fill(c, b.Vel, 0, RT_NG));
+    HIPCHK(dev_fill(c, b.G, 0, RT_NG_ALL));
     HIPCHK(hipStreamSynchronize(c->stream));             // (relw_b2 is read from the host)
     c->relw_b2_dev = b.P + RT_P_B2;
     c->rt_cfg = *cfg;
@@ -188,7 +183,6 @@ extern "C" int sn_relw_train_step(sn_ctx *c, int n, int n_vp, const float *unfus
     if ((rc = m.inputs([&](Carve &w) { m.in(w, unfused, R * V); m.in(w, features, R * RT_D); m.in(w, Y, N * V); })) != SN_OK) return rc;
     if ((rc = m.outputs([&](Carve &w) { m.out(w, fused, N * V); m.out(w, weights, R); m.out(w, counts, 4 * N); })) != SN_OK) return rc;
     if ((rc = rt_step_device(c, n, n_vp, unfused, features, Y, fused, weights, counts, loss)) != SN_OK) return rc;
-    if ((rc = m.back(fused, N * V)) != SN_OK || (rc = m.back(weights, R)) != SN_OK || (rc = m.back(counts, 4 * N)) != SN_OK) return rc;
     return m.finish();
 }
 

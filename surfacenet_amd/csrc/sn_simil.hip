@@ -170,15 +170,13 @@ static int run_simil(sn_ctx *c, const SimilWs &w, int n)
         for (int k = 0; k < 5; ++k) { fa.pool[k] = w.pool[k].p; fa.lo_off[k] = w.pool[k].lo; }
         fa.feat = w.feat; fa.n = n;
         ProfScope ps(c, "s_features", 0, (double)n * kSimilFeat * (2.0 * (sp ? 2 : 1) + 4.0));
-        if (sp) hipLaunchKernelGGL(simil_features_kernel<1>, dim3((unsigned)n), dim3(256), 0, c->stream, fa);
-        else hipLaunchKernelGGL(simil_features_kernel<0>, dim3((unsigned)n), dim3(256), 0, c->stream, fa);
-        HIPCHK(hipGetLastError());
+        if (sp) LAUNCH(simil_features_kernel<1>, dim3((unsigned)n), dim3(256), fa);
+        else LAUNCH(simil_features_kernel<0>, dim3((unsigned)n), dim3(256), fa);
     }
     {
         ProfScope ps(c, "s_dense", 2.0 * n * kSimilFeat * kEmb, (double)n * (kSimilFeat + kEmb) * 4.0 + (double)kSimilFeat * kEmb * 4.0);
-        hipLaunchKernelGGL(simil_dense_kernel, dim3((unsigned)((n + 31) / 32), kDenseKS), dim3(256), 0, c->stream, w.feat, c->semb_W, w.part, n);
-        hipLaunchKernelGGL(simil_dense_reduce_kernel, dim3((unsigned)((n * kEmb + 255) / 256)), dim3(256), 0, c->stream, w.part, c->semb_b, w.emb, n);
-        HIPCHK(hipGetLastError());
+        LAUNCH(simil_dense_kernel, dim3((unsigned)((n + 31) / 32), kDenseKS), dim3(256), w.feat, c->semb_W, w.part, n);
+        LAUNCH(simil_dense_reduce_kernel, dim3((unsigned)((n * kEmb + 255) / 256)), dim3(256), w.part, c->semb_b, w.emb, n);
     }
     return SN_OK;
 }
@@ -197,11 +195,10 @@ static int launch_crop(sn_ctx *c, int view, int n, const double *ch_dev, const d
     const float mb = mean_bgr ? mean_bgr[0] : 0.f, mg = mean_bgr ? mean_bgr[1] : 0.f, mr = mean_bgr ? mean_bgr[2] : 0.f;
     const int sp = simil_mode(c);
     ProfScope ps(c, "patch_crop", 0, (double)total * (3.0 + (patches_dev ? 3.0 : 0.0) + (p0.p ? 16.0 * (sp ? 2 : 1) : 0.0)));
-    if (sp) hipLaunchKernelGGL(patch_crop_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, img, c->h_img_h[view], c->h_img_w[view],
-                               ch_dev, cw_dev, n, patches_dev, p0.p, p0.lo, mb, mg, mr);
-    else hipLaunchKernelGGL(patch_crop_kernel<0>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, img, c->h_img_h[view], c->h_img_w[view],
-                            ch_dev, cw_dev, n, patches_dev, p0.p, p0.lo, mb, mg, mr);
-    HIPCHK(hipGetLastError());
+    if (sp) LAUNCH(patch_crop_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), img, c->h_img_h[view], c->h_img_w[view],
+                   ch_dev, cw_dev, n, patches_dev, p0.p, p0.lo, mb, mg, mr);
+    else LAUNCH(patch_crop_kernel<0>, dim3((unsigned)((total + 255) / 256)), dim3(256), img, c->h_img_h[view], c->h_img_w[view],
+                ch_dev, cw_dev, n, patches_dev, p0.p, p0.lo, mb, mg, mr);
     return SN_OK;
 }
 
@@ -253,9 +250,8 @@ extern "C" int sn_patch2embedding(sn_ctx *c, int n, const float *patches, float 
         {
             const long long total = (long long)m * kPatch * kPatch;
             ProfScope ps(c, "nchw_to_p0", 0, (double)total * (12.0 + 16.0 * (simil_mode(c) ? 2 : 1)));
-            if (simil_mode(c)) hipLaunchKernelGGL(nchw_to_p0_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, d_x, m, w.p0.p, w.p0.lo);
-            else hipLaunchKernelGGL(nchw_to_p0_kernel<0>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, d_x, m, w.p0.p, w.p0.lo);
-            HIPCHK(hipGetLastError());
+            if (simil_mode(c)) LAUNCH(nchw_to_p0_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), d_x, m, w.p0.p, w.p0.lo);
+            else LAUNCH(nchw_to_p0_kernel<0>, dim3((unsigned)((total + 255) / 256)), dim3(256), d_x, m, w.p0.p, w.p0.lo);
         }
         if ((rc = run_simil(c, w, m)) != SN_OK) return rc;
         HIPCHK(hipMemcpyAsync(embeddings + (size_t)i0 * kEmb, w.emb, sizeof(float) * kEmb * m, hipMemcpyDeviceToHost, c->stream));
@@ -307,10 +303,8 @@ extern "C" int sn_embeddingpair2simil(sn_ctx *c, int n_pairs, const float *emb_p
     if ((rc = m.outputs([&](Carve &w) { m.out(w, similarity, (size_t)n_pairs); })) != SN_OK) return rc;
     {
         ProfScope ps(c, "pair_simil", 0, (double)n_pairs * (2.0 * kEmb + 1.0) * 4.0);
-        hipLaunchKernelGGL(pair_simil_kernel, dim3((unsigned)((n_pairs + 3) / 4)), dim3(256), 0, c->stream, emb_pairs, similarity, n_pairs, c->ssim_w, c->ssim_b);
-        HIPCHK(hipGetLastError());
+        LAUNCH(pair_simil_kernel, dim3((unsigned)((n_pairs + 3) / 4)), dim3(256), emb_pairs, similarity, n_pairs, c->ssim_w, c->ssim_b);
     }
-    if ((rc = m.back(similarity, (size_t)n_pairs)) != SN_OK) return rc;
     return m.finish();
 }
 
@@ -334,11 +328,9 @@ extern "C" int sn_embeddings2simil(sn_ctx *c, int n_cubes, int n_views, const fl
     if ((rc = m.outputs([&](Carve &w) { m.out(w, similarity, ns); })) != SN_OK) return rc;
     {
         ProfScope ps(c, "pair_simil_all", 0, (double)ns * (2.0 * kEmb + 1.0) * 4.0);
-        hipLaunchKernelGGL(pair_simil_all_kernel, dim3((unsigned)((ns + 3) / 4)), dim3(256), 0, c->stream, embeddings, d_p, similarity, (long long)ns, n_views, P,
-                           c->ssim_w, c->ssim_b);
-        HIPCHK(hipGetLastError());
+        LAUNCH(pair_simil_all_kernel, dim3((unsigned)((ns + 3) / 4)), dim3(256), embeddings, d_p, similarity, (long long)ns, n_views, P,
+               c->ssim_w, c->ssim_b);
     }
-    if ((rc = m.back(similarity, ns)) != SN_OK) return rc;
     return m.finish();
 }
 

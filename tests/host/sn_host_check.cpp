@@ -86,8 +86,11 @@ static void check_carve_empty_get()
 
 // ---- MirrorPlan: a host buffer as the "device", memcpy as the copy -----------------------------------------------------------------------------
 // What sn_internal.h's HostMirror does with a plan, without a device: one buffer per layout (measured, then placed), the recorded inputs
-// copied in, an output's first `count` elements copied back.
+// copied in, an output's first `count` elements copied back early (back), every output not yet returned copied back at its staged size
+// (finish). `copies` lists what went to the caller's arrays, in order.
 struct HostExec {
+    struct Copy { const void *host; size_t bytes; };
+    std::vector<Copy> copies;
     MirrorPlan plan;
     std::vector<unsigned char> buf[2];                           // the inputs' and the outputs' buffer
     unsigned char *base[2] = {nullptr, nullptr};
@@ -111,10 +114,20 @@ struct HostExec {
     }
     template <typename T> void back(const T *dev, size_t count)
     {
-        if (!plan.on || !dev || !count) return;
-        const MirrorPlan::Rec *r = plan.find(dev);
+        if (!plan.on || !dev) return;
+        const MirrorPlan::Rec *r = plan.note_back(dev, count * sizeof(T));
         CHECK(r && !r->input && count * sizeof(T) <= r->bytes);
-        memcpy(r->host, dev, count * sizeof(T));
+        if (count) to_host(r->host, dev, count * sizeof(T));
+    }
+    void finish()
+    {
+        CHECK(plan.each_pending([&](void *host, const void *dev, size_t bytes) { return to_host(host, dev, bytes); }));
+    }
+    bool to_host(void *host, const void *dev, size_t bytes)
+    {
+        memcpy(host, dev, bytes);
+        copies.push_back(Copy{host, bytes});
+        return true;
     }
     // every recorded region: aligned, inside its buffer, apart from every other and from the scratch
     void check_regions() const
@@ -165,8 +178,70 @@ template <typename T> static void check_back(HostExec &x, T *dev, std::vector<T>
     }
 }
 
+// ---- finish(): what goes back without being asked for ------------------------------------------------------------------------------------
+// A caller's array of count + 1 elements and what the plan made of it: `dev` is the swapped pointer (the array itself with the mirror off).
+struct Arr { unsigned char *host; size_t host_bytes; unsigned char *dev; size_t bytes, elem; };
+template <typename T> static Arr arr(std::vector<T> &host, const T *dev, size_t count)
+{
+    return Arr{reinterpret_cast<unsigned char *>(host.data()), host.size() * sizeof(T), reinterpret_cast<unsigned char *>(const_cast<T *>(dev)),
+               count * sizeof(T), sizeof(T)};
+}
+static void scribble(unsigned char *p, size_t bytes, unsigned seed)
+{
+    for (size_t i = 0; i < bytes; ++i) p[i] = (unsigned char)(seed * 131u + i * 7u + (i >> 8));
+}
+static bool scribbled(const unsigned char *p, size_t bytes, unsigned seed)
+{
+    for (size_t i = 0; i < bytes; ++i)
+        if (p[i] != (unsigned char)(seed * 131u + i * 7u + (i >> 8))) return false;
+    return true;
+}
+
+// The call ends with finish() and names no output again. early: each output's first half is returned by back() before the kernels "write" a
+// second pattern, so whatever finish() copied of it would show. The inputs' device copies are overwritten too: none of that may come back.
+static void check_finish(HostExec &x, const std::vector<Arr> &ins, const std::vector<Arr> &outs, bool early)
+{
+    std::vector<std::vector<unsigned char>> in_before;
+    for (const Arr &a : ins) in_before.emplace_back(a.host, a.host + a.host_bytes);
+    for (const Arr &a : outs) memset(a.host, 0x5c, a.host_bytes);
+    if (!x.plan.on) {                                            // a device form: nothing is copied, by back() or by finish()
+        for (const Arr &a : outs) { CHECK(a.dev == a.host); x.back(a.dev, a.bytes / 2); }
+        x.finish();
+        CHECK(x.copies.empty());
+        for (const Arr &a : outs)
+            for (size_t i = 0; i < a.host_bytes; ++i) CHECK(a.host[i] == 0x5c);
+        for (size_t k = 0; k < ins.size(); ++k) CHECK(memcmp(ins[k].host, in_before[k].data(), ins[k].host_bytes) == 0);
+        return;
+    }
+    x.copies.clear();
+    for (const Arr &a : outs) scribble(a.dev, a.bytes, 21);
+    std::vector<size_t> expect;                                  // bytes of each output that arrive
+    for (const Arr &a : outs) expect.push_back(early ? a.bytes / a.elem / 2 * a.elem : a.bytes);
+    if (early) {
+        for (size_t k = 0; k < outs.size(); ++k) x.back(outs[k].dev, expect[k]);
+        for (const Arr &a : outs) scribble(a.dev, a.bytes, 22);
+    }
+    for (const Arr &a : ins) scribble(a.dev, a.bytes, 23);
+    x.finish();
+    size_t n_copies = 0;
+    for (size_t k = 0; k < outs.size(); ++k) {
+        const Arr &a = outs[k];
+        CHECK(scribbled(a.host, expect[k], 21));                 // the first pattern, at exactly the expected size
+        for (size_t i = expect[k]; i < a.host_bytes; ++i) CHECK(a.host[i] == 0x5c);
+        if (!expect[k]) continue;
+        CHECK(n_copies < x.copies.size() && x.copies[n_copies].host == a.host && x.copies[n_copies].bytes == expect[k]);      // once, in order
+        ++n_copies;
+    }
+    CHECK(x.copies.size() == n_copies);                          // nothing else: no input, no output twice, none at its staged size after back()
+    for (size_t k = 0; k < ins.size(); ++k) CHECK(memcmp(ins[k].host, in_before[k].data(), ins[k].host_bytes) == 0);
+    x.finish();
+    CHECK(x.copies.size() == n_copies);                          // a second finish() has nothing left to return
+}
+
+enum Ending { ENDS_BACK, ENDS_FINISH, ENDS_EARLY_FINISH };       // explicit back() of every output | finish() alone | back() of a half, then finish()
+
 // sn_normals' arrays (sn_normals.hip nm_call): n cubes, T voxels, K views per cube of V cameras; the moments are not asked for (a null output)
-static void check_mirror_normals(size_t n, bool on)
+static void check_mirror_normals(size_t n, bool on, Ending ending)
 {
     const size_t T = 7 * n, K = 5, V = 9;
     std::vector<int64_t> off = pattern<int64_t>(n + 1, 1);
@@ -189,10 +264,14 @@ static void check_mirror_normals(size_t n, bool on)
     });
     x.carve(1, [&](Carve &w) { x.plan.out(w, p_normals, 3 * T); x.plan.out(w, p_moments, 10 * T); });
     CHECK(p_moments == nullptr);                                 // a null array takes no region and stays null
+    const std::vector<Arr> ins = {arr(off, p_off, n + 1), arr(cube, p_cube, 3 * n), arr(ijk, p_ijk, 3 * T), arr(mask, p_mask, T),
+                                  arr(xyz, p_xyz, 3 * n), arr(resol, p_resol, n), arr(view, p_view, n * K), arr(cams, p_cams, 3 * V)};
+    const std::vector<Arr> outs = {arr(normals, p_normals, 3 * T)};
     if (!on) {                                                   // a device form: no pointer changes, no region is taken
         CHECK(x.plan.recs.empty() && p_off == off.data() && p_cams == cams.data() && p_normals == normals.data());
         CHECK(x.size[0] == std::max<size_t>(n, 1) * sizeof(float) && x.size[1] == 0);      // (the scratch alone)
         x.back(p_normals, 3 * T);
+        if (ending != ENDS_BACK) check_finish(x, ins, outs, ending == ENDS_EARLY_FINISH);
         return;
     }
     CHECK(x.plan.recs.size() == 9);
@@ -200,11 +279,12 @@ static void check_mirror_normals(size_t n, bool on)
     check_arrived(x, p_off, off, n + 1); check_arrived(x, p_cube, cube, 3 * n); check_arrived(x, p_ijk, ijk, 3 * T); check_arrived(x, p_mask, mask, T);
     check_arrived(x, p_xyz, xyz, 3 * n); check_arrived(x, p_resol, resol, n); check_arrived(x, p_view, view, n * K); check_arrived(x, p_cams, cams, 3 * V);
     CHECK(x.plan.find(scratch) == nullptr && x.plan.find(normals.data()) == nullptr);
-    check_back(x, p_normals, normals, 3 * T);
+    if (ending == ENDS_BACK) check_back(x, p_normals, normals, 3 * T);
+    else check_finish(x, ins, outs, ending == ENDS_EARLY_FINISH);
 }
 
 // sn_mesh's arrays (sn_mesh.hip ms_call / ms_run): the outputs are staged at the counts the kernels found, nv vertices and nq quads
-static void check_mirror_mesh(size_t n, bool on)
+static void check_mirror_mesh(size_t n, bool on, Ending ending)
 {
     const size_t T = 7 * n, nv = 3 * n, nq = 2 * n;
     std::vector<int64_t> off = pattern<int64_t>(n + 1, 11), vsrc(nv + 1);
@@ -223,15 +303,19 @@ static void check_mirror_mesh(size_t n, bool on)
         x.plan.out(w, p_vmm, 3 * nv); x.plan.out(w, p_vlat, 3 * nv); x.plan.out(w, p_vcell, 3 * nv); x.plan.out(w, p_vsrc, nv); x.plan.out(w, p_quads, 4 * nq);
     });
     CHECK(p_vcell == nullptr);
+    const std::vector<Arr> ins = {arr(off, p_off, n + 1), arr(cube, p_cube, 3 * n), arr(ijk, p_ijk, 3 * T), arr(mask, p_mask, T), arr(nrm, p_nrm, 3 * T)};
+    const std::vector<Arr> outs = {arr(vmm, p_vmm, 3 * nv), arr(vlat, p_vlat, 3 * nv), arr(vsrc, p_vsrc, nv), arr(quads, p_quads, 4 * nq)};
     if (!on) {
         CHECK(x.plan.recs.empty() && x.size[0] == 0 && x.size[1] == 0);
         CHECK(p_off == off.data() && p_nrm == nrm.data() && p_vmm == vmm.data() && p_quads == quads.data());
+        if (ending != ENDS_BACK) check_finish(x, ins, outs, ending == ENDS_EARLY_FINISH);
         return;
     }
     CHECK(x.plan.recs.size() == 9);
     x.check_regions();
     check_arrived(x, p_off, off, n + 1); check_arrived(x, p_cube, cube, 3 * n); check_arrived(x, p_ijk, ijk, 3 * T); check_arrived(x, p_mask, mask, T);
     check_arrived(x, p_nrm, nrm, 3 * T);
+    if (ending != ENDS_BACK) return check_finish(x, ins, outs, ending == ENDS_EARLY_FINISH);
     check_back(x, p_vmm, vmm, 3 * nv); check_back(x, p_vlat, vlat, 3 * nv); check_back(x, p_vsrc, vsrc, nv); check_back(x, p_quads, quads, 4 * nq);
 }
 
@@ -357,10 +441,16 @@ int main()
         check_carve(normals_layout, n);
         check_carve(grid_layout, n);
         for (bool on : {true, false}) {
-            check_mirror_normals(n, on);
-            check_mirror_mesh(n, on);
+            check_mirror_normals(n, on, ENDS_BACK);
+            check_mirror_mesh(n, on, ENDS_BACK);
         }
     }
+    for (size_t n : {(size_t)0, (size_t)1, (size_t)5})
+        for (bool on : {true, false})
+            for (Ending ending : {ENDS_FINISH, ENDS_EARLY_FINISH}) {
+                check_mirror_normals(n, on, ending);
+                check_mirror_mesh(n, on, ending);
+            }
     check_carve_empty_get();
     check_table_cap();
     check_packed_lists();

@@ -265,6 +265,104 @@ def test_dense2sparse_small_large_small(ctx):
     assert _same(first, _dense2sparse(ctx, 1))
 
 
+# ---- the host mirror returns what was staged, and no more ---------------------------------------------------------------------------------------
+SENTINEL = 0x5C
+
+
+def _sentinels(spec):
+    """One array per (rows, width, dtype) of spec, every byte SENTINEL."""
+    outs = [np.empty((rows, width) if width > 1 else (rows,), dtype) for rows, width, dtype in spec]
+    for o in outs:
+        o.view(np.uint8)[...] = SENTINEL
+    return outs
+
+
+def _host_and_device(ctx, ins, spec, call):
+    """call(form, input pointers, output pointers) -> status on sentinel-filled outputs, through ctypes: the host form on the arrays themselves,
+    the device form on copies staged here and read back whole. -> (host outputs, device outputs)."""
+    from surfacenet_amd import _lib
+    host, dev = _sentinels(spec), _sentinels(spec)
+    assert call(False, [_lib.ptr(a) for a in ins], [_lib.ptr(o) for o in host]) == 0, _lib.last_error()
+    with ctx._on_device([a for a in ins if a is not None]) as src, ctx._on_device(dev) as dst:
+        src = iter(src)
+        assert call(True, [None if a is None else next(src) for a in ins], dst) == 0, _lib.last_error()
+        for o, d in zip(dev, dst):
+            ctx.d2h(o, d)
+    return host, dev
+
+
+def _rows_then_sentinel(host, dev, rows):
+    """Rows [0, rows[k]) of host output k equal the device form's byte for byte, and every byte beyond them is still the sentinel."""
+    for k, (h, d, r) in enumerate(zip(host, dev, rows)):
+        assert 0 < r <= h.shape[0], k
+        assert np.array_equal(h[:r].view(np.uint8), d[:r].view(np.uint8)), k
+        assert (h[r:].view(np.uint8) == SENTINEL).all(), k
+    assert any(r < h.shape[0] for h, r in zip(host, rows))      # the tail exists
+
+
+def test_mesh_simplify_host_form_returns_the_counted_rows_only(ctx):
+    """Outputs that hold 9 vertices and 8 faces, of which the simplified 2 x 2 sheet needs fewer: the host form writes what the device form
+    writes, and nothing behind it."""
+    import ctypes
+    from surfacenet_amd import _lib
+    v = np.asarray([(i, j, 0) for i in range(3) for j in range(3)], np.float64)
+    quads = np.asarray([(3 * i + j, 3 * (i + 1) + j, 3 * (i + 1) + j + 1, 3 * i + j + 1) for i in range(2) for j in range(2)])
+    f = np.ascontiguousarray(meshsimplify_ref.triangulate(quads), np.int32)
+    want = meshsimplify_ref.simplify(v, f, 2)
+    C, G = want["vertices"].shape[0], want["faces"].shape[0]
+    assert v.shape[0] == 9 and f.shape[0] == 8 and 0 < C < 9 and 0 < G < 8
+    cfg = ctx._on_lattice(_lib.MeshSimplifyCfg(2, 0), (0.0, 0.0, 0.0), 1.0)
+    spec = ((9, 3, np.float32), (9, 3, np.float64), (9, 1, np.int32), (9, 1, np.int32), (8, 3, np.int32), (8, 1, np.int32), (9, 1, np.int32))
+    counts = []
+
+    def call(device, ins, outs):
+        nv, nf = ctypes.c_longlong(-1), ctypes.c_longlong(-1)
+        fn = ctx._lib.sn_mesh_simplify_dev if device else ctx._lib.sn_mesh_simplify
+        rc = fn(ctx._h, ctypes.byref(cfg), 9, ins[0], 8, ins[1], 9, 8, *outs, ctypes.byref(nv), ctypes.byref(nf))
+        counts.append((nv.value, nf.value))
+        return rc
+
+    host, dev = _host_and_device(ctx, [v, f], spec, call)
+    assert counts == [(C, G), (C, G)]
+    _rows_then_sentinel(host, dev, [C, C, C, C, G, G, 9])
+    assert np.array_equal(host[4][:G], want["faces"]) and np.array_equal(host[6], want["vert_cluster"])
+
+
+@pytest.mark.parametrize("pooling", [False, True])
+def test_dense2sparse_host_form_returns_the_listed_rows_only(ctx, pooling):
+    """sn_dense2sparse stages its lists at their upper bound, n s^3 rows, and returns the T rows its offsets table counts: those equal the
+    device form's, and rows [T, n s^3) of the caller's arrays are not written."""
+    import ctypes
+    from surfacenet_amd import _lib
+    n, n_vp, cap = 2, 2, 2 * S ** 3
+    rs = np.random.RandomState(7)
+    pred = np.full((n, S, S, S), 0.125, np.float32)
+    for i, kept in enumerate((5, 7)):                           # a handful of voxels per cube above min_prob, each value a float16
+        at = rs.choice(S ** 3, kept, replace=False)
+        pred[i].reshape(-1)[at] = (0.6 + 0.3 * rs.rand(kept)).astype(np.float16)
+    pairs = np.ascontiguousarray(rs.randint(0, 4, (n, n_vp, 2)), np.int64)
+    xyz = (rs.rand(n, 3) * [60, 60, 40] + [-30, -30, 590]).astype(np.float32)
+    resol = np.full(n, 0.4, np.float32)
+    rgb = rs.randint(0, 256, (n, 3, S, S, S)).astype(np.uint8)
+    cfg = _lib.SparseCfg(0.5, 0, 0, S, int(pooling))
+    spec = ((n + 1, 1, np.int64), (cap, 3, np.uint8), (cap, 1, np.uint16), (cap, 3, np.uint8)) + (((cap, 1, np.uint8),) if pooling else ())
+    ins = [pairs, xyz, resol, pred, rgb] if pooling else [None, None, None, pred, rgb]
+
+    def call(device, ins, outs):
+        outs = list(outs) + [None] * (5 - len(outs))
+        if not device:
+            return ctx._lib.sn_dense2sparse(ctx._h, n, n_vp, *ins, ctypes.byref(cfg), *outs)
+        return ctx._lib.sn_dense2sparse_dev(ctx._h, n, n_vp, *ins, ctypes.byref(cfg), votes_ws[0] if pooling else None, *outs)
+
+    with ctx._on_device([np.zeros(n * S ** 3, np.uint8)]) as votes_ws:      # the device form's scratch: every voxel's votes
+        host, dev = _host_and_device(ctx, ins, spec, call)
+    off = host[0]
+    T = int(off[n])
+    assert off.tolist() == [0, 5, 12] and T < cap
+    _rows_then_sentinel(host, dev, [n + 1] + [T] * (len(spec) - 1))
+    assert np.array_equal(np.sort(host[2][:T].view(np.float16)), np.sort(pred[pred >= 0.5].astype(np.float16)))
+
+
 # ---- similarityNet: the chunk workspace and the per-call buffer ---------------------------------------------------------------------------------------
 def _centres(n):
     rs = np.random.RandomState(n)
