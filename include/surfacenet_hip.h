@@ -36,7 +36,8 @@ extern "C" {
  * sn_mesh_normals and sn_mesh_normals_dev - a mesh's own area-weighted normals with its exact area and volume;
  * sn_mesh_orient, sn_mesh_orient_dev and sn_mesh_orient_cfg - a mesh's faces made to turn one way, its pieces and their exact volumes;
  * sn_mesh_render, sn_mesh_render_dev, sn_mesh_vertex_colors, sn_mesh_vertex_colors_dev and sn_mesh_render_cfg - a mesh rendered back into its
- * views: depth maps, face ids, visibility, vertex colours. */
+ * views: depth maps, face ids, visibility, vertex colours; sn_mesh_intersect, sn_mesh_intersect_dev and sn_mesh_intersect_cfg - the pairs of
+ * faces of a mesh that cross or touch each other, exactly. */
 
 /* The library is built with -fvisibility=hidden: the functions below are its WHOLE dynamic symbol table
  * (tests/test_abi.py compares `nm -D` with this header). */
@@ -519,7 +520,7 @@ SN_API int sn_mesh_normals_dev(sn_ctx *ctx, int n_verts, const double *verts_dev
  * [0, n_verts) or a referenced coordinate outside the range (or not a number), the text naming the first offending face; nv not 3 or 4,
  * n_verts or n_faces > 2^28, 2^30 or more edges; and sign not 0 or 1, min_faces < 0, keep_largest not 0 or 1. Non-manifold edges are not
  * split or paired, non-orientable pieces are reported and left alone, an open piece has no outward test, vertices that lose all their faces
- * stay, and nothing looks for self-intersections. Everything is an integer: the result equals the numpy restatement tests/meshorient_ref.py
+ * stay, and self-intersections are sn_mesh_intersect's to find. Everything is an integer: the result equals the numpy restatement tests/meshorient_ref.py
  * byte for byte, on every run. The workspace belongs to the context (grown on demand); both forms return when the work is done. */
 typedef struct sn_mesh_orient_cfg {
     int sign;                  /* 0: majority - the fewer faces of a piece turn; 1: outward - a closed piece turns iff its volume is negative */
@@ -533,6 +534,47 @@ SN_API int sn_mesh_orient_dev(sn_ctx *ctx, const sn_mesh_orient_cfg *cfg, int n_
                               const int32_t *faces_dev, int32_t *faces_out_dev, unsigned char *face_flip_dev, int32_t *face_component_dev,
                               unsigned char *face_keep_dev, int32_t *comp_faces_dev, unsigned char *comp_flags_dev,
                               unsigned long long *comp_vol6_dev, long long *counts);
+
+/* ---- a mesh's self-intersections, exactly -----------------------------------------------------------------------------------
+ * The inputs are sn_mesh_smooth's: verts (n_verts,3) float64 in lattice cells, faces (n_faces,nv) int32 with nv = 3 or 4; referenced vertices,
+ * q = int64(rint(v * 65536)) and its range -4 <= v < 2^21 - 8 as there. Every difference of two q is below 2^38 and every 3x3 determinant of
+ * differences below 2^117: all arithmetic is exact in 128-bit integers, and only signs are used.
+ *   1 triangles  a triangle face is one triangle, a quad (a,b,c,d) is (a,b,c) then (a,c,d). A triangle is DEGENERATE iff two of its indices
+ *                are equal or (q_b - q_a) x (q_c - q_a) = 0: it is skipped, and its face is counted once among the degenerate faces.
+ *   2 signs      orient3(a,b,c,d) = sign(((b - a) x (c - a)) . (d - a)). The drop axis of a triangle is the axis of its normal's largest
+ *                magnitude, the lowest axis among equals; orient2 is the sign of the 2x2 determinant in the two kept axes, in their order.
+ *   3 segment    closed segment pq against closed non-degenerate triangle abc: sp = orient3(a,b,c,p), sq = orient3(a,b,c,q). sp * sq > 0: no.
+ *                Both 0: in the triangle's projection, yes iff p is in the triangle, or q is, or pq meets one of the three edges - a point is
+ *                in the triangle iff its three orient2 signs do not hold both a positive and a negative; segment against segment is the
+ *                four-sign test, collinear endpoints decided by the closed bounding box. Otherwise: yes iff orient3(p,q,a,b),
+ *                orient3(p,q,b,c), orient3(p,q,c,a) do not hold both a positive and a negative.
+ *   4 triangles  two non-degenerate triangles of different faces, k = the vertex INDICES they share. k = 0: they intersect iff one of the six
+ *                edge-against-triangle tests says yes. k = 1: iff the edge opposite the shared index in one meets the other triangle, either
+ *                way round. k = 2, shared edge u < v, apexes a, b: iff orient3(q_u,q_v,q_a,q_b) = 0 and (q_v - q_u) x (q_a - q_u), (q_v - q_u)
+ *                x (q_b - q_u) have the same sign in the first one's drop axis - coplanar and folded over. k = 3: they intersect. Vertices
+ *                that coincide in position but not in index are k = 0 contact: closed sets, so T-junctions and coincident seams intersect.
+ *   5 pairs      faces f < g are an intersecting pair iff some triangle of f and some triangle of g intersect; the two triangles of one quad
+ *                are never tested against each other.
+ * Outputs, each optional (NULL) except counts:
+ *   face_hit (n_faces) uint8: 1 iff the face is in some pair; face_pairs (n_faces) int32: the pairs it is in, saturating at 2^31 - 1;
+ *   pairs (cap_pairs,2) int32: the first min(P, cap_pairs) pairs in ascending (f, g) order, nothing beyond them;
+ *   counts[8]: non-degenerate triangles, degenerate faces, candidate triangle pairs tested exactly (this one depends on the broad phase and
+ *   is no part of the contract), intersecting pairs P, faces hit, pairs with a k = 0 hit, pairs with a k >= 1 hit and no k = 0 hit, pairs
+ *   written.
+ * A short cap_pairs is no refusal: the list is truncated and counts[3] says what a second call needs. n_faces = 0: counts 0, nothing written.
+ * SN_ERR_ARG, nothing written but counts (zeros), in sn_mesh_smooth's words: a face index outside [0, n_verts) or a referenced coordinate
+ * outside the range (or not a number), the text naming the first offending face; nv not 3 or 4, n_verts or n_faces > 2^28; and cap_pairs < 0,
+ * a null cfg, more than 2^26 triangles, 2^30 or more intersecting triangle pairs. There is no repair, and the work is quadratic in the triangles
+ * that crowd one grid cell. Everything is an integer: the result equals the restatement tests/meshintersect_ref.py byte for byte (but
+ * counts[2]), on every run. The workspace belongs to the context (grown on demand); both forms return when the work is done. */
+typedef struct sn_mesh_intersect_cfg {
+    long long cap_pairs;       /* >= 0: rows of `pairs` */
+} sn_mesh_intersect_cfg;
+SN_API int sn_mesh_intersect(sn_ctx *ctx, const sn_mesh_intersect_cfg *cfg, int n_verts, const double *verts, int n_faces, int nv,
+                             const int32_t *faces, unsigned char *face_hit, int32_t *face_pairs, int32_t *pairs, long long *counts);
+SN_API int sn_mesh_intersect_dev(sn_ctx *ctx, const sn_mesh_intersect_cfg *cfg, int n_verts, const double *verts_dev, int n_faces, int nv,
+                                 const int32_t *faces_dev, unsigned char *face_hit_dev, int32_t *face_pairs_dev, int32_t *pairs_dev,
+                                 long long *counts);
 
 /* ---- the mesh back in its views: depth maps, face ids, visibility, colours --------------------------------------------
  * sn_mesh_render rasterises a mesh into V views of one size: verts (n_verts,3) float64 in WORLD coordinates (as sn_mesh_sample's), faces

@@ -726,6 +726,30 @@ class Context(object):
         # (no face: either form returns at once and writes nothing, so there is nothing to stage or to copy back)
         return self._host_or_device("sn_mesh_orient", device and F > 0, (v, f), run, spec, lambda name, sizes: F, (), words=12)
 
+    def mesh_intersect(self, verts, faces, cap_pairs=None, device=False):
+        """A mesh's self-intersections, exactly (sn_mesh_intersect): verts (V,3) float64 in lattice cells, faces (F,3)
+        or (F,4) int32, cap_pairs >= 0 the rows the pair list may hold - a shorter list is truncated, not refused; None: F rows first and, when
+        there are more pairs, one more call at exactly their number. Returns a dict: face_hit (F,) uint8, face_pairs (F,) int32, pairs
+        (min(P, cap_pairs),2) int32 in ascending (f, g) order, counts (8,) int64 = non-degenerate triangles, degenerate faces, candidate
+        triangle pairs tested exactly (depends on the broad phase), intersecting pairs P, faces hit, pairs with a k = 0 hit, pairs with a
+        k >= 1 hit only, pairs written. device=True stages the mesh in device memory here and runs sn_mesh_intersect_dev on it: the same
+        result."""
+        v, f = self._mesh_arrays(verts, faces)
+        V, (F, nv) = v.shape[0], f.shape
+        spec = (("face_hit", 1, np.uint8), ("face_pairs", 1, np.int32), ("pairs", 2, np.int32))
+
+        def call(cap):
+            cfg = _lib.MeshIntersectCfg(cap)
+            rows = lambda name, sizes: min(max(sizes[0], 0), max(cap, 0)) if name == "pairs" else F
+            run = lambda fn, _, ins, outs, counts: fn(self._h, ctypes.byref(cfg), V, ins[0], F, nv, ins[1], *outs, *counts)
+            # (no face: either form returns at once and writes nothing, so there is nothing to stage or to copy back)
+            return self._host_or_device("sn_mesh_intersect", device and F > 0, (v, f), run, spec, rows, (cap,), words=8, sized=(3,))
+
+        out = call(F if cap_pairs is None else int(cap_pairs))
+        if cap_pairs is None and int(out["counts"][3]) > F:
+            out = call(int(out["counts"][3]))
+        return out
+
     def _render_args(self, verts, faces, cameraPOs, shape, near, tol):
         """-> (verts, faces, P or None, V, cfg) of mesh_render and mesh_vertex_colors: cameraPOs (V,3,4), None = the cameras of set_cameras."""
         v, f = self._mesh_arrays(verts, faces)

@@ -228,6 +228,19 @@ static inline int mor_check_args(const sn_mesh_orient_cfg *cfg, int n_verts, int
     return SN_OK;
 }
 
+// (sn_mesh_intersect has no lattice; its one sized output is truncated, not refused. Its grid's table of 16 slots per triangle is scanned
+// with an int: at most 2^26 triangles)
+static inline int mxi_check_args(const sn_mesh_intersect_cfg *cfg, int n_verts, int n_faces, int nv)
+{
+    int rc;
+    if (!cfg) return fail(SN_ERR_ARG, "null cfg");
+    const double origin[3] = {0.0, 0.0, 0.0};
+    if ((rc = mesh_check_common(n_verts, n_faces, nv, origin, 1.0)) != SN_OK) return rc;
+    if (cfg->cap_pairs < 0) return fail(SN_ERR_ARG, "cap_pairs = %lld must be >= 0", cfg->cap_pairs);
+    if ((long long)n_faces * (nv - 2) > (1ll << 26)) return fail(SN_ERR_ARG, "%lld triangles: at most 2^26", (long long)n_faces * (nv - 2));
+    return SN_OK;
+}
+
 // (sn_mesh_render and sn_mesh_vertex_colors have no lattice: world coordinates, one image size, V views; have_P: the caller gave cameras, so
 // V is the caller's - without them V is the context's and is judged there)
 static inline int mrd_check_args(const sn_mesh_render_cfg *cfg, int n_verts, int n_faces, int nv, bool have_P, int V)

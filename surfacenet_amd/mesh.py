@@ -8,9 +8,11 @@
     fill_holes         the mesh with its small holes capped: boundary loops and centroid fans
     mesh_normals       the normals of a mesh from the mesh itself, area-weighted, with its exact area and volume
     orient_mesh        the faces of a mesh made to turn one way, its pieces with their exact volumes, small pieces removed
+    self_intersections the pairs of faces of a mesh that cross or touch each other, exactly
     render_mesh        the mesh back in its views: depth maps, face ids, the pixels of every face, the visible vertices
     colour_vertices    the colour of every vertex from the views that see it
-    chain_settings     the checked keywords of the stages that follow extract_mesh in a scene: fill, smooth, decimate, orient
+    chain_settings     the checked keywords of the stages that follow extract_mesh in a scene: fill, smooth, decimate, orient, check (DESIGN.md
+                       section 4.19)
     run_chain          those stages, each on the result of the one before it
     save_mesh_2ply     binary little-endian PLY of a quad or triangle mesh
     save_stage_2ply    the same of a stage's mesh, normals and colours gathered through its vert_src (stage_tag: the file's tag), or with
@@ -413,6 +415,47 @@ def orient_mesh(vert_lattice, faces, sign="majority", min_faces=0, keep_largest=
     return res
 
 
+INTERSECT_COUNTS = ("n_triangles", "n_degenerate_faces", "n_pairs", "n_faces_hit", "n_disjoint_pairs", "n_adjacent_pairs")
+_INTERSECT_WORDS = (0, 1, 3, 4, 5, 6)                         # their places in the library's counts (2: the broad phase's candidates, 7: written)
+
+
+def check_intersect_args(max_pairs=None):
+    """-> max_pairs of self_intersections (None: every pair), or ValueError."""
+    if max_pairs is None:
+        return None
+    try:
+        n = int(max_pairs)
+    except (TypeError, ValueError):
+        raise ValueError("max_pairs = %r must be an integer or None" % (max_pairs,))
+    if isinstance(max_pairs, (bool, np.bool_)) or n != max_pairs or not 0 <= n < 1 << 62:
+        raise ValueError("max_pairs = %r: an integer number of pairs >= 0, or None for all of them" % (max_pairs,))
+    return n
+
+
+def self_intersections(vert_lattice, faces, max_pairs=None):
+    """The pairs of faces of a mesh that have a point in common beyond what their shared vertices explain, exactly:
+    vert_lattice (V,3) float32 or float64 in lattice cells as any stage returns it, faces (F,3) triangles or (F,4) quads - a quad is its
+    triangles (a,b,c), (a,c,d), pairs name the quads. Positions are the stages' fixed point, q = rint(v * 65536), and every test is a sign
+    of an exact integer. Closed sets: two faces that only touch - a T-junction, a seam of coincident but distinct vertices, a duplicate -
+    intersect; two faces that share one or two vertex indices intersect only where they have more than those in common (a fold). A
+    degenerate triangle is skipped. -> dict: pairs (P',2) int32 the first max_pairs (None: all) pairs f < g in ascending order, face_hit (F,)
+    bool, face_pairs (F,) int32 the pairs a face is in, n_triangles, n_degenerate_faces, n_pairs, n_faces_hit, n_disjoint_pairs (a hit of
+    two triangles without a common index), n_adjacent_pairs (the others), truncated = n_pairs > len(pairs). There is no repair. ValueError
+    on bad shapes, dtypes, max_pairs, face indices or coordinates before the library is touched."""
+    v, f = _mesh_arrays(vert_lattice, faces)
+    cap = check_intersect_args(max_pairs)
+    _, _, V, F, _, _ = _mesh_args(v, f, (0.0, 0.0, 0.0), 1.0, None, "faces")
+    if V == 0 or F == 0:                                        # no face (V = 0 with faces was refused): nothing for the library to do
+        m = dict(pairs=np.zeros((0, 2), np.int32), face_hit=np.zeros((F,), np.uint8), face_pairs=np.zeros((F,), np.int32),
+                 counts=np.zeros((8,), np.int64))
+    else:
+        m = runtime.any_context().mesh_intersect(v.astype(np.float64), f.astype(np.int32), cap_pairs=cap)
+    res = dict(pairs=m["pairs"], face_hit=m["face_hit"].astype(bool), face_pairs=m["face_pairs"])
+    res.update({k: int(m["counts"][i]) for k, i in zip(INTERSECT_COUNTS, _INTERSECT_WORDS)})
+    res["truncated"] = res["n_pairs"] > res["pairs"].shape[0]
+    return res
+
+
 RENDER_COUNTS = ("n_triangles", "n_clipped", "n_degenerate", "n_rasterised", "n_pairs", "n_pixels", "n_visible")
 MAX_IMAGE_DIM = 16384
 
@@ -548,7 +591,8 @@ def colour_vertices(vertices, faces, cameraPOs, images, vert_visible=None, near=
 # argument, the keyword a bare value stands for (a number, or orient's sign word), the defaults (their keys are the allowed ones), what a
 # refusal says the argument is, the check of the keywords, the stage, the letter of its PLY file's tag, and what the stage keeps of the mesh
 # that goes in: None - nothing, its result is a new mesh with its own vert_src -, "faces" - it moves the vertices -, "vertices" - it
-# replaces the faces under the key they came in. mesh_cell is a number only: its second keyword is mesh_placement.
+# replaces the faces under the key they came in -, "mesh" - all of it: the stage reports on the mesh and the next one reads the same mesh; it
+# has no letter, so no file. mesh_cell is a number only: its second keyword is mesh_placement; mesh_check's bare value is True: the defaults.
 _Stage = collections.namedtuple("_Stage", "key arg first defaults words check run letter keeps")
 _CHAIN = (
     _Stage("filled", "mesh_fill", "max_len", dict(max_len=64, orientation="holes"), "a largest loop length or a dict of max_len, orientation",
@@ -558,24 +602,27 @@ _CHAIN = (
     _Stage("simplified", "mesh_cell", "cell", None, None, check_simplify_args, simplify_mesh, "c", None),
     _Stage("oriented", "mesh_orient", "sign", dict(sign="majority", min_faces=0, keep_largest=False),
            "a sign word or a dict of sign, min_faces, keep_largest", check_orient_args, orient_mesh, "o", "vertices"),
+    _Stage("checked", "mesh_check", "max_pairs", dict(max_pairs=None), "True or a dict of max_pairs", check_intersect_args, self_intersections,
+           None, "mesh"),
 )
 _STAGES = {row.key: row for row in _CHAIN}
 
 
 def _stage_keywords(row, value):
     """A stage's argument - a number (the row's first keyword) or a dict of keywords - as all of its keywords, or ValueError."""
-    kw = dict(value) if isinstance(value, dict) else {row.first: value}
-    if set(kw) - set(row.defaults):
+    kw = dict(value) if isinstance(value, dict) else ({} if row.keeps == "mesh" and value is True else {row.first: value})
+    if set(kw) - set(row.defaults) or (row.keeps == "mesh" and not isinstance(value, dict) and value is not True):
         raise ValueError("%s = %r: %s" % (row.arg, value, row.words))
     return dict(row.defaults, **kw)
 
 
-def chain_settings(mesh_fill=None, mesh_smooth=None, mesh_cell=None, mesh_placement="mean", mesh_orient=None):
-    """scene_postpass's mesh_fill, mesh_smooth, mesh_cell / mesh_placement and mesh_orient -> [(key, keywords), ...]: the stages asked for
-    (not None) in the chain's order - "filled", "smoothed", "simplified", "oriented" - each with the checked keywords of fill_holes,
-    smooth_mesh, simplify_mesh, orient_mesh. ValueError for the first bad argument in the order mesh_orient, mesh_cell, mesh_smooth,
-    mesh_fill; the library is not touched."""
-    given = dict(mesh_fill=mesh_fill, mesh_smooth=mesh_smooth, mesh_cell=mesh_cell, mesh_orient=mesh_orient)
+def chain_settings(mesh_fill=None, mesh_smooth=None, mesh_cell=None, mesh_placement="mean", mesh_orient=None, mesh_check=None):
+    """scene_postpass's mesh_fill, mesh_smooth, mesh_cell / mesh_placement, mesh_orient and mesh_check -> [(key, keywords), ...]: the stages
+    asked for (not None; mesh_check=False asks for nothing either) in the chain's order - "filled", "smoothed", "simplified", "oriented",
+    "checked" - each with the checked keywords of fill_holes, smooth_mesh, simplify_mesh, orient_mesh, self_intersections. ValueError for
+    the first bad argument in the order mesh_check, mesh_orient, mesh_cell, mesh_smooth, mesh_fill; the library is not touched."""
+    given = dict(mesh_fill=mesh_fill, mesh_smooth=mesh_smooth, mesh_cell=mesh_cell, mesh_orient=mesh_orient,
+                 mesh_check=None if mesh_check is False else mesh_check)
     stages = []
     for row in reversed(_CHAIN):
         value = given[row.arg]
@@ -588,7 +635,9 @@ def chain_settings(mesh_fill=None, mesh_smooth=None, mesh_cell=None, mesh_placem
 
 def stage_tag(key, kw):
     """The tag of a chain stage's PLY file, <prefix><name>_mesh<tag>.ply: "_f<max_len>", "_s<iterations>", "_c<cell>", and "_o" - the letter
-    alone where the stage's first keyword is a word."""
+    alone where the stage's first keyword is a word; None for a stage that writes no file (the check)."""
+    if _STAGES[key].letter is None:
+        return None
     first = kw[_STAGES[key].first]
     return "_" + _STAGES[key].letter + ("" if isinstance(first, str) else "%d" % int(first))
 
@@ -603,11 +652,14 @@ def run_chain(m, stages, origin, resol):
     decimate, orient; origin / resol as lattice_origin returns them. -> {key: the stage's result}: fill_holes' and simplify_mesh's dicts as
     they are, both with vert_src; "smoothed" the mesh that went in - m, or vertices, vert_lattice, faces, vert_src of the filled one - with
     smooth_mesh's positions and statistics, so it holds quads without a fill and faces after one; "oriented" the mesh that went in with
-    orient_mesh's kept, oriented faces under the key its faces came in (quads or faces) and the rest of orient_mesh's dict beside them."""
+    orient_mesh's kept, oriented faces under the key its faces came in (quads or faces) and the rest of orient_mesh's dict beside them;
+    "checked" self_intersections' report on the mesh that went in, which goes on as it is."""
     res = {}
     for key, kw in stages:
         run, keeps = _STAGES[key].run, _STAGES[key].keeps
-        if keeps == "faces":                                    # indices stay: the mesh's other keys carry over
+        if keeps == "mesh":                                     # a report: the mesh goes on as it is
+            res[key] = run(m["vert_lattice"], _faces(m), **kw)
+        elif keeps == "faces":                                    # indices stay: the mesh's other keys carry over
             m = res[key] = dict(m, **run(m["vert_lattice"], _faces(m), origin=origin, resol=resol, **kw))
         elif keeps == "vertices":                               # vertices stay: the new faces take the place of the old
             r = run(m["vert_lattice"], _faces(m), resol=resol, **kw)

@@ -566,7 +566,7 @@ def reconstruct_scene(images_list, cameraPOs_np, cubes_param_np, cube_D_mm, cube
 def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, gamma=0.8, beta=6, N_refine_iter=8, init_probThresh=0.5,
                    max_probThresh=0.9, keep_iterations=False, cameraTs_np=None, cube_overlapping_ratio=0.5, unique=False, mesh=False, mesh_radius=2,
                    mesh_reach=0, mesh_ply_prefix=None, min_component=None, component_connectivity=26, mesh_cell=None, mesh_placement="mean",
-                   mesh_smooth=None, mesh_fill=None, mesh_normals="source", mesh_orient=None, mesh_render=None):
+                   mesh_smooth=None, mesh_fill=None, mesh_normals="source", mesh_orient=None, mesh_render=None, mesh_check=None):
     """The reconstruction's last two stages on `reconstruct_scene`'s dict, in memory and on the GPU, as the reference runs them on its files:
       * main_reconstruct.py:172-175  thinning masks (prob >= tau, votes >= gamma * N_vp * 2), then denoise_crossCubes with D_cube = cube_D
       * main.py:37-43 -> utils/adapthresh.py  adaptive thresholding with D_cube = cube_Dcenter, init / max threshold init_probThresh /
@@ -614,7 +614,11 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
         default None adds no key and writes no file): fixThresh_mesh_render, adapt_mesh_render - mesh.render_mesh of the LAST mesh of the chain
         (the mesh of mesh=True without a chain) in world mm: depth, face, face_pixels, vert_visible, views and the counts; tol=None is half
         the lattice's resol. With images (one (H,W,3) uint8 per camera) also vert_rgb and vert_views of mesh.colour_vertices with that
-        visibility, and with mesh_ply_prefix too <prefix>fixThresh_mesh_v.ply / <prefix>adapt_mesh_v.ply: the last mesh with those colours."""
+        visibility, and with mesh_ply_prefix too <prefix>fixThresh_mesh_v.ply / <prefix>adapt_mesh_v.ply: the last mesh with those colours.
+      mesh_check=True or dict(max_pairs=) (needs mesh=True; the default None adds no key and changes no byte):
+        fixThresh_mesh_checked, adapt_mesh_checked - mesh.self_intersections' report on the LAST mesh of the chain (the mesh of mesh=True
+        without a chain): pairs, face_hit, face_pairs, the counts and truncated. n_pairs = 0 says that no two faces of it cross or touch.
+        The mesh itself goes on unchanged, and no file is written."""
     from . import adapthresh, denoising, sparseCubes
     from . import mesh as _mesh
     from . import normals as _normals
@@ -623,10 +627,12 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
         raise ValueError("mesh=True needs cameraTs_np: the mesher reads the oriented normals")
     for arg, value, does in (("mesh_cell", mesh_cell, "simplifies"), ("mesh_smooth", mesh_smooth, "smooths"), ("mesh_fill", mesh_fill, "fills the holes of"),
                              ("mesh_normals", None if mesh_normals == "source" else mesh_normals, "takes its normals from"),
-                             ("mesh_orient", mesh_orient, "orients"), ("mesh_render", mesh_render, "renders")):
+                             ("mesh_orient", mesh_orient, "orients"), ("mesh_render", mesh_render, "renders"),
+                             ("mesh_check", None if mesh_check is False else mesh_check, "checks")):
         if value is not None and not mesh:
             raise ValueError("%s needs mesh=True: it %s the mesh that mesh=True extracts" % (arg, does))
-    stages = _mesh.chain_settings(mesh_fill, mesh_smooth, mesh_cell, mesh_placement, mesh_orient)      # fill, smooth, decimate, orient: those asked for
+    stages = _mesh.chain_settings(mesh_fill, mesh_smooth, mesh_cell, mesh_placement, mesh_orient, mesh_check)      # fill, smooth, decimate, orient, check: those asked for
+    meshes = [key for key, _ in stages if _mesh.stage_tag(key, dict(stages)[key]) is not None]      # the stages whose result is a mesh
     _mesh.check_normals_arg(mesh_normals, "mesh_normals")
     render = None if mesh_render is None else _mesh.check_render_setting(mesh_render)
     ply_tags = dict([("", "")] + [("_" + key, _mesh.stage_tag(key, kw)) for key, kw in stages])      # result key's ending -> file name's
@@ -680,6 +686,9 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
                 lattice = _mesh.lattice_origin(cube_ijk, out["param_np"], stride_vox)
             chain = _mesh.run_chain(m, stages, *(lattice or ((0.0, 0.0, 0.0), 1.0)))
             for end, stage_mesh in [("", m)] + [("_" + key, chain[key]) for key in chain]:
+                if end and end[1:] not in meshes:               # a report on a mesh, not a mesh: no normals, no file
+                    res[name + "_mesh" + end] = stage_mesh
+                    continue
                 if mesh_normals == "mesh":                      # (a copy: a later stage's dict may share this one's arrays, not its keys)
                     own = _mesh.mesh_normals(stage_mesh["vert_lattice"], _mesh._faces(stage_mesh), resol=lattice[1] if lattice else 1.0)
                     stage_mesh = dict(stage_mesh, vert_normals=own["vert_normals"], area=own["area"], volume=own["volume"])
@@ -688,7 +697,7 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
                     _mesh.save_stage_2ply("%s%s_mesh%s.ply" % (mesh_ply_prefix, name, ply_tags[end]), stage_mesh, normal_l, out.get("rgb_list"),
                                           normals=mesh_normals)
             if render is not None:                              # the last mesh of the chain, back in its views
-                last = chain[stages[-1][0]] if stages else m
+                last = chain[meshes[-1]] if meshes else m
                 tol = render["tol"] if render["tol"] is not None else (0.5 * lattice[1] if lattice else 0.0)
                 r = _mesh.render_mesh(last["vertices"], _mesh._faces(last), render["cameraPOs"], render["shape"], render["near"], tol, render["views"])
                 if render["images"] is not None:
