@@ -5,7 +5,9 @@
 //   LtPairs   two words {key + 1, value}; key + 1 != 0, so an all-zero table is empty and the value words start as 0 as well
 // Every probe ends at a free slot: a table holds at least twice the keys that can be inserted (table_cap in sn_host.h; ray pooling's LDS
 // tables are at most 5/6 full), and (h + 1) & mask walks from the last slot on to slot 0. tests/test_gpu_hash_adversary.py holds that wrap-around
-// and the claim races along one long run, with keys built to start every walk in a table's last sixteen slots (tests/hash_adversary.py).
+// and the claim races along one long run, with keys built to start every walk in a table's last sixteen slots (tests/hash_adversary.py); the
+// LDS tables are held at 83 % full (3,400 keys in 4,096 slots) through the address_space(3) instantiations, the COHERENT probe at the 42 %
+// that is the most it can meet there (it runs only when every voxel of a cube is selected).
 // The helpers are templates over the pointer type so that each instantiation addresses ONE address space: with generic pointers to an LDS table
 // every access becomes a flat instruction behind a full s_waitcnt (postpass.h instantiates them with address_space(3) pointers).
 #pragma once

@@ -11,6 +11,9 @@ at least twice its keys, every walk ends at a free slot.
     probe_model                 sequential linear probing: slot, walk length, wrap per key; the keys a planted fault loses
     table_cap                   sn_host.h's capacity rule (only to know which capacity a case WILL meet; the key sets do not depend on it)
     *_case                      one builder per key form: the stage's ordinary arguments plus the key multiset each of its tables receives
+    late_at, TARGETED           key forms with too few candidates for that (ray pooling's pixels and cells, the mesher's bricks) are late at the ONE
+                                capacity their stage's sizing rule - restated here, pinned to the headers by the CPU test - gives them; the
+                                self-intersection grid's cells are late everywhere and stand with them
 
 A case is a dict: `tables` maps a table's name to dict(keys (uint64, in insertion order: what the model hashes), cap); everything else is the
 stage's input. Do not modify a case: they are cached and shared."""
@@ -69,6 +72,14 @@ def late_keys(candidates, w=W, top=TOP):
     return c[late_mask(c, w, top)]
 
 
+def late_at(candidates, cap, w=W):
+    """The candidates that start their walk in the last 2^w slots of a table of `cap` slots (bits [w, log2 cap) of the hash all set): late at
+    THAT capacity, whatever they do at another. A key form with too few candidates for late_keys has enough of these."""
+    assert cap & (cap - 1) == 0 and cap > 1 << w
+    c = np.asarray(candidates).astype(U64)
+    return c[late_mask(c, w, cap.bit_length() - 1)]
+
+
 def table_cap(n, factor, min_cap):
     """sn_host.h: the smallest power of two >= factor * n, at least min_cap."""
     cap = int(min_cap)
@@ -77,17 +88,41 @@ def table_cap(n, factor, min_cap):
     return cap
 
 
+# The sizing rules of the stages whose cases are late at ONE capacity, restated once (tests/test_hash_adversary_cpu.py reads the constants out of
+# postpass.h and meshintersect.h and holds every such case to the rule: a targeted case is adversarial only while the rule here is the kernel's).
+RP_LIST, RP_LDS_M, RP_LDS_CAP, MXI_BIG = 8192, 3400, 4096, 64
+LDS_FILL = (5, 6)                                               # RP_LDS_M selected voxels in RP_LDS_CAP slots: 83 %, at most 5/6
+
+
+def ray_pool_rule(m):
+    """ray_pool_kernel's tables for m selected voxels of a (cube, view) -> dict(cap, lds, listed): the smallest power of two >= 2 m, at least
+    64; m <= RP_LDS_M caps it at RP_LDS_CAP and puts the tables into LDS; the voxels are listed iff m <= RP_LIST."""
+    cap = table_cap(m, 2, 64)
+    lds = m <= RP_LDS_M
+    return dict(cap=min(cap, RP_LDS_CAP) if lds else cap, lds=lds, listed=m <= RP_LIST)
+
+
+def brick_cap(total):
+    """The mesher's brick table has the cell table's own mask: table_cap(total, 2, 64) for `total` packed voxels."""
+    return table_cap(total, 2, 64)
+
+
+def intersect_cap(n_tris, budget=8):
+    """The intersection grid's cell table: twice the entries a level may have, max(budget, 8) per triangle, at least 1,024 slots."""
+    return table_cap(max(budget, 8) * int(n_tris), 2, 1024)
+
+
 # ---- the reference model ----------------------------------------------------------------------------------------------------------------------------
-def probe_model(keys, cap, fault=None):
+def probe_model(keys, cap, fault=None, fill=(1, 2)):
     """Sequential linear probing of `keys` (in order; a repeated key finds its slot) into `cap` slots from mix64(key) & (cap - 1).
     -> dict(slot, walk, wrapped: per DISTINCT key in order of first appearance (slot -1: lost); keys: those distinct keys; lost: the keys the
     fault loses; taken: occupied slots). fault: "no_wrap" the walk ends at slot `mask`; "limit" the walk gives up after 64 steps; "lost_race" a key
-    that finds its first slot taken by another key is dropped."""
+    that finds its first slot taken by another key is dropped. fill: the fullest the table may be, (1, 2) half; ray pooling's LDS tables: LDS_FILL."""
     assert cap & (cap - 1) == 0 and fault in (None,) + FAULTS
     keys = np.asarray(keys).astype(U64)
     _, first = np.unique(keys, return_index=True)
     distinct = keys[np.sort(first)]
-    assert fault is not None or 2 * distinct.size <= cap, "a table holds at least twice its keys"
+    assert fault is not None or fill[1] * distinct.size <= fill[0] * cap, "a table holds at least twice its keys (LDS tables: 6/5 of them)"
     start = (mix64(distinct) & U64(cap - 1)).astype(np.int64).tolist()
     nxt = list(range(cap + 1))                               # nxt[s]: the first free slot >= s (cap: none), with path compression
 
@@ -567,6 +602,255 @@ def ptcubes_case(dtype="float64"):
     return _freeze(dict(name="ptcubes_" + dtype, pts=pts, cells=q, n_late=len(late_cells()), tables=dict(set=_table(keys, len(pts), 4, 2048))))
 
 
+# ---- the mesher's brick table: late at the capacity the stage gives it -----------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def bricks_mesh_case(total=512, bias=4):
+    """cells512b's shape for the mesher's brick table (mesh.h: key of (g + 4) >> 2): `total` masked voxels with normals in `total` distinct
+    cells of one cube, so the cell table and the brick table get 2 * total slots. Three quarters of them sit one per brick, at local cell
+    (1, 2, 3) - (k % 2, 0, 0), in the bricks of [1, 33)^3 whose key is late AT THAT CAPACITY (the block has 32,768 bricks: a few hundred of those, a
+    handful late at every capacity), in arrange()'s order; the rest are the sheet, whose bricks are not late."""
+    cap = brick_cap(total)
+    a = np.arange(1, 1 + BLOCK // 4, dtype=np.int64)
+    b = np.stack(np.meshgrid(a, a, a, indexing="ij"), -1).reshape(-1, 3)
+    bkeys = keys_of_cells(b)
+    b = b[np.isin(bkeys, late_at(bkeys, cap))]
+    b = b[arrange(keys_of_cells(b), 3 * total // 4)]
+    assert len(b) == 3 * total // 4
+    late = 4 * b + np.asarray([1, 2, 3]) - (np.arange(len(b)) % 2)[:, None] * np.asarray([1, 0, 0]) - bias      # world cells
+    sheet = np.asarray([(x, y, 65) for x in range(60, 100) for y in range(60, 76)], np.int64)
+    sheet = sheet[~late_mask(keys_of_cells((sheet + bias) >> 2), W, cap.bit_length() - 1)][:total - len(late)]
+    cells = np.concatenate([late, sheet])
+    assert len(cells) == total and np.unique(cells, axis=0).shape[0] == total and cells.min() >= 0 and cells.max() < BLOCK
+    s = nref.hand_scene([[0, 0, 0]], [cells.astype(np.uint8)], stride_vox=STRIDE)
+    s["mask"], s["normals"], s["cameraTs"] = np.ones(total, bool), np.tile(np.asarray([0, 0, 1], np.float32), (total, 1)), nref.cameras_above(4) + CAMERA_SHIFT
+    g = nref.world_cells(s["offsets"], s["ijk"], s["cube_ijk"], STRIDE) + bias
+    s.update(name="bricks_mesh", bias=bias, n_late=len(late), rule_n=total,
+             tables=dict(brick=_table(keys_of_cells(g >> 2), total, 2, 64), cell=_table(keys_of_cells(g), total, 2, 64)))
+    return _freeze(s)
+
+
+def without_bricks(s, lost):
+    """The scene with every voxel whose (biased) brick key is in `lost` unmasked: what a brick table that lost those keys holds."""
+    g = nref.world_cells(s["offsets"], s["ijk"], s["cube_ijk"], s["stride_vox"]) + s["bias"]
+    return dict(s, mask=np.asarray(s["mask"]) & ~np.isin(keys_of_cells(g >> 2), lost))
+
+
+# ---- the self-intersection grid ----------------------------------------------------------------------------------------------------------------------------
+MXI_OFFSET = 4                                                  # meshintersect_rules.h: grid cell at level 0 = floor(v) + 4
+# a grid cell's contents, in sixteenths of the cell from its min corner: (corners, faces)
+_MXI_A = [(3, 3, 4), (13, 3, 4), (8, 13, 12)]                   # a tilted triangle
+_MXI_CONTENTS = (
+    (_MXI_A + [(8, 6, 3), (8, 6, 13), (8, 10, 8)], [(0, 1, 2), (3, 4, 5)]),                  # a second one through it: a hit
+    (_MXI_A + [(4, 11, 5), (5, 12, 5), (4, 12, 6)], [(0, 1, 2), (3, 4, 5)]),                 # a small one in a corner of its box: a candidate only
+    (_MXI_A, [(0, 1, 2)]),                                                                  # alone
+    ([(4, 4, 8), (12, 4, 8), (8, 12, 8), (8, 2, 12)], [(0, 1, 2), (1, 0, 3)]),               # two that share an edge and fold away: adjacent, no hit
+)
+
+
+def _mxi_big():
+    """More than MXI_BIG triangles for one cell: 64 level ones at 64 heights, not one box overlapping another, and three upright ones through most
+    of them."""
+    v = []
+    for i in range(MXI_BIG):
+        z = (20 + 3 * i) / 16.0                                 # heights 20/256 .. 209/256 of the cell
+        v += [(3, 3, z), (13, 3, z), (8, 13, z)]
+    for x in (7, 8, 9):
+        v += [(x, 6, 1.5), (x, 6, 14.5), (x, 10, 8)]
+    return np.asarray(v, np.float64), [(3 * t, 3 * t + 1, 3 * t + 2) for t in range(MXI_BIG + 3)]
+
+
+@functools.lru_cache(maxsize=None)
+def intersect_case(scale=1):
+    """Small triangles strictly inside the late grid cells of level 0 (arranged_cells(): late at every capacity; the grid of under 1,024
+    triangles has 16,384 slots). mxi_tris_kernel boxes floor(v) + 4, so cell c holds the points of [c - 4, c - 3)^3. The cells take the four
+    contents of _MXI_CONTENTS in turn, several triangles of one cell racing for one key; the LAST cell of the order - the longest walk - holds
+    _mxi_big()'s 67 triangles, a cell for the big-cell list. scale 8: the same mesh with (v + 4) scaled by 8, which presents the same keys at
+    level 3."""
+    cells = arranged_cells()
+    verts, faces, tri_cell = [], [], []
+    for n, c in enumerate(cells.tolist()):
+        if n == len(cells) - 1:
+            local, f = _mxi_big()
+            local = local / 16.0
+        else:
+            p, f = _MXI_CONTENTS[n % len(_MXI_CONTENTS)]
+            local = np.asarray(p, np.float64) / 16.0
+        base = sum(len(v) for v in verts)
+        verts.append(local + np.asarray(c, np.float64) - MXI_OFFSET)
+        faces += [[base + i for i in t] for t in f]
+        tri_cell += [c] * len(f)
+    v = np.concatenate(verts)
+    if scale != 1:
+        v = (v + MXI_OFFSET) * float(scale) - MXI_OFFSET
+    f = np.asarray(faces, np.int32)
+    tri_cell = np.asarray(tri_cell, np.int64)
+    return _freeze(dict(name="intersect" if scale == 1 else "intersect_x%d" % scale, verts=v, faces=f, tri_cell=tri_cell, cells=cells, n_late=len(cells),
+                        scale=scale, level=int(scale).bit_length() - 1, rule_n=len(f),
+                        tables=dict(grid=dict(keys=_ro(keys_of_cells(tri_cell)), cap=intersect_cap(len(f))))))
+
+
+def without_grid_cells(c, lost):
+    """The faces of an intersect case whose grid cell's key is not in `lost`."""
+    return np.asarray(c["faces"])[~np.isin(keys_of_cells(c["tri_cell"]), lost)]
+
+
+# ---- ray pooling's pixel and cell tables ---------------------------------------------------------------------------------------------------------------------
+RP_THRESH = 0.5
+RP_PAIRS = np.asarray([[[0, 1], [0, 2]]], np.int64)             # view 0, the adversarial one, twice (the multiplicity path); views 1 and 2 once
+# views 1 and 2: every entry a small integer, so their projections are exact too; view 2 is a perspective one with 4 + i depth bins
+_RP_SIDE = [[[1, 0, 0, -3], [0, 1, 0, 0], [0, 0, 0, 1]], [[0, 64, 0, 0], [0, 0, 64, 0], [1, 0, 0, 4]]]
+
+
+def pixel_key(w, h):
+    """postpass.h's pixel key: (w, h) as two int32 with the sign bits flipped - (-1, -1) would otherwise be the empty sentinel."""
+    w, h = ((np.asarray(a, np.int64) & 0xffffffff).astype(U64) ^ U64(0x80000000) for a in (w, h))
+    return (w << U64(32)) | h
+
+
+def rp_cell_key(slot, d):
+    """postpass.h's cell key: the pixel's slot and the depth bin as int32 bits."""
+    return (np.asarray(slot).astype(U64) << U64(32)) | (np.asarray(d, np.int64) & 0xffffffff).astype(U64)
+
+
+def _ro(a):
+    a = np.ascontiguousarray(a)
+    a.setflags(write=False)
+    return a
+
+
+def _project(cam, D):
+    """(w, h, d) of every voxel of a D^3 cube at xyz 0, resol 1 under `cam`, in float64 as the kernel and post_oracle compute them (the entries
+    are integers below 2^53 and so is every product and sum: the FMA chain is exact, the divisions round once)."""
+    i, j, k = (x.reshape(-1).astype(np.float64) for x in np.indices((D, D, D)))
+    q = [cam[r][0] * i + cam[r][1] * j + cam[r][2] * k + cam[r][3] for r in range(3)]
+    return [np.rint(x).astype(np.int64) for x in (q[0] / q[2], q[1] / q[2], q[2] / 1.0)]
+
+
+def _rp_case(name, table, D, cam0, sel, voxel_keys, pred16, cap, n_late, **more):
+    m = len(sel)
+    pred = np.full(D ** 3, 0.125, np.float32)
+    pred[sel] = pred16.astype(np.float32) / 2048.0              # multiples of 2^-11 in [0.5, 1): exact in fp16
+    assert int((pred.astype(np.float16) > np.float16(RP_THRESH)).sum()) == m and np.array_equal(pred.astype(np.float16).astype(np.float32), pred)
+    rule = ray_pool_rule(m)
+    assert rule["cap"] == cap
+    cams = np.asarray([cam0] + _RP_SIDE, np.float64)
+    return _freeze(dict(name=name, D=D, cameras=cams, pairs=RP_PAIRS.copy(), xyz=np.zeros((1, 3), np.float32), resol=np.ones(1, np.float32),
+                        pred=pred.reshape(1, D, D, D), thresh=RP_THRESH, view=0, selected=sel, voxel_keys=voxel_keys, rule=rule, rule_n=m, n_late=n_late,
+                        fill=LDS_FILL if rule["lds"] else (1, 2), tables={table: dict(keys=_ro(voxel_keys.copy()), cap=cap)}, **more))
+
+
+@functools.lru_cache(maxsize=None)
+def rp_pixels_case(m, D=32):
+    """Ray pooling's PIXEL table under view 0, an affine camera (third row 0 0 0 1): voxel `flat` of a D^3 cube at xyz 0, resol 1 lands on pixel
+    w = flat - 1000, h = -1 - 7 (i - i0) + 3 (j - j0) - 11 (k - k0), (i0, j0, k0) the voxel of flat index 999: pairwise distinct pixels, one
+    cell each (d = 1), most of them negative or far outside any image, and voxel 999 on (-1, -1), the pixel whose plain key is the empty
+    sentinel. Selected: that voxel, the voxels whose pixel key is late at the capacity ray_pool_rule(m) gives (at most 3 m / 4 of them, the
+    first in flat order) and seeded others up to m. Keys in flat order (the kernel's own order is whatever the atomics give)."""
+    cap = ray_pool_rule(m)["cap"]
+    flat = np.arange(D ** 3, dtype=np.int64)
+    i, j, k = np.unravel_index(flat, (D, D, D))
+    i0, j0, k0 = np.unravel_index(999, (D, D, D))
+    cam0 = [[D * D, D, 1, -1000], [-7, 3, -11, -1 + 7 * i0 - 3 * j0 + 11 * k0], [0, 0, 0, 1]]
+    w, h, d = _project(cam0, D)
+    assert np.array_equal(w, flat - 1000) and np.array_equal(h, -1 - 7 * (i - i0) + 3 * (j - j0) - 11 * (k - k0)) and (d == 1).all()
+    assert (w[999], h[999]) == (-1, -1)
+    keys = pixel_key(w, h)
+    late = late_mask(keys, W, cap.bit_length() - 1)
+    late[999] = False
+    rs = np.random.RandomState(m)
+    late_idx = np.nonzero(late)[0][:3 * m // 4]
+    rest = np.nonzero(~late)[0]
+    rest = rest[rest != 999]
+    sel = np.sort(np.concatenate([late_idx, [999], rs.choice(rest, m - 1 - len(late_idx), replace=False)]))
+    return _rp_case("pixels%d" % m, "pixel", D, cam0, sel, keys[sel], 1229 + rs.randint(0, 600, m), cap, len(late_idx))
+
+
+@functools.lru_cache(maxsize=None)
+def rp_cells_case(m, D=32, w=W):
+    """Ray pooling's CELL table under view 0: depth bin d = 2^20 + D j + k (third row 0 D 1 2^20), h = H (second row H times the third) and
+    w = rint(G 2^20 (i - D / 2) / d) = G (i - D / 2), off by less than G / 64 before the rint: D pixels, one per i, half of them at negative w,
+    D^2 cells each. The cell key is (pixel slot << 32) | d; (G, H) is the first pair for which the D pixels' home slots are pairwise distinct,
+    so every pixel gets its home slot whoever inserts first. Selected: the voxels whose cell key starts in the last 2^w slots of the capacity
+    ray_pool_rule(m) gives, and seeded others up to m. The late cells carry the largest predictions of their pixels, larger the further the
+    model walks them (a pixel's winner is the key a fault loses first); the two best late cells of the pixel with the most of them carry the
+    SAME prediction: the tie goes to the smaller d."""
+    cap = ray_pool_rule(m)["cap"]
+    S = 1 << 20
+    assert D == 32
+    for G, H in ((g, h) for g in range(1, 32) for h in range(-9, 10)):
+        pw = G * (np.arange(D, dtype=np.int64) - D // 2)
+        home = (mix64(pixel_key(pw, np.full(D, H))) & U64(cap - 1)).astype(np.int64)
+        if np.unique(home).size == D:
+            break
+    cam0 = [[G * S, 0, 0, -G * S * (D // 2)], [0, H * D, H, H * S], [0, D, 1, S]]
+    pix_w, pix_h, d = _project(cam0, D)
+    flat = np.arange(D ** 3, dtype=np.int64)
+    i, j, k = np.unravel_index(flat, (D, D, D))
+    assert np.array_equal(pix_w, pw[i]) and (pix_h == H).all() and np.array_equal(d, S + D * j + k)
+    keys = rp_cell_key(home[i], d)
+    late = late_mask(keys, w, cap.bit_length() - 1)
+    rs = np.random.RandomState(m + 1)
+    late_idx = np.nonzero(late)[0]
+    sel = np.sort(np.concatenate([late_idx, rs.choice(np.nonzero(~late)[0], m - len(late_idx), replace=False)]))
+    is_late = late[sel]
+    model = probe_model(keys[sel], cap, fill=LDS_FILL if m <= RP_LDS_M else (1, 2))
+    pred16 = 1229 + rs.randint(0, 400, m)
+    order = np.argsort(model["walk"][is_late], kind="stable")
+    rank = np.empty(len(order), np.int64)
+    rank[order] = np.arange(len(order))
+    pred16[is_late] = 1847 + rank * 190 // len(order)
+    per_pixel = np.bincount(i[sel][is_late], minlength=D)
+    tied = np.nonzero(is_late & (i[sel] == int(np.argmax(per_pixel))))[0]
+    tied = tied[np.argsort(pred16[tied], kind="stable")[-2:]]
+    pred16[tied] = 2047
+    return _rp_case("rp_cells%d" % m, "cell", D, cam0, sel, keys[sel], pred16, cap, len(late_idx), pixel_slots=home, tied=sel[tied], w=w)
+
+
+@functools.lru_cache(maxsize=None)
+def rp_zeros_case(D=12, G=2, H=-3, S=1049629):
+    """The one way to lt_find<LtKeys, true> on the LDS tables: a voxel whose stored prediction is 0 asks for its pixel's cell at the view's
+    minimum depth bin, and a 0 is selected only without a threshold, when EVERY voxel is: D^3 <= RP_LDS_M and D a multiple of 4 means D = 12 at
+    the most, 1,728 keys in the 4,096 slots. rp_cells_case's view 0 (a pixel per i, bin d = S + D j + k, so every pixel has its cell at the
+    minimum bin S, voxel (i, 0, 0)). (G, H, S) were searched for (H in -3 .. 3, G in 1 .. 31, S from 2^20 up: the first with distinct pixel home
+    slots, 19 cell keys that start in the table's last sixteen slots, and a minimum-bin key of a pixel i >= 1 among them); the CPU test holds
+    what they were searched for. The slices of those pixels and two more hold zeros only, so each of their 143 other voxels looks that key up
+    (found: no vote; missed: a vote for voxel 0, which nothing else in view 0 elects - slice 0 is not all zero and voxel 0 holds a 0). The
+    other slices hold eighths, a zero among them now and then."""
+    m = D ** 3
+    rule = ray_pool_rule(m)
+    cap, half = rule["cap"], D // 2
+    assert rule["lds"] and D % 4 == 0 and (D + 4) ** 3 > RP_LDS_M      # the largest cube edge the library takes whose every voxel fits the LDS tables
+    pw = G * (np.arange(D, dtype=np.int64) - half)
+    home = (mix64(pixel_key(pw, np.full(D, H))) & U64(cap - 1)).astype(np.int64)
+    late = late_mask(rp_cell_key(home, S), W, cap.bit_length() - 1)
+    late[0] = False
+    cam0 = [[G * S, 0, 0, -G * S * half], [0, H * D, H, H * S], [0, D, 1, S]]
+    pix_w, pix_h, d = _project(cam0, D)
+    i, j, k = np.unravel_index(np.arange(m), (D, D, D))
+    assert np.array_equal(pix_w, pw[i]) and (pix_h == H).all() and np.array_equal(d, S + D * j + k)
+    zero = late.copy()
+    zero[[n for n in range(1, D) if not late[n]][:2]] = True
+    rs = np.random.RandomState(D)
+    pred = (rs.randint(0, 8, m) / 8.0).astype(np.float32)
+    pred[zero[i]] = 0
+    pred[0] = 0
+    pred[1] = 0.5                                                # slice 0 is not all zero, whatever the seed
+    keys = rp_cell_key(home[i], d)
+    cams = np.asarray([cam0] + _RP_SIDE, np.float64)
+    return _freeze(dict(name="zeros_lds", D=D, cameras=cams, pairs=RP_PAIRS.copy(), xyz=np.zeros((1, 3), np.float32), resol=np.ones(1, np.float32),
+                        pred=pred.reshape(1, D, D, D), thresh=None, view=0, selected=np.arange(m), voxel_keys=keys, rule=rule, rule_n=m,
+                        n_late=int(late_mask(keys, W, cap.bit_length() - 1).sum()), fill=(1, 2), pixel_slots=home, zero_pixels=np.nonzero(zero)[0],
+                        late_pixels=np.nonzero(late)[0], dmin=S, tables=dict(cell=dict(keys=_ro(keys.copy()), cap=cap))))
+
+
+def without_voxels(c, lost):
+    """A ray-pooling case's predictions with every selected voxel whose key is in `lost` below the threshold: what a table that lost those
+    keys has pooled."""
+    pred = np.array(c["pred"]).reshape(-1)
+    pred[c["selected"][np.isin(c["voxel_keys"], lost)]] = 0.125
+    return pred.reshape(c["pred"].shape)
+
+
 # ---- every case, by the name the tests print ------------------------------------------------------------------------------------------------------------------
 BUILDERS = {
     "cells32": lambda: cells_case(32), "cells512": lambda: cells_case(512), "cells1500": lambda: cells_case(1500),
@@ -580,6 +864,42 @@ ADVERSARIAL = {"cells32": "cell", "cells512": "cell", "cells1500": "cell", "cell
                "bricks": "brick", "cubemap": "map", "edges3": "edge", "edges4": "edge", "simplify": ("vertex", "face"), "reduce1": "grid",
                "reduce3": "grid", "nn": "query", "gt": "grid", "ptcubes_f64": "set", "ptcubes_f32": "set"}
 HALF_FULL = ("cells32", "cells512", "cells32b", "cells512b")
+
+
+# The cases whose keys are late at the ONE capacity their stage's sizing rule gives them (late_at): (builder, its adversarial table). They are
+# no part of BUILDERS, whose cases are held at every capacity.
+TARGETED = {
+    "pixels_lds32": (lambda: rp_pixels_case(32), "pixel"), "pixels_lds2048": (lambda: rp_pixels_case(2048), "pixel"),
+    "pixels_lds3400": (lambda: rp_pixels_case(RP_LDS_M), "pixel"), "pixels_global": (lambda: rp_pixels_case(4096), "pixel"),
+    "pixels_unlisted": (lambda: rp_pixels_case(RP_LIST + 1, 64), "pixel"),
+    "cells_lds2048": (lambda: rp_cells_case(2048), "cell"), "cells_lds3400": (lambda: rp_cells_case(RP_LDS_M), "cell"),
+    "cells_global": (lambda: rp_cells_case(4096), "cell"),
+    "bricks_mesh": (bricks_mesh_case, "brick"), "intersect": (intersect_case, "grid"),
+}
+RAY_POOL = tuple(n for n in TARGETED if n.startswith(("pixels", "cells")))
+# ... and the only way to the COHERENT probe of the LDS tables: every voxel selected, zeros among them
+FULL = {"zeros_lds": (rp_zeros_case, "cell")}
+
+
+def targeted(name):
+    """-> (case, its adversarial table)"""
+    build, table = (TARGETED if name in TARGETED else FULL)[name]
+    case = build()
+    return case, case["tables"][table]
+
+
+def rp_votes(c, pred=None, pairs=None):
+    """post_oracle.ray_pool_1cube on a ray-pooling case (or on other predictions or another pair list for it): (D, D, D) uint8."""
+    from oracle import post_oracle
+    p16 = np.asarray(c["pred"] if pred is None else pred)[0].astype(np.float16)
+    pairs = c["pairs"][0] if pairs is None else np.asarray(pairs)
+    return post_oracle.ray_pool_1cube(c["cameras"], p16, pairs, c["xyz"][0], c["resol"][0], c["thresh"]).astype(np.uint8)
+
+
+@functools.lru_cache(maxsize=None)
+def rp_want(name):
+    """The votes of a ray-pooling case, computed once and shared (read-only) among the tests."""
+    return _ro(rp_votes(targeted(name)[0]))
 
 
 def tables_of(name):

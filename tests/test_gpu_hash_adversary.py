@@ -3,8 +3,14 @@
 sixteen slots of whatever table the stage sizes, so the claims race along one run hundreds of slots long that walks off slot `mask` on to
 slot 0, duplicates of one key among them - the walks no random or geometric input of the suite reaches (tests/test_hash_adversary_cpu.py
 shows both halves of that on a model). Every stage runs through the entry its own GPU test uses and is held to the same restatement by the
-same comparison, twice (equal bytes), in the host-array form and, where there is one, the device form. Nothing here is at workload size."""
+same comparison, twice (equal bytes), in the host-array form and, where there is one, the device form. Nothing here is at workload size.
+
+Ray pooling's pixel and cell tables (in LDS, where the four arrays lie back to back and may be 83 % full, and in global memory), the mesher's
+brick table and the self-intersection grid get keys that are late at the one capacity their sizing rule gives them (hash_adversary.TARGETED)."""
 import ctypes
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -14,6 +20,7 @@ import gtcubes_ref
 import hash_adversary as ha
 import mesh_ref as mr
 import meshfill_ref as fref
+import meshintersect_ref as xref
 import meshorient_ref as oref
 import meshsimplify_ref as simref
 import meshsmooth_ref as smref
@@ -25,6 +32,11 @@ import ptcubes_ref
 
 pytestmark = pytest.mark.gpu
 ORIGIN, RESOL = (-20.0, -20.0, -20.0), 0.4
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _case(name):
+    return ha.BUILDERS[name]() if name in ha.BUILDERS else ha.targeted(name)[0]
 
 
 @pytest.fixture(scope="module")
@@ -129,7 +141,7 @@ def _normals(ctx, name):
 
 def _mesh(ctx, name):
     import test_gpu_mesh as tm
-    s = ha.BUILDERS[name]()
+    s = _case(name)
     want = mr.mesh_ref(*mr.scene_args(s), radius=2, reach=0, origin=ORIGIN, resol=RESOL)
     assert want["quads"].shape[0] > 0 and want["n_cells"] >= s["n_late"]
     host = _twice(lambda: tm._run(ctx, s))
@@ -292,11 +304,78 @@ def _ptcubes(ctx, name):
     assert np.array_equal(ijk_d, ijk) and np.array_equal(xyz_d, xyz) and np.array_equal(ijk, want[0]["ijk"])
 
 
+# ---- ray pooling: the pixel table and the cell table, in LDS and in global memory ------------------------------------------------------------------------------
+def _ray_pool(_, name):
+    import surfacenet_amd
+    c = _case(name)
+    want = ha.rp_want(name)
+    D = c["D"]
+    n, n_vp = c["pairs"].shape[:2]
+    assert want.any() and want.max() <= 2 * n_vp
+    with surfacenet_amd.Context(cube_D=D, max_samples=4) as ctx:
+        ctx.set_cameras(c["cameras"])
+        got = _twice(lambda: ctx.ray_pool(c["pairs"], c["xyz"], c["resol"], c["pred"], c["thresh"]))
+        assert got.dtype == np.uint8 and got.shape == (1, D, D, D) and got.tobytes() == want.tobytes()
+        with _Staged(ctx) as st:
+            d_in = [st.up(c["pairs"].astype(np.int64)), st.up(c["xyz"]), st.up(c["resol"]), st.up(c["pred"])]
+            d_votes = st.up(np.full(D ** 3, 7, np.uint8))
+            for _ in range(2):
+                ctx.ray_pool_dev(n, n_vp, *(d_in + [d_votes]), prediction_thresh=c["thresh"])
+                dev = np.empty(D ** 3, np.uint8)
+                ctx.d2h(dev, d_votes)
+                assert dev.tobytes() == want.tobytes()
+
+
+# ---- the self-intersection grid ------------------------------------------------------------------------------------------------------------------------------
+def _intersect(ctx, name):
+    c = _case(name)
+    v, f = c["verts"], c["faces"]
+    want = xref.intersect(v, f)
+    assert xref.grid_level(v, f)[0] == 0 and want["counts"][3] > 200
+    for device in (False, True):
+        got = _twice(lambda: ctx.mesh_intersect(v, f, device=device))
+        assert xref.same_bytes(got, want) == [], (device, xref.same_bytes(got, want), got["counts"].tolist(), want["counts"].tolist())
+
+
+_CHILD = """import sys
+import numpy as np
+sys.path[:0] = [%r, %r]
+import hash_adversary as ha
+from surfacenet_amd import runtime
+c = ha.intersect_case(8)
+ctx = runtime.any_context()
+out = {}
+for device in (False, True):
+    for run in (0, 1):
+        got = ctx.mesh_intersect(c["verts"], c["faces"], device=device)
+        out.update({"%%s_%%d_%%d" %% (k, device, run): got[k] for k in ("face_hit", "face_pairs", "pairs", "counts")})
+np.savez(sys.argv[1], **out)
+"""
+
+
+def test_late_grid_cells_at_a_forced_level(gpu_required, tmp_path):
+    """The mesh with (v + 4) scaled by 8 presents the same late keys at level 3, which SN_MXI_LEVEL forces in the test-only twin (one child
+    process, as in tests/test_gpu_meshintersect.py): the restatement on the scaled mesh, host and device form, twice."""
+    c = ha.intersect_case(8)
+    want = xref.intersect(c["verts"], c["faces"])
+    assert xref.same_bytes(want, xref.intersect(*[_case("intersect")[k] for k in ("verts", "faces")])) == []
+    env = dict(os.environ, SURFACENET_HIP_LIB=os.path.join(ROOT, "surfacenet_amd", "libsurfacenet_hip_dbg.so"), SN_MXI_LEVEL=str(c["level"]))
+    script, out = tmp_path / "child.py", str(tmp_path / "forced.npz")
+    script.write_text(_CHILD % (ROOT, os.path.join(ROOT, "tests")))
+    subprocess.check_call([sys.executable, str(script), out], env=env, cwd=ROOT)
+    got = np.load(out)
+    for device in (0, 1):
+        for run in (0, 1):
+            r = {k: got["%s_%d_%d" % (k, device, run)] for k in xref.KEYS}
+            assert xref.same_bytes(r, want) == [], (device, run, xref.same_bytes(r, want), r["counts"].tolist(), want["counts"].tolist())
+
+
 # ---- one test per stage and case -------------------------------------------------------------------------------------------------------------------------------
 STAGES = [(_unique, ("cells32", "cells512", "cells1500", "bricks")), (_components, ("cells32", "cells512", "cells1500", "bricks")),
-          (_normals, ("bricks", "cells1500")), (_mesh, ("cells32b", "cells512b", "cells1500b")), (_denoise, ("cubemap",)), (_adapthresh, ("cubemap",)),
+          (_normals, ("bricks", "cells1500")), (_mesh, ("cells32b", "cells512b", "cells1500b", "bricks_mesh")), (_denoise, ("cubemap",)), (_adapthresh, ("cubemap",)),
           (_smooth, ("edges3", "edges4")), (_fill, ("edges3", "edges4")), (_orient, ("edges3", "edges4")), (_simplify, ("simplify",)),
-          (_point_reduce, ("reduce1", "reduce3")), (_nn_dist2, ("nn",)), (_gt_cubes, ("gt",)), (_ptcubes, ("ptcubes_f64", "ptcubes_f32"))]
+          (_point_reduce, ("reduce1", "reduce3")), (_nn_dist2, ("nn",)), (_gt_cubes, ("gt",)), (_ptcubes, ("ptcubes_f64", "ptcubes_f32")),
+          (_ray_pool, ha.RAY_POOL + tuple(ha.FULL)), (_intersect, ("intersect",))]
 RUNS = [(fn, name) for fn, names in STAGES for name in names]
 
 

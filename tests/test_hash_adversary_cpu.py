@@ -6,7 +6,15 @@ least 3/4 of the late keys inserted (or cap / 2 where that is smaller); at the t
 coordinate-derived builders are held to the cells their stage's restatement assigns. Three planted faults - a walk that stops at slot `mask`,
 a walk cut after 64 steps, a key dropped when its first slot is taken - lose keys of every adversarial case at the capacity its stage uses and
 (the cut walk) none of the scenes the suite had; and with the lost keys' entries removed the restatements' results fail the stages' own
-comparisons. `pytest -s -k figures` prints the figures profiles/hashadv/README.md records."""
+comparisons. `pytest -s -k figures` prints the figures profiles/hashadv/README.md records.
+
+Ray pooling's pixel and cell tables and the mesher's brick table have too few candidates for keys late at every capacity: their cases
+(hash_adversary.TARGETED) are late at the one capacity the stage's sizing rule gives them, so the rule's constants are read out of the headers,
+every case is held to the rule and to the same conditions at that capacity (a wrap, a walk of 64 steps, a key lost to each fault, another
+result from the restatement without the lost keys), and the self-intersection grid's case stands with them."""
+import os
+import re
+
 import numpy as np
 import pytest
 
@@ -269,6 +277,241 @@ def test_the_smoothers_edge_statistics_notice_lost_edges(fault, nv):
         test_gpu_meshsmooth._compare(smref.smooth(c["verts"], faces, 0), want)
 
 
+# ---- the cases that are late at the one capacity their stage gives them: ray pooling, the mesher's bricks; and the intersection grid -------------------------
+TARGETED = list(ha.TARGETED)
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "surfacenet_amd", "csrc")
+
+
+def _header_constant(header, name):
+    text = open(os.path.join(CSRC, header)).read()
+    found = re.findall(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text)
+    assert len(found) == 1, (header, name, found)
+    return int(found[0])
+
+
+def test_the_restated_sizing_rules_are_the_kernels():
+    """A targeted case is adversarial only while the rule it was built for is the kernel's: the constants are read out of the headers' text."""
+    assert ha.RP_LIST == _header_constant("postpass.h", "RP_LIST")
+    assert ha.RP_LDS_M == _header_constant("postpass.h", "RP_LDS_M")
+    assert ha.RP_LDS_CAP == _header_constant("postpass.h", "RP_LDS_CAP")
+    assert ha.MXI_BIG == _header_constant("meshintersect.h", "MXI_BIG")
+    assert ha.MXI_OFFSET == _header_constant("meshintersect_rules.h", "MXI_CELL_OFFSET")
+    assert ha.LDS_FILL[1] * ha.RP_LDS_M <= ha.LDS_FILL[0] * ha.RP_LDS_CAP < ha.LDS_FILL[1] * (ha.RP_LDS_M + 14)      # 83 %: all but the 5/6 the header promises
+    rule = ha.ray_pool_rule
+    assert rule(1) == dict(cap=64, lds=True, listed=True) and rule(32)["cap"] == 64 and rule(33)["cap"] == 128
+    assert rule(2048)["cap"] == 4096 and rule(2049) == dict(cap=4096, lds=True, listed=True) and rule(3400)["cap"] == 4096
+    assert rule(3401) == dict(cap=8192, lds=False, listed=True) and rule(4096)["cap"] == 8192 and rule(4097)["cap"] == 16384
+    assert rule(8192) == dict(cap=16384, lds=False, listed=True) and rule(8193) == dict(cap=32768, lds=False, listed=False)
+    assert ha.brick_cap(512) == 1024 and ha.intersect_cap(1024) == 16384 and ha.intersect_cap(513) == 16384 and ha.intersect_cap(3, 4) == 1024
+    assert np.array_equal(ha.late_at(np.arange(1 << 16), 1024), np.arange(1 << 16)[(ha.mix64(np.arange(1 << 16)) & np.uint64(1023)) >= 1008])
+
+
+def _model(name, fault=None):
+    c, t = ha.targeted(name)
+    return ha.probe_model(t["keys"], t["cap"], fault, fill=c.get("fill", (1, 2)))
+
+
+@pytest.mark.parametrize("name", TARGETED)
+def test_targeted_cases_enter_the_keys_their_rule_was_evaluated_for(name):
+    c, t = ha.targeted(name)
+    keys, cap = t["keys"], t["cap"]
+    assert len(keys) == c["rule_n"]                             # the keys entered number what the rule was evaluated for
+    at_cap = ha.late_mask(keys, ha.W, cap.bit_length() - 1)
+    assert np.array_equal(np.unique(ha.late_at(keys, cap)), np.unique(keys[at_cap]))
+    assert np.unique(keys[at_cap]).size >= c["n_late"] and c["n_late"] >= (24 if len(keys) == 32 else 64)
+    if name in ha.RAY_POOL:
+        m = int((c["pred"].astype(np.float16) > np.float16(c["thresh"])).sum())
+        assert m == c["rule_n"] == len(c["selected"]) and c["rule"] == ha.ray_pool_rule(m) and cap == c["rule"]["cap"]
+        assert c["rule"]["lds"] == ("_lds" in name) and c["rule"]["listed"] == ("unlisted" not in name)
+        assert c["fill"] == (ha.LDS_FILL if c["rule"]["lds"] else (1, 2)) and c["fill"][1] * m <= c["fill"][0] * cap
+        views = c["pairs"].reshape(-1).tolist()
+        assert len(set(views)) >= 2 and views.count(c["view"]) == 2      # two distinct views at least, the adversarial one repeated
+        w, h, d = (x[c["selected"]] for x in ha._project(c["cameras"][c["view"]].tolist(), c["D"]))
+        if name.startswith("pixels"):
+            assert np.unique(np.stack([w, h], 1), axis=0).shape[0] == m and np.array_equal(ha.pixel_key(w, h), keys)      # one cell per pixel
+            assert ((w == -1) & (h == -1)).sum() == 1 and (w < 0).sum() > 10 and (h < 0).sum() > 10 and (np.maximum(w, h) > 5000).any()
+            assert int(ha.pixel_key(-1, -1)) ^ 0x8000000080000000 == 0xffffffffffffffff      # (-1, -1) unflipped is the empty sentinel
+        else:
+            pix = np.unique(np.stack([w, h], 1), axis=0)
+            home = (ha.mix64(ha.pixel_key(pix[:, 0], pix[:, 1])) & np.uint64(cap - 1)).astype(np.int64)
+            assert 24 <= len(pix) == np.unique(home).size and (pix[:, 0] < 0).any()      # every pixel gets its home slot, whoever comes first
+            slot = home[np.searchsorted(pix[:, 0], w)]
+            assert np.array_equal(ha.rp_cell_key(slot, d), keys) and np.unique(keys).size == m
+            assert np.bincount(np.searchsorted(pix[:, 0], w)).max() > 50      # many cells on one pixel
+            p = c["pred"].reshape(-1)[c["selected"]]
+            for px in np.unique(w[at_cap]):                     # the late cells hold the largest predictions of their pixels
+                assert p[(w == px) & at_cap].min() > p[(w == px) & ~at_cap].max()
+            a, b = c["tied"]
+            pa, pb = c["pred"].reshape(-1)[[a, b]]
+            assert a != b and pa == pb == p.max() and a // c["D"] ** 2 == b // c["D"] ** 2
+            alone = ha.rp_votes(c, pairs=[[c["view"], c["view"]]]).reshape(-1)      # the tie goes to the smaller depth bin: view 0 votes for it alone
+            near, far = (a, b) if d[c["selected"] == a][0] < d[c["selected"] == b][0] else (b, a)
+            assert alone[near] == 2 and alone[far] == 0
+    elif name == "bricks_mesh":
+        assert c["mask"].all() and c["mask"].size == c["rule_n"] == 512 and cap == ha.brick_cap(c["mask"].size) == c["tables"]["cell"]["cap"] == 1024
+        g = nref.world_cells(c["offsets"], c["ijk"], c["cube_ijk"], c["stride_vox"])
+        assert np.unique(g, axis=0).shape[0] == 512 and np.array_equal(ha.keys_of_cells((g + 4) >> 2), keys)
+        assert c["n_late"] == 384 and at_cap[:384].all() and np.unique(keys[:384]).size == 384 and not at_cap[384:].any()      # one voxel per late brick
+        assert not ha.late_mask(keys).sum() > 16                 # late at every capacity: a handful, as the README's "not reached" said
+    else:
+        import meshintersect_ref as mref
+        assert cap == ha.intersect_cap(c["faces"].shape[0]) == 16384 and ha.late_mask(keys).all()      # (these are late at every capacity)
+        assert mref.grid_level(c["verts"], c["faces"]) == (0, c["faces"].shape[0])      # the natural level is 0, a triangle in one cell
+        cells = np.floor(c["verts"][c["faces"]]).astype(np.int64) + ha.MXI_OFFSET
+        assert (cells == c["tri_cell"][:, None, :]).all()       # every corner strictly inside the triangle's late cell
+        assert (np.abs(c["verts"] - np.rint(c["verts"])) >= 1.0 / 16).all()
+        per_cell = np.unique(keys, return_counts=True)[1]
+        assert per_cell.max() == ha.MXI_BIG + 3 and sorted(set(per_cell.tolist())) == [1, 2, ha.MXI_BIG + 3]
+        assert _model(name)["walk"][-1] >= 400                   # the big cell is the last key: its slot is the end of the run
+        r = mref.intersect(c["verts"], c["faces"])
+        assert r["counts"][3] > 200 and r["counts"][2] > r["counts"][3] + 100 and r["counts"][1] == 0      # hits, and candidates that are none
+        x8 = ha.intersect_case(8)
+        assert np.array_equal(x8["faces"], c["faces"]) and x8["level"] == 3
+        cells8 = (np.floor(x8["verts"][x8["faces"]]).astype(np.int64) + ha.MXI_OFFSET) >> 3
+        assert (cells8 == c["tri_cell"][:, None, :]).all()      # the same keys at level 3
+        assert mref.same_bytes(mref.intersect(x8["verts"], x8["faces"]), r) == []
+
+
+@pytest.mark.parametrize("name", TARGETED)
+def test_targeted_keys_wrap_walk_and_are_lost_to_every_fault(name):
+    """The set of occupied slots of linear probing does not depend on the insertion order (a run is filled from its first slot on, whoever comes
+    first), and neither does which START slots lie in a run that reaches slot `mask`: that is why this sequential model speaks for the GPU's
+    racing inserts. Which key ends where does depend on it, so the conditions count keys and steps; they name no key."""
+    c, t = ha.targeted(name)
+    m = _model(name)
+    n = len(m["keys"])
+    assert m["wrapped"].sum() >= 1, name
+    if n > ha.LIMIT:
+        assert m["walk"].max() >= ha.LIMIT, (name, int(m["walk"].max()))
+    for fault in ha.FAULTS:
+        lost = len(_model(name, fault)["lost"])
+        if fault == "limit" and n <= ha.LIMIT:
+            assert lost == 0                                     # 32 keys cannot walk 64 steps
+        else:
+            assert lost >= 1, (name, fault)
+    taken = np.zeros(t["cap"], bool)
+    taken[m["slot"]] = True
+    again = ha.probe_model(t["keys"][np.random.RandomState(5).permutation(len(t["keys"]))], t["cap"], fill=c.get("fill", (1, 2)))
+    other = np.zeros(t["cap"], bool)
+    other[again["slot"]] = True
+    assert np.array_equal(taken, other) and again["wrapped"].sum() >= 1      # another order: the same slots
+
+
+@pytest.mark.parametrize("fault", ha.FAULTS)
+@pytest.mark.parametrize("name", ha.RAY_POOL)
+def test_ray_pooling_notices_lost_keys(name, fault):
+    if fault == "limit" and name.endswith("32"):
+        return                                                   # (no key to lose)
+    c, _ = ha.targeted(name)
+    lost = _model(name, fault)["lost"]
+    broken = ha.without_voxels(c, lost)
+    assert 0 < (broken != c["pred"]).sum() == len(lost)
+    assert not np.array_equal(ha.rp_votes(c, broken), ha.rp_want(name))
+
+
+def test_the_zero_predictions_case_reaches_the_coherent_probe_of_the_lds_tables():
+    """ray_pool_kernel calls lt_find<LtKeys, true> for a voxel that stores a 0 on a pixel whose cells all store 0, at another bin than the view's
+    minimum: only without a threshold, so with every voxel selected, so in LDS only for a cube of at most 12^3 (the library takes multiples of 4):
+    1,728 keys in 4,096 slots. No fault can lose 64 steps there; the case is held to what its camera was searched for: the looked-up key of an
+    all-zero slice starts in the last sixteen slots, in a run that passes slot `mask` in any order of the inserts."""
+    c, t = ha.targeted("zeros_lds")
+    D, m = c["D"], c["D"] ** 3
+    assert c["thresh"] is None and m == c["rule_n"] == len(t["keys"]) == np.unique(t["keys"]).size and (D + 4) ** 3 > ha.RP_LDS_M >= m
+    assert c["rule"] == ha.ray_pool_rule(m) == dict(cap=4096, lds=True, listed=True)
+    w, h, d = ha._project(c["cameras"][0].tolist(), D)
+    i = np.arange(m) // (D * D)
+    pix = np.unique(np.stack([w, h], 1), axis=0)
+    home = (ha.mix64(ha.pixel_key(pix[:, 0], pix[:, 1])) & np.uint64(t["cap"] - 1)).astype(np.int64)
+    assert len(pix) == D == np.unique(home).size and np.array_equal(pix[i, 0], w)      # a pixel per i, each at its home slot
+    assert np.array_equal(ha.rp_cell_key(home[i], d), t["keys"]) and d.min() == c["dmin"]
+    pred = c["pred"].reshape(D, D * D)
+    zero = np.nonzero((pred == 0).all(axis=1))[0]
+    assert np.array_equal(zero, c["zero_pixels"]) and len(zero) == 3 and 0 not in zero and pred[0, 0] == 0
+    assert (d.reshape(D, -1)[:, 0] == c["dmin"]).all()          # every pixel has its cell at the minimum bin: voxel (i, 0, 0)
+    lookups = ha.rp_cell_key(home[c["late_pixels"]], c["dmin"])  # the key 143 voxels of a late zero slice each look up
+    assert len(lookups) >= 1 and np.isin(c["late_pixels"], zero).all() and np.isin(lookups, t["keys"]).all()
+    assert c["n_late"] == 19 == len(ha.late_at(t["keys"], t["cap"])) and np.isin(lookups, ha.late_at(t["keys"], t["cap"])).all()
+    model = ha.probe_model(t["keys"], t["cap"])
+    taken = np.zeros(t["cap"], bool)
+    taken[model["slot"]] = True
+    start = int(ha.mix64(lookups).min() & np.uint64(t["cap"] - 1))
+    assert start >= t["cap"] - 16 and taken[start:].all() and taken[:8].all()      # the run those lookups start in passes slot `mask` by 8 slots
+    assert model["wrapped"].sum() >= 1 and len(ha.probe_model(t["keys"], t["cap"], "no_wrap")["lost"]) >= 1
+    alone = ha.rp_votes(c, pairs=[[0, 0]]).reshape(D, D * D)
+    assert (alone[zero, 0] == 2).all() and not alone[zero, 1:].any() and alone[0, 0] == 0      # found: the cell votes; missed: voxel 0 would get the vote
+    assert (alone > 0).sum() == D
+
+
+def _fullest_inputs(m):
+    """test_gpu_post.test_ray_pool_tables_at_their_fullest's inputs, restated: -> per distinct view the pixel keys and, with the pixel slots the
+    model gives in flat order, the cell keys of the selected voxels."""
+    from oracle import post_oracle
+    import test_gpu_post
+    D = 16
+    rs = np.random.RandomState(m)
+    pred = np.full(D ** 3, 0.1, np.float32)
+    pred[rs.permutation(D ** 3)[:m]] = (0.6 + 0.3 * rs.rand(m)).astype(np.float32)
+    sel = np.nonzero(pred.astype(np.float16) > np.float16(0.5))[0]
+    assert len(sel) == m
+    xyz, r = np.asarray([-3.0, 2.0, 640.0], np.float32).astype(np.float64), float(np.float32(0.4))
+    i, j, k = np.unravel_index(sel, (D, D, D))
+    X, Y, Z = i * r + xyz[0], j * r + xyz[1], k * r + xyz[2]
+    cap, fill = ha.ray_pool_rule(m)["cap"], (ha.LDS_FILL if ha.ray_pool_rule(m)["lds"] else (1, 2))
+    out = []
+    for view in (0, 1, 2):
+        q = post_oracle._numerators(test_gpu_post.P_DTU[view], X, Y, Z)
+        w, h, d = np.rint(q[0] / q[2]).astype(np.int64), np.rint(q[1] / q[2]).astype(np.int64), np.rint(q[2] / r).astype(np.int64)
+        pk = ha.pixel_key(w, h)
+        pm = ha.probe_model(pk, cap, fill=fill)
+        slot = dict(zip(pm["keys"].tolist(), pm["slot"].tolist()))
+        out.append((pk, ha.rp_cell_key([slot[x] for x in pk.tolist()], d), cap, fill))
+    return out
+
+
+@pytest.mark.parametrize("m", [32, 2048, 3400, 4096])
+def test_the_fullest_ray_pool_inputs_lose_nothing_to_a_walk_that_stops(m):
+    """The seeded voxels under the DTU cameras hash uniformly: in every view's PIXEL table (its keys are the input's own, whatever the order) no
+    walk wraps and none is longer than 8 slots, so a walk that stops at slot `mask` or after 64 steps loses none of them. The CELL keys hold the
+    pixel's slot, which the race decides; with the slots the model gives in flat order they wrap 0 to 7 keys per view by chance, and at
+    m = 3,400 (83 % full) the longest walks are 119, 168 and 65 slots: figures, not conditions, since another order gives other keys. No such
+    walk is there by construction."""
+    for pk, ck, cap, fill in _fullest_inputs(m):
+        model = ha.probe_model(pk, cap, fill=fill)
+        assert model["wrapped"].sum() == 0 and model["walk"].max() <= 8
+        for fault in ("no_wrap", "limit"):
+            assert len(ha.probe_model(pk, cap, fault, fill=fill)["lost"]) == 0, (m, fault)
+        assert ha.probe_model(ck, cap, fill=fill)["wrapped"].sum() <= 7      # (this order's; see above)
+
+
+@pytest.mark.parametrize("fault", ha.FAULTS)
+def test_the_intersection_stage_notices_lost_grid_cells(fault):
+    import meshintersect_ref as mref
+    c, _ = ha.targeted("intersect")
+    faces = ha.without_grid_cells(c, _model("intersect", fault)["lost"])
+    assert 0 < faces.shape[0] < c["faces"].shape[0]
+    want = mref.intersect(c["verts"], c["faces"])
+    broken = mref.intersect(c["verts"], faces)
+    assert broken["counts"][3] < want["counts"][3] and broken["counts"][4] < want["counts"][4]      # pairs and hit faces go with the cells
+
+
+@pytest.mark.parametrize("fault", ha.FAULTS)
+def test_the_mesher_notices_lost_bricks(fault):
+    import mesh_ref as mr
+    import test_gpu_mesh
+    c, _ = ha.targeted("bricks_mesh")
+    broken = ha.without_bricks(c, _model("bricks_mesh", fault)["lost"])
+    assert 0 < broken["mask"].sum() < c["mask"].sum()
+    want = mr.mesh_ref(*mr.scene_args(c), radius=2, reach=0)
+    assert want["quads"].shape[0] > 0 and want["n_cells"] == 512
+    with pytest.raises(AssertionError):
+        test_gpu_mesh._compare(_mesh_outputs(mr.mesh_ref(*mr.scene_args(broken), radius=2, reach=0)), want)
+
+
+def _mesh_outputs(r):
+    """mesh_ref's dict under the names the stage returns (test_gpu_mesh._compare reads got["verts_lattice"], want["vert_lattice"])."""
+    return dict(r, verts_lattice=r["vert_lattice"])
+
+
 # ---- the figures ----------------------------------------------------------------------------------------------------------------------------------------------
 def test_figures():
     """What profiles/hashadv/README.md records (run with -s)."""
@@ -282,6 +525,20 @@ def test_figures():
                                                                                  t["cap"], m["walk"].max(), m["wrapped"].sum(), len(m["keys"]), *lost))
         worst = min((_condition(t["keys"], cap)[1] / max(min(0.75 * _condition(t["keys"], cap)[0], cap / 2), 1), cap) for cap in CAPS)
         assert worst[0] >= 1
+    for name in TARGETED + list(ha.FULL):
+        c, t = ha.targeted(name)
+        m = _model(name)
+        at_cap = int(ha.late_mask(m["keys"], ha.W, t["cap"].bit_length() - 1).sum())
+        print("| %s | %s | %d | %d | %d | %d, %.0f %% | %d | %d of %d | %d | %d | %d |" % (name, ha.TARGETED.get(name, ha.FULL.get(name))[1], len(t["keys"]), len(m["keys"]), at_cap, t["cap"],
+                                                                                            100.0 * len(m["keys"]) / t["cap"], m["walk"].max(), m["wrapped"].sum(), len(m["keys"]),
+                                                                                            *[len(_model(name, f)["lost"]) for f in ha.FAULTS]))
+    for m_sel in (32, 2048, 3400, 4096):
+        for view, (pk, ck, cap, fill) in enumerate(_fullest_inputs(m_sel)):
+            for table, keys in (("pixel", pk), ("cell", ck)):
+                m = ha.probe_model(keys, cap, fill=fill)
+                print("| fullest m = %d, view %d | %s | %d | %d | %d | %d | %d | %d of %d | %d | %d | %d |" % (
+                    m_sel, view, table, len(keys), len(m["keys"]), int(ha.late_mask(m["keys"], ha.W, cap.bit_length() - 1).sum()), cap, m["walk"].max(), m["wrapped"].sum(),
+                    len(m["keys"]), *[len(ha.probe_model(keys, cap, f, fill=fill)["lost"]) for f in ha.FAULTS]))
     for name, t in _existing().items():
         m = ha.probe_model(t["keys"], t["cap"])
         print("| %s | existing | %d | %d | %d | %d | %d | %d of %d | %d | %d | %d |" % (name, len(t["keys"]), len(m["keys"]), int(ha.late_mask(m["keys"]).sum()), t["cap"],
