@@ -11,10 +11,12 @@
   * PADDING: the padded channels (6 -> 8, 300 -> 304, 100 -> 104) are exact zeros in every plane; workspace samples beyond the batch are
     untouched.
 
-Shapes: the smallest cube sizes that reach each tile / halo case of ConvKernel::launch - cube_D 8 and 12 (every tile partial; all four
-precision modes, i.e. every storage format), 20 and 28 (partial tiles above 8 at levels 0 and 1; quarter extents 5 and 7 under the dilated
-chain), 24, 40 and 44 (quarter extents 6, 10 = 8 + R and 11: partial tiles ABOVE 8 under conv4_x, which no test ran before), one sample.
-Measured figures of the first run: profiles/layers/README.md."""
+Shapes: the smallest cube sizes that reach each tile / halo case of ConvKernel::launch, for EVERY plan build_plan_t can select (precision,
+conv4_fp8; tests/golden/conv_plan.json): cube_D 8 and 12 (every tile partial), 20 (extents 20 / 10 / 5: a partial tile behind a full one at
+levels 0 and 1, two full 8-tiles and one full 16-tile at level 0), 40 (interior full tiles at level 0; quarter extent 10 = 8 + R, the smallest
+multi-tile extent the dilated kernels accept) and 44 (22 / 11: a partial tile at every level at once), one sample; the default plan also at
+24 and 28 (quarter extents 6 and 7). tests/test_layers_cpu.py holds CASES to the tile classes (layer_check.tile_classes) each plan can reach.
+Measured figures: profiles/layers/README.md."""
 import ctypes
 import os
 import time
@@ -29,7 +31,17 @@ import synth
 pytestmark = pytest.mark.gpu
 
 ALL = ("f16x3", "f16x3p", "f16m8", "f16")
-CASES = [(s, p) for s in (8, 12) for p in ALL] + [(20, "f16x3"), (28, "f16x3"), (24, "f16x3"), (40, "f16x3"), (40, "f16x3p"), (44, "f16x3")]
+# (cube_D, precision, conv4_fp8); conv4_fp8 None: the mode's own (sn.Context is given none) - 1 in f16x3
+CASES = [(s, p, None) for s in (8, 12) for p in ALL] + [(s, "f16x3", None) for s in (20, 28, 24, 40)] + [(40, "f16x3p", None), (44, "f16x3", None)]
+CASES += [(s, p, None) for p in ("f16m8", "f16") for s in (20, 40, 44)] + [(20, "f16x3p", None), (44, "f16x3p", None)]
+# conv4_fp8 = 2 (conv4_1 on three fp16 MFMAs storing hi + fp8 codes: an instantiation no other plan has) and 0 (the public opt-out). 20 is there
+# because the tile classes of a plan are counted over the plan's own cases (test_layers_cpu.py): extents 16 .. 31 are the only ones with exactly
+# one full 16-wide conv1_x tile, and a 40 of the opt-out plan is its only quarter extent of 8 + R.
+CASES += [(s, "f16x3", 2) for s in (12, 20, 40, 44)] + [(s, "f16x3", 0) for s in (12, 20, 40, 44)]
+
+
+def case_id(c):
+    return "%d-%s" % c[:2] + ("" if c[2] is None else "-conv4_fp8_%d" % c[2])
 
 
 @pytest.fixture(scope="module")
@@ -62,50 +74,42 @@ def read_back(ctx, dbg):
     return raws, lays
 
 
-def check_layouts(lays, s, max_samples, precision):
-    """What sn_debug_tensor_info says against what the mode is documented to store (DESIGN.md sections 3 and 5)."""
-    fmt_of = {"f16": ad.FMT_F16, "f16x3p": ad.FMT_HILO, "f16m8": ad.FMT_M6}
-    default = dict(cat=ad.FMT_M6, ma=ad.FMT_M6, a3=ad.FMT_HILO_M8, b4=ad.FMT_M8)
+def check_layouts(lays, s, max_samples, precision, conv4_fp8=None):
+    """What sn_debug_tensor_info says against what the plan is documented to store (layer_check.storage: DESIGN.md sections 3 and 5, build_plan_t)."""
+    fmt, e8 = lc.storage(precision, conv4_fp8)
+    assert set(lays) == set(fmt)
     for buf, lay in lays.items():
-        assert lay.fmt == (default.get(buf, ad.FMT_HILO) if precision == "f16x3" else fmt_of[precision]), (buf, lay.fmt)
+        assert lay.fmt == fmt[buf], (buf, lay.fmt, fmt[buf])
+        assert lay.e8 == e8[buf], (buf, lay.e8, e8[buf])
         assert lay.max_samples() == max_samples and s % lay.extent == 0 and lay.extent in (s, s // 2, s // 4) and lay.cs % 8 == 0
         assert lay.cs - lc.BUFFERS[buf][1] in (0, 2, 4)
-    assert lays["cat"].e8 == 125 and lays["ma"].e8 == 127 and lays["x0"].e8 == 132 and lays["b4"].e8 == 127      # mx_format.h: s = 2, 0, -5, 0
 
 
-def check_padding(pads, extras, lays):
-    for buf, pad in pads.items():
-        assert np.isfinite(pad).all(), buf
-        assert pad.shape[1] == (lays[buf].cs - lc.BUFFERS[buf][1])
-        # their producers write them as exact zeros (zero weight rows, zero folded scale and shift; the CVC warp / upload zero channels 6, 7)
-        assert not pad.any(), (buf, float(np.abs(pad).max()))
-        C = lc.BUFFERS[buf][1]
-        for k in ("hi", "hi_code", "lo_code"):
-            if k in extras[buf]:
-                assert np.isfinite(extras[buf][k]).all() and not extras[buf][k][:, C:].any(), (buf, k)
-    assert set(b for b in pads if pads[b].shape[1]) == set(lc.PADDED)
+check_padding = lc.check_padding
 
 
-@pytest.mark.parametrize("s,precision", CASES)
-def test_every_stored_tensor_and_every_launch(sn, dbg, s, precision):
+@pytest.mark.parametrize("s,precision,conv4_fp8", CASES, ids=[case_id(c) for c in CASES])
+def test_every_stored_tensor_and_every_launch(sn, dbg, s, precision, conv4_fp8):
     t0 = time.time()
     values = list(synth.calibrated_params(1))
     X = synth.random_cvc(1, s, 40 + s)
-    with sn.Context(cube_D=s, max_samples=1, precision=precision) as ctx:
+    plan = "%s%s" % (precision, "" if conv4_fp8 is None else ", conv4_fp8 = %d" % conv4_fp8)
+    with sn.Context(cube_D=s, max_samples=1, precision=precision, **({} if conv4_fp8 is None else dict(conv4_fp8=conv4_fp8))) as ctx:
         ctx.load_param_values(values)
         _, unfused = ctx.forward(X, None, n_vp=1)
         raws, lays = read_back(ctx, dbg)
     t_gpu = time.time() - t0
-    check_layouts(lays, s, 1, precision)
+    check_layouts(lays, s, 1, precision, conv4_fp8)
     dec, pads, extras = lc.decode_all(raws, lays, values, 1, unfused)
     check_padding(pads, extras, lays)
-    exact, ref, factor = lc.references(X, values, precision)
-    g = lc.global_table(dec, exact, ref, factor, "cube_D %d, %s: stored tensors against the fp64 oracle" % (s, precision))
+    exact, ref, factor = lc.references(X, values, precision, conv4_fp8)
+    g = lc.global_table(dec, exact, ref, factor, "cube_D %d, %s: stored tensors against the fp64 oracle" % (s, plan))
     t_glob = time.time() - t0
-    loc = lc.local_table(dec, values, precision, "cube_D %d, %s: each launch against the fp64 step on its own stored input" % (s, precision))
+    loc = lc.local_table(dec, values, precision, "cube_D %d, %s: each launch against the fp64 step on its own stored input" % (s, plan), conv4_fp8=conv4_fp8)
     print("  wall time: device + read-back %.1f s, global check %.1f s, local check %.1f s" % (t_gpu, t_glob - t_gpu, time.time() - t0 - t_glob))
     bad_g = [(r[0], "%.3e > %.3e" % (r[1], r[3])) for r in g if not r[1] <= r[3]]
     bad_l = [(r[0], r[1], "%.3e > %.3e" % (r[2], r[4])) for r in loc if not r[2] <= r[4]]
+    print("  closest to its bound (device / bound): global %s %.2f, local %s %.2f" % (lc.closest(g, 1, 3, 0) + lc.closest(loc, 2, 4, 1)))
     assert not bad_g and not bad_l, (bad_g, bad_l)
 
 
