@@ -1,4 +1,4 @@
-// mesh_input.h — what the mesh stages (meshsample.h, meshsimplify.h, meshsmooth.h, meshfill.h) ask of a mesh they are given, stated once
+// mesh_input.h — what every mesh stage (meshsample.h, meshsimplify.h, meshedges.h, meshnormals.h, meshrender.h) asks of a mesh it is given, stated once
 // (DESIGN.md section 4.18): the limits, the two predicates their kernels test with, and how a kernel reports the first bad face. Plain C++17,
 // no hip/ include: sn_host.h checks the counts and words the refusal from the same constants, and the host checks compile it alone.
 //   - at most MESH_MAX_ITEMS vertices and as many faces;

@@ -1,6 +1,6 @@
-// meshfill.h — the small holes of a triangle or quad mesh, capped: the closed boundary loops of the edge table meshsmooth.h builds, each decided
+// meshfill.h — the small holes of a triangle or quad mesh, capped: the closed boundary loops of the edge table of meshedges.h, each decided
 // (hole or rim of an open piece) and every hole of at most max_len edges closed by a fan of triangles around one new vertex at the loop's
-// centroid. DESIGN.md section 4.17 states the contract; tests/meshfill_ref.py restates it in numpy. After the build of meshsmooth_build.h:
+// centroid. DESIGN.md section 4.17 states the contract; tests/meshfill_ref.py restates it in numpy. After the table's build (sn_meshedges.hip):
 //   init      per vertex: its own union-find parent
 //   halfedge  per face and side: the side's slot is looked up; a side on an edge of count 1 is a boundary half-edge p -> r: it counts itself in
 //             out[p] and in[r], stores next[p] = r and third[p] = s (any writer's value stays: they are only read where out[p] = 1, where there
@@ -21,13 +21,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "meshsmooth.h"
+#include "meshedges.h"
 #include "unionfind.h"
 
 namespace sn {
 
 constexpr int MFL_NT = 256;
-constexpr int MFL_REC = 3;                                        // the build's position record: 24 bytes
 constexpr unsigned MFL_COMPLEX = 1;                               // root flag: a vertex of the component is not simple
 constexpr unsigned char MFL_NONE = 0, MFL_FILLED = 1, MFL_LONG = 2, MFL_RIM = 3, MFL_CPLX = 4;      // vert_loop
 constexpr int MFL_NO_ROOT = -1;
@@ -74,13 +73,13 @@ __device__ __forceinline__ double mfl_vote_dot(const long long qp[3], const long
     return (ax * bx + ay * by) + az * bz;
 }
 
-static __global__ void __launch_bounds__(MFL_NT) mfl_init_kernel(MsmArgs a, MflArgs b)
+static __global__ void __launch_bounds__(MFL_NT) mfl_init_kernel(MsmEdges a, MflArgs b)
 {
     const long long v = (long long)blockIdx.x * MFL_NT + threadIdx.x;
     if (v < a.V) b.parent[v] = (unsigned)v;
 }
 
-static __global__ void __launch_bounds__(MFL_NT) mfl_halfedge_kernel(MsmArgs a, MflArgs b)
+static __global__ void __launch_bounds__(MFL_NT) mfl_halfedge_kernel(MsmEdges a, MflArgs b)
 {
     const long long f = (long long)blockIdx.x * MFL_NT + threadIdx.x;
     if (f >= a.F) return;
@@ -105,7 +104,7 @@ static __global__ void __launch_bounds__(MFL_NT) mfl_halfedge_kernel(MsmArgs a, 
     }
 }
 
-static __global__ void __launch_bounds__(MFL_NT) mfl_measure_kernel(MsmArgs a, MflArgs b)
+static __global__ void __launch_bounds__(MFL_NT) mfl_measure_kernel(MsmEdges a, MflArgs b)
 {
     const long long v = (long long)blockIdx.x * MFL_NT + threadIdx.x;
     if (v >= a.V) return;
@@ -118,14 +117,14 @@ static __global__ void __launch_bounds__(MFL_NT) mfl_measure_kernel(MsmArgs a, M
     if (o != 1 || b.in[v] != 1 || (fl & MSM_NONMAN)) atomicOr(b.rflag + root, MFL_COMPLEX);
 }
 
-static __global__ void __launch_bounds__(MFL_NT) mfl_sum_kernel(MsmArgs a, MflArgs b)
+static __global__ void __launch_bounds__(MFL_NT) mfl_sum_kernel(MsmEdges a, MflArgs b)
 {
     const long long v = (long long)blockIdx.x * MFL_NT + threadIdx.x;
     if (v >= a.V) return;
     const int root = b.vroot[v];
     if (!mfl_candidate(b, root)) return;
     long long q[3];
-    msm_load<MFL_REC>(a.pos[0], (size_t)v, q);
+    msm_load(a.pos, (size_t)v, q);
     for (int k = 0; k < 3; ++k) atomicAdd(b.rsum + 3 * (size_t)root + k, (unsigned long long)q[k]);
 }
 
@@ -135,7 +134,7 @@ __device__ __forceinline__ void mfl_centroid(const MflArgs &b, int root, long lo
     for (int k = 0; k < 3; ++k) c[k] = msm_mean((long long)b.rsum[3 * (size_t)root + k], n);
 }
 
-static __global__ void __launch_bounds__(MFL_NT) mfl_vote_kernel(MsmArgs a, MflArgs b)
+static __global__ void __launch_bounds__(MFL_NT) mfl_vote_kernel(MsmEdges a, MflArgs b)
 {
     const long long v = (long long)blockIdx.x * MFL_NT + threadIdx.x;
     if (v >= a.V) return;
@@ -143,14 +142,14 @@ static __global__ void __launch_bounds__(MFL_NT) mfl_vote_kernel(MsmArgs a, MflA
     if (!mfl_candidate(b, root)) return;
     long long c[3], qp[3], qr[3], qs[3];
     mfl_centroid(b, root, c);
-    msm_load<MFL_REC>(a.pos[0], (size_t)v, qp);
-    msm_load<MFL_REC>(a.pos[0], (size_t)b.next[v], qr);       // out[v] = 1: one writer, a vertex index of a checked face
-    msm_load<MFL_REC>(a.pos[0], (size_t)b.third[v], qs);
+    msm_load(a.pos, (size_t)v, qp);
+    msm_load(a.pos, (size_t)b.next[v], qr);       // out[v] = 1: one writer, a vertex index of a checked face
+    msm_load(a.pos, (size_t)b.third[v], qs);
     if (mfl_vote_dot(qp, qr, qs, c) < 0.0) atomicAdd(b.rvotes + root, 1u);
 }
 
 // One lane per vertex, at work where the vertex is its component's root; hflag for every v <= V. The counts per wave in registers.
-static __global__ void __launch_bounds__(MFL_NT) mfl_classify_kernel(MsmArgs a, MflArgs b)
+static __global__ void __launch_bounds__(MFL_NT) mfl_classify_kernel(MsmEdges a, MflArgs b)
 {
     const long long stride = (long long)gridDim.x * MFL_NT;
     const int lane = threadIdx.x & 63;
@@ -180,7 +179,7 @@ __device__ __forceinline__ unsigned char mfl_state(const MflArgs &b, long long v
     return root == MFL_NO_ROOT ? MFL_NONE : b.rstate[root];
 }
 
-static __global__ void __launch_bounds__(MFL_NT) mfl_flag_kernel(MsmArgs a, MflArgs b)
+static __global__ void __launch_bounds__(MFL_NT) mfl_flag_kernel(MsmEdges a, MflArgs b)
 {
     const long long v = (long long)blockIdx.x * MFL_NT + threadIdx.x;
     if (v > a.V) return;
@@ -188,7 +187,7 @@ static __global__ void __launch_bounds__(MFL_NT) mfl_flag_kernel(MsmArgs a, MflA
 }
 
 // after the scans and the build: E and the boundary edges from the build's block, H and T from the scans' ends
-static __global__ void mfl_counts_kernel(MsmArgs a, MflArgs b)
+static __global__ void mfl_counts_kernel(MsmEdges a, MflArgs b)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     b.st->counts[0] = b.st->msm.counts[0];
@@ -196,7 +195,7 @@ static __global__ void mfl_counts_kernel(MsmArgs a, MflArgs b)
     b.st->counts[7] = (unsigned long long)b.tpos[a.V];
 }
 
-static __global__ void __launch_bounds__(MFL_NT) mfl_emit_kernel(MsmArgs a, MflArgs b)
+static __global__ void __launch_bounds__(MFL_NT) mfl_emit_kernel(MsmEdges a, MflArgs b)
 {
 #pragma clang fp contract(off)
     const long long v = (long long)blockIdx.x * MFL_NT + threadIdx.x;

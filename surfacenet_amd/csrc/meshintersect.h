@@ -1,6 +1,6 @@
 // meshintersect.h — the self-intersections of a triangle or quad mesh, exactly: which pairs of faces have a point in common beyond what their
 // shared vertices explain. DESIGN.md section 4.23 states the contract; tests/meshintersect_ref.py restates it in Python integers. The kernels
-// run after the smoother's build (meshsmooth_build.h: mark, quantise, edges, degree) on its quantised positions; the rules themselves are
+// run after the build of the edge table (meshedges.h: mark, quantise, edges, degree) on its quantised positions; the rules themselves are
 // meshintersect_rules.h, the lines the CPU check compiles too.
 //   tris     per face: its one or two triangles (a,b,c), (a,c,d); a non-degenerate triangle stores its box in lattice cells and adds, for
 //            every grid level s = 0 .. 21, the grid cells of 2^s lattice cells that the box overlaps; a workgroup sums in LDS and sends one
@@ -25,14 +25,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "blocksum.h"
 #include "lattice_table.h"
+#include "meshedges.h"
 #include "meshintersect_rules.h"
-#include "meshsmooth.h"
 
 namespace sn {
 
 constexpr int MXI_NT = 256;
-constexpr int MXI_REC = 3;                                      // the build's position record: three int64
 constexpr int MXI_BIG = 64;                                     // a cell of more entries is walked by a whole workgroup
 constexpr unsigned long long MXI_CELLS_CAP = 1ull << 34;        // a triangle's cells at one level saturate here: far beyond any budget
 
@@ -63,38 +63,17 @@ struct MxiArgs {
     unsigned char *face_hit; int32_t *face_pairs; int32_t *pairs;
 };
 
-// dst[k] += the workgroup's sum of x[k] (every lane holds its own count): one atomic per count and workgroup. Every thread calls it.
-template <int N>
-__device__ __forceinline__ void mxi_block_add(unsigned long long *dst, const unsigned long long (&x)[N])
-{
-    __shared__ unsigned long long part[MXI_NT / 64][N];
-    const int t = threadIdx.x;
-    unsigned long long s[N];
-    for (int k = 0; k < N; ++k) {
-        s[k] = x[k];
-        for (int d = 32; d > 0; d >>= 1) s[k] += __shfl_xor(s[k], d, 64);
-    }
-    if ((t & 63) == 0)
-        for (int k = 0; k < N; ++k) part[t >> 6][k] = s[k];
-    __syncthreads();
-    if (t < N) {
-        unsigned long long sum = 0;
-        for (int w = 0; w < MXI_NT / 64; ++w) sum += part[w][t];
-        if (sum) atomicAdd(dst + t, sum);
-    }
-}
-
 // the indices and the quantised corners of triangle t: corners (0, h + 1, h + 2) of its face, h = its place in the face
-__device__ __forceinline__ void mxi_load_tri(const MsmArgs &a, const MxiArgs &b, unsigned t, int idx[3], long long q[3][3])
+__device__ __forceinline__ void mxi_load_tri(const MsmEdges &a, const MxiArgs &b, unsigned t, int idx[3], long long q[3][3])
 {
     const size_t f = t >> b.tshift;
     const int h = (int)(t & ((1u << b.tshift) - 1u));
     const int32_t *row = a.faces + (size_t)a.nv * f;
     idx[0] = row[0]; idx[1] = row[h + 1]; idx[2] = row[h + 2];
-    for (int k = 0; k < 3; ++k) msm_load<MXI_REC>(a.pos[0], (size_t)idx[k], q[k]);
+    for (int k = 0; k < 3; ++k) msm_load(a.pos, (size_t)idx[k], q[k]);
 }
 
-static __global__ void __launch_bounds__(MXI_NT) mxi_tris_kernel(MsmArgs a, MxiArgs b)
+static __global__ void __launch_bounds__(MXI_NT) mxi_tris_kernel(MsmEdges a, MxiArgs b)
 {
     __shared__ unsigned long long acc[MXI_LEVELS + 2];          // the level totals, the triangles, the degenerate faces
     const int t = threadIdx.x;
@@ -119,7 +98,7 @@ static __global__ void __launch_bounds__(MXI_NT) mxi_tris_kernel(MsmArgs a, MxiA
             if (ok) {
                 const int tri[3] = {idx[0], idx[h + 1], idx[h + 2]};
                 long long q[3][3];
-                for (int k = 0; k < 3; ++k) msm_load<MXI_REC>(a.pos[0], (size_t)tri[k], q[k]);
+                for (int k = 0; k < 3; ++k) msm_load(a.pos, (size_t)tri[k], q[k]);
                 live = !mxi_degenerate(tri, q[0], q[1], q[2]);
                 degenerate = degenerate || !live;
                 for (int d = 0; d < 3; ++d) {
@@ -177,7 +156,7 @@ static __global__ void __launch_bounds__(MXI_NT) mxi_cells_kernel(MxiArgs b)
 
 // Triangles ta, tb in the grid cell `cell` of level s: a candidate iff of different faces, the boxes overlap and the cell owns the pair;
 // then the exact test, and a hit's key.
-__device__ __forceinline__ void mxi_candidate(const MsmArgs &a, const MxiArgs &b, unsigned ta, unsigned tb, int s, const long long cell[3],
+__device__ __forceinline__ void mxi_candidate(const MsmEdges &a, const MxiArgs &b, unsigned ta, unsigned tb, int s, const long long cell[3],
                                               unsigned long long &candidates)
 {
     const unsigned fa = ta >> b.tshift, fb = tb >> b.tshift;
@@ -200,7 +179,7 @@ __device__ __forceinline__ void mxi_candidate(const MsmArgs &a, const MxiArgs &b
 }
 
 // Grid-stride over the entries: entry i of a small cell against the entries after it; the first entry of a big cell lists the cell.
-static __global__ void __launch_bounds__(MXI_NT) mxi_pairs_kernel(MsmArgs a, MxiArgs b)
+static __global__ void __launch_bounds__(MXI_NT) mxi_pairs_kernel(MsmEdges a, MxiArgs b)
 {
     const unsigned long long total = b.st->w[MXI_W_ENTRIES];
     const long long n_ent = total > (unsigned long long)b.ecap ? 0 : (long long)total;
@@ -223,12 +202,12 @@ static __global__ void __launch_bounds__(MXI_NT) mxi_pairs_kernel(MsmArgs a, Mxi
         const unsigned ta = b.ent[e];
         for (long long j = e + 1; j < first + n; ++j) mxi_candidate(a, b, ta, b.ent[j], s, cell, candidates);
     }
-    const unsigned long long sums[1] = {candidates};
-    mxi_block_add(&b.st->w[MXI_W_COUNTS + 2], sums);
+    const unsigned long long sums[1] = {wave_sum(candidates)};
+    block_add<MXI_NT>(&b.st->w[MXI_W_COUNTS + 2], sums);
 }
 
 // A workgroup per listed cell, grid-stride over the list: row i of the cell's pairs, the lanes along it.
-static __global__ void __launch_bounds__(MXI_NT) mxi_pairs_big_kernel(MsmArgs a, MxiArgs b)
+static __global__ void __launch_bounds__(MXI_NT) mxi_pairs_big_kernel(MsmEdges a, MxiArgs b)
 {
     const unsigned long long listed = b.st->w[MXI_W_BIG];
     const long long n_big = listed > (unsigned long long)b.bcap ? b.bcap : (long long)listed;
@@ -245,8 +224,8 @@ static __global__ void __launch_bounds__(MXI_NT) mxi_pairs_big_kernel(MsmArgs a,
             for (int j = i + 1 + (int)threadIdx.x; j < n; j += MXI_NT) mxi_candidate(a, b, ta, b.ent[first + j], s, cell, candidates);
         }
     }
-    const unsigned long long sums[1] = {candidates};
-    mxi_block_add(&b.st->w[MXI_W_COUNTS + 2], sums);
+    const unsigned long long sums[1] = {wave_sum(candidates)};
+    block_add<MXI_NT>(&b.st->w[MXI_W_COUNTS + 2], sums);
 }
 
 // is sorted key i the first of its face pair?
@@ -270,17 +249,18 @@ static __global__ void __launch_bounds__(MXI_NT) mxi_count_kernel(MxiArgs b)
         atomicAdd(b.fpairs + mxi_key_f(key), 1u);
         atomicAdd(b.fpairs + mxi_key_g(key), 1u);
     }
-    const unsigned long long p[1] = {pairs}, k[2] = {disjoint, pairs - disjoint};
-    mxi_block_add(&b.st->w[MXI_W_COUNTS + 3], p);
+    const unsigned long long p[1] = {wave_sum(pairs)};
+    block_add<MXI_NT>(&b.st->w[MXI_W_COUNTS + 3], p);
     __syncthreads();                                            // (the helper's LDS is used twice)
-    mxi_block_add(&b.st->w[MXI_W_COUNTS + 5], k);
+    const unsigned long long k[2] = {wave_sum(disjoint), wave_sum(pairs - disjoint)};
+    block_add<MXI_NT>(&b.st->w[MXI_W_COUNTS + 5], k);
 }
 
 static __global__ void __launch_bounds__(MXI_NT) mxi_faces_kernel(MxiArgs b, long long F)
 {
     const long long f = (long long)blockIdx.x * MXI_NT + threadIdx.x;
-    const unsigned long long hit[1] = {f < F && b.fpairs[f] ? 1ull : 0ull};
-    mxi_block_add(&b.st->w[MXI_W_COUNTS + 4], hit);
+    const unsigned long long hit[1] = {wave_sum(f < F && b.fpairs[f] ? 1ull : 0ull)};
+    block_add<MXI_NT>(&b.st->w[MXI_W_COUNTS + 4], hit);
 }
 
 static __global__ void __launch_bounds__(MXI_NT) mxi_emit_pairs_kernel(MxiArgs b)

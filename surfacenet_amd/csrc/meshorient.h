@@ -1,7 +1,7 @@
 // meshorient.h — the orientation of a triangle or quad mesh: faces made to turn one way piece by piece, the sign of every piece, the pieces
 // themselves with their face counts, closedness and exact volumes, and the removal of small pieces. DESIGN.md section 4.21 states the
-// contract; tests/meshorient_ref.py restates it in numpy. The kernels run after the smoother's build (meshsmooth_build.h: mark, quantise,
-// edges, degree) on its edge table, its side counts and its quantised positions.
+// contract; tests/meshorient_ref.py restates it in numpy. The kernels run after the build of the edge table (meshedges.h: mark, quantise,
+// edges, degree) on the table, its side counts and its quantised positions.
 //   sides    per face: both nodes of its double cover become their own parents; every side with distinct ends finds its edge's slot
 //            (lt_find) and, on a slot of two sides, sends its code (meshorient_rules.h) to the slot's two words with atomicMin / atomicMax
 //   links    per slot (grid-stride): a slot of two sides of two different faces f < g is a link, r = its two direction bits are equal; the
@@ -24,15 +24,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "blocksum.h"
+#include "meshedges.h"
 #include "meshnormals.h"
 #include "meshorient_rules.h"
-#include "meshsmooth.h"
 #include "unionfind.h"
 
 namespace sn {
 
 constexpr int MOR_NT = 256;
-constexpr int MOR_REC = 3;                                      // the build's position record: three int64
 constexpr unsigned MOR_R_OPEN = 1, MOR_R_NONOR = 2;             // bits of a piece's record while it is summed
 
 // What the host reads once, after the keep kernel and before any output is touched: 136 bytes.
@@ -59,7 +59,7 @@ struct MorArgs {
 };
 
 // the corners of face f, or false: a face the build refused (an index outside [0, V), a referenced coordinate out of range)
-__device__ __forceinline__ bool mor_corners(const MsmArgs &a, long long f, int idx[4])
+__device__ __forceinline__ bool mor_corners(const MsmEdges &a, long long f, int idx[4])
 {
     bool ok = true;
     for (int k = 0; k < a.nv; ++k) {
@@ -72,32 +72,7 @@ __device__ __forceinline__ bool mor_corners(const MsmArgs &a, long long f, int i
     return ok;
 }
 
-// the sum of x over the wave's lanes, in every lane
-__device__ __forceinline__ unsigned long long mor_wave_sum(unsigned long long x)
-{
-    for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d, 64);
-    return x;
-}
-
-// dst[k] += the workgroup's sum of x[k], the counts its waves kept in registers (every lane of a wave holds its wave's): one atomic per
-// count and workgroup, sent by N neighbouring lanes at once. One atomic per count and WAVE puts 8192 of them on one address in every
-// grid-stride kernel here, about 10 ns each (profiles/meshorient/). Every thread of the workgroup calls it.
-template <int N>
-__device__ __forceinline__ void mor_block_add(unsigned long long *dst, const unsigned long long (&x)[N])
-{
-    __shared__ unsigned long long part[MOR_NT / 64][N];
-    const int t = threadIdx.x;
-    if ((t & 63) == 0)
-        for (int k = 0; k < N; ++k) part[t >> 6][k] = x[k];
-    __syncthreads();
-    if (t < N) {
-        unsigned long long sum = 0;
-        for (int w = 0; w < MOR_NT / 64; ++w) sum += part[w][t];
-        if (sum) atomicAdd(dst + t, sum);
-    }
-}
-
-static __global__ void __launch_bounds__(MOR_NT) mor_sides_kernel(MsmArgs a, MorArgs b)
+static __global__ void __launch_bounds__(MOR_NT) mor_sides_kernel(MsmEdges a, MorArgs b)
 {
     const long long f = (long long)blockIdx.x * MOR_NT + threadIdx.x;
     if (f >= a.F) return;
@@ -118,7 +93,7 @@ static __global__ void __launch_bounds__(MOR_NT) mor_sides_kernel(MsmArgs a, Mor
 }
 
 // Grid-stride over the slots, the bound the same for a whole wave: the ballots count for all of it.
-static __global__ void __launch_bounds__(MOR_NT) mor_links_kernel(MsmArgs a, MorArgs b)
+static __global__ void __launch_bounds__(MOR_NT) mor_links_kernel(MsmEdges a, MorArgs b)
 {
     const unsigned long long stride = (unsigned long long)gridDim.x * MOR_NT;
     const unsigned lane = threadIdx.x & 63;
@@ -143,11 +118,11 @@ static __global__ void __launch_bounds__(MOR_NT) mor_links_kernel(MsmArgs a, Mor
         bad += (unsigned long long)__popcll(__ballot(link && r));
     }
     const unsigned long long sums[2] = {links, bad};
-    mor_block_add(&b.st->counts[0], sums);
+    block_add<MOR_NT>(&b.st->counts[0], sums);
 }
 
 // One face per lane. red: per lane the three limbs, the reversed faces, the record bits and the faces of the workgroup's tree.
-static __global__ void __launch_bounds__(MOR_NT) mor_faces_kernel(MsmArgs a, MorArgs b)
+static __global__ void __launch_bounds__(MOR_NT) mor_faces_kernel(MsmEdges a, MorArgs b)
 {
     __shared__ unsigned long long red[MOR_NT][6];
     __shared__ unsigned first, differ;
@@ -165,7 +140,7 @@ static __global__ void __launch_bounds__(MOR_NT) mor_faces_kernel(MsmArgs a, Mor
         int idx[4];
         if (mor_corners(a, f, idx)) {
             long long q[4][3];
-            for (int k = 0; k < a.nv; ++k) msm_load<MOR_REC>(a.pos[0], (size_t)idx[k], q[k]);
+            for (int k = 0; k < a.nv; ++k) msm_load(a.pos, (size_t)idx[k], q[k]);
             mnr_i128 six = mnr_triple(q[0], q[1], q[2]);
             if (a.nv == 4) six += mnr_triple(q[0], q[2], q[3]);
             vol = mnr_limbs_of(rel ? -six : six);               // rule 5: s = -1 iff rel
@@ -208,7 +183,7 @@ static __global__ void __launch_bounds__(MOR_NT) mor_faces_kernel(MsmArgs a, Mor
 }
 
 // Grid-stride over the face indices, a piece's id among them: root(2c) = 2c. After the faces kernel a piece's record is its root's own.
-static __global__ void __launch_bounds__(MOR_NT) mor_pieces_kernel(MsmArgs a, MorArgs b)
+static __global__ void __launch_bounds__(MOR_NT) mor_pieces_kernel(MsmEdges a, MorArgs b)
 {
     const long long stride = (long long)gridDim.x * MOR_NT;
     const int lane = threadIdx.x & 63;
@@ -237,11 +212,11 @@ static __global__ void __launch_bounds__(MOR_NT) mor_pieces_kernel(MsmArgs a, Mo
         closed += (unsigned long long)__popcll(__ballot(shut));
         turned += (unsigned long long)__popcll(__ballot(flipc));
     }
-    const unsigned long long sums[5] = {pieces, nonor, closed, mor_wave_sum(turned_faces), turned};
-    mor_block_add(&b.st->counts[2], sums);
+    const unsigned long long sums[5] = {pieces, nonor, closed, wave_sum(turned_faces), turned};
+    block_add<MOR_NT>(&b.st->counts[2], sums);
 }
 
-static __global__ void __launch_bounds__(MOR_NT) mor_keep_kernel(MsmArgs a, MorArgs b)
+static __global__ void __launch_bounds__(MOR_NT) mor_keep_kernel(MsmEdges a, MorArgs b)
 {
     const long long stride = (long long)gridDim.x * MOR_NT;
     const int lane = threadIdx.x & 63;
@@ -257,11 +232,11 @@ static __global__ void __launch_bounds__(MOR_NT) mor_keep_kernel(MsmArgs a, MorA
         }
         kept += (unsigned long long)__popcll(__ballot(keep));
     }
-    const unsigned long long sums[2] = {mor_wave_sum(kept_faces), kept};
-    mor_block_add(&b.st->counts[7], sums);
+    const unsigned long long sums[2] = {wave_sum(kept_faces), kept};
+    block_add<MOR_NT>(&b.st->counts[7], sums);
 }
 
-static __global__ void __launch_bounds__(MOR_NT) mor_emit_kernel(MsmArgs a, MorArgs b)
+static __global__ void __launch_bounds__(MOR_NT) mor_emit_kernel(MsmEdges a, MorArgs b)
 {
     const long long f = (long long)blockIdx.x * MOR_NT + threadIdx.x;
     if (f >= a.F) return;

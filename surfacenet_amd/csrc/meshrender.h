@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "blocksum.h"
 #include "cvc_warp.h"
 #include "mesh_input.h"
 #include "meshrender_rules.h"
@@ -65,30 +66,6 @@ struct MrdArgs {
     // the current view's outputs (each optional)
     double *depth; int32_t *face; int32_t *face_pixels; unsigned char *vis;
 };
-
-// the sum of x over the wave's lanes, in every lane
-__device__ __forceinline__ unsigned long long mrd_wave_sum(unsigned long long x)
-{
-    for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d, 64);
-    return x;
-}
-
-// dst[k] += the workgroup's sum of x[k], every lane of a wave holding its wave's sums: one atomic per count and workgroup. Every thread of
-// the workgroup calls it.
-template <int N>
-__device__ __forceinline__ void mrd_block_add(unsigned long long *dst, const unsigned long long (&x)[N])
-{
-    __shared__ unsigned long long part[MRD_NT / 64][N];
-    const int t = threadIdx.x;
-    if ((t & 63) == 0)
-        for (int k = 0; k < N; ++k) part[t >> 6][k] = x[k];
-    __syncthreads();
-    if (t < N) {
-        unsigned long long sum = 0;
-        for (int w = 0; w < MRD_NT / 64; ++w) sum += part[w][t];
-        if (sum) atomicAdd(dst + t, sum);
-    }
-}
 
 static __global__ void __launch_bounds__(MRD_NT) mrd_check_kernel(MrdArgs a, const double *P_all, int n_p)
 {
@@ -192,7 +169,7 @@ static __global__ void __launch_bounds__(MRD_NT) mrd_setup_kernel(MrdArgs a)
     }
     const unsigned long long sums[4] = {(unsigned long long)__popcll(__ballot(live)), (unsigned long long)__popcll(__ballot(status == 1)),
                                         (unsigned long long)__popcll(__ballot(status == 2)), (unsigned long long)__popcll(__ballot(status == 0))};
-    mrd_block_add(&a.st->counts[0], sums);
+    block_add<MRD_NT>(&a.st->counts[0], sums);
 }
 
 // One sample with its three signed edge values. PASS 1: the depth; PASS 2: the id where the depth is the pixel's.
@@ -227,14 +204,14 @@ static __global__ void __launch_bounds__(MRD_NT) mrd_raster_small_kernel(MrdArgs
         }
     }
     if (PASS == 1) {
-        const unsigned long long sums[1] = {mrd_wave_sum(pairs)};
-        mrd_block_add(&a.st->counts[4], sums);
+        const unsigned long long sums[1] = {wave_sum(pairs)};
+        block_add<MRD_NT>(&a.st->counts[4], sums);
     }
 }
 
 // A workgroup per chunk, grid-stride over the view's chunks: the chunk's triangle is the last entry of the list whose first chunk is not
 // above it (bisection, at most 32 steps), its pixels the chunk's share of the box in row-major order. Every thread of a workgroup walks the
-// same chunks, so the barriers inside mrd_block_add are reached by all.
+// same chunks, so the barriers inside block_add are reached by all.
 template <int PASS>
 static __global__ void __launch_bounds__(MRD_NT) mrd_raster_big_kernel(MrdArgs a)
 {
@@ -260,8 +237,8 @@ static __global__ void __launch_bounds__(MRD_NT) mrd_raster_big_kernel(MrdArgs a
         }
     }
     if (PASS == 1) {
-        const unsigned long long sums[1] = {mrd_wave_sum(pairs)};
-        mrd_block_add(&a.st->counts[4], sums);
+        const unsigned long long sums[1] = {wave_sum(pairs)};
+        block_add<MRD_NT>(&a.st->counts[4], sums);
     }
 }
 
@@ -312,7 +289,7 @@ static __global__ void __launch_bounds__(MRD_NT) mrd_resolve_kernel(MrdArgs a, i
                 left &= ~same;
             }
         }
-    hits = mrd_wave_sum(hits);
+    hits = wave_sum(hits);
     if (lane == 0) { part[tid >> 6] = hits; kept_face[tid >> 6] = pf; kept_count[tid >> 6] = pc; }
     __syncthreads();
     if (tid == 0) {
@@ -353,7 +330,7 @@ static __global__ void __launch_bounds__(MRD_NT) mrd_visible_kernel(MrdArgs a)
         if (a.vis) a.vis[v] = seen ? 1 : 0;
     }
     const unsigned long long sums[1] = {(unsigned long long)__popcll(__ballot(seen))};
-    mrd_block_add(&a.st->counts[6], sums);
+    block_add<MRD_NT>(&a.st->counts[6], sums);
 }
 
 struct MrdColorArgs {
@@ -387,8 +364,8 @@ static __global__ void __launch_bounds__(MRD_NT) mrd_colors_kernel(MrdColorArgs 
         if (a.rgb)
             for (int ch = 0; ch < 3; ++ch) a.rgb[3 * i + ch] = n ? (unsigned char)mrd_mean(sum[ch], n) : 0;
     }
-    const unsigned long long sums[2] = {(unsigned long long)__popcll(__ballot(n > 0)), mrd_wave_sum(n)};
-    mrd_block_add(a.counts, sums);
+    const unsigned long long sums[2] = {(unsigned long long)__popcll(__ballot(n > 0)), wave_sum(n)};
+    block_add<MRD_NT>(a.counts, sums);
 }
 
 }  // namespace sn

@@ -1,9 +1,8 @@
 // sn_meshfill.hip — C ABI of the hole filler (meshfill.h). The device form works on the caller's device arrays; the host
-// form is the same computation on the host mirror's device copies of its arrays (sn_internal.h HostMirror). The edge table is the smoother's,
-// built by the sequence the smoother runs (meshsmooth_build.h); everything after it is plain launches on the context's stream.
-#include "sn_internal.h"
+// form is the same computation on the host mirror's device copies of its arrays (sn_internal.h HostMirror). The edge table and the
+// sequence around it are sn_meshedges.h's (MsmStage); everything after the build is plain launches on the context's stream.
+#include "sn_meshedges.h"
 #include "meshfill.h"
-#include "meshsmooth_build.h"
 #include "scan.h"
 
 namespace {
@@ -17,25 +16,17 @@ int mfl_check(sn_ctx *c, const sn_mesh_fill_cfg *cfg, int n_verts, int n_faces, 
     return rc != SN_OK ? rc : mfl_check_args(cfg, n_verts, n_faces, nv, cap_verts, cap_faces);
 }
 
-// What both forms do once their arguments are checked, F > 0.
+// What both forms do once their arguments are checked.
 int mfl_run(sn_ctx *c, bool host, const sn_mesh_fill_cfg *cfg, int V, const double *verts, int F, int nv, const int32_t *faces, long long cap_verts,
             long long cap_faces, MflOut d, long long *counts)
 {
-    HostMirror m(c, host);
-    int rc = m.inputs([&](Carve &w) { m.in(w, verts, 3 * (size_t)V); m.in(w, faces, (size_t)nv * (size_t)F); });
-    if (rc != SN_OK) return rc;
-    const size_t cap = msm_table_cap(F, nv);
-    MsmArgs a;
-    msm_set_inputs(a, V, verts, F, nv, faces, cfg->origin, cfg->resol, cap);
+    MsmStage s(c, host);
     MflArgs b;
     memset(&b, 0, sizeof b);
     b.max_len = cfg->max_len; b.orientation = cfg->orientation;
     int *sums = nullptr;
     const size_t n = (size_t)V;
-    auto layout = [&](Carve &w) {
-        b.st = w.get<MflStat>(1);
-        a.st = b.st ? &b.st->msm : nullptr;                     // the build writes into the head of the one block the host reads
-        msm_carve_build<MFL_REC>(w, a, cap);
+    int rc = s.build(c->mfl_ws, V, verts, F, nv, faces, cfg->origin, cfg->resol, b.st, [&](Carve &w) {
         b.parent = w.get<unsigned>(n);
         b.out = w.get<int>(n);
         b.in = w.get<int>(n);
@@ -52,12 +43,11 @@ int mfl_run(sn_ctx *c, bool host, const sn_mesh_fill_cfg *cfg, int V, const doub
         b.tflag = w.get<int>(n + 1);
         b.tpos = w.get<int>(n + 1);
         sums = w.get<int>(scan_sums(n + 1));
-    };
-    if ((rc = dev_carve(c, c->mfl_ws, layout, 256)) != SN_OK) return rc;
+    });
+    if (rc != SN_OK || s.empty) return rc;                      // no face: all counts 0, nothing written
+    const MsmEdges &a = s.e;
+    HostMirror &m = s.m;
     const unsigned vb = blocks(V, MFL_NT), vb1 = blocks((long long)V + 1, MFL_NT), fb = blocks(F, MFL_NT);
-    const unsigned loop_blocks = (unsigned)std::max(c->num_cus, 1) * 8u;      // the grid-stride kernel: eight workgroups per CU at most
-    HIPCHK(dev_fill(c, b.st, 0, 1));
-    if ((rc = msm_build<MFL_REC>(c, a, cap)) != SN_OK) return rc;
     if (V > 0) {
         {
             ProfScope ps(c, "mfl_halfedge", 0, (double)F * nv * 24.0 + (double)V * 28.0);
@@ -81,7 +71,7 @@ int mfl_run(sn_ctx *c, bool host, const sn_mesh_fill_cfg *cfg, int V, const doub
     }
     {
         ProfScope ps(c, "mfl_place", 0, (double)V * 40.0);
-        LAUNCH(mfl_classify_kernel, dim3(std::min(vb1, loop_blocks)), dim3(MFL_NT), a, b);
+        LAUNCH(mfl_classify_kernel, dim3(std::min(vb1, loop_blocks(c))), dim3(MFL_NT), a, b);
         LAUNCH(mfl_flag_kernel, dim3(vb1), dim3(MFL_NT), a, b);
         if ((rc = scan_exclusive(c, b.hflag, b.hpos, V + 1, sums)) != SN_OK) return rc;      // hpos[V] = H
         if ((rc = scan_exclusive(c, b.tflag, b.tpos, V + 1, sums)) != SN_OK) return rc;      // tpos[V] = T
@@ -89,8 +79,7 @@ int mfl_run(sn_ctx *c, bool host, const sn_mesh_fill_cfg *cfg, int V, const doub
     }
     // the one read before any output is touched: the first bad face, the edge limit, the counts, then the caps
     MflStat st;
-    HIPCHK(read_status(c, &st, b.st));
-    if ((rc = msm_report(st.msm, V, false)) != SN_OK) return rc;
+    if ((rc = s.status(&st, b.st)) != SN_OK) return rc;
     for (int k = 0; k < 8; ++k) counts[k] = (long long)st.counts[k];
     const size_t H = (size_t)st.counts[3], T = (size_t)st.counts[7];
     if ((long long)H > cap_verts || (long long)T > cap_faces)
@@ -109,15 +98,6 @@ int mfl_run(sn_ctx *c, bool host, const sn_mesh_fill_cfg *cfg, int V, const doub
     return m.finish();
 }
 
-int mfl_dispatch(sn_ctx *c, bool host, const sn_mesh_fill_cfg *cfg, int V, const double *verts, int F, int nv, const int32_t *faces,
-                 long long cap_verts, long long cap_faces, MflOut d, long long *counts)
-{
-    if (F == 0) return SN_OK;                                   // no face: all counts 0, nothing written
-    if (!faces || (V > 0 && !verts)) return fail(SN_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(c->device));
-    return mfl_run(c, host, cfg, V, verts, F, nv, faces, cap_verts, cap_faces, d, counts);
-}
-
 }  // namespace
 
 extern "C" int sn_mesh_fill_dev(sn_ctx *c, const sn_mesh_fill_cfg *cfg, int n_verts, const double *verts_dev, int n_faces, int nv,
@@ -128,7 +108,7 @@ extern "C" int sn_mesh_fill_dev(sn_ctx *c, const sn_mesh_fill_cfg *cfg, int n_ve
     int rc;
     if ((rc = mfl_check(c, cfg, n_verts, n_faces, nv, cap_verts, cap_faces, counts)) != SN_OK) return rc;
     const MflOut o = {new_verts_mm_dev, new_verts_lattice_dev, loop_root_dev, loop_len_dev, new_faces_dev, vert_loop_dev};
-    return mfl_dispatch(c, false, cfg, n_verts, verts_dev, n_faces, nv, faces_dev, cap_verts, cap_faces, o, counts);
+    return mfl_run(c, false, cfg, n_verts, verts_dev, n_faces, nv, faces_dev, cap_verts, cap_faces, o, counts);
 }
 
 extern "C" int sn_mesh_fill(sn_ctx *c, const sn_mesh_fill_cfg *cfg, int n_verts, const double *verts, int n_faces, int nv, const int32_t *faces,
@@ -138,5 +118,5 @@ extern "C" int sn_mesh_fill(sn_ctx *c, const sn_mesh_fill_cfg *cfg, int n_verts,
     int rc;
     if ((rc = mfl_check(c, cfg, n_verts, n_faces, nv, cap_verts, cap_faces, counts)) != SN_OK) return rc;
     const MflOut o = {new_verts_mm, new_verts_lattice, loop_root, loop_len, new_faces, vert_loop};
-    return mfl_dispatch(c, true, cfg, n_verts, verts, n_faces, nv, faces, cap_verts, cap_faces, o, counts);
+    return mfl_run(c, true, cfg, n_verts, verts, n_faces, nv, faces, cap_verts, cap_faces, o, counts);
 }

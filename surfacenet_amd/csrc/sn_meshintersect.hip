@@ -1,12 +1,11 @@
 // sn_meshintersect.hip — C ABI of the mesh self-intersection stage (meshintersect.h). The device form works on the
 // caller's device arrays; the host form is the same computation on the host mirror's device copies of its arrays (sn_internal.h HostMirror).
-// The quantised positions are the smoother's, built by the sequence the smoother runs (meshsmooth_build.h); everything after it is plain
+// The quantised positions are the edge table's, and the sequence around its build is sn_meshedges.h's (MsmStage); everything after it is plain
 // launches on the context's stream. The host reads the status block once before any output is touched - the first bad face, the hits - and,
 // when something was hit, the counts once more after the sort; a clean mesh costs the one read.
-#include "sn_internal.h"
+#include "sn_meshedges.h"
 #include "bitonic.h"
 #include "meshintersect.h"
-#include "meshsmooth_build.h"
 #include "scan.h"
 
 namespace {
@@ -32,27 +31,24 @@ int mxi_switch(const char *name, int lo, int hi, int none)
 }
 
 // the broad phase's narrow half: the candidates of every cell, tested exactly; the hits' keys as far as the list goes
-int mxi_pairs(sn_ctx *c, const MsmArgs &a, const MxiArgs &b, unsigned loop_blocks)
+int mxi_pairs(sn_ctx *c, const MsmEdges &a, const MxiArgs &b)
 {
+    const unsigned lb = loop_blocks(c);
     ProfScope ps(c, "mxi_pairs", 0, (double)b.ecap * 8.0 + (double)b.n_tris * (24.0 + 12.0 + 72.0));
     HIPCHK(dev_fill(c, &b.st->w[MXI_W_COUNTS + 2], 0, 1));
     HIPCHK(dev_fill(c, &b.st->w[MXI_W_KEYS], 0, 2));           // the hits, the listed cells
-    LAUNCH(mxi_pairs_kernel, dim3(std::min(blocks(b.ecap, MXI_NT), loop_blocks)), dim3(MXI_NT), a, b);
-    LAUNCH(mxi_pairs_big_kernel, dim3(loop_blocks), dim3(MXI_NT), a, b);
+    LAUNCH(mxi_pairs_kernel, dim3(std::min(blocks(b.ecap, MXI_NT), lb)), dim3(MXI_NT), a, b);
+    LAUNCH(mxi_pairs_big_kernel, dim3(lb), dim3(MXI_NT), a, b);
     return SN_OK;
 }
 
-// What both forms do once their arguments are checked, F > 0.
+// What both forms do once their arguments are checked.
 int mxi_run(sn_ctx *c, bool host, const sn_mesh_intersect_cfg *cfg, int V, const double *verts, int F, int nv, const int32_t *faces, MxiOut d,
             long long *counts)
 {
-    HostMirror m(c, host);
-    int rc = m.inputs([&](Carve &w) { m.in(w, verts, 3 * (size_t)V); m.in(w, faces, (size_t)nv * (size_t)F); });
-    if (rc != SN_OK) return rc;
-    const size_t cap = msm_table_cap(F, nv), n = (size_t)F;
+    MsmStage s(c, host);
+    const size_t n = (size_t)F;
     const double origin[3] = {0.0, 0.0, 0.0};
-    MsmArgs a;
-    msm_set_inputs(a, V, verts, F, nv, faces, origin, 1.0, cap);
     MxiArgs b;
     memset(&b, 0, sizeof b);
     b.tshift = nv - 3;
@@ -63,18 +59,14 @@ int mxi_run(sn_ctx *c, bool host, const sn_mesh_intersect_cfg *cfg, int V, const
     b.force_level = mxi_switch("SN_MXI_LEVEL", 0, MXI_LEVELS - 1, -1);
     b.budget = mxi_switch("SN_MXI_BUDGET", 1, 64, 8);
     b.ecap = std::max(b.budget, 8) * b.n_tris;                  // (level 21: at most 8 cells per triangle)
-    auto layout = [&](Carve &w) {
-        b.st = w.get<MxiStat>(1);
-        a.st = b.st ? &b.st->msm : nullptr;                     // the build writes into the head of the one block the host reads
-        msm_carve_build<MXI_REC>(w, a, cap);
+    int rc = s.build(c->mxi_ws, V, verts, F, nv, faces, origin, 1.0, b.st, [&](Carve &w) {
         b.box = w.get<int>(6 * (size_t)b.n_tris);
         b.fpairs = w.get<unsigned>(n);
-    };
-    if ((rc = dev_carve(c, c->mxi_ws, layout, 256)) != SN_OK) return rc;
+    });
+    if (rc != SN_OK || s.empty) return rc;                      // no face: all counts 0, nothing written
+    const MsmEdges &a = s.e;
+    HostMirror &m = s.m;
     const unsigned fb = blocks(F, MXI_NT), tb = blocks(b.n_tris, MXI_NT);
-    const unsigned loop_blocks = (unsigned)std::max(c->num_cus, 1) * 8u;      // the grid-stride kernels: eight workgroups per CU at most
-    HIPCHK(dev_fill(c, b.st, 0, 1));
-    if ((rc = msm_build<MXI_REC>(c, a, cap)) != SN_OK) return rc;
     {
         // per face: its indices and flags, its corners' records, a box per triangle
         ProfScope ps(c, "mxi_tris", 0, (double)F * nv * (4.0 + 4.0 + 24.0) + (double)b.n_tris * 24.0);
@@ -82,8 +74,7 @@ int mxi_run(sn_ctx *c, bool host, const sn_mesh_intersect_cfg *cfg, int V, const
     }
     MxiStat st;
     if (b.force_level >= 0) {                                   // (twin only) a forced level's entries are whatever they are: size by them
-        HIPCHK(read_status(c, &st, b.st));
-        if ((rc = msm_report(st.msm, V, false)) != SN_OK) return rc;
+        if ((rc = s.status(&st, b.st)) != SN_OK) return rc;
         const unsigned long long e = st.w[MXI_W_TOTALS + b.force_level];
         if (e > (1ull << 28)) return fail(SN_ERR_ARG, "SN_MXI_LEVEL = %d: %llu entries, at most 2^28", b.force_level, e);
         b.ecap = std::max<long long>(b.ecap, (long long)e);
@@ -124,16 +115,15 @@ int mxi_run(sn_ctx *c, bool host, const sn_mesh_intersect_cfg *cfg, int V, const
         if ((rc = scan_exclusive(c, b.count, b.start, (int)gcap, sums)) != SN_OK) return rc;
         LAUNCH(mxi_cells_kernel<true>, dim3(tb), dim3(MXI_NT), b);
     }
-    if ((rc = mxi_pairs(c, a, b, loop_blocks)) != SN_OK) return rc;
+    if ((rc = mxi_pairs(c, a, b)) != SN_OK) return rc;
     // the one read before any output is touched: the first bad face, the level and its entries, the hits
-    HIPCHK(read_status(c, &st, b.st));
-    if ((rc = msm_report(st.msm, V, false)) != SN_OK) return rc;
+    if ((rc = s.status(&st, b.st)) != SN_OK) return rc;
     if (st.w[MXI_W_ENTRIES] > (unsigned long long)b.ecap) return fail(SN_ERR_STATE, "%llu grid entries for room of %lld", st.w[MXI_W_ENTRIES], b.ecap);
     if ((long long)st.w[MXI_W_KEYS] >= MXI_MAX_KEYS) return fail(SN_ERR_ARG, "%llu intersecting triangle pairs: at most 2^30 - 1", st.w[MXI_W_KEYS]);
     if ((long long)st.w[MXI_W_KEYS] > b.kcap) {                 // count first, grow, walk again
         b.kcap = c->mxi_kcap = pow2((long long)st.w[MXI_W_KEYS]);
         if ((rc = dev_carve(c, c->mxi_keys, keys_layout)) != SN_OK) return rc;
-        if ((rc = mxi_pairs(c, a, b, loop_blocks)) != SN_OK) return rc;
+        if ((rc = mxi_pairs(c, a, b)) != SN_OK) return rc;
         HIPCHK(read_status(c, &st, b.st));
         if ((long long)st.w[MXI_W_KEYS] > b.kcap) return fail(SN_ERR_STATE, "the second walk hit %llu pairs, the first %lld", st.w[MXI_W_KEYS], b.kcap);
     }
@@ -172,15 +162,6 @@ int mxi_run(sn_ctx *c, bool host, const sn_mesh_intersect_cfg *cfg, int V, const
     return SN_OK;
 }
 
-int mxi_dispatch(sn_ctx *c, bool host, const sn_mesh_intersect_cfg *cfg, int V, const double *verts, int F, int nv, const int32_t *faces, MxiOut d,
-                 long long *counts)
-{
-    if (F == 0) return SN_OK;                                   // no face: all counts 0, nothing written
-    if (!faces || (V > 0 && !verts)) return fail(SN_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(c->device));
-    return mxi_run(c, host, cfg, V, verts, F, nv, faces, d, counts);
-}
-
 }  // namespace
 
 extern "C" int sn_mesh_intersect_dev(sn_ctx *c, const sn_mesh_intersect_cfg *cfg, int n_verts, const double *verts_dev, int n_faces, int nv,
@@ -190,7 +171,7 @@ extern "C" int sn_mesh_intersect_dev(sn_ctx *c, const sn_mesh_intersect_cfg *cfg
     int rc;
     if ((rc = mxi_check(c, cfg, n_verts, n_faces, nv, counts)) != SN_OK) return rc;
     const MxiOut o = {face_hit_dev, face_pairs_dev, pairs_dev};
-    return mxi_dispatch(c, false, cfg, n_verts, verts_dev, n_faces, nv, faces_dev, o, counts);
+    return mxi_run(c, false, cfg, n_verts, verts_dev, n_faces, nv, faces_dev, o, counts);
 }
 
 extern "C" int sn_mesh_intersect(sn_ctx *c, const sn_mesh_intersect_cfg *cfg, int n_verts, const double *verts, int n_faces, int nv,
@@ -199,5 +180,5 @@ extern "C" int sn_mesh_intersect(sn_ctx *c, const sn_mesh_intersect_cfg *cfg, in
     int rc;
     if ((rc = mxi_check(c, cfg, n_verts, n_faces, nv, counts)) != SN_OK) return rc;
     const MxiOut o = {face_hit, face_pairs, pairs};
-    return mxi_dispatch(c, true, cfg, n_verts, verts, n_faces, nv, faces, o, counts);
+    return mxi_run(c, true, cfg, n_verts, verts, n_faces, nv, faces, o, counts);
 }

@@ -33,7 +33,6 @@ int mnr_run(sn_ctx *c, bool host, int V, const double *verts, int F, int nv, con
         a.vn = w.get<float>(3 * (size_t)V);
     };
     if ((rc = dev_carve(c, c->mnr_ws, layout, 256)) != SN_OK) return rc;
-    const unsigned loop_blocks = (unsigned)std::max(c->num_cus, 1) * 8u;      // grid-stride kernels: eight workgroups per CU at most
     HIPCHK(dev_fill(c, a.st, 0, 1));
     HIPCHK(dev_fill(c, &a.st->first_bad, 0xff, 1));      // MESH_NO_BAD
     {
@@ -41,11 +40,11 @@ int mnr_run(sn_ctx *c, bool host, int V, const double *verts, int F, int nv, con
         ProfScope ps(c, "mnr_faces", 0, (double)F * (nv * (4.0 + 24.0 + 48.0) + 12.0) + (double)V * 49.0);
         HIPCHK(dev_fill(c, a.ref, 0, std::max<size_t>((size_t)V, 1)));
         HIPCHK(dev_fill(c, a.acc, 0, 6 * std::max<size_t>((size_t)V, 1)));
-        LAUNCH(mnr_faces_kernel, dim3(std::min(blocks(F, MNR_NT), loop_blocks)), dim3(MNR_NT), a);
+        LAUNCH(mnr_faces_kernel, dim3(std::min(blocks(F, MNR_NT), loop_blocks(c))), dim3(MNR_NT), a);
     }
     if (V > 0) {
         ProfScope ps(c, "mnr_verts", 0, (double)V * (1.0 + 48.0 + 12.0));
-        LAUNCH(mnr_verts_kernel, dim3(std::min(blocks(V, MNR_NT), loop_blocks)), dim3(MNR_NT), a);
+        LAUNCH(mnr_verts_kernel, dim3(std::min(blocks(V, MNR_NT), loop_blocks(c))), dim3(MNR_NT), a);
     }
     // the one read, before any output is touched: the first bad face, the counts, the sums
     MnrStat st;

@@ -1,10 +1,9 @@
 // sn_meshorient.hip — C ABI of the mesh orientation stage (meshorient.h). The device form works on the caller's device
-// arrays; the host form is the same computation on the host mirror's device copies of its arrays (sn_internal.h HostMirror). The edge table is
-// the smoother's, built by the sequence the smoother runs (meshsmooth_build.h); everything after it is plain launches on the context's stream,
-// one read of the status block, then the kernel that writes the outputs.
-#include "sn_internal.h"
+// arrays; the host form is the same computation on the host mirror's device copies of its arrays (sn_internal.h HostMirror). The edge table
+// and the sequence around it are sn_meshedges.h's (MsmStage); everything after the build is plain launches on the context's stream, one read
+// of the status block, then the kernel that writes the outputs.
+#include "sn_meshedges.h"
 #include "meshorient.h"
-#include "meshsmooth_build.h"
 
 namespace {
 
@@ -20,17 +19,13 @@ int mor_check(sn_ctx *c, const sn_mesh_orient_cfg *cfg, int n_verts, int n_faces
     return rc != SN_OK ? rc : mor_check_args(cfg, n_verts, n_faces, nv);
 }
 
-// What both forms do once their arguments are checked, F > 0.
+// What both forms do once their arguments are checked.
 int mor_run(sn_ctx *c, bool host, const sn_mesh_orient_cfg *cfg, int V, const double *verts, int F, int nv, const int32_t *faces, MorOut d,
             long long *counts)
 {
-    HostMirror m(c, host);
-    int rc = m.inputs([&](Carve &w) { m.in(w, verts, 3 * (size_t)V); m.in(w, faces, (size_t)nv * (size_t)F); });
-    if (rc != SN_OK) return rc;
-    const size_t cap = msm_table_cap(F, nv), n = (size_t)F;
+    MsmStage s(c, host);
+    const size_t n = (size_t)F;
     const double origin[3] = {0.0, 0.0, 0.0};
-    MsmArgs a;
-    msm_set_inputs(a, V, verts, F, nv, faces, origin, 1.0, cap);
     MorArgs b;
     memset(&b, 0, sizeof b);
     b.sign = cfg->sign; b.min_faces = cfg->min_faces; b.keep_largest = cfg->keep_largest;
@@ -38,12 +33,9 @@ int mor_run(sn_ctx *c, bool host, const sn_mesh_orient_cfg *cfg, int V, const do
     // two on an MI355X (tools/bench_meshorient.py, profiles/meshorient/); the test-only twin reads SN_MOR_NO_REDUCE to send per lane for the
     // A/B. The results are the same bits.
     b.reduce = sn_ab_switch("SN_MOR_NO_REDUCE") ? 0 : 1;
-    auto layout = [&](Carve &w) {
-        b.st = w.get<MorStat>(1);
-        a.st = b.st ? &b.st->msm : nullptr;                     // the build writes into the head of the one block the host reads
-        msm_carve_build<MOR_REC>(w, a, cap);
-        b.slot_lo = w.get<unsigned>(cap);
-        b.slot_hi = w.get<unsigned>(cap);
+    int rc = s.build(c->mor_ws, V, verts, F, nv, faces, origin, 1.0, b.st, [&](Carve &w) {
+        b.slot_lo = w.get<unsigned>(s.cap());
+        b.slot_hi = w.get<unsigned>(s.cap());
         b.parent = w.get<unsigned>(2 * n);
         b.linked = w.get<unsigned>(n);
         b.root = w.get<unsigned>(n);
@@ -52,12 +44,12 @@ int mor_run(sn_ctx *c, bool host, const sn_mesh_orient_cfg *cfg, int V, const do
         b.rec_bits = w.get<unsigned>(n);
         b.rec_vol = w.get<unsigned long long>(3 * n);
         b.flags = w.get<unsigned char>(n);
-    };
-    if ((rc = dev_carve(c, c->mor_ws, layout, 256)) != SN_OK) return rc;
-    const unsigned fb = blocks(F, MOR_NT), sb = blocks((long long)cap, MOR_NT);
-    const unsigned loop_blocks = (unsigned)std::max(c->num_cus, 1) * 8u;      // the grid-stride kernels: eight workgroups per CU at most
-    HIPCHK(dev_fill(c, b.st, 0, 1));
-    if ((rc = msm_build<MOR_REC>(c, a, cap)) != SN_OK) return rc;
+    });
+    if (rc != SN_OK || s.empty) return rc;                      // no face: all counts 0, nothing written
+    const MsmEdges &a = s.e;
+    HostMirror &m = s.m;
+    const size_t cap = s.cap();
+    const unsigned fb = blocks(F, MOR_NT), sb = blocks((long long)cap, MOR_NT), lb = loop_blocks(c);
     {
         // per side: its face's indices, a probe, the slot's count, two atomics
         ProfScope ps(c, "mor_sides", 0, (double)F * (nv * (4.0 + 4.0 + 16.0 + 4.0 + 8.0) + 8.0) + (double)cap * 8.0);
@@ -68,7 +60,7 @@ int mor_run(sn_ctx *c, bool host, const sn_mesh_orient_cfg *cfg, int V, const do
     {
         ProfScope ps(c, "mor_links", 0, (double)cap * 20.0 + (double)F * nv * 0.5 * (8.0 + 32.0) + (double)F * 4.0);
         HIPCHK(dev_fill(c, b.linked, 0, n));
-        LAUNCH(mor_links_kernel, dim3(std::min(sb, loop_blocks)), dim3(MOR_NT), a, b);
+        LAUNCH(mor_links_kernel, dim3(std::min(sb, lb)), dim3(MOR_NT), a, b);
     }
     {
         // per face: two walks to the root, its indices, its corners' records, the piece's record
@@ -81,13 +73,12 @@ int mor_run(sn_ctx *c, bool host, const sn_mesh_orient_cfg *cfg, int V, const do
     }
     {
         ProfScope ps(c, "mor_pieces", 0, (double)F * 8.0);
-        LAUNCH(mor_pieces_kernel, dim3(std::min(fb, loop_blocks)), dim3(MOR_NT), a, b);
-        LAUNCH(mor_keep_kernel, dim3(std::min(fb, loop_blocks)), dim3(MOR_NT), a, b);
+        LAUNCH(mor_pieces_kernel, dim3(std::min(fb, lb)), dim3(MOR_NT), a, b);
+        LAUNCH(mor_keep_kernel, dim3(std::min(fb, lb)), dim3(MOR_NT), a, b);
     }
     // the one read, before any output is touched: the first bad face, the edge limit, the counts
     MorStat st;
-    HIPCHK(read_status(c, &st, b.st));
-    if ((rc = msm_report(st.msm, V, false)) != SN_OK) return rc;
+    if ((rc = s.status(&st, b.st)) != SN_OK) return rc;
     rc = m.outputs([&](Carve &w) {
         m.out(w, d.faces_out, (size_t)nv * n); m.out(w, d.face_flip, n); m.out(w, d.face_component, n); m.out(w, d.face_keep, n);
         m.out(w, d.comp_faces, n); m.out(w, d.comp_flags, n); m.out(w, d.comp_vol6, 3 * n);
@@ -105,15 +96,6 @@ int mor_run(sn_ctx *c, bool host, const sn_mesh_orient_cfg *cfg, int V, const do
     return SN_OK;
 }
 
-int mor_dispatch(sn_ctx *c, bool host, const sn_mesh_orient_cfg *cfg, int V, const double *verts, int F, int nv, const int32_t *faces, MorOut d,
-                 long long *counts)
-{
-    if (F == 0) return SN_OK;                                   // no face: all counts 0, nothing written
-    if (!faces || (V > 0 && !verts)) return fail(SN_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(c->device));
-    return mor_run(c, host, cfg, V, verts, F, nv, faces, d, counts);
-}
-
 }  // namespace
 
 extern "C" int sn_mesh_orient_dev(sn_ctx *c, const sn_mesh_orient_cfg *cfg, int n_verts, const double *verts_dev, int n_faces, int nv,
@@ -124,7 +106,7 @@ extern "C" int sn_mesh_orient_dev(sn_ctx *c, const sn_mesh_orient_cfg *cfg, int 
     int rc;
     if ((rc = mor_check(c, cfg, n_verts, n_faces, nv, counts)) != SN_OK) return rc;
     const MorOut o = {faces_out_dev, face_flip_dev, face_component_dev, face_keep_dev, comp_faces_dev, comp_flags_dev, comp_vol6_dev};
-    return mor_dispatch(c, false, cfg, n_verts, verts_dev, n_faces, nv, faces_dev, o, counts);
+    return mor_run(c, false, cfg, n_verts, verts_dev, n_faces, nv, faces_dev, o, counts);
 }
 
 extern "C" int sn_mesh_orient(sn_ctx *c, const sn_mesh_orient_cfg *cfg, int n_verts, const double *verts, int n_faces, int nv, const int32_t *faces,
@@ -134,5 +116,5 @@ extern "C" int sn_mesh_orient(sn_ctx *c, const sn_mesh_orient_cfg *cfg, int n_ve
     int rc;
     if ((rc = mor_check(c, cfg, n_verts, n_faces, nv, counts)) != SN_OK) return rc;
     const MorOut o = {faces_out, face_flip, face_component, face_keep, comp_faces, comp_flags, comp_vol6};
-    return mor_dispatch(c, true, cfg, n_verts, verts, n_faces, nv, faces, o, counts);
+    return mor_run(c, true, cfg, n_verts, verts, n_faces, nv, faces, o, counts);
 }

@@ -83,7 +83,7 @@ int mrd_render(sn_ctx *c, bool host, const sn_mesh_render_cfg *cfg, int n_verts,
     // a big triangle's box is walked in chunks; every triangle of a view may be big and fill the image: the chunks of all of them fit 31 bits
     a.chunk_px = MRD_CHUNK_PX;
     while ((unsigned long long)(T + 1) * (npix / (size_t)a.chunk_px + 1) >= (1ull << 31)) a.chunk_px *= 2;
-    const dim3 big_grid((unsigned)std::max(c->num_cus, 1) * 8u);      // grid-stride over the view's chunks: eight workgroups per CU at most
+    const dim3 big_grid(loop_blocks(c));                        // grid-stride over the view's chunks
     for (int v = 0; v < V; ++v) {
         a.P = cams + 12 * (size_t)v;
         a.depth = host ? s.depth : (o.depth ? o.depth + (size_t)v * npix : nullptr);

@@ -1,6 +1,6 @@
 """Times the mesh smoother at DTU scale, next to sn_mesh on the same scene in the same run.
 
-    python tools/bench_meshsmooth.py [--out profiles/meshsmooth/bench_meshsmooth.json] [--reps 5] [--iterations 10] [--no-ab]
+    python tools/bench_meshsmooth.py [--out profiles/meshsmooth/bench_meshsmooth.json] [--reps 5] [--iterations 10]
 
 Scene: the "dtu" scene of tools/bench_postpass.py as tools/bench_meshsimplify.py sets it up, meshed by sn_mesh; the smoother runs on its quads
 and on their triangulation. Before anything is reported the GPU result (3 iterations, curve mode) is compared with the restatement
@@ -13,14 +13,11 @@ and on their triangulation. Before anything is reported the GPU result (3 iterat
                           and one row word; pass_GBps = that over pass_ms, pass_share_of_hbm = that over the 6.3 TB/s a float4 copy achieves on
                           this part. The positions of this scene fit the last-level cache, so the share is not bounded by 1
   mesh_*                  sn_mesh the same ways in the same run
-  record_ab               pass_ms with the 24-byte record (the product's) and with the padded 32-byte one, both from the test-only twin library
-                          in child processes (SN_MSM_REC32 switches it)
 No time is aimed at: the numbers are written down.
 """
 import argparse
 import json
 import os
-import subprocess
 import sys
 import time
 
@@ -67,8 +64,6 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "meshsmooth", "bench_meshsmooth.json"))
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--iterations", type=int, default=10)
-    ap.add_argument("--no-ab", action="store_true")
-    ap.add_argument("--pass-only", action="store_true", help="print pass_ms of the quad and triangle mesh as one JSON line and exit (the A/B child)")
     args = ap.parse_args()
     import meshsmooth_ref
     from surfacenet_amd import mesh, runtime
@@ -78,9 +73,6 @@ def main():
     faces = dict(quads=np.ascontiguousarray(m["quads"], dtype=np.int32), triangles=np.ascontiguousarray(mesh.triangulate(m["quads"]), dtype=np.int32))
     lam, mu = meshsmooth_ref.q16(0.5), meshsmooth_ref.q16(-0.53)
     run = lambda f, n=args.iterations, **kw: ctx.mesh_smooth(lat, f, n, lam, mu, 1, origin=origin, resol=resol, **kw)
-    if args.pass_only:
-        print(json.dumps({k: _summary(*_median_stages(ctx, lambda: run(f), args.reps))["pass_ms"] for k, f in faces.items()}))
-        return
     res = dict(tool="tools/bench_meshsmooth.py", resol=resol, reps=args.reps, iterations=args.iterations, lam_q16=lam, mu_q16=mu, boundary="curve",
                vertices=int(lat.shape[0]), hbm_achievable_TBps=HBM_ACHIEVABLE / 1e12, record_bytes=RECORD, meshes={}, **counts)
     try:
@@ -121,20 +113,10 @@ def main():
         row["ratio_to_mesh_kernel"] = row["kernel_ms"] / res["mesh_kernel_ms"]
         row["ratio_to_mesh_packed"] = row["packed_ms"] / res["mesh_packed_ms"]
     save()
-    if not args.no_ab:
-        dbg = os.path.join(ROOT, "surfacenet_amd", "libsurfacenet_hip_dbg.so")
-        res["record_ab"] = {}
-        for label, extra in (("rec24_pass_ms", {}), ("rec32_pass_ms", {"SN_MSM_REC32": "1"})):
-            env = {k: v for k, v in os.environ.items() if k != "SN_MSM_REC32"}
-            env.update(SURFACENET_HIP_LIB=dbg, **extra)
-            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--pass-only", "--reps", str(args.reps), "--iterations", str(args.iterations)],
-                                 env=env, capture_output=True, text=True, timeout=300)
-            res["record_ab"][label] = json.loads(out.stdout.strip().splitlines()[-1]) if out.returncode == 0 else "failed: %s" % out.stderr[-300:]
-        save()
     print(json.dumps(dict(mesh_kernel_ms=res["mesh_kernel_ms"], vertices=res["vertices"],
                           meshes={k: {a: b for a, b in row.items() if a in ("faces", "edges", "packed_ms", "device_ms", "kernel_ms", "build_ms", "pass_ms",
                                                                             "topology_ms", "pass_GBps", "pass_share_of_hbm", "ratio_to_mesh_kernel")}
-                                  for k, row in res["meshes"].items()}, record_ab=res.get("record_ab")), default=float))
+                                  for k, row in res["meshes"].items()}), default=float))
 
 
 if __name__ == "__main__":
