@@ -37,7 +37,8 @@ extern "C" {
  * sn_mesh_orient, sn_mesh_orient_dev and sn_mesh_orient_cfg - a mesh's faces made to turn one way, its pieces and their exact volumes;
  * sn_mesh_render, sn_mesh_render_dev, sn_mesh_vertex_colors, sn_mesh_vertex_colors_dev and sn_mesh_render_cfg - a mesh rendered back into its
  * views: depth maps, face ids, visibility, vertex colours; sn_mesh_intersect, sn_mesh_intersect_dev and sn_mesh_intersect_cfg - the pairs of
- * faces of a mesh that cross or touch each other, exactly. */
+ * faces of a mesh that cross or touch each other, exactly; sn_mesh_distance, sn_mesh_distance_dev and sn_mesh_distance_cfg - for every
+ * point of a set the nearest point of a mesh: its squared distance, its face, the point itself. */
 
 /* The library is built with -fvisibility=hidden: the functions below are its WHOLE dynamic symbol table
  * (tests/test_abi.py compares `nm -D` with this header). */
@@ -575,6 +576,41 @@ SN_API int sn_mesh_intersect(sn_ctx *ctx, const sn_mesh_intersect_cfg *cfg, int 
 SN_API int sn_mesh_intersect_dev(sn_ctx *ctx, const sn_mesh_intersect_cfg *cfg, int n_verts, const double *verts_dev, int n_faces, int nv,
                                  const int32_t *faces_dev, unsigned char *face_hit_dev, int32_t *face_pairs_dev, int32_t *pairs_dev,
                                  long long *counts);
+
+/* ---- distance from points to a mesh: the exact nearest triangle ------------------------------------------------------
+ * sn_mesh_distance gives, for each of n_pts points, the nearest point of a mesh: verts (n_verts,3) float64 in WORLD coordinates (as
+ * sn_mesh_render's), faces (n_faces,nv) int32, nv = 3 or 4 - a quad (a,b,c,d) is the triangles (a,b,c), (a,c,d), triangle t = f for nv = 3
+ * and t = 2 f + half for nv = 4 -, pts (n_pts,3) float64, finite. All float arithmetic is fp64 with + - * / and comparisons only, without
+ * contraction, in fixed orders: dot(a,b) = (a0*b0 + a1*b1) + a2*b2, cross(a,b) = (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0).
+ *   1 segment    P against closed segment UV: e = V - U, w = P - U, ee = dot(e,e), we = dot(w,e). ee == 0 or we <= 0: the closest point c is
+ *                U; else we >= ee: c is V itself; else t = we / ee, c = U + e*t per component. d2 = dot(P - c, P - c).
+ *   2 triangle   P against ABC, corners in face order: e1 = B - A, e2 = C - A, n = cross(e1,e2), nn = dot(n,n). If nn > 0: w = P - A,
+ *                nb = dot(cross(w,e2), n), ng = dot(cross(e1,w), n), and if nb > 0, ng > 0 and nb + ng < nn the face candidate is c = A +
+ *                (e1*(nb/nn) + e2*(ng/nn)). The answer is the first, in the order face, AB, BC, CA, of the candidates with the least d2. A
+ *                DEGENERATE triangle (nn == 0: a repeated index, collinear or coincident corners) is its three segments.
+ *   3 mesh       the least d2 over all triangles and, among those that attain it, the smallest triangle index: face is that triangle's
+ *                face, closest its c. The answer depends on no traversal order and not on the grid.
+ *   4 cap        the answer is reported when the minimum d2 is below max_dist*max_dist * (1 + 2^-40) (sn_nn_dist2's cap); otherwise d2 =
+ *                +inf, face = -1, closest = three NaNs. The same for n_faces = 0.
+ * Outputs, each optional (NULL) except counts: d2 (n_pts) float64, face (n_pts) int32, closest (n_pts,3) float64; counts[8] = triangles,
+ * degenerate triangles, points answered, points beyond the cap, (point, triangle) tests run (this one belongs to the broad phase and is no
+ * part of the contract), 0, 0, 0. n_pts = 0 is legal: the mesh is checked and counted.
+ * SN_ERR_ARG, nothing written but counts (zeros): a face index outside [0, n_verts) or a non-finite coordinate of a referenced vertex (the
+ * text names the first offending face, in sn_mesh_sample's words; unreferenced vertices may hold anything); a non-finite point (the text
+ * names the first); nv not 3 or 4, n_verts or n_faces > 2^28, n_pts > 2^29, max_dist not finite or not > 0, a null cfg, more than 2^26
+ * triangles (the grid's tables). Limits: the distance is unsigned; no barycentric coordinates come out; a uniform grid, no hierarchy: the
+ * work is quadratic in the triangles that crowd one grid cell; coordinates whose squares overflow fp64 give what rule 2's arithmetic
+ * gives. The result equals the restatement tests/meshdistance_ref.py bit for bit (but counts[4]), on every run. The workspace belongs to
+ * the context (grown on demand); both forms return when the work is done. */
+typedef struct sn_mesh_distance_cfg {
+    double max_dist;           /* finite, > 0: rule 4's cap */
+} sn_mesh_distance_cfg;
+SN_API int sn_mesh_distance(sn_ctx *ctx, const sn_mesh_distance_cfg *cfg, int n_verts, const double *verts, int n_faces, int nv,
+                            const int32_t *faces, long long n_pts, const double *pts, double *d2, int32_t *face, double *closest,
+                            long long *counts);
+SN_API int sn_mesh_distance_dev(sn_ctx *ctx, const sn_mesh_distance_cfg *cfg, int n_verts, const double *verts_dev, int n_faces, int nv,
+                                const int32_t *faces_dev, long long n_pts, const double *pts_dev, double *d2_dev, int32_t *face_dev,
+                                double *closest_dev, long long *counts);
 
 /* ---- the mesh back in its views: depth maps, face ids, visibility, colours --------------------------------------------
  * sn_mesh_render rasterises a mesh into V views of one size: verts (n_verts,3) float64 in WORLD coordinates (as sn_mesh_sample's), faces

@@ -750,6 +750,32 @@ class Context(object):
             out = call(int(out["counts"][3]))
         return out
 
+    DISTANCE_OUTPUTS = ("d2", "face", "closest")
+
+    def mesh_distance(self, verts, faces, pts, max_dist, outputs=DISTANCE_OUTPUTS, device=False):
+        """For every point the nearest point of a mesh (sn_mesh_distance): verts (V,3) float64 in world coordinates,
+        faces (F,3) or (F,4) int32, pts (n,3) float64, max_dist > 0 the cap. Returns a dict of those of `outputs` that were asked for - d2
+        (n,) float64 (+inf beyond the cap), face (n,) int32 (-1 there), closest (n,3) float64 (NaN there) - and counts (8,) int64 =
+        triangles, degenerate triangles, points answered, points beyond the cap, (point, triangle) tests run (the broad phase's own
+        number), 0, 0, 0. device=True stages the mesh and the points in device memory here and runs sn_mesh_distance_dev on them: the same
+        result."""
+        v, f = self._mesh_arrays(verts, faces)
+        p = self._points(pts)
+        V, (F, nv), n = v.shape[0], f.shape, p.shape[0]
+        if set(outputs) - set(self.DISTANCE_OUTPUTS):
+            raise ValueError("outputs = %r: of %r" % (outputs, self.DISTANCE_OUTPUTS))
+        cfg = _lib.MeshDistanceCfg(float(max_dist))
+        widths = dict(d2=(1, np.float64), face=(1, np.int32), closest=(3, np.float64))
+        spec = tuple((name,) + widths[name] for name in self.DISTANCE_OUTPUTS if name in outputs)
+
+        def run(fn, _, ins, outs, counts):
+            given = dict(zip([name for name, _, _ in spec], outs))
+            return fn(self._h, ctypes.byref(cfg), V, ins[0], F, nv, ins[1], n, ins[2], *[given.get(name) for name in self.DISTANCE_OUTPUTS], *counts)
+        out = self._host_or_device("sn_mesh_distance", device, (v, f, p), run, spec, lambda name, sizes: n, (), words=8)
+        if "closest" in out:
+            out["closest"] = out["closest"].reshape(n, 3)
+        return out
+
     def _render_args(self, verts, faces, cameraPOs, shape, near, tol):
         """-> (verts, faces, P or None, V, cfg) of mesh_render and mesh_vertex_colors: cameraPOs (V,3,4), None = the cameras of set_cameras."""
         v, f = self._mesh_arrays(verts, faces)

@@ -1,6 +1,6 @@
 // sn_internal.h — shared by the translation units of libsurfacenet_hip.so (sn_api.hip: context, weights, hot path, RCCL, profiling;
 // sn_post.hip: ray pooling + dense2sparse; sn_simil.hip: similarityNet + patch cropping; sn_crosscube.hip: cross-cube denoising + adaptive
-// thresholding; sn_pointeval.hip: point-cloud evaluation; sn_ptcubes.hip: point-seeded cube list; sn_normals.hip: normals + de-duplication; sn_components.hip: connected components; sn_mesh.hip: surface mesh; sn_meshsample.hip: surface samples of a mesh; sn_meshsimplify.hip: mesh simplification; sn_meshedges.hip: a mesh's edge table and the stages' sequence around it; sn_meshsmooth.hip: mesh smoothing; sn_meshfill.hip: hole filling; sn_meshnormals.hip: the mesh's own normals, area and volume; sn_meshorient.hip: consistent orientation, pieces and their volumes; sn_meshintersect.hip: exact self-intersections; sn_meshrender.hip: the mesh rendered into its views, vertex colours;
+// thresholding; sn_pointeval.hip: point-cloud evaluation; sn_ptcubes.hip: point-seeded cube list; sn_normals.hip: normals + de-duplication; sn_components.hip: connected components; sn_mesh.hip: surface mesh; sn_meshsample.hip: surface samples of a mesh; sn_meshsimplify.hip: mesh simplification; sn_meshedges.hip: a mesh's edge table and the stages' sequence around it; sn_meshsmooth.hip: mesh smoothing; sn_meshfill.hip: hole filling; sn_meshnormals.hip: the mesh's own normals, area and volume; sn_meshorient.hip: consistent orientation, pieces and their volumes; sn_meshintersect.hip: exact self-intersections; sn_meshdistance.hip: the nearest point of a mesh for every point of a set; sn_meshrender.hip: the mesh rendered into its views, vertex colours;
 // sn_gtcubes.hip: ground-truth occupancy cubes + weighted accuracy; sn_relwtrain.hip: training of the view-pair weighting net):
 // the context, owned device memory and the buffers that grow on demand (DevBuf), temporary device work buffers (TmpDev), the host forms' device copies of their arrays (HostMirror),
 // the checked launch (LAUNCH), typed fills and status reads (dev_fill, read_status),
@@ -193,6 +193,7 @@ struct sn_ctx {
     DevBuf mor_ws;                // mesh orientation (sn_meshorient.hip): status, the edge table, two words per slot, the double cover's parents, per-piece records
     DevBuf mxi_ws, mxi_grid, mxi_keys;   // self-intersections (sn_meshintersect.hip): status, the edge table's build, boxes | the grid's table, runs and entries | the hits' keys
     long long mxi_kcap = 0;       // ... the longest key list a call on this context has needed
+    DevBuf mdi_ws, mdi_grid;      // point-to-mesh distance (sn_meshdistance.hip): status, boxes, the queries' best so far, the far list | the two grids' tables, runs and entries
     DevBuf mrd_ws;                // mesh renderer (sn_meshrender.hip): status, one view's projected vertices, triangle classes, big list, z-buffer, id words, a host form's staging
     // the ground-truth cloud sn_gt_bind sorted into its grid (sn_gtcubes.hip gt_layout places the arrays in gt_ws from gt_n alone)
     DevBuf gt_ws; bool gt_bound = false; long long gt_n = 0, gt_dim[3] = {0, 0, 0}; double gt_o[3] = {0, 0, 0}, gt_cell = 0;

@@ -245,23 +245,30 @@ def _save_base_eval(EvalName, base, cSet):
 
 
 def mesh_compare(vertices, faces, Qstl, obs_mask, BB, Res, plane, dst=0.2, sample_dst=None, max_dist=60.0, seed=0, order=None, cSet=None,
-                 Margin=None):
+                 Margin=None, completeness="samples"):
     """The DTU practice for a mesh: sample its surface at sample_dst (default dst; mesh.sample_surface), then
     point_compare on the samples, which reduces them at dst. vertices (V,3), faces (F,3) or (F,4). Returns point_compare's BaseEval fields plus
-    n_samples and n_faces."""
+    n_samples and n_faces. completeness="samples" (the default) measures Dstl, the distance from every point of Qstl to the reconstruction,
+    to the reduced samples: up to 2/3 sample_dst too large. completeness="surface" measures it to the mesh's surface itself
+    (mesh.point_to_mesh), capped at max_dist as the protocol caps it, and says so under the key "completeness" -
+    a dict without that key was measured to the samples. Ddata comes from the samples either way."""
     from . import mesh
+    if completeness not in ("samples", "surface"):
+        raise ValueError("completeness = %r: \"samples\" or \"surface\"" % (completeness,))
     points, _ = mesh.sample_surface(vertices, faces, dst if sample_dst is None else sample_dst)
     base = point_compare(points, Qstl, obs_mask, BB, Res, plane, dst=dst, max_dist=max_dist, seed=seed, order=order, cSet=cSet, Margin=Margin)
     base.update(n_samples=int(points.shape[0]), n_faces=int(np.asarray(faces).shape[0]))
+    if completeness == "surface":
+        base.update(Dstl=mesh.point_to_mesh(base["Qstl"], vertices, faces, max_dist)["dist"], completeness="surface")
     return base
 
 
-def eval_mesh_ply(cSet, MeshInName, EvalName, dataPath, dst=0.2, sample_dst=None, max_dist=60.0, seed=0):
+def eval_mesh_ply(cSet, MeshInName, EvalName, dataPath, dst=0.2, sample_dst=None, max_dist=60.0, seed=0, completeness="samples"):
     """eval_ply for a mesh PLY (read_ply_mesh): the same DTU files in, the same BaseEval .mat out (plus n_samples and n_faces), the four numbers
-    of eval_acc_compl back."""
+    of eval_acc_compl back. completeness as mesh_compare takes it."""
     vertices, faces = read_ply_mesh(MeshInName)
     Qstl, m, P = _dtu_files(cSet, dataPath)
     base = mesh_compare(vertices, faces, Qstl, m["ObsMask"], m["BB"], m["Res"], P, dst=dst, sample_dst=sample_dst, max_dist=max_dist, seed=seed,
-                        cSet=cSet, Margin=m["Margin"] if "Margin" in m else None)
+                        cSet=cSet, Margin=m["Margin"] if "Margin" in m else None, completeness=completeness)
     _save_base_eval(EvalName, base, cSet)
     return eval_acc_compl(base)

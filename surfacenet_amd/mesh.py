@@ -456,6 +456,100 @@ def self_intersections(vert_lattice, faces, max_pairs=None):
     return res
 
 
+DISTANCE_COUNTS = ("n_triangles", "n_degenerate", "n_answered", "n_beyond")
+MAX_QUERY_POINTS = 1 << 29
+MAX_DISTANCE_TRIANGLES = 1 << 26
+
+
+def check_distance_args(points, max_dist=60.0):
+    """-> (points (n,3) float64, max_dist) of point_to_mesh, or ValueError: points float32 or float64 (n,3), at most 2^29 of them, finite - the
+    first that is not is named, as the library names it -, max_dist finite and > 0."""
+    p = np.asarray(points)
+    if p.dtype not in (np.float32, np.float64):
+        raise ValueError("points must be float32 or float64, not %s" % p.dtype)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError("points must be (n,3), not %r" % (p.shape,))
+    if p.shape[0] > MAX_QUERY_POINTS:
+        raise ValueError("%d points: at most 2^29" % p.shape[0])
+    try:
+        d = float(max_dist)
+    except (TypeError, ValueError):
+        raise ValueError("max_dist = %r must be a number" % (max_dist,))
+    if isinstance(max_dist, (bool, np.bool_)) or not (np.isfinite(d) and d > 0):
+        raise ValueError("max_dist = %r must be finite and > 0" % (max_dist,))
+    bad = ~np.isfinite(p).all(axis=1)
+    if bad.any():
+        raise ValueError("point %d: a coordinate is not finite" % int(np.argmax(bad)))
+    return p.astype(np.float64), d
+
+
+def point_to_mesh(points, vertices, faces, max_dist=60.0):
+    """For every point the nearest point of a mesh, exactly over all its triangles: points (n,3) float32 or float64,
+    vertices (V,3) in the same WORLD coordinates, faces (F,3) triangles or (F,4) quads - a quad is its triangles (a,b,c), (a,c,d), `face`
+    names the quad. A degenerate triangle is its three segments. -> dict: dist2 (n,) float64 the squared distance (+inf where it is not
+    below max_dist^2 (1 + 2^-40)), dist (n,) float64 = min(sqrt(dist2), max_dist) as the DTU protocol caps it, face (n,) int32 (-1 beyond
+    the cap), closest (n,3) float64 (NaN there), n_triangles, n_degenerate, n_answered, n_beyond. The distance is unsigned. ValueError on
+    bad shapes, dtypes, max_dist, face indices or coordinates before the library is touched."""
+    v, f = _world_mesh(vertices, faces)
+    p, d = check_distance_args(points, max_dist)
+    n, T = p.shape[0], f.shape[0] * (f.shape[1] - 2)
+    if T > MAX_DISTANCE_TRIANGLES:
+        raise ValueError("%d triangles: at most 2^26" % T)
+    if n == 0 or v.shape[0] == 0:                               # no point, or no vertex and so no face: nothing for the library to do
+        m = dict(d2=np.full((n,), np.inf), face=np.full((n,), -1, np.int32), closest=np.full((n, 3), np.nan), counts=np.array([0, 0, 0, n, 0, 0, 0, 0], np.int64))
+    else:
+        m = runtime.any_context().mesh_distance(v, f, p, d)
+    res = dict(dist2=m["d2"], dist=np.minimum(np.sqrt(m["d2"]), d), face=m["face"], closest=m["closest"])
+    res.update({k: int(c) for k, c in zip(DISTANCE_COUNTS, m["counts"])})
+    return res
+
+
+def _deviation(dist, n_beyond):
+    """The statistics of one direction of mesh_deviation: host numpy on the capped distances, float64."""
+    d = np.asarray(dist, np.float64)
+    if d.size == 0:
+        return dict(n=0, n_beyond=0, max=0.0, mean=0.0, rms=0.0)
+    return dict(n=int(d.size), n_beyond=int(n_beyond), max=float(d.max()), mean=float(d.mean()), rms=float(np.sqrt((d * d).mean())))
+
+
+def check_deviation_setting(value):
+    """reconstruct.scene_postpass's mesh_deviation -> None (None or False: not asked for) or dict(dst=, max_dist=) with both checked - dst
+    None stays None: the lattice's resol -, or ValueError. The library is not touched."""
+    if value is None or value is False:
+        return None
+    if value is not True and (not isinstance(value, dict) or set(value) - {"dst", "max_dist"}):
+        raise ValueError("mesh_deviation = %r: True or a dict of dst, max_dist" % (value,))
+    kw = dict(dict(dst=None, max_dist=60.0), **({} if value is True else value))
+    _, kw["max_dist"] = check_distance_args(np.zeros((0, 3)), kw["max_dist"])
+    if kw["dst"] is not None:
+        try:
+            d = float(kw["dst"])
+        except (TypeError, ValueError):
+            raise ValueError("dst = %r must be a number" % (kw["dst"],))
+        if isinstance(kw["dst"], (bool, np.bool_)) or not (np.isfinite(d) and d > 0):
+            raise ValueError("dst = %r must be finite and > 0" % (kw["dst"],))
+        kw["dst"] = d
+    return kw
+
+
+def mesh_deviation(vertices_a, faces_a, vertices_b, faces_b, dst, max_dist=60.0):
+    """How far two meshes in the same world coordinates are from each other: the surface samples of a at density dst
+    (sample_surface) against the surface of b (point_to_mesh), and the reverse. -> dict: a_to_b and b_to_a, each a dict of n the samples,
+    n_beyond those farther than max_dist, and max, mean, rms of their distances capped at max_dist; hausdorff, the larger max. It is a
+    SAMPLED Hausdorff distance: a lower bound of the true one and, every point of a triangle lying within 2/3 dst of a sample, within
+    2/3 dst of it (below the cap). ValueError before the library is touched."""
+    va, fa = _world_mesh(vertices_a, faces_a)
+    vb, fb = _world_mesh(vertices_b, faces_b)
+    check_distance_args(np.zeros((0, 3)), max_dist)
+    res = {}
+    for key, (v0, f0), (v1, f1) in (("a_to_b", (va, fa), (vb, fb)), ("b_to_a", (vb, fb), (va, fa))):
+        pts = sample_surface(v0, f0, dst)[0] if f0.shape[0] else np.zeros((0, 3))
+        r = point_to_mesh(pts, v1, f1, max_dist)
+        res[key] = _deviation(r["dist"], r["n_beyond"])
+    res["hausdorff"] = max(res["a_to_b"]["max"], res["b_to_a"]["max"])
+    return res
+
+
 RENDER_COUNTS = ("n_triangles", "n_clipped", "n_degenerate", "n_rasterised", "n_pairs", "n_pixels", "n_visible")
 MAX_IMAGE_DIM = 16384
 

@@ -566,7 +566,7 @@ def reconstruct_scene(images_list, cameraPOs_np, cubes_param_np, cube_D_mm, cube
 def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, gamma=0.8, beta=6, N_refine_iter=8, init_probThresh=0.5,
                    max_probThresh=0.9, keep_iterations=False, cameraTs_np=None, cube_overlapping_ratio=0.5, unique=False, mesh=False, mesh_radius=2,
                    mesh_reach=0, mesh_ply_prefix=None, min_component=None, component_connectivity=26, mesh_cell=None, mesh_placement="mean",
-                   mesh_smooth=None, mesh_fill=None, mesh_normals="source", mesh_orient=None, mesh_render=None, mesh_check=None):
+                   mesh_smooth=None, mesh_fill=None, mesh_normals="source", mesh_orient=None, mesh_render=None, mesh_check=None, mesh_deviation=None):
     """The reconstruction's last two stages on `reconstruct_scene`'s dict, in memory and on the GPU, as the reference runs them on its files:
       * main_reconstruct.py:172-175  thinning masks (prob >= tau, votes >= gamma * N_vp * 2), then denoise_crossCubes with D_cube = cube_D
       * main.py:37-43 -> utils/adapthresh.py  adaptive thresholding with D_cube = cube_Dcenter, init / max threshold init_probThresh /
@@ -618,7 +618,11 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
       mesh_check=True or dict(max_pairs=) (needs mesh=True; the default None adds no key and changes no byte):
         fixThresh_mesh_checked, adapt_mesh_checked - mesh.self_intersections' report on the LAST mesh of the chain (the mesh of mesh=True
         without a chain): pairs, face_hit, face_pairs, the counts and truncated. n_pairs = 0 says that no two faces of it cross or touch.
-        The mesh itself goes on unchanged, and no file is written."""
+        The mesh itself goes on unchanged, and no file is written.
+      mesh_deviation=True or dict(dst=, max_dist=) (needs mesh=True; the default None adds no key and changes no byte):
+        fixThresh_mesh_deviation, adapt_mesh_deviation - mesh.mesh_deviation of the LAST mesh of the chain against the extracted mesh of
+        mesh=True, in world mm: what the chain cost in millimetres, a_to_b from the last mesh to the extracted one, b_to_a back, and
+        hausdorff. True means dst = the lattice's resol and max_dist = 60.0. No file is written."""
     from . import adapthresh, denoising, sparseCubes
     from . import mesh as _mesh
     from . import normals as _normals
@@ -628,13 +632,15 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
     for arg, value, does in (("mesh_cell", mesh_cell, "simplifies"), ("mesh_smooth", mesh_smooth, "smooths"), ("mesh_fill", mesh_fill, "fills the holes of"),
                              ("mesh_normals", None if mesh_normals == "source" else mesh_normals, "takes its normals from"),
                              ("mesh_orient", mesh_orient, "orients"), ("mesh_render", mesh_render, "renders"),
-                             ("mesh_check", None if mesh_check is False else mesh_check, "checks")):
+                             ("mesh_check", None if mesh_check is False else mesh_check, "checks"),
+                             ("mesh_deviation", None if mesh_deviation is False else mesh_deviation, "measures the chain against")):
         if value is not None and not mesh:
             raise ValueError("%s needs mesh=True: it %s the mesh that mesh=True extracts" % (arg, does))
     stages = _mesh.chain_settings(mesh_fill, mesh_smooth, mesh_cell, mesh_placement, mesh_orient, mesh_check)      # fill, smooth, decimate, orient, check: those asked for
     meshes = [key for key, _ in stages if _mesh.stage_tag(key, dict(stages)[key]) is not None]      # the stages whose result is a mesh
     _mesh.check_normals_arg(mesh_normals, "mesh_normals")
     render = None if mesh_render is None else _mesh.check_render_setting(mesh_render)
+    deviation = _mesh.check_deviation_setting(mesh_deviation)
     ply_tags = dict([("", "")] + [("_" + key, _mesh.stage_tag(key, kw)) for key, kw in stages])      # result key's ending -> file name's
     if min_component is not None:
         from . import components as _components
@@ -682,7 +688,7 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
             res[name + "_unique_list"] = _normals.unique_voxels(cube_ijk, ijk_l, masks, stride_vox) if n else []
         if mesh:
             m = _mesh.extract_mesh(cube_ijk, ijk_l, masks, normal_l, out["param_np"], stride_vox, mesh_radius, mesh_reach) if n else _mesh.empty_mesh()
-            if n and (stages or mesh_normals == "mesh" or render is not None) and lattice is None:      # (once: the lattice that extract_mesh has just accepted)
+            if n and (stages or mesh_normals == "mesh" or render is not None or deviation is not None) and lattice is None:      # (once: the lattice that extract_mesh has just accepted)
                 lattice = _mesh.lattice_origin(cube_ijk, out["param_np"], stride_vox)
             chain = _mesh.run_chain(m, stages, *(lattice or ((0.0, 0.0, 0.0), 1.0)))
             for end, stage_mesh in [("", m)] + [("_" + key, chain[key]) for key in chain]:
@@ -707,6 +713,11 @@ def scene_postpass(out, cube_D, cube_Dcenter, N_viewPairs4inference, tau=0.7, ga
                     if mesh_ply_prefix is not None and n:
                         _mesh.save_stage_2ply("%s%s_mesh_v.ply" % (mesh_ply_prefix, name), last, normal_l, normals=mesh_normals, rgb_np=r["vert_rgb"])
                 res[name + "_mesh_render"] = r
+            if deviation is not None:                           # the last mesh of the chain against the extracted one, in mm
+                last = chain[meshes[-1]] if meshes else m
+                dst = deviation["dst"] if deviation["dst"] is not None else (lattice[1] if lattice else 1.0)
+                res[name + "_mesh_deviation"] = _mesh.mesh_deviation(last["vertices"], _mesh._faces(last), m["vertices"], m["quads"], dst,
+                                                                     deviation["max_dist"])
     return res
 
 
