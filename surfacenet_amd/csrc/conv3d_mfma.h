@@ -92,7 +92,9 @@ struct ConvArgs {
     long long side_lo_off, pool_lo_off;
     int side_cs, side_coff, pool_cs, side_act;
     unsigned *status;         // numeric status word of the context (or nullptr): status_bit is OR-ed in when an output value is not
-    unsigned status_bit;      // finite or exceeds the fp16 range its hi plane is stored in (|y| > 65504)
+    unsigned status_bit;      // finite or exceeds the fp16 range its hi plane is stored in (|y| > 65504). Contract: the error and the warning word are
+                              // functions of the accumulators and halves of lanes that STORE - a fragment lane whose voxel lies outside the volume or
+                              // whose channel is padding feeds neither tracker (sn_track_merge; tests/test_gpu_numstatus.py)
     unsigned mx_sat_bits;     // != 0: the output tensor carries a 6-bit code plane; fp16 bits of the largest value its static premultiplier represents
                               // (7.5 * 2^-s). A larger stored value saturates its code (only that element's correction term degrades): status[1] |= status_bit,
                               // a WARNING the host can read (sn_numeric_status), never an error
@@ -142,6 +144,15 @@ __device__ __forceinline__ void sn_track_acc(f32x2_t &c, const f32x4 &a)
 // sigmoid(NaN) in a 1x1x1 side convolution - and pack_conv_host rejects every non-finite folded constant at load time (SN_ERR_ARG naming the layer and
 // channel; tests/test_gpu_numerics.py::test_non_finite_batchnorm_constants_are_rejected_at_load), so no NaN can enter behind sn_track_acc. ADVICE r4.)
 __device__ __forceinline__ void sn_track_h2(unsigned &c, unsigned h2) { asm volatile("v_pk_max_f16 %0, %1, %0" : "+v"(c) : "v"(h2)); }
+// The trackers of ONE voxel fragment (fc: 0 or a sticky NaN, fh: its largest stored half) join the kernel's only for the lanes whose voxel is
+// stored: a lane outside the volume holds the BN affine of whatever its halo staged - ReLU(shift) on zeros - and must not speak (ConvArgs::status_bit).
+// Per fragment, not per value: three selects and two packed operations per fragment, none per value.
+__device__ __forceinline__ void sn_track_merge_acc(f32x2_t &c, const f32x2_t &fc, bool stored)
+{
+    const f32x2_t m = {stored ? fc.x : 0.f, stored ? fc.y : 0.f};
+    asm volatile("v_pk_fma_f32 %0, %1, 0, %0 op_sel_hi:[1,0,1]" : "+v"(c) : "v"(m));
+}
+__device__ __forceinline__ void sn_track_merge_h2(unsigned &c, unsigned fh, bool stored) { sn_track_h2(c, stored ? fh : 0u); }
 __device__ __forceinline__ unsigned sn_tracked_max_bits(unsigned h) { const unsigned lo = h & 0x7fffu, hi = (h >> 16) & 0x7fffu; return lo > hi ? lo : hi; }   // fp16 bits of the largest stored value
 __device__ __forceinline__ bool sn_tracked_bad(const f32x2_t &c, unsigned h) { return !(c.x == 0.f && c.y == 0.f) || sn_tracked_max_bits(h) >= 0x7c00u; }
 
@@ -1392,7 +1403,10 @@ conv3d_f16_mfma(ConvArgs a)
                 int hx_, hy_, hz_;
                 frag_xyz(m, hx_, hy_, hz_);
                 const int gx = x0 + hx_, gy = y0 + hy_, gz = z0 + hz_;
-                const bool writer = !(v & 1) && (R2 || !(v & YX)) && gx < DX && gy < D && gz < D;     // D is even: the whole quad is inside
+                const bool inside = gx < DX && gy < D && gz < D;                    // D is even: the whole quad is inside
+                const bool writer = !(v & 1) && (R2 || !(v & YX)) && inside;
+                f32x2_t fc = {0.f, 0.f};            // this fragment's trackers (sn_track_merge_*)
+                unsigned fh = 0;
                 const size_t vlin = ((size_t)gx * Do + (gy >> 1)) * Do + (gz >> 1);
 #pragma unroll
                 for (int n = 0; n < NF; ++n) {
@@ -1412,9 +1426,9 @@ conv3d_f16_mfma(ConvArgs a)
                         h[r] = hh;
                         if constexpr (OSPLIT == 1) l[r] = ll;
                     }
-                    sn_track_acc(trk_acc, acc[m][n]);
-                    if constexpr (R2) sn_track_acc(trk_acc, acc[m + 1 < MF ? m + 1 : m][n]);
-                    { const uint2 hb = __builtin_bit_cast(uint2, h); sn_track_h2(trk_h, hb.x); sn_track_h2(trk_h, hb.y); }
+                    sn_track_acc(fc, acc[m][n]);
+                    if constexpr (R2) sn_track_acc(fc, acc[m + 1 < MF ? m + 1 : m][n]);
+                    { const uint2 hb = __builtin_bit_cast(uint2, h); sn_track_h2(fh, hb.x); sn_track_h2(fh, hb.y); }
                     if (writer && nl < a.out_cp) {
                         const int ch = a.out_coff + nl;
                         _Float16 *o = a.out + (size_t)b * VOLo * a.out_cs + ((size_t)(ch >> 3) * VOLo + vlin) * 8 + (ch & 7);
@@ -1427,6 +1441,9 @@ conv3d_f16_mfma(ConvArgs a)
                         }
                     }
                 }
+                // (x is the patch index: a lane beyond the last patch reads what an earlier, larger batch left there)
+                sn_track_merge_acc(trk_acc, fc, inside);
+                sn_track_merge_h2(trk_h, fh, inside);
             }
         } else if constexpr (EPI == EPI_SIDEPOOL) {
             static_assert(NF * 16 <= 96 && OSPLIT <= 2 && SPLIT <= 2, "side conv K chunks (formats 0..2)");
@@ -1434,6 +1451,9 @@ conv3d_f16_mfma(ConvArgs a)
             const size_t VOLo = (size_t)Do * Do * Do;
             // this layer's outputs, in registers: y[m][n][r] = ReLU(BN(acc)), fp32
             float y[MF][NF][4];
+            f32x2_t fcm[MF];                    // the accumulator tracker of each voxel fragment (sn_track_merge_acc)
+#pragma unroll
+            for (int m = 0; m < MF; ++m) fcm[m] = f32x2_t{0.f, 0.f};
 #pragma unroll
             for (int n = 0; n < NF; ++n) {
                 const int nl = n * 16 + kq * 4;
@@ -1447,7 +1467,13 @@ conv3d_f16_mfma(ConvArgs a)
                         y[m][n][r] = t;
                     }
 #pragma unroll
-                for (int m = 0; m < MF; ++m) sn_track_acc(trk_acc, acc[m][n]);     // (a value beyond fp16 shows up as +inf in the pooled store / the side conv's operand)
+                for (int m = 0; m < MF; ++m) sn_track_acc(fcm[m], acc[m][n]);     // (a value beyond fp16 shows up as +inf in the pooled store / the side conv's operand)
+            }
+#pragma unroll
+            for (int m = 0; m < MF; ++m) {
+                int hx, hy, hz;
+                frag_xyz(m, hx, hy, hz);
+                sn_track_merge_acc(trk_acc, fcm[m], x0 + hx < DX && y0 + hy < D && z0 + hz < D);
             }
             // ---- side conv (1x1x1 over all NF*16 channels) on the matrix cores: B operand = the outputs as this lane holds them
             f32x4 sacc[MF];
@@ -1504,8 +1530,14 @@ conv3d_f16_mfma(ConvArgs a)
                         }
                         const uint2 hb = __builtin_bit_cast(uint2, h);
                         hw[e][0] = hb.x; hw[e][1] = hb.y;
-                        sn_track_acc(trk_acc, sacc[mp + e]);
-                        sn_track_h2(trk_h, hb.x); sn_track_h2(trk_h, hb.y);
+                        {   // (one fragment's side output: its trackers are the values themselves)
+                            f32x2_t fc = {0.f, 0.f};
+                            unsigned fh = 0;
+                            sn_track_acc(fc, sacc[mp + e]);
+                            sn_track_h2(fh, hb.x); sn_track_h2(fh, hb.y);
+                            sn_track_merge_acc(trk_acc, fc, valid[e]);
+                            sn_track_merge_h2(trk_h, fh, valid[e]);
+                        }
                         if constexpr (OSPLIT == 1) {
                             const uint2 lb = __builtin_bit_cast(uint2, l);
                             lw[e][0] = lb.x; lw[e][1] = lb.y;
@@ -1552,6 +1584,7 @@ conv3d_f16_mfma(ConvArgs a)
                 // per-lane part of the store address as ONE 32-bit byte offset (pooled voxel, the lane's half of its 8-channel group, + one group
                 // plane for kq >= 2), the rest wave-uniform: see EPI_STORE (a spilled 64-bit address reloaded inside the store loop = vmcnt(0) per store)
                 const unsigned pvoff = ((unsigned)(((gx >> 1) * Do + (gy >> 1)) * Do + (gz >> 1)) + (unsigned)(kq >> 1) * (unsigned)VOLo) * 16u + (unsigned)(kq & 1) * 8u;
+                unsigned fh = 0;                    // the pooled cell's tracker (D even: a cell is inside or outside as a whole; NF * 16 = out_cp: no padded channel)
 #pragma unroll
                 for (int n = 0; n < NF; ++n) {
                     half4 h, l;
@@ -1567,7 +1600,7 @@ conv3d_f16_mfma(ConvArgs a)
                         if constexpr (SPLIT == 1) l[r] = ll;
                     }
                     const int ch = n * 16 + kq * 4;
-                    { const uint2 hb = __builtin_bit_cast(uint2, h); sn_track_h2(trk_h, hb.x); sn_track_h2(trk_h, hb.y); }
+                    { const uint2 hb = __builtin_bit_cast(uint2, h); sn_track_h2(fh, hb.x); sn_track_h2(fh, hb.y); }
                     if (writer && ch < a.out_cp) {
                         char *const plane = reinterpret_cast<char *>(a.pool_out) + 2 * ((size_t)b * VOLo * a.pool_cs + (size_t)(2 * n) * VOLo * 8);     // wave-uniform
                         _Float16 *o = reinterpret_cast<_Float16 *>(plane + pvoff);
@@ -1580,6 +1613,7 @@ conv3d_f16_mfma(ConvArgs a)
                         }
                     }
                 }
+                sn_track_merge_h2(trk_h, fh, gx < DX && gy < D && gz < D);
             }
         } else if constexpr (EPI == EPI_STORE) {
             // Lane (v, kq) holds channels 4kq..4kq+3 of 16-channel fragment n: the 16-byte group of a voxel is split between lanes
@@ -1616,10 +1650,12 @@ conv3d_f16_mfma(ConvArgs a)
                     scv[n] = *reinterpret_cast<const f32x4 *>(cstl + n * 16);
                     shv[n] = *reinterpret_cast<const f32x4 *>(cstl + NF * 16 + n * 16);
                 } else {
+                    // (a padded channel reads its own constants, as under CST_LDS: pack_conv_host sizes both tables nsplit * NF * 16 + 16 and leaves
+                    // the entries behind the last real channel zero, so its lanes - zero weight rows - track exact zeros; with channel 0's constants
+                    // in their place the trackers saw ReLU(shift[0 .. 3]) in lanes that store nothing)
                     const int nl = (blockIdx.y * NF + n) * 16 + kq * 4;
-                    const int nlc = nl < a.out_cp ? nl : 0;
-                    scv[n] = *reinterpret_cast<const f32x4 *>(a.scale + nlc);
-                    shv[n] = *reinterpret_cast<const f32x4 *>(a.shift + nlc);
+                    scv[n] = *reinterpret_cast<const f32x4 *>(a.scale + nl);
+                    shv[n] = *reinterpret_cast<const f32x4 *>(a.shift + nl);
                 }
             }
 #pragma unroll
@@ -1633,6 +1669,16 @@ conv3d_f16_mfma(ConvArgs a)
                 frag_xyz(mp + (odd ? 1 : 0), hx_, hy_, hz_);
                 const int gx = x0 + hx_, gy = y0 + hy_, gz = z0 + hz_;
                 const bool my_valid = gx < DX && gy < D && gz < D;
+                // the trackers of the pair's two fragments, and whether this lane's voxel of each is inside the volume (sn_track_merge_*)
+                f32x2_t fc[2] = {{0.f, 0.f}, {0.f, 0.f}};
+                unsigned fh[2] = {0u, 0u};
+                bool frag_valid[2];
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    int fx, fy, fz;
+                    frag_xyz(mp + e, fx, fy, fz);
+                    frag_valid[e] = x0 + fx < DX && y0 + fy < D && z0 + fz < D;
+                }
                 const unsigned my_voff = ((unsigned)((gx * D + gy) * D + gz) + (unsigned)(kq >> 1) * (unsigned)VOL) * 16u;
 #pragma unroll
                 for (int n = 0; n < NF; ++n) {
@@ -1665,8 +1711,8 @@ conv3d_f16_mfma(ConvArgs a)
                         }
                         const uint2 hb = __builtin_bit_cast(uint2, h);
                         hw[e][0] = hb.x; hw[e][1] = hb.y;
-                        sn_track_acc(trk_acc, acc[mp + e][n]);       // (the accumulator: ReLU would turn a NaN / -inf one into a clean 0)
-                        sn_track_h2(trk_h, hb.x); sn_track_h2(trk_h, hb.y);
+                        sn_track_acc(fc[e], acc[mp + e][n]);         // (the accumulator: ReLU would turn a NaN / -inf one into a clean 0)
+                        sn_track_h2(fh[e], hb.x); sn_track_h2(fh[e], hb.y);
                         if constexpr (OLO) {
                             const uint2 lb = __builtin_bit_cast(uint2, l);
                             lw[e][0] = lb.x; lw[e][1] = lb.y;
@@ -1705,6 +1751,11 @@ conv3d_f16_mfma(ConvArgs a)
                         } else
                         if (st) *reinterpret_cast<u32x4 *>(oc) = u32x4{c0[0], c0[1], c1[0], c1[1]};
                     }
+                }
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    sn_track_merge_acc(trk_acc, fc[e], frag_valid[e]);
+                    sn_track_merge_h2(trk_h, fh[e], frag_valid[e]);
                 }
             }
             };
@@ -1748,7 +1799,7 @@ conv3d_f16_mfma(ConvArgs a)
                 p += __shfl_xor(p, 16);
                 p += __shfl_xor(p, 32);
                 const float t = p * a.scale3 + a.shift3;
-                bad |= !(fabsf(t) <= 3.0e38f);                 // NaN / inf logit (an overflowed accumulator upstream)
+                bad |= valid && !(fabsf(t) <= 3.0e38f);        // NaN / inf logit (an overflowed accumulator upstream) of a voxel that is stored
                 if (valid && kq == 0) a.out_f32[vox] = sn_sigmoid(t);
             }
         }
