@@ -38,7 +38,8 @@ extern "C" {
  * sn_mesh_render, sn_mesh_render_dev, sn_mesh_vertex_colors, sn_mesh_vertex_colors_dev and sn_mesh_render_cfg - a mesh rendered back into its
  * views: depth maps, face ids, visibility, vertex colours; sn_mesh_intersect, sn_mesh_intersect_dev and sn_mesh_intersect_cfg - the pairs of
  * faces of a mesh that cross or touch each other, exactly; sn_mesh_distance, sn_mesh_distance_dev and sn_mesh_distance_cfg - for every
- * point of a set the nearest point of a mesh: its squared distance, its face, the point itself. */
+ * point of a set the nearest point of a mesh: its squared distance, its face, the point itself; sn_mesh_winding, sn_mesh_winding_dev and
+ * sn_mesh_winding_cfg - for every point of a set how many times a mesh winds around it, exactly: inside, outside or on the surface. */
 
 /* The library is built with -fvisibility=hidden: the functions below are its WHOLE dynamic symbol table
  * (tests/test_abi.py compares `nm -D` with this header). */
@@ -611,6 +612,44 @@ SN_API int sn_mesh_distance(sn_ctx *ctx, const sn_mesh_distance_cfg *cfg, int n_
 SN_API int sn_mesh_distance_dev(sn_ctx *ctx, const sn_mesh_distance_cfg *cfg, int n_verts, const double *verts_dev, int n_faces, int nv,
                                 const int32_t *faces_dev, long long n_pts, const double *pts_dev, double *d2_dev, int32_t *face_dev,
                                 double *closest_dev, long long *counts);
+
+/* ---- inside or outside: the exact winding number of points against a mesh ---------------------------------------------
+ * sn_mesh_winding counts, for each of n_pts points, the signed crossings of the point's ray along +axis with a mesh. The mesh is
+ * sn_mesh_smooth's: verts (n_verts,3) float64 in lattice cells, faces (n_faces,nv) int32, nv = 3 or 4 - a quad (a,b,c,d) is the triangles
+ * (a,b,c), (a,c,d) -, referenced coordinates in -4 <= v < 2^21 - 8; pts (n_pts,3) float64 in lattice cells, every coordinate in the same
+ * range. Vertex and query positions become q = int64(rint(v * 65536)). Everything is an integer and exact in 128 bits; only signs are used.
+ *   1 axes      the ray runs along +w, w = axis; the kept axes are (u, v) = (w + 1, w + 2) mod 3, a cyclic permutation.
+ *   2 triangle  n = (b - a) x (c - a); A2 = n_w, the doubled signed area of the (u, v) projection, s = sign(A2); D = n . (p - a).
+ *   3 surface   a triangle with n != 0 HOLDS p iff D = 0 and, in the projection along the triangle's own drop axis (sn_mesh_intersect's rule
+ *               2), the three orient2 signs of p against ab, bc, ca do not hold both a positive and a negative (closed). It does not depend
+ *               on axis. on_surface[i] = 1 iff some triangle holds p_i.
+ *   4 crossing  a triangle with s != 0 is CROSSED by the ray of p iff it is covered, half open - for each edge x -> y of ab, bc, ca, with
+ *               e = s ((y_u - x_u)(p_v - x_v) - (y_v - x_v)(p_u - x_u)) and (dx, dy) = s (y_u - x_u, y_v - x_v): e > 0, or e = 0 and dy > 0,
+ *               or e = 0, dy = 0 and dx > 0 (sn_mesh_render's rule 4) - and lies strictly above p: D s < 0. A triangle with s = 0 is never
+ *               crossed.
+ *   5 outputs   winding[i] = the sum of s over the crossed triangles, crossings[i] their number. A face whose normal points along +w adds
+ *               +1: a closed mesh turned outward gives +1 inside and 0 outside.
+ * Outputs, each optional (NULL) except counts: winding (n_pts) int32, crossings (n_pts) int32, on_surface (n_pts) uint8; counts[8] =
+ * triangles with s != 0, triangles with s = 0 but n != 0, triangles with n = 0, points with winding != 0, (point, triangle) entries looked at
+ * (this one belongs to the broad phase and is no part of the contract), points on the surface, 0, 0. n_pts = 0 is legal: the mesh is checked and
+ * counted. n_faces = 0: all zeros.
+ * SN_ERR_ARG, nothing written but counts (zeros), in sn_mesh_smooth's words: a face index outside [0, n_verts) or a referenced coordinate
+ * outside the range (or not a number), the text naming the first offending face, an index before a coordinate; then the first point with a
+ * coordinate outside the range (or not a number); nv not 3 or 4, n_verts or n_faces > 2^28, n_pts > 2^29, axis outside 0 .. 2, a null cfg,
+ * more than 2^26 triangles. Limits: the winding number of an open or inconsistently turned mesh depends on the axis (on_surface does not);
+ * there is no fractional winding number; a uniform 2-D grid, no hierarchy: a query looks at every triangle of its column's cell. The result
+ * equals the restatement tests/meshwinding_ref.py byte for byte (but counts[4]), on every run. The workspace belongs to the context (grown on
+ * demand); both forms return when the work is done. */
+typedef struct sn_mesh_winding_cfg {
+    int axis;                  /* 0, 1 or 2: the ray runs along +axis */
+    int reserved;              /* 0 */
+} sn_mesh_winding_cfg;
+SN_API int sn_mesh_winding(sn_ctx *ctx, const sn_mesh_winding_cfg *cfg, int n_verts, const double *verts, int n_faces, int nv,
+                           const int32_t *faces, long long n_pts, const double *pts, int32_t *winding, int32_t *crossings,
+                           unsigned char *on_surface, long long *counts);
+SN_API int sn_mesh_winding_dev(sn_ctx *ctx, const sn_mesh_winding_cfg *cfg, int n_verts, const double *verts_dev, int n_faces, int nv,
+                               const int32_t *faces_dev, long long n_pts, const double *pts_dev, int32_t *winding_dev, int32_t *crossings_dev,
+                               unsigned char *on_surface_dev, long long *counts);
 
 /* ---- the mesh back in its views: depth maps, face ids, visibility, colours --------------------------------------------
  * sn_mesh_render rasterises a mesh into V views of one size: verts (n_verts,3) float64 in WORLD coordinates (as sn_mesh_sample's), faces

@@ -776,6 +776,29 @@ class Context(object):
             out["closest"] = out["closest"].reshape(n, 3)
         return out
 
+    WINDING_OUTPUTS = ("winding", "crossings", "on_surface")
+
+    def mesh_winding(self, verts, faces, pts, axis=2, outputs=WINDING_OUTPUTS, device=False):
+        """For every point how many times a mesh winds around it, exactly (sn_mesh_winding): verts (V,3) float64 in
+        lattice cells, faces (F,3) or (F,4) int32, pts (n,3) float64 in lattice cells, axis 0, 1 or 2 the axis the rays run along. Returns a
+        dict of those of `outputs` that were asked for - winding (n,) int32 the signed crossings, crossings (n,) int32 their number,
+        on_surface (n,) uint8 - and counts (8,) int64 = triangles that can be crossed, triangles parallel to the rays, degenerate triangles,
+        points with winding != 0, (point, triangle) entries looked at (the broad phase's own number), points on the surface, 0, 0. device=True stages
+        the mesh and the points in device memory here and runs sn_mesh_winding_dev on them: the same result."""
+        v, f = self._mesh_arrays(verts, faces)
+        p = self._points(pts)
+        V, (F, nv), n = v.shape[0], f.shape, p.shape[0]
+        if set(outputs) - set(self.WINDING_OUTPUTS):
+            raise ValueError("outputs = %r: of %r" % (outputs, self.WINDING_OUTPUTS))
+        cfg = _lib.MeshWindingCfg(int(axis), 0)
+        widths = dict(winding=(1, np.int32), crossings=(1, np.int32), on_surface=(1, np.uint8))
+        spec = tuple((name,) + widths[name] for name in self.WINDING_OUTPUTS if name in outputs)
+
+        def run(fn, _, ins, outs, counts):
+            given = dict(zip([name for name, _, _ in spec], outs))
+            return fn(self._h, ctypes.byref(cfg), V, ins[0], F, nv, ins[1], n, ins[2], *[given.get(name) for name in self.WINDING_OUTPUTS], *counts)
+        return self._host_or_device("sn_mesh_winding", device, (v, f, p), run, spec, lambda name, sizes: n, (), words=8)
+
     def _render_args(self, verts, faces, cameraPOs, shape, near, tol):
         """-> (verts, faces, P or None, V, cfg) of mesh_render and mesh_vertex_colors: cameraPOs (V,3,4), None = the cameras of set_cameras."""
         v, f = self._mesh_arrays(verts, faces)

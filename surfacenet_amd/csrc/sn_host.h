@@ -255,6 +255,20 @@ static inline int mdi_check_args(const sn_mesh_distance_cfg *cfg, int n_verts, i
     return SN_OK;
 }
 
+// (sn_mesh_winding has no lattice of its own: lattice cells, every output has n_pts rows. Its grid's tables are the intersection stage's in
+// size: at most 2^26 triangles)
+static inline int wnd_check_args(const sn_mesh_winding_cfg *cfg, int n_verts, int n_faces, int nv, long long n_pts)
+{
+    int rc;
+    if (!cfg) return fail(SN_ERR_ARG, "null cfg");
+    const double origin[3] = {0.0, 0.0, 0.0};
+    if ((rc = mesh_check_common(n_verts, n_faces, nv, origin, 1.0)) != SN_OK) return rc;
+    if (n_pts < 0 || n_pts > (1ll << 29)) return fail(SN_ERR_ARG, "n_pts = %lld: 0 .. 2^29", n_pts);
+    if (cfg->axis < 0 || cfg->axis > 2) return fail(SN_ERR_ARG, "axis = %d: 0 (x), 1 (y) or 2 (z)", cfg->axis);
+    if ((long long)n_faces * (nv - 2) > (1ll << 26)) return fail(SN_ERR_ARG, "%lld triangles: at most 2^26", (long long)n_faces * (nv - 2));
+    return SN_OK;
+}
+
 // (sn_mesh_render and sn_mesh_vertex_colors have no lattice: world coordinates, one image size, V views; have_P: the caller gave cameras, so
 // V is the caller's - without them V is the context's and is judged there)
 static inline int mrd_check_args(const sn_mesh_render_cfg *cfg, int n_verts, int n_faces, int nv, bool have_P, int V)

@@ -9,6 +9,8 @@
     mesh_normals       the normals of a mesh from the mesh itself, area-weighted, with its exact area and volume
     orient_mesh        the faces of a mesh made to turn one way, its pieces with their exact volumes, small pieces removed
     self_intersections the pairs of faces of a mesh that cross or touch each other, exactly
+    winding_number     inside, outside or on the surface: how many times the mesh winds around a point, exactly
+    signed_distance    point_to_mesh's distance with winding_number's sign
     render_mesh        the mesh back in its views: depth maps, face ids, the pixels of every face, the visible vertices
     colour_vertices    the colour of every vertex from the views that see it
     chain_settings     the checked keywords of the stages that follow extract_mesh in a scene: fill, smooth, decimate, orient, check (DESIGN.md
@@ -548,6 +550,90 @@ def mesh_deviation(vertices_a, faces_a, vertices_b, faces_b, dst, max_dist=60.0)
         res[key] = _deviation(r["dist"], r["n_beyond"])
     res["hausdorff"] = max(res["a_to_b"]["max"], res["b_to_a"]["max"])
     return res
+
+
+WINDING_COUNTS = ("n_triangles", "n_parallel", "n_degenerate", "n_inside", "n_on_surface")
+_WINDING_WORDS = (0, 1, 2, 3, 5)                                # their places in the library's counts (4: the broad phase's tests)
+AXES = {"x": 0, "y": 1, "z": 2}
+
+
+def check_winding_args(points, axis=2):
+    """-> (points (n,3) float64, axis 0..2) of winding_number, or ValueError: points float32 or float64 (n,3) in lattice cells, at most 2^29
+    of them, every coordinate in [-4, 2^21 - 8) - the first that is not is named, as the library names it -, axis 0, 1, 2 or "x", "y", "z"."""
+    p = np.asarray(points)
+    if p.dtype not in (np.float32, np.float64):
+        raise ValueError("points_lattice must be float32 or float64, not %s" % p.dtype)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError("points_lattice must be (n,3), not %r" % (p.shape,))
+    if p.shape[0] > MAX_QUERY_POINTS:
+        raise ValueError("%d points: at most 2^29" % p.shape[0])
+    if isinstance(axis, str):
+        if axis not in AXES:
+            raise ValueError("axis = %r: 0, 1, 2 or one of %s" % (axis, sorted(AXES)))
+        a = AXES[axis]
+    else:
+        try:
+            a = int(axis)
+        except (TypeError, ValueError):
+            raise ValueError("axis = %r: 0, 1, 2 or one of %s" % (axis, sorted(AXES)))
+        if isinstance(axis, (bool, np.bool_)) or a != axis or not 0 <= a <= 2:
+            raise ValueError("axis = %r: 0, 1, 2 or one of %s" % (axis, sorted(AXES)))
+    with np.errstate(invalid="ignore"):
+        bad = ~((p >= -4.0) & (p < 2097144.0)).all(axis=1)      # (NaN fails)
+    if bad.any():
+        raise ValueError("point %d: a coordinate is outside [-4, 2^21 - 8) lattice cells" % int(np.argmax(bad)))
+    return p.astype(np.float64), a
+
+
+def winding_number(points_lattice, vert_lattice, faces, axis=2):
+    """For every point how many times a mesh winds around it, exactly: points_lattice (n,3) float32 or float64 and
+    vert_lattice (V,3) in lattice cells as any stage returns them, faces (F,3) triangles or (F,4) quads - a quad is its triangles (a,b,c),
+    (a,c,d) -, axis the axis the rays run along. Positions are the stages' fixed point, q = rint(v * 65536), and every test is a sign of an
+    exact integer; a ray through a vertex or along an edge counts each crossing once (the renderer's fill rule). -> dict: winding (n,) int32
+    the signed crossings - a closed mesh turned outward (orient_mesh(sign="outward")) gives +1 inside and 0 outside -, crossings (n,) int32
+    their number, on_surface (n,) bool the point lies on a triangle (closed, the same for every axis), inside (n,) bool = winding != 0,
+    n_triangles (those a ray can cross), n_parallel (parallel to the rays), n_degenerate, n_inside, n_on_surface. On an open or
+    inconsistently turned mesh the winding number depends on the axis. ValueError on bad shapes, dtypes, axis, face indices or coordinates
+    before the library is touched."""
+    v, f = _mesh_arrays(vert_lattice, faces)
+    p, a = check_winding_args(points_lattice, axis)
+    _, _, V, F, _, _ = _mesh_args(v, f, (0.0, 0.0, 0.0), 1.0, None, "faces")
+    n, T = p.shape[0], F * (f.shape[1] - 2)
+    if T > MAX_DISTANCE_TRIANGLES:
+        raise ValueError("%d triangles: at most 2^26" % T)
+    if n == 0 or F == 0:                                        # no point, or no face: nothing for the library to do
+        m = dict(winding=np.zeros((n,), np.int32), crossings=np.zeros((n,), np.int32), on_surface=np.zeros((n,), np.uint8),
+                 counts=np.zeros((8,), np.int64))
+    else:
+        m = runtime.any_context().mesh_winding(v.astype(np.float64), f.astype(np.int32), p, axis=a)
+    res = dict(winding=m["winding"], crossings=m["crossings"], on_surface=m["on_surface"].astype(bool), inside=m["winding"] != 0)
+    res.update({k: int(m["counts"][i]) for k, i in zip(WINDING_COUNTS, _WINDING_WORDS)})
+    return res
+
+
+def signed_distance(points_lattice, vert_lattice, faces, max_dist=60.0, axis=2, resol=1.0):
+    """The signed distance of points to a closed mesh, host code over point_to_mesh - with the lattice positions
+    as its world - and winding_number: points_lattice (n,3) and vert_lattice (V,3) in lattice cells, max_dist in lattice cells, resol the
+    cell size the distances are scaled by. -> dict: dist (n,) float64 = point_to_mesh's capped distance * resol, negative where the point
+    is inside (winding != 0) and exactly 0.0 where it lies on the surface or its squared distance is 0; face (n,) int32, closest (n,3)
+    float64 (scaled by resol), winding (n,) int32, on_surface (n,) bool. The distance uses the float64 positions as given and the sign the
+    quantised ones: they can disagree only within 2^-17 cell of the surface. ValueError before the library is touched."""
+    try:
+        r = float(resol)
+    except (TypeError, ValueError):
+        raise ValueError("resol = %r must be a number" % (resol,))
+    if isinstance(resol, (bool, np.bool_)) or not (np.isfinite(r) and r > 0):
+        raise ValueError("resol = %r must be finite and > 0" % (resol,))
+    v, f = _mesh_arrays(vert_lattice, faces)
+    p, a = check_winding_args(points_lattice, axis)
+    check_distance_args(p, max_dist)
+    _mesh_args(v, f, (0.0, 0.0, 0.0), 1.0, None, "faces")
+    w = winding_number(p, v, f, axis=a)
+    d = point_to_mesh(p, v, f, max_dist=max_dist)
+    dist = d["dist"] * r
+    dist = np.where(w["inside"], -dist, dist)
+    dist[w["on_surface"] | (d["dist2"] == 0.0)] = 0.0
+    return dict(dist=dist, face=d["face"], closest=d["closest"] * r, winding=w["winding"], on_surface=w["on_surface"])
 
 
 RENDER_COUNTS = ("n_triangles", "n_clipped", "n_degenerate", "n_rasterised", "n_pairs", "n_pixels", "n_visible")
