@@ -39,7 +39,8 @@ extern "C" {
  * views: depth maps, face ids, visibility, vertex colours; sn_mesh_intersect, sn_mesh_intersect_dev and sn_mesh_intersect_cfg - the pairs of
  * faces of a mesh that cross or touch each other, exactly; sn_mesh_distance, sn_mesh_distance_dev and sn_mesh_distance_cfg - for every
  * point of a set the nearest point of a mesh: its squared distance, its face, the point itself; sn_mesh_winding, sn_mesh_winding_dev and
- * sn_mesh_winding_cfg - for every point of a set how many times a mesh winds around it, exactly: inside, outside or on the surface. */
+ * sn_mesh_winding_cfg - for every point of a set how many times a mesh winds around it, exactly: inside, outside or on the surface;
+ * sn_mesh_voxelize, sn_mesh_voxelize_dev and sn_mesh_voxelize_cfg - a mesh voxelised into cubes: exact solid and surface occupancy. */
 
 /* The library is built with -fvisibility=hidden: the functions below are its WHOLE dynamic symbol table
  * (tests/test_abi.py compares `nm -D` with this header). */
@@ -650,6 +651,44 @@ SN_API int sn_mesh_winding(sn_ctx *ctx, const sn_mesh_winding_cfg *cfg, int n_ve
 SN_API int sn_mesh_winding_dev(sn_ctx *ctx, const sn_mesh_winding_cfg *cfg, int n_verts, const double *verts_dev, int n_faces, int nv,
                                const int32_t *faces_dev, long long n_pts, const double *pts_dev, int32_t *winding_dev, int32_t *crossings_dev,
                                unsigned char *on_surface_dev, long long *counts);
+
+/* ---- a mesh back into cubes of voxels: exact solid and surface occupancy ------------------------------------------------
+ * sn_mesh_voxelize gives every voxel of n_cubes cubes of D^3 voxels two bits against a mesh. The mesh is sn_mesh_winding's: verts
+ * (n_verts,3) float64 in lattice cells, faces (n_faces,nv) int32, nv = 3 or 4 - a quad (a,b,c,d) is the triangles (a,b,c), (a,c,d) -,
+ * referenced coordinates in -4 <= v < 2^21 - 8, q = int64(rint(v * 65536)). cube_ijk (n_cubes,3) int32, stride_vox >= 1, D in 1 .. 64.
+ *   1 cells     voxel (n; i,j,k) is the world cell g = cube_ijk[n] * stride_vox + (i,j,k); its centre is the lattice point g, p = g * 65536
+ *               in the fixed point; its box is the closed [p - 32768, p + 32768]^3. Cubes may overlap: a shared cell gets the same bits.
+ *   2 solid     bit 0: the winding number of p is not zero under sn_mesh_winding's rules 1, 2, 4, 5 along cfg.axis, unchanged - the bit
+ *               equals (sn_mesh_winding(centres).winding != 0) byte for byte, on any mesh.
+ *   3 surface   bit 1: some triangle with n != 0 has a point in common with the voxel's closed box, decided by the separating-axis test
+ *               in exact integers on 13 axes - the 3 box axes, the triangle's normal, the 9 products of a box axis and an edge. They
+ *               are separated iff on some axis the triangle's interval lies strictly beyond the box's: touching is a hit. The bit does
+ *               not depend on cfg.axis. Degenerate triangles (n = 0) take no part in either bit; they are counted.
+ * cfg.modes says which bits are computed (bit 0 solid, bit 1 surface, 1 .. 3; the other bit is 0), cfg.select (1 .. 3) which make Y.
+ * Outputs, each optional (NULL) except counts: occ (n_cubes,D,D,D) uint8 in [n,i,j,k] order, the bits; Y (n_cubes,1,D,D,D) float32, 1.0
+ * iff occ & select, else 0.0 - the tensor sn_gt_cubes writes; per_cube (n_cubes,2) int64 solid, surface voxels; counts[8] = triangles
+ * with s != 0, triangles with s = 0 but n != 0, triangles with n = 0, solid voxels, surface voxels, voxels with both bits, (column,
+ * triangle) pairs covered, (voxel, triangle) box tests run - the last two belong to the broad phase and are no part of the contract.
+ * n_cubes = 0 is legal: the mesh is checked and counted. n_faces = 0: all zeros.
+ * SN_ERR_ARG, nothing written but counts (zeros), in sn_mesh_smooth's words: a face index outside [0, n_verts) or a referenced coordinate
+ * outside the range (or not a number), the text naming the first offending face; then the first cube with a negative ijk or whose last
+ * cell cube_ijk * stride_vox + D - 1 reaches 2^21 - 8; nv not 3 or 4, n_verts or n_faces > 2^28, more than 2^26 triangles, n_cubes < 0, D
+ * outside 1 .. 64, stride_vox < 1, axis outside 0 .. 2, modes or select outside 1 .. 3, n_cubes * D^3 > 2^33, a null cfg. Limits: no
+ * world-mm input, no signed-distance field, no hierarchy - a huge triangle over many cubes costs its box of columns in every cube it
+ * covers. The result equals the restatement tests/meshvoxel_ref.py byte for byte (but counts[6], counts[7]), on every run. The
+ * workspace belongs to the context (grown on demand); both forms return when the work is done. */
+typedef struct sn_mesh_voxelize_cfg {
+    int axis;                  /* 0, 1 or 2: the rays of the solid bit run along +axis */
+    int modes;                 /* bit 0 solid, bit 1 surface: 1 .. 3 */
+    int select;                /* 1 .. 3: the bits of occ that make Y */
+    int reserved;              /* 0 */
+} sn_mesh_voxelize_cfg;
+SN_API int sn_mesh_voxelize(sn_ctx *ctx, const sn_mesh_voxelize_cfg *cfg, int n_verts, const double *verts, int n_faces, int nv,
+                            const int32_t *faces, int n_cubes, const int32_t *cube_ijk, int D, int stride_vox, unsigned char *occ, float *Y,
+                            long long *per_cube, long long *counts);
+SN_API int sn_mesh_voxelize_dev(sn_ctx *ctx, const sn_mesh_voxelize_cfg *cfg, int n_verts, const double *verts_dev, int n_faces, int nv,
+                                const int32_t *faces_dev, int n_cubes, const int32_t *cube_ijk_dev, int D, int stride_vox,
+                                unsigned char *occ_dev, float *Y_dev, long long *per_cube_dev, long long *counts);
 
 /* ---- the mesh back in its views: depth maps, face ids, visibility, colours --------------------------------------------
  * sn_mesh_render rasterises a mesh into V views of one size: verts (n_verts,3) float64 in WORLD coordinates (as sn_mesh_sample's), faces

@@ -24,7 +24,7 @@ ABI_SYMBOLS = [
     "sn_components", "sn_components_dev",
     "sn_mesh", "sn_mesh_dev", "sn_mesh_sample", "sn_mesh_sample_dev", "sn_mesh_simplify", "sn_mesh_simplify_dev",
     "sn_mesh_smooth", "sn_mesh_smooth_dev", "sn_mesh_fill", "sn_mesh_fill_dev", "sn_mesh_normals", "sn_mesh_normals_dev",
-    "sn_mesh_orient", "sn_mesh_orient_dev", "sn_mesh_intersect", "sn_mesh_intersect_dev", "sn_mesh_distance", "sn_mesh_distance_dev", "sn_mesh_winding", "sn_mesh_winding_dev", "sn_mesh_render", "sn_mesh_render_dev", "sn_mesh_vertex_colors", "sn_mesh_vertex_colors_dev",
+    "sn_mesh_orient", "sn_mesh_orient_dev", "sn_mesh_intersect", "sn_mesh_intersect_dev", "sn_mesh_distance", "sn_mesh_distance_dev", "sn_mesh_winding", "sn_mesh_winding_dev", "sn_mesh_voxelize", "sn_mesh_voxelize_dev", "sn_mesh_render", "sn_mesh_render_dev", "sn_mesh_vertex_colors", "sn_mesh_vertex_colors_dev",
     "sn_point_reduce", "sn_nn_dist2", "sn_point_flags",
     "sn_ptcubes", "sn_ptcubes_dev", "sn_ptcubes_sparse_dev",
     "sn_gt_bind", "sn_gt_bind_dev", "sn_gt_cubes", "sn_gt_cubes_dev", "sn_weighted_accuracy", "sn_weighted_accuracy_dev",
@@ -92,6 +92,10 @@ class MeshDistanceCfg(ctypes.Structure):
 
 class MeshWindingCfg(ctypes.Structure):
     _fields_ = [("axis", ctypes.c_int), ("reserved", ctypes.c_int)]
+
+
+class MeshVoxelizeCfg(ctypes.Structure):
+    _fields_ = [("axis", ctypes.c_int), ("modes", ctypes.c_int), ("select", ctypes.c_int), ("reserved", ctypes.c_int)]
 
 
 class MeshRenderCfg(ctypes.Structure):
@@ -209,6 +213,10 @@ def load():
                             [P(ctypes.c_longlong)]),
         "sn_mesh_winding_dev": (c_int, [c_void_p, P(MeshWindingCfg), c_int, c_void_p, c_int, c_int, c_void_p, ctypes.c_longlong] + [c_void_p] * 4 +
                                 [P(ctypes.c_longlong)]),
+        "sn_mesh_voxelize": (c_int, [c_void_p, P(MeshVoxelizeCfg), c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int] + [c_void_p] * 3 +
+                             [P(ctypes.c_longlong)]),
+        "sn_mesh_voxelize_dev": (c_int, [c_void_p, P(MeshVoxelizeCfg), c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int] + [c_void_p] * 3 +
+                                 [P(ctypes.c_longlong)]),
         "sn_mesh_render": (c_int, [c_void_p, P(MeshRenderCfg), c_int, c_void_p, c_int, c_int, c_void_p, c_int] + [c_void_p] * 5 + [P(ctypes.c_longlong)]),
         "sn_mesh_render_dev": (c_int, [c_void_p, P(MeshRenderCfg), c_int, c_void_p, c_int, c_int, c_void_p, c_int] + [c_void_p] * 5 + [P(ctypes.c_longlong)]),
         "sn_mesh_vertex_colors": (c_int, [c_void_p, P(MeshRenderCfg), c_int, c_void_p, c_int, c_int, c_void_p, c_int] + [c_void_p] * 4 +

@@ -799,6 +799,38 @@ class Context(object):
             return fn(self._h, ctypes.byref(cfg), V, ins[0], F, nv, ins[1], n, ins[2], *[given.get(name) for name in self.WINDING_OUTPUTS], *counts)
         return self._host_or_device("sn_mesh_winding", device, (v, f, p), run, spec, lambda name, sizes: n, (), words=8)
 
+    VOXELIZE_OUTPUTS = ("occ", "Y", "per_cube")
+
+    def mesh_voxelize(self, verts, faces, cube_ijk, D, stride_vox, axis=2, modes=3, select=2, outputs=VOXELIZE_OUTPUTS, device=False):
+        """A mesh voxelised into cubes, exactly (sn_mesh_voxelize): verts (V,3) float64 in lattice cells, faces (F,3)
+        or (F,4) int32, cube_ijk (N,3) int32, D 1..64 the cube side in voxels, stride_vox >= 1 - voxel (n; i,j,k) is the world cell cube_ijk[n]
+        * stride_vox + (i,j,k), its centre that lattice point -, axis 0, 1 or 2 the axis the solid bit's rays run along, modes the bits that
+        are computed (1 solid, 2 surface, 3 both), select the bits that make Y. Returns a dict of those of `outputs` that were asked for -
+        occ (N,D,D,D) uint8 the bits, Y (N,1,D,D,D) float32, per_cube (N,2) int64 solid and surface voxels - and counts (8,) int64 =
+        triangles that can be crossed, triangles parallel to the rays, degenerate triangles, solid voxels, surface voxels, voxels with both
+        bits, (column, triangle) pairs covered, (voxel, triangle) box tests run (the last two are the broad phase's own numbers).
+        device=True stages the mesh and the cubes in device memory here and runs sn_mesh_voxelize_dev on them: the same result."""
+        v, f = self._mesh_arrays(verts, faces)
+        cube = np.ascontiguousarray(cube_ijk, dtype=np.int32).reshape(-1, 3)
+        V, (F, nv), N, D = v.shape[0], f.shape, cube.shape[0], int(D)
+        if set(outputs) - set(self.VOXELIZE_OUTPUTS):
+            raise ValueError("outputs = %r: of %r" % (outputs, self.VOXELIZE_OUTPUTS))
+        cfg = _lib.MeshVoxelizeCfg(int(axis), int(modes), int(select), 0)
+        vox = N * D ** 3 if 1 <= D <= 64 else 0                 # (a refused D writes nothing)
+        widths = dict(occ=(1, np.uint8), Y=(1, np.float32), per_cube=(2, np.int64))
+        spec = tuple((name,) + widths[name] for name in self.VOXELIZE_OUTPUTS if name in outputs)
+
+        def run(fn, _, ins, outs, counts):
+            given = dict(zip([name for name, _, _ in spec], outs))
+            return fn(self._h, ctypes.byref(cfg), V, ins[0], F, nv, ins[1], N, ins[2], D, int(stride_vox),
+                      *[given.get(name) for name in self.VOXELIZE_OUTPUTS], *counts)
+        out = self._host_or_device("sn_mesh_voxelize", device, (v, f, cube), run, spec, lambda name, sizes: N if name == "per_cube" else vox, (), words=8)
+        if "occ" in out:
+            out["occ"] = out["occ"].reshape(N, D, D, D)
+        if "Y" in out:
+            out["Y"] = out["Y"].reshape(N, 1, D, D, D)
+        return out
+
     def _render_args(self, verts, faces, cameraPOs, shape, near, tol):
         """-> (verts, faces, P or None, V, cfg) of mesh_render and mesh_vertex_colors: cameraPOs (V,3,4), None = the cameras of set_cameras."""
         v, f = self._mesh_arrays(verts, faces)

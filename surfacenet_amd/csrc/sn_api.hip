@@ -296,12 +296,17 @@ static int ensure_workspace(sn_ctx *c)
     int rc;
     for (int t = T_X0; t <= T_MA; ++t) {      // one buffer per tensor of the plan's table: [samples][extent^3][channel stride] per plane
         _Float16 *&p = c->*kTensors[t].buf;
-        if ((rc = dev_alloc(c, &p, S * (v1 >> (3 * kTensors[t].level)) * kTensors[t].ch * npl)) != SN_OK) return rc;
+        const size_t count = S * (v1 >> (3 * kTensors[t].level)) * kTensors[t].ch * npl;
+        if ((rc = dev_alloc(c, &p, count)) != SN_OK) return rc;
         c->ws_owned.push_back(p);
+        // The bytes no kernel writes - the padding channels of a channel stride - are zero, not what an earlier owner of the memory left:
+        // two contexts that ran the same calls hold the same bytes, whatever the process allocated and freed before them.
+        HIPCHK(dev_fill(c, p, 0, count));
     }
     if (c->split == 1) {      // default mode: the fp8 code plane of conv3_3's output (read by conv4_1; side_op3 reads the hi / lo planes)
         if ((rc = dev_alloc(c, &c->a3c, (size_t)(S * v3 * 160))) != SN_OK) return rc;
         c->ws_owned.push_back(c->a3c);
+        HIPCHK(dev_fill(c, c->a3c, 0, (size_t)(S * v3 * 160)));
     }
     c->ws_ready = true; c->ws_split = c->split;
     return SN_OK;

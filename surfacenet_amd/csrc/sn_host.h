@@ -269,6 +269,24 @@ static inline int wnd_check_args(const sn_mesh_winding_cfg *cfg, int n_verts, in
     return SN_OK;
 }
 
+// (sn_mesh_voxelize: the winding stage's mesh and limits, then the cubes - the device form's arrays hold n_cubes * D^3 voxels, at most 2^33)
+static inline int vox_check_args(const sn_mesh_voxelize_cfg *cfg, int n_verts, int n_faces, int nv, int n_cubes, int D, int stride_vox)
+{
+    int rc;
+    if (!cfg) return fail(SN_ERR_ARG, "null cfg");
+    const double origin[3] = {0.0, 0.0, 0.0};
+    if ((rc = mesh_check_common(n_verts, n_faces, nv, origin, 1.0)) != SN_OK) return rc;
+    if (n_cubes < 0) return fail(SN_ERR_ARG, "n_cubes = %d must be >= 0", n_cubes);
+    if (D < 1 || D > 64) return fail(SN_ERR_ARG, "D = %d: 1 .. 64", D);
+    if (stride_vox < 1) return fail(SN_ERR_ARG, "stride_vox = %d must be >= 1", stride_vox);
+    if (cfg->axis < 0 || cfg->axis > 2) return fail(SN_ERR_ARG, "axis = %d: 0 (x), 1 (y) or 2 (z)", cfg->axis);
+    if (cfg->modes < 1 || cfg->modes > 3) return fail(SN_ERR_ARG, "modes = %d: 1 (solid), 2 (surface) or 3 (both)", cfg->modes);
+    if (cfg->select < 1 || cfg->select > 3) return fail(SN_ERR_ARG, "select = %d: 1 (solid), 2 (surface) or 3 (either)", cfg->select);
+    if ((long long)n_faces * (nv - 2) > (1ll << 26)) return fail(SN_ERR_ARG, "%lld triangles: at most 2^26", (long long)n_faces * (nv - 2));
+    if ((long long)n_cubes * D * D * D > (1ll << 33)) return fail(SN_ERR_ARG, "%lld voxels: at most 2^33", (long long)n_cubes * D * D * D);
+    return SN_OK;
+}
+
 // (sn_mesh_render and sn_mesh_vertex_colors have no lattice: world coordinates, one image size, V views; have_P: the caller gave cameras, so
 // V is the caller's - without them V is the context's and is judged there)
 static inline int mrd_check_args(const sn_mesh_render_cfg *cfg, int n_verts, int n_faces, int nv, bool have_P, int V)

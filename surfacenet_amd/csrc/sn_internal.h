@@ -194,6 +194,7 @@ struct sn_ctx {
     DevBuf mxi_ws, mxi_grid, mxi_keys;   // self-intersections (sn_meshintersect.hip): status, the edge table's build, boxes | the grid's table, runs and entries | the hits' keys
     long long mxi_kcap = 0;       // ... the longest key list a call on this context has needed
     DevBuf wnd_ws, wnd_grid;      // winding numbers (sn_meshwinding.hip): status, boxes, what the queries found | the grid's table, runs and entries
+    DevBuf vox_ws, vox_grid;      // mesh voxelisation (sn_meshvoxel.hip): status, boxes, the slabs' counts | the grid's table, runs and entries
     DevBuf mdi_ws, mdi_grid;      // point-to-mesh distance (sn_meshdistance.hip): status, boxes, the queries' best so far, the far list | the two grids' tables, runs and entries
     DevBuf mrd_ws;                // mesh renderer (sn_meshrender.hip): status, one view's projected vertices, triangle classes, big list, z-buffer, id words, a host form's staging
     // the ground-truth cloud sn_gt_bind sorted into its grid (sn_gtcubes.hip gt_layout places the arrays in gt_ws from gt_n alone)

@@ -4,6 +4,7 @@ of `SurfaceNet_fn_trainVal` (nets/SurfaceNet.py:253-264) compare the network aga
 * `bind_points(pts_xyz, cube_D_mm)`          binds a ground-truth cloud (a DTU `stlXXX_total.ply`, the output of a finer pass ...)
 * `gt_cubes(cubes, cube_D)`                  the target tensor `Y` (n,1,s,s,s) float32 of a batch of cubes: the occupancy of the bound cloud
 * `gt_cubes_from_points(pts, cubes, cube_D)` both in one call
+* `gt_cubes_from_mesh(vert_lattice, faces, cube_ijk, cube_D, stride_vox)` the same tensor from a mesh in lattice cells
 * `weighted_accuracy(pred, Y)`               `__weighted_accuracy__` (nets/SurfaceNet.py:203-224) of a batch
 * `accuracy_from_counts(counts)`             the same from the (n,4) integer counts the GPU returns (host arithmetic, float64)
 
@@ -75,6 +76,24 @@ def gt_cubes_from_points(pts, cubes, cube_D):
     bound = BoundCloud(ctx, p, side)
     _cloud = (p, side, {id(ctx): bound})
     return ctx.gt_cubes((xyz, resol))
+
+
+def gt_cubes_from_mesh(vert_lattice, faces, cube_ijk, cube_D, stride_vox, select="surface", axis=2):
+    """The target tensor Y (n,1,cube_D,cube_D,cube_D) float32 from a MESH in lattice cells (mesh.voxelize states the
+    voxels): 1.0 where a voxel has one of the selected bits - "surface": its closed box meets a triangle, "solid": its centre is inside,
+    "either" -, else 0.0. `weighted_accuracy(pred, Y)` takes it as it is. No cloud is bound or needed."""
+    from . import mesh
+    v, f = mesh._mesh_arrays(vert_lattice, faces)
+    if select is None:
+        raise ValueError("select = None: of %s" % sorted(mesh.VOXEL_SELECTS))
+    cube, D, stride, _, a, sel = mesh.check_voxelize_args(cube_ijk, cube_D, stride_vox, axis=axis, select=select)
+    mesh._mesh_args(v, f, (0.0, 0.0, 0.0), 1.0, None, "faces")
+    if f.shape[0] * (f.shape[1] - 2) > mesh.MAX_DISTANCE_TRIANGLES:
+        raise ValueError("%d triangles: at most 2^26" % (f.shape[0] * (f.shape[1] - 2)))
+    if cube.shape[0] == 0 or f.shape[0] == 0:
+        return np.zeros((cube.shape[0], 1, D, D, D), np.float32)
+    return runtime.any_context().mesh_voxelize(v.astype(np.float64), f.astype(np.int32), cube, D, stride, axis=a, modes=sel, select=sel,
+                                               outputs=("Y",))["Y"]
 
 
 def accuracy_from_counts(counts):

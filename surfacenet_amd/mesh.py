@@ -636,6 +636,100 @@ def signed_distance(points_lattice, vert_lattice, faces, max_dist=60.0, axis=2, 
     return dict(dist=dist, face=d["face"], closest=d["closest"] * r, winding=w["winding"], on_surface=w["on_surface"])
 
 
+VOXEL_MODES = {"solid": 1, "surface": 2}
+VOXEL_SELECTS = {"solid": 1, "surface": 2, "either": 3}
+VOXEL_COUNTS = ("n_triangles", "n_parallel", "n_degenerate", "n_solid_voxels", "n_surface_voxels", "n_both_voxels", "n_pairs", "n_tests")
+MAX_CUBE_D = 64
+MAX_VOXELS = 1 << 33
+
+
+def _voxel_bits(value, table, name):
+    """A name of `table`, or a sequence of them, as its bits."""
+    names = (value,) if isinstance(value, str) else value
+    try:
+        names = tuple(names)
+        if not names or not all(isinstance(n, str) and n in table for n in names):
+            raise TypeError
+    except TypeError:
+        raise ValueError("%s = %r: of %s" % (name, value, sorted(table)))
+    bits = 0
+    for n in names:
+        bits |= table[n]
+    return bits
+
+
+def check_voxelize_args(cube_ijk, cube_D, stride_vox, mode=("solid", "surface"), axis=2, select=None):
+    """-> (cube_ijk (N,3) int32, D, stride, modes bits, axis 0..2, select bits or None) of voxelize, or ValueError in the library's words:
+    cube_ijk integers (N,3), cube_D an integer in 1..64, stride_vox an integer >= 1, mode "solid", "surface" or both, axis as winding_number
+    takes it, select "solid", "surface" or "either"; at most 2^33 voxels; the first cube with a negative ijk, then the first whose last cell
+    cube_ijk * stride_vox + cube_D - 1 reaches 2^21 - 8."""
+    c = np.asarray(cube_ijk)
+    if c.dtype.kind not in "iu":
+        raise ValueError("cube_ijk must hold integers, not %s" % c.dtype)
+    if c.ndim != 2 or c.shape[1] != 3:
+        raise ValueError("cube_ijk must be (N,3), not %r" % (c.shape,))
+    for name, value in (("cube_D", cube_D), ("stride_vox", stride_vox)):
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+            raise ValueError("%s = %r must be an integer" % (name, value))
+    D, stride = int(cube_D), int(stride_vox)
+    if not 1 <= D <= MAX_CUBE_D:
+        raise ValueError("D = %d: 1 .. 64" % D)
+    if stride < 1 or stride >= 1 << 31:
+        raise ValueError("stride_vox = %d must be >= 1" % stride)
+    modes = _voxel_bits(mode, VOXEL_MODES, "mode")
+    sel = None if select is None else _voxel_bits(select, VOXEL_SELECTS, "select")
+    _, a = check_winding_args(np.zeros((0, 3)), axis)
+    if c.shape[0] * D ** 3 > MAX_VOXELS:
+        raise ValueError("%d voxels: at most 2^33" % (c.shape[0] * D ** 3))
+    c64 = c.astype(np.int64)
+    if c.shape[0] and (np.abs(c64) >= 1 << 31).any():
+        raise ValueError("cube_ijk must fit int32")
+    negative, reach = (c64 < 0).any(axis=1), (c64 * stride + D - 1 >= 2097144).any(axis=1)
+    bad = negative | reach
+    if bad.any():
+        n = int(np.argmax(bad))
+        raise ValueError("cube %d: a negative ijk" % n if negative[n] else "cube %d: its last cell reaches 2^21 - 8 lattice cells" % n)
+    return np.ascontiguousarray(c64.astype(np.int32)), D, stride, modes, a, sel
+
+
+def voxelize(vert_lattice, faces, cube_ijk, cube_D, stride_vox, mode=("solid", "surface"), axis=2):
+    """A mesh back into cubes of voxels, exactly: vert_lattice (V,3) in lattice cells as any stage returns them,
+    faces (F,3) triangles or (F,4) quads, cube_ijk (N,3), cube_D and stride_vox as extract_mesh takes them - voxel (n; i,j,k) is the world
+    cell cube_ijk[n] * stride_vox + (i,j,k) and its centre that lattice point -, mode "solid", "surface" or both, axis the axis the solid
+    bit's rays run along. solid: the winding number of the voxel's centre is not zero (winding_number's `inside`, byte for byte); surface:
+    the voxel's closed box meets a triangle (touching counts; the same for every axis). -> dict: occ (N,D,D,D) uint8 the bits (1 solid, 2
+    surface), solid and surface (N,D,D,D) bool, n_solid and n_surface (N,) int64 per cube, and the counts n_triangles, n_parallel,
+    n_degenerate, n_solid_voxels, n_surface_voxels, n_both_voxels, n_pairs, n_tests (the last two: the broad phase's cost). Cubes may
+    overlap; a shared cell has the same bits in each. ValueError on bad arguments before the library is touched."""
+    v, f = _mesh_arrays(vert_lattice, faces)
+    cube, D, stride, modes, a, _ = check_voxelize_args(cube_ijk, cube_D, stride_vox, mode, axis)
+    _, _, V, F, _, _ = _mesh_args(v, f, (0.0, 0.0, 0.0), 1.0, None, "faces")
+    if F * (f.shape[1] - 2) > MAX_DISTANCE_TRIANGLES:
+        raise ValueError("%d triangles: at most 2^26" % (F * (f.shape[1] - 2)))
+    N = cube.shape[0]
+    if N == 0 or F == 0:                                        # no cube, or no face: nothing for the library to do
+        m = dict(occ=np.zeros((N, D, D, D), np.uint8), per_cube=np.zeros((N, 2), np.int64), counts=np.zeros((8,), np.int64))
+    else:
+        m = runtime.any_context().mesh_voxelize(v.astype(np.float64), f.astype(np.int32), cube, D, stride, axis=a, modes=modes, select=modes,
+                                                outputs=("occ", "per_cube"))
+    res = dict(occ=m["occ"], solid=(m["occ"] & 1).view(bool), surface=((m["occ"] >> 1) & 1).view(bool), n_solid=m["per_cube"][:, 0].copy(),
+               n_surface=m["per_cube"][:, 1].copy())
+    res.update({k: int(x) for k, x in zip(VOXEL_COUNTS, m["counts"])})
+    return res
+
+
+def occupancy_lists(occ, select="surface"):
+    """voxelize's occ (N,D,D,D) uint8 as sparse cubes: (vxl_ijk_list, vxl_mask_list) - per cube the (n,3) uint8 ijk of its voxels with one
+    of the selected bits ("surface", "solid" or "either"), in [i,j,k] order, and an all-True mask -, the form extract_mesh,
+    normals.estimate_normals, the components pass, sparseCubes.unique_voxels and the PLY writers take."""
+    o = np.asarray(occ)
+    if o.dtype != np.uint8 or o.ndim != 4 or not o.shape[1] == o.shape[2] == o.shape[3]:
+        raise ValueError("occ must be uint8 (N,D,D,D), not %s %r" % (o.dtype, o.shape))
+    bits = _voxel_bits(select, VOXEL_SELECTS, "select")
+    ijk_list = [np.argwhere(cube & bits).astype(np.uint8).reshape(-1, 3) for cube in o]
+    return ijk_list, [np.ones((len(a),), bool) for a in ijk_list]
+
+
 RENDER_COUNTS = ("n_triangles", "n_clipped", "n_degenerate", "n_rasterised", "n_pairs", "n_pixels", "n_visible")
 MAX_IMAGE_DIM = 16384
 
