@@ -181,7 +181,9 @@ SN_API int sn_forward_dev(sn_ctx *ctx, int n, int n_vp, const float *X_dev, cons
  * pixel / depth bin falls outside the int32 range (a cube on the camera plane; the reference has no such limit). */
 SN_API int sn_ray_pool(sn_ctx *ctx, int n, int n_vp, const int64_t *view_pairs, const float *xyz, const float *resol,
                 const float *pred, int use_thresh, float min_prob, unsigned char *votes);
-/* Device-resident, asynchronous; the range error is reported by the next sn_synchronize. */
+/* Device-resident, asynchronous; the range error is reported by the next sn_synchronize. votes_dev (and votes_ws_dev of
+ * sn_dense2sparse_dev) must be 4-byte aligned: the votes are added a 32-bit word at a time (s^3 is a multiple of 4, so
+ * every cube's votes then start on a word). pred_dev may have any float alignment; 16-byte aligned cubes are read faster. */
 SN_API int sn_ray_pool_dev(sn_ctx *ctx, int n, int n_vp, const int64_t *view_pairs_dev, const float *xyz_dev,
                     const float *resol_dev, const float *pred_dev, int use_thresh, float min_prob,
                     unsigned char *votes_dev);

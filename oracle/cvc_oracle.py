@@ -100,6 +100,12 @@ def gen_non0Batch_npBool(boolIndicators, batch_size):
 def color_fuse(viewPair_coloredCubes, viewPair_surf_predictions, weight4viewPair):
     """utils/utils.py:8-42 generate_voxelLevelWeighted_coloredCubes restated op by op in float32:
     vw = w*pred; vw /= sum_p vw; mc = mean over the pair's two views; rgb = uint8(sum_p vw*mc)."""
+    with np.errstate(invalid="ignore"):
+        return np.nan_to_num(color_fuse_float(viewPair_coloredCubes, viewPair_surf_predictions, weight4viewPair), nan=0.0).astype(np.uint8)
+
+
+def color_fuse_float(viewPair_coloredCubes, viewPair_surf_predictions, weight4viewPair):
+    """color_fuse before the NaN -> 0 and the uint8 cast: the float32 sums (n, 3, D, D, D)."""
     pred = np.asarray(viewPair_surf_predictions, dtype=np.float32)
     n, P, D = pred.shape[:3]
     w = np.asarray(weight4viewPair, dtype=np.float32)
@@ -115,4 +121,4 @@ def color_fuse(viewPair_coloredCubes, viewPair_surf_predictions, weight4viewPair
         for p in range(P):
             mc = (X[:, p, 0] + X[:, p, 1]) / np.float32(2)
             out = out + (vw[:, p] / tot)[:, None] * mc
-        return np.nan_to_num(out, nan=0.0).astype(np.uint8)
+    return out

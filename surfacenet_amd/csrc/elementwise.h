@@ -258,6 +258,7 @@ static __global__ void __launch_bounds__(256) mx_scan_kernel(const _Float16 *t, 
 }
 
 // unfused [n][n_vp][s3] f32, w [n][n_vp] -> fused [n][s3]; w == nullptr (n_vp == 1) copies.
+// fp32 in this order (no contraction; tests/hotloop_cases.py restates it): wsum = ((0 + w_0) + w_1) + ..., then ((0 + u_0 * (w_0 / wsum)) + u_1 * (w_1 / wsum)) + ...
 static __global__ void __launch_bounds__(256) fuse_kernel(const float *unfused, const float *w, float *fused, int n_vp, int s3, long long total)
 {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;

@@ -64,6 +64,7 @@ __device__ __forceinline__ auto rp_ld(P p) { return __hip_atomic_load(p, __ATOMI
 template <typename P, typename T>
 __device__ __forceinline__ void rp_max(P p, T v) { (void)__hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
+// (`votes` is 4-byte aligned - the caller's contract, include/surfacenet_hip.h: the byte of voxel i is added to inside its 32-bit word)
 __device__ __forceinline__ void rp_vote(uint8_t *votes, unsigned i, unsigned mult)
 {
     atomicAdd(reinterpret_cast<unsigned *>(votes) + (i >> 2), mult << (8 * (i & 3)));
